@@ -28,9 +28,8 @@ if ROOT not in sys.path:
 
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 os.environ.setdefault("FID_PROFILE", "1")  # per-stage hipEvents on the context stream
-# GPU_MAX_HW_QUEUES is NOT set here (rounds 1 - 3 defaulted it to 24): the line is measured with the HIP runtime's own default
-# number of hardware queues, which is what a ROS node that links the library gets.  extra.hw_queues_24 re-runs the headline and
-# the cfg 5 side result in child processes with GPU_MAX_HW_QUEUES=24 (the variable is read when the runtime starts).
+# The number of hardware queues is NOT set here: the line is measured with the HIP runtime's own default, which is what a ROS
+# node that links the library gets.
 
 import numpy as np  # noqa: E402
 
@@ -40,6 +39,11 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 # FID_BENCH_DRYRUN=cpu: the launcher / rank plumbing only (gloo, no GPU, no detector, a sleeping stand-in for the step), so that
 # the N-rank path of this very file is covered by the CPU test suite.  The line it prints carries "dryrun": true and no metric.
 DRYRUN = os.environ.get("FID_BENCH_DRYRUN", "") == "cpu"
+if DRYRUN:
+    # no process of the dry run (launcher, torch.distributed.run, ranks) may open the GPU: torch is shown no device, and asked
+    # through its device count instead of the HIP runtime (which opens the GPU to count them) -- torchrun and gloo both ask
+    os.environ["HIP_VISIBLE_DEVICES"] = ""
+    os.environ["PYTORCH_NVML_BASED_CUDA_CHECK"] = "1"
 # FID_BENCH_OVERSUBSCRIBE=1: every rank maps to cuda:0 (the development lease is ONE GPU) and the clock reduction runs on gloo
 # (RCCL refuses two ranks on one device).  It exists so that the N-rank path -- N processes, each with torch's HIP runtime AND
 # libfid_amd.so and real kernels -- is executed by the GPU test suite; the line it prints says "oversubscribed" and n_gpus 1.
@@ -898,9 +902,11 @@ def main_stag(args):
     pool = fstag.StagPool(hd, ec, n_contexts=T, max_width=W, max_height=H, device=local_rank)
     K = synth.K_DEFAULT
     batch = np.stack([frames[i % len(frames)] for i in range(B)])
+    last = []  # the markers and poses the latest step returned
 
     def step():
-        m, _ = pool.detect_markers_batch(batch, K, None, 0.18)
+        m, p = pool.detect_markers_batch(batch, K, None, 0.18)
+        last[:] = [m, p]
         return sum(len(x) for x in m)
 
     def barrier():
@@ -919,6 +925,11 @@ def main_stag(args):
     dt_local = time.perf_counter() - t0
     barrier()
     fps, dt = job_throughput(B * args.steps, n_gpus, time.perf_counter() - t0, dist, f"cuda:{local_rank}")
+    if args.dump_outputs and rank == 0:
+        m, p = last
+        seeds = shard_seeds(rank, world, min(B, STAG_UNIQUE), "stag")
+        dump_outputs(args.dump_outputs, [seeds[i % len(seeds)] for i in range(B)], [len(x) for x in m],
+                     [{"marker": m[f], "pose": p[f]} for f in range(B)])
     ranks = gather_ranks(dist, rank, f"cuda:{local_rank}", B * args.steps, dt_local)
     assert len(ranks) == n_gpus
     if rank == 0:
@@ -1031,6 +1042,58 @@ def gather_ranks(dist, rank, device, units, dt_local, markers=None, extra=None):
     return got
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def aruco_last_outputs(det):
+    """What the last batch `det` collected returned to its caller, read from the context's result buffers (the timed steps
+    collect with unpack=False): (markers found per frame, one {"marker": fid_marker records, "pose": fid_pose_out records} per
+    frame)."""
+    mm = det.max_markers
+    counts = [int(det._n[f]) for f in range(det._last_frames)]  # (-1: the frame on which the reference's detectMarkers throws)
+    per_frame = [{"marker": det._out_np[f * mm:f * mm + max(n, 0)], "pose": det._poses_np[f * mm:f * mm + max(n, 0)]}
+                 for f, n in enumerate(counts)]
+    return counts, per_frame
+
+
+def dump_outputs(dirname, seeds, counts, per_frame):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy, float32 where the library returns float32, else float64.
+    seeds: the seed every frame of the step was made from; counts: markers per frame; per_frame: one {name: structured array}
+    per frame.  Every field becomes <name>_<field>, the frames concatenated (marker_frame: the frame of each row).  When the
+    whole would exceed DUMP_MAX_BYTES, a fixed seeded sample of the frames is written (sampled_frames: which)."""
+
+    def arrays(frames):
+        out = {"frame_seed": np.asarray([seeds[f] for f in frames], np.float64),
+               "markers_per_frame": np.asarray([counts[f] for f in frames], np.float64),
+               "marker_frame": np.concatenate([np.full(max(counts[f], 0), f, np.float64) for f in frames])}
+        for name in per_frame[0]:
+            recs = np.concatenate([per_frame[f][name] for f in frames])
+            for field in recs.dtype.names:
+                if field == "reserved":
+                    continue
+                v = recs[field]
+                if v.dtype.kind in "iu" and v.dtype.itemsize == 8:  # (64-bit words: two exact halves)
+                    out[f"{name}_{field}_hi32"] = (v.astype(np.uint64) >> np.uint64(32)).astype(np.float64)
+                    out[f"{name}_{field}_lo32"] = (v.astype(np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.float64)
+                else:
+                    out[f"{name}_{field}"] = v.astype(np.float32 if v.dtype == np.float32 else np.float64)
+        return out
+
+    def size(out):
+        return sum(a.nbytes + 256 for a in out.values())  # (+ the .npy header)
+
+    frames = list(range(len(counts)))
+    out = arrays(frames)
+    while size(out) > DUMP_MAX_BYTES and len(frames) > 1:
+        keep = max(1, int(len(frames) * DUMP_MAX_BYTES / size(out) * 0.9))
+        frames = sorted(np.random.default_rng(0).choice(len(counts), keep, replace=False).tolist())
+        out = arrays(frames)
+        out["sampled_frames"] = np.asarray(frames, np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def main_dryrun(args):
     rank, local_rank, world = rank_env(args)
     pin = pin_rank(local_rank, world)  # (before anything allocates or starts threads)
@@ -1041,7 +1104,7 @@ def main_dryrun(args):
 
     def barrier():
         if dist is not None:
-            dist.barrier()
+            dist.monitored_barrier()  # (gloo's own: dist.barrier() asks torch for the machine's accelerator, which opens the GPU)
 
     barrier()
     t0 = time.perf_counter()
@@ -1076,7 +1139,7 @@ def main_dryrun(args):
         dist.destroy_process_group()
 
 
-def main_feed_jpeg(args, rank, local_rank, world, dist, host, pin, budget):
+def main_feed_jpeg(args, rank, local_rank, world, dist, host, seeds, pin, budget):
     """--feed jpeg: a step = one batch of JPEG files in host memory -> markers + poses on the host (JpegStream).  The third way a
     camera node can feed a GPU (resident / raw over PCIe / compressed); never the headline."""
     import torch
@@ -1101,6 +1164,8 @@ def main_feed_jpeg(args, rank, local_rank, world, dist, host, pin, budget):
     dt_local = time.perf_counter() - t0
     barrier()
     fps, dt = job_throughput(B * args.steps, world, time.perf_counter() - t0, dist, f"cuda:{local_rank}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, seeds, *aruco_last_outputs(st.dets[(args.steps - 1) % 2]))
     ranks = gather_ranks(dist, rank, f"cuda:{local_rank}", B * args.steps, dt_local, found, extra={"pin": pin})
     if rank == 0:
         print(json.dumps({
@@ -1142,6 +1207,9 @@ def main():
     ap.add_argument("--streams", type=int, default=128, help="stag workload: frame slots per GPU (groups of 16 in lockstep)")
     ap.add_argument("--workload", choices=["aruco", "stag"], default="aruco",
                     help="aruco = the BASELINE.json metric (default); stag = BASELINE cfg 5, the stag_detect path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: markers and poses of every frame, the seed "
+                         "each frame was made from) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -1201,7 +1269,7 @@ def main():
     # --feed host: a capture ring of two pinned batches per rank (a step's frames must stay put until its results are collected)
     h_ring = [torch.from_numpy(host).pin_memory().numpy(), torch.from_numpy(host.copy()).pin_memory().numpy()] if feed_host else None
     if feed_jpeg:
-        return main_feed_jpeg(args, rank, local_rank, world, dist, host, pin, budget)
+        return main_feed_jpeg(args, rank, local_rank, world, dist, host, [seeds[i % unique] for i in range(B)], pin, budget)
     # The steps go through `depth` contexts in turn (fiducials_amd/pipeline.py: fid_submit_device / fid_collect): step k + 1 is
     # enqueued before step k's results are fetched, so the latency-bound end of one batch runs under the front of the next.
     # Every step is a whole pass (gray .. pose, results on the host) over its own 256 frames; all K are finished inside the
@@ -1251,6 +1319,8 @@ def main():
     assert counted[1] == args.steps  # every step's results were fetched inside the timed region
     barrier()
     fps, dt = job_throughput(B * args.steps, n_gpus, time.perf_counter() - t0, dist, f"cuda:{local_rank}")
+    if args.dump_outputs and rank == 0:  # (before any other call reuses the context that collected the last step)
+        dump_outputs(args.dump_outputs, [seeds[i % unique] for i in range(B)], *aruco_last_outputs(pipe.detectors[pipe.last_collected]))
     # BASELINE cfg 4 is eight CAMERA streams: frames arrive in host memory, and on an 8-GPU node the honest per-GPU row is the
     # host-fed one (one PCIe link per GPU, the host's memory system shared by all ranks).  So a multi-GPU run measures it too, every
     # rank at the same time, OUTSIDE the timed region of `value`: the same batch from a pinned ring of two (fid_submit_batch), a few
@@ -1380,30 +1450,6 @@ def main():
                 out["extra"]["cfg5_stag"] = json.loads(lines[-1])
             except Exception as e:  # noqa: BLE001
                 out["extra"]["cfg5_stag"] = {"error": repr(e)}
-            if "GPU_MAX_HW_QUEUES" not in os.environ:
-                # the same two numbers with GPU_MAX_HW_QUEUES=24 (what rounds 1 - 3 set for themselves): child processes, because
-                # the runtime reads the variable when it starts
-                hq = {"GPU_MAX_HW_QUEUES": "24"}
-                try:
-                    env = dict(os.environ, LOCAL_RANK=str(local_rank), GPU_MAX_HW_QUEUES="24")
-                    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "10", "--warmup", "3", "--batch", str(B),
-                           "--unique", str(unique), "--no-extras", "--no-cpu-baseline"]
-                    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-                    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-                    if p.returncode != 0 or not lines:
-                        raise RuntimeError(f"rc {p.returncode}: {p.stderr[-300:]}")
-                    doc = json.loads(lines[-1])
-                    hq["cfg3"] = {"value": doc["value"], "unit": "frames/s", "ms_per_step": doc["ms_per_step"], "steps": doc["steps"]}
-                    cmd = [sys.executable, os.path.abspath(__file__), "--stag-side-child", "--gpus", "1", "--no-cpu-baseline"]
-                    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
-                    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-                    if p.returncode != 0 or not lines:
-                        raise RuntimeError(f"stag rc {p.returncode}: {p.stderr[-300:]}")
-                    doc = json.loads(lines[-1])
-                    hq["cfg5_stag"] = {"value": doc["value"], "unit": "frames/s", "ms_single_frame": doc.get("ms_single_frame")}
-                except Exception as e:  # noqa: BLE001
-                    hq["error"] = repr(e)
-                out["extra"]["hw_queues_24"] = hq
         if n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(frames_u, K, D)
         print(json.dumps(out))

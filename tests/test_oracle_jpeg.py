@@ -1,19 +1,18 @@
 """The JPEG oracle (oracle/jpeg_oracle.c: baseline decode as cv::imdecode / libjpeg-turbo does it in front of the node when
 image_transport runs compressed, aruco_detect.launch:6) against libjpeg-turbo's own output: the committed fixtures
 (tests/golden/jpeg_cases.npz, made by tools/make_jpeg_golden.py with Pillow), libjpeg-turbo itself where Pillow is importable,
-and the reference's own JPEG files where /root/reference is mounted."""
+and the reference's own JPEG files (copies under tests/golden/)."""
 import hashlib
 import io
 import os
-import struct
 
 import numpy as np
 import pytest
 
 from oracle import jpeg as oj
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "jpeg_cases.npz")
-REF = "/root/reference/"
+GOLD_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLD = os.path.join(GOLD_DIR, "jpeg_cases.npz")
 
 
 @pytest.fixture(scope="module")
@@ -74,28 +73,14 @@ def test_against_libjpeg_turbo_directly():
     assert n == 54
 
 
-def _bag_jpeg(path):
-    bag = open(path, "rb").read()
-    pos = 0
-    while True:
-        i = bag.find(b"\xff\xd8\xff", pos)
-        if i < 0:
-            return None
-        n = struct.unpack("<I", bag[i - 4:i])[0]
-        if 1000 < n < 5_000_000 and bag[i + n - 2:i + n] == b"\xff\xd9":
-            return bag[i:i + n]
-        pos = i + 3
-
-
-@pytest.mark.skipif(not os.path.exists(REF + "fiducial_slam/test/test_images/403.jpg"), reason="needs /root/reference")
 def test_the_references_own_jpeg_files(gold):
-    """fiducial_slam/test/test_images/403.jpg (auto_init_403_test) and the CompressedImage frame of aruco_images.bag: the
-    oracle's decode has the SHA-256 libjpeg-turbo's decode had when the fixtures were made."""
+    """fiducial_slam/test/test_images/403.jpg (auto_init_403_test) and the CompressedImage frame of aruco_images.bag (the JPEG
+    stream cut out of the bag as it is stored there): the oracle's decode has the SHA-256 libjpeg-turbo's decode had when the
+    fixtures were made."""
     want = dict(s.split("=") for s in gold["reference_sha256"].tolist())
-    d = open(REF + "fiducial_slam/test/test_images/403.jpg", "rb").read()
+    d = open(os.path.join(GOLD_DIR, "403.jpg"), "rb").read()
     assert hashlib.sha256(oj.decode(d).tobytes()).hexdigest() == want["403.jpg"]
-    blob = _bag_jpeg(REF + "fiducial_slam/test/aruco_images.bag")
-    assert blob is not None
+    blob = open(os.path.join(GOLD_DIR, "aruco_images_bag_frame.jpg"), "rb").read()
     assert hashlib.sha256(oj.decode(blob).tobytes()).hexdigest() == want["aruco_images.bag"]
 
 

@@ -1,17 +1,21 @@
 """The reference-built STag oracle (oracle/_ref): loads, and its pieces behave as the reference code reads."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle import stag_ref
 
-pytestmark = pytest.mark.skipif(not stag_ref.available(), reason="oracle/_ref/libstag_ref.so not built")
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
 def test_constants_are_the_reference_ones():
+    _need_ref()
     assert stag_ref.constants() == dict(EDGE_VERTICAL=1, EDGE_HORIZONTAL=2, ANCHOR_PIXEL=254)
 
 
 def test_smooth5_is_the_fixed_binomial_kernel():
+    _need_ref()
     img = np.zeros((9, 9), np.uint8)
     img[4, 4] = 255
     s = stag_ref.smooth5(img)
@@ -21,6 +25,7 @@ def test_smooth5_is_the_fixed_binomial_kernel():
 
 
 def test_vertical_step_edge_gives_vertical_anchors_sorted_by_gradient():
+    _need_ref()
     img = np.zeros((12, 16), np.uint8)
     img[:, 8:] = 200
     grad, dirs = stag_ref.gradient(img, 16)
@@ -101,8 +106,9 @@ def test_rendered_codewords_come_back_from_the_reference_detector(hd, ec):
 @pytest.mark.parametrize("size", [(1920, 1080), (640, 480), (320, 240), (160, 120)])
 def test_host_made_tables_equal_the_references(size):
     """The tables the product makes on the host (fid_stag_host_tables: no device needed) against the reference's own NFALUT,
-    ComputeMinLineLength and Stag::fillCodeLocations; past the table's end, against nfa() itself."""
-    _need_ref()
+    ComputeMinLineLength and Stag::fillCodeLocations; past the table's end, against nfa() itself.  Where oracle/_ref is not
+    built, against the reference's tables as committed (tests/golden/stag_host_tables.npz, tools/make_stag_tables_golden.py:
+    past the table's end, the least k with nfa(n, k) >= 0), which are checked against oracle/_ref wherever it is built."""
     import ctypes as C
     from fiducials_amd import _lib
     w, h = size
@@ -112,12 +118,23 @@ def test_host_made_tables_equal_the_references(size):
     locs = np.zeros((72, 3))
     rc = L.fid_stag_host_tables(w, h, kmin.ctypes.data, len(kmin), C.byref(n), C.byref(ls), locs.ctypes.data, C.byref(mll))
     assert rc == _lib.FID_OK
-    lut, rmll, rlocs = stag_ref.host_tables(w, h)
+    gold = np.load(os.path.join(GOLD, "stag_host_tables.npz"))
+    glut, gmll, glocs, gkmin = (gold[f"{w}x{h}_{k}"] for k in ("lut", "mll", "locs", "kmin"))
+    live = stag_ref.available()
+    if live:
+        lut, rmll, rlocs = stag_ref.host_tables(w, h)
+        assert np.array_equal(lut, glut) and rmll == int(gmll) and np.array_equal(rlocs, glocs)  # the committed tables are the reference's
+    else:
+        lut, rmll, rlocs = glut, int(gmll), glocs
+    assert n.value - len(lut) <= len(gkmin)
     assert ls.value == len(lut) == (w + h) // 8 and mll.value == rmll
     assert np.array_equal(kmin[:len(lut)], lut)
     assert np.array_equal(locs, rlocs), np.abs(locs - rlocs).max()
     for nn in list(range(len(lut), min(n.value, len(lut) + 40))) + list(range(n.value - 5, n.value)):  # k >= kmin[n]  <=>  nfa(n, k) >= 0
         km = int(kmin[nn])
+        assert (km if km <= nn else nn + 1) == int(gkmin[nn - len(lut)]), nn
+        if not live:
+            continue
         if km <= nn:
             assert stag_ref.nfa_valid(nn, km, w, h) and (km == 0 or not stag_ref.nfa_valid(nn, km - 1, w, h)), nn
         else:
