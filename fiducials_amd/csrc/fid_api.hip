@@ -22,6 +22,8 @@ const char *const kStageNames[ST_COUNT] = {"to_gray", "threshold", "find_starts"
                                            "near", "resolve", "identify", "filter_markers", "subpix", "pose", "seed_walk", "seedless_chain"};
 
 constexpr int TX = 128, TY = 32, NT = 256;
+constexpr int THRW_NT = 512, THRW_WT = 16;  // k_threshold_wide: 512 threads x 16 columns cover the 8191-px frame limit
+static_assert(THRW_NT * THRW_WT >= 8191, "k_threshold_wide: a row per workgroup");
 
 }  // namespace
 
@@ -130,6 +132,8 @@ struct fid_ctx {
     float4 *d_cmeta = nullptr;
     uint32_t *d_near = nullptr;
     DevIdent *d_ident = nullptr;
+    uint8_t *d_bits = nullptr;  // [max_batch][max_cands][msb^2] cell bits (FID_TAP_BITS)
+    int bits_cap = 0;           // msb^2 the array has room for
     fid_marker *d_pre = nullptr, *d_markers = nullptr, *d_filter_scratch = nullptr;
     int *d_accsrc = nullptr, *d_mksrc = nullptr;  // the filtered candidate behind every identified / kept marker (k_filter_markers -> k_refine_contour)
     fid_pose_out *d_poses = nullptr;
@@ -246,12 +250,17 @@ fid_status apply_params(fid_ctx *c, const fid_params *p)
     P.nscales = nsc;
     P.rmax = 0;
     for (int i = 0; i < nsc; i++) {
-        int w = p->adaptiveThreshWinSizeMin + i * p->adaptiveThreshWinSizeStep;
+        long long w = p->adaptiveThreshWinSizeMin + (long long)i * p->adaptiveThreshWinSizeStep;
         if (w % 2 == 0) w++;
-        P.win[i] = w;
-        if (w / 2 > P.rmax) P.rmax = w / 2;
+        if (w > FID_MAX_THR_WIN) {
+            c->last_error = "adaptive threshold window " + std::to_string(w) + " px: windows above " + std::to_string(FID_MAX_THR_WIN) +
+                            " px (2 x 8191 + 1) are not supported";
+            return FID_E_UNSUPPORTED;
+        }
+        P.win[i] = (int)w;
+        if (w / 2 > P.rmax) P.rmax = (int)(w / 2);
     }
-    if (P.rmax > 40) return FID_E_UNSUPPORTED;  // LDS tile budget of k_threshold
+    // (rmax <= 40: k_threshold; above, k_threshold_wide -- any window up to FID_MAX_THR_WIN)
     {
         // adaptiveThreshold: idelta = type == THRESH_BINARY ? cvCeil(delta) : cvFloor(delta); aruco passes THRESH_BINARY_INV
         double cdelta = p->adaptiveThreshConstant;
@@ -266,8 +275,18 @@ fid_status apply_params(fid_ctx *c, const fid_params *p)
     P.borderBits = p->markerBorderBits;
     P.cellSize = p->perspectiveRemovePixelPerCell;
     P.cellMargin = (int)(p->perspectiveRemoveIgnoredMarginPerCell * p->perspectiveRemovePixelPerCell);
-    if (P.markerSize + 2 * P.borderBits > FID_MAX_CELLS) return FID_E_UNSUPPORTED;
-    if (P.cellSize < 1 || P.cellSize - 2 * P.cellMargin < 1 || (P.markerSize + 2 * P.borderBits) * P.cellSize > 160) return FID_E_UNSUPPORTED;
+    if (P.markerSize + 2 * P.borderBits > FID_MAX_CELLS) {
+        c->last_error = "markerSize + 2 x markerBorderBits = " + std::to_string(P.markerSize + 2 * P.borderBits) + " cells: at most " +
+                        std::to_string(FID_MAX_CELLS) + " are supported";
+        return FID_E_UNSUPPORTED;
+    }
+    if (P.cellSize < 1 || P.cellSize - 2 * P.cellMargin < 1) return FID_E_UNSUPPORTED;
+    if ((long long)(P.markerSize + 2 * P.borderBits) * P.cellSize > FID_MAX_PATCH) {
+        c->last_error = "unwarped patch of (markerSize + 2 x markerBorderBits) x perspectiveRemovePixelPerCell = " +
+                        std::to_string((long long)(P.markerSize + 2 * P.borderBits) * P.cellSize) + " px a side: at most " +
+                        std::to_string(FID_MAX_PATCH) + " are supported";
+        return FID_E_UNSUPPORTED;
+    }
     P.minOtsuStdDev = p->minOtsuStdDev;
     P.maxBorderErr = (int)(c->dict_ms * c->dict_ms * p->maxErroneousBitsInBorderRate);
     P.maxCorr = (int)((double)c->dict_maxc * p->errorCorrectionRate);
@@ -278,9 +297,13 @@ fid_status apply_params(fid_ctx *c, const fid_params *p)
     if (p->cornerRefinementMethod < 0 || p->cornerRefinementMethod > 2) return FID_E_UNSUPPORTED;
     P.refine = p->cornerRefinementMethod;
     P.subpixWin = p->cornerRefinementWinSize;
-    if (P.refine == 1 && (P.subpixWin < 1 || P.subpixWin > SP_MAXWIN || p->cornerRefinementMaxIterations < 1 ||
-                     !(p->cornerRefinementMinAccuracy > 0)))
+    if (P.refine == 1 && (P.subpixWin < 1 || P.subpixWin > SP_MAXWIN_MAX || p->cornerRefinementMaxIterations < 1 ||
+                     !(p->cornerRefinementMinAccuracy > 0))) {
+        if (P.subpixWin > SP_MAXWIN_MAX)
+            c->last_error = "cornerRefinementWinSize " + std::to_string(P.subpixWin) + ": at most " + std::to_string(SP_MAXWIN_MAX) +
+                            " is supported with CORNER_REFINE_SUBPIX";
         return FID_E_INVALID_ARG;
+    }
     {
         int mi = p->cornerRefinementMaxIterations;
         P.subpixMaxIter = mi < 1 ? 1 : (mi > 100 ? 100 : mi);
@@ -612,6 +635,17 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                 using C = ThrCfg<3, 4, 13>;
                 dim3 grid((W + C::TX - 1) / C::TX, (H + C::TY - 1) / C::TY, Fs);
                 hipLaunchKernelGGL((k_threshold_fixed<3, 4, 13>), grid, dim3(C::NT), C::LDS_BYTES, st, g, gfstride, masks, P);
+            } else if (P.rmax > 40) {
+                // windows above 81 px: bands of whole rows, enough of them to fill the chip (a band pays a closed-form start of its
+                // running column sums, up to min(2 rmax + 1, H) rows per scale, so they are not cut below 16 rows)
+                int bands = (512 + Fs - 1) / Fs;
+                const int maxb = (H + 15) / 16;
+                bands = bands < 1 ? 1 : (bands > maxb ? maxb : bands);
+                const int BH = (H + bands - 1) / bands;
+                const size_t lds = (size_t)(W + 1 + THRW_NT / 64) * sizeof(unsigned long long);
+                fid_launch_log("k_threshold_wide", THRW_NT, lds);
+                hipLaunchKernelGGL((k_threshold_wide<THRW_NT, THRW_WT>), dim3((H + BH - 1) / BH, 1, Fs), dim3(THRW_NT), lds, st, g, gfstride,
+                                   masks, P, BH);
             } else {
                 int R = P.rmax, RW = TX + 2 * R, RH = TY + 2 * R, PT = (RW + 1) | 1;
                 size_t lds = (size_t)(RH + 1) * PT * sizeof(uint32_t);
@@ -844,7 +878,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             int SZ = (P.markerSize + 2 * P.borderBits) * P.cellSize;
             fid_launch_log("k_identify", 64, (size_t)((size_t)SZ * SZ));
             hipLaunchKernelGGL(k_identify, dim3(c->tail_grid > 0 ? c->tail_grid : 256 * 4), dim3(64), (size_t)SZ * SZ, st, g, gfstride, filtered, worklist, nwork,
-                               c->d_dict, ident, P);
+                               c->d_dict, ident, c->d_bits + f0 * MC * (size_t)(P.markerSize + 2 * P.borderBits) * (P.markerSize + 2 * P.borderBits), P);
         }
         mark(ST_IDENT + 1);
         // ---- K7
@@ -861,8 +895,10 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                                    (const int *)(c->d_mksrc + f0 * MM), (const DevCand *)filtered,
                                    (const uint32_t *)(c->d_dense ? c->d_dense + (size_t)f0 * P.maxChunks * (CK / 4) : nullptr), (const uint32_t *)tab,
                                    (const uint32_t *)pool, counts, P);
+            else if (P.subpixWin <= 7)  // (the LDS and tap registers of k_subpix follow its window bound)
+                hipLaunchKernelGGL(k_subpix<7>, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
             else
-                hipLaunchKernelGGL(k_subpix, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
+                hipLaunchKernelGGL(k_subpix<SP_MAXWIN_MAX>, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
         }
         mark(ST_SUBPIX + 1);
         if (c->pose_cam_valid) {
@@ -1199,7 +1235,7 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
         for (int i = 0; i < 20; i++) TRYHIP(hipEventCreate(&c->sub_ev[sb][i]));
     }
     const size_t F = L.max_batch, MC = L.max_candidates_per_frame, MM = L.max_markers_per_frame;
-    TRY(dalloc(c, &c->d_subpix_mask, (size_t)(2 * SP_MAXWIN + 1) * (2 * SP_MAXWIN + 1)));
+    TRY(dalloc(c, &c->d_subpix_mask, (size_t)(2 * SP_MAXWIN_MAX + 1) * (2 * SP_MAXWIN_MAX + 1)));
     TRY(dalloc(c, &c->d_probe_tables, (size_t)4096));
     hipLaunchKernelGGL(k_probe_tables, dim3(1), dim3(256), 0, nullptr, c->d_probe_tables);
     TRYHIP(hipGetLastError());
@@ -1261,6 +1297,13 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     TRY(dalloc(c, &c->d_filtered, F * MC));
     TRY(dalloc(c, &c->d_near, F * MC * (MC / 32)));
     TRY(dalloc(c, &c->d_ident, F * MC));
+    // (the cell bits: room for any grid of up to 9 cells -- every 7x7 or smaller dictionary with a 1-cell border -- or the one the
+    //  parameters ask for; fid_set_params grows it)
+    {
+        const int msb = c->P.markerSize + 2 * c->P.borderBits;
+        c->bits_cap = msb * msb > 81 ? msb * msb : 81;
+        TRY(dalloc(c, &c->d_bits, F * MC * c->bits_cap));
+    }
     TRY(dalloc(c, &c->d_pre, F * MM));
     TRY(dalloc(c, &c->d_filter_scratch, F * MC));
     TRY(dalloc(c, &c->d_accsrc, F * MC));
@@ -1278,6 +1321,9 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
                                (int)ThrCfg<3, 4, 13>::LDS_BYTES));
     TRYHIP(hipFuncSetAttribute((const void *)k_approx, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
     TRYHIP(hipFuncSetAttribute((const void *)k_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    TRYHIP(hipFuncSetAttribute((const void *)k_threshold_wide<THRW_NT, THRW_WT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)((8191 + 1 + THRW_NT / 64) * sizeof(unsigned long long))));
+    TRYHIP(hipFuncSetAttribute((const void *)k_identify, hipFuncAttributeMaxDynamicSharedMemorySize, FID_MAX_PATCH * FID_MAX_PATCH));
     TRYHIP(hipFuncSetAttribute((const void *)k_filter_markers, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
 #undef TRY
 #undef TRYHIP
@@ -1291,7 +1337,7 @@ void fid_destroy(fid_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *dev[] = {c->d_in, c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
-                   c->d_ident, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
+                   c->d_ident, c->d_bits, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
                    c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n};
     for (void *p : dev)
         if (p) (void)hipFree(p);
@@ -1358,6 +1404,22 @@ fid_status fid_set_params(fid_ctx *c, const fid_params *p)
             (void)apply_params(c, &keep);
             c->last_error = "maxMarkerPerimeterRate larger than the context was created for";
             return FID_E_UNSUPPORTED;
+        }
+    }
+    if (rc == FID_OK) {
+        // a wider grid than the cell-bits array has room for: grow it (nothing is in flight here)
+        const int msb = c->P.markerSize + 2 * c->P.borderBits;
+        if (msb * msb > c->bits_cap) {
+            uint8_t *nb = nullptr;
+            const hipError_t e = hipMalloc((void **)&nb, (size_t)c->lim.max_batch * c->lim.max_candidates_per_frame * msb * msb);
+            if (e != hipSuccess) {
+                (void)apply_params(c, &keep);
+                c->last_error = std::string("hipMalloc (cell bits): ") + hipGetErrorString(e);
+                return e == hipErrorOutOfMemory ? FID_E_OUT_OF_MEMORY : FID_E_HIP;
+            }
+            HIPCHK(c, hipFree(c->d_bits));
+            c->d_bits = nb;
+            c->bits_cap = msb * msb;
         }
     }
     if (rc != FID_OK) (void)apply_params(c, &keep);
@@ -1760,18 +1822,15 @@ fid_status fid_tap_read(fid_ctx *c, fid_tap which, void *dst, int64_t dst_bytes)
         return FID_OK;
     }
     case FID_TAP_BITS:
+        HIPCHK(c, hipMemcpy(dst, c->d_bits, (size_t)F * P.maxCands * msb * msb, hipMemcpyDeviceToHost));
+        return FID_OK;
     case FID_TAP_IDENT: {
         std::vector<DevIdent> tmp((size_t)F * P.maxCands);
         HIPCHK(c, hipMemcpy(tmp.data(), c->d_ident, tmp.size() * sizeof(DevIdent), hipMemcpyDeviceToHost));
-        if (which == FID_TAP_BITS) {
-            uint8_t *o = (uint8_t *)dst;
-            for (size_t i = 0; i < tmp.size(); i++) memcpy(o + i * msb * msb, tmp[i].bits, (size_t)msb * msb);
-        } else {
-            int32_t *o = (int32_t *)dst;
-            for (size_t i = 0; i < tmp.size(); i++) {
-                o[2 * i] = tmp[i].id;
-                o[2 * i + 1] = tmp[i].rot;
-            }
+        int32_t *o = (int32_t *)dst;
+        for (size_t i = 0; i < tmp.size(); i++) {
+            o[2 * i] = tmp[i].id;
+            o[2 * i + 1] = tmp[i].rot;
         }
         return FID_OK;
     }

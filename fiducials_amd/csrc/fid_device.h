@@ -18,7 +18,9 @@
 //   cands     DevCand [F][max_cands]          quads leaving _findMarkerContours
 //   sorted / filtered DevCand [F][max_cands]  OpenCV order; after reorder + too-close filter
 //   near      u32  [F][max_cands][max_cands/32]
-//   ident     DevIdent [F][max_cands]
+//   ident     DevIdent [F][max_cands]         id, rotation
+//   bits      u8   [F][max_cands][msb^2]      cell bits of the unwarped candidate (msb = marker_size + 2 border; the array
+//                                              grows at fid_set_params when msb^2 outgrows it)
 //   markers   fid_marker [F][max_markers]     (pre- and post-subpix)
 //   poses     fid_pose_out [F][max_markers]
 #pragma once
@@ -58,7 +60,9 @@ static inline void fid_launch_log(const char *kernel, unsigned block, size_t lds
 #define MASK_PADW 1  // zero tile columns in front of every tile row
 #define MT_ROWS 16   // rows per mask tile
 #define FID_MAX_SCALES 32
-#define FID_MAX_CELLS 9  // marker_size + 2*border <= 9 (7x7 dictionaries)
+#define FID_MAX_CELLS 16   // marker_size + 2*border <= 16 (the oracle's _identifyOneCandidate bound)
+#define FID_MAX_PATCH 256  // unwarped patch side (marker_size + 2*border) * perspectiveRemovePixelPerCell: 64 KiB of LDS
+#define FID_MAX_THR_WIN (2 * 8191 + 1)  // adaptive-threshold windows: the widest that matters for an 8191-px frame
 
 struct DevParams {
     int W, H, gstride, WW, TC, TR, nscales, nframes;  // WW mask words per image row; TC x TR mask tiles per plane
@@ -99,9 +103,8 @@ struct DevCand {
     unsigned pad;
 };
 
-struct DevIdent {
+struct DevIdent {  // (the cell bits of a candidate are in their own array, [F][max_cands][msb * msb] u8: FID_TAP_BITS)
     int id, rot;
-    unsigned char bits[FID_MAX_CELLS * FID_MAX_CELLS + 3];
 };
 
 // ---- seed-accelerated contour tracing.  A border-following state is (pixel, direction d back to the previous pixel).

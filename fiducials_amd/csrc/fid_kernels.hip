@@ -3,7 +3,7 @@
 //  /root/reference/aruco_detect/src/aruco_detect.cpp:350 and :247; stage map in SURVEY.md §8a).
 //
 //   K0 k_to_gray        a2  bgr8/rgb8 -> gray (15-bit fixed point), or stride compaction
-//   K1 k_threshold_stream (node window table) / k_threshold (any table)   a3  the 13 adaptive-threshold scales from one
+//   K1 k_threshold_stream (node table) / k_threshold (rmax <= 40) / k_threshold_wide (any window)   a3  the scales from one
 //                       pass over the image, bit-packed tiled masks out; k_threshold_fixed = the round-1 tile kernel (FID_THR=tile)
 //   K2 k_find_starts    a4  border-following start points and tracing seeds by bit-parallel tests on mask words
 //   K3 k_probe<6>, <32> a4  one lane per start: a few steps of Suzuki-Abe border following sieve the starts
@@ -373,6 +373,116 @@ __global__ __launch_bounds__(NT) void k_threshold(const uint8_t *__restrict__ gr
             if (lane == 0) {
                 mrow[(long long)s * plane] = (uint32_t)b;
                 mrow[(long long)s * plane + MT_ROWS] = (uint32_t)(b >> 32);  // next tile column
+            }
+        }
+    }
+}
+
+// K1 for tables with a window above 81 px (rmax > 40: k_threshold's (TY + 2 rmax + 1) x PT integral no longer fits the LDS).
+// The same test, 2*boxsum >= (2*(src + idelta) - 1) * win^2, with nothing in LDS that grows with the window.  One workgroup =
+// one band of BH whole rows of one frame (frames are grid z).  Per scale:
+//   V(x)    the vertical box sum of column x over rows clamp(y - r) .. clamp(y + r): a thread keeps the V of its chunk of WT
+//           consecutive columns in registers.  At the band's first row V is set up in closed form -- (rows above the frame) x
+//           row 0 + the rows inside + (rows below) x row H-1 -- and then moves one row at a time (+ row clamp(y + r + 1),
+//           - row clamp(y - r)).
+//   HP(x)   the row prefix of V, u64 in LDS (a block scan of the chunk sums); the box sum of x is then
+//           HP(min(x + r + 1, W)) - HP(max(x - r, 0)) + max(0, r - x) V(0) + max(0, x + r + 1 - W) V(W - 1):
+//           BORDER_REPLICATE in closed form.  Everything is exact in 64 bits for any window up to FID_MAX_THR_WIN (V < 2^22,
+//           sum < 2^37), so windows wider and taller than the frame are plain cases.
+// LDS: (W + 1 + NT / 64) u64.  Mask words: a wave ballots 64 consecutive x into two words of the tiled layout, as k_threshold
+// does (bits at x >= W are zero; the words past them keep the zeros the re-zero left).
+template <int NT, int WT>
+__global__ __launch_bounds__(NT) void k_threshold_wide(const uint8_t *__restrict__ gray, long long gfstride,
+                                                        uint32_t *__restrict__ masks, const DevParams P, int BH)
+{
+    extern __shared__ unsigned long long HP[];  // [W + 1] row prefix of V, then [NT / 64] wave totals
+    constexpr int NWAVES = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int W = P.W, H = P.H, gs = P.gstride, S = P.nscales, TC = P.TC;
+    const int f = blockIdx.z, y0 = blockIdx.x * BH;
+    if (y0 >= H) return;  // (uniform)
+    const int y1 = y0 + BH < H ? y0 + BH : H;
+    const uint8_t *g = gray + (long long)f * gfstride;
+    const long long plane = (long long)P.TR * TC * MT_ROWS;
+    uint32_t *mframe = masks + (long long)f * S * plane;
+    unsigned long long *wtot = HP + W + 1;
+    const int K = (W + NT - 1) / NT;               // columns per thread (<= WT: W <= NT * WT is checked by the host)
+    const int c0 = tid * K;                        // this thread's chunk: [c0, min(c0 + K, W))
+    const int nk = c0 >= W ? 0 : (W - c0 < K ? W - c0 : K);
+    const int nseg = (W + 63) / 64;
+    for (int s = 0; s < S; s++) {
+        const int win = P.win[s], r = win >> 1;
+        const long long area = (long long)win * win;
+        uint32_t V[WT];
+        {
+            const int lo = y0 - r > 0 ? y0 - r : 0, hi = y0 + r < H - 1 ? y0 + r : H - 1;
+            const uint32_t nabove = r > y0 ? (uint32_t)(r - y0) : 0u, nbelow = y0 + r > H - 1 ? (uint32_t)(y0 + r - (H - 1)) : 0u;
+#pragma unroll
+            for (int j = 0; j < WT; j++) V[j] = 0;
+            for (int yy = lo; yy <= hi; yy++) {
+                const uint8_t *row = g + (long long)yy * gs + c0;
+#pragma unroll
+                for (int j = 0; j < WT; j++)
+                    if (j < nk) V[j] += row[j];
+            }
+            const uint8_t *top = g + c0, *bot = g + (long long)(H - 1) * gs + c0;
+#pragma unroll
+            for (int j = 0; j < WT; j++)
+                if (j < nk) V[j] += nabove * top[j] + nbelow * bot[j];
+        }
+        for (int y = y0; y < y1; y++) {
+            if (y > y0) {
+                const int yin = y + r < H - 1 ? y + r : H - 1, yout = y - 1 - r > 0 ? y - 1 - r : 0;
+                const uint8_t *ri = g + (long long)yin * gs + c0, *ro = g + (long long)yout * gs + c0;
+#pragma unroll
+                for (int j = 0; j < WT; j++)
+                    if (j < nk) V[j] += (uint32_t)ri[j] - (uint32_t)ro[j];
+            }
+            // block scan of the chunk sums -> HP.  (Two barriers a row: the one after the wave totals also orders this row's
+            // writes after every wave's reads of the previous row's HP.)
+            unsigned long long tot = 0;
+#pragma unroll
+            for (int j = 0; j < WT; j++)
+                if (j < nk) tot += V[j];
+            unsigned long long inc = tot;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned long long t = __shfl_up(inc, o, WAVE);
+                if (lane >= o) inc += t;
+            }
+            if (lane == 63) wtot[wid] = inc;
+            __syncthreads();
+            unsigned long long run = inc - tot;
+            for (int w = 0; w < wid; w++) run += wtot[w];
+            if (tid == 0) HP[0] = 0;
+#pragma unroll
+            for (int j = 0; j < WT; j++)
+                if (j < nk) {
+                    run += V[j];
+                    HP[c0 + j + 1] = run;
+                }
+            __syncthreads();
+            const unsigned long long v0 = HP[1], vl = HP[W] - HP[W - 1];
+            const uint8_t *grow = g + (long long)y * gs;
+            uint32_t *mrow = mframe + (long long)s * plane;
+            for (int seg = wid; seg < nseg; seg += NWAVES) {
+                const int x = seg * 64 + lane;
+                const bool valid = x < W;
+                bool fg = false;
+                if (valid) {
+                    const int a = x - r, b = x + r + 1;
+                    unsigned long long sum = HP[b < W ? b : W] - HP[a > 0 ? a : 0];
+                    if (a < 0) sum += (unsigned long long)(-a) * v0;
+                    if (b > W) sum += (unsigned long long)(b - W) * vl;
+                    const long long t2 = 2LL * ((long long)grow[x] + P.idelta) - 1;
+                    fg = 2 * (long long)sum >= t2 * area;
+                }
+                const unsigned long long m = ballot64(fg);
+                if (lane == 0) {
+                    uint32_t *q = mrow + mask_word(TC, y + 1, MASK_PADW + 2 * seg);
+                    q[0] = (uint32_t)m;
+                    q[MT_ROWS] = (uint32_t)(m >> 32);  // next tile column
+                }
             }
         }
     }
@@ -4319,8 +4429,9 @@ __device__ __forceinline__ int sat_round_int(double v)
 __global__ __launch_bounds__(64) void k_identify(const uint8_t *__restrict__ gray, long long gfstride,
                                                   const DevCand *__restrict__ filtered, const unsigned *__restrict__ worklist,
                                                   const unsigned *__restrict__ nwork, const uint8_t *__restrict__ dict,
-                                                  DevIdent *__restrict__ ident, const DevParams P)
+                                                  DevIdent *__restrict__ ident, uint8_t *__restrict__ bits, const DevParams P)
 {
+    // (any grid up to FID_MAX_CELLS cells a side and patch up to FID_MAX_PATCH px: nothing below depends on the sizes but the LDS)
     extern __shared__ uint8_t patch[];  // S*S bytes
     __shared__ int hist[256];
     __shared__ uint8_t cellbits[FID_MAX_CELLS * FID_MAX_CELLS];
@@ -4338,6 +4449,7 @@ __global__ __launch_bounds__(64) void k_identify(const uint8_t *__restrict__ gra
         const DevCand *cdp = filtered + (long long)f * P.maxCands + k;  // (read in place: a copy indexed by lane went through scratch memory)
         const uint8_t *g = gray + (long long)f * gfstride;
         DevIdent *out = ident + (long long)f * P.maxCands + k;
+        uint8_t *obits = bits + ((long long)f * P.maxCands + k) * (msb * msb);
         __syncthreads();
 #ifdef ID_TIMING
         unsigned long long ti[6];
@@ -4637,7 +4749,7 @@ __global__ __launch_bounds__(64) void k_identify(const uint8_t *__restrict__ gra
         }
         __syncthreads();
         ID_T(4)
-        for (int c = lane; c < msb * msb; c += 64) out->bits[c] = cellbits[c];
+        for (int c = lane; c < msb * msb; c += 64) obits[c] = cellbits[c];
         // ---- _getBorderErrors (every lane computes the same scalar answer from LDS)
         int borderErrors = 0;
         for (int y = 0; y < msb; y++)
@@ -4847,13 +4959,17 @@ __global__ __launch_bounds__(64) void k_filter_markers(const DevCand *__restrict
 // K7b: cornerSubPix (cornersubpix.cpp) with getRectSubPix 8u->32f (samplers.cpp), one wave per corner.
 // The (2w+3)^2 patch and the per-tap products are computed in parallel; each of the five accumulators is
 // summed by its own lane in the reference's (i, j) order so the float corner equals the sequential result
-// bit for bit.
-#define SP_MAXWIN 7
+// bit for bit.  SP_MAXWIN (a template argument: the window bound the LDS arrays and per-lane tap registers are sized for) is
+// instantiated for 7 (cornerRefinementWinSize <= 7, the node's 5 among them) and for 15 (8..15, the oracle's bound).
+#define SP_MAXWIN_MAX 15
+template <int SP_MAXWIN>
 __global__ __launch_bounds__(64) void k_subpix(const uint8_t *__restrict__ gray, long long gfstride,
                                                 const fid_marker *__restrict__ pre, fid_marker *__restrict__ out,
                                                 const DevCounts *__restrict__ counts, const float *__restrict__ maskw,
                                                 const DevParams P)
 {
+    // taps per lane: (2 w + 1)^2 taps of the window, 64 at a time
+    constexpr int SP_NK = ((2 * SP_MAXWIN + 1) * (2 * SP_MAXWIN + 1) + 63) / 64;
     __shared__ float sp[(2 * SP_MAXWIN + 3) * (2 * SP_MAXWIN + 3)];
     // (rows padded to a multiple of 16 taps; the pad holds -0.0, the one value x + pad == x holds for bit for bit, for every x)
     constexpr int SP_NTP = ((2 * SP_MAXWIN + 1) * (2 * SP_MAXWIN + 1) + 15) & ~15;
@@ -4899,9 +5015,9 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t *__restrict__ gray,
             }
         // (the window weights of this lane's taps: read once, not once per iteration -- a global load in front of every
         //  iteration's products sat on the critical path)
-        float wgt[4];
+        float wgt[SP_NK];
 #pragma unroll
-        for (int k = 0; k < 4; k++) wgt[k] = lane + 64 * k < ww * ww ? maskw[lane + 64 * k] : 0.f;
+        for (int k = 0; k < SP_NK; k++) wgt[k] = lane + 64 * k < ww * ww ? maskw[lane + 64 * k] : 0.f;
         constexpr int SP_PR = ((2 * SP_MAXWIN + 3) * (2 * SP_MAXWIN + 3) + 63) / 64;
         int poff[SP_PR], pjj[SP_PR];
 #pragma unroll
@@ -5015,7 +5131,7 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t *__restrict__ gray,
             __syncthreads();
             SP_T(tp0)
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
+            for (int k = 0; k < SP_NK; k++) {
                 const int t = lane + 64 * k;
                 if (t >= ww * ww) break;
                 int i = t / ww, j = t - i * ww;

@@ -86,20 +86,25 @@ typedef enum fid_encoding {  /* sensor_msgs/Image encodings the node accepts via
     FID_ENC_BIGENDIAN = 0x100 /* OR-ed onto a 16-bit encoding: sensor_msgs/Image.is_bigendian (cv_bridge swaps the bytes first) */
 } fid_encoding;
 
-/* aruco::DetectorParameters, fields and defaults as set by the node (aruco_detect.cpp:690-727) */
+/* aruco::DetectorParameters, fields and defaults as set by the node (aruco_detect.cpp:690-727).  Ranges the library takes beyond the
+ * defaults (past them fid_create / fid_set_params refuse, and fid_last_error names the bound):
+ *   adaptive-threshold windows  any odd window from 3 up to 2 x 8191 + 1 px, at most 32 scales (FID_E_UNSUPPORTED above)
+ *   cornerRefinementWinSize     1 .. 15 with CORNER_REFINE_SUBPIX (FID_E_INVALID_ARG above)
+ *   marker grid                 marker_size + 2 markerBorderBits <= 16 cells, and the unwarped patch
+ *                               (marker_size + 2 markerBorderBits) x perspectiveRemovePixelPerCell <= 256 px (FID_E_UNSUPPORTED) */
 typedef struct fid_params {
     double adaptiveThreshConstant;                 /* 7    */
     int32_t adaptiveThreshWinSizeMin;              /* 3    */
-    int32_t adaptiveThreshWinSizeMax;              /* 53   */
+    int32_t adaptiveThreshWinSizeMax;              /* 53   (up to 2 x 8191 + 1) */
     int32_t adaptiveThreshWinSizeStep;             /* 4    */
     int32_t cornerRefinementMethod;                /* 1 = CORNER_REFINE_SUBPIX (node default), 0 = NONE, 2 = CORNER_REFINE_CONTOUR
                                                       (doCornerRefinement && !cornerRefinementSubPix, :274-283, :700-711) */
-    int32_t cornerRefinementWinSize;               /* 5    */
+    int32_t cornerRefinementWinSize;               /* 5    (up to 15) */
     int32_t cornerRefinementMaxIterations;         /* 30   */
     double cornerRefinementMinAccuracy;            /* 0.01 */
     double errorCorrectionRate;                    /* 0.6  */
     double minCornerDistanceRate;                  /* 0.05 */
-    int32_t markerBorderBits;                      /* 1    */
+    int32_t markerBorderBits;                      /* 1    (marker_size + 2 markerBorderBits <= 16) */
     int32_t minDistanceToBorder;                   /* 3    */
     double maxErroneousBitsInBorderRate;           /* 0.04 */
     double minMarkerDistanceRate;                  /* 0.05 */
@@ -107,7 +112,7 @@ typedef struct fid_params {
     double maxMarkerPerimeterRate;                 /* 4.0  */
     double minOtsuStdDev;                          /* 5.0  */
     double perspectiveRemoveIgnoredMarginPerCell;  /* 0.13 */
-    int32_t perspectiveRemovePixelPerCell;         /* 8    */
+    int32_t perspectiveRemovePixelPerCell;         /* 8    (patch side <= 256 px) */
     int32_t reserved0;
     double polygonalApproxAccuracyRate;            /* 0.01 */
 } fid_params;
@@ -220,7 +225,8 @@ typedef enum fid_tap {
     FID_TAP_MASKS = 0,       /* uint32 [nframes][nscales][height][words_per_row], bit x&31 of word x>>5 */
     FID_TAP_CANDIDATES = 1,  /* fid_candidate [nframes][max_candidates_per_frame], OpenCV order */
     FID_TAP_FILTERED = 2,    /* fid_candidate after reorder + too-close filter */
-    FID_TAP_BITS = 3,        /* uint8 [nframes][max_candidates_per_frame][(ms+2)^2] for FILTERED entries */
+    FID_TAP_BITS = 3,        /* uint8 [nframes][max_candidates_per_frame][msb][msb] for FILTERED entries, msb = marker_size +
+                                2 markerBorderBits */
     FID_TAP_IDENT = 4,       /* int32 [nframes][max_candidates_per_frame][2] id, rotation */
     FID_TAP_PRESUBPIX = 5,   /* fid_marker [nframes][max_markers_per_frame] */
     FID_TAP_COUNTS = 6,      /* int32 [nframes][12]: starts, contour slots, candidates, filtered, accepted, markers, overflow flags,
