@@ -16,7 +16,7 @@ namespace {
 
 enum { ST_GRAY = 0, ST_THRESH, ST_STARTS, ST_PROBE, ST_WALK, ST_APPROX, ST_SORT, ST_NEAR, ST_RESOLVE, ST_IDENT, ST_FILTER, ST_SUBPIX, ST_POSE, ST_SEEDWALK,
        ST_SEEDLESS, ST_COUNT };
-// (trace mode 2: walk_probe / walk_full / approx are the main stream's seed walk / link + cycles + copy / approx of the seed
+// (cycle tracing: walk_probe / walk_full / approx are the main stream's seed walk / link + cycles + copy / approx of the seed
 //  cycles; seedless_chain is the auxiliary stream's probes + survivor walk + cycles + copy + approx beside them)
 const char *const kStageNames[ST_COUNT] = {"to_gray", "threshold", "find_starts", "walk_probe", "walk_full", "approx", "sort_cands",
                                            "near", "resolve", "identify", "filter_markers", "subpix", "pose", "seed_walk", "seedless_chain"};
@@ -91,7 +91,7 @@ struct fid_ctx {
     uint2 *d_starts = nullptr, *d_surv1 = nullptr, *d_surv = nullptr;
     uint32_t *d_pool = nullptr;
     // seed-accelerated tracing
-    DevSeg *d_segs = nullptr;
+    DevSegC *d_segs = nullptr;
     DevPend *d_pend = nullptr;
     uint2 *d_seedq = nullptr;
     unsigned long long *d_seedhash = nullptr;  // per frame: seed state -> seed index (SeedHash, fid_kernels.hip)
@@ -99,21 +99,11 @@ struct fid_ctx {
     uint4 *d_wres = nullptr, *d_cinfo = nullptr;
     uint32_t *d_cbase = nullptr, *d_dense = nullptr;
     uint4 *d_recs = nullptr;  // copy records: pieces of the accepted contours
-    int thr_mode = 1;    // node window table: 1 = k_threshold_stream (default), 0 (FID_THR=tile) = k_threshold_fixed
-    // The probe survivors' walk.  Default: k_walk_full<2> (8 KB of LDS per wave).  FID_SURV_WALK=new: k_seed_walk<true> (round 5:
-    // the seed walker's toroidal prefetched windows, 16 KB per wave) -- 1.21 -> 1.00 M VALU wave-instructions per frame at 0.30
-    // instead of 0.23 of the lanes, the stage 9 % shorter, identical results; but on the two-context bench 33.2 - 33.9 k frames/s
-    // against 33.9 - 34.3 k (five interleaved rounds; with half the waves 33.7 k): what it takes of the CUs' LDS costs the other
-    // batch's kernels more than its instructions save.  Kept as an option and in the parity tests.
-    int surv_walk_old = 1;
-    int surv_blocks_x = 0;  // FID_SURV_BLOCKS_X: workgroups of k_seed_walk<true> = x times k_walk_full<2>'s waves (0: half of them)
     int thr_xcd = 1;  // strips dealt out so that an XCD works through neighbouring strips (FID_THR_XCD=0: plain grid order)
     int thr_nw = 3, thr_split = 0, thr_rows = 0;  // stream kernel: consumer waves per workgroup, un-fused LDS reads, rows per workgroup (0 = automatic)
-    int trace_mode = 2;  // 2: cycle tracing (borders read off the seed cycles; starts only for borders without a seed);
-                         // 1 (FID_TRACE=chain): round-2 seed tracing (every border found by a probe survivor); 0 (FID_TRACE=legacy):
-                         // probe passes + whole-border walk only
+    bool whole_border_walk = false;  // probe passes + whole-border walk only (FID_TRACE=legacy, and a call whose seed tables overflowed);
+                                     // else cycle tracing: borders read off the seed cycles, starts only for borders without a seed
     int sw_blocks = 0;   // FID_SW_BLOCKS: seed-walker workgroups per frame (0 = automatic)
-    int probe_lut = 1;   // table-driven probe passes (FID_PROBE_LUT=0: the arithmetic ones)
     int tail_grid = 4096;  // FID_TAIL_GRID: workgroups of k_identify (x 4: k_subpix) -- 1024 left 5 k candidates five rounds of an 80 us chain: +5 %
     int filter_lds = 256;  // markers k_filter_markers keeps in LDS (FID_FILTER_LDS; more go through the global scratch)
     int light_x = 1;     // FID_LIGHT_X: grid multiplier of k_near / k_seg_cycles, 1024 threads for k_sort_cands
@@ -364,7 +354,7 @@ size_t masks_elems(const fid_ctx *c, int W, int H, int F)
     return (size_t)F * c->P.nscales * TR * TC * MT_ROWS;
 }
 
-// the streams of sub-batches 0 .. nsub - 1 (and their auxiliary streams in the traced modes), made on first use
+// the streams of sub-batches 0 .. nsub - 1 (and their auxiliary streams under cycle tracing), made on first use
 fid_status ensure_streams(fid_ctx *c, int nsub, int F)
 {
     if (c->piece_chain) nsub = 2;  // (piece k works on main stream k & 1 and auxiliary stream k & 1)
@@ -374,12 +364,12 @@ fid_status ensure_streams(fid_ctx *c, int nsub, int F)
         //  queues carries side by side; with a fifth and sixth stream alive the default cost 17 % against GPU_MAX_HW_QUEUES >= 8)
         if (sb == 0) c->sub_stream[0] = c->stream;
         else if (!c->sub_stream[sb] && nsub > 1) HIPCHK(c, hipStreamCreateWithPriority(&c->sub_stream[sb], hipStreamNonBlocking, c->sub_prio[sb]));
-        if (!c->aux_stream[sb] && c->trace_mode >= 1) HIPCHK(c, hipStreamCreateWithPriority(&c->aux_stream[sb], hipStreamNonBlocking, c->sub_prio[sb]));
+        if (!c->aux_stream[sb] && !c->whole_border_walk) HIPCHK(c, hipStreamCreateWithPriority(&c->aux_stream[sb], hipStreamNonBlocking, c->sub_prio[sb]));
     }
     // one piece = two streams so far: a third one still fits the runtime's default of four hardware queues
     // (only for calls of a few frames -- the node's shape: a 256-frame batch of a chain is one piece too, but two contexts in turn
     //  would then hold six streams, and more than four live streams cost the batch 17 % in round 3)
-    if (nsub == 1 && F <= 16 && c->trace_mode == 2 && !c->idx_stream && !getenv("FID_NO_IDX_STREAM")) HIPCHK(c, hipStreamCreateWithFlags(&c->idx_stream, hipStreamNonBlocking));
+    if (nsub == 1 && F <= 16 && !c->whole_border_walk && !c->idx_stream && !getenv("FID_NO_IDX_STREAM")) HIPCHK(c, hipStreamCreateWithFlags(&c->idx_stream, hipStreamNonBlocking));
     return FID_OK;
 }
 
@@ -549,7 +539,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     // ---- the batch is cut into sub-batches that run the whole pipeline on their own streams: the latency-bound
     //      tail of one sub-batch's kernels (the longest border, the last candidates) overlaps the next one's bulk
     // (decided HERE and nowhere else: frames that come up from the host are cut by the copy's pieces whether or not the copy overlaps)
-    c->piece_chain = c->pieces > 1 && !c->chained && !c->host_feed && !c->from_host_call && c->trace_mode == 2 && c->sub_frames <= 0 &&
+    c->piece_chain = c->pieces > 1 && !c->chained && !c->host_feed && !c->from_host_call && !c->whole_border_walk && c->sub_frames <= 0 &&
                      F >= 32 * c->pieces && c->stagger == 0;
     const SubPlan plan = plan_sub_batches(c, F);
     const int nsub = plan.nsub;
@@ -614,7 +604,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         {
             bool node_table = P.nscales == 13;  // 3, 7, ..., 51: the node defaults (aruco_detect.cpp:690-693)
             for (int i = 0; i < P.nscales && node_table; i++) node_table = P.win[i] == 3 + 4 * i;
-            if (node_table && c->thr_mode == 1) {
+            if (node_table) {
                 // strips of 64 * NW columns, cut into row segments so that the grid fills the chip (a segment pays a warm-up
                 // of about ten steps, so they are kept as tall as the batch allows)
                 const int cols = 64 * c->thr_nw, strips = (W + cols - 1) / cols;
@@ -631,10 +621,6 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                 else if (c->thr_nw == 5) launch_thr_stream<5, false>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
                 else if (c->thr_split) launch_thr_stream<3, true>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
                 else launch_thr_stream<3, false>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
-            } else if (node_table) {
-                using C = ThrCfg<3, 4, 13>;
-                dim3 grid((W + C::TX - 1) / C::TX, (H + C::TY - 1) / C::TY, Fs);
-                hipLaunchKernelGGL((k_threshold_fixed<3, 4, 13>), grid, dim3(C::NT), C::LDS_BYTES, st, g, gfstride, masks, P);
             } else if (P.rmax > 40) {
                 // windows above 81 px: bands of whole rows, enough of them to fill the chip (a band pays a closed-form start of its
                 // running column sums, up to min(2 rmax + 1, H) rows per scale, so they are not cut below 16 rows)
@@ -663,10 +649,10 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             if (k2blocks > 256) k2blocks = 256;
         }
       if (phase == 0) {
-        // the traced modes' start / seed enumeration belongs to the first round as well: every sub-batch's find_starts is then
+        // cycle tracing's start / seed enumeration belongs to the first round as well: every sub-batch's find_starts is then
         // queued before any walk, and (fs_barrier) the walks of all sub-batches wait for the last find_starts -- beside another
         // sub-batch's seed walk and probes a find_starts took 2.5 ms for 92 frames, beside another find_starts 1.1 ms for 164
-        if (c->trace_mode >= 1) {
+        if (!c->whole_border_walk) {
             hipLaunchKernelGGL(k_find_starts<true>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
                                c->d_seedq + f0 * (size_t)P.maxContours, P);
             mark(ST_STARTS + 1);
@@ -675,7 +661,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         }
         return FID_OK;
       }
-        if (c->trace_mode >= 1 && nsub > 1 && c->fs_barrier && !chainp)
+        if (!c->whole_border_walk && nsub > 1 && c->fs_barrier && !chainp)
             for (int o = 0; o < nsub; o++)
                 if (o != sb) HIPCHK(c, hipStreamWaitEvent(st, c->fs_done[o], 0));
         // persistent walker workgroups (WALK_WAVES waves each) per frame: about 16 waves per CU over the sub-batch
@@ -689,7 +675,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         const int cap1 = pts_cap_first(P);
         const size_t lds1 = (size_t)cap1 * sizeof(uint32_t) + (size_t)K4_SHORT_STACK * sizeof(int2);
         const size_t lds2 = (size_t)(P.maxPerim + 1) * sizeof(uint32_t) + (size_t)K4_LONG_STACK * sizeof(int2);
-        if (c->trace_mode == 0) {
+        if (c->whole_border_walk) {
             hipLaunchKernelGGL(k_find_starts<false>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
                                (uint2 *)nullptr, P);
             mark(ST_STARTS + 1);
@@ -697,7 +683,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             hipLaunchKernelGGL((k_probe<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, st, masks, starts, surv1, counts, c->d_global, P);
             hipLaunchKernelGGL((k_probe<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, st, masks, surv1, surv, counts, c->d_global, P);
             mark(ST_PROBE + 1);
-            hipLaunchKernelGGL(k_walk_full<0>, dim3(wb, Fs), dim3(64 * WALK_WAVES), 0, st, masks, surv, contours, tab, pool, (DevSeg *)nullptr,
+            hipLaunchKernelGGL(k_walk_full<0>, dim3(wb, Fs), dim3(64 * WALK_WAVES), 0, st, masks, surv, contours, tab, pool, (DevSegC *)nullptr,
                                (DevPend *)nullptr, counts, c->d_global, P);
             mark(ST_WALK + 1);
             // ---- K4: short contours with a small LDS footprint first, then the long / flagged ones
@@ -709,10 +695,8 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                                P.maxPerim + 1, K4_LONG_STACK, 1, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
             mark(ST_APPROX + 1);
         } else {
-            // ---- seed-accelerated tracing: seeds walk their segments while the starts are sieved; survivors walk to the
-            //      first seed; link -> chain -> flatten
             const size_t MCn = (size_t)P.maxContours;
-            DevSeg *segs = c->d_segs + f0 * MCn;
+            DevSegC *segs = c->d_segs + f0 * MCn;
             DevPend *pend = c->d_pend + f0 * MCn;
             uint2 *seedq = c->d_seedq + f0 * MCn;
             unsigned long long *seedhash = c->d_seedhash + (size_t)f0 * P.seedHashCap;
@@ -720,7 +704,6 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             uint32_t *cbase = c->d_cbase + f0 * MCn;
             uint32_t *dense = c->d_dense + (size_t)f0 * P.maxChunks * (CK / 4);  // (one code byte per point)
             // (k_find_starts<true> was queued in the first round)
-          if (c->trace_mode == 2) {
             // ---- cycle tracing.  Main stream: the seeds walk their segments, link, the cycles become contour list A, copy,
             //      approxPolyDP.  Auxiliary stream, beside it: seed index, then the chain that only exists for borders WITHOUT a
             //      seed state (probe passes that drop a start at the first seed state, survivor walk, contour list B, copy,
@@ -738,8 +721,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             // -- the main stream's first kernel goes out BEFORE the auxiliary chain's eight launches: the host needs ~15 us to
             //    enqueue those, and for a single frame the seed walk sat waiting behind them (round 4, cfg 2 timeline)
             if (c->profile) (void)hipEventRecord(ev[14], st);
-            hipLaunchKernelGGL(k_seed_walk<false>, dim3(swb, Fs), dim3(64 * SW_WAVES), 0, st, masks, seedq, tab, pool, (DevSegC *)segs, counts,
-                               c->d_global, P, (uint4 *)nullptr, (DevPend *)nullptr);
+            hipLaunchKernelGGL(k_seed_walk, dim3(swb, Fs), dim3(64 * SW_WAVES), 0, st, masks, seedq, tab, pool, segs, counts, c->d_global, P);
             if (c->profile) (void)hipEventRecord(ev[15], st);
             mark(ST_PROBE + 1);
             chain_point(1);
@@ -751,32 +733,23 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             if (si != sa) HIPCHK(c, hipStreamWaitEvent(si, c->aux_fork[sb], 0));
             hipLaunchKernelGGL(k_seed_index, dim3(8 * gm, Fs), dim3(256), 0, si, seedq, seedhash, counts, P);
             HIPCHK(c, hipEventRecord(c->aux_idx[sb], si));
-            if (c->probe_lut) {
-                if (c->probe_refill0 && gm == 1)
-                    hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(c->probe_refill0, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-                else
+            if (c->probe_refill0 && gm == 1)
+                hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(c->probe_refill0, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
+                                   (const uint4 *)c->d_probe_tables);
+            else
                 hipLaunchKernelGGL((k_probe_lut<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
                                    (const uint4 *)c->d_probe_tables);
-                if (c->probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
-                    hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(c->probe_refill, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-                else
-                    hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-            } else {
-                hipLaunchKernelGGL((k_probe<PROBE0_STEPS, 0, true>), dim3(64 * gm, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P);
-                hipLaunchKernelGGL((k_probe<PROBE1_STEPS, 1, true>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P);
-            }
+            if (c->probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
+                hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(c->probe_refill, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
+                                   (const uint4 *)c->d_probe_tables);
+            else
+                hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
+                                   (const uint4 *)c->d_probe_tables);
             const int wb3 = c->walk2_div > 0 ? (wb / c->walk2_div > 0 ? wb / c->walk2_div : 1) : wb2;
-            if (c->surv_walk_old)
-                hipLaunchKernelGGL(k_walk_full<2>, dim3(wb3, Fs), dim3(64 * WALK_WAVES), 0, sa, masks, surv, wres, tab, pool, segs, pend, counts,
-                                   c->d_global, P);
-            else  // (FID_SURV_WALK=new: the survivors on the seed walker's prefetched windows)
-                hipLaunchKernelGGL(k_seed_walk<true>, dim3(c->surv_blocks_x > 0 ? wb3 * (WALK_WAVES / SW_WAVES) * c->surv_blocks_x : wb3, Fs), dim3(64 * SW_WAVES), 0, sa, masks,
-                                   (const uint2 *)surv, tab, pool, (DevSegC *)nullptr, counts, c->d_global, P, wres, pend);
+            hipLaunchKernelGGL(k_walk_full<2>, dim3(wb3, Fs), dim3(64 * WALK_WAVES), 0, sa, masks, surv, wres, tab, pool, segs, pend, counts,
+                               c->d_global, P);
             if (si != sa) HIPCHK(c, hipStreamWaitEvent(sa, c->aux_idx[sb], 0));  // (the survivors' seed look-ups need the map)
-            hipLaunchKernelGGL(k_seg_cycles<0>, dim3(8 * gm, Fs), dim3(64), 0, sa, seedq, (const DevSegC *)segs, pend, wres, contours, cinfo, cbase,
+            hipLaunchKernelGGL(k_seg_cycles<0>, dim3(8 * gm, Fs), dim3(64), 0, sa, seedq, segs, pend, wres, contours, cinfo, cbase,
                                recs, counts, c->d_global, P, 1, 0);
             hipLaunchKernelGGL(k_seg_copy, dim3(cpb / 4 > 0 ? cpb / 4 : 1, Fs), dim3(256), 0, sa, recs, tab, pool, dense, counts, P, 1);
             fid_launch_log("k_approx", 64, (size_t)(lds1));
@@ -789,15 +762,15 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             HIPCHK(c, hipEventRecord(c->aux_join[sb], sa));
             // -- main stream, continued
             HIPCHK(c, hipStreamWaitEvent(st, c->aux_idx[sb], 0));
-            hipLaunchKernelGGL(k_seg_link2, dim3(16 * gm, Fs), dim3(256), 0, st, seedq, (DevSegC *)segs, seedhash, counts, P);
+            hipLaunchKernelGGL(k_seg_link2, dim3(16 * gm, Fs), dim3(256), 0, st, seedq, segs, seedhash, counts, P);
             // (a call of one or two frames: a lane for every seed at once -- a workgroup that came round to a second 64 seeds walked a
             //  second longest cycle behind the first, 2 x 26 us of the single frame's 55 us)
             const int scb = Fs <= 2 ? (int)((P.maxContours + 63) / 64 < 4096 ? (P.maxContours + 63) / 64 : 4096) : 32 * gm * c->light_x;
             if (Fs <= 2)
-                hipLaunchKernelGGL(k_seg_cycles<48>, dim3(scb, Fs), dim3(64), 0, st, seedq, (const DevSegC *)segs, pend, wres, contours, cinfo, cbase,
+                hipLaunchKernelGGL(k_seg_cycles<48>, dim3(scb, Fs), dim3(64), 0, st, seedq, segs, pend, wres, contours, cinfo, cbase,
                                    recs, counts, c->d_global, P, 0, getenv("FID_NO_SEGC_WARM") ? 0 : 1);
             else
-                hipLaunchKernelGGL(k_seg_cycles<0>, dim3(scb, Fs), dim3(64), 0, st, seedq, (const DevSegC *)segs, pend, wres, contours, cinfo, cbase,
+                hipLaunchKernelGGL(k_seg_cycles<0>, dim3(scb, Fs), dim3(64), 0, st, seedq, segs, pend, wres, contours, cinfo, cbase,
                                    recs, counts, c->d_global, P, 0, 0);
             hipLaunchKernelGGL(k_seg_copy, dim3(cpb, Fs), dim3(256), 0, st, recs, tab, pool, dense, counts, P, 0);
             mark(ST_WALK + 1);
@@ -819,38 +792,6 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             } else {
                 HIPCHK(c, hipStreamWaitEvent(st, c->aux_join[sb], 0));
             }
-          } else {
-            // the seed walk needs only the seeds: it runs on its own stream beside the probe passes and the survivor walk
-            // (both walks are a throughput phase followed by a tail of a few long walkers; side by side the tails overlap)
-            hipStream_t sa = c->aux_stream[sb];
-            HIPCHK(c, hipEventRecord(c->aux_fork[sb], st));
-            HIPCHK(c, hipStreamWaitEvent(sa, c->aux_fork[sb], 0));
-            if (c->profile) (void)hipEventRecord(ev[14], sa);
-            hipLaunchKernelGGL(k_walk_full<1>, dim3(wb2, Fs), dim3(64 * WALK_WAVES), 0, sa, masks, seedq, wres, tab, pool, segs, pend, counts,
-                               c->d_global, P);
-            if (c->profile) (void)hipEventRecord(ev[15], sa);
-            HIPCHK(c, hipEventRecord(c->aux_join[sb], sa));
-            hipLaunchKernelGGL((k_probe<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, st, masks, starts, surv1, counts, c->d_global, P);
-            hipLaunchKernelGGL((k_probe<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, st, masks, surv1, surv, counts, c->d_global, P);
-            mark(ST_PROBE + 1);
-            hipLaunchKernelGGL(k_walk_full<2>, dim3(wb2, Fs), dim3(64 * WALK_WAVES), 0, st, masks, surv, wres, tab, pool, segs, pend, counts,
-                               c->d_global, P);
-            HIPCHK(c, hipStreamWaitEvent(st, c->aux_join[sb], 0));
-            hipLaunchKernelGGL(k_seed_index, dim3(8 * gm, Fs), dim3(256), 0, st, seedq, seedhash, counts, P);
-            hipLaunchKernelGGL(k_seg_link, dim3(16 * gm, Fs), dim3(256), 0, st, seedq, segs, surv, pend, seedhash, counts, c->d_global, P);
-            uint4 *recs = c->d_recs + 2 * f0 * MCn;
-            hipLaunchKernelGGL(k_seg_chain, dim3(16 * gm, Fs), dim3(64), 0, st, surv, pend, wres, segs, contours, cinfo, cbase, recs, counts,
-                               c->d_global, P);
-            hipLaunchKernelGGL(k_seg_copy, dim3(c->copy_blocks > 0 ? c->copy_blocks : 256, Fs), dim3(256), 0, st, recs, tab, pool, dense, counts, P, -1);
-            mark(ST_WALK + 1);
-            fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, c->d_global, P, cap1,
-                               K4_SHORT_STACK, 0, dense, cbase);
-            fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, c->d_global, P,
-                               P.maxPerim + 1, K4_LONG_STACK, 1, dense, cbase);
-            mark(ST_APPROX + 1);
-          }
         }
         if (nsub > 1 && c->stagger > 0) HIPCHK(c, hipEventRecord(c->walk_done[sb], st));
         chain_point(4);
@@ -976,11 +917,11 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
                 float ms = 0.f;
                 if (hipEventElapsedTime(&ms, c->sub_ev[sb][i], c->sub_ev[sb][i + 1]) == hipSuccess) c->stage_ms[i] += ms;
             }
-        if (c->trace_mode >= 1)  // the seed walk runs on the auxiliary streams, beside walk_probe and part of walk_full
+        if (!c->whole_border_walk)  // the seed walk, and the seedless chain beside it on the auxiliary streams
             for (int sb = 0; sb < c->last_nsub; sb++) {
                 float ms = 0.f;
                 if (hipEventElapsedTime(&ms, c->sub_ev[sb][14], c->sub_ev[sb][15]) == hipSuccess) c->stage_ms[ST_SEEDWALK] += ms;
-                if (c->trace_mode == 2 && hipEventElapsedTime(&ms, c->sub_ev[sb][16], c->sub_ev[sb][17]) == hipSuccess) c->stage_ms[ST_SEEDLESS] += ms;
+                if (hipEventElapsedTime(&ms, c->sub_ev[sb][16], c->sub_ev[sb][17]) == hipSuccess) c->stage_ms[ST_SEEDLESS] += ms;
                 if (c->pose_cam_valid && hipEventElapsedTime(&ms, c->sub_ev[sb][18], c->sub_ev[sb][19]) == hipSuccess) c->stage_ms[ST_POSE] += ms;
             }
     }
@@ -1001,7 +942,7 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
                     (double)d[21] / d[1], (double)d[22] / d[1], (double)d[23] / d[1], (double)d[24] / d[1]);
     }
 #endif
-    if (c->trace_mode >= 1 && (c->h_global->overflow & (2u | 8u))) {
+    if (!c->whole_border_walk && (c->h_global->overflow & (2u | 8u))) {
         // the tracing seeds and their points scale with the total border length of the frame, texture included: when they
         // do not fit max_contours_per_frame / max_points_per_frame, trace this call with the whole-border walk, which only
         // needs room for the probe survivors
@@ -1009,28 +950,23 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
             fprintf(stderr, "fid: seed tracing overflow flags 0x%x (frame 0: seeds %d starts %d surv %d chunks %d; maxContours %d maxChunks %d shift %d): whole-border walk\n",
                     c->h_global->overflow, c->h_counts[0].nseeds, c->h_counts[0].nstarts, c->h_counts[0].nsurv, c->h_counts[0].npool, c->P.maxContours,
                     c->P.maxChunks, c->P.seedShift);
-        const int tm = c->trace_mode;
-        c->trace_mode = 0;
+        c->whole_border_walk = true;
         c->fallbacks++;
         const fid_ctx::Pending pd = c->pend;
         const fid_status rc2 = run_detect(c, pd.d_src, pd.F, pd.W, pd.H, pd.stride, pd.fstride, pd.enc, out, cap_per_frame, n_per_frame);
-        c->trace_mode = tm;
+        c->whole_border_walk = false;
         return rc2;
     }
     fid_status rc = FID_OK;
     if (c->h_global->overflow) {
         const unsigned ov = c->h_global->overflow;
-        if (ov & 16u) {
-            c->last_error = "internal error: broken segment chain";
-        } else {
-            // which table: so that the caller knows which limit to raise
-            c->last_error = "internal capacity exceeded:";
-            if (ov & 1u) c->last_error += " max_starts_per_frame";
-            if (ov & 2u) c->last_error += " max_contours_per_frame";
-            if (ov & 4u) c->last_error += " approximation stack";
-            if (ov & 8u) c->last_error += " max_points_per_frame";
-            c->last_error += " (raise fid_limits)";
-        }
+        // which table: so that the caller knows which limit to raise
+        c->last_error = "internal capacity exceeded:";
+        if (ov & 1u) c->last_error += " max_starts_per_frame";
+        if (ov & 2u) c->last_error += " max_contours_per_frame";
+        if (ov & 4u) c->last_error += " approximation stack";
+        if (ov & 8u) c->last_error += " max_points_per_frame";
+        c->last_error += " (raise fid_limits)";
         rc = FID_E_CAPACITY;
     }
     for (int f = 0; f < F; f++) {
@@ -1180,13 +1116,10 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
         c->resolve_reg_max = v < 0 ? 0 : (v > 64 ? 64 : v);
     }
     if (getenv("FID_COPY_BLOCKS")) c->copy_blocks = atoi(getenv("FID_COPY_BLOCKS"));
-    if (getenv("FID_THR")) c->thr_mode = strcmp(getenv("FID_THR"), "tile") ? 1 : 0;
     if (getenv("FID_THR_NW")) c->thr_nw = atoi(getenv("FID_THR_NW")) == 3 ? 3 : 5;
     if (getenv("FID_THR_SPLIT")) c->thr_split = atoi(getenv("FID_THR_SPLIT")) != 0;
     if (getenv("FID_THR_ROWS")) c->thr_rows = atoi(getenv("FID_THR_ROWS"));
     if (getenv("FID_THR_XCD")) c->thr_xcd = atoi(getenv("FID_THR_XCD")) != 0;
-    if (getenv("FID_SURV_WALK")) c->surv_walk_old = !strcmp(getenv("FID_SURV_WALK"), "old");
-    if (getenv("FID_SURV_BLOCKS_X")) c->surv_blocks_x = atoi(getenv("FID_SURV_BLOCKS_X"));  // (0: half as many waves as k_walk_full<2> had)
     if (getenv("FID_WALK_BLOCKS")) c->walk_blocks = atoi(getenv("FID_WALK_BLOCKS")) > 0 ? atoi(getenv("FID_WALK_BLOCKS")) : c->walk_blocks;
     memset(&c->P, 0, sizeof(c->P));
 
@@ -1254,13 +1187,11 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     TRY(dalloc(c, &c->d_surv, F * L.max_starts_per_frame));
     c->max_chunks = (L.max_points_per_frame + CK - 1) / CK;
     TRY(dalloc(c, &c->d_pool, F * (size_t)c->max_chunks * CKW));
-    c->trace_mode = 2;
-    if (const char *tm = getenv("FID_TRACE")) c->trace_mode = !strcmp(tm, "legacy") ? 0 : !strcmp(tm, "chain") ? 1 : 2;
+    c->whole_border_walk = getenv("FID_TRACE") && !strcmp(getenv("FID_TRACE"), "legacy");
     if (getenv("FID_SW_BLOCKS")) c->sw_blocks = atoi(getenv("FID_SW_BLOCKS"));
     if (getenv("FID_STAGGER")) c->stagger = atoi(getenv("FID_STAGGER"));
     if (getenv("FID_PIECES")) c->pieces = atoi(getenv("FID_PIECES"));
     if (getenv("FID_FS_BARRIER")) c->fs_barrier = atoi(getenv("FID_FS_BARRIER"));
-    if (getenv("FID_PROBE_LUT")) c->probe_lut = atoi(getenv("FID_PROBE_LUT"));
     if (getenv("FID_TAIL_GRID")) c->tail_grid = atoi(getenv("FID_TAIL_GRID"));
     if (getenv("FID_FILTER_LDS")) c->filter_lds = atoi(getenv("FID_FILTER_LDS")) > 0 ? atoi(getenv("FID_FILTER_LDS")) : 1;
     if (getenv("FID_LIGHT_X")) c->light_x = atoi(getenv("FID_LIGHT_X")) > 0 ? atoi(getenv("FID_LIGHT_X")) : 1;
@@ -1269,8 +1200,7 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     if (getenv("FID_PROBE_REFILL")) c->probe_refill = atoi(getenv("FID_PROBE_REFILL"));
     if (getenv("FID_PROBE_REFILL0")) c->probe_refill0 = atoi(getenv("FID_PROBE_REFILL0"));
     if (getenv("FID_CHAIN_AT")) c->chain_at = atoi(getenv("FID_CHAIN_AT"));
-    static_assert(sizeof(DevSegC) == sizeof(DevSeg), "the two segment records share one buffer");
-    if (c->trace_mode >= 1) {
+    if (!c->whole_border_walk) {
         TRY(dalloc(c, &c->d_segs, F * L.max_contours_per_frame));
         TRY(dalloc(c, &c->d_pend, F * L.max_contours_per_frame));
         TRY(dalloc(c, &c->d_seedq, F * L.max_contours_per_frame));
@@ -1317,8 +1247,6 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     TRYHIP(hipMemset(c->d_masks, 0, c->masks_bytes));
     // opt in to large dynamic LDS where needed
     TRYHIP(hipFuncSetAttribute((const void *)k_threshold<TX, TY, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-    TRYHIP(hipFuncSetAttribute((const void *)k_threshold_fixed<3, 4, 13>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)ThrCfg<3, 4, 13>::LDS_BYTES));
     TRYHIP(hipFuncSetAttribute((const void *)k_approx, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
     TRYHIP(hipFuncSetAttribute((const void *)k_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     TRYHIP(hipFuncSetAttribute((const void *)k_threshold_wide<THRW_NT, THRW_WT>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1841,7 +1769,7 @@ fid_status fid_tap_read(fid_ctx *c, fid_tap which, void *dst, int64_t dst_bytes)
         int32_t *o = (int32_t *)dst;
         for (int f = 0; f < F; f++) {
             o[12 * f + 0] = c->h_counts[f].nstarts;
-            o[12 * f + 1] = c->trace_mode == 0 ? (c->h_counts[f].nsurv < c->P.maxContours ? c->h_counts[f].nsurv : c->P.maxContours) : c->h_counts[f].ncontours + c->h_counts[f].ncontours2;
+            o[12 * f + 1] = c->whole_border_walk ? (c->h_counts[f].nsurv < c->P.maxContours ? c->h_counts[f].nsurv : c->P.maxContours) : c->h_counts[f].ncontours + c->h_counts[f].ncontours2;
             o[12 * f + 10] = c->h_counts[f].nseeds;
             o[12 * f + 2] = c->h_counts[f].ncand;
             o[12 * f + 3] = c->h_counts[f].nfilt;

@@ -113,8 +113,7 @@ struct DevIdent {  // (the cell bits of a candidate are in their own array, [F][
 // component (d in E, NE, NW, W, SW, SE), or a row y = 0 (mod G) entered with a vertical component (d in NE, N, NW, SW, S, SE) --
 // and the neighbour X(d) that border following must have found empty on the way in (the one "to the right of travel":
 // direction d+2 for an axis move, d+1 for a diagonal one) is background.  Every seed follows its border only to the next
-// seed state (a SEGMENT); a probe survivor follows its border only to the first seed state and the rest of the border is read
-// off the segment chain.
+// seed state (a SEGMENT), and a border that has a seed state is read off its cycle of segments.
 // Why grid lines: a border cannot move G pixels in x or in y without stepping onto one, so the seed-free stretches are
 // BOUNDED (about 2 G steps for anything but a border that curls up inside one G x G cell) -- the longest sequential piece of
 // the whole tracing.  (Round 1 / early round 2 used a thinning lattice, one class per pixel: same seed count, but the gaps
@@ -136,16 +135,8 @@ __host__ __device__ inline uint32_t seed_key(int x, int y, int d) { return (uint
 // the neighbour direction that is empty when a state with back direction d was entered
 __host__ __device__ inline int seed_empty_dir(int d) { return (d + ((d & 1) ? 1 : 2)) & 7; }
 #define SEG_INVALID 0xffffffffu
-struct DevSeg {           // one per seed
-    uint32_t next_key;    // the seed state the segment ran into: x | y << 13 | d << 26 (same scale)
-    uint32_t next_idx;    // ... and that seed's index (filled in by k_seg_link)
-    uint32_t n;           // states in the segment (SEG_INVALID: longer than maxPerimeterPixels / pool exhausted)
-    uint32_t mout;        // min raster index (pidx) over the segment's pixels
-    uint32_t mhole;       // min raster index over the background 4-neighbours its searches passed over
-    uint32_t pad[3];
-};
-// Trace mode 2 ("cycle tracing"): the segment record of a seed when the contours are read off the seed cycles alone (no probe
-// survivor needed for a border that has a seed).  Same size as DevSeg: the two share their buffer.
+// Cycle tracing: the segment record of a seed.  The contours of the borders that have a seed are read off the seed cycles alone
+// (no probe survivor needed for them).
 //   ko / kh: the smallest discovery key among the segment's states that START a border the way cvFindNextContour /
 //   icvFetchContour would (outer: W neighbour background and back direction = first foreground clockwise from NW, key = raster
 //   index of the pixel; hole: E neighbour background and back direction = first foreground clockwise from SE, key = raster index
@@ -165,7 +156,7 @@ struct DevSegC {
 struct DevPend {          // one per probe survivor that stopped in front of a seed state
     uint32_t p;           // states it walked itself (0 = not stopped: the survivor closed or died on its own)
     uint32_t next_key;    // that seed state: x | y << 13 | d << 26
-    uint32_t next_idx;    // its seed index (k_seg_link)
+    uint32_t next_idx;    // (not used)
     uint32_t pad;
 };
 
@@ -185,8 +176,8 @@ struct DevCounts {
     int ndense;     // contour points copied to the dense point array so far
     int nseeds;     // seeds found by k_find_starts<true>
     int nwalk2;     // work queue head of the seed walker
-    int nrec;       // copy records written by k_seg_chain / k_seg_cycles (pieces of accepted contours)
-    int ncontours2; // trace mode 2: contours of the borders WITHOUT a seed (second list: [maxContours / 2, maxContours) of the frame's
+    int nrec;       // copy records written by k_seg_cycles (pieces of accepted contours)
+    int ncontours2; // cycle tracing: contours of the borders WITHOUT a seed (second list: [maxContours / 2, maxContours) of the frame's
     int nrec2;      //   contour arrays, second half of its record array), traced on the auxiliary stream beside the seed cycles
     int pad[15];
 };

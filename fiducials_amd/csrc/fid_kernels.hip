@@ -4,12 +4,14 @@
 //
 //   K0 k_to_gray        a2  bgr8/rgb8 -> gray (15-bit fixed point), or stride compaction
 //   K1 k_threshold_stream (node table) / k_threshold (rmax <= 40) / k_threshold_wide (any window)   a3  the scales from one
-//                       pass over the image, bit-packed tiled masks out; k_threshold_fixed = the round-1 tile kernel (FID_THR=tile)
+//                       pass over the image, bit-packed tiled masks out
 //   K2 k_find_starts    a4  border-following start points and tracing seeds by bit-parallel tests on mask words
-//   K3 k_probe<6>, <32> a4  one lane per start: a few steps of Suzuki-Abe border following sieve the starts
-//      k_walk_full<1>, <2>  persistent walkers on private LDS windows: seeds follow their segment, probe survivors walk to the
-//                       first seed (<0>: whole borders, FID_TRACE=legacy); points go to pool chunks as they are found
-//      k_seg_link / k_seg_chain / k_seg_copy   segment chains -> accepted contours -> dense point arrays
+//   K3 k_seed_walk      a4  persistent walkers on private LDS windows: every seed follows its segment to the next seed state;
+//                       points go to pool chunks as they are found
+//      k_probe_lut / k_probe_refill   one lane per start: a few steps of Suzuki-Abe border following sieve the starts of
+//                       the borders without a seed state; k_walk_full<2> walks the survivors
+//      k_seg_link2 / k_seg_cycles / k_seg_copy   segment cycles -> accepted contours -> dense point arrays
+//      (FID_TRACE=legacy, and the fallback when the seed tables overflow: k_probe<6>, <32> + k_walk_full<0>, whole borders)
 //   K4 k_approx         a4  one wave per accepted contour: approxPolyDP in OpenCV's slice order, quad gates
 //   K5 k_sort_cands / k_near / k_resolve   a5  OpenCV order, corner reorder, too-close filter
 //   K6 k_identify       a6/a7 one wave per candidate: homography (LU on 64 lanes), unwarp, Otsu, bits, Hamming
@@ -488,14 +490,6 @@ __global__ __launch_bounds__(NT) void k_threshold_wide(const uint8_t *__restrict
     }
 }
 
-// v_writelane_b32: park a wave-uniform value in lane K of a VGPR (one VALU op, no exec juggling)
-template <int K>
-__device__ __forceinline__ uint32_t write_lane(uint32_t val, uint32_t old)
-{
-    asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(old) : "s"(val), "n"(K));
-    return old;
-}
-
 template <int... Ks, typename F>
 __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Ks...>, F &&f)
 {
@@ -505,185 +499,6 @@ template <int N, typename F>
 __device__ __forceinline__ void static_for(F &&f)
 {
     static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F &&>(f));
-}
-
-// ------------------------------------------------------------------------------------------------
-// K1 (fast path): the same arithmetic for the window table WMIN, WMIN + WSTEP, ... (NS windows) fixed at
-// compile time -- the node-default table 3, 7, ..., 51 (aruco_detect.cpp:690-693) -- so that every integral
-// corner is one ds_read_b32 with an immediate offset.
-//   tile          TX x TY = 128 x 120 output pixels per 1024-thread workgroup (16 waves, one workgroup per CU:
-//                 the (TY + 2R + 1) x PT u32 integral takes 128.6 KB of the 160 KB LDS); halo re-read 1.97x
-//   phase 1       wave per raw row: one dword (4 px) per lane, 4-px local prefix + wave scan -> row prefix in LDS
-//   phase 2       column prefix in two levels (5 row chunks x 184 columns, 34 values in registers per thread)
-//   phase 3       wave per (row, 64-px segment): per scale 4 LDS reads, 2*sum >= t2*win^2, v_cmp = the mask
-//                 word pair; ballots are parked in lane k of the accumulators; each lane then stores its row's
-//                 four words per scale into the tiled mask layout
-template <int WMIN, int WSTEP, int NS>
-struct ThrCfg {
-    static constexpr int TX = 128, TY = 120, NT = 1024, NW = NT / 64;
-    static constexpr int R = (WMIN + (NS - 1) * WSTEP) / 2;  // largest radius
-    static constexpr int HL = (R + 3) & ~3;                  // left halo, dword aligned
-    static constexpr int RAWW = (HL + TX + R + 3) & ~3;      // raw columns loaded per row
-    static constexpr int NDW = RAWW / 4;                     // dwords per raw row (<= 64)
-    static constexpr int RAWH = TY + 2 * R;                  // raw rows
-    static constexpr int PT = RAWW + 4;                      // integral pitch (column 0 = zero column)
-    static constexpr int NCH = 5;                            // row chunks of the column prefix
-    static constexpr int CH = (RAWH + NCH - 1) / NCH;
-    static constexpr int ROWS_PER_WAVE = (RAWH + NW - 1) / NW;
-    static constexpr int ITEMS = (TY + NW - 1) / NW;         // output rows per wave
-    static constexpr size_t LDS_BYTES = (size_t)((RAWH + 1) * PT + NCH * RAWW) * sizeof(uint32_t);
-    static_assert(NDW <= 64, "one dword per lane");
-    static_assert(NCH * RAWW <= NT, "column-prefix threads");
-};
-
-template <int WMIN, int WSTEP, int NS>
-__global__ __launch_bounds__(1024) void k_threshold_fixed(const uint8_t *__restrict__ gray, long long gfstride,
-                                                           uint32_t *__restrict__ masks, const DevParams P)
-{
-    using C = ThrCfg<WMIN, WSTEP, NS>;
-    constexpr int TX = C::TX, TY = C::TY, NW = C::NW, R = C::R, HL = C::HL, RAWW = C::RAWW, NDW = C::NDW, RAWH = C::RAWH,
-                  PT = C::PT, NCH = C::NCH, CH = C::CH;
-    extern __shared__ uint32_t I[];       // (RAWH + 1) x PT, I[j][i] = sum of raw rows < j, raw cols < i
-    uint32_t *tot = I + (RAWH + 1) * PT;  // NCH x RAWW chunk totals
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY, f = blockIdx.z;
-    const uint8_t *g = gray + (long long)f * gfstride;
-    const int W = P.W, H = P.H, gs = P.gstride;
-
-    // this wave's output rows: ty = wid + NW * k; their centre pixels are fetched now, used in phase 3
-    uint32_t gpix[C::ITEMS][2];
-#pragma unroll
-    for (int k = 0; k < C::ITEMS; k++) {
-        int gy = y0 + wid + NW * k;
-        gy = gy < H ? gy : H - 1;
-#pragma unroll
-        for (int sg = 0; sg < 2; sg++) {
-            int gx = x0 + sg * 64 + lane;
-            gx = gx < W ? gx : W - 1;
-            gpix[k][sg] = g[(long long)gy * gs + gx];
-        }
-    }
-    // zero row / zero column
-    for (int i = tid; i < PT; i += C::NT) I[i] = 0;
-    for (int i = tid; i <= RAWH; i += C::NT) I[i * PT] = 0;
-    // ---- phase 1: row prefix
-    {
-        const bool fast = ((((uintptr_t)g) | (unsigned)gs) & 3) == 0 && x0 - HL >= 0 && x0 - HL + RAWW <= W;
-        uint32_t raw[C::ROWS_PER_WAVE];
-#pragma unroll
-        for (int k = 0; k < C::ROWS_PER_WAVE; k++) {
-            int ry = wid + NW * k;
-            int gy = y0 - R + ry;
-            gy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy);
-            const uint8_t *grow = g + (long long)gy * gs;
-            uint32_t v = 0;
-            if (ry < RAWH && lane < NDW) {
-                int gx = x0 - HL + 4 * lane;
-                if (fast) {
-                    v = *reinterpret_cast<const uint32_t *>(grow + gx);
-                } else {
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        int xx = gx + b;
-                        xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-                        v |= (uint32_t)grow[xx] << (8 * b);
-                    }
-                }
-            }
-            raw[k] = v;
-        }
-#pragma unroll
-        for (int k = 0; k < C::ROWS_PER_WAVE; k++) {
-            int ry = wid + NW * k;
-            if (ry >= RAWH) break;  // wave-uniform
-            uint32_t v = raw[k];
-            int p0 = v & 0xff, p1 = p0 + ((v >> 8) & 0xff), p2 = p1 + ((v >> 16) & 0xff), p3 = p2 + (v >> 24);
-            int e = wave_iscan(p3) - p3;
-            if (lane < NDW) {
-                uint32_t *dst = I + (ry + 1) * PT + 1 + 4 * lane;
-                dst[0] = (uint32_t)(e + p0);
-                dst[1] = (uint32_t)(e + p1);
-                dst[2] = (uint32_t)(e + p2);
-                dst[3] = (uint32_t)(e + p3);
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase 2: column prefix, chunk j of CH rows x column c per thread
-    {
-        const int c = tid % RAWW, j = tid / RAWW;
-        const bool act = tid < NCH * RAWW;
-        uint32_t v[CH];
-        uint32_t *col = I + (1 + j * CH) * PT + 1 + c;
-        if (act) {
-#pragma unroll
-            for (int k = 0; k < CH; k++) v[k] = (j * CH + k < RAWH) ? col[k * PT] : 0u;
-#pragma unroll
-            for (int k = 1; k < CH; k++) v[k] += v[k - 1];
-            tot[j * RAWW + c] = v[CH - 1];
-        }
-        __syncthreads();
-        if (act) {
-            uint32_t off = 0;
-#pragma unroll
-            for (int q = 0; q < NCH - 1; q++) off += q < j ? tot[q * RAWW + c] : 0u;
-#pragma unroll
-            for (int k = 0; k < CH; k++)
-                if (j * CH + k < RAWH) col[k * PT] = v[k] + off;
-        }
-    }
-    __syncthreads();
-    // ---- phase 3: all scales for this wave's rows
-    uint4 acc[NS];
-#pragma unroll
-    for (int s = 0; s < NS; s++) acc[s] = make_uint4(0u, 0u, 0u, 0u);
-    static_for<C::ITEMS>([&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        const int ty = wid + NW * k;
-        if (ty < TY) {  // wave-uniform
-#pragma unroll
-            for (int sg = 0; sg < 2; sg++) {
-                const int x = sg * 64 + lane;
-                const int t2 = 2 * ((int)gpix[k][sg] + P.idelta) - 1;
-                const unsigned long long vmask = ballot64(x0 + x < W);
-                // base = I[ry - R][cx - R] with ry = ty + R, cx = x + HL (raw coordinates of the pixel)
-                const uint32_t *base = I + ty * PT + (x + HL - R);
-#pragma unroll
-                for (int s = 0; s < NS; s++) {
-                    const int win = WMIN + s * WSTEP, r = win >> 1;
-                    const int o_tl = (R - r) * PT + (R - r), o_tr = (R - r) * PT + (R + r + 1);
-                    const int o_bl = (R + r + 1) * PT + (R - r), o_br = (R + r + 1) * PT + (R + r + 1);
-                    int sum = (int)(base[o_br] - base[o_tr] - base[o_bl] + base[o_tl]);
-                    unsigned long long b = ballot64(2 * sum >= __mul24(t2, win * win)) & vmask;
-                    uint32_t lo = (uint32_t)b, hi = (uint32_t)(b >> 32);
-                    if (sg == 0) {
-                        acc[s].x = write_lane<k>(lo, acc[s].x);
-                        acc[s].y = write_lane<k>(hi, acc[s].y);
-                    } else {
-                        acc[s].z = write_lane<k>(lo, acc[s].z);
-                        acc[s].w = write_lane<k>(hi, acc[s].w);
-                    }
-                }
-            }
-        }
-    });
-    // lane k holds row wid + NW * k: one 16-byte store per (row, scale)
-    {
-        const int ty = wid + NW * lane;
-        const int gy = y0 + ty;
-        if (lane < C::ITEMS && ty < TY && gy < H) {
-            const long long plane = (long long)P.TR * P.TC * MT_ROWS;
-            uint32_t *mrow = masks + (long long)f * NS * plane + mask_word(P.TC, gy + 1, MASK_PADW + (x0 >> 5));
-#pragma unroll
-            for (int s = 0; s < NS; s++) {
-                uint32_t *q = mrow + (long long)s * plane;  // the four words sit in four neighbouring tiles
-                q[0] = acc[s].x;
-                q[MT_ROWS] = acc[s].y;
-                q[2 * MT_ROWS] = acc[s].z;
-                q[3 * MT_ROWS] = acc[s].w;
-            }
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1058,7 +873,7 @@ __global__ __launch_bounds__(64 * (NW + 1)) void k_threshold_stream(const uint8_
 // ---- SeedHash: seed state -> seed index, one open-addressing table of 64-bit entries per frame.
 // entry = generation (10 bits, 54..63) | state (x | y << 13 | d << 26 | scale << 29: 34 bits, 20..53) | seed index (20 bits).
 // The generation is a per-call number (1..1023): entries of earlier calls count as empty, so the table is never cleared
-// between calls (the host clears it when the number wraps).  Inserts (k_seed_index) and lookups (k_seg_link) are in
+// between calls (the host clears it when the number wraps).  Inserts (k_seed_index) and lookups (k_seg_link2) are in
 // different kernels; the table holds at most maxContours entries in >= 2 maxContours slots.
 __device__ __forceinline__ unsigned long long seedhash_key(uint32_t state, int scale) { return (unsigned long long)state | ((unsigned long long)scale << 29); }
 __device__ __forceinline__ unsigned seedhash_slot(unsigned long long key, int cap)
@@ -1503,7 +1318,7 @@ __device__ __forceinline__ int pidx(int x, int y, int W) { return (y + 1) * (W +
 // record carries anyway.  0.5 + 1 bytes per point through HBM instead of 4 + 4 twice.
 #define CK 64
 #define CKW 8
-#define REC_NO_CHUNK 0xffffffffu  // copy record: the row's chunks are all in chunk_tab (probe survivors, trace mode 1)
+#define REC_NO_CHUNK 0xffffffffu  // copy record: the row's chunks are all in chunk_tab (probe survivors)
 // packed step of a chain code: dx + 65536 dy as a 32-bit integer (x + 65536 y is linear: sums of these are sums of steps)
 __device__ __forceinline__ uint32_t code_delta(unsigned c)
 {
@@ -1570,9 +1385,7 @@ __device__ __forceinline__ long long chunk_tab_at(const DevParams &P, int f, uns
 #ifndef PROBE1_STEPS
 #define PROBE1_STEPS 32
 #endif
-// STOPSEED (trace mode 2): a start whose walk meets a seed state is dropped -- its border is a seed cycle, k_seg_cycles
-// finds it without a start.
-template <int STEPS, int LEVEL, bool STOPSEED = false>
+template <int STEPS, int LEVEL>
 __global__ __launch_bounds__(256) void k_probe(const uint32_t *__restrict__ masks, const uint2 *__restrict__ in_list,
                                                 uint2 *__restrict__ out_list, DevCounts *__restrict__ counts,
                                                 DevGlobal *__restrict__ G, const DevParams P)
@@ -1599,8 +1412,6 @@ __global__ __launch_bounds__(256) void k_probe(const uint32_t *__restrict__ mask
         // canonical key: outer = own index, hole = index of the background pixel to the right
         const int key = hole ? pidx(x0 + 1, y0, W) : pidx(x0, y0, W);
         const int s_end = hole ? 0 : 4;
-        const int sgm = (8 << P.seedShift) - 1;
-        auto on_seed = [&](int x, int y, int d, unsigned nbh) { return seed_state(x, y, d, sgm) && !((nbh >> seed_empty_dir(d)) & 1u); };
         int count = 0, ok = active, closed = 0;
         unsigned nb = ok ? nb8(m, x0, y0) : 0u;
         if (!ok) {
@@ -1621,7 +1432,6 @@ __global__ __launch_bounds__(256) void k_probe(const uint32_t *__restrict__ mask
             // backward cursor starts on i1 with forward direction pointing at the start pixel
             int bx = i1x, by = i1y, bf = (sdir + 4) & 7;
             if (!hole && pidx(bx, by, W) < key) ok = 0;
-            if (STOPSEED && on_seed(x0, y0, sdir, nb)) ok = 0;  // the start state itself
             int cx = x0, cy = y0;
             while (ok) {
                 // ---- forward step: first foreground counter-clockwise from sdir + 1
@@ -1656,10 +1466,6 @@ __global__ __launch_bounds__(256) void k_probe(const uint32_t *__restrict__ mask
                 }
                 sdir = (sn + 4) & 7;
                 nb = nb8(m, cx, cy);
-                if (STOPSEED && on_seed(cx, cy, sdir, nb)) {
-                    ok = 0;
-                    break;
-                }
                 // ---- backward step: predecessor = first foreground clockwise from bf - 1
                 {
                     unsigned bn = nb8(m, bx, by);
@@ -1674,7 +1480,6 @@ __global__ __launch_bounds__(256) void k_probe(const uint32_t *__restrict__ mask
                         }
                     }
                     int bd = (c0 - tz) & 7;
-                    if (STOPSEED && on_seed(bx, by, bd, bn)) ok = 0;  // the state (pixel, back direction) the cursor stood in
                     bx += dir_dx(bd);
                     by += dir_dy(bd);
                     bf = (bd + 4) & 7;
@@ -1787,18 +1592,16 @@ __device__ __forceinline__ unsigned win_raw(const uint32_t *s_winw, int lane4, i
 }
 
 // MODE 0: a walker follows a whole border from a probe survivor and applies the canonical-start test as it goes.
-// MODE 1: a walker follows one SEGMENT, from its seed state to the next seed state, and records length and minima.
-// MODE 2: as MODE 0, but the walker stops in front of the first seed state it meets (k_seg_chain takes over from there).
+// MODE 2: as MODE 0, but the walker stops in front of the first seed state it meets (its seed cycle has the border already).
 template <int MODE>
 // Four independent walker waves per workgroup (one per SIMD: one-wave workgroups were all placed on the same SIMD of a
 // CU, which capped a CU at one SIMD's issue rate); they share nothing but the step table.
 #define WALK_WAVES 4
 __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *__restrict__ masks, const uint2 *__restrict__ surv,
                                                    uint4 *__restrict__ contours, uint32_t *__restrict__ chunk_tab,
-                                                   uint32_t *__restrict__ pool, DevSeg *__restrict__ segs, DevPend *__restrict__ pend,
+                                                   uint32_t *__restrict__ pool, DevSegC *__restrict__ segs, DevPend *__restrict__ pend,
                                                    DevCounts *__restrict__ counts, DevGlobal *__restrict__ G, const DevParams P)
 {
-    constexpr bool SEG = MODE == 1;
     // window: 64 px x 16 rows per lane = 2 word columns x 4 row quarters; chunk j = c * 4 + q (16 bytes = rows
     // 4q..4q+3 of word column c) of lane l lives at s_win[j * 64 + l].  8 KB per wave -> 16 waves per CU.
     __shared__ uint4 s_win_all[WALK_WAVES][8 * 64];
@@ -1831,22 +1634,22 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
         const uint2 *fin = surv;
         unsigned *qhead = nullptr;
         auto set_queue = [&](int fr) {
-            n = (unsigned)(SEG ? counts[fr].nseeds : counts[fr].nsurv);
+            n = (unsigned)counts[fr].nsurv;
             n = n < (unsigned)P.maxStarts ? n : (unsigned)P.maxStarts;
             if (n > ccap) {  // more walkers than contour rows: reported, never silently dropped
                 if (lane == 0) atomicOr(&G->overflow, 2u);
                 n = ccap;
             }
-            fin = surv + (long long)fr * (SEG ? P.maxContours : P.maxStarts);
-            qhead = (unsigned *)(SEG ? &counts[fr].nwalk2 : &counts[fr].nwalk);
+            fin = surv + (long long)fr * P.maxStarts;
+            qhead = (unsigned *)&counts[fr].nwalk;
         };
         set_queue(f);
         int all_done = 0;  // no frame of the launch has walkers waiting any more (wave-uniform)
-        // per-lane views of the walker's own frame lf: contour rows, chunk rows (seeds 0 .. maxContours-1, survivors
-        // maxContours .. 2 maxContours-1); point chunks are numbered across the whole launch
+        // per-lane views of the walker's own frame lf: contour rows, chunk rows (the survivors' rows maxContours .. 2 maxContours-1);
+        // point chunks are numbered across the whole launch
         int lf = f;
         auto fco_of = [&](int fr) { return contours + (long long)fr * P.maxContours; };
-        auto tab_at = [&](int fr, unsigned sl, unsigned k) -> uint32_t & { return chunk_tab[chunk_tab_at(P, fr, (SEG ? 0u : ccap) + sl, k)]; };
+        auto tab_at = [&](int fr, unsigned sl, unsigned k) -> uint32_t & { return chunk_tab[chunk_tab_at(P, fr, ccap + sl, k)]; };
         uint32_t *const fpool = pool;
         // the wave's current batch of the frame's survivor queue: [next, rend), records of batch base .. base + 63 in `pre`
         unsigned next = 0, rend = 0, pre_base = 0;  // wave-uniform
@@ -1865,9 +1668,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
         unsigned chunkA = 0, chunkB = 0;  // pool chunks of the even / odd 64-point blocks around `count`
         int kreg = 0;                     // highest block index that has a chunk
         unsigned ovf = 0;
-        unsigned mout = 0xffffffffu, mhole = 0xffffffffu;  // MODE 1: running minima of the segment
-        int too_long = 0, stopped = 0;
-        int brx = -1, bry = -1, brd = -1;  // MODE 1: state remembered for the cycle test
+        int stopped = 0;
         uint32_t acc = 0;  // the chain codes of the last (up to) eight points, oldest in the low nibble; every eighth step they leave as ONE word
         unsigned arena_next = 0, arena_end = 0;  // wave-uniform
 #ifdef FID_DEBUG_STATS
@@ -1907,14 +1708,13 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                     if (raw == 0) {
                         count = 1;  // (the contour's only point is its start: no step, no code)
                         closed = 1;
-                        mout = (unsigned)pc;
                         state = ST_FINAL;
                     } else {
-                        // a seed starts in its seed state; a survivor as icvFetchContour starts a border
-                        sdir = SEG ? (int)(st.y & 7u) : first_dir(raw_to_nb(raw), hole ? 0 : 4);
+                        // as icvFetchContour starts a border
+                        sdir = first_dir(raw_to_nb(raw), hole ? 0 : 4);
                         i1x = x0 + dir_dx(sdir);
                         i1y = y0 + dir_dy(sdir);
-                        if (!SEG && !hole && pidx(i1x, i1y, W) < key) {
+                        if (!hole && pidx(i1x, i1y, W) < key) {
                             ok = 0;
                             state = ST_FINAL;
                         }
@@ -1924,7 +1724,6 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
             if ((state == ST_ACTIVE || state == ST_NEED) && count > P.maxPerim) {
                 // checked here, not per step: a walk overshoots by at most WALK_RUN points
                 ok = 0;
-                too_long = 1;
                 state = ST_FINAL;
             }
 #ifdef FID_DEBUG_STATS
@@ -1937,21 +1736,13 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                     const int rem = count & 7, b0 = count - rem;
                     if (rem) fpool[((b0 & CK ? chunkB : chunkA) * CKW) + (unsigned)((b0 & (CK - 1)) >> 3)] = acc >> (4 * (8 - rem));
                 }
-                if (SEG) {
-                    DevSeg *r = segs + (long long)lf * P.maxContours + slot;
-                    r->next_key = seed_key(cx, cy, sdir);  // the seed state the walk stopped in front of
-                    r->n = too_long || !ok ? SEG_INVALID : (unsigned)count;
-                    r->mout = mout;
-                    r->mhole = mhole;
-                } else {
-                    // stopped in front of a seed state (MODE 2): k_seg_chain decides; else decided here
-                    const int accept = ok && closed && !stopped && count >= P.minPerim && count <= P.maxPerim;
-                    fco_of(lf)[slot] = make_uint4(st.x, st.y, accept ? (unsigned)count : 0u, (unsigned)key);
-                    if (MODE == 2) {
-                        DevPend *pd = pend + (long long)lf * P.maxContours + slot;
-                        pd->p = ok && stopped ? (unsigned)count : 0u;
-                        pd->next_key = seed_key(cx, cy, sdir);
-                    }
+                // stopped in front of a seed state (MODE 2): k_seg_cycles decides; else decided here
+                const int accept = ok && closed && !stopped && count >= P.minPerim && count <= P.maxPerim;
+                fco_of(lf)[slot] = make_uint4(st.x, st.y, accept ? (unsigned)count : 0u, (unsigned)key);
+                if (MODE == 2) {
+                    DevPend *pd = pend + (long long)lf * P.maxContours + slot;
+                    pd->p = ok && stopped ? (unsigned)count : 0u;
+                    pd->next_key = seed_key(cx, cy, sdir);
                 }
                 state = ST_IDLE;
 #ifdef FID_DEBUG_STATS
@@ -1979,9 +1770,8 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                     int fr = (f + hop + k) % F;
                     if (fr == f) fr = -1;
                     if (k < F && fr >= 0) {
-                        const unsigned done = __hip_atomic_load((unsigned *)(SEG ? &counts[fr].nwalk2 : &counts[fr].nwalk), __ATOMIC_RELAXED,
-                                                                __HIP_MEMORY_SCOPE_AGENT);
-                        unsigned m = (unsigned)(SEG ? counts[fr].nseeds : counts[fr].nsurv);
+                        const unsigned done = __hip_atomic_load((unsigned *)&counts[fr].nwalk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        unsigned m = (unsigned)counts[fr].nsurv;
                         m = m < (unsigned)P.maxStarts ? m : (unsigned)P.maxStarts;
                         m = m < ccap ? m : ccap;
                         has = done < m;
@@ -2027,21 +1817,10 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                         if (slot < ccap) {
                             lf = f;
                             st = make_uint2(gx, gy);
-                            int s;
-                            if (SEG) {  // x | y << 13 | scale << 27, back direction of the seed state
-                                x0 = gx & 0x1fff;
-                                y0 = (gx >> 13) & 0x1fff;
-                                hole = 0;
-                                s = gx >> 27;
-                                mout = mhole = 0xffffffffu;
-                                too_long = 0;
-                                brx = bry = brd = -1;
-                            } else {
-                                x0 = st.x & 0xffff;
-                                y0 = st.x >> 16;
-                                s = (st.y >> 16) & 0xff;
-                                hole = (st.y >> 24) & 1;
-                            }
+                            x0 = st.x & 0xffff;
+                            y0 = st.x >> 16;
+                            const int s = (st.y >> 16) & 0xff;
+                            hole = (st.y >> 24) & 1;
                             pl = masks + ((long long)f * S + s) * plane;
                             key = hole ? pidx(x0 + 1, y0, W) : pidx(x0, y0, W);
                             count = 0;
@@ -2088,12 +1867,8 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                         if (mine + 1 >= pcap) {
                             ovf |= 8u;
                             ok = 0;
-                            if (SEG) {
-                                segs[(long long)lf * P.maxContours + slot].n = SEG_INVALID;
-                            } else {
-                                fco_of(lf)[slot] = make_uint4(st.x, st.y, 0u, (unsigned)key);
-                                if (MODE == 2) pend[(long long)lf * P.maxContours + slot].p = 0u;
-                            }
+                            fco_of(lf)[slot] = make_uint4(st.x, st.y, 0u, (unsigned)key);
+                            if (MODE == 2) pend[(long long)lf * P.maxContours + slot].p = 0u;
                             state = ST_IDLE;
                         } else if (fresh) {
                             chunkA = mine;
@@ -2165,39 +1940,8 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
                     const int sn = e & 7, code = (e >> 3) & 7;
                     const int hmag = (code & 1) ? W2 : 1;
                     const int hoff = (code & 2) ? hmag : -hmag;
-                    if (SEG) {
-                        if (count > 0 && (e & 0x40u) && seed_state(cx, cy, sdir, sgm)) {
-                            closed = 1;  // the next seed state: the segment ends in front of it
-                            state = ST_FINAL;
-                        } else if (count > 0 && cx == brx && cy == bry && sdir == brd) {
-                            // Brent's cycle test: a seed that is not a real border state has walked into a border without
-                            // seeds and is going round it; nobody links to such a seed
-                            ok = 0;
-                            state = ST_FINAL;
-                        } else {
-                            if ((count & (count - 1)) == 0) {  // remember the state at every power of two
-                                brx = cx;
-                                bry = cy;
-                                brd = sdir;
-                            }
-                            const unsigned hv = code ? (unsigned)(pc + hoff) : 0xffffffffu;
-                            mhole = hv < mhole ? hv : mhole;
-                            mout = (unsigned)pc < mout ? (unsigned)pc : mout;
-                            acc = __builtin_amdgcn_alignbit((uint32_t)sn, acc, 4);
-                            if ((count & 7) == 7) fpool[((count & CK ? chunkB : chunkA) * CKW) + (unsigned)((count & (CK - 1)) >> 3)] = acc;
-                            count++;
-                            const int dx = dir_dx(sn), dy = dir_dy(sn);
-                            cx += dx;
-                            cy += dy;
-                            pc += __mul24(dy, W2) + dx;
-                            sdir = (sn + 4) & 7;
-                            ndx = dx;
-                            ndy = dy;
-                            const unsigned xr = (unsigned)(cx + (MASK_PADW * 32 - 1) - wx0), rr = (unsigned)(cy - wy0);
-                            state = (xr > 61u || rr > 13u) ? ST_NEED : ST_ACTIVE;
-                        }
-                    } else if (MODE == 2 && count > 0 && (e & 0x40u) && seed_state(cx, cy, sdir, sgm)) {
-                        stopped = 1;  // the first seed state on this border: the segment chain continues from here
+                    if (MODE == 2 && count > 0 && (e & 0x40u) && seed_state(cx, cy, sdir, sgm)) {
+                        stopped = 1;  // the first seed state on this border: its seed cycle has the border already
                         state = ST_FINAL;
                     } else {
                         // background pixels examined in the 4-directions belong to this border's hole region
@@ -2254,18 +1998,10 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *_
 }
 
 // ------------------------------------------------------------------------------------------------
-// Seed-accelerated tracing (k_find_starts<true> + k_walk_full<1>, <2> + the three passes below).
+// Seed-accelerated tracing (k_find_starts<true> + the seed walker and the segment passes below).
 // A border-following state is (pixel, direction back to the previous pixel); one step maps a state to the next one and does
 // not depend on how the walk was started, so a border is a cycle of states.  SEED states cut every cycle that contains some
-// into segments: seed i owns the states from its start state up to, not including, the next seed state.  The whole-border
-// walk of a probe survivor then only has to reach the first seed state on its border (it keeps applying the canonical
-// test on the way and closes by itself on a border without seeds); the rest comes from the segment records:
-//   k_seg_link     next seed state -> seed index (SeedHash) for every segment and every stopped survivor
-//   k_seg_chain    every stopped survivor: once around the seed cycle, summing lengths and taking the two running minima;
-//                  the acceptance test is the one the whole-border walk applies (no pixel -- outer -- or examined
-//                  background 4-neighbour -- hole -- with a raster index below the start's key; perimeter gate)
-//   k_seg_copy     the pieces of the accepted contours (the survivor's own points, then the segments in cycle order, the
-//                  last one cut where the survivor started; listed by k_seg_chain) into a dense array for k_approx
+// into segments: seed i owns the states from its start state up to, not including, the next seed state.
 // The longest sequential piece is the longest seed-free stretch of a border, not the longest border.
 
 // the frame's seed list -> SeedHash, one thread per seed (the inserts wait for their compare-and-swap: a kernel of its own
@@ -2285,163 +2021,17 @@ __global__ __launch_bounds__(256) void k_seed_index(const uint2 *__restrict__ se
     }
 }
 
-__global__ __launch_bounds__(256) void k_seg_link(const uint2 *__restrict__ seedq, DevSeg *__restrict__ segs,
-                                                   const uint2 *__restrict__ surv, DevPend *__restrict__ pend,
-                                                   const unsigned long long *__restrict__ seedhash, DevCounts *__restrict__ counts,
-                                                   DevGlobal *__restrict__ G, const DevParams P)
-{
-    const int f = blockIdx.y;
-    unsigned ns = (unsigned)counts[f].nseeds, nv = (unsigned)counts[f].nsurv;
-    ns = ns < (unsigned)P.maxContours ? ns : (unsigned)P.maxContours;
-    nv = nv < (unsigned)P.maxContours ? nv : (unsigned)P.maxContours;
-    const unsigned long long *fsh = seedhash + (long long)f * P.seedHashCap;
-    const uint2 *fsq = seedq + (long long)f * P.maxContours;
-    DevSeg *fsg = segs + (long long)f * P.maxContours;
-    const uint2 *fsv = surv + (long long)f * P.maxStarts;
-    DevPend *fpd = pend + (long long)f * P.maxContours;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < ns + nv; i += gridDim.x * blockDim.x) {
-        if (i < ns) {
-            const unsigned sc = fsq[i].x >> 27;
-            // (a segment that was abandoned -- too long, pool exhausted -- has no next seed)
-            const unsigned nx = fsg[i].n == SEG_INVALID ? SEG_INVALID
-                                                        : seedhash_find(fsh, P.seedHashCap, P.seedGen, seedhash_key(fsg[i].next_key, (int)sc));
-            fsg[i].next_idx = nx < ns ? nx : SEG_INVALID;  // (a seed beyond the table's capacity was reported by k_find_starts)
-        } else {
-            const unsigned j = i - ns;
-            if (fpd[j].p) {
-                const unsigned sc = (fsv[j].y >> 16) & 0xffu;
-                const unsigned nx = seedhash_find(fsh, P.seedHashCap, P.seedGen, seedhash_key(fpd[j].next_key, (int)sc));
-                fpd[j].next_idx = nx < ns ? nx : SEG_INVALID;
-            }
-        }
-    }
-}
-
-// stopped survivors: once around the seed cycle.  Accepted contours (also the ones k_walk_full<2> closed by itself, which
-// it appended already) end up in `contours` (start, meta, length, key) with {survivor index, own points, first seed}.
-// An accepted contour gets its place in the dense point array here (cbase) and goes round its cycle a second time to leave
-// one COPY RECORD per piece {chunk row, place in the dense array, points}: the survivor's own points, then the segments in
-// cycle order, the last one cut where the survivor started.  k_seg_copy moves the pieces, all of them in parallel (walking
-// the chain inside the copy kernel made one wave wait for two dependent loads per segment).
-__global__ __launch_bounds__(64) void k_seg_chain(const uint2 *__restrict__ surv, const DevPend *__restrict__ pend,
-                                                   const uint4 *__restrict__ wres, const DevSeg *__restrict__ segs,
-                                                   uint4 *__restrict__ contours,
-                                                   uint4 *__restrict__ cinfo, uint32_t *__restrict__ cbase, uint4 *__restrict__ recs,
-                                                   DevCounts *__restrict__ counts, DevGlobal *__restrict__ G, const DevParams P)
-{
-    const int f = blockIdx.y;
-    const int lane = lane_id();
-    unsigned nv = (unsigned)counts[f].nsurv;
-    nv = nv < (unsigned)P.maxContours ? nv : (unsigned)P.maxContours;
-    const uint2 *fsv = surv + (long long)f * P.maxStarts;
-    const DevPend *fpd = pend + (long long)f * P.maxContours;
-    const DevSeg *fsg = segs + (long long)f * P.maxContours;
-    uint4 *fco = contours + (long long)f * P.maxContours;
-    uint4 *fci = cinfo + (long long)f * P.maxContours;
-    uint32_t *fcb = cbase + (long long)f * P.maxContours;
-    uint4 *frc = recs + (long long)f * 2 * P.maxContours;
-    const unsigned dcap = (unsigned)P.maxChunks * CK, rcap = 2u * (unsigned)P.maxContours;
-    const int W = P.W;
-    for (unsigned i0 = blockIdx.x * 64; i0 < nv; i0 += gridDim.x * 64) {
-        const unsigned i = i0 + lane;
-        int accept = 0;
-        unsigned L = 0, key = 0, first = SEG_INVALID, own = 0, hops = 0;
-        uint2 st = make_uint2(0u, 0u);
-        if (i < nv) {
-            const DevPend pd = fpd[i];
-            if (!pd.p) {
-                // decided by the walker itself (a border without seeds): accepted iff it left a length
-                const uint4 w = wres[(long long)f * P.maxContours + i];
-                if (w.z) {
-                    st = make_uint2(w.x, w.y);
-                    L = own = w.z;
-                    key = w.w;
-                    accept = 1;
-                }
-            } else {
-                st = fsv[i];
-                const int x0 = st.x & 0xffff, y0 = st.x >> 16;
-                const int hole = (st.y >> 24) & 1;
-                key = (unsigned)(hole ? pidx(x0 + 1, y0, W) : pidx(x0, y0, W));
-                first = pd.next_idx;
-                own = pd.p;
-                unsigned cur = first;
-                for (int h = 0; h <= P.maxPerim && cur != SEG_INVALID; h++) {  // (every segment has >= 1 state)
-                    const DevSeg r = fsg[cur];
-                    if (r.n == SEG_INVALID || r.n == 0u) break;
-                    if ((hole ? r.mhole : r.mout) < key) break;  // a smaller key on the border: not the canonical start
-                    L += r.n;
-                    hops++;
-                    if (L > (unsigned)P.maxPerim) break;
-                    if (r.next_idx == first) {
-                        accept = L >= (unsigned)P.minPerim;
-                        break;
-                    }
-                    cur = r.next_idx;
-                }
-                if (first == SEG_INVALID) atomicOr(&G->overflow, 16u);  // a seed state without a seed: must not happen
-            }
-        }
-        const unsigned long long mk = ballot64(accept);
-        if (mk) {
-            // contour slots, dense points and copy records of the wave's accepted contours: one atomic each
-            // (a contour's codes start on a multiple of 8 bytes: k_approx reads them eight to a lane)
-            const unsigned myL = accept ? (L + 7u) & ~7u : 0u, myR = accept ? hops + 1u : 0u;
-            const unsigned sL = wave_iscan_dpp(myL), sR = wave_iscan_dpp(myR);
-            const unsigned totL = (unsigned)__builtin_amdgcn_readlane((int)sL, 63), totR = (unsigned)__builtin_amdgcn_readlane((int)sR, 63);
-            unsigned bslot = 0, bdense = 0, brec = 0;
-            if (lane == 63) {
-                bslot = atomicAdd((unsigned *)&counts[f].ncontours, (unsigned)__popcll(mk));
-                bdense = atomicAdd((unsigned *)&counts[f].ndense, totL);
-                brec = atomicAdd((unsigned *)&counts[f].nrec, totR);
-            }
-            bslot = (unsigned)__builtin_amdgcn_readlane((int)bslot, 63);
-            bdense = (unsigned)__builtin_amdgcn_readlane((int)bdense, 63);
-            brec = (unsigned)__builtin_amdgcn_readlane((int)brec, 63);
-            const unsigned idx = bslot + (unsigned)__popcll(mk & ((1ull << lane) - 1ull));
-            if (accept) {
-                if (idx < (unsigned)P.maxContours) {
-                    fco[idx] = make_uint4(st.x, st.y, L, key);
-                    fci[idx] = make_uint4(i, own, first, 0u);
-                    const unsigned dst0 = bdense + sL - myL;
-                    unsigned rec = brec + sR - myR;
-                    if (dst0 + L > dcap || rec + myR > rcap) {
-                        atomicOr(&G->overflow, 8u);
-                        fcb[idx] = SEG_INVALID;
-                    } else {
-                        fcb[idx] = dst0;
-                        frc[rec++] = make_uint4((unsigned)P.maxContours + i, dst0, own < L ? own : L, REC_NO_CHUNK);  // the survivor's own points
-                        unsigned off = own, cur = first;
-                        while (off < L && cur != SEG_INVALID) {
-                            const DevSeg r = fsg[cur];
-                            if (r.n == 0u || r.n == SEG_INVALID) break;  // (never for a segment of an accepted cycle)
-                            const unsigned take = r.n < L - off ? r.n : L - off;
-                            frc[rec++] = make_uint4(cur, dst0 + off, take, REC_NO_CHUNK);
-                            off += take;
-                            cur = r.next_idx;
-                        }
-                        for (; rec < brec + sR; rec++) frc[rec] = make_uint4(0u, 0u, 0u, 0u);  // (records reserved, not needed)
-                    }
-                } else {
-                    atomicOr(&G->overflow, 2u);
-                }
-            }
-        }
-    }
-}
-
 // the pieces of the accepted contours, from their pool chunks into the dense array: one wave per copy record
 // {chunk row, place in the dense array, points | first point of the piece inside its row << 16, the row's first chunk or REC_NO_CHUNK}
 __global__ __launch_bounds__(256) void k_seg_copy(const uint4 *__restrict__ recs, const uint32_t *__restrict__ chunk_tab,
                                                    const uint32_t *__restrict__ pool, uint32_t *__restrict__ dense,
                                                    const DevCounts *__restrict__ counts, const DevParams P, int part)
 {
-    // part -1: the frame's whole record array (trace mode 1); 0 / 1: its first / second half (trace mode 2, lists A / B)
+    // part 0 / 1: the first / second half of the frame's record array (lists A / B)
     const int f = blockIdx.y;
     const int lane = lane_id();
     unsigned nr = (unsigned)(part == 1 ? counts[f].nrec2 : counts[f].nrec);
-    const unsigned rcap = (part < 0 ? 2u : 1u) * (unsigned)P.maxContours;
-    nr = nr < rcap ? nr : rcap;
+    nr = nr < (unsigned)P.maxContours ? nr : (unsigned)P.maxContours;
     const uint4 *frc = recs + (long long)f * 2 * P.maxContours + (part == 1 ? (unsigned)P.maxContours : 0u);
     const uint32_t *fpool = pool;  // chunks are numbered across the whole launch
     uint8_t *fd = reinterpret_cast<uint8_t *>(dense) + (long long)f * P.maxChunks * CK;  // (one byte per point: its chain code)
@@ -2473,8 +2063,9 @@ __global__ __launch_bounds__(256) void k_seg_copy(const uint4 *__restrict__ recs
     }
 }
 
-// K3 probe passes, table-driven (trace mode 2).  Same decisions as k_probe<…, STOPSEED = true> -- a start survives only while it
-// can still be the canonical start of a border that has NO seed state and can pass the perimeter gate -- but a step is what a
+// K3 probe passes, table-driven (cycle tracing).  k_probe's decisions, and a start is dropped as soon as either cursor meets a seed
+// state -- a start survives only while it can still be the canonical start of a border that has NO seed state and can pass the
+// perimeter gate (a border with a seed state is a seed cycle, k_seg_cycles finds it without a start) -- but a step is what a
 // walker's step is: the raw 3 x 3 neighbourhood byte (three mask rows, one alignbit each) and ONE table look-up per cursor
 // (forward: next direction, the smallest examined background 4-neighbour, seed-state flag; backward: previous direction, ditto)
 // instead of nb8()'s bit shuffles, a find-first-set on the rotated neighbourhood and a loop over the examined directions.
@@ -2832,7 +2423,8 @@ __global__ __launch_bounds__(256) void k_probe_refill(const uint32_t *__restrict
 //   k_seg_cycles   one lane per segment: once around its cycle while one of its two start candidates can still be the
 //                  cycle's smallest; the lane that holds the canonical start lists the pieces (copy records) -- plus the
 //                  borders the survivor walk closed by itself
-//   k_seg_copy     as before (records now carry a source offset: the first segment is cut at the start state)
+//   k_seg_copy     the pieces of the accepted contours into a dense array for k_approx (a record carries a source offset:
+//                  the first segment is cut at the start state)
 
 // step table of the seed walker: index raw | backdir << 8 -> next direction | starts-an-outer-border << 3 |
 // starts-a-hole-border << 4 | seed state on a grid column << 5 | seed state on a grid row << 6
@@ -2855,8 +2447,8 @@ __device__ __forceinline__ void build_step_lut2(uint8_t *lut, int tid, int nthre
     }
 }
 
-// The seed walker.  As k_walk_full<1> (persistent waves, per-frame queues, LDS windows filled by LDS-DMA at batched
-// checkpoints, points into pool chunks), with what the round-2 counters asked for:
+// The seed walker.  As k_walk_full (persistent waves, per-frame queues, LDS windows filled by LDS-DMA at batched checkpoints,
+// points into pool chunks), with what the round-2 counters asked for:
 //   * window = 2 x 2 mask tiles (64 px x 32 rows, 256 bytes per lane), TOROIDAL: tile (tr, tc) lives in slot (tr & 1, tc & 1), so
 //     moving the window by one tile replaces two tiles and keeps two.  A walker that travels (net displacement since the last
 //     checkpoint) gets the tiles ahead of it fetched while it keeps stepping in the tiles it has: a lane waits for memory only
@@ -2873,17 +2465,10 @@ __device__ __forceinline__ void build_step_lut2(uint8_t *lut, int tid, int nthre
 #ifndef SW_RUN
 #define SW_RUN 32
 #endif
-// SURV (round 5): the same machinery for the PROBE SURVIVORS -- what k_walk_full<2> does (a survivor starts a border the way
-// icvFetchContour would, applies the canonical-start test as it goes, stops in front of the first seed state or closes the
-// border by itself; results into the survivors' contour rows and DevPend) on the seed walker's toroidal prefetched windows
-// instead of k_walk_full's reload-when-left windows (23 % of the lanes stepping there).  seedq = the survivor list, segs unused;
-// wres / pend unused for seeds.
-template <bool SURV>
 __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const uint32_t *__restrict__ masks, const uint2 *__restrict__ seedq,
                                                               uint32_t *__restrict__ chunk_tab, uint32_t *__restrict__ pool,
                                                               DevSegC *__restrict__ segs, DevCounts *__restrict__ counts,
-                                                              DevGlobal *__restrict__ G, const DevParams P, uint4 *__restrict__ wres,
-                                                              DevPend *__restrict__ pend_out)
+                                                              DevGlobal *__restrict__ G, const DevParams P)
 {
     // chunk j = pcx * 8 + (row >> 2 & 7) of lane l (16 bytes: rows 4q..4q+3 of one word column) at s_win[j * 64 + l]
     __shared__ uint4 s_win_all[SW_WAVES][16 * 64];
@@ -2892,13 +2477,12 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
     const uint32_t *s_winw = reinterpret_cast<const uint32_t *>(s_win);
     const int lane = lane_id();
     const int lane4 = lane * 4;
-    if (SURV) build_step_lut(s_lut, threadIdx.x, 64 * SW_WAVES);  // (next direction | hole-canonical code << 3 | seed flag << 6)
-    else build_step_lut2(s_lut, threadIdx.x, 64 * SW_WAVES);
+    build_step_lut2(s_lut, threadIdx.x, 64 * SW_WAVES);
     __syncthreads();
     int f = blockIdx.y;
     const unsigned ccap = (unsigned)P.maxContours, pcap = (unsigned)P.maxChunks * (unsigned)P.nframes;
     const int S = P.nscales, TC = P.TC, TR = P.TR, F = P.nframes;
-    const int W = P.W, W2 = P.W + 2;
+    const int W2 = P.W + 2;
     const int sgm = (8 << P.seedShift) - 1;
     const long long plane = (long long)TR * TC * MT_ROWS;
     enum { ST_IDLE = 0, ST_ACTIVE, ST_NEED, ST_LOADING, ST_FINAL };
@@ -2911,14 +2495,13 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
     const uint2 *fin = seedq;
     unsigned *qhead = nullptr;
     auto set_queue = [&](int fr) {
-        n = (unsigned)(SURV ? counts[fr].nsurv : counts[fr].nseeds);
-        if (SURV) n = n < (unsigned)P.maxStarts ? n : (unsigned)P.maxStarts;
+        n = (unsigned)counts[fr].nseeds;
         if (n > ccap) {
             if (lane == 0) atomicOr(&G->overflow, 2u);
             n = ccap;
         }
-        fin = seedq + (long long)fr * (SURV ? P.maxStarts : P.maxContours);
-        qhead = (unsigned *)(SURV ? &counts[fr].nwalk : &counts[fr].nwalk2);
+        fin = seedq + (long long)fr * P.maxContours;
+        qhead = (unsigned *)&counts[fr].nwalk2;
     };
     set_queue(f);
     int all_done = 0;
@@ -2943,9 +2526,6 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
     unsigned brkey = 0xffffffffu;
     uint32_t acc = 0;  // chain codes of the last (up to) eight points
     unsigned arena_next = 0, arena_end = 0;
-    // SURV: the survivor record, its start pixel / kind / key, the pixel after the start, what the walk found
-    uint2 sst = make_uint2(0u, 0u);
-    int x0 = 0, y0 = 0, hole = 0, key = 0, i1x = 0, i1y = 0, first = 0, closed = 0, stopped = 0;
     // raw 3 x 3 neighbourhood byte of the walker's pixel out of its toroidal window
     auto raw_here = [&]() {
         const int xb = cx + (MASK_PADW * 32 - 1);
@@ -2988,25 +2568,6 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
                 state = (xr > vxs || rr > vys) ? ST_NEED : ST_ACTIVE;
             }
         }
-        if (SURV && first && state == ST_ACTIVE) {
-            // the survivor's first look at its start pixel: single-pixel domain, initial direction
-            //   do { s = (s - 1) & 7; } while (*i1 == 0 && s != s_end)  == first foreground clockwise from s_end - 1
-            first = 0;
-            const unsigned raw = raw_here();
-            if (raw == 0) {
-                count = 1;  // (the contour's only point is its start: no step, no code)
-                closed = 1;
-                state = ST_FINAL;
-            } else {
-                sdir = first_dir(raw_to_nb(raw), hole ? 0 : 4);
-                i1x = x0 + dir_dx(sdir);
-                i1y = y0 + dir_dy(sdir);
-                if (!hole && pidx(i1x, i1y, W) < key) {
-                    ok = 0;
-                    state = ST_FINAL;
-                }
-            }
-        }
         if ((state == ST_ACTIVE || state == ST_NEED) && count > P.maxPerim) {
             ok = 0;
             too_long = 1;
@@ -3016,18 +2577,9 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
         if (state == ST_FINAL) {
             const int rem = count & 7, b0 = count - rem;
             if (rem) pool[((b0 & CK ? chunkB : chunkA) * CKW) + (unsigned)((b0 & (CK - 1)) >> 3)] = acc >> (4 * (8 - rem));
-            if (SURV) {
-                // stopped in front of a seed state: k_seg_cycles decides; else decided here
-                const int accept = ok && closed && !stopped && count >= P.minPerim && count <= P.maxPerim;
-                wres[(long long)lf * P.maxContours + slot] = make_uint4(sst.x, sst.y, accept ? (unsigned)count : 0u, (unsigned)key);
-                DevPend *pd = pend_out + (long long)lf * P.maxContours + slot;
-                pd->p = ok && stopped ? (unsigned)count : 0u;
-                pd->next_key = seed_key(cx, cy, sdir);
-            } else {
-                uint4 *r = reinterpret_cast<uint4 *>(segs + (long long)lf * P.maxContours + slot);
-                r[0] = make_uint4(SEG_INVALID, too_long || !ok ? SEG_INVALID : (unsigned)count, ko, kh);  // next_idx (k_seg_link2 fills it in), n, ko, kh
-                r[1] = make_uint4(seed_key(cx, cy, sdir), po | (ph << 16), 0u, chunk0);                  // next_key, pos, linked, chunk0
-            }
+            uint4 *r = reinterpret_cast<uint4 *>(segs + (long long)lf * P.maxContours + slot);
+            r[0] = make_uint4(SEG_INVALID, too_long || !ok ? SEG_INVALID : (unsigned)count, ko, kh);  // next_idx (k_seg_link2 fills it in), n, ko, kh
+            r[1] = make_uint4(seed_key(cx, cy, sdir), po | (ph << 16), 0u, chunk0);                  // next_key, pos, linked, chunk0
             state = ST_IDLE;
         }
         // ---- hand out new work
@@ -3042,10 +2594,8 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
                 int fr = (f + hop + k) % F;
                 if (fr == f) fr = -1;
                 if (k < F && fr >= 0) {
-                    const unsigned done = __hip_atomic_load((unsigned *)(SURV ? &counts[fr].nwalk : &counts[fr].nwalk2), __ATOMIC_RELAXED,
-                                                            __HIP_MEMORY_SCOPE_AGENT);
-                    unsigned m = (unsigned)(SURV ? counts[fr].nsurv : counts[fr].nseeds);
-                    if (SURV) m = m < (unsigned)P.maxStarts ? m : (unsigned)P.maxStarts;
+                    const unsigned done = __hip_atomic_load((unsigned *)&counts[fr].nwalk2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    unsigned m = (unsigned)counts[fr].nseeds;
                     m = m < ccap ? m : ccap;
                     has = done < m;
                 }
@@ -3082,20 +2632,6 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
                 if (state == ST_IDLE && next + (unsigned)rank < rend) {
                     slot = n - 1 - (next + (unsigned)rank);
                     lf = f;
-                    if (SURV) {  // x | y << 16, scale << 16 | hole << 24
-                        sst = make_uint2(gx, gy);
-                        x0 = cx = gx & 0xffff;
-                        y0 = cy = gx >> 16;
-                        hole = (gy >> 24) & 1;
-                        pl = masks + ((long long)f * S + (int)((gy >> 16) & 0xff)) * plane;
-                        pc = pidx(cx, cy, P.W);
-                        key = hole ? pidx(x0 + 1, y0, P.W) : pc;
-                        cxp = cx;  // (no direction yet: the first window is centred on the start)
-                        cyp = cy;
-                        sdir = 0;
-                        first = 1;
-                        closed = stopped = 0;
-                    } else {
                     cx = gx & 0x1fff;
                     cy = (gx >> 13) & 0x1fff;
                     sdir = (int)(gy & 7u);
@@ -3104,7 +2640,6 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
                     // the state was entered from the neighbour in direction sdir: travelling the other way
                     cxp = cx + 2 * dir_dx(sdir);
                     cyp = cy + 2 * dir_dy(sdir);
-                    }
                     count = 0;
                     ok = 1;
                     too_long = 0;
@@ -3135,29 +2670,19 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
                 const unsigned mine = arena_next + (unsigned)__popcll(b1 & lt) + 2u * (unsigned)__popcll(b2 & lt);
                 arena_next += total;
                 if (fresh || want1) {
-                    const unsigned trow = (SURV ? ccap : 0u) + slot;  // (survivors: the upper rows)
                     if (mine + 1 >= pcap) {
                         ovf |= 8u;
-                        if (SURV) {
-                            wres[(long long)lf * P.maxContours + slot] = make_uint4(sst.x, sst.y, 0u, (unsigned)key);
-                            pend_out[(long long)lf * P.maxContours + slot].p = 0u;
-                        } else {
-                            segs[(long long)lf * P.maxContours + slot].n = SEG_INVALID;
-                        }
+                        segs[(long long)lf * P.maxContours + slot].n = SEG_INVALID;
                         state = ST_IDLE;
                         pend = 0;
                     } else if (fresh) {
                         chunkA = chunk0 = mine;
-                        chunkB = mine + 1;
-                        if (SURV) {  // (a segment's first two chunks travel in its record: the table only holds the ones beyond)
-                            chunk_tab[chunk_tab_at(P, lf, trow, 0)] = chunkA;
-                            chunk_tab[chunk_tab_at(P, lf, trow, 1)] = chunkB;
-                        }
+                        chunkB = mine + 1;  // (a segment's first two chunks travel in its record: the table only holds the ones beyond)
                     } else {
                         kreg++;
                         if (kreg & 1) chunkB = mine;
                         else chunkA = mine;
-                        chunk_tab[chunk_tab_at(P, lf, trow, (unsigned)kreg)] = mine;
+                        chunk_tab[chunk_tab_at(P, lf, slot, (unsigned)kreg)] = mine;
                     }
                 }
             }
@@ -3233,35 +2758,7 @@ __global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const 
             d_iters++;
             d_active += __popcll(act);
 #endif
-            if (SURV && state == ST_ACTIVE) {
-                const unsigned raw = raw_here();
-                const unsigned e = s_lut[raw | ((unsigned)sdir << 8)];
-                const int sn = e & 7, code = (e >> 3) & 7;
-                const int hmag = (code & 1) ? W2 : 1;
-                const int hoff = (code & 2) ? hmag : -hmag;
-                if (count > 0 && (e & 0x40u) && seed_state(cx, cy, sdir, sgm)) {
-                    stopped = 1;  // the first seed state on this border: its seed cycle has the border already
-                    state = ST_FINAL;
-                } else {
-                    // background pixels examined in the 4-directions belong to this border's hole region
-                    int bad = hole && code && (pc + hoff < key);
-                    acc = __builtin_amdgcn_alignbit((uint32_t)sn, acc, 4);
-                    if ((count & 7) == 7) pool[((count & CK ? chunkB : chunkA) * CKW) + (unsigned)((count & (CK - 1)) >> 3)] = acc;
-                    count++;
-                    const int dx = dir_dx(sn), dy = dir_dy(sn);
-                    const int nx = cx + dx, ny = cy + dy;
-                    const int cl = !bad && nx == x0 && ny == y0 && cx == i1x && cy == i1y;
-                    cx = nx;
-                    cy = ny;
-                    pc += __mul24(dy, W2) + dx;
-                    bad |= !cl && !hole && pc < key;
-                    sdir = sn ^ 4;
-                    const unsigned xr = (unsigned)(cx + (MASK_PADW * 32 - 1) - vxb), rr = (unsigned)(cy - vyb);
-                    closed = cl;
-                    ok = !bad;
-                    state = (bad || cl) ? ST_FINAL : (xr > vxs || rr > vys) ? ST_NEED : ST_ACTIVE;
-                }
-            } else if (!SURV && state == ST_ACTIVE) {
+            if (state == ST_ACTIVE) {
                 const unsigned raw = raw_here();
                 const unsigned e = s_lut[raw | ((unsigned)sdir << 8)];
                 const unsigned skey = seed_key(cx, cy, sdir);
@@ -3539,9 +3036,9 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
     __shared__ int dst[2 * 16];
     const int lane = lane_id();
     const int f = blockIdx.y;
-    // legacy path: contour slot = survivor index; segment tracing (dense != nullptr): the accepted contours, compact
-    // (part: trace mode 2 keeps two contour lists per frame -- 1: the seed cycles, first half of the slots; 2: the seedless
-    //  borders, second half -- worked on by two launches on different streams; 0: one list)
+    // legacy path: contour slot = survivor index; cycle tracing (dense != nullptr): the accepted contours, compact, in two lists
+    // per frame (part 1: the seed cycles, first half of the slots; 2: the seedless borders, second half -- worked on by two launches
+    // on different streams)
     unsigned n = (unsigned)(dense ? (part == 2 ? counts[f].ncontours2 : counts[f].ncontours) : counts[f].nsurv);
     n = n < (unsigned)P.maxStarts ? n : (unsigned)P.maxStarts;
     n = n < (unsigned)P.maxContours ? n : (unsigned)P.maxContours;

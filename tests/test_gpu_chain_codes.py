@@ -91,7 +91,7 @@ def test_long_seedless_borders_and_long_segments(seed):
         det.close()
 
 
-@pytest.mark.parametrize("mode", ["legacy", "chain"])
+@pytest.mark.parametrize("mode", ["legacy"])
 def test_the_other_tracing_modes_read_the_same_codes(monkeypatch, mode):
     monkeypatch.setenv("FID_TRACE", mode)
     img = shapes_frame(4)

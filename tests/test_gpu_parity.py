@@ -310,10 +310,9 @@ def test_detector_parameter_matrix(k, dic):
 
 
 def test_whole_border_walk_and_seed_tracing_agree(monkeypatch):
-    """The three contour-tracing paths of the library (FID_TRACE=legacy: probe passes + whole-border walk; chain: round 2's
-    seed tracing, every border found by a probe survivor; default = cycles: borders read off the seed cycles, starts only for
-    borders without a seed) must all reproduce the oracle stage by stage, on adversarial blobs (rings, 1-px lines, large
-    blobs longer than maxMarkerPerimeterRate), on a noisy frame and in a batch."""
+    """The two contour-tracing paths of the library (FID_TRACE=legacy: probe passes + whole-border walk; default = cycles:
+    borders read off the seed cycles, starts only for borders without a seed) must both reproduce the oracle stage by stage,
+    on adversarial blobs (rings, 1-px lines, large blobs longer than maxMarkerPerimeterRate), on a noisy frame and in a batch."""
     rng = np.random.default_rng(5)
     blobs = np.full((720, 1280), 190, np.uint8)
     for _ in range(150):
@@ -323,7 +322,7 @@ def test_whole_border_walk_and_seed_tracing_agree(monkeypatch):
     blobs = np.clip(blobs.astype(np.int32) + rng.integers(-6, 7, blobs.shape), 0, 255).astype(np.uint8)
     d = get_predefined_dictionary(6)
     fr = make_frame(d, 77, width=1280, height=720, n_markers=8)
-    for mode in ("legacy", "chain", "cycles"):
+    for mode in ("legacy", "cycles"):
         monkeypatch.setenv("FID_TRACE", mode)
         det = ArucoDetector(6, max_width=1280, max_height=720, max_batch=3)
         try:
@@ -339,29 +338,25 @@ def test_whole_border_walk_and_seed_tracing_agree(monkeypatch):
             det.close()
 
 
-def test_both_survivor_walkers_agree_with_the_oracle(monkeypatch):
-    """Round 5: the probe survivors walk on the seed walker's prefetched windows (k_seed_walk<true>); FID_SURV_WALK=old keeps
-    k_walk_full<2>.  Both must reproduce the oracle stage by stage where survivors matter: borders WITHOUT a seed state (shapes
-    that live inside one cell of the seed grid, at the grid spacing of single-frame and of batch calls), rings and spirals, a
-    marker frame, a batch; and the tables too small for the survivors' points end in FID_E_CAPACITY on both."""
+def test_survivor_walk_agrees_with_the_oracle(monkeypatch):
+    """The probe survivors' walk (k_walk_full<2>) must reproduce the oracle stage by stage where survivors matter: borders
+    WITHOUT a seed state (shapes that live inside one cell of the seed grid, at the grid spacing of single-frame and of batch
+    calls), rings and spirals, a marker frame, a batch."""
     d = get_predefined_dictionary(6)
     cells = _cell_cases()
     fr = make_frame(d, 91, width=1280, height=720, n_markers=8, side_range=(48, 110))  # (small markers: outlines inside one cell)
-    for walker in ("new", "old"):
-        monkeypatch.setenv("FID_SURV_WALK", walker)
-        for shift in ("2", "4"):  # seed grid 32 px / 128 px
-            monkeypatch.setenv("FID_SEED_SHIFT", shift)
-            det = ArucoDetector(6, max_width=1280, max_height=720, max_batch=3, max_contours=65536, max_points=1 << 22)
-            try:
-                check_stages(det, cells, d)
-                check_stages(det, fr.image, d)
-                res = det.detect_markers_batch(np.stack([fr.image, cells, fr.image]))
-                oids, ocorners = oracle.detect(fr.image, d)
-                assert res[0][1].tolist() == oids.tolist() == res[2][1].tolist()
-                assert np.array_equal(res[0][0], ocorners) and np.array_equal(res[2][0], ocorners)
-            finally:
-                det.close()
-        monkeypatch.delenv("FID_SEED_SHIFT")
+    for shift in ("2", "4"):  # seed grid 32 px / 128 px
+        monkeypatch.setenv("FID_SEED_SHIFT", shift)
+        det = ArucoDetector(6, max_width=1280, max_height=720, max_batch=3, max_contours=65536, max_points=1 << 22)
+        try:
+            check_stages(det, cells, d)
+            check_stages(det, fr.image, d)
+            res = det.detect_markers_batch(np.stack([fr.image, cells, fr.image]))
+            oids, ocorners = oracle.detect(fr.image, d)
+            assert res[0][1].tolist() == oids.tolist() == res[2][1].tolist()
+            assert np.array_equal(res[0][0], ocorners) and np.array_equal(res[2][0], ocorners)
+        finally:
+            det.close()
 
 
 def _cell_cases(w=1280, h=720):
@@ -463,7 +458,7 @@ def test_internal_capacity_is_reported_not_silent(monkeypatch):
     from fiducials_amd._lib import FidError
     d = get_predefined_dictionary(6)
     fr = make_frame(d, 3, width=1280, height=720, n_markers=8)
-    for mode in ("legacy", "chain", "cycles"):
+    for mode in ("legacy", "cycles"):
         monkeypatch.setenv("FID_TRACE", mode)
         det = ArucoDetector(6, max_width=1280, max_height=720, max_contours=96)
         try:
@@ -708,14 +703,14 @@ def test_contour_refinement_on_the_reference_images(key):
 
 
 def test_contour_refinement_cfg2_every_tracing_mode_batch_and_pose(monkeypatch):
-    """cfg 2 frames under CORNER_REFINE_CONTOUR: corners == the oracle's in all three tracing modes (the contour points come from
-    the dense point array in the traced modes, from the chunk pool behind the whole-border walk), as a batch, switched on and
+    """cfg 2 frames under CORNER_REFINE_CONTOUR: corners == the oracle's in both tracing modes (the contour points come from
+    the dense point array under cycle tracing, from the chunk pool behind the whole-border walk), as a batch, switched on and
     off on a live context (dynamic_reconfigure), and the poses follow the refined corners."""
     d = get_predefined_dictionary(6)
     frames = [make_frame(d, s) for s in (1000, 1001)]
     p, op = params_pair(cornerRefinementMethod=2)
     want = [oracle.detect(fr.image, d, params=op) for fr in frames]
-    for mode in ("cycles", "chain", "legacy"):
+    for mode in ("cycles", "legacy"):
         monkeypatch.setenv("FID_TRACE", mode)
         det = ArucoDetector(d, params=p, max_width=1920, max_height=1080, max_batch=2)
         try:

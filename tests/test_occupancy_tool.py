@@ -22,18 +22,18 @@ def test_static_sheet_of_the_shipped_library():
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout)
     k = d["kernels"]
-    for name in ("k_threshold_stream<3,4,13,3,false>", "k_seed_walk<false>", "k_walk_full<2>", "k_probe_lut<6,0>", "k_raw_to_gray", "k_probe_tables",
+    for name in ("k_threshold_stream<3,4,13,3,false>", "k_seed_walk", "k_walk_full<2>", "k_probe_lut<6,0>", "k_raw_to_gray", "k_probe_tables",
                  "k_stag_route_walk[g]", "k_stag_route_extract_big[g]", "k_stag_ccl_flatten[g]", "k_stag_refine[g]"):
         assert name in k, name
         assert 0 < k[name]["vgpr"] <= 512 and k[name]["launches"], name
     # the walkers' static LDS: 2 x 16 KB of windows + the 2 KB step table
-    assert k["k_seed_walk<false>"]["lds_static"] == 34816 and k["k_walk_full<2>"]["lds_static"] == 34816
+    assert k["k_seed_walk"]["lds_static"] == 34816 and k["k_walk_full<2>"]["lds_static"] == 34816
     # no kernel of the shipped library spills VECTOR registers or uses scratch memory (scalar registers spilled into vector lanes --
     # v_writelane / v_readlane, no memory -- occur in the largest kernels and are listed by the sheet)
     assert not [n for n, v in k.items() if v.get("spills", {}).get("vgpr")], [n for n, v in k.items() if v.get("spills", {}).get("vgpr")]
     # (scratch memory itself is used by a few kernels with dynamically indexed local arrays -- the simplex, the decoder, the rank sort --
     #  never by the streaming or the walking kernels)
-    for name in ("k_threshold_stream<3,4,13,3,false>", "k_find_starts<true>", "k_seed_walk<false>", "k_walk_full<2>", "k_probe_lut<6,0>",
+    for name in ("k_threshold_stream<3,4,13,3,false>", "k_find_starts<true>", "k_seed_walk", "k_walk_full<2>", "k_probe_lut<6,0>",
                  "k_stag_route_walk[g]", "k_stag_ccl_flatten[g]", "k_stag_smooth_grad[g]"):
         assert k[name]["scratch"] == 0, name
     assert len(d["device_text_sha256"]) == 64

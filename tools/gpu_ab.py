@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B runs of the cfg 3 batch under different library knobs (environment variables read at fid_create), one process,
-frames generated once.  Usage: python tools/gpu_ab.py "FID_THR=tile" "FID_THR_NW=3 FID_THR_SPLIT=0" ...   ('' = defaults)"""
+frames generated once.  Usage: python tools/gpu_ab.py "FID_THR_NW=5" "FID_THR_NW=3 FID_THR_SPLIT=0" ...   ('' = defaults)"""
 import json
 import os
 import sys

@@ -289,7 +289,7 @@ def main():
         out["beside_threshold"] = {}
         for n in (4, 3, 2, 1):
             row = {}
-            for g in ("k_walk_full<2>", "k_seed_walk<true>", "k_seed_walk<false>", "k_seg_cycles<0u>", "k_seg_cycles<48u>", "k_probe_lut<6,0>", "k_approx", "k_seg_copy"):
+            for g in ("k_walk_full<2>", "k_seed_walk", "k_seg_cycles<0u>", "k_seg_cycles<48u>", "k_probe_lut<6,0>", "k_approx", "k_seg_copy"):
                 sh = shape(g)
                 if sh:
                     row[g] = fits_beside(thr, n, sh)

@@ -1,7 +1,7 @@
 // pmc_calib.hip -- known-byte-count kernels in the access patterns this library uses, to calibrate rocprofv3's FETCH_SIZE /
 // WRITE_SIZE on gfx950 (MI355X_MICROARCH.md: FETCH_SIZE reads 1/2 of a wide coalesced stream; other widths uncalibrated).
 // Each kernel moves exactly N bytes (N = 1 GiB, far beyond the 256 MiB Infinity Cache) once.
-//   rd4    4 B per lane, coalesced rows                 (k_threshold_fixed's dword loads, most list reads)
+//   rd4    4 B per lane, coalesced rows                 (most list reads)
 //   rd1    1 B per lane, coalesced                      (k_threshold_stream's producer wave)
 //   rd16   16 B per lane, coalesced                     (k_find_starts' tile loads)
 //   rdlds  16 B per lane through LDS-DMA (global_load_lds_dwordx4)   (the walkers' window refills)
