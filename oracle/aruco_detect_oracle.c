@@ -97,7 +97,7 @@ int ora_to_gray(const uint8_t *img, int w, int h, int stride, int enc, uint8_t *
  *          (ColumnSum<ushort,uchar> fixed-point for win^2<=256, ColumnSum<int,uchar> float/double
  *          scale otherwise); for odd win both equal exact rounding because sum/win^2 can never sit
  *          on a half (tests/test_oracle_units.py::test_box_mean_rounding checks the fixed-point
- *          formula exhaustively).
+ *          formula exhaustively; tests/test_threshold_reference.py the double-scale path above 2^23).
  *   idelta = type == THRESH_BINARY ? cvCeil(C) : cvFloor(C) (thresh.cpp adaptiveThreshold): aruco passes
  *   THRESH_BINARY_INV, so FLOOR;  dst = (src - mean <= -idelta) ? 255 : 0 (tab[i] = i - 255 <= -idelta)   */
 int ora_adaptive_threshold(const uint8_t *gray, int w, int h, int win, double C, uint8_t *out)
@@ -129,15 +129,23 @@ int ora_adaptive_threshold(const uint8_t *gray, int w, int h, int win, double C,
             rs[x] = acc;
         }
     }
-    int32_t *col = (int32_t *)calloc((size_t)w, sizeof(int32_t));
-    if (!col) {
+    /* 2 * col + area <= 511 * area: 32 bits hold it up to win 2049 (the node's windows are timed on this path); from win 2051
+     * on the column sums and the rounding go to 64 bits.  (A row sum is at most 255 * win < 2^22 for any window.) */
+    const int wide = 511LL * area >= (1LL << 31);
+    void *colbuf = calloc((size_t)w, wide ? sizeof(int64_t) : sizeof(int32_t));
+    if (!colbuf) {
         free(rowsum);
         return -2;
     }
+    int32_t *col = (int32_t *)colbuf;
+    int64_t *col64 = (int64_t *)colbuf;
     for (int k = -r; k <= r; k++) {
         int yy = k < 0 ? 0 : (k >= h ? h - 1 : k);
         const int32_t *rs = rowsum + (size_t)yy * w;
-        for (int x = 0; x < w; x++) col[x] += rs[x];
+        if (wide)
+            for (int x = 0; x < w; x++) col64[x] += rs[x];
+        else
+            for (int x = 0; x < w; x++) col[x] += rs[x];
     }
     for (int y = 0; y < h; y++) {
         if (y > 0) {
@@ -145,16 +153,27 @@ int ora_adaptive_threshold(const uint8_t *gray, int w, int h, int win, double C,
             yo = yo < 0 ? 0 : yo;
             yi = yi >= h ? h - 1 : yi;
             const int32_t *ro = rowsum + (size_t)yo * w, *ri = rowsum + (size_t)yi * w;
-            for (int x = 0; x < w; x++) col[x] += ri[x] - ro[x];
+            if (wide)
+                for (int x = 0; x < w; x++) col64[x] += ri[x] - ro[x];
+            else
+                for (int x = 0; x < w; x++) col[x] += ri[x] - ro[x];
         }
         const uint8_t *s = gray + (size_t)y * w;
         uint8_t *d = out + (size_t)y * w;
-        for (int x = 0; x < w; x++) {
-            int mean = (2 * col[x] + area) / (2 * area); /* round(sum/area), never a tie */
-            d[x] = (s[x] - mean <= -idelta) ? 255 : 0;
+        if (wide) {
+            const int64_t area64 = area;
+            for (int x = 0; x < w; x++) {
+                int mean = (int)((2 * col64[x] + area64) / (2 * area64));
+                d[x] = (s[x] - mean <= -idelta) ? 255 : 0;
+            }
+        } else {
+            for (int x = 0; x < w; x++) {
+                int mean = (2 * col[x] + area) / (2 * area); /* round(sum/area), never a tie */
+                d[x] = (s[x] - mean <= -idelta) ? 255 : 0;
+            }
         }
     }
-    free(col);
+    free(colbuf);
     free(rowsum);
     return 0;
 }
