@@ -4,6 +4,8 @@
 //   fid_stag_quads.hip  s7, s8  quads, decoding          fid_stag_pose.hip   s9, s10 pose refinement, marker pose
 // Front end = what Stag::detectMarkers -> QuadDetector::detectQuads -> EDInterface::runEDPFandEDLines -> DetectEdgesByEDPF
 // (/root/reference/stag_detect/src/stag/ED/ED.cpp:144-187) runs before the edge routing:
+//   K9- k_stag_ingest        a frame in device memory (fid_stag_detect_markers_device / _batch_device) -> the context's gray
+//                            image: mono8 strided copy, bgr8 / rgb8 -> gray (StagNode's msgToGray, 15-bit form, see there)
 //
 //   K9a k_stag_smooth_grad   SmoothImage(sigma = 1.0) = cv::GaussianBlur 5x5, sigma 0 (ImageSmooth.cpp:43-55) fused with
 //                            ComputeGradientMapByPrewitt (GradientOperators.cpp:77-136): one LDS tile, 3-px halo
@@ -34,6 +36,74 @@ __device__ __forceinline__ int stag_reflect101(int p, int n)
     while (p < 0 || p >= n) p = p < 0 ? -p : 2 * n - 2 - p;
     return p;
 }
+
+// A frame the caller already holds in device memory -> d_src, the tightly packed W x H gray every later kernel reads.  One lane =
+// 16 gray bytes of one row (lanes numbered row-major over the frame's 16-pixel chunks): mono8 is a strided copy; bgr8 / rgb8 go
+// through cvtColor's RGB2Gray<uchar> in OpenCV 4.x's 15-bit form, (B*3735 + G*19235 + R*9798 + 2^14) >> 15 -- k_to_gray's, and
+// what the JPEG decoder's MONO8 output is (StagNode::msgToGray, host/include/stag_host.hpp, keeps its 14-bit form; DESIGN.md
+// section 7).  A lane whose source chunk is 16-byte aligned reads it as one (mono8) or three (colour: 48 bytes) uint4, and writes its
+// 16 gray bytes as one uint4 where the destination is aligned; otherwise byte by byte (odd widths and strides, the tail of a row).
+// Every source byte is read once, every gray byte written once.  The frame lies at base + off: in a group every frame's arguments
+// are frame 0's but for off (the recorder's one per-frame scalar, fid_stag_batch.h) and dst (its context's slab delta), so a
+// group's ingest is one launch.
+__device__ __forceinline__ void k_stag_ingest_impl(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
+                                                   long long stride, int enc)
+{
+    const long long cpr = (W + 15) >> 4;  // 16-pixel chunks per row
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cpr * H) return;
+    const int y = (int)(i / cpr), x0 = (int)(i - (long long)y * cpr) * 16;
+    const int n = W - x0 < 16 ? W - x0 : 16;
+    const int bpp = enc == FID_ENC_MONO8 ? 1 : 3;
+    const uint8_t *s = base + off + (unsigned long long)y * (unsigned long long)stride + (unsigned long long)x0 * bpp;
+    uint8_t *d = dst + (size_t)y * W + x0;
+    const bool swide = n == 16 && ((uintptr_t)s & 15) == 0, dwide = n == 16 && ((uintptr_t)d & 15) == 0;
+    unsigned o[4] = {0u, 0u, 0u, 0u};
+    if (enc == FID_ENC_MONO8) {
+        if (swide) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(s);
+            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+        } else {
+            for (int k = 0; k < n; k++) o[k >> 2] |= (unsigned)s[k] << ((k & 3) * 8);
+        }
+    } else {
+        const bool bfirst = enc == FID_ENC_BGR8;
+        if (swide) {
+            const uint4 *q = reinterpret_cast<const uint4 *>(s);
+            const uint4 a = q[0], b = q[1], c = q[2];
+            const unsigned w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int p = 0; p < 16; p++) {
+                const int c0 = (int)((w[(3 * p) >> 2] >> (((3 * p) & 3) * 8)) & 0xffu);
+                const int c1 = (int)((w[(3 * p + 1) >> 2] >> (((3 * p + 1) & 3) * 8)) & 0xffu);
+                const int c2 = (int)((w[(3 * p + 2) >> 2] >> (((3 * p + 2) & 3) * 8)) & 0xffu);
+                const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
+                o[p >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((p & 3) * 8);
+            }
+        } else {
+            for (int k = 0; k < n; k++) {
+                const int c0 = s[3 * k], c1 = s[3 * k + 1], c2 = s[3 * k + 2];
+                const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
+                o[k >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((k & 3) * 8);
+            }
+        }
+    }
+    if (dwide) {
+        *reinterpret_cast<uint4 *>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else {
+        for (int k = 0; k < n; k++) d[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
+    }
+}
+__global__ __launch_bounds__(256) void k_stag_ingest(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
+                                                     long long stride, int enc)
+{
+    k_stag_ingest_impl(dst, base, off, W, H, stride, enc);
+}
+struct k_stag_ingest_fn {
+    static constexpr int kBounds = 256;
+    __device__ __forceinline__ void operator()(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
+                                               long long stride, int enc) const { k_stag_ingest_impl(dst, base, off, W, H, stride, enc); }
+};
 
 // One workgroup = one SX x SY output tile.  src tile + 3 px halo (BORDER_REFLECT_101) -> LDS; horizontal [1 4 6 4 1] pass
 // -> LDS u16; vertical pass + (x + 128) >> 8 -> smoothed tile + 1 px halo in LDS; Prewitt |gx| + |gy| and edge direction
@@ -816,6 +886,10 @@ struct StagJob {
     // what is asked for
     const uint8_t *gray = nullptr;
     int width = 0, height = 0, stride = 0, last = SS_MARKERS;
+    // ... or a frame in device memory at dev + dev_off (stride in bytes, enc mono8 / bgr8 / rgb8): k_stag_ingest instead of the staging
+    const uint8_t *dev = nullptr;
+    unsigned long long dev_off = 0;
+    int enc = FID_ENC_MONO8;
     fid_stag_marker *out = nullptr;
     int cap = 0;
     int32_t *n_out = nullptr;
@@ -1008,7 +1082,9 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
     for (;;) {  // (a frame queued ahead passes all its segments in this one call: "continue" where the counted road returns)
     switch (j.seg) {
     case 0: {  // ---- smoothing, gradient, anchors, anchor sort
-        if (!j.gray || j.width < 8 || j.height < 8 || j.width > c->maxW || j.height > c->maxH || j.stride < j.width) return stag_finish(j, FID_E_INVALID_ARG);
+        const int bpp = j.dev && j.enc != FID_ENC_MONO8 ? 3 : 1;
+        if ((!j.gray && !j.dev) || j.width < 8 || j.height < 8 || j.width > c->maxW || j.height > c->maxH || j.stride < j.width * bpp)
+            return stag_finish(j, FID_E_INVALID_ARG);
         if (j.last >= SS_UNREFINED && !c->d_words) return stag_finish(j, FID_E_INVALID_ARG);  // no marker library loaded
         const int W = j.width, H = j.height;
         j.spec = stag_spec_enabled(grouped) && !j.nospec && j.last >= SS_MARKERS && c->route_mode == 1 && c->pred.valid && c->pred.W == W && c->pred.H == H &&
@@ -1018,9 +1094,15 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
             j.spec = false;
         }
         if (j.spec) stag_plan(c, j);
-        if (!j.staged)
-            for (int y = 0; y < H; y++) memcpy(c->h_src + (size_t)y * W, j.gray + (size_t)y * j.stride, (size_t)W);
-        if (STAG_MEMCPY(c->d_src, c->h_src, (size_t)W * H, hipMemcpyHostToDevice, st) != hipSuccess) return stag_finish(j, FID_E_HIP);
+        if (j.dev) {  // (the frame is on the device already: no staging, no copy engine)
+            const unsigned long long lanes = (unsigned long long)((W + 15) >> 4) * H;
+            STAG_LAUNCH(k_stag_ingest, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, c->d_src, j.dev, j.dev_off, W, H, (long long)j.stride, j.enc);
+            if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
+        } else {
+            if (!j.staged)
+                for (int y = 0; y < H; y++) memcpy(c->h_src + (size_t)y * W, j.gray + (size_t)y * j.stride, (size_t)W);
+            if (STAG_MEMCPY(c->d_src, c->h_src, (size_t)W * H, hipMemcpyHostToDevice, st) != hipSuccess) return stag_finish(j, FID_E_HIP);
+        }
         if (STAG_MEMSET(c->d_rowhist, 0, (size_t)H * STAG_BINS * 2, st) != hipSuccess) return stag_finish(j, FID_E_HIP);
         STAG_LAUNCH(k_stag_smooth_grad, dim3((W + SX - 1) / SX, (H + SY - 1) / SY), dim3(256), 0, st, c->d_src, W, W, H, GRADIENT_THRESH,
                            c->d_smooth, c->d_grad, c->d_dir);
@@ -1615,9 +1697,10 @@ fid_status fid_stag_pose_last(fid_stag_ctx *c, const double K[9], const double D
 // host thread goes round the groups, so the wait of one group overlaps the kernels of the others.  A group takes its next
 // frames when all of its frames are through (frames that need an extra segment -- a routing fallback -- hold their group for
 // that round).  Results are those of frame-by-frame calls: same kernels bodies, same per-frame buffers, no shared state.
-static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
-                                    int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
-                                    fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+// frames: host memory, or (dev_frames) device memory in encoding enc -- then a group's first launch is k_stag_ingest, no staging.
+static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
+                                    int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5],
+                                    double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
 {
     // a group is at most as large as the smallest argument table (the routing kernels carry ~250 bytes of arguments per frame and
     // kernel-argument memory is 4 KB: a group one frame larger would launch them twice)
@@ -1684,7 +1767,12 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
                     for (int k = 0; k < gs && f0 + k < nframes; k++) {
                         const int f = f0 + k;
                         StagJob j;
-                        j.gray = frames + (size_t)f * frame_stride; j.width = width; j.height = height; j.stride = stride;
+                        if (dev_frames) {
+                            j.dev = dev_frames; j.dev_off = (unsigned long long)f * (unsigned long long)frame_stride; j.enc = enc;
+                        } else {
+                            j.gray = frames + (size_t)f * frame_stride;
+                        }
+                        j.width = width; j.height = height; j.stride = stride;
                         j.out = markers + (size_t)f * cap_per_frame; j.cap = cap_per_frame; j.n_out = n_per_frame + f;
                         j.last = (K && poses) ? SS_POSE : SS_MARKERS;
                         j.K = K; j.D = D; j.marker_size = marker_size;
@@ -1695,7 +1783,7 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
                     }
                     // the frames' rows into the contexts' pinned staging buffers, side by side: 2 MB of memcpy per 1080p frame is
                     // ~0.1 ms, and one thread doing it for a group of 64 kept the group's stream empty for 6 ms of every cycle
-                    if (stage_threads > 1 && G.live > 1 && width >= 8 && height >= 8 && width <= ctxs[g * gs]->maxW && height <= ctxs[g * gs]->maxH &&
+                    if (!dev_frames && stage_threads > 1 && G.live > 1 && width >= 8 && height >= 8 && width <= ctxs[g * gs]->maxW && height <= ctxs[g * gs]->maxH &&
                         stride >= width) {
                         const int nlive = G.live;
                         auto stage = [&](int t, int T) {
@@ -1786,24 +1874,16 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
     return first_err;
 }
 
-// Frames over several contexts: every context carries one frame at a time through the segments of stag_advance; a host
-// thread goes round ITS contexts, one segment each, so the waits of its contexts overlap.  A context that finishes a frame
-// takes the next one off a shared counter.  One thread keeps about a thousand frames a second going (a frame is ~60 launches,
-// ~15 copies and a 2 MB staging memcpy: 0.9 ms of host time), so the contexts are dealt out to FID_STAG_THREADS threads
-// (default 4, at most one per context).  Results are those of frame-by-frame calls (a frame never sees another frame's data).
-fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
-                                         int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
-                                         fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+// the two batch entry points' common part, their arguments checked (frames: host memory; dev_frames: device memory in encoding enc)
+static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
+                             int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+                             fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
 {
-    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0) return FID_E_INVALID_ARG;
-    for (int t = 0; t < nctx; t++)
-        if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
-    if (K && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
     for (int f = 0; f < nframes; f++) n_per_frame[f] = 0;  // every count is defined whatever happens to a frame
     // frames as a grid dimension (default); FID_STAG_BATCH=contexts: round 2's road, a stream per context and host threads
     if (!(getenv("FID_STAG_BATCH") && !strcmp(getenv("FID_STAG_BATCH"), "contexts")))
-        return stag_batch_groups(ctxs, nctx, frames, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses, cap_per_frame,
-                                 n_per_frame);
+        return stag_batch_groups(ctxs, nctx, frames, dev_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
+                                 cap_per_frame, n_per_frame);
     int nthreads = 4;
     if (const char *e = getenv("FID_STAG_THREADS")) nthreads = atoi(e);
     nthreads = nthreads < 1 ? 1 : (nthreads > nctx ? nctx : nthreads);
@@ -1826,7 +1906,12 @@ fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx
                         dry = true;
                     } else {
                         StagJob j;
-                        j.gray = frames + (size_t)f * frame_stride; j.width = width; j.height = height; j.stride = stride;
+                        if (dev_frames) {
+                            j.dev = dev_frames; j.dev_off = (unsigned long long)f * (unsigned long long)frame_stride; j.enc = enc;
+                        } else {
+                            j.gray = frames + (size_t)f * frame_stride;
+                        }
+                        j.width = width; j.height = height; j.stride = stride;
                         j.out = markers + (size_t)f * cap_per_frame; j.cap = cap_per_frame; j.n_out = n_per_frame + f;
                         j.last = (K && poses) ? SS_POSE : SS_MARKERS;
                         j.K = K; j.D = D; j.marker_size = marker_size;
@@ -1868,6 +1953,93 @@ fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx
     return first_err;
 }
 
+// Frames over several contexts: every context carries one frame at a time through the segments of stag_advance; a host
+// thread goes round ITS contexts, one segment each, so the waits of its contexts overlap.  A context that finishes a frame
+// takes the next one off a shared counter.  One thread keeps about a thousand frames a second going (a frame is ~60 launches,
+// ~15 copies and a 2 MB staging memcpy: 0.9 ms of host time), so the contexts are dealt out to FID_STAG_THREADS threads
+// (default 4, at most one per context).  Results are those of frame-by-frame calls (a frame never sees another frame's data).
+fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
+                                         int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+                                         fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+{
+    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0) return FID_E_INVALID_ARG;
+    for (int t = 0; t < nctx; t++)
+        if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
+    if (K && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
+                      cap_per_frame, n_per_frame);
+}
+
+// ---- frames in device memory (fid_stag_detect_markers_device / _batch_device).  Everything such a call can be refused for is
+// checked here, before anything is put on a stream.  The frames must lie in device memory of the contexts' device: the first and
+// the last byte the call reads are looked up (hipPointerGetAttributes), and where the runtime knows the allocation around the first
+// one (hipMemGetAddressRange) every byte read must lie inside it.
+static int stag_enc_bpp(int enc)
+{
+    return enc == FID_ENC_MONO8 ? 1 : (enc == FID_ENC_BGR8 || enc == FID_ENC_RGB8) ? 3 : 0;  // (what stag_ros::msgToGray accepts)
+}
+static bool stag_on_device(const void *p, int device)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();  // (not a HIP allocation: the error must not be left for the launches' checks to find)
+        return false;
+    }
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) && a.device == device;
+}
+static fid_status stag_check_device_frames(const uint8_t *d, int device, int32_t nframes, int32_t width, int32_t height, int32_t stride,
+                                           int64_t frame_stride, int enc)
+{
+    const int bpp = stag_enc_bpp(enc);
+    if (bpp == 0) return FID_E_UNSUPPORTED;
+    if (!d || width < 8 || height < 8 || (int64_t)stride < (int64_t)width * bpp || frame_stride < 0) return FID_E_INVALID_ARG;
+    const unsigned long long span = (unsigned long long)(nframes - 1) * (unsigned long long)frame_stride +
+                                    (unsigned long long)(height - 1) * (unsigned long long)stride + (unsigned long long)width * bpp;
+    if (!stag_on_device(d, device) || !stag_on_device(d + span - 1, device)) return FID_E_INVALID_ARG;
+    hipDeviceptr_t base = nullptr;
+    size_t bytes = 0;
+    if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)d) == hipSuccess) {
+        if (d + span > (const uint8_t *)base + bytes) return FID_E_INVALID_ARG;
+    } else {
+        (void)hipGetLastError();
+    }
+    return FID_OK;
+}
+
+fid_status fid_stag_detect_markers_device(fid_stag_ctx *c, const void *d_img, int32_t width, int32_t height, int32_t stride, fid_encoding enc,
+                                          fid_stag_marker *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !c->d_words) return FID_E_INVALID_ARG;
+    if (stag_enc_bpp(enc) == 0) return FID_E_UNSUPPORTED;
+    if (width > c->maxW || height > c->maxH) return FID_E_INVALID_ARG;
+    const fid_status rc = stag_check_device_frames((const uint8_t *)d_img, c->device, 1, width, height, stride, 0, enc);
+    if (rc != FID_OK) return rc;
+    StagJob j;
+    j.dev = (const uint8_t *)d_img; j.enc = enc; j.width = width; j.height = height; j.stride = stride; j.last = SS_MARKERS;
+    j.out = out; j.cap = cap; j.n_out = n_out;
+    return stag_run(c, j);
+}
+
+fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+                                                double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                                int32_t *n_per_frame)
+{
+    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0) return FID_E_INVALID_ARG;
+    for (int t = 0; t < nctx; t++)
+        if (!ctxs[t] || !ctxs[t]->d_words || width > ctxs[t]->maxW || height > ctxs[t]->maxH || ctxs[t]->device != ctxs[0]->device) return FID_E_INVALID_ARG;
+    if (K && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    if (stag_enc_bpp(enc) == 0) return FID_E_UNSUPPORTED;
+    if (nframes > 0) {
+        const fid_status rc = stag_check_device_frames((const uint8_t *)d_frames, ctxs[0]->device, nframes, width, height, stride, frame_stride, enc);
+        if (rc != FID_OK) return rc;
+    } else if (!d_frames) {
+        return FID_E_INVALID_ARG;
+    }
+    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers,
+                      poses, cap_per_frame, n_per_frame);
+}
+
 fid_status fid_stag_queue_stats(const fid_stag_ctx *c, int32_t *queued, int32_t *rerun)
 {
     if (!c) return FID_E_INVALID_ARG;
@@ -1897,6 +2069,7 @@ int64_t fid_stag_tap_bytes(fid_stag_ctx *c, fid_stag_tap which)
     case FID_STAG_TAP_VLINES: return c->lines_validated ? (int64_t)c->n_vlines * (int64_t)sizeof(fid_stag_line) : 0;
     case FID_STAG_TAP_QUADS: return c->quadded ? (int64_t)c->n_quads * (int64_t)sizeof(fid_stag_quad) : 0;
     case FID_STAG_TAP_MARKERS: return c->decoded ? (int64_t)c->n_markers * (int64_t)sizeof(fid_stag_marker) : 0;
+    case FID_STAG_TAP_GRAY: return n;
     }
     return 0;
 }
@@ -1925,6 +2098,7 @@ fid_status fid_stag_tap_read(fid_stag_ctx *c, fid_stag_tap which, void *dst, int
     case FID_STAG_TAP_VLINES: src = c->d_vlines; break;
     case FID_STAG_TAP_QUADS: src = c->d_quads; break;
     case FID_STAG_TAP_MARKERS: src = c->d_markers; break;
+    case FID_STAG_TAP_GRAY: src = c->d_src; break;
     }
     if (!src) return FID_E_INVALID_ARG;
     if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;

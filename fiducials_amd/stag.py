@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import FidError
 
 (TAP_SMOOTH, TAP_GRAD, TAP_DIR, TAP_ANCHORS, TAP_SORTED, TAP_EDGEIMG, TAP_SEGMENTS, TAP_SEGPIX, TAP_SMOOTH2, TAP_VGRAD, TAP_VPROB,
- TAP_VSEGMENTS, TAP_LINES, TAP_VLINES, TAP_QUADS, TAP_MARKERS) = range(16)
+ TAP_VSEGMENTS, TAP_LINES, TAP_VLINES, TAP_QUADS, TAP_MARKERS, TAP_GRAY) = range(17)
 
 MARKER_DTYPE = np.dtype([("id", "i4"), ("shift", "i4"), ("corners", "f8", (4, 2)), ("center", "f8", (2,)), ("H", "f8", (3, 3)),
                          ("lineInf", "f8", (3,)), ("projectiveDistortion", "f8"), ("code", "u8")])
@@ -108,6 +108,28 @@ class StagDetector:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return self._mbuf[:n.value].copy()
 
+    def detect_markers_device(self, data_ptr: int, width: int, height: int, stride: int | None = None, encoding: str = "mono8") -> np.ndarray:
+        """detect_markers on a frame already resident on this context's device (e.g. a torch uint8 tensor's data_ptr(); the work that
+        wrote it must be complete, torch.cuda.synchronize()).  encoding: mono8, bgr8 or rgb8; stride in bytes (default: packed rows).
+        Colour goes to gray in OpenCV 4.x's 15-bit form (fid_stag_detect_markers_device); tap(TAP_GRAY) reads the gray image."""
+        enc = _lib.ENC.get(encoding, -1)  # (any other encoding: the library refuses it, FID_E_UNSUPPORTED)
+        bpp = _lib.ENC_BYTES_PER_PIXEL.get(encoding, 1)
+        stride = stride or width * bpp
+        n = C.c_int32(0)
+        if getattr(self, "_mbuf", None) is None:
+            self._mbuf = np.zeros(512, MARKER_DTYPE)
+        rc = self._L.fid_stag_detect_markers_device(self._ctx, C.c_void_p(data_ptr), width, height, stride, enc, self._mbuf.ctypes.data,
+                                                    len(self._mbuf), C.byref(n))
+        if rc == _lib.FID_OK or rc == _lib.FID_E_CAPACITY:
+            self.shape = (height, width)
+        if rc == _lib.FID_E_CAPACITY:
+            m = self.markers()
+            if len(m) > len(self._mbuf):
+                return m
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return self._mbuf[:n.value].copy()
+
     def pose_last(self, K, D, marker_size: float) -> np.ndarray:
         """Common::solvePnpSingle for the markers of the last detect_markers*() call (POSE_DTYPE)."""
         K = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
@@ -160,7 +182,7 @@ class StagDetector:
             if rc != _lib.FID_OK:
                 raise FidError(rc, self._L.fid_strerror(rc).decode())
         h, w = self.shape
-        if which in (TAP_SMOOTH, TAP_DIR, TAP_ANCHORS, TAP_EDGEIMG, TAP_SMOOTH2):
+        if which in (TAP_SMOOTH, TAP_DIR, TAP_ANCHORS, TAP_EDGEIMG, TAP_SMOOTH2, TAP_GRAY):
             return buf.reshape(h, w)
         if which in (TAP_GRAD, TAP_VGRAD):
             return buf.view(np.int16).reshape(h, w)
@@ -207,3 +229,26 @@ class StagPool:
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return [markers[f, :counts[f]] for f in range(F)], [poses[f, :counts[f]] for f in range(F)]
+
+    def detect_markers_batch_device(self, data_ptr: int, nframes: int, width: int, height: int, stride: int | None = None,
+                                    frame_stride: int | None = None, encoding: str = "mono8", K=None, D=None, marker_size: float = 0.18,
+                                    cap_per_frame: int = 64):
+        """detect_markers_batch on frames already resident on the pool's device (fid_stag_detect_markers_batch_device): frame f at
+        data_ptr + f * frame_stride (default: packed frames), mono8 / bgr8 / rgb8, no host staging.  -> (markers per frame, poses
+        per frame)."""
+        enc = _lib.ENC.get(encoding, -1)  # (any other encoding: the library refuses it, FID_E_UNSUPPORTED)
+        bpp = _lib.ENC_BYTES_PER_PIXEL.get(encoding, 1)
+        stride = stride or width * bpp
+        frame_stride = frame_stride or stride * height
+        markers = np.zeros((nframes, cap_per_frame), MARKER_DTYPE)
+        poses = np.zeros((nframes, cap_per_frame), POSE_DTYPE)
+        counts = np.zeros(max(nframes, 1), np.int32)
+        Kp = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        Dp = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
+        rc = self._L.fid_stag_detect_markers_batch_device(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride,
+                                                          frame_stride, enc, None if Kp is None else Kp.ctypes.data, Dp.ctypes.data,
+                                                          float(marker_size), markers.ctypes.data, poses.ctypes.data, cap_per_frame,
+                                                          counts.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return [markers[f, :counts[f]] for f in range(nframes)], [poses[f, :counts[f]] for f in range(nframes)]

@@ -7,6 +7,7 @@
 #define STAG_HOST_HPP
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <fstream>
 #include <stdexcept>
 #include <string>
@@ -66,6 +67,38 @@ class Stag {
             rc = fid_stag_detect_markers(ctx, data, cols, rows, step, m.data(), (int32_t)m.size(), &n);
         }
         if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_detect_markers: ") + fid_strerror(rc));
+        setMarkers(m, n);
+    }
+    // the same on a frame in device memory of this context's device (a decoded JPEG: fid_jpeg_device_ptr; mono8, bgr8 or rgb8,
+    // colour in the 15-bit gray form, include/fid_abi.h)
+    void detectMarkersDevice(const void *d_data, int cols, int rows, int step, fid_encoding enc = FID_ENC_MONO8)
+    {
+        std::vector<fid_stag_marker> m(256);
+        int32_t n = 0;
+        fid_status rc = fid_stag_detect_markers_device(ctx, d_data, cols, rows, step, enc, m.data(), (int32_t)m.size(), &n);
+        if (rc == FID_E_CAPACITY) {
+            m.resize((size_t)n);
+            rc = fid_stag_detect_markers_device(ctx, d_data, cols, rows, step, enc, m.data(), (int32_t)m.size(), &n);
+        }
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_detect_markers_device: ") + fid_strerror(rc));
+        setMarkers(m, n);
+    }
+    std::vector<Marker> getMarkerList() const { return markers; }
+
+    // Common::solvePnpSingle for the markers of the last detectMarkers() (stag_detect.cpp:140-165)
+    std::vector<fid_stag_pose_out> solvePnpSingle(const double K[9], const double D[5], double marker_size)
+    {
+        std::vector<fid_stag_pose_out> p(markers.empty() ? 1 : markers.size());
+        int32_t n = 0;
+        const fid_status rc = fid_stag_pose_last(ctx, K, D, marker_size, p.data(), (int32_t)p.size(), &n);
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_pose_last: ") + fid_strerror(rc));
+        p.resize((size_t)n);
+        return p;
+    }
+
+   private:
+    void setMarkers(const std::vector<fid_stag_marker> &m, int32_t n)
+    {
         markers.clear();
         for (int i = 0; i < n; i++) {
             Marker k;
@@ -82,20 +115,6 @@ class Stag {
             markers.push_back(k);
         }
     }
-    std::vector<Marker> getMarkerList() const { return markers; }
-
-    // Common::solvePnpSingle for the markers of the last detectMarkers() (stag_detect.cpp:140-165)
-    std::vector<fid_stag_pose_out> solvePnpSingle(const double K[9], const double D[5], double marker_size)
-    {
-        std::vector<fid_stag_pose_out> p(markers.empty() ? 1 : markers.size());
-        int32_t n = 0;
-        const fid_status rc = fid_stag_pose_last(ctx, K, D, marker_size, p.data(), (int32_t)p.size(), &n);
-        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_pose_last: ") + fid_strerror(rc));
-        p.resize((size_t)n);
-        return p;
-    }
-
-   private:
     fid_stag_ctx *ctx = nullptr;
     std::vector<uint64_t> words;
     std::vector<Marker> markers;
@@ -191,8 +210,12 @@ class StagNode {
     };
 
     StagNode(const Params &p, const std::string &data_dir = "fiducials_amd/data", int max_width = 1920, int max_height = 1080, int device = 0)
-        : params(p), stag(p.libraryHD, p.errorCorrection, false, data_dir, max_width, max_height, device)
+        : params(p), stag(p.libraryHD, p.errorCorrection, false, data_dir, max_width, max_height, device), maxW(max_width), maxH(max_height), dev(device)
     {
+    }
+    ~StagNode()
+    {
+        if (jctx) fid_jpeg_destroy(jctx);
     }
 
     // StagNode::cameraInfoCallback (:219-263): the first message is kept, later ones are ignored
@@ -244,9 +267,76 @@ class StagNode {
         int step = 0;
         if (!msgToGray(msg, &gray_, &data, &step)) return false;
         stag.detectMarkers(data, (int)msg.width, (int)msg.height, step);
+        publishMarkers(msg.header, out);
+        return true;
+    }
+
+    // the same callback for a frame that arrives compressed (the shipped cfg/single.yaml: is_compressed, the node then subscribes
+    // to <raw_image_topic>/compressed).  What the subscriber plugin's cv::imdecode hands to msgToGray, made gray the way
+    // cvtColor(BGR2GRAY) does in OpenCV 4.x (15-bit form): a JPEG is decoded ON THE DEVICE (fid_jpeg_decode, MONO8) and detected
+    // where it lies (fid_stag_detect_markers_device); a PNG is decoded on the host (fid_png_decode, MONO8) and goes the host road.
+    // false: nothing is published (no CameraInfo yet, or a frame that cannot be decoded: the plugin drops those).
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out)
+    {
+        out->markers.clear();
+        out->tf.clear();
+        out->array = Detection2DArray();
+        out->array_published = false;
+        if (!got_camera_info) return false;
+        const uint8_t *file = msg.data.data();
+        const int64_t nbytes = (int64_t)msg.data.size();
+        static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+        if (nbytes >= 8 && !std::memcmp(file, png_sig, 8)) {
+            fid_png_info pi = {};
+            fid_status rc = fid_png_probe(file, nbytes, &pi);
+            if (rc != FID_OK || pi.width > maxW || pi.height > maxH) {
+                last_error = rc != FID_OK ? std::string("compressed frame: ") + fid_png_last_error() : "compressed frame: larger than the context";
+                return false;
+            }
+            gray_.resize((size_t)pi.width * pi.height);
+            rc = fid_png_decode(file, nbytes, FID_ENC_MONO8, gray_.data(), (int64_t)gray_.size(), nullptr);
+            if (rc != FID_OK) {
+                last_error = std::string("compressed frame: ") + fid_png_last_error();
+                return false;
+            }
+            stag.detectMarkers(gray_.data(), pi.width, pi.height, pi.width);
+            publishMarkers(msg.header, out);
+            return true;
+        }
+        if (!jctx) {
+            const fid_status rc = fid_jpeg_create(dev, maxW, maxH, 1, &jctx);
+            if (rc != FID_OK) {
+                jctx = nullptr;
+                last_error = std::string("fid_jpeg_create: ") + fid_strerror(rc);
+                return false;
+            }
+        }
+        if (fid_jpeg_decode(jctx, &file, &nbytes, 1, FID_ENC_MONO8, nullptr, 0) != FID_OK) {
+            last_error = std::string("compressed frame: ") + fid_jpeg_last_error(jctx);
+            return false;
+        }
+        int32_t w = 0, h = 0, stride = 0;
+        int64_t fstride = 0;
+        const void *gray = fid_jpeg_device_ptr(jctx, &w, &h, &stride, &fstride);
+        stag.detectMarkersDevice(gray, w, h, stride, FID_ENC_MONO8);
+        publishMarkers(msg.header, out);
+        return true;
+    }
+
+    const std::vector<Marker> lastMarkers() const { return stag.getMarkerList(); }
+    const std::string &lastError() const { return last_error; }
+
+    Params params;
+    bool got_camera_info = false;
+    double K[9] = {0}, D[5] = {0};
+
+   private:
+    // the tail of imageCallback (:133-215): poses of the last detection and everything the node publishes for them
+    void publishMarkers(const Header &header, Outputs *out)
+    {
         const std::vector<Marker> markers = stag.getMarkerList();
         const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(K, D, (double)params.marker_size);
-        out->array.header = msg.header;
+        out->array.header = header;
         for (size_t i = 0; i < markers.size(); i++) {
             double q[4];
             rotationToQuaternion(poses[i].R, q);  // tf::Matrix3x3::getRotation
@@ -256,7 +346,7 @@ class StagNode {
             const std::string id = std::to_string(markers[i].id);
             if (params.publish_tf) {  // Common::publishTransform: tf first, then the PoseStamped
                 TransformStamped t;
-                t.header = msg.header;
+                t.header = header;
                 t.child_frame_id = params.tag_tf_prefix + id;
                 t.tx = pose.px; t.ty = pose.py; t.tz = pose.pz;
                 t.qx = pose.ox; t.qy = pose.oy; t.qz = pose.oz; t.qw = pose.ow;
@@ -264,12 +354,12 @@ class StagNode {
             }
             PoseStamped ps;
             ps.header.frame_id = id;  // (sic: the marker id, common.hpp:73)
-            ps.header.sec = msg.header.sec;
-            ps.header.nsec = msg.header.nsec;
+            ps.header.sec = header.sec;
+            ps.header.nsec = header.nsec;
             ps.pose = pose;
             out->markers.push_back(ps);
             Detection2D det;
-            det.header = msg.header;
+            det.header = header;
             ObjectHypothesisWithPose hyp;
             hyp.id = markers[i].id;
             hyp.pose = pose;
@@ -277,18 +367,13 @@ class StagNode {
             out->array.detections.push_back(det);
         }
         out->array_published = true;
-        return true;
     }
 
-    const std::vector<Marker> lastMarkers() const { return stag.getMarkerList(); }
-
-    Params params;
-    bool got_camera_info = false;
-    double K[9] = {0}, D[5] = {0};
-
-   private:
     Stag stag;
     std::vector<uint8_t> gray_;
+    int maxW = 0, maxH = 0, dev = 0;
+    fid_jpeg_ctx *jctx = nullptr;  // made when the first compressed JPEG frame arrives
+    std::string last_error;
 };
 
 }  // namespace fiducials_amd

@@ -46,7 +46,8 @@ extern "C" {
  * 6: + fid_stag_queue_stats (STag frames queued ahead of their own counts), fid_image_to_bgr8 (round 5).
  * 7: fid_detect* / fid_submit* take the raw-camera encodings themselves (FID_ENC_BAYER_*8, FID_ENC_MONO16 / BGR16 / RGB16 / BGRA16 /
  * RGBA16 [| FID_ENC_BIGENDIAN], FID_ENC_YUV422): the conversion cv_bridge::toCvCopy(msg, BGR8) + BGR2GRAY is folded into the
- * device's first kernel, so what crosses PCIe is the message's own bytes; + fid_encoding_from_string (round 6). */
+ * device's first kernel, so what crosses PCIe is the message's own bytes; + fid_encoding_from_string (round 6).  Added under 7
+ * (entry points only): fid_stag_detect_markers_device, fid_stag_detect_markers_batch_device, FID_STAG_TAP_GRAY. */
 #define FID_ABI_VERSION 7
 
 typedef enum fid_status {
@@ -273,6 +274,8 @@ void *fid_stream(fid_ctx *ctx);
  *   fid_stag_detect_markers            + PoseRefiner::refineMarkerPose = Stag::detectMarkers PoseRefiner.cpp:12-190
  *   fid_stag_pose_last                 Common::solvePnpSingle on centre + 4 corners         common.hpp:34-46
  *   fid_stag_detect_markers_batch      frames over several contexts (host threads inside the library)
+ *   fid_stag_detect_markers_device / fid_stag_detect_markers_batch_device
+ *                                      the same two on frames already in device memory (mono8, bgr8, rgb8)
  * The constructor mirrors Stag::Stag(int libraryHD, int errorCorrection, bool keepLogs) (include/stag/Stag.h:41); the
  * marker library (the published HDxx codewords) is handed over with fid_stag_load_library like the aruco dictionary. */
 typedef struct fid_stag_ctx fid_stag_ctx;
@@ -370,7 +373,9 @@ typedef enum fid_stag_tap {
     /* after fid_stag_detect_quads (VLINES then carry the corrected line directions): */
     FID_STAG_TAP_QUADS = 14,     /* fid_stag_quad [noQuads]: QuadDetector::getQuads() */
     /* after fid_stag_detect_markers_unrefined: */
-    FID_STAG_TAP_MARKERS = 15    /* fid_stag_marker [n]: Stag::markers before PoseRefiner::refineMarkerPose */
+    FID_STAG_TAP_MARKERS = 15,   /* fid_stag_marker [n]: Stag::markers before PoseRefiner::refineMarkerPose */
+    /* after any call that ran the front end, host or device: */
+    FID_STAG_TAP_GRAY = 16       /* uint8 [h][w] the gray image the pipeline read (a device frame's after k_stag_ingest) */
 } fid_stag_tap;
 /* Common::solvePnpSingle (stag_ros/common.hpp:34-46) for every marker of the last fid_stag_detect_markers* call: centre + four
  * corners against (0,0,0), (-h,h,0), (h,h,0), (h,-h,0), (-h,-h,0), h = float(marker_size / 2) (stag_detect.cpp:144-162) */
@@ -384,6 +389,23 @@ fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx
                                          int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, const double K[9], const double D[5],
                                          double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
                                          int32_t *n_per_frame);
+/* The two calls above on frames that are already in DEVICE memory (a decoded JPEG batch: fid_jpeg_device_ptr, a torch tensor, a
+ * previous stage's output): no pinned staging, no host -> device copy; the pipeline's first kernel reads the caller's frame and
+ * writes the context's gray image.  enc: FID_ENC_MONO8, FID_ENC_BGR8 or FID_ENC_RGB8 (what stag_ros::msgToGray accepts); colour
+ * goes to gray as cvtColor's RGB2Gray<uchar> in OpenCV 4.x's 15-bit form, (B*3735 + G*19235 + R*9798 + 2^14) >> 15 -- the form of
+ * fid_detect and of fid_jpeg_decode's MONO8 output.  (The host side's StagNode::msgToGray uses the 14-bit form, which differs by 1
+ * on 43 864 of the 2^24 colours)  Contract as fid_detect_device: the frames must be complete when the call
+ * is made (work on another stream finished) and lie on the contexts' device; they are read until the call returns.  Frame f is at
+ * d_frames + f * frame_stride_bytes.  Results, fid_stag_pose_last and the taps are those of the host calls on the same gray image.
+ * Refused, before any work: FID_E_UNSUPPORTED for another encoding; FID_E_INVALID_ARG for a NULL pointer, stride_bytes < width *
+ * bytes per pixel, a frame larger than a context, frames that are not device memory of the contexts' device (or reach past the
+ * allocation they start in), contexts on different devices. */
+fid_status fid_stag_detect_markers_device(fid_stag_ctx *ctx, const void *d_img, int32_t width, int32_t height, int32_t stride_bytes,
+                                          fid_encoding enc, fid_stag_marker *out, int32_t cap, int32_t *n_out);
+fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, fid_encoding enc,
+                                                const double K[9], const double D[5], double marker_size, fid_stag_marker *markers,
+                                                fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame);
 int64_t fid_stag_tap_bytes(fid_stag_ctx *ctx, fid_stag_tap which);
 fid_status fid_stag_tap_read(fid_stag_ctx *ctx, fid_stag_tap which, void *dst, int64_t dst_bytes);
 /* Frames queued ahead (ABI 6).  A context that has finished a frame sizes the next frame's launches by that frame's counts (plus a

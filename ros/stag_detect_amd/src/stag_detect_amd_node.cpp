@@ -17,6 +17,7 @@
 #include <image_transport/image_transport.h>
 #include <ros/ros.h>
 #include <sensor_msgs/CameraInfo.h>
+#include <sensor_msgs/CompressedImage.h>
 #include <sensor_msgs/Image.h>
 #include <tf2_ros/transform_broadcaster.h>
 #include <vision_msgs/Detection2DArray.h>
@@ -81,8 +82,10 @@ class RosStagNode {
         pnh_.param("device", device, 0);
         node_.reset(new fa::StagNode(p, data_dir, max_width, max_height, device));  // (throws std::invalid_argument like Stag::Stag)
 
-        image_sub_ = it_.subscribe(p.raw_image_topic, 1, &RosStagNode::imageCb, this,
-                                   image_transport::TransportHints(p.is_compressed ? "compressed" : "raw"));
+        // is_compressed (the shipped cfg/single.yaml): the CompressedImage messages themselves, decoded by the node -- a JPEG on the
+        // device, where the detector then reads it (StagNode::compressedImageCallback) -- instead of image_transport's CPU plugin
+        if (p.is_compressed) compressed_sub_ = nh_.subscribe(p.raw_image_topic + "/compressed", 1, &RosStagNode::compressedCb, this);
+        else image_sub_ = it_.subscribe(p.raw_image_topic, 1, &RosStagNode::imageCb, this, image_transport::TransportHints("raw"));
         caminfo_sub_ = nh_.subscribe(p.camera_info_topic, 1, &RosStagNode::camInfoCb, this);
         if (p.show_markers) debug_pub_ = it_.advertise("stag_ros/image_markers", 1);
         markers_pub_ = nh_.advertise<geometry_msgs::PoseStamped>(p.markers_topic, 10);
@@ -111,7 +114,28 @@ class RosStagNode {
             ROS_ERROR("stag_detect_amd: %s", e.what());
             return;
         }
-        if (node_->params.show_markers) {
+        publish(msg->header, out, msg.get());
+    }
+    void compressedCb(const sensor_msgs::CompressedImage::ConstPtr &msg)
+    {
+        fa::CompressedImage cm;
+        cm.header = to_host(msg->header);
+        cm.format = msg->format;
+        cm.data = msg->data;
+        fa::StagNode::Outputs out;
+        try {
+            if (!node_->compressedImageCallback(cm, &out)) return;
+        } catch (const std::exception &e) {
+            ROS_ERROR("stag_detect_amd: %s", e.what());
+            return;
+        }
+        publish(msg->header, out, nullptr);  // (no marker image: a compressed frame's pixels are on the device, not in a host message)
+    }
+    // what imageCb publishes for a detection; frame: the raw message the marker image is drawn on (nullptr: none)
+    void publish(const std_msgs::Header &header, const fa::StagNode::Outputs &out, const sensor_msgs::Image *frame)
+    {
+        if (frame && node_->params.show_markers) {
+            const sensor_msgs::Image *msg = frame;
             // the reference publishes Stag::drawMarkers() (circles, lines and id text through OpenCV's drawing tables); here: the
             // frame as bgr8 with the marker outlines as cv::line(LINE_8) draws them (fid_draw_detected_markers) -- a cue, not its pixels
             sensor_msgs::Image dbg;
@@ -173,8 +197,8 @@ class RosStagNode {
             // the fiducial_msgs contract (vertices + transforms) from the same detections
             fiducial_msgs::FiducialArray fva;
             fiducial_msgs::FiducialTransformArray fta;
-            fva.header = fta.header = msg->header;
-            fva.image_seq = fta.image_seq = (int32_t)msg->header.seq;
+            fva.header = fta.header = header;
+            fva.image_seq = fta.image_seq = (int32_t)header.seq;
             const std::vector<fa::Marker> markers = node_->lastMarkers();
             for (size_t i = 0; i < markers.size() && i < out.markers.size(); i++) {
                 fiducial_msgs::Fiducial f;
@@ -212,7 +236,7 @@ class RosStagNode {
     bool fiducial_msgs_output_ = false;
     image_transport::Subscriber image_sub_;
     image_transport::Publisher debug_pub_;
-    ros::Subscriber caminfo_sub_;
+    ros::Subscriber caminfo_sub_, compressed_sub_;
     ros::Publisher markers_pub_, array_pub_, vertices_pub_, transforms_pub_;
     tf2_ros::TransformBroadcaster broadcaster_;
 };
