@@ -100,6 +100,7 @@ SYMBOLS = [
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
     "fid_to_bgr", "fid_image_to_bgr8", "fid_encoding_from_string", "fid_draw_detected_markers", "fid_dict_load_file", "fid_dict_last_error",
+    "fid_to_bgr_device", "fid_draw_detected_markers_device", "fid_jpeg_marker_image",
 ]
 
 _LIB = None
@@ -258,6 +259,10 @@ def load():
     if hasattr(L, "fid_encoding_from_string"):  # (ABI 7; tools/gpu_stag_ab_libs.py also loads the builds of earlier rounds through FID_LIB)
         L.fid_encoding_from_string.argtypes = [C.c_char_p, i32, C.POINTER(C.c_int), C.POINTER(i32)]
     L.fid_draw_detected_markers.argtypes = [vp, i32, i32, i32, C.POINTER(FidMarker), i32, C.c_uint32]
+    if hasattr(L, "fid_to_bgr_device"):  # (the overlay on the device; FID_LIB may name a build from before it)
+        L.fid_to_bgr_device.argtypes = [vp, i32, i32, i32, i32, i64, C.c_int, vp, i32, i64]
+        L.fid_draw_detected_markers_device.argtypes = [vp, i32, i32, i32, i32, i64, C.POINTER(FidMarker), i32, C.POINTER(i32), C.c_uint32]
+        L.fid_jpeg_marker_image.argtypes = [vp, i32, C.c_int, C.POINTER(FidMarker), i32, C.c_uint32, vp, i64]
     L.fid_dict_load_file.argtypes = [C.c_char_p, i32, vp, i64, C.POINTER(FidDict)]
     L.fid_dict_last_error.argtypes = []
     L.fid_dict_last_error.restype = C.c_char_p

@@ -1119,6 +1119,8 @@ struct fid_jpeg_ctx {
     JpImage *h_imgs = nullptr;
     unsigned *h_flag = nullptr;
     uint16_t *h_lut = nullptr;
+    // fid_jpeg_marker_image (fid_draw.hip): the marker image of one frame and the markers drawn on it, made on first use
+    uint8_t *d_mark = nullptr, *d_mark_mk = nullptr;
     std::unordered_map<unsigned long long, int> lut_slot;
     std::vector<JpHuffSpec> lut_spec;  // the table behind every slot: a hash hit is only a hit if the table is the same
     int lut_next = 0, lut_cap = 0;  // cached 16-bit code tables: room for four new ones per frame of a call and 16 more
@@ -1257,7 +1259,7 @@ void fid_jpeg_destroy(fid_jpeg_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *dev[] = {c->d_scan, c->d_coefs, c->d_planes, c->d_out, c->d_imgs, c->d_luts, c->d_lut1, c->d_state[0], c->d_state[1], c->d_chg[0], c->d_chg[1],
-                   c->d_nblk, c->d_blkbase, c->d_flag};
+                   c->d_nblk, c->d_blkbase, c->d_flag, c->d_mark, c->d_mark_mk};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {c->h_scan, c->h_imgs, c->h_flag, c->h_lut};

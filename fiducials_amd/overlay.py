@@ -1,6 +1,7 @@
 """The /fiducial_images overlay (aruco_detect.cpp:381-387) on top of the C-ABI: `to_bgr` = cv_bridge::toCvCopy(msg, BGR8),
 `draw_detected_markers` = the part of aruco::drawDetectedMarkers that is restated exactly (the four LINE_8 sides of every
-marker; include/fid_abi.h says what is not drawn and why).  Host code on both sides: no GPU needed."""
+marker; include/fid_abi.h says what is not drawn and why).  Host code on both sides: no GPU needed.  `to_bgr_device` and
+`draw_detected_markers_device` below do the same, byte for byte, on torch tensors in GPU memory."""
 from __future__ import annotations
 
 import ctypes as C
@@ -63,4 +64,80 @@ def draw_detected_markers(bgr: np.ndarray, corners: np.ndarray, ids: np.ndarray 
     rc = _lib.load().fid_draw_detected_markers(bgr.ctypes.data, w, h, bgr.strides[0], mk, n, flags)
     if rc != _lib.FID_OK:
         raise FidError(rc, "fid_draw_detected_markers")
+    return bgr
+
+
+# ---- the same overlay on frames in device memory (torch uint8 tensors on the GPU): fid_to_bgr_device / fid_draw_detected_markers_device.
+# The bytes are those of to_bgr / draw_detected_markers, frame by frame.  The work queued on the tensors' current stream is waited
+# for first (the library reads frames that are complete when it is called and returns when it is done).
+_MARKER = np.dtype([("id", "<i4"), ("corners", "<f4", 8)])  # fid_marker
+_ENC_OF_CHANNELS = {1: "mono8", 3: "bgr8", 4: "bgra8"}
+
+
+def _frames(t, name: str):
+    """a [N, H, W, C] or [H, W, C] uint8 cuda tensor -> (batch tensor, single, N, H, W, C, row stride, frame stride) in bytes"""
+    import torch
+
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda:
+        raise ValueError(f"{name}: a uint8 tensor on the GPU is taken")
+    single = t.dim() == 3
+    b = t.unsqueeze(0) if single else t
+    if b.dim() != 4:
+        raise ValueError(f"{name}: [N, H, W, C] or [H, W, C] is taken, got {tuple(t.shape)}")
+    n, h, w, c = b.shape
+    if b.stride(3) != 1 or (w > 1 and b.stride(2) != c) or n < 1 or h < 1 or w < 1:
+        raise ValueError(f"{name}: the pixels of a row must be packed (strides (.., {c}, 1)), got {tuple(b.stride())}")
+    if h > 1 and b.stride(1) < w * c or n > 1 and b.stride(0) < 0:
+        raise ValueError(f"{name}: rows overlap, strides {tuple(b.stride())}")
+    return b, single, n, h, w, c, (b.stride(1) if h > 1 else w * c), (b.stride(0) if n > 1 else 0)
+
+
+def to_bgr_device(src, encoding: str | None = None, out=None):
+    """toCvCopy(BGR8) of [N, H, W, C] / [H, W, C] frames on the GPU (C = 1, 3 or 4: mono8, bgr8 / rgb8, bgra8 / rgba8; strided views
+    of packed pixels are taken).  out: a [N, H, W, 3] / [H, W, 3] uint8 tensor on the same GPU to write (strided rows allowed),
+    or None for a new one.  Returns out."""
+    import torch
+
+    s, single, n, h, w, c, sstride, sfstride = _frames(src, "to_bgr_device")
+    encoding = encoding or _ENC_OF_CHANNELS.get(c, "")
+    if _lib.ENC_BYTES_PER_PIXEL.get(encoding) != c or encoding not in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8"):
+        raise ValueError(f"to_bgr_device: {c} channels do not make {encoding!r}")
+    if out is None:
+        out = torch.empty((n, h, w, 3) if not single else (h, w, 3), dtype=torch.uint8, device=src.device)
+    o, _, on, oh, ow, oc, dstride, dfstride = _frames(out, "to_bgr_device(out)")
+    if (on, oh, ow, oc) != (n, h, w, 3):
+        raise ValueError(f"to_bgr_device: out is {tuple(out.shape)} for {n} frames of {h} x {w}")
+    torch.cuda.current_stream(src.device).synchronize()
+    rc = _lib.load().fid_to_bgr_device(s.data_ptr(), n, w, h, sstride, sfstride, _lib.ENC[encoding], o.data_ptr(), dstride, dfstride)
+    if rc != _lib.FID_OK:
+        raise FidError(rc, "fid_to_bgr_device")
+    return out
+
+
+def draw_detected_markers_device(bgr, corners, ids=None, flags: int = 0):
+    """draw_detected_markers in place on [N, H, W, 3] / [H, W, 3] BGR frames on the GPU (strided rows and frames allowed).  corners:
+    for one frame an (n, 4, 2) array; for N frames a sequence of N such arrays (ids likewise, one array per frame, or None).
+    Returns bgr."""
+    import torch
+
+    b, single, n, h, w, c, stride, fstride = _frames(bgr, "draw_detected_markers_device")
+    if c != 3:
+        raise ValueError("draw_detected_markers_device takes 3-channel BGR frames")
+    per = [corners] if single else list(corners)
+    pid = [ids] if single else (list(ids) if ids is not None else [None] * len(per))
+    if len(per) != n or len(pid) != n:
+        raise ValueError(f"draw_detected_markers_device: markers of {len(per)} frames for {n} frames")
+    per = [np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 8) for q in per]
+    cnt = np.array([len(q) for q in per], dtype=np.int32)
+    cap = max(int(cnt.max()), 1)
+    mk = np.zeros(n * cap, _MARKER)
+    for f, q in enumerate(per):
+        mk["corners"][f * cap:f * cap + len(q)] = q
+        if pid[f] is not None:
+            mk["id"][f * cap:f * cap + len(q)] = np.asarray(pid[f], dtype=np.int32).reshape(-1)[:len(q)]
+    torch.cuda.current_stream(bgr.device).synchronize()
+    rc = _lib.load().fid_draw_detected_markers_device(b.data_ptr(), n, w, h, stride, fstride, mk.ctypes.data_as(C.POINTER(FidMarker)), cap,
+                                                     cnt.ctypes.data_as(C.POINTER(C.c_int32)), flags)
+    if rc != _lib.FID_OK:
+        raise FidError(rc, "fid_draw_detected_markers_device")
     return bgr

@@ -153,6 +153,12 @@ class FiducialsNode {
     // on the device (fid_jpeg_decode: what the subscriber plugin's cv::imdecode + toCvCopy(BGR8) + BGR2GRAY produce) and the
     // detector runs on the device-resident gray image
     bool compressedImageCallback(const CompressedImage &msg, FiducialArray *out);
+    // ... and with the image /fiducial_images carries when ~publish_images is set: the decoded BGR8 frame with the marker outlines
+    // (drawn only when markers were found, :381), as imageCallback(msg, out, image) makes it for a raw frame.  A JPEG is then
+    // decoded to BGR8 on the device, detected there and drawn there (fid_jpeg_marker_image); a PNG is decoded to BGR8 and drawn on
+    // the host.  The vertices are those of the two-argument form.  image->data is empty unless an image is published; with
+    // publish_images off or image == nullptr the call is the two-argument form.
+    bool compressedImageCallback(const CompressedImage &msg, FiducialArray *out, Image *image);
     bool poseEstimateCallback(const FiducialArray &msg, FiducialTransformArray *out);  // :397-538 (fiducial_msgs view)
     bool poseEstimateCallback(const FiducialArray &msg, PoseOutputs *out);             // ... everything it publishes
     bool enableDetectionsCallback(bool data, std::string *message);  // :573-588

@@ -276,8 +276,15 @@ class StagNode {
     // cvtColor(BGR2GRAY) does in OpenCV 4.x (15-bit form): a JPEG is decoded ON THE DEVICE (fid_jpeg_decode, MONO8) and detected
     // where it lies (fid_stag_detect_markers_device); a PNG is decoded on the host (fid_png_decode, MONO8) and goes the host road.
     // false: nothing is published (no CameraInfo yet, or a frame that cannot be decoded: the plugin drops those).
-    bool compressedImageCallback(const CompressedImage &msg, Outputs *out)
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out) { return compressedImageCallback(msg, out, nullptr); }
+    // ... and the image the reference publishes on stag_ros/image_markers for every frame when show_markers is set (:123-133):
+    // Stag::drawMarkers() draws on the detector's GRAY image expanded to BGR (Drawer.cpp:123-129).  Here: that gray image as bgr8
+    // with the marker outlines of fid_draw_detected_markers (cv::line LINE_8; the reference's circles and text are not drawn,
+    // include/fid_abi.h) -- made on the device for a JPEG (fid_jpeg_marker_image on the gray already decoded there), on the host
+    // for a PNG.  image->data is empty unless an image is published.
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out, Image *image)
     {
+        if (image) image->data.clear();
         out->markers.clear();
         out->tf.clear();
         out->array = Detection2DArray();
@@ -301,6 +308,17 @@ class StagNode {
             }
             stag.detectMarkers(gray_.data(), pi.width, pi.height, pi.width);
             publishMarkers(msg.header, out);
+            if (params.show_markers && image) {
+                startMarkerImage(image, msg.header, pi.width, pi.height);
+                const std::vector<fid_marker> mk = markersToDraw();
+                fid_status rcd = fid_to_bgr(gray_.data(), pi.width, pi.height, pi.width, FID_ENC_MONO8, image->data.data(), (int64_t)image->data.size());
+                if (rcd == FID_OK)
+                    rcd = fid_draw_detected_markers(image->data.data(), pi.width, pi.height, (int32_t)image->step, mk.data(), (int32_t)mk.size(), 0);
+                if (rcd != FID_OK) {
+                    last_error = std::string("marker image: ") + fid_strerror(rcd);
+                    image->data.clear();
+                }
+            }
             return true;
         }
         if (!jctx) {
@@ -320,6 +338,16 @@ class StagNode {
         const void *gray = fid_jpeg_device_ptr(jctx, &w, &h, &stride, &fstride);
         stag.detectMarkersDevice(gray, w, h, stride, FID_ENC_MONO8);
         publishMarkers(msg.header, out);
+        if (params.show_markers && image) {
+            startMarkerImage(image, msg.header, w, h);
+            const std::vector<fid_marker> mk = markersToDraw();
+            const fid_status rcd = fid_jpeg_marker_image(jctx, 0, FID_ENC_MONO8, mk.data(), (int32_t)mk.size(), 0, image->data.data(),
+                                                         (int64_t)image->data.size());
+            if (rcd != FID_OK) {
+                last_error = std::string("marker image: ") + fid_strerror(rcd) + " (" + fid_jpeg_last_error(jctx) + ")";
+                image->data.clear();
+            }
+        }
         return true;
     }
 
@@ -331,6 +359,31 @@ class StagNode {
     double K[9] = {0}, D[5] = {0};
 
    private:
+    // the markers of the last detection as the drawer takes them (corners cast to float, as the ROS glue does)
+    std::vector<fid_marker> markersToDraw() const
+    {
+        std::vector<fid_marker> mk;
+        for (const Marker &m : stag.getMarkerList()) {
+            fid_marker k;
+            k.id = m.id;
+            for (int c = 0; c < 4; c++) {
+                k.corners[2 * c] = (float)m.corners[(size_t)c].x;
+                k.corners[2 * c + 1] = (float)m.corners[(size_t)c].y;
+            }
+            mk.push_back(k);
+        }
+        return mk;
+    }
+    static void startMarkerImage(Image *image, const Header &h, int32_t w, int32_t ht)
+    {
+        image->header = h;
+        image->height = (uint32_t)ht;
+        image->width = (uint32_t)w;
+        image->encoding = "bgr8";
+        image->is_bigendian = 0;
+        image->step = (uint32_t)w * 3;
+        image->data.resize((size_t)w * ht * 3);
+    }
     // the tail of imageCallback (:133-215): poses of the last detection and everything the node publishes for them
     void publishMarkers(const Header &header, Outputs *out)
     {

@@ -376,7 +376,29 @@ bool FiducialsNode::imageCallback(const Image &msg, FiducialArray *out, Image *i
 
 bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, FiducialArray *out)
 {
+    return compressedImageCallback(msg, out, nullptr);
+}
+
+// the sensor_msgs/Image fields of a marker image (cv_bridge keeps the source header; bgr8, tightly packed rows)
+static void startMarkerImage(Image *image, const Header &h, int32_t w, int32_t ht)
+{
+    image->header = h;
+    image->height = (uint32_t)ht;
+    image->width = (uint32_t)w;
+    image->encoding = "bgr8";
+    image->is_bigendian = 0;
+    image->step = (uint32_t)w * 3;
+    image->data.resize((size_t)w * ht * 3);
+}
+
+bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, FiducialArray *out, Image *image)
+{
+    if (image) image->data.clear();  // (filled only when the frame's marker image is published)
     if (enable_detections == false) return false;
+    // with ~publish_images the frame is decoded to BGR8 -- what cv::imdecode hands to toCvCopy(BGR8), the image the outlines are
+    // drawn on (:381-387) -- and the detector makes its gray from that; without, it is decoded straight to gray.  Both grays are
+    // OpenCV 4.x's 15-bit BGR2GRAY, so the vertices are the same either way.
+    const bool want = publish_images && image;
     if (!jctx) {
         const fid_status rc = fid_jpeg_create(dev, maxW, maxH, 1, &jctx);
         if (rc != FID_OK) {
@@ -397,8 +419,8 @@ bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, Fiducial
         fid_encoding enc = FID_ENC_MONO8;
         int px = 1;
         if (rc == FID_OK) {  // (the header is only looked at once it has been parsed)
-            enc = pi.gray ? FID_ENC_MONO8 : FID_ENC_BGR8;
-            px = pi.gray ? 1 : 3;
+            enc = pi.gray && !want ? FID_ENC_MONO8 : FID_ENC_BGR8;
+            px = enc == FID_ENC_MONO8 ? 1 : 3;
             png_frame.resize((size_t)pi.width * pi.height * px);
             rc = fid_png_decode(file, nbytes, enc, png_frame.data(), (int64_t)png_frame.size(), nullptr);
         }
@@ -412,23 +434,45 @@ bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, Fiducial
             last_error = fid_last_error(ctx);
             return false;
         }
-        return publishVertices(msg.header, n, out);
+        publishVertices(msg.header, n, out);
+        if (want) {  // the decoded BGR8 frame itself, with the outlines drawn on the host (as for a raw frame)
+            startMarkerImage(image, msg.header, pi.width, pi.height);
+            memcpy(image->data.data(), png_frame.data(), image->data.size());
+            if (n > 0) {
+                rc = fid_draw_detected_markers(image->data.data(), pi.width, pi.height, (int32_t)image->step, markers.data(), n, 0);
+                if (rc != FID_OK) {
+                    last_error = std::string("overlay: ") + fid_strerror(rc);
+                    image->data.clear();
+                }
+            }
+        }
+        return true;
     }
-    // gray = cvtColor(BGR2GRAY) of what cv::imdecode returns, left on the device
-    fid_status rc = fid_jpeg_decode(jctx, &file, &nbytes, 1, FID_ENC_MONO8, nullptr, 0);
+    // gray = cvtColor(BGR2GRAY) of what cv::imdecode returns, left on the device (or that BGR8 image itself, see above)
+    const fid_encoding dec = want ? FID_ENC_BGR8 : FID_ENC_MONO8;
+    fid_status rc = fid_jpeg_decode(jctx, &file, &nbytes, 1, dec, nullptr, 0);
     if (rc != FID_OK) {  // (the subscriber plugin logs and drops a frame it cannot decode)
         last_error = std::string("compressed frame: ") + fid_jpeg_last_error(jctx);
         return false;
     }
     int32_t w = 0, h = 0, stride = 0, n = 0;
     int64_t fstride = 0;
-    const void *gray = fid_jpeg_device_ptr(jctx, &w, &h, &stride, &fstride);
-    rc = fid_detect_device(ctx, gray, 1, w, h, stride, fstride, FID_ENC_MONO8, markers.data(), (int32_t)markers.size(), &n);
+    const void *frame = fid_jpeg_device_ptr(jctx, &w, &h, &stride, &fstride);
+    rc = fid_detect_device(ctx, frame, 1, w, h, stride, fstride, dec, markers.data(), (int32_t)markers.size(), &n);
     if (rc != FID_OK) {
         last_error = fid_last_error(ctx);
         return false;
     }
-    return publishVertices(msg.header, n, out);
+    publishVertices(msg.header, n, out);
+    if (want) {  // drawn on the device where the frame lies (every detected marker, ignored ids included, as for a raw frame)
+        startMarkerImage(image, msg.header, w, h);
+        rc = fid_jpeg_marker_image(jctx, 0, FID_ENC_BGR8, markers.data(), n, 0, image->data.data(), (int64_t)image->data.size());
+        if (rc != FID_OK) {
+            last_error = std::string("overlay: ") + fid_strerror(rc) + " (" + fid_jpeg_last_error(jctx) + ")";
+            image->data.clear();
+        }
+    }
+    return true;
 }
 
 bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, FiducialTransformArray *out)

@@ -505,6 +505,26 @@ fid_status fid_to_bgr(const uint8_t *img, int32_t width, int32_t height, int32_t
                        int64_t out_bytes);
 fid_status fid_draw_detected_markers(uint8_t *bgr, int32_t width, int32_t height, int32_t stride_bytes, const fid_marker *markers,
                                      int32_t n, uint32_t flags);
+/* The same two steps on frames in DEVICE memory, for frames that never reach the host (a JPEG decoded on the device, a caller's
+ * frames in HBM).  Contract as fid_detect_device: the frames are complete when the call is made, the call returns when the work
+ * is done.  The device is the one the memory lies on; every byte read or written must be device memory of that one device,
+ * inside its allocation (FID_E_INVALID_ARG otherwise).  The bytes are those of the host calls, frame by frame.
+ * fid_to_bgr_device: nframes frames, any source and destination row / frame strides (frames written must not overlap, nor
+ * overlap the source).  fid_draw_detected_markers_device: in place; frame f's markers are markers[f * cap_per_frame ..
+ * + n_per_frame[f]) in HOST memory; cap_per_frame at most 4096 (the largest max_markers_per_frame of any context). */
+fid_status fid_to_bgr_device(const void *d_src, int32_t nframes, int32_t width, int32_t height, int32_t stride_bytes,
+                             int64_t frame_stride_bytes, fid_encoding enc, void *d_bgr, int32_t bgr_stride_bytes,
+                             int64_t bgr_frame_stride_bytes);
+fid_status fid_draw_detected_markers_device(void *d_bgr, int32_t nframes, int32_t width, int32_t height, int32_t stride_bytes,
+                                            int64_t frame_stride_bytes, const fid_marker *markers, int32_t cap_per_frame,
+                                            const int32_t *n_per_frame, uint32_t flags);
+/* For a caller without a HIP allocator (the g++-only host side): the marker image of frame `frame` of the last fid_jpeg_decode,
+ * made on the device in a buffer the JPEG context owns and copied once to host_bgr (width * 3 bytes per row, tightly packed;
+ * FID_E_CAPACITY if host_bytes is less than width * height * 3).  base FID_ENC_BGR8: the decoded colour image (that decode must
+ * have been to BGR8); FID_ENC_MONO8: the decoded gray image expanded to BGR (that decode must have been to MONO8).  At most 4096
+ * markers (host memory). */
+fid_status fid_jpeg_marker_image(fid_jpeg_ctx *ctx, int32_t frame, fid_encoding base, const fid_marker *markers, int32_t n,
+                                 uint32_t flags, uint8_t *host_bgr, int64_t host_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * aruco::getPredefinedDictionary(dicno) (aruco_detect.cpp:671, ~dictionary :611) from a table file the DEPLOYER has.  OpenCV's

@@ -123,13 +123,25 @@ class RosStagNode {
         cm.format = msg->format;
         cm.data = msg->data;
         fa::StagNode::Outputs out;
+        fa::Image markers;  // (the detector's gray image with the outlines; a JPEG frame's is drawn on the device)
         try {
-            if (!node_->compressedImageCallback(cm, &out)) return;
+            if (!node_->compressedImageCallback(cm, &out, node_->params.show_markers ? &markers : nullptr)) return;
         } catch (const std::exception &e) {
             ROS_ERROR("stag_detect_amd: %s", e.what());
             return;
         }
-        publish(msg->header, out, nullptr);  // (no marker image: a compressed frame's pixels are on the device, not in a host message)
+        if (node_->params.show_markers && !markers.data.empty()) {
+            sensor_msgs::Image dbg;
+            dbg.header = to_ros(markers.header);
+            dbg.height = markers.height;
+            dbg.width = markers.width;
+            dbg.encoding = markers.encoding;
+            dbg.is_bigendian = markers.is_bigendian;
+            dbg.step = markers.step;
+            dbg.data.swap(markers.data);
+            debug_pub_.publish(dbg);
+        }
+        publish(msg->header, out, nullptr);  // (the marker image is published above)
     }
     // what imageCb publishes for a detection; frame: the raw message the marker image is drawn on (nullptr: none)
     void publish(const std_msgs::Header &header, const fa::StagNode::Outputs &out, const sensor_msgs::Image *frame)
