@@ -8,10 +8,14 @@ DICT_5X5_250 markers each (BASELINE cfg 3), the batch being resident in HBM when
 sides.  With --gpus N every rank owns an independent stream of frames on its own GPU (cfg 4): no
 data-path collective, scaling = "weak".
 
-Also reported on the same JSON line:
-  roofline      the dominant kernel's algorithmic bytes / its hipEvent-measured launch time vs 8 TB/s
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line; beside the headline the line carries
+  roofline      the dominant kernel's algorithmic bytes / its hipEvent-measured launch time vs 8 TB/s (from the timed steps)
+With --full it also measures, after the timed steps and outside them:
   cpu_baseline  the CPU oracle (restatement of the reference's OpenCV path) timed on the host cores
                 of this box on a bounded sample of the same frames (rank 0, N = 1 only)
+  extra         cfg 2 single-frame latency, cfg 3 from host memory, the JPEG ingest, a short cfg 5 (STag) run (N = 1)
+  one_at_a_time the same steps one call after the other on one context
+  host_fed      N > 1: every rank's host-fed rate beside the resident one
 """
 from __future__ import annotations
 
@@ -334,15 +338,17 @@ def _gen_one(args):
     return make_frame(get_predefined_dictionary(dname), seed, width=W, height=H, n_markers=MARKERS).image
 
 
-def make_frames(seeds, dname="DICT_5X5_250"):
-    """Synthetic frames, generated on the host cores with a process pool and cached."""
-    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"fid_synth_{dname}_{W}x{H}_{MARKERS}")
-    os.makedirs(cache, exist_ok=True)
+def make_frames(seeds, dname="DICT_5X5_250", cache=True):
+    """Synthetic frames, generated on the host cores with a process pool.  cache: keep them under TMPDIR for
+    the next caller (tests, tools); a run of this script makes its own (cache=False), never reading what an earlier run left."""
+    cdir = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"fid_synth_{dname}_{W}x{H}_{MARKERS}") if cache else None
+    if cdir:
+        os.makedirs(cdir, exist_ok=True)
     out = [None] * len(seeds)
     todo = []
     for i, s in enumerate(seeds):
-        p = os.path.join(cache, f"{s}.npy")
-        if os.path.exists(p):
+        p = os.path.join(cdir, f"{s}.npy") if cdir else None
+        if p and os.path.exists(p):
             try:
                 out[i] = np.load(p)
                 continue
@@ -358,8 +364,10 @@ def make_frames(seeds, dname="DICT_5X5_250"):
             imgs = pool.map(_gen_one, [(s, dname) for _, s in todo], chunksize=1)
         for (i, s), im in zip(todo, imgs):
             out[i] = im
+            if not cdir:
+                continue
             try:
-                np.save(os.path.join(cache, f"{s}.npy"), im)
+                np.save(os.path.join(cdir, f"{s}.npy"), im)
             except Exception:
                 pass
     return np.stack(out)
@@ -765,25 +773,32 @@ def jpeg_side_result(local_rank, frames):
 STAG_HD, STAG_EC, STAG_MARKERS, STAG_UNIQUE = 21, 7, 12, 16
 
 
-def make_stag_frames(seeds):
+def make_stag_frames(seeds, cache=True):
     """The cfg 5 frames: 1920x1080, every one of the 12 ids of library HD21 once per frame (round 2 drew 20 markers from the
-    12 ids and checkDuplicate threw half of the rendered work away: the line said 20 markers and found 10)."""
+    12 ids and checkDuplicate threw half of the rendered work away: the line said 20 markers and found 10).  cache: as in
+    make_frames."""
     import multiprocessing as mp
 
-    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"fid_synth_stag_HD{STAG_HD}_{W}x{H}_{STAG_MARKERS}")
-    os.makedirs(cache, exist_ok=True)
+    cdir = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"fid_synth_stag_HD{STAG_HD}_{W}x{H}_{STAG_MARKERS}") if cache else None
+    if cdir:
+        os.makedirs(cdir, exist_ok=True)
     out, todo = {}, []
     for sd in seeds:
         try:
-            out[sd] = np.load(os.path.join(cache, f"{sd}.npy"))
+            if cdir:
+                out[sd] = np.load(os.path.join(cdir, f"{sd}.npy"))
+                continue
         except Exception:  # noqa: BLE001
-            todo.append(sd)
+            pass
+        todo.append(sd)
     if todo:
         with mp.get_context("fork").Pool(max(1, min(len(todo), (os.cpu_count() or 2), 32))) as pool:
             for sd, im in zip(todo, pool.map(_gen_stag_one, todo, chunksize=1)):
                 out[sd] = im
+                if not cdir:
+                    continue
                 try:
-                    np.save(os.path.join(cache, f"{sd}.npy"), im)
+                    np.save(os.path.join(cdir, f"{sd}.npy"), im)
                 except Exception:  # noqa: BLE001
                     pass
     return [out[sd] for sd in seeds]
@@ -824,7 +839,7 @@ def stag_side_result(local_rank, args):
     #  kernel launched once per group -- round 6: a launch carries frame 0's arguments and 32 bytes per further frame, so a group is no
     #  longer held to the 16 frames whose argument tuples fit 4 KB.  Rounds 3 - 5: 128 slots = eight groups of 16, 256 frames per step.)
     hd, ec, B, T = STAG_HD, STAG_EC, 1024, 256  # (r5 shape 256 / 128: 5.5 k frames/s with this library; 1 024 / 256: 7.3 k; 2 048 / 256: 7.6 k)
-    frames = make_stag_frames(shard_seeds(0, 1, STAG_UNIQUE, "stag"))
+    frames = make_stag_frames(shard_seeds(0, 1, STAG_UNIQUE, "stag"), cache=False)
     pool = fstag.StagPool(hd, ec, n_contexts=T, max_width=W, max_height=H, device=local_rank)
     batch = np.stack([frames[i % len(frames)] for i in range(B)])
     pool.detect_markers_batch(batch, synth.K_DEFAULT, None, 0.18)
@@ -895,7 +910,7 @@ def main_stag(args):
     from fiducials_amd import stag as fstag, synth
 
     hd, ec, B = STAG_HD, STAG_EC, min(args.batch, 256)
-    frames = make_stag_frames(shard_seeds(rank, world, min(B, STAG_UNIQUE), "stag"))
+    frames = make_stag_frames(shard_seeds(rank, world, min(B, STAG_UNIQUE), "stag"), cache=False)
     # several contexts side by side (fid_stag_detect_markers_batch: one host thread + one HIP stream per context inside the
     # library): a frame's work is a chain of small kernels, several frames in flight fill the GPU
     T = max(1, min(args.streams, B))
@@ -948,7 +963,7 @@ def main_stag(args):
                          "frac": round(fps / n_gpus * algo / 1e9 / HBM_PEAK_GBS, 6), "traffic": None},
             "ranks": ranks,
         }
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and not args.no_cpu_baseline:  # (--full only: see main)
             from oracle import stag_ref
 
             if stag_ref.available():
@@ -1115,7 +1130,7 @@ def main_dryrun(args):
     fps, dt = job_throughput(B * args.steps, world, dt_local, dist, "cpu")
     # (the host-fed leg of a multi-GPU run, as a stand-in: the same keys the real run reports per rank)
     host_leg = None
-    if world > 1 or os.environ.get("FID_BENCH_HOST_LEG") == "1":
+    if (world > 1 or os.environ.get("FID_BENCH_HOST_LEG") == "1") and not args.no_extras:
         barrier()
         th = time.perf_counter()
         for _ in range(2):
@@ -1201,8 +1216,11 @@ def main():
                          "streams, one PCIe link per GPU).  jpeg: every step's frames are JPEG files in host memory (the node's launch "
                          "default transport:=compressed), decoded on the device ahead of the detector by the rank's decoder threads "
                          "(host_budget).  Both say so in config.feed and are not the headline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg 2 latency and cfg 5 (STag) side results")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what is not the headline: the CPU baselines, the cfg 2 / cfg 3-from-host / "
+                         "JPEG / cfg 5 side results (extra), one_at_a_time, and with --gpus N > 1 the host-fed rate of every rank")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full without extra, one_at_a_time and the host-fed rates")
     ap.add_argument("--stag-side-child", action="store_true", help=argparse.SUPPRESS)  # the cfg 5 side result, own process
     ap.add_argument("--streams", type=int, default=128, help="stag workload: frame slots per GPU (groups of 16 in lockstep)")
     ap.add_argument("--workload", choices=["aruco", "stag"], default="aruco",
@@ -1213,6 +1231,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing after them
+        args.no_cpu_baseline = args.no_extras = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # N ranks of this script, one per GPU; rank 0 prints the line
     if DRYRUN:
@@ -1247,7 +1267,7 @@ def main():
     unique = min(unique, B)
     # cfg 3: seeds 1000 + i ; cfg 4 stream s: 10000 * s + i
     seeds = shard_seeds(rank, world, unique)
-    frames_u = make_frames(seeds)
+    frames_u = make_frames(seeds, cache=False)
 
     import torch
 
@@ -1322,7 +1342,7 @@ def main():
     if args.dump_outputs and rank == 0:  # (before any other call reuses the context that collected the last step)
         dump_outputs(args.dump_outputs, [seeds[i % unique] for i in range(B)], *aruco_last_outputs(pipe.detectors[pipe.last_collected]))
     # BASELINE cfg 4 is eight CAMERA streams: frames arrive in host memory, and on an 8-GPU node the honest per-GPU row is the
-    # host-fed one (one PCIe link per GPU, the host's memory system shared by all ranks).  So a multi-GPU run measures it too, every
+    # host-fed one (one PCIe link per GPU, the host's memory system shared by all ranks).  So a multi-GPU --full run measures it too, every
     # rank at the same time, OUTSIDE the timed region of `value`: the same batch from a pinned ring of two (fid_submit_batch), a few
     # steps.  Per rank: both rates, the link's GB/s, the NUMA pin.  (N = 1: extra.cfg3_from_host carries it; FID_BENCH_HOST_LEG=1 forces it.)
     host_leg = None
@@ -1439,7 +1459,7 @@ def main():
             try:
                 # in a process of its own: the contexts of the runs above keep their hardware queues after they are closed,
                 # and 16 more streams on top oversubscribe the queues (measured: 310 frames/s in-process, 1300 alone)
-                cmd = [sys.executable, os.path.abspath(__file__), "--stag-side-child", "--gpus", "1"]
+                cmd = [sys.executable, os.path.abspath(__file__), "--stag-side-child", "--gpus", "1", "--full"]
                 if args.no_cpu_baseline:
                     cmd.append("--no-cpu-baseline")
                 env = dict(os.environ, LOCAL_RANK=str(local_rank))

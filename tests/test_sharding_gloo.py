@@ -74,6 +74,8 @@ def test_bench_launcher_spawns_one_rank_per_gpu():
     # whole-job rate = all ranks' frames / the slowest rank's time: rank 1 sleeps twice as long as rank 0
     slow = min(x["fps"] for x in r["ranks"])
     assert r["value"] <= 2 * slow * 1.05 and r["value"] < sum(x["fps"] for x in r["ranks"])
+    # a plain run measures nothing after its timed steps: the host-fed leg is --full's
+    assert "host_fed" not in r and not any("host_fed_fps" in x for x in r["ranks"])
 
 
 def test_bench_refuses_a_rank_count_that_is_not_running():
@@ -91,7 +93,7 @@ def test_eight_ranks_dry_run_seeds_budget_and_affinity():
     host gives it, and every rank pins itself to the CPUs of its GPU's NUMA node (here: a made-up node map handed to the dry run,
     ranks 0-3 on node 0, 4-7 on node 1 where the machine has such nodes; ranks of one node get disjoint slices)."""
     import json
-    out = _run_bench(["--gpus", "8", "--steps", "2", "--warmup", "0", "--feed", "jpeg"],
+    out = _run_bench(["--gpus", "8", "--steps", "2", "--warmup", "0", "--feed", "jpeg", "--full"],
                      {"FID_BENCH_DRYRUN": "cpu", "FID_BENCH_DRYRUN_NODES": "0,0,0,0,1,1,1,1"}, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -149,9 +151,9 @@ def test_two_ranks_with_real_kernels_on_one_gpu():
     assert r["config"]["frames_per_step"] == 64 and r["value"] > 0
     # whole-job rate = both ranks' frames / the slower rank's time
     assert r["value"] <= 2 * min(x["fps"] for x in r["ranks"]) * 1.05
-    # (round 6) WITHOUT --no-extras -- what the driver's scaling run starts: after the timed region every rank also measures the
-    # host-fed rate (pinned ring, fid_submit_batch), and the line carries both per rank with the link's GB/s and the pin
-    out = _run_bench(["--gpus", "2", "--batch", "32", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    # (round 6) --full WITHOUT --no-extras: after the timed region every rank also measures the host-fed rate (pinned ring,
+    # fid_submit_batch), and the line carries both per rank with the link's GB/s and the pin
+    out = _run_bench(["--gpus", "2", "--batch", "32", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                      {"FID_BENCH_OVERSUBSCRIBE": "1"}, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

@@ -30,4 +30,4 @@ gzip -9 $OUT/*_trace.csv; ls -la $OUT
 # --- and that the round's first changes (advice items) left the STag road where it was
 ( time timeout 900 python -m pytest tests/test_gpu_stag.py tests/test_overlay.py -m gpu -q -x --timeout 400 ) > $OUT/pytest_stag.log 2>&1; tail -5 $OUT/pytest_stag.log
 ( timeout 300 python tools/gpu_stag_spec_stress.py 120 3 ) > $OUT/spec_stress.log 2>&1; tail -4 $OUT/spec_stress.log
-( time timeout 600 python bench.py --steps 20 --warmup 5 ) > $OUT/bench.log 2>&1; grep '^{' $OUT/bench.log > $OUT/bench.json; cut -c1-400 $OUT/bench.json
+( time timeout 600 python bench.py --steps 20 --warmup 5 --full ) > $OUT/bench.log 2>&1; grep '^{' $OUT/bench.log > $OUT/bench.json; cut -c1-400 $OUT/bench.json
