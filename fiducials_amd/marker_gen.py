@@ -105,16 +105,7 @@ def write_pdf(path: str, marker_ids, dicno: int = 7, paper_size=PAPER["letter"],
         _check_printable(d, mid, allow_fillers)
     k = 72 / 25.4  # mm -> pt
     pw, ph = paper_size
-    objs = []  # (object number -> bytes), numbered from 1
-
-    def add(body: bytes) -> int:
-        objs.append(body)
-        return len(objs)
-
-    font = add(b"<< /Type /Font /Subtype /Type1 /BaseFont /Helvetica >>")
-    pages_id = 2 + 0  # reserved below
-    add(b"")  # placeholder for /Pages (object 2)
-    page_ids = []
+    streams = []
     for mid in marker_ids:
         if not 0 <= mid < d.n_markers:
             raise ValueError(f"marker id {mid} not in {d.name}")
@@ -135,9 +126,28 @@ def write_pdf(path: str, marker_ids, dicno: int = 7, paper_size=PAPER["letter"],
             c.append("%.3f %.3f m %.3f %.3f l S" % (x1 * k, (ph - y1) * k, x2 * k, (ph - y2) * k))
         c.append("0 g")
         for x, y, size, s in texts:
-            width = 0.5 * size * len(s)  # Helvetica averages half an em per character: centred well enough for a label
-            c.append("BT /F1 %g Tf %.3f %.3f Td (%s) Tj ET" % (size, x * k - width / 2, (ph - y) * k, s.replace("(", "\\(").replace(")", "\\)")))
-        stream = "\n".join(c).encode("ascii")
+            c.append(pdf_text(x, y, size, s, ph))
+        streams.append("\n".join(c).encode("ascii"))
+    with open(path, "wb") as fh:
+        fh.write(pdf_file(streams, paper_size))
+
+
+def pdf_file(page_streams, paper_size) -> bytes:
+    """A complete PDF 1.4 file, one page of `paper_size` (mm) per content stream; the streams draw in points and may use the
+    built-in Helvetica as /F1."""
+    k = 72 / 25.4  # mm -> pt
+    pw, ph = paper_size
+    objs = []  # (object number -> bytes), numbered from 1
+
+    def add(body: bytes) -> int:
+        objs.append(body)
+        return len(objs)
+
+    font = add(b"<< /Type /Font /Subtype /Type1 /BaseFont /Helvetica >>")
+    pages_id = 2 + 0  # reserved below
+    add(b"")  # placeholder for /Pages (object 2)
+    page_ids = []
+    for stream in page_streams:
         content = add(b"<< /Length %d >>\nstream\n" % len(stream) + stream + b"\nendstream")
         page_ids.append(add(b"<< /Type /Page /Parent 2 0 R /MediaBox [0 0 %.3f %.3f] /Contents %d 0 R /Resources << /Font << /F1 %d 0 R >> >> >>"
                             % (pw * k, ph * k, content, font)))
@@ -153,8 +163,14 @@ def write_pdf(path: str, marker_ids, dicno: int = 7, paper_size=PAPER["letter"],
     for off in offsets:
         out += b"%010d 00000 n \n" % off
     out += b"trailer\n<< /Size %d /Root %d 0 R >>\nstartxref\n%d\n%%%%EOF\n" % (len(objs) + 1, catalog, xref)
-    with open(path, "wb") as fh:
-        fh.write(bytes(out))
+    return bytes(out)
+
+
+def pdf_text(x: float, y: float, size: float, s: str, page_height: float) -> str:
+    """The content-stream operators of a label in Helvetica (/F1) of `size` pt, centred on x, baseline at y (mm, origin top left)."""
+    k = 72 / 25.4  # mm -> pt
+    width = 0.5 * size * len(s)  # Helvetica averages half an em per character: centred well enough for a label
+    return "BT /F1 %g Tf %.3f %.3f Td (%s) Tj ET" % (size, x * k - width / 2, (page_height - y) * k, s.replace("(", "\\(").replace(")", "\\)"))
 
 
 def main(argv=None) -> int:
