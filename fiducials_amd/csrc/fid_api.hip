@@ -673,8 +673,8 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         const int gm = Fs >= 16 ? 1 : 16 / Fs;
         const int wb2 = wb > 1 ? wb / 2 : 1;  // the two walks share the CUs' LDS
         const int cap1 = pts_cap_first(P);
-        const size_t lds1 = (size_t)cap1 * sizeof(uint32_t) + (size_t)K4_SHORT_STACK * sizeof(int2);
-        const size_t lds2 = (size_t)(P.maxPerim + 1) * sizeof(uint32_t) + (size_t)K4_LONG_STACK * sizeof(int2);
+        const size_t lds1 = k_approx_lds_bytes(cap1);
+        const size_t lds2 = k_approx_lds_bytes(P.maxPerim + 1);
         if (c->whole_border_walk) {
             hipLaunchKernelGGL(k_find_starts<false>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
                                (uint2 *)nullptr, P);
@@ -688,11 +688,11 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             mark(ST_WALK + 1);
             // ---- K4: short contours with a small LDS footprint first, then the long / flagged ones
             fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, c->d_global, P, cap1,
-                               K4_SHORT_STACK, 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, P, cap1, 0,
+                               (const uint32_t *)nullptr, (const uint32_t *)nullptr);
             fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, c->d_global, P,
-                               P.maxPerim + 1, K4_LONG_STACK, 1, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, P,
+                               P.maxPerim + 1, 1, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
             mark(ST_APPROX + 1);
         } else {
             const size_t MCn = (size_t)P.maxContours;
@@ -753,11 +753,11 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                                recs, counts, c->d_global, P, 1, 0);
             hipLaunchKernelGGL(k_seg_copy, dim3(cpb / 4 > 0 ? cpb / 4 : 1, Fs), dim3(256), 0, sa, recs, tab, pool, dense, counts, P, 1);
             fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(32 * gm, Fs), dim3(64), lds1, sa, contours, tab, pool, cands, counts, c->d_global, P, cap1,
-                               K4_SHORT_STACK, 0, dense, cbase, 2);
+            hipLaunchKernelGGL(k_approx, dim3(32 * gm, Fs), dim3(64), lds1, sa, contours, tab, pool, cands, counts, P, cap1, 0,
+                               dense, cbase, 2);
             fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(8 * gm, Fs), dim3(64), lds2, sa, contours, tab, pool, cands, counts, c->d_global, P,
-                               P.maxPerim + 1, K4_LONG_STACK, 1, dense, cbase, 2);
+            hipLaunchKernelGGL(k_approx, dim3(8 * gm, Fs), dim3(64), lds2, sa, contours, tab, pool, cands, counts, P,
+                               P.maxPerim + 1, 1, dense, cbase, 2);
             if (c->profile) (void)hipEventRecord(ev[17], sa);
             HIPCHK(c, hipEventRecord(c->aux_join[sb], sa));
             // -- main stream, continued
@@ -776,11 +776,11 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             mark(ST_WALK + 1);
             chain_point(2);
             fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, c->d_global, P, cap1,
-                               K4_SHORT_STACK, 0, dense, cbase, 1);
+            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, P, cap1, 0,
+                               dense, cbase, 1);
             fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, c->d_global, P,
-                               P.maxPerim + 1, K4_LONG_STACK, 1, dense, cbase, 1);
+            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, P,
+                               P.maxPerim + 1, 1, dense, cbase, 1);
             mark(ST_APPROX + 1);
             chain_point(3);
             if (chainp) {
@@ -964,7 +964,6 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
         c->last_error = "internal capacity exceeded:";
         if (ov & 1u) c->last_error += " max_starts_per_frame";
         if (ov & 2u) c->last_error += " max_contours_per_frame";
-        if (ov & 4u) c->last_error += " approximation stack";
         if (ov & 8u) c->last_error += " max_points_per_frame";
         c->last_error += " (raise fid_limits)";
         rc = FID_E_CAPACITY;

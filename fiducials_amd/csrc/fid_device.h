@@ -184,7 +184,7 @@ struct DevCounts {
 
 // global counters
 struct DevGlobal {
-    unsigned overflow;  // bit0 starts/survivors, bit1 contours, bit2 approxPolyDP stack, bit3 point pool
+    unsigned overflow;  // bit0 starts/survivors, bit1 contours, bit3 point pool (bit2: unused -- k_approx's slice stack is bounded by the vertex limit)
     unsigned pad[3];
     unsigned long long dbg[32];  // FID_DEBUG_STATS builds: walk-loop statistics
 };

@@ -3010,9 +3010,17 @@ __global__ __launch_bounds__(64) void k_seg_cycles(const uint2 *__restrict__ see
 
 // points per contour the first (short-LDS) launch of k_approx accepts
 #define K4_SHORT_PTS 2048
-#define K4_SHORT_STACK 256
-#define K4_LONG_STACK 1024
+// Most vertices a raw polygon may have and still end as a quad: the clean-up pass drops at most one vertex per two steps of its
+// cnt steps, ceil(cnt / 2) of them, so 9 can end as 4 and 10 cannot end below 5.
+#define K4_MAX_RAW 9
+// Slice stack entries.  Every slice on the stack ends as at least one vertex of the raw polygon (it is accepted and emits its
+// start point, or split into two slices that each do), so new_count + top never falls, ends as the raw polygon's vertex count
+// and is checked before every pop: a contour is rejected as soon as it exceeds K4_MAX_RAW -- exactly the contours whose raw polygon
+// has more vertices than that.  So top <= 9 at a pop and <= 10 after the two pushes that may follow it, whatever the contour.
+#define K4_STACK 16
 __device__ __host__ inline int pts_cap_first(const DevParams &P) { return P.maxPerim < K4_SHORT_PTS ? P.maxPerim : K4_SHORT_PTS; }
+// dynamic LDS of a k_approx launch that takes contours of up to pts_cap points (codes8_to_points writes whole groups of eight)
+inline size_t k_approx_lds_bytes(int pts_cap) { return (size_t)((pts_cap + 7) & ~7) * sizeof(uint32_t); }
 
 // ------------------------------------------------------------------------------------------------
 // K4: one wave per accepted contour: gather its points from the chunk pool into LDS (one coalesced 256-byte
@@ -3020,19 +3028,16 @@ __device__ __host__ inline int pts_cap_first(const DevParams &P) { return P.maxP
 // approxPolyDP_<int> orders its work (the slice stack is sequential, each slice's farthest-point search is a
 // wave reduction with first-maximum tie-break), then _findMarkerContours' gates (aruco.cpp): 4 points,
 // convex, min side, distance to the image border.
-// LDS (points + slice stack) is what limits residency, so the launch is bucketed by contour length: the
-// first launch takes contours of at most pts_cap points with a short stack and flags the rare contour whose
-// slice stack overflows (bit 25 of the slot's meta word); the second launch, sized for maxPerimeterPixels,
-// takes the longer and the flagged ones.
-#define K4_RETRY_BIT (1u << 25)
-__global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, const uint32_t *__restrict__ chunk_tab,
+// LDS (the points) is what limits residency, so the launch is bucketed by contour length: the first launch
+// takes contours of at most pts_cap points, the second one, sized for maxPerimeterPixels, the longer ones.
+__global__ __launch_bounds__(64) void k_approx(const uint4 *__restrict__ contours, const uint32_t *__restrict__ chunk_tab,
                                                 const uint32_t *__restrict__ pool, DevCand *__restrict__ cands,
-                                                DevCounts *__restrict__ counts, DevGlobal *__restrict__ G, const DevParams P,
-                                                int pts_cap, int stack_cap, int second_pass, const uint32_t *__restrict__ dense,
-                                                const uint32_t *__restrict__ cbase, int part = 0)
+                                                DevCounts *__restrict__ counts, const DevParams P, int pts_cap, int second_pass,
+                                                const uint32_t *__restrict__ dense, const uint32_t *__restrict__ cbase, int part = 0)
 {
-    extern __shared__ __attribute__((aligned(16))) uint32_t pts[];  // pts_cap points, then stack_cap slices
-    int2 *stack = reinterpret_cast<int2 *>(pts + pts_cap);
+    // pts_cap points, rounded up to a multiple of 8 (k_approx_lds_bytes): the gather stores a lane's eight points whole
+    extern __shared__ __attribute__((aligned(16))) uint32_t pts[];
+    __shared__ int2 stack[K4_STACK];
     __shared__ int dst[2 * 16];
     const int lane = lane_id();
     const int f = blockIdx.y;
@@ -3045,7 +3050,7 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
     const unsigned loff = part == 2 ? (unsigned)P.maxContours / 2u : 0u;
     if (part) n = n < (unsigned)P.maxContours / 2u ? n : (unsigned)P.maxContours / 2u;
     const int W = P.W, H = P.H;
-    uint4 *fco = contours + (long long)f * P.maxContours + loff;
+    const uint4 *fco = contours + (long long)f * P.maxContours + loff;
     const uint32_t *fpool = pool;  // chunks are numbered across the whole launch
     // this workgroup's slots are blockIdx.x, blockIdx.x + gridDim.x, ...: 64 of them are looked at with one
     // load (a lane each); only the accepted ones of the right length class are then processed in turn
@@ -3054,7 +3059,7 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
       uint4 mine = make_uint4(0u, 0u, 0u, 0u);
       if (myci < n) mine = fco[myci];
       int take = mine.z != 0;  // count 0 = slot of a walk that was dropped
-      if (second_pass) take = take && ((int)mine.z > pts_cap_first(P) || (mine.y & K4_RETRY_BIT));
+      if (second_pass) take = take && (int)mine.z > pts_cap_first(P);
       else take = take && (int)mine.z <= pts_cap;
       unsigned long long todo = ballot64(take);
       while (todo) {
@@ -3105,23 +3110,29 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
         int sx = 0, sy = 0;
         // 1. find approximately two farthest points
         for (int it = 0; it < 3; it++) {
-            pos = (pos + rs_start) % count;
+            pos += rs_start;  // (both below count: the sum needs no division)
+            pos = pos >= count ? pos - count : pos;
             uint32_t sp = pts[pos];
             sx = sp & 0xffff;
             sy = sp >> 16;
             // points j = 1 .. count-1 at index (pos + j) % count; READ_PT leaves pos back at its start
             // (per lane the largest distance and the FIRST index that has it -- j only grows inside a lane, so a strict compare
             //  keeps it; the first-maximum tie-break across lanes is wave_argmax_first's, once per pass)
+            // (two loops over the lane's j, in front of and behind the contour's end: no index wrap per point)
             unsigned bd = 0, bj = 0;
-            for (int j = 1 + lane; j < count; j += 64) {
-                int idx = pos + j;
-                idx = idx >= count ? idx - count : idx;
-                uint32_t p = pts[idx];
-                int dx = (int)(p & 0xffff) - sx, dy = (int)(p >> 16) - sy;
-                unsigned d = (unsigned)(dx * dx + dy * dy);
-                const bool gt = d > bd;
-                bd = gt ? d : bd;
-                bj = gt ? (unsigned)j : bj;
+            {
+                int j = 1 + lane, off = pos;  // point j is pts[off + j]
+                auto point = [&]() {
+                    const uint32_t p = pts[off + j];
+                    int dx = (int)(p & 0xffff) - sx, dy = (int)(p >> 16) - sy;
+                    unsigned d = (unsigned)(dx * dx + dy * dy);
+                    const bool gt = d > bd;
+                    bd = gt ? d : bd;
+                    bj = gt ? (unsigned)j : bj;
+                };
+                for (; j < count - pos; j += 64) point();
+                off -= count;
+                for (; j < count; j += 64) point();
             }
             unsigned md, mj;
             wave_argmax_first(bd, bd ? bj : 0xffffffffu, md, mj);
@@ -3131,8 +3142,8 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
         }
         if (!le_eps) {
             int2 rs, sl;
-            rs.y = sl.x = pos % count;
-            sl.y = rs.x = (rs_start + sl.x) % count;
+            rs.y = sl.x = pos;
+            sl.y = rs.x = rs_start + pos >= count ? rs_start + pos - count : rs_start + pos;
             if (lane == 0) {
                 stack[0] = rs;
                 stack[1] = sl;
@@ -3147,7 +3158,11 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
         }
         __syncthreads();
         // 3. recursive process
-        while (top > 0 && !reject) {
+        while (top > 0) {
+            if (new_count + top > K4_MAX_RAW) {  // at least that many vertices before the clean-up pass: they cannot end as 4
+                reject = 1;
+                break;
+            }
             int2 sl = stack[--top];
             uint32_t ep = pts[sl.y];
             int ex = ep & 0xffff, ey = ep >> 16;
@@ -3162,17 +3177,23 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
                 int dx = ex - sx, dy = ey - sy;
                 unsigned lbd = 0, lbt = 0;
                 bool any = false;
-                for (int t = lane; t < mcount; t += 64) {
-                    int idx = sl.x + 1 + t;
-                    idx = idx >= count ? idx - count : idx;
-                    uint32_t p = pts[idx];
-                    int px = p & 0xffff, py = p >> 16;
-                    int cr = (py - sy) * dx - (px - sx) * dy;
-                    unsigned d = (unsigned)(cr < 0 ? -cr : cr);
-                    const bool gt = d > lbd || !any;  // (the first point of the lane counts even at distance 0: its index is the tie-break)
-                    lbd = gt ? d : lbd;
-                    lbt = gt ? (unsigned)t : lbt;
-                    any = true;
+                // (as in the passes: the lane's t in front of the contour's end, then behind it)
+                {
+                    int t = lane, off = sl.x + 1;  // interior point t is pts[off + t]
+                    auto point = [&]() {
+                        const uint32_t p = pts[off + t];
+                        int px = p & 0xffff, py = p >> 16;
+                        int cr = (py - sy) * dx - (px - sx) * dy;
+                        unsigned d = (unsigned)(cr < 0 ? -cr : cr);
+                        const bool gt = d > lbd || !any;  // (the first point of the lane counts even at distance 0: its index is the tie-break)
+                        lbd = gt ? d : lbd;
+                        lbt = gt ? (unsigned)t : lbt;
+                        any = true;
+                    };
+                    const int ahead = count - (sl.x + 1) < mcount ? count - (sl.x + 1) : mcount;
+                    for (; t < ahead; t += 64) point();
+                    off -= count;
+                    for (; t < mcount; t += 64) point();
                 }
                 unsigned mdist, mt;
                 wave_argmax_first(any ? lbd : 0u, any ? lbt : 0xffffffffu, mdist, mt);
@@ -3188,29 +3209,17 @@ __global__ __launch_bounds__(64) void k_approx(uint4 *__restrict__ contours, con
             }
             __syncthreads();
             if (le_eps) {
-                if (new_count >= 9) {
-                    reject = 1;  // the clean-up pass removes at most half: more than 8 can never end as 4
-                } else {
-                    if (lane == 0) {
-                        dst[2 * new_count] = sx;
-                        dst[2 * new_count + 1] = sy;
-                    }
-                    new_count++;
+                if (lane == 0) {
+                    dst[2 * new_count] = sx;
+                    dst[2 * new_count + 1] = sy;
                 }
+                new_count++;
             } else {
-                if (top + 2 > stack_cap) {
-                    reject = 1;
-                    if (lane == 0) {
-                        if (second_pass) atomicOr(&G->overflow, 4u);
-                        else fco[ci].y = c.y | K4_RETRY_BIT;  // the second launch has the long stack
-                    }
-                } else {
-                    if (lane == 0) {
-                        stack[top] = make_int2(split, sl.y);   // right_slice
-                        stack[top + 1] = make_int2(sl.x, split);  // slice
-                    }
-                    top += 2;
+                if (lane == 0) {
+                    stack[top] = make_int2(split, sl.y);   // right_slice
+                    stack[top + 1] = make_int2(sl.x, split);  // slice
                 }
+                top += 2;
             }
             __syncthreads();
         }
