@@ -96,6 +96,7 @@ SYMBOLS = [
     "fid_detect_batch", "fid_detect_device", "fid_submit_device", "fid_submit_batch", "fid_collect", "fid_order_after", "fid_pose", "fid_pose_last", "fid_refine_contour_corners", "fid_tap_bytes", "fid_tap_read",
     "fid_last_stage_ms", "fid_last_launches", "fid_stream", "fid_strerror", "fid_last_error", "fid_abi_version",
     "fid_stag_create", "fid_stag_destroy", "fid_stag_edge_frontend", "fid_stag_detect_edges", "fid_stag_detect_edges_validated", "fid_stag_detect_lines", "fid_stag_detect_lines_validated", "fid_stag_detect_quads", "fid_stag_host_tables", "fid_stag_load_library", "fid_stag_detect_markers_unrefined", "fid_stag_detect_markers", "fid_stag_pose_last", "fid_stag_detect_markers_batch", "fid_stag_tap_bytes", "fid_stag_tap_read", "fid_stag_queue_stats", "fid_stag_detect_markers_device", "fid_stag_detect_markers_batch_device",
+    "fid_stag_tag_from_three_corners", "fid_stag_layout_load_file", "fid_stag_layout_last_error", "fid_stag_set_layout", "fid_stag_bundle_pose_last", "fid_stag_bundle_pose", "fid_stag_detect_bundles_batch", "fid_stag_detect_bundles_batch_device",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
@@ -238,6 +239,15 @@ def load():
     L.fid_stag_queue_stats.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.fid_stag_detect_markers_device.argtypes = [vp, vp, i32, i32, i32, C.c_int, vp, i32, C.POINTER(i32)]
     L.fid_stag_detect_markers_batch_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, vp, vp, C.c_double, vp, vp, i32, vp]
+    L.fid_stag_tag_from_three_corners.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.fid_stag_layout_load_file.argtypes = [C.c_char_p, vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, i32]
+    L.fid_stag_layout_last_error.argtypes = []
+    L.fid_stag_layout_last_error.restype = C.c_char_p
+    L.fid_stag_set_layout.argtypes = [vp, vp, i32, i32]
+    L.fid_stag_bundle_pose_last.argtypes = [vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.fid_stag_bundle_pose.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.POINTER(i32)]
+    L.fid_stag_detect_bundles_batch.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, vp, vp, C.c_double, vp, vp, i32, vp, vp, vp]
+    L.fid_stag_detect_bundles_batch_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, vp, vp, C.c_double, vp, vp, i32, vp, vp, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

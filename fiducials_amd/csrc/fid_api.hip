@@ -1830,3 +1830,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_png.hip"
 #include "fid_draw.hip"
 #include "fid_dict.hip"
+#include "fid_stag_layout.hip"

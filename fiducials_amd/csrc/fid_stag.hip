@@ -660,6 +660,14 @@ struct fid_stag_ctx {
     bool decoded = false;
     int *d_chosen = nullptr;
     fid_stag_pose_out *d_poses = nullptr;
+    // the layout (fid_stag_set_layout): its tags ordered by bundle, d_lstart[b] .. d_lstart[b + 1] the tags of bundle b; one result
+    // slot per bundle; room for markers handed in from the host (fid_stag_bundle_pose).  All inside the slab: a group's launches merge.
+    fid_stag_tag *d_ltags = nullptr;
+    int *d_lstart = nullptr, *d_hn = nullptr;
+    fid_stag_bundle_pose_out *d_bposes = nullptr;
+    fid_stag_marker *d_hmarkers = nullptr;
+    std::vector<fid_stag_tag> layout;  // as it lies on the device
+    int n_bundles = 0;
     int W = 0, H = 0;
     unsigned n_anchors = 0;
     // pinned landing area of the asynchronous device -> host read-backs (a copy into pageable memory would make the
@@ -670,6 +678,7 @@ struct fid_stag_ctx {
         int spec_bad;  // (a frame queued ahead: a count exceeded what its launches were sized for)
         fid_stag_marker markers[STAG_PIN_MARKERS];
         fid_stag_pose_out poses[STAG_PIN_MARKERS];
+        fid_stag_bundle_pose_out bposes[FID_STAG_MAX_BUNDLES];
     } *hp = nullptr;
     uint8_t *h_src = nullptr;  // pinned staging of the input frame (host rows -> here -> one asynchronous DMA)
     // a frame QUEUED AHEAD (round 5): the counts of the last frame this context finished size the next frame's launches, so that
@@ -690,6 +699,7 @@ struct fid_stag_ctx {
     int split_lds_env = -1;              // FID_STAG_SPLIT_LDS (pixels per wave of k_stag_split_lines that live in LDS)
 };
 
+#define STAG_LAYOUT_TAGS (FID_STAG_MAX_BUNDLES * FID_STAG_MAX_TAGS_PER_BUNDLE)  // the most tags a layout can hold
 #define STAG_WORDS_RESERVE (1u << 20)  // bytes of the slab kept for the marker library (HD11, the largest: 22 309 words)
 struct StagSlab {
     struct Item {
@@ -819,6 +829,9 @@ fid_status fid_stag_create(int libraryHD, int errorCorrection, int max_width, in
     ok = ok && slab.take((void **)&c->d_specbad, 16) && slab.take((void **)&c->d_words_slab, STAG_WORDS_RESERVE);
     ok = ok && slab.take((void **)&c->d_chosen, (n / 9 + 16) * 4) &&
          slab.take((void **)&c->d_poses, (n / 9 + 16) * sizeof(fid_stag_pose_out));
+    ok = ok && slab.take((void **)&c->d_ltags, STAG_LAYOUT_TAGS * sizeof(fid_stag_tag)) && slab.take((void **)&c->d_lstart, (FID_STAG_MAX_BUNDLES + 1) * 4) &&
+         slab.take((void **)&c->d_bposes, FID_STAG_MAX_BUNDLES * sizeof(fid_stag_bundle_pose_out)) &&
+         slab.take((void **)&c->d_hmarkers, STAG_LAYOUT_TAGS * sizeof(fid_stag_marker)) && slab.take((void **)&c->d_hn, 4);
     ok = ok && slab.commit(&c->d_slab, &c->slab_bytes);
     ok = ok && hipMemcpy(c->d_caps, caps_host, sizeof(caps_host), hipMemcpyHostToDevice) == hipSuccess && hipMemset(c->d_specbad, 0, 16) == hipSuccess;
     ok = ok && hipHostMalloc((void **)&c->hp, sizeof(fid_stag_ctx::Pinned), hipHostMallocDefault) == hipSuccess &&
@@ -897,6 +910,9 @@ struct StagJob {
     double marker_size = 0;
     fid_stag_pose_out *poses = nullptr;
     int pose_cap = 0;
+    fid_stag_bundle_pose_out *bposes = nullptr;  // the bundle step behind the marker pose (contexts with a layout; needs K): room for the layout's bundles
+    int32_t *n_bposes = nullptr;
+    bool bposes_ran = false;
     // where it stands
     int seg = 0, rstate = RS_NONE;
     bool done = false;
@@ -1038,6 +1054,16 @@ static std::atomic<long long> g_stag_ns_sync(0), g_stag_ns_seg[12];
 #define STAG_NOW() std::chrono::steady_clock::now()
 #define STAG_NS(a, b) std::chrono::duration_cast<std::chrono::nanoseconds>((b) - (a)).count()
 #endif
+// the records of the bundles of which a tag was found, in bundle order (the kernel leaves one slot per bundle, n_tags = 0 where none was)
+static int stag_hand_over_bundles(const fid_stag_bundle_pose_out *slots, int n_bundles, fid_stag_bundle_pose_out *out, int32_t *n_out)
+{
+    int n = 0;
+    for (int b = 0; b < n_bundles; b++)
+        if (slots[b].n_tags > 0) out[n++] = slots[b];
+    if (n_out) *n_out = n;
+    return n;
+}
+
 static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j);
 static fid_status stag_advance(fid_stag_ctx *c, StagJob &j)
 {
@@ -1485,6 +1511,18 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 if (STAG_MEMCPY(c->hp->poses, c->d_poses, (size_t)nm * sizeof(fid_stag_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
                     return stag_finish(j, FID_E_HIP);
             }
+            if (j.bposes && j.K && c->n_bundles > 0) {
+                // Common::solvePnpBundle for every bundle of the layout, one wave each; the slots come back through the pinned block
+                PoseCam bcam;
+                for (int i = 0; i < 9; i++) bcam.K[i] = j.K[i];
+                for (int i = 0; i < 5; i++) bcam.D[i] = j.D ? j.D[i] : 0.0;
+                bcam.fiducial_len = 0.0;
+                STAG_LAUNCH(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
+                if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
+                if (STAG_MEMCPY(c->hp->bposes, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
+                    return stag_finish(j, FID_E_HIP);
+                j.bposes_ran = true;
+            }
             // (the frame's flag is in the pinned block already: every k_stag_spec_guard writes it there)
             j.seg = 8;
             return FID_OK;  // (the frame's one wait)
@@ -1521,6 +1559,18 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 hipSuccess)
                 return stag_finish(j, FID_E_HIP);
         }
+        if (j.bposes && j.K && c->n_bundles > 0 && c->n_markers > 0) {
+            // Common::solvePnpBundle for every bundle of the layout, one wave each; the slots come back through the pinned block
+            PoseCam bcam;
+            for (int i = 0; i < 9; i++) bcam.K[i] = j.K[i];
+            for (int i = 0; i < 5; i++) bcam.D[i] = j.D ? j.D[i] : 0.0;
+            bcam.fiducial_len = 0.0;
+            STAG_LAUNCH(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
+            if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
+            if (STAG_MEMCPY(c->hp->bposes, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
+                return stag_finish(j, FID_E_HIP);
+            j.bposes_ran = true;
+        }
         j.seg = 8;
         return FID_OK;
     }
@@ -1546,6 +1596,7 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 c->pred.valid = false;
                 j.spec = false;
                 j.nospec = true;
+                j.bposes_ran = false;
                 j.seg = 0;
                 j.rstate = RS_NONE;
                 continue;
@@ -1565,12 +1616,14 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 if (j.out) memcpy(j.out, h.markers, (size_t)c->n_markers * sizeof(fid_stag_marker));
                 if (j.last == SS_POSE && j.poses) memcpy(j.poses, h.poses, (size_t)c->n_markers * sizeof(fid_stag_pose_out));
             }
+            if (j.bposes_ran) stag_hand_over_bundles(c->hp->bposes, c->n_bundles, j.bposes, j.n_bposes);
             return stag_finish(j, FID_OK);
         }
         if (c->n_markers > 0 && c->n_markers <= STAG_PIN_MARKERS) {
             if (j.out) memcpy(j.out, c->hp->markers, (size_t)c->n_markers * sizeof(fid_stag_marker));
             if (j.last == SS_POSE && j.poses) memcpy(j.poses, c->hp->poses, (size_t)c->n_markers * sizeof(fid_stag_pose_out));
         }
+        if (j.bposes_ran) stag_hand_over_bundles(c->hp->bposes, c->n_bundles, j.bposes, j.n_bposes);
         stag_learn(c, j, j.rstate == RS_PAR_B);
         return stag_finish(j, FID_OK);
     }
@@ -1691,6 +1744,99 @@ fid_status fid_stag_pose_last(fid_stag_ctx *c, const double K[9], const double D
     return hipStreamSynchronize(st) == hipSuccess ? FID_OK : FID_E_HIP;
 }
 
+
+// ---- tag bundles (fid_abi.h: "tag bundles and per-tag geometry")
+fid_status fid_stag_set_layout(fid_stag_ctx *c, const fid_stag_tag *tags, int32_t n_tags, int32_t n_bundles)
+{
+    if (!c || n_tags < 0) return FID_E_INVALID_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
+    if (n_tags == 0) {
+        if (c->stream && hipStreamSynchronize(c->stream) != hipSuccess) return FID_E_HIP;
+        c->layout.clear();
+        c->n_bundles = 0;
+        return FID_OK;
+    }
+    if (!tags || n_bundles < 1 || !c->d_words) return FID_E_INVALID_ARG;
+    if (n_bundles > FID_STAG_MAX_BUNDLES) return FID_E_UNSUPPORTED;
+    int count[FID_STAG_MAX_BUNDLES] = {0}, start[FID_STAG_MAX_BUNDLES + 1] = {0};
+    const int n_ids = c->n_words / 4;  // (the library: four rotations of every marker)
+    for (int t = 0; t < n_tags; t++) {
+        const fid_stag_tag &g = tags[t];
+        if (g.bundle < 0 || g.bundle >= n_bundles || g.id < 0 || g.id >= n_ids) return FID_E_INVALID_ARG;
+        for (int a = 0; a < 4; a++) {
+            for (int k = 0; k < 3; k++)
+                if (!(g.corners[a][k] - g.corners[a][k] == 0) || !(g.center[k] - g.center[k] == 0)) return FID_E_INVALID_ARG;  // (not finite)
+            for (int b = a + 1; b < 4; b++)
+                if (g.corners[a][0] == g.corners[b][0] && g.corners[a][1] == g.corners[b][1] && g.corners[a][2] == g.corners[b][2]) return FID_E_INVALID_ARG;
+        }
+        for (int u = 0; u < t; u++)
+            if (tags[u].id == g.id) return FID_E_INVALID_ARG;
+        count[g.bundle]++;
+    }
+    for (int b = 0; b < n_bundles; b++) {
+        if (count[b] == 0) return FID_E_INVALID_ARG;
+        if (count[b] > FID_STAG_MAX_TAGS_PER_BUNDLE) return FID_E_UNSUPPORTED;
+        start[b + 1] = start[b] + count[b];
+    }
+    std::vector<fid_stag_tag> ordered((size_t)n_tags);
+    int fill[FID_STAG_MAX_BUNDLES] = {0};
+    for (int t = 0; t < n_tags; t++) ordered[(size_t)(start[tags[t].bundle] + fill[tags[t].bundle]++)] = tags[t];
+    if (c->stream && hipStreamSynchronize(c->stream) != hipSuccess) return FID_E_HIP;
+    if (hipMemcpy(c->d_ltags, ordered.data(), (size_t)n_tags * sizeof(fid_stag_tag), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_lstart, start, (size_t)(n_bundles + 1) * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        return FID_E_HIP;
+    c->layout.swap(ordered);
+    c->n_bundles = n_bundles;
+    return FID_OK;
+}
+
+// the bundle kernel on a marker list in device memory, its slots read back and handed over in bundle order
+static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const double K[9], const double D[5], const fid_stag_marker *d_markers, const int *d_n,
+                                       fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    PoseCam cam;
+    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
+    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.0;
+    cam.fiducial_len = 0.0;
+    hipStream_t st = stag_stream(c);
+    hipLaunchKernelGGL(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags, c->d_lstart, cam, c->d_bposes);
+    if (hipGetLastError() != hipSuccess) return FID_E_HIP;
+    fid_stag_bundle_pose_out slots[FID_STAG_MAX_BUNDLES];
+    if (hipMemcpyAsync(slots, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
+    if (hipStreamSynchronize(st) != hipSuccess) return FID_E_HIP;
+    int n = 0;
+    for (int b = 0; b < c->n_bundles; b++) n += slots[b].n_tags > 0;
+    if (n_out) *n_out = n;
+    if (n > cap) return FID_E_CAPACITY;
+    (void)stag_hand_over_bundles(slots, c->n_bundles, out, nullptr);
+    return FID_OK;
+}
+
+fid_status fid_stag_bundle_pose_last(fid_stag_ctx *c, const double K[9], const double D[5], fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !K || !out || cap < 0 || !c->decoded) return FID_E_INVALID_ARG;
+    if (n_out) *n_out = 0;
+    if (c->n_bundles == 0 || c->n_markers == 0) return FID_OK;  // (no layout: nothing is launched)
+    if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
+    return stag_bundle_pose_run(c, K, D, c->d_markers, c->d_nmarkers, out, cap, n_out);
+}
+
+fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double D[5], const fid_stag_marker *markers, int32_t n,
+                                fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !K || !out || cap < 0 || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
+    if (n > STAG_LAYOUT_TAGS) return FID_E_CAPACITY;
+    if (n_out) *n_out = 0;
+    if (c->n_bundles == 0 || n == 0) return FID_OK;
+    if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
+    hipStream_t st = stag_stream(c);
+    const int nn = n;
+    if (hipMemcpyAsync(c->d_hmarkers, markers, (size_t)n * sizeof(fid_stag_marker), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(c->d_hn, &nn, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return FID_E_HIP;
+    return stag_bundle_pose_run(c, K, D, c->d_hmarkers, c->d_hn, out, cap, n_out);
+}
+
 // Frames as a grid dimension (round 3; fid_stag_batch.h).  The contexts are cut into GROUPS of up to STAG_MAXF; a group takes
 // that many frames and carries them through the segments of stag_advance in LOCKSTEP on one stream: per segment one wait for the
 // group's stream, the host part of every frame (its launches recorded), then every launch site once for the whole group.  One
@@ -1700,7 +1846,8 @@ fid_status fid_stag_pose_last(fid_stag_ctx *c, const double K[9], const double D
 // frames: host memory, or (dev_frames) device memory in encoding enc -- then a group's first launch is k_stag_ingest, no staging.
 static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
                                     int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5],
-                                    double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+                                    double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                                    fid_stag_bundle_pose_out *bposes, int32_t *n_bposes)
 {
     // a group is at most as large as the smallest argument table (the routing kernels carry ~250 bytes of arguments per frame and
     // kernel-argument memory is 4 KB: a group one frame larger would launch them twice)
@@ -1777,6 +1924,7 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
                         j.last = (K && poses) ? SS_POSE : SS_MARKERS;
                         j.K = K; j.D = D; j.marker_size = marker_size;
                         j.poses = poses ? poses + (size_t)f * cap_per_frame : nullptr; j.pose_cap = cap_per_frame;
+                        if (bposes) { j.bposes = bposes + (size_t)f * ctxs[0]->n_bundles; j.n_bposes = n_bposes + f; }
                         G.jobs[k] = j;
                         G.frame_of[k] = f;
                         G.live++;
@@ -1877,13 +2025,16 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
 // the two batch entry points' common part, their arguments checked (frames: host memory; dev_frames: device memory in encoding enc)
 static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
                              int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
-                             fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+                             fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                             fid_stag_bundle_pose_out *bposes = nullptr, int32_t *n_bposes = nullptr)
 {
     for (int f = 0; f < nframes; f++) n_per_frame[f] = 0;  // every count is defined whatever happens to a frame
+    if (bposes)
+        for (int f = 0; f < nframes; f++) n_bposes[f] = 0;
     // frames as a grid dimension (default); FID_STAG_BATCH=contexts: round 2's road, a stream per context and host threads
     if (!(getenv("FID_STAG_BATCH") && !strcmp(getenv("FID_STAG_BATCH"), "contexts")))
         return stag_batch_groups(ctxs, nctx, frames, dev_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
-                                 cap_per_frame, n_per_frame);
+                                 cap_per_frame, n_per_frame, bposes, n_bposes);
     int nthreads = 4;
     if (const char *e = getenv("FID_STAG_THREADS")) nthreads = atoi(e);
     nthreads = nthreads < 1 ? 1 : (nthreads > nctx ? nctx : nthreads);
@@ -1916,6 +2067,7 @@ static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint
                         j.last = (K && poses) ? SS_POSE : SS_MARKERS;
                         j.K = K; j.D = D; j.marker_size = marker_size;
                         j.poses = poses ? poses + (size_t)f * cap_per_frame : nullptr; j.pose_cap = cap_per_frame;
+                        if (bposes) { j.bposes = bposes + (size_t)f * ctxs[0]->n_bundles; j.n_bposes = n_bposes + f; }
                         jobs[k] = j;
                         frame_of[k] = f;
                         live++;
@@ -2038,6 +2190,57 @@ fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32
     }
     return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers,
                       poses, cap_per_frame, n_per_frame);
+}
+
+
+// the two batch calls with the bundle step: every context must carry the same layout (the records of a frame are indexed by it)
+static fid_status stag_same_layout(fid_stag_ctx *const *ctxs, int32_t nctx)
+{
+    if (!ctxs || nctx <= 0 || !ctxs[0] || ctxs[0]->n_bundles == 0) return FID_E_INVALID_ARG;
+    for (int t = 1; t < nctx; t++) {
+        if (!ctxs[t] || ctxs[t]->n_bundles != ctxs[0]->n_bundles || ctxs[t]->layout.size() != ctxs[0]->layout.size()) return FID_E_INVALID_ARG;
+        if (memcmp(ctxs[t]->layout.data(), ctxs[0]->layout.data(), ctxs[0]->layout.size() * sizeof(fid_stag_tag)) != 0) return FID_E_INVALID_ARG;
+    }
+    return FID_OK;
+}
+
+fid_status fid_stag_detect_bundles_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
+                                         int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+                                         fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                                         fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
+{
+    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !K || !bundle_poses || !n_bundles_per_frame)
+        return FID_E_INVALID_ARG;
+    for (int t = 0; t < nctx; t++)
+        if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
+    if (poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    const fid_status rc = stag_same_layout(ctxs, nctx);
+    if (rc != FID_OK) return rc;
+    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
+                      cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
+}
+
+fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+                                                double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                                int32_t *n_per_frame, fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
+{
+    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !K || !bundle_poses || !n_bundles_per_frame)
+        return FID_E_INVALID_ARG;
+    for (int t = 0; t < nctx; t++)
+        if (!ctxs[t] || !ctxs[t]->d_words || width > ctxs[t]->maxW || height > ctxs[t]->maxH || ctxs[t]->device != ctxs[0]->device) return FID_E_INVALID_ARG;
+    if (poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    if (stag_enc_bpp(enc) == 0) return FID_E_UNSUPPORTED;
+    const fid_status lrc = stag_same_layout(ctxs, nctx);
+    if (lrc != FID_OK) return lrc;
+    if (nframes > 0) {
+        const fid_status rc = stag_check_device_frames((const uint8_t *)d_frames, ctxs[0]->device, nframes, width, height, stride, frame_stride, enc);
+        if (rc != FID_OK) return rc;
+    } else if (!d_frames) {
+        return FID_E_INVALID_ARG;
+    }
+    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers,
+                      poses, cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
 }
 
 fid_status fid_stag_queue_stats(const fid_stag_ctx *c, int32_t *queued, int32_t *rerun)

@@ -989,3 +989,433 @@ struct k_stag_pose_fn {
     static constexpr int kBounds = 64;
     __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out) const { k_stag_pose_impl(markers, nmarkers, cam, marker_size, out); }
 };
+
+// ------------------------------------------------------------------------------------------------ K18: bundle pose
+// Common::solvePnpBundle (stag_ros/common.hpp:48-59): cv::solvePnP (ITERATIVE) over all points of all tags of a bundle that were
+// seen -- per found tag its centre and c0..c3 (the layout's fid_stag_tag, bundle frame) against Marker::center / Marker::corners,
+// the tags in the order their markers stand in the marker list.  One wave per bundle (blockIdx.x; the frames of a group ride in
+// the trampoline's grid, fid_stag_batch.h):
+//   (1) lanes scan the marker list for the bundle's ids (unique per frame after checkDuplicate) and gather the points into LDS;
+//   (2) the planarity decision of cvFindExtrinsicCameraParams2: eigenvalues of the centred scatter matrix, w2 / w1 < 1e-3
+//       (NOT the reference's checkCoplanar, common.hpp:85-103, which solvePnpBundle never calls);
+//   (3) the start.  Coplanar: OpenCV's own -- the points turned into their plane by the scatter matrix's eigenvectors, the DLT
+//       homography over ALL of them (HomographyEstimatorCallback::runKernel: float inputs, normalised, the 9 x 9 symmetric
+//       eigenproblem by cyclic Jacobi in LDS, lane k the k-th row / column of a rotation), R and t from its columns.  Not coplanar
+//       (tags on several faces): the closed-form four-corner pose of the found tag that is largest in the image, composed with that
+//       tag's place in the bundle (OpenCV runs a 12 x 12 DLT there; parity unpinned);
+//   (4) CvLevMarq as in k_stag_pose: <= 20 iterations, lambda 10^k from -3, the same accept / reject and stop rule, plumb-bob
+//       distortion in the projection and its Jacobian.  Up to 120 residuals strided over the 64 lanes; J^T J (21), J^T e (6) and
+//       the norms are per-lane partial sums and one xor-butterfly over the wave -- a fixed order: reproducible from run to run,
+//       the same value in every lane.
+#define SB_MAX_TAGS 12  // FID_STAG_MAX_TAGS_PER_BUNDLE
+#define SB_MAX_PTS (5 * SB_MAX_TAGS)
+struct SbLds {
+    double obj[SB_MAX_PTS][3], img[SB_MAX_PTS][2], mn[SB_MAX_PTS][2], Mxy[SB_MAX_PTS][2];
+    double A[81], V[81], area[SB_MAX_TAGS];
+    int ids[SB_MAX_TAGS], tagof[SB_MAX_TAGS], mk[SB_MAX_TAGS];
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+    v += shfl_xor_f64(v, 1);
+    v += shfl_xor_f64(v, 2);
+    v += shfl_xor_f64(v, 4);
+    v += shfl_xor_f64(v, 8);
+    v += shfl_xor_f64(v, 16);
+    v += shfl_xor_f64(v, 32);
+    return v;
+}
+
+// entry j of the two DLT rows of one correspondence: Lx = {X, Y, 1, 0, 0, 0, -x X, -x Y, -x}, Ly = {0, 0, 0, X, Y, 1, -y X, -y Y, -y}
+__device__ __forceinline__ void sb_dlt_entry(int j, double X, double Y, double x, double y, double *lx, double *ly)
+{
+    const double b = j % 3 == 0 ? X : (j % 3 == 1 ? Y : 1.0);
+    *lx = j < 3 ? b : (j < 6 ? 0.0 : -x * b);
+    *ly = j < 3 ? 0.0 : (j < 6 ? b : -y * b);
+}
+
+// HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS (both already rounded to
+// float, as findHomography converts its inputs); every lane returns the same H
+__device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
+{
+    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
+    for (int i = 0; i < n; i++) {
+        cmx += s->mn[i][0];
+        cmy += s->mn[i][1];
+        cMx += s->Mxy[i][0];
+        cMy += s->Mxy[i][1];
+    }
+    cmx /= n; cmy /= n; cMx /= n; cMy /= n;
+    for (int i = 0; i < n; i++) {
+        smx += fabs(s->mn[i][0] - cmx);
+        smy += fabs(s->mn[i][1] - cmy);
+        sMx += fabs(s->Mxy[i][0] - cMx);
+        sMy += fabs(s->Mxy[i][1] - cMy);
+    }
+    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
+    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
+    // LtL: lane e < 45 owns entry (j, k), j <= k, and sums it over the points in their order
+    if (lane < 45) {
+        int j = 0, k = lane;
+        while (k >= 9 - j) {
+            k -= 9 - j;
+            j++;
+        }
+        k += j;
+        double acc = 0;
+        for (int i = 0; i < n; i++) {
+            const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
+            const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
+            double lxj, lyj, lxk, lyk;
+            sb_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
+            sb_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
+            acc += lxj * lxk + lyj * lyk;
+        }
+        s->A[j * 9 + k] = acc;
+        s->A[k * 9 + j] = acc;
+    }
+    for (int e = lane; e < 81; e += 64) s->V[e] = (e / 9 == e % 9) ? 1. : 0.;
+    SR_LDS_SYNC();
+    // cyclic Jacobi on the 9 x 9 (rows of V = eigenvectors): the rotation's angle in every lane, lane k < 9 turns its entries
+    for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) off += s->A[p * 9 + q] * s->A[p * 9 + q];
+        if (!(off >= 1e-300)) break;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) {
+                const double apq = s->A[p * 9 + q];
+                if (fabs(apq) < 1e-300) continue;  // (wave-uniform)
+                const double app = s->A[p * 9 + p], aqq = s->A[q * 9 + q];
+                const double theta = (aqq - app) / (2. * apq);
+                const double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                const double c = 1. / sqrt(t * t + 1.), sn = t * c;
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double akp = s->A[lane * 9 + p], akq = s->A[lane * 9 + q];
+                    s->A[lane * 9 + p] = c * akp - sn * akq;
+                    s->A[lane * 9 + q] = sn * akp + c * akq;
+                }
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double apk = s->A[p * 9 + lane], aqk = s->A[q * 9 + lane];
+                    s->A[p * 9 + lane] = c * apk - sn * aqk;
+                    s->A[q * 9 + lane] = sn * apk + c * aqk;
+                    const double vpk = s->V[p * 9 + lane], vqk = s->V[q * 9 + lane];
+                    s->V[p * 9 + lane] = c * vpk - sn * vqk;
+                    s->V[q * 9 + lane] = sn * vpk + c * vqk;
+                }
+                SR_LDS_SYNC();
+            }
+    }
+    int row = 0;
+    double wmin = s->A[0];
+    for (int i = 1; i < 9; i++)
+        if (s->A[i * 9 + i] <= wmin) {
+            wmin = s->A[i * 9 + i];
+            row = i;
+        }
+    double H0[9], T[9];
+    for (int i = 0; i < 9; i++) H0[i] = s->V[row * 9 + i];
+    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    sr_mul3(invHnorm, H0, T);
+    sr_mul3(T, Hnorm2, H0);
+    if (!(H0[8] != 0)) return false;
+    const double sc = 1. / H0[8];
+    for (int i = 0; i < 9; i++) H[i] = H0[i] * sc;
+    return true;
+}
+
+// rotation and translation from a plane -> normalised-image homography (cvFindExtrinsicCameraParams2, planar branch)
+__device__ __forceinline__ void sb_pose_from_h(double h[9], double t3[3])
+{
+    const double h1n = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]), h2n = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
+    const double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), stt = 2. / fmax(h1n + h2n, DBL_EPSILON);
+    t3[0] = h[2] * stt; t3[1] = h[5] * stt; t3[2] = h[8] * stt;
+    h[0] *= s1; h[3] *= s1; h[6] *= s1;
+    h[1] *= s2; h[4] *= s2; h[7] *= s2;
+    h[2] = h[3] * h[7] - h[6] * h[4];
+    h[5] = h[6] * h[1] - h[0] * h[7];
+    h[8] = h[0] * h[4] - h[3] * h[1];
+    double rtmp[3], dummy[27];
+    rodrigues_m2v(h, rtmp);
+    rodrigues_v2m(rtmp, h, dummy, false);
+}
+
+__device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
+                                                         const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam,
+                                                         fid_stag_bundle_pose_out *__restrict__ out)
+{
+    __shared__ SbLds s;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double *K = cam.K, *kd = cam.D;
+    const int t0 = lstart[b];
+    int nt = lstart[b + 1] - t0;
+    nt = nt < 0 ? 0 : (nt > SB_MAX_TAGS ? SB_MAX_TAGS : nt);
+    const int nm = *nmarkers;
+    // ---- (1) the bundle's tags among the frame's markers, in marker order
+    if (lane < nt) s.ids[lane] = ltags[t0 + lane].id;
+    SR_LDS_SYNC();
+    int found = 0;
+    for (int m0 = 0; m0 < nm && found < SB_MAX_TAGS; m0 += 64) {
+        const int m = m0 + lane;
+        int ti = -1;
+        if (m < nm) {
+            const int id = markers[m].id;
+            for (int k = nt - 1; k >= 0; k--)
+                if (s.ids[k] == id) ti = k;
+        }
+        const unsigned long long hit = __ballot(ti >= 0);
+        if (ti >= 0) {
+            const int pos = found + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
+            if (pos < SB_MAX_TAGS) {
+                s.tagof[pos] = ti;
+                s.mk[pos] = m;
+            }
+        }
+        found += __builtin_popcountll(hit);
+    }
+    found = found > SB_MAX_TAGS ? SB_MAX_TAGS : found;
+    if (found == 0) {
+        if (lane == 0) {
+            fid_stag_bundle_pose_out o;
+            o.bundle = b;
+            o.n_tags = 0;
+            for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
+            for (int i = 0; i < 9; i++) o.R[i] = 0.;
+            out[b] = o;
+        }
+        return;
+    }
+    SR_LDS_SYNC();
+    const int npts = 5 * found;
+    if (lane < npts) {
+        const int p = lane / 5, q = lane % 5;
+        const fid_stag_tag *tg = ltags + t0 + s.tagof[p];
+        const fid_stag_marker *mk = markers + s.mk[p];
+        for (int a = 0; a < 3; a++) s.obj[lane][a] = q == 0 ? tg->center[a] : tg->corners[q - 1][a];
+        const double u = q == 0 ? mk->center[0] : mk->corners[2 * (q - 1)], v = q == 0 ? mk->center[1] : mk->corners[2 * (q - 1) + 1];
+        s.img[lane][0] = u;
+        s.img[lane][1] = v;
+        double x, y;
+        sp_undistort(K, kd, u, v, &x, &y);
+        s.mn[lane][0] = (double)(float)x;  // (the DLT's input: findHomography converts to float)
+        s.mn[lane][1] = (double)(float)y;
+        if (q == 0) {  // the tag's area in the image (shoelace over its four corners)
+            double a2 = 0;
+            for (int i = 0; i < 4; i++) {
+                const int i1 = (i + 1) & 3;
+                a2 += mk->corners[2 * i] * mk->corners[2 * i1 + 1] - mk->corners[2 * i1] * mk->corners[2 * i + 1];
+            }
+            s.area[p] = fabs(a2);
+        }
+    }
+    SR_LDS_SYNC();
+    // ---- (2) planarity: the centred scatter matrix of the object points and its eigenvalues (every lane the same)
+    double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
+    {
+        double MM[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+        for (int i = 0; i < npts; i++)
+            for (int a = 0; a < 3; a++) Mc[a] += s.obj[i][a];
+        for (int a = 0; a < 3; a++) Mc[a] /= npts;
+        for (int i = 0; i < npts; i++) {
+            const double d[3] = {s.obj[i][0] - Mc[0], s.obj[i][1] - Mc[1], s.obj[i][2] - Mc[2]};
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+#pragma unroll
+                for (int c = 0; c < 3; c++) MM[a][c] += d[a] * d[c];
+        }
+        jacobi3(MM, Vt);
+        W[0] = MM[0][0]; W[1] = MM[1][1]; W[2] = MM[2][2];
+        // eigenvalues descending, the rows of Vt with them (cv::SVD's order)
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            int mx = i;
+#pragma unroll
+            for (int j = i + 1; j < 3; j++)
+                if (W[j] > W[mx]) mx = j;
+            if (mx != i) {
+                const double t = W[i];
+                W[i] = W[mx];
+                W[mx] = t;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const double u = Vt[i][k];
+                    Vt[i][k] = Vt[mx][k];
+                    Vt[mx][k] = u;
+                }
+            }
+        }
+    }
+    const bool planar = W[2] / W[1] < 1e-3;
+    // ---- (3) the start
+    double param[6] = {0, 0, 0, 0, 0, 0};
+    if (planar) {
+        double Rt[9];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) Rt[3 * i + j] = Vt[i][j];
+        if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10)
+            for (int i = 0; i < 9; i++) Rt[i] = (i % 4 == 0) ? 1. : 0.;
+        const double det = Rt[0] * (Rt[4] * Rt[8] - Rt[5] * Rt[7]) - Rt[1] * (Rt[3] * Rt[8] - Rt[5] * Rt[6]) + Rt[2] * (Rt[3] * Rt[7] - Rt[4] * Rt[6]);
+        if (det < 0)
+            for (int i = 0; i < 9; i++) Rt[i] = -Rt[i];
+        double tt[3];
+        for (int i = 0; i < 3; i++) tt[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
+        if (lane < npts) {
+            const double *src = s.obj[lane];
+            s.Mxy[lane][0] = (double)(float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
+            s.Mxy[lane][1] = (double)(float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
+        }
+        SR_LDS_SYNC();
+        double h[9], R[9];
+        if (sb_homography_dlt(&s, npts, lane, h)) {
+            double t3[3];
+            sb_pose_from_h(h, t3);
+            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
+            sr_mul3(h, Rt, R);
+        } else {
+            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+        }
+        rodrigues_m2v(R, param);
+    } else {
+        int big = 0;
+        for (int p = 1; p < found; p++)
+            if (s.area[p] > s.area[big]) big = p;
+        const double *c0 = s.obj[5 * big + 1], *c1 = s.obj[5 * big + 2], *c3 = s.obj[5 * big + 4], *cc = s.obj[5 * big];
+        // the tag's frame in the bundle: x along c0 -> c1, y along c3 -> c0, origin at its centre
+        double ex[3], ey[3], ez[3];
+        for (int a = 0; a < 3; a++) {
+            ex[a] = c1[a] - c0[a];
+            ey[a] = c0[a] - c3[a];
+        }
+        const double wx = sqrt(ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2]), wy = sqrt(ey[0] * ey[0] + ey[1] * ey[1] + ey[2] * ey[2]);
+        for (int a = 0; a < 3; a++) ex[a] /= wx;
+        ez[0] = ex[1] * ey[2] - ex[2] * ey[1]; ez[1] = ex[2] * ey[0] - ex[0] * ey[2]; ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
+        const double wz = sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
+        for (int a = 0; a < 3; a++) ez[a] /= wz;
+        ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
+        double mnx[4], mny[4];
+        for (int i = 0; i < 4; i++) sp_undistort(K, kd, s.img[5 * big + 1 + i][0], s.img[5 * big + 1 + i][1], &mnx[i], &mny[i]);
+        // unit square -> quad, composed with (X, Y) -> ((X + wx / 2) / wx, (wy / 2 - Y) / wy): k_stag_pose's start for a wx x wy tag
+        const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
+        const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
+        const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
+        const double den = dx1 * dy2 - dy1 * dx2;
+        double h[9], Rq[9], tq[3] = {0, 0, 0};
+        bool okh = den != 0. && wx > 0. && wy > 0. && wz > 0.;
+        if (okh) {
+            const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
+            const double a = x1 - x0 + gg * x1, bq = x3 - x0 + hh * x3, c = x0;
+            const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
+            const double scx = 1. / wx, scy = 1. / wy;
+            h[0] = a * scx;  h[1] = -bq * scy; h[2] = 0.5 * a + 0.5 * bq + c;
+            h[3] = d * scx;  h[4] = -e * scy;  h[5] = 0.5 * d + 0.5 * e + ff;
+            h[6] = gg * scx; h[7] = -hh * scy; h[8] = 0.5 * gg + 0.5 * hh + 1.;
+            okh = h[8] != 0.;
+            if (okh) {
+                const double sc = 1. / h[8];
+                for (int i = 0; i < 9; i++) h[i] *= sc;
+            }
+        }
+        if (okh) {
+            sb_pose_from_h(h, tq);
+            // bundle -> camera: X_cam = Rq B^T (X - centre) + tq, B = [ex ey ez]
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) Rq[3 * i + j] = h[3 * i] * ex[j] + h[3 * i + 1] * ey[j] + h[3 * i + 2] * ez[j];
+            for (int i = 0; i < 3; i++) param[3 + i] = tq[i] - (Rq[3 * i] * cc[0] + Rq[3 * i + 1] * cc[1] + Rq[3 * i + 2] * cc[2]);
+        } else {
+            for (int i = 0; i < 9; i++) Rq[i] = (i % 4 == 0) ? 1. : 0.;
+        }
+        rodrigues_m2v(Rq, param);
+    }
+    // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l and l + 64
+    const int nres = 2 * npts;
+    const bool act0 = lane < nres, act1 = lane + 64 < nres;
+    const int r0 = act0 ? lane : 0, r1 = act1 ? lane + 64 : 0;
+    const double M0[3] = {s.obj[r0 >> 1][0], s.obj[r0 >> 1][1], s.obj[r0 >> 1][2]}, M1[3] = {s.obj[r1 >> 1][0], s.obj[r1 >> 1][1], s.obj[r1 >> 1][2]};
+    const double mobs0 = s.img[r0 >> 1][r0 & 1], mobs1 = s.img[r1 >> 1][r1 & 1];
+    double prevParam[6], S[21], gJ[6], J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0};
+    double err0 = 0, err1 = 0, prevErrNorm = 0, errNorm = 0;
+    int lambdaLg10 = -3, iters = 0, state = 1;
+    for (int i = 0; i < 6; i++) prevParam[i] = param[i];
+    for (;;) {
+        bool needJ = false, needErr = false;
+        if (state == 1) {
+            needJ = needErr = true;
+            state = 2;
+        } else if (state == 2) {
+            int idx = 0;
+            for (int a = 0; a < 6; a++) {
+                for (int c = a; c < 6; c++) S[idx++] = wave_sum_f64(J0[a] * J0[c] + J1[a] * J1[c]);
+                gJ[a] = wave_sum_f64(J0[a] * err0 + J1[a] * err1);
+            }
+            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
+            double xs[6];
+            solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
+            for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
+            if (iters == 0) prevErrNorm = sqrt(wave_sum_f64(err0 * err0 + err1 * err1));
+            needErr = true;
+            state = 3;
+        } else {
+            errNorm = sqrt(wave_sum_f64(err0 * err0 + err1 * err1));
+            bool retry = false;
+            if (errNorm > prevErrNorm) {
+                if (++lambdaLg10 <= 16) {
+                    double xs[6];
+                    solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
+                    for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
+                    needErr = true;
+                    state = 3;
+                    retry = true;
+                }
+            }
+            if (!retry) {
+                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
+                double dn = 0, pn = 0;
+                for (int i = 0; i < 6; i++) {
+                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
+                    pn += prevParam[i] * prevParam[i];
+                }
+                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
+                if (++iters >= 20 || rel < FLT_EPSILON) break;
+                prevErrNorm = errNorm;
+                needJ = needErr = true;
+                state = 2;
+            }
+        }
+        if (!needErr) break;
+        if (act0) {
+            err0 = project_one(M0, param, K, kd, r0 & 1, J0, needJ) - mobs0;
+        } else {
+            err0 = 0.;
+            for (int i = 0; i < 6; i++) J0[i] = 0.;
+        }
+        if (act1) {
+            err1 = project_one(M1, param, K, kd, r1 & 1, J1, needJ) - mobs1;
+        } else {
+            err1 = 0.;
+            for (int i = 0; i < 6; i++) J1[i] = 0.;
+        }
+    }
+    if (lane == 0) {
+        fid_stag_bundle_pose_out o;
+        o.bundle = b;
+        o.n_tags = found;
+        for (int i = 0; i < 3; i++) {
+            o.rvec[i] = param[i];
+            o.tvec[i] = param[3 + i];
+        }
+        double dummy[27];
+        rodrigues_v2m(param, o.R, dummy, false);
+        out[b] = o;
+    }
+}
+__global__ __launch_bounds__(64) void k_stag_bundle_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out)
+{
+    k_stag_bundle_pose_impl(markers, nmarkers, ltags, lstart, cam, out);
+}
+struct k_stag_bundle_pose_fn {
+    static constexpr int kBounds = 64;
+    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out) const { k_stag_bundle_pose_impl(markers, nmarkers, ltags, lstart, cam, out); }
+};

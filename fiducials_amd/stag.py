@@ -17,6 +17,9 @@ from ._lib import FidError
 MARKER_DTYPE = np.dtype([("id", "i4"), ("shift", "i4"), ("corners", "f8", (4, 2)), ("center", "f8", (2,)), ("H", "f8", (3, 3)),
                          ("lineInf", "f8", (3,)), ("projectiveDistortion", "f8"), ("code", "u8")])
 POSE_DTYPE = np.dtype([("id", "i4"), ("reserved", "i4"), ("rvec", "f8", (3,)), ("tvec", "f8", (3,)), ("R", "f8", (3, 3))])
+TAG_DTYPE = np.dtype([("id", "i4"), ("bundle", "i4"), ("corners", "f8", (4, 3)), ("center", "f8", (3,))])  # fid_stag_tag
+BUNDLE_POSE_DTYPE = np.dtype([("bundle", "i4"), ("n_tags", "i4"), ("rvec", "f8", (3,)), ("tvec", "f8", (3,)), ("R", "f8", (3, 3))])
+MAX_BUNDLES, MAX_TAGS_PER_BUNDLE, FRAME_LEN = 64, 12, 64  # FID_STAG_MAX_BUNDLES, FID_STAG_MAX_TAGS_PER_BUNDLE, FID_STAG_FRAME_LEN
 QUAD_DTYPE = np.dtype([("corners", "f8", (4, 2)), ("lineInf", "f8", (3,)), ("projectiveDistortion", "f8")])
 LINE_DTYPE = np.dtype([("a", "f8"), ("b", "f8"), ("sx", "f8"), ("sy", "f8"), ("ex", "f8"), ("ey", "f8"), ("invert", "i4"),
                        ("segmentNo", "i4"), ("firstPixelIndex", "i4"), ("len", "i4")])
@@ -30,6 +33,58 @@ def load_library(hd: int) -> np.ndarray:
     if hd not in (11, 13, 15, 17, 19, 21, 23) or not os.path.exists(path):
         raise FidError(_lib.FID_E_INVALID_ARG, "Invalid library HD. Possible values are 11, 13, 15, 17, 19, 21, or 23")
     return np.ascontiguousarray(np.fromfile(path, dtype="<u8").astype(np.uint64))
+
+
+class Layout:
+    """The bundles a node is configured with (stag_ros/load_yaml_tags.h): `tags` (TAG_DTYPE, ordered by bundle), and per bundle its
+    frame name and whether it is a standalone tag of the `tags:` list (a bundle of one tag)."""
+
+    def __init__(self, tags: np.ndarray, frames: list[str], standalone: np.ndarray):
+        self.tags = np.ascontiguousarray(tags, dtype=TAG_DTYPE)
+        self.frames = list(frames)
+        self.standalone = np.asarray(standalone, dtype=bool)
+
+    @property
+    def n_bundles(self) -> int:
+        return len(self.frames)
+
+
+def tag_from_three_corners(tag_id: int, bundle: int, c0, c1, c2) -> np.ndarray:
+    """A tag (TAG_DTYPE, one element) from the three corners the YAML gives (load_yaml_tags.h:22-30), through the C side."""
+    out = np.zeros(1, TAG_DTYPE)
+    c = [np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (c0, c1, c2)]
+    rc = _lib.load().fid_stag_tag_from_three_corners(int(tag_id), int(bundle), c[0].ctypes.data, c[1].ctypes.data, c[2].ctypes.data, out.ctypes.data)
+    if rc != _lib.FID_OK:
+        raise FidError(rc, "fid_stag_tag_from_three_corners")
+    return out[0]
+
+
+def board_layout(ids, corners, frame: str = "board") -> Layout:
+    """One bundle of the tags `ids` with `corners` (n, 4, 3): c0..c2 are taken, c3 and the centre made as the loader makes them."""
+    tags = np.array([tag_from_three_corners(int(i), 0, c[0], c[1], c[2]) for i, c in zip(ids, np.asarray(corners, float))], dtype=TAG_DTYPE)
+    return Layout(tags, [frame], np.zeros(1, bool))
+
+
+def load_layout(path: str) -> Layout:
+    """loadTagsBundles (load_yaml_tags.h:75-105) from the YAML file `rosparam load` would read, through the C loader
+    (fid_stag_layout_load_file; host code, no device).  Raises FidError with the loader's message for a malformed file."""
+    L = _lib.load()
+    tags = np.zeros(4096, TAG_DTYPE)
+    standalone = np.zeros(1024, np.uint8)
+    frames = np.zeros((1024, FRAME_LEN), np.uint8)
+    nt, nb = C.c_int32(0), C.c_int32(0)
+    rc = L.fid_stag_layout_load_file(str(path).encode(), tags.ctypes.data, len(tags), C.byref(nt), C.byref(nb), standalone.ctypes.data,
+                                     frames.ctypes.data, len(standalone))
+    if rc != _lib.FID_OK:
+        raise FidError(rc, L.fid_stag_layout_last_error().decode() or L.fid_strerror(rc).decode())
+    names = [bytes(frames[b]).split(b"\0", 1)[0].decode() for b in range(nb.value)]
+    return Layout(tags[:nt.value].copy(), names, standalone[:nb.value].astype(bool))
+
+
+def _compact_K_D(K, D):
+    Kp = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+    Dp = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
+    return Kp, Dp
 
 
 class StagDetector:
@@ -141,6 +196,38 @@ class StagDetector:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return out[:n.value].copy()
 
+    def set_layout(self, layout: "Layout | None"):
+        """The context's bundles (fid_stag_set_layout); None or an empty layout clears it."""
+        tags = np.zeros(0, TAG_DTYPE) if layout is None else np.ascontiguousarray(layout.tags, dtype=TAG_DTYPE)
+        nb = 0 if layout is None or len(tags) == 0 else layout.n_bundles
+        rc = self._L.fid_stag_set_layout(self._ctx, tags.ctypes.data if len(tags) else None, len(tags), nb)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        self.layout = layout if len(tags) else None
+
+    def bundle_pose_last(self, K, D) -> np.ndarray:
+        """Common::solvePnpBundle for the markers of the last detect_markers*() call, on the device (BUNDLE_POSE_DTYPE): one record per
+        bundle of which a tag was found, in bundle order."""
+        Kp, Dp = _compact_K_D(K, D)
+        out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
+        n = C.c_int32(0)
+        rc = self._L.fid_stag_bundle_pose_last(self._ctx, Kp.ctypes.data, Dp.ctypes.data, out.ctypes.data, len(out), C.byref(n))
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return out[:n.value].copy()
+
+    def bundle_pose(self, K, D, markers: np.ndarray) -> np.ndarray:
+        """The same kernel on markers handed in from the host (MARKER_DTYPE; id, corners and center are read)."""
+        Kp, Dp = _compact_K_D(K, D)
+        m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)
+        out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
+        n = C.c_int32(0)
+        rc = self._L.fid_stag_bundle_pose(self._ctx, Kp.ctypes.data, Dp.ctypes.data, m.ctypes.data if len(m) else None, len(m), out.ctypes.data,
+                                          len(out), C.byref(n))
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return out[:n.value].copy()
+
     def queue_stats(self) -> tuple[int, int]:
         """(frames enqueued ahead of their own counts, how many of them had to be run again on the counted road)."""
         q, r = C.c_int32(0), C.c_int32(0)
@@ -214,6 +301,55 @@ class StagPool:
     def close(self):
         for d in self.dets:
             d.close()
+
+    def set_layout(self, layout: "Layout | None"):
+        """The same layout on every slot (what detect_bundles_batch asks for)."""
+        for d in self.dets:
+            d.set_layout(layout)
+
+    def _n_bundles(self) -> int:
+        lay = getattr(self.dets[0], "layout", None)
+        return lay.n_bundles if lay is not None else 0
+
+    def detect_bundles_batch(self, frames: np.ndarray, K, D=None, marker_size: float = 0.18, cap_per_frame: int = 64):
+        """detect_markers_batch with the bundle step behind the marker pose (fid_stag_detect_bundles_batch)
+        -> (markers per frame, poses per frame, bundle poses per frame)."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint8)
+        F, h, w = fr.shape
+        nb = max(self._n_bundles(), 1)
+        markers = np.zeros((F, cap_per_frame), MARKER_DTYPE)
+        poses = np.zeros((F, cap_per_frame), POSE_DTYPE)
+        bposes = np.zeros((F, nb), BUNDLE_POSE_DTYPE)
+        counts, bcounts = np.zeros(max(F, 1), np.int32), np.zeros(max(F, 1), np.int32)
+        Kp, Dp = _compact_K_D(K, D)
+        rc = self._L.fid_stag_detect_bundles_batch(self._arr, len(self.dets), fr.ctypes.data, F, w, h, w, w * h, Kp.ctypes.data, Dp.ctypes.data,
+                                                   float(marker_size), markers.ctypes.data, poses.ctypes.data, cap_per_frame, counts.ctypes.data,
+                                                   bposes.ctypes.data, bcounts.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return ([markers[f, :counts[f]] for f in range(F)], [poses[f, :counts[f]] for f in range(F)],
+                [bposes[f, :bcounts[f]] for f in range(F)])
+
+    def detect_bundles_batch_device(self, data_ptr: int, nframes: int, width: int, height: int, K, D=None, stride: int | None = None,
+                                    frame_stride: int | None = None, encoding: str = "mono8", marker_size: float = 0.18, cap_per_frame: int = 64):
+        """detect_bundles_batch on frames already resident on the pool's device (fid_stag_detect_bundles_batch_device)."""
+        enc = _lib.ENC.get(encoding, -1)
+        bpp = _lib.ENC_BYTES_PER_PIXEL.get(encoding, 1)
+        stride = stride or width * bpp
+        frame_stride = frame_stride or stride * height
+        nb = max(self._n_bundles(), 1)
+        markers = np.zeros((nframes, cap_per_frame), MARKER_DTYPE)
+        poses = np.zeros((nframes, cap_per_frame), POSE_DTYPE)
+        bposes = np.zeros((nframes, nb), BUNDLE_POSE_DTYPE)
+        counts, bcounts = np.zeros(max(nframes, 1), np.int32), np.zeros(max(nframes, 1), np.int32)
+        Kp, Dp = _compact_K_D(K, D)
+        rc = self._L.fid_stag_detect_bundles_batch_device(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride, frame_stride,
+                                                          enc, Kp.ctypes.data, Dp.ctypes.data, float(marker_size), markers.ctypes.data,
+                                                          poses.ctypes.data, cap_per_frame, counts.ctypes.data, bposes.ctypes.data, bcounts.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return ([markers[f, :counts[f]] for f in range(nframes)], [poses[f, :counts[f]] for f in range(nframes)],
+                [bposes[f, :bcounts[f]] for f in range(nframes)])
 
     def detect_markers_batch(self, frames: np.ndarray, K=None, D=None, marker_size: float = 0.18, cap_per_frame: int = 64):
         fr = np.ascontiguousarray(frames, dtype=np.uint8)

@@ -289,3 +289,62 @@ def make_stag_frame(codewords: np.ndarray, seed: int, width: int = 1920, height:
 def make_batch(d: Dictionary, seeds, **kw) -> tuple[np.ndarray, list[SynthFrame]]:
     frames = [make_frame(d, int(s), **kw) for s in seeds]
     return np.stack([f.image for f in frames]), frames
+
+
+@dataclass
+class StagBoardFrame:
+    image: np.ndarray          # (H, W) uint8
+    ids: np.ndarray            # (n,) int32, row-major over the board
+    R: np.ndarray              # (3, 3) board -> camera
+    rvec: np.ndarray           # (3,)
+    tvec: np.ndarray           # (3,)
+    corners_board: np.ndarray  # (n, 4, 3) c0..c3 of every tag in the board frame, clockwise from the tag's first corner
+    corners_image: np.ndarray  # (n, 4, 2) their projections
+
+
+def make_stag_board_frame(hd: int, ids, cols: int, rows: int, K, R, t, seed: int, width: int = 640, height: int = 480,
+                          tag_px: int = 96, tag_size: float = 0.08, gap_px: int = 40, noise_sigma: float = 2.0) -> StagBoardFrame:
+    """A flat board of STag tags (a docking plate, a calibration board) under ONE rigid pose: cols x rows tags of library HD<hd>,
+    stag_marker_gen.render(hd, id, tag_px, quiet_zone=0) pasted on white with gap_px between them and around them, tag_size metres
+    across a tag; seen by the pinhole camera K through the plane homography K [r1 r2 t], 3 x 3 samples a pixel, grey levels 25 ... 235
+    on a 150 background, blur sigma 0.8, noise, seeded.  Board frame: x right, y down, origin at the board's centre, z = 0."""
+    from .stag_marker_gen import render
+
+    rng = np.random.default_rng(seed)
+    ids = np.asarray(ids, dtype=np.int32)
+    assert len(ids) == cols * rows
+    K = np.asarray(K, float).reshape(3, 3)
+    R = np.asarray(R, float).reshape(3, 3)
+    t = np.asarray(t, float).reshape(3)
+    tw, th = cols * tag_px + (cols + 1) * gap_px, rows * tag_px + (rows + 1) * gap_px
+    tex = np.full((th, tw), 255, np.uint8)
+    mpp = tag_size / tag_px  # metres per texture pixel
+    cb = np.zeros((len(ids), 4, 3))
+    for k, tag_id in enumerate(ids):
+        gx, gy = k % cols, k // cols
+        x0, y0 = gap_px + gx * (tag_px + gap_px), gap_px + gy * (tag_px + gap_px)
+        tex[y0:y0 + tag_px, x0:x0 + tag_px] = render(hd, int(tag_id), tag_px, quiet_zone=0)
+        for c, (dx, dy) in enumerate(((0, 0), (tag_px, 0), (tag_px, tag_px), (0, tag_px))):
+            cb[k, c] = ((x0 + dx - tw / 2.0) * mpp, (y0 + dy - th / 2.0) * mpp, 0.0)
+    Hm = K @ np.stack([R[:, 0], R[:, 1], t], axis=1)  # board plane (X, Y, 1) -> image
+    Hi = np.linalg.inv(Hm)
+    ss = 3
+    sub = (np.arange(ss) + 0.5) / ss - 0.5
+    px = (np.arange(width)[:, None] + sub[None, :]).reshape(-1)
+    py = (np.arange(height)[:, None] + sub[None, :]).reshape(-1)
+    PX, PY = np.meshgrid(px, py)
+    den = Hi[2, 0] * PX + Hi[2, 1] * PY + Hi[2, 2]
+    U = (Hi[0, 0] * PX + Hi[0, 1] * PY + Hi[0, 2]) / den / mpp + tw / 2.0
+    V = (Hi[1, 0] * PX + Hi[1, 1] * PY + Hi[1, 2]) / den / mpp + th / 2.0
+    inside = (U >= 0) & (U < tw) & (V >= 0) & (V < th) & (den * np.sign(Hi[2, 2]) > 0)
+    ui = np.clip(np.floor(U).astype(np.int64), 0, tw - 1)
+    vi = np.clip(np.floor(V).astype(np.int64), 0, th - 1)
+    val = np.where(inside, 25.0 + (235.0 - 25.0) * tex[vi, ui].astype(np.float32) / 255.0, 150.0).astype(np.float32)
+    img = val.reshape(height, ss, width, ss).mean(axis=(1, 3))
+    img = _blur(img, 0.8)
+    if noise_sigma > 0:
+        img = img + rng.normal(0.0, noise_sigma, size=img.shape).astype(np.float32)
+    Pc = cb.reshape(-1, 3) @ R.T + t
+    uv = Pc @ K.T
+    ci = (uv[:, :2] / uv[:, 2:3]).reshape(len(ids), 4, 2)
+    return StagBoardFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), ids, R, _rot_to_rvec(R), t, cb, ci)

@@ -96,6 +96,23 @@ class Stag {
         return p;
     }
 
+    // the node's `bundles` and `tags` (stag_nodelet.h:90-91) on the device; an empty list clears them
+    void setLayout(const std::vector<fid_stag_tag> &tags, int n_bundles)
+    {
+        const fid_status rc = fid_stag_set_layout(ctx, tags.empty() ? nullptr : tags.data(), (int32_t)tags.size(), n_bundles);
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_set_layout: ") + fid_strerror(rc));
+    }
+    // Common::solvePnpBundle (common.hpp:48-59) for the markers of the last detectMarkers(): one record per bundle that was seen
+    std::vector<fid_stag_bundle_pose_out> solvePnpBundle(const double K[9], const double D[5])
+    {
+        std::vector<fid_stag_bundle_pose_out> p(FID_STAG_MAX_BUNDLES);
+        int32_t n = 0;
+        const fid_status rc = fid_stag_bundle_pose_last(ctx, K, D, p.data(), (int32_t)p.size(), &n);
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_bundle_pose_last: ") + fid_strerror(rc));
+        p.resize((size_t)n);
+        return p;
+    }
+
    private:
     void setMarkers(const std::vector<fid_stag_marker> &m, int32_t n)
     {
@@ -201,9 +218,18 @@ class StagNode {
         bool is_compressed = false, show_markers = true, publish_tf = false;
         std::string tag_tf_prefix = "STag_";
         float marker_size = 0.18f;
+        // the layout (loadTagsBundles, load_yaml_tags.h:75-105): the YAML file that holds `tags:` / `bundles:`, or the tags set in
+        // code -- layout_tags with, per bundle, its frame name and whether it is a standalone tag of the `tags:` list.  Neither: no
+        // layout, the node publishes what it always has.
+        std::string layout_file;
+        std::vector<fid_stag_tag> layout_tags;
+        std::vector<std::string> layout_frames;
+        std::vector<uint8_t> layout_standalone;
+        std::string bundles_topic = "stag_ros/bundles";
     };
     struct Outputs {
         std::vector<PoseStamped> markers;  // Common::publishTransform, one message per marker, in marker order
+        std::vector<PoseStamped> bundles;  // bundlePub (stag_nodelet.h:73): one per bundle that was seen, header.frame_id = its frame
         Detection2DArray array;
         std::vector<TransformStamped> tf;
         bool array_published = false;  // (the reference returns before markersArrayPub.publish when a pose comes back empty)
@@ -212,6 +238,26 @@ class StagNode {
     StagNode(const Params &p, const std::string &data_dir = "fiducials_amd/data", int max_width = 1920, int max_height = 1080, int device = 0)
         : params(p), stag(p.libraryHD, p.errorCorrection, false, data_dir, max_width, max_height, device), maxW(max_width), maxH(max_height), dev(device)
     {
+        if (!params.layout_file.empty()) {
+            int32_t nt = 0, nb = 0;
+            fid_status rc = fid_stag_layout_load_file(params.layout_file.c_str(), nullptr, 0, &nt, &nb, nullptr, nullptr, 0);
+            if (rc == FID_E_CAPACITY || (rc == FID_OK && nt > 0)) {
+                params.layout_tags.resize((size_t)nt);
+                params.layout_standalone.assign((size_t)nb, 0);
+                std::vector<char> names((size_t)nb * FID_STAG_FRAME_LEN);
+                rc = fid_stag_layout_load_file(params.layout_file.c_str(), params.layout_tags.data(), nt, &nt, &nb, params.layout_standalone.data(),
+                                               names.data(), nb);
+                params.layout_frames.clear();
+                for (int b = 0; b < nb; b++) params.layout_frames.push_back(std::string(names.data() + (size_t)b * FID_STAG_FRAME_LEN));
+            }
+            if (rc != FID_OK) throw std::invalid_argument(std::string("layout: ") + fid_stag_layout_last_error());
+        }
+        if (!params.layout_tags.empty()) {
+            if (params.layout_standalone.size() != params.layout_frames.size()) throw std::invalid_argument("layout: a frame name and a standalone flag per bundle");
+            for (const fid_stag_tag &t : params.layout_tags)
+                if (t.bundle < 0 || (size_t)t.bundle >= params.layout_frames.size()) throw std::invalid_argument("layout: bundle index without a frame name");
+            stag.setLayout(params.layout_tags, (int)params.layout_frames.size());
+        }
     }
     ~StagNode()
     {
@@ -259,6 +305,7 @@ class StagNode {
     bool imageCallback(const Image &msg, Outputs *out)
     {
         out->markers.clear();
+        out->bundles.clear();
         out->tf.clear();
         out->array = Detection2DArray();
         out->array_published = false;
@@ -286,6 +333,7 @@ class StagNode {
     {
         if (image) image->data.clear();
         out->markers.clear();
+        out->bundles.clear();
         out->tf.clear();
         out->array = Detection2DArray();
         out->array_published = false;
@@ -389,14 +437,34 @@ class StagNode {
     {
         const std::vector<Marker> markers = stag.getMarkerList();
         const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(K, D, (double)params.marker_size);
+        // with a layout: a member of a multi-tag bundle is not published on its own; a standalone tag of `tags:` is, posed from its
+        // own corners and under its own frame; ids the layout does not name keep the marker_size pose
+        std::vector<fid_stag_bundle_pose_out> bposes;
+        if (!params.layout_tags.empty()) bposes = stag.solvePnpBundle(K, D);
+        auto bundleOf = [this](int id) {  // getTagIndex / getBundleIndex (stag_nodelet.h:59-60)
+            for (const fid_stag_tag &t : params.layout_tags)
+                if (t.id == id) return (int)t.bundle;
+            return -1;
+        };
+        auto poseOf = [](const double R[9], const double tvec[3]) {
+            double q[4];
+            rotationToQuaternion(R, q);  // tf::Matrix3x3::getRotation
+            Pose pose;
+            pose.px = tvec[0]; pose.py = tvec[1]; pose.pz = tvec[2];
+            pose.ox = q[0]; pose.oy = q[1]; pose.oz = q[2]; pose.ow = q[3];
+            return pose;
+        };
         out->array.header = header;
         for (size_t i = 0; i < markers.size(); i++) {
-            double q[4];
-            rotationToQuaternion(poses[i].R, q);  // tf::Matrix3x3::getRotation
-            Pose pose;
-            pose.px = poses[i].tvec[0]; pose.py = poses[i].tvec[1]; pose.pz = poses[i].tvec[2];
-            pose.ox = q[0]; pose.oy = q[1]; pose.oz = q[2]; pose.ow = q[3];
-            const std::string id = std::to_string(markers[i].id);
+            Pose pose = poseOf(poses[i].R, poses[i].tvec);
+            std::string id = std::to_string(markers[i].id);
+            const int b = bundleOf(markers[i].id);
+            if (b >= 0) {
+                if (!params.layout_standalone[(size_t)b]) continue;
+                for (const fid_stag_bundle_pose_out &bp : bposes)
+                    if (bp.bundle == b) pose = poseOf(bp.R, bp.tvec);
+                id = params.layout_frames[(size_t)b];
+            }
             if (params.publish_tf) {  // Common::publishTransform: tf first, then the PoseStamped
                 TransformStamped t;
                 t.header = header;
@@ -418,6 +486,25 @@ class StagNode {
             hyp.pose = pose;
             det.results.push_back(hyp);
             out->array.detections.push_back(det);
+        }
+        for (const fid_stag_bundle_pose_out &bp : bposes) {
+            if (params.layout_standalone[(size_t)bp.bundle]) continue;
+            const Pose pose = poseOf(bp.R, bp.tvec);
+            const std::string &frame = params.layout_frames[(size_t)bp.bundle];
+            if (params.publish_tf) {
+                TransformStamped t;
+                t.header = header;
+                t.child_frame_id = params.tag_tf_prefix + frame;
+                t.tx = pose.px; t.ty = pose.py; t.tz = pose.pz;
+                t.qx = pose.ox; t.qy = pose.oy; t.qz = pose.oz; t.qw = pose.ow;
+                out->tf.push_back(t);
+            }
+            PoseStamped ps;
+            ps.header.frame_id = frame;
+            ps.header.sec = header.sec;
+            ps.header.nsec = header.nsec;
+            ps.pose = pose;
+            out->bundles.push_back(ps);
         }
         out->array_published = true;
     }

@@ -47,7 +47,8 @@ extern "C" {
  * 7: fid_detect* / fid_submit* take the raw-camera encodings themselves (FID_ENC_BAYER_*8, FID_ENC_MONO16 / BGR16 / RGB16 / BGRA16 /
  * RGBA16 [| FID_ENC_BIGENDIAN], FID_ENC_YUV422): the conversion cv_bridge::toCvCopy(msg, BGR8) + BGR2GRAY is folded into the
  * device's first kernel, so what crosses PCIe is the message's own bytes; + fid_encoding_from_string (round 6).  Added under 7
- * (entry points only): fid_stag_detect_markers_device, fid_stag_detect_markers_batch_device, FID_STAG_TAP_GRAY. */
+ * (entry points only): fid_stag_detect_markers_device, fid_stag_detect_markers_batch_device, FID_STAG_TAP_GRAY; the tag bundle
+ * family (fid_stag_tag, fid_stag_layout_load_file, fid_stag_set_layout, fid_stag_bundle_pose*, fid_stag_detect_bundles_batch*). */
 #define FID_ABI_VERSION 7
 
 typedef enum fid_status {
@@ -416,6 +417,74 @@ fid_status fid_stag_tap_read(fid_stag_ctx *ctx, fid_stag_tap which, void *dst, i
  * run under the other groups' kernels anyway); FID_STAG_SPEC=0 in the environment keeps every frame on it.  queued: frames enqueued that way since fid_stag_create; rerun: how
  * many of them had to be run again. */
 fid_status fid_stag_queue_stats(const fid_stag_ctx *ctx, int32_t *queued, int32_t *rerun);
+
+/* ---- tag bundles and per-tag geometry (additions to ABI 7: entry points and structs only).  The half of the reference's design
+ * that its imageCallback never calls: stag_ros/structures.hpp:6-16 (Tag, Bundle), stag_ros/load_yaml_tags.h:11-105 (the `tags:` /
+ * `bundles:` parameters), stag_ros/common.hpp:48-59 (solvePnpBundle), stag_ros/stag_nodelet.h:59-60,73,90-91 (getBundleIndex,
+ * getTagIndex, bundlePub, bundles, tags).  A BUNDLE is a rigid body with one or more tags whose corners are given in the body's
+ * frame; a standalone tag of the `tags:` list is a bundle of one tag; a LAYOUT is the set of bundles a context is configured with.
+ * Bounds: at most FID_STAG_MAX_BUNDLES bundles in a layout, at most FID_STAG_MAX_TAGS_PER_BUNDLE tags in a bundle (5 points a
+ * tag: 60 points, 120 residuals).  With no layout set nothing here launches a kernel and every other entry point behaves as
+ * before; with one set they still do (fid_stag_pose_last keeps posing every marker as a marker_size square). */
+#define FID_STAG_MAX_BUNDLES 64
+#define FID_STAG_MAX_TAGS_PER_BUNDLE 12
+#define FID_STAG_FRAME_LEN 64 /* bytes of a frame name slot, terminator included */
+/* Tag (structures.hpp:6-11) with the index of its bundle in place of the frame name */
+typedef struct fid_stag_tag {
+    int32_t id;
+    int32_t bundle;        /* index of the bundle the tag belongs to */
+    double corners[4][3];  /* c0..c3 in the bundle frame, in the order of fid_stag_marker.corners (clockwise from the first corner) */
+    double center[3];
+} fid_stag_tag;
+/* parseTags / parseBundles (load_yaml_tags.h:22-30, :56-64): a tag from the three corners the YAML gives: center = (c2 + c0) / 2,
+ * c3 = c0 + (c2 - c1) */
+fid_status fid_stag_tag_from_three_corners(int32_t id, int32_t bundle, const double c0[3], const double c1[3], const double c2[3],
+                                           fid_stag_tag *out);
+/* loadTagsBundles (load_yaml_tags.h:75-105) from the YAML file that `rosparam load` would put on the parameter server: top-level
+ * `tags:` = list of {id, frame, corners: [[x, y, z] x 3]}, top-level `bundles:` = list of {frame, tags: [{id, corners}]}; flow and
+ * block style of that subset.  Host code, no device.  Bundles come first, in file order, then every entry of `tags:` as a bundle of
+ * one tag with standalone[b] = 1; the tags are ordered by bundle.  standalone: [bundle_cap]; frames: [bundle_cap][FID_STAG_FRAME_LEN]
+ * (either may be NULL).  n_tags / n_bundles are always set; FID_E_CAPACITY if a cap is too small; a malformed file (and an id listed
+ * twice) is FID_E_INVALID_ARG with nothing written to tags -- never a half-read layout; fid_stag_layout_last_error() says what. */
+fid_status fid_stag_layout_load_file(const char *path, fid_stag_tag *tags, int32_t tag_cap, int32_t *n_tags, int32_t *n_bundles,
+                                     uint8_t *standalone, char *frames, int32_t bundle_cap);
+const char *fid_stag_layout_last_error(void);
+/* the context's layout (the node's `bundles` and `tags`, stag_nodelet.h:90-91), copied to the device; tags in any order, n_bundles =
+ * 1 + the largest bundle index, every bundle with at least one tag.  n_tags = 0 clears it.  Refused, layout unchanged:
+ * FID_E_INVALID_ARG for an id listed twice, an id outside the context's marker library (load it first), a tag with two equal
+ * corners, a bundle index outside [0, n_bundles), an empty bundle; FID_E_UNSUPPORTED for more than FID_STAG_MAX_BUNDLES bundles or
+ * more than FID_STAG_MAX_TAGS_PER_BUNDLE tags in one bundle. */
+fid_status fid_stag_set_layout(fid_stag_ctx *ctx, const fid_stag_tag *tags, int32_t n_tags, int32_t n_bundles);
+typedef struct fid_stag_bundle_pose_out {
+    int32_t bundle;  /* index in the layout */
+    int32_t n_tags;  /* tags of the bundle that were found (5 points each) */
+    double rvec[3], tvec[3];
+    double R[9];     /* cv::Rodrigues(rvec), row-major */
+} fid_stag_bundle_pose_out;
+/* Common::solvePnpBundle (common.hpp:48-59) for the markers of the last fid_stag_detect_markers* call, on the device: one record
+ * per bundle of which at least one tag was found, in bundle order.  Object points: centre, c0..c3 of every found tag, the tags in
+ * the order their markers stand in the marker list; image points: Marker::center, Marker::corners.  cv::solvePnP (ITERATIVE): for a
+ * coplanar set (OpenCV's test: eigenvalue ratio of the centred scatter matrix < 1e-3, not common.hpp:85-103 checkCoplanar) the
+ * homography start over all points, else the closed-form pose of the tag largest in the image composed with its place in the
+ * bundle; then CvLevMarq.  No layout: n_out = 0. */
+fid_status fid_stag_bundle_pose_last(fid_stag_ctx *ctx, const double K[9], const double D[5], fid_stag_bundle_pose_out *out, int32_t cap,
+                                     int32_t *n_out);
+/* the same kernel on n markers handed in from host memory (id, corners and center are read), as fid_pose does for aruco; the
+ * markers of the last detect call stay as they are.  n <= FID_STAG_MAX_BUNDLES * FID_STAG_MAX_TAGS_PER_BUNDLE. */
+fid_status fid_stag_bundle_pose(fid_stag_ctx *ctx, const double K[9], const double D[5], const fid_stag_marker *markers, int32_t n,
+                                fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out);
+/* fid_stag_detect_markers_batch / _batch_device with the bundle step (bundlePub, stag_nodelet.h:73) behind the marker pose, for
+ * contexts that all carry the same layout (FID_E_INVALID_ARG otherwise, or with none).  K is required.  bundle_poses: nframes x
+ * (the layout's number of bundles) records, frame f's first n_bundles_per_frame[f] filled, in bundle order. */
+fid_status fid_stag_detect_bundles_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width,
+                                         int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, const double K[9], const double D[5],
+                                         double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                         int32_t *n_per_frame, fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
+fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, fid_encoding enc,
+                                                const double K[9], const double D[5], double marker_size, fid_stag_marker *markers,
+                                                fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                                                fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * JPEG ingest.  With the launch file's default `transport:=compressed` (aruco_detect/launch/aruco_detect.launch:6) the frames

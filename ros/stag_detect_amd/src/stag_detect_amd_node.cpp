@@ -10,6 +10,9 @@
 // `stag_ros/markers_array` onto /fiducial_transforms (stag_detect.launch:10) works as before.
 // `~fiducial_msgs_output` (new, default false): publish fiducial_msgs/FiducialArray on `fiducial_vertices` and
 // FiducialTransformArray on `fiducial_transforms` as well -- the contract fiducial_slam consumes (BASELINE north_star).
+// `~tags` / `~bundles`: the layout, read as stag_ros::loadTagsBundles reads it (load_yaml_tags.h:75-105; `rosparam load` of the
+// deployer's YAML puts them there), or `~layout_file`: the path of that YAML for the library's own loader.  With a layout the node
+// advertises `stag_ros/bundles` (bundlePub, stag_nodelet.h:73): one PoseStamped per bundle that was seen.
 #include <fiducial_msgs/FiducialArray.h>
 #include <fiducial_msgs/FiducialTransformArray.h>
 #include <geometry_msgs/PoseStamped.h>
@@ -21,6 +24,8 @@
 #include <sensor_msgs/Image.h>
 #include <tf2_ros/transform_broadcaster.h>
 #include <vision_msgs/Detection2DArray.h>
+#include <XmlRpcException.h>
+#include <XmlRpcValue.h>
 
 #include <memory>
 #include <string>
@@ -57,6 +62,54 @@ geometry_msgs::Pose to_ros(const fa::Pose &p)
     return o;
 }
 
+// a coordinate of the parameter server: the YAML's `0` arrives as an int, `0.0` as a double
+double number(XmlRpc::XmlRpcValue &v)
+{
+    if (v.getType() == XmlRpc::XmlRpcValue::TypeInt) return (double)(int &)v;
+    return (double &)v;
+}
+// one tag description {id, corners: [[x, y, z] x 3]} (parseTags / parseBundles, load_yaml_tags.h:17-30, :51-64)
+fid_stag_tag parseTag(XmlRpc::XmlRpcValue &d, int bundle)
+{
+    double c[3][3];
+    XmlRpc::XmlRpcValue &corners = d["corners"];
+    if (corners.size() != 3) throw XmlRpc::XmlRpcException("a tag needs three corners");
+    for (int i = 0; i < 3; i++) {
+        if (corners[i].size() != 3) throw XmlRpc::XmlRpcException("a corner needs three numbers");
+        for (int a = 0; a < 3; a++) c[i][a] = number(corners[i][a]);
+    }
+    fid_stag_tag t;
+    (void)fid_stag_tag_from_three_corners((int)d["id"], bundle, c[0], c[1], c[2], &t);
+    return t;
+}
+// stag_ros::loadTagsBundles: `bundles` first, then every entry of `tags` as a bundle of one tag (the order of the file loader)
+void loadTagsBundles(const ros::NodeHandle &nh, fa::StagNode::Params *p)
+{
+    XmlRpc::XmlRpcValue tags, bundles;
+    try {
+        if (nh.getParam("bundles", bundles)) {
+            for (int b = 0; b < bundles.size(); b++) {
+                XmlRpc::XmlRpcValue &bt = bundles[b]["tags"];
+                for (int i = 0; i < bt.size(); i++) p->layout_tags.push_back(parseTag(bt[i], (int)p->layout_frames.size()));
+                p->layout_frames.push_back((std::string &)bundles[b]["frame"]);
+                p->layout_standalone.push_back(0);
+            }
+        }
+        if (nh.getParam("tags", tags)) {
+            for (int i = 0; i < tags.size(); i++) {
+                p->layout_tags.push_back(parseTag(tags[i], (int)p->layout_frames.size()));
+                p->layout_frames.push_back((std::string &)tags[i]["frame"]);
+                p->layout_standalone.push_back(1);
+            }
+        }
+    } catch (XmlRpc::XmlRpcException &e) {
+        ROS_ERROR("stag_detect_amd: error loading tag / bundle descriptions: %s", e.getMessage().c_str());
+        p->layout_tags.clear();
+        p->layout_frames.clear();
+        p->layout_standalone.clear();
+    }
+}
+
 class RosStagNode {
    public:
     RosStagNode() : pnh_("~"), it_(nh_)
@@ -80,6 +133,8 @@ class RosStagNode {
         pnh_.param("max_width", max_width, 1920);
         pnh_.param("max_height", max_height, 1080);
         pnh_.param("device", device, 0);
+        pnh_.param("layout_file", p.layout_file, std::string());
+        if (p.layout_file.empty()) loadTagsBundles(pnh_, &p);
         node_.reset(new fa::StagNode(p, data_dir, max_width, max_height, device));  // (throws std::invalid_argument like Stag::Stag)
 
         // is_compressed (the shipped cfg/single.yaml): the CompressedImage messages themselves, decoded by the node -- a JPEG on the
@@ -90,6 +145,7 @@ class RosStagNode {
         if (p.show_markers) debug_pub_ = it_.advertise("stag_ros/image_markers", 1);
         markers_pub_ = nh_.advertise<geometry_msgs::PoseStamped>(p.markers_topic, 10);
         array_pub_ = nh_.advertise<vision_msgs::Detection2DArray>(p.markers_array_topic, 10);
+        if (!node_->params.layout_tags.empty()) bundles_pub_ = nh_.advertise<geometry_msgs::PoseStamped>(p.bundles_topic, 10);
         if (fiducial_msgs_output_) {
             vertices_pub_ = nh_.advertise<fiducial_msgs::FiducialArray>("fiducial_vertices", 1);
             transforms_pub_ = nh_.advertise<fiducial_msgs::FiducialTransformArray>("fiducial_transforms", 1);
@@ -190,6 +246,22 @@ class RosStagNode {
             ps.pose = to_ros(out.markers[i].pose);
             markers_pub_.publish(ps);
         }
+        for (size_t i = 0; i < out.bundles.size(); i++) {  // (their TF stands behind the markers' in out.tf)
+            const size_t k = out.markers.size() + i;
+            if (node_->params.publish_tf && k < out.tf.size()) {
+                geometry_msgs::TransformStamped t;
+                t.header = to_ros(out.tf[k].header);
+                t.child_frame_id = out.tf[k].child_frame_id;
+                t.transform.translation.x = out.tf[k].tx; t.transform.translation.y = out.tf[k].ty; t.transform.translation.z = out.tf[k].tz;
+                t.transform.rotation.x = out.tf[k].qx; t.transform.rotation.y = out.tf[k].qy; t.transform.rotation.z = out.tf[k].qz;
+                t.transform.rotation.w = out.tf[k].qw;
+                broadcaster_.sendTransform(t);
+            }
+            geometry_msgs::PoseStamped ps;
+            ps.header = to_ros(out.bundles[i].header);
+            ps.pose = to_ros(out.bundles[i].pose);
+            bundles_pub_.publish(ps);
+        }
         vision_msgs::Detection2DArray arr;
         arr.header = to_ros(out.array.header);
         for (const fa::Detection2D &d : out.array.detections) {
@@ -249,7 +321,7 @@ class RosStagNode {
     image_transport::Subscriber image_sub_;
     image_transport::Publisher debug_pub_;
     ros::Subscriber caminfo_sub_, compressed_sub_;
-    ros::Publisher markers_pub_, array_pub_, vertices_pub_, transforms_pub_;
+    ros::Publisher markers_pub_, array_pub_, bundles_pub_, vertices_pub_, transforms_pub_;
     tf2_ros::TransformBroadcaster broadcaster_;
 };
 

@@ -6,6 +6,8 @@
 #include <functional>
 #include <memory>
 #include <string>
+
+#include "XmlRpcValue.h"
 namespace ros {
 struct Time {
     uint32_t sec = 0, nsec = 0;
@@ -23,6 +25,7 @@ class NodeHandle {
     explicit NodeHandle(const std::string &ns);
     template <typename T>
     bool param(const std::string &name, T &val, const T &def) const;
+    bool getParam(const std::string &key, XmlRpc::XmlRpcValue &v) const;
     template <typename M>
     Publisher advertise(const std::string &topic, uint32_t queue_size, bool latch = false);
     template <typename M, typename T>
