@@ -48,6 +48,15 @@ class FidPoseOut(C.Structure):
                 ("object_error", C.c_double), ("fiducial_area", C.c_double)]
 
 
+class FidMapEntry(C.Structure):
+    _fields_ = [("id", C.c_int32), ("reserved0", C.c_int32), ("len", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
+class FidMapPoseOut(C.Structure):
+    _fields_ = [("n_markers", C.c_int32), ("n_over", C.c_int32), ("rvec", C.c_double * 3), ("tvec", C.c_double * 3), ("R", C.c_double * 9),
+                ("cam_R", C.c_double * 9), ("cam_t", C.c_double * 3), ("image_error", C.c_double)]
+
+
 class FidLimits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_starts_per_frame", C.c_int32), ("max_contours_per_frame", C.c_int32),
@@ -88,6 +97,7 @@ def encoding_value(encoding: str, is_bigendian: bool = False) -> int:
     return v | ENC_BIGENDIAN if is_bigendian and 9 <= v <= 13 else v
 
 
+MAP_MAX_ENTRIES, MAP_MAX_USED = 4096, 256  # FID_MAP_MAX_ENTRIES, FID_MAP_MAX_USED
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -97,6 +107,7 @@ SYMBOLS = [
     "fid_last_stage_ms", "fid_last_launches", "fid_stream", "fid_strerror", "fid_last_error", "fid_abi_version",
     "fid_stag_create", "fid_stag_destroy", "fid_stag_edge_frontend", "fid_stag_detect_edges", "fid_stag_detect_edges_validated", "fid_stag_detect_lines", "fid_stag_detect_lines_validated", "fid_stag_detect_quads", "fid_stag_host_tables", "fid_stag_load_library", "fid_stag_detect_markers_unrefined", "fid_stag_detect_markers", "fid_stag_pose_last", "fid_stag_detect_markers_batch", "fid_stag_tap_bytes", "fid_stag_tap_read", "fid_stag_queue_stats", "fid_stag_detect_markers_device", "fid_stag_detect_markers_batch_device",
     "fid_stag_tag_from_three_corners", "fid_stag_layout_load_file", "fid_stag_layout_last_error", "fid_stag_set_layout", "fid_stag_bundle_pose_last", "fid_stag_bundle_pose", "fid_stag_detect_bundles_batch", "fid_stag_detect_bundles_batch_device",
+    "fid_map_load_file", "fid_map_last_error", "fid_map_entry_from_rpy", "fid_set_map", "fid_map_pose_last", "fid_map_pose",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
@@ -248,6 +259,13 @@ def load():
     L.fid_stag_bundle_pose.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.POINTER(i32)]
     L.fid_stag_detect_bundles_batch.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, vp, vp, C.c_double, vp, vp, i32, vp, vp, vp]
     L.fid_stag_detect_bundles_batch_device.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, vp, vp, C.c_double, vp, vp, i32, vp, vp, vp]
+    L.fid_map_load_file.argtypes = [C.c_char_p, C.c_double, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.fid_map_last_error.argtypes = []
+    L.fid_map_last_error.restype = C.c_char_p
+    L.fid_map_entry_from_rpy.argtypes = [i32, C.c_double, vp, vp, vp]
+    L.fid_set_map.argtypes = [vp, vp, i32]
+    L.fid_map_pose_last.argtypes = [vp, vp, vp, vp, i32]
+    L.fid_map_pose.argtypes = [vp, vp, vp, vp, i32, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

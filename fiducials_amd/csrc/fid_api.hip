@@ -154,6 +154,17 @@ struct fid_ctx {
     // same camera then only hands the results over.  Same kernel, same arithmetic, same results.
     bool pose_cam_valid = false, pose_done = false;
     double pose_K[9] = {}, pose_D[5] = {}, pose_len = 0.;
+    // the map of fiducials (fid_set_map; nothing of it exists until the first one is set): its ids ascending, per entry the four
+    // object points in the map frame; a fid_map_pose_out per frame of a batch and one more for fid_map_pose, on the device and in
+    // pinned host memory; room for markers handed in from the host.  map_cam_* / map_done: as pose_cam_* / pose_done, for k_map_pose
+    int *d_map_ids = nullptr;
+    double *d_map_obj = nullptr;
+    int map_n = 0;
+    fid_map_pose_out *d_mposes = nullptr, *h_mposes = nullptr;
+    fid_marker *d_map_in = nullptr;
+    int map_in_cap = 0;
+    bool map_cam_valid = false, map_done = false;
+    double map_K[9] = {}, map_D[5] = {};
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -164,6 +175,10 @@ struct fid_ctx {
     float stage_ms[ST_COUNT] = {};
     std::string last_error;
 };
+
+// k_map_pose for F frames on a stream (fid_map_pose.hip, at the end of this translation unit)
+static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
+                            const double K[9], const double D[5], fid_map_pose_out *d_out);
 
 namespace {
 
@@ -883,7 +898,15 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     HIPCHK(c, hipGetLastError());
     // ---- results
     c->pose_done = false;
+    c->map_done = false;
+    const bool map_ahead = c->map_n > 0 && c->map_cam_valid;
+    if (map_ahead) {
+        // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
+        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_K, c->map_D, c->d_mposes);
+        HIPCHK(c, hipGetLastError());
+    }
     HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_cam_valid ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
+    if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
     c->last_frames = F;
     c->last_W = W;
     c->last_H = H;
@@ -908,6 +931,7 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
     c->in_flight = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->pose_done = c->pose_cam_valid;
+    c->map_done = c->map_n > 0 && c->map_cam_valid;
     if (c->profile) {
         // a stage's time = its event-bracketed time on its own stream, summed over the sub-batches (with more than
         // one sub-batch the brackets of different streams overlap in wall time)
@@ -1265,10 +1289,11 @@ void fid_destroy(fid_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void *dev[] = {c->d_in, c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
                    c->d_ident, c->d_bits, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
-                   c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n};
+                   c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n,
+                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {c->h_res};
+    void *host[] = {c->h_res, c->h_mposes};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     for (int i = 0; i <= ST_COUNT; i++)
@@ -1831,3 +1856,5 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_draw.hip"
 #include "fid_dict.hip"
 #include "fid_stag_layout.hip"
+#include "fid_map.hip"
+#include "fid_map_pose.hip"

@@ -1,0 +1,525 @@
+// fid_map_pose.hip -- one camera pose per frame from a map of fiducials (fid_abi.h).  Part of the fid_api.hip translation unit,
+// behind fid_stag.hip: the kernel shares its device functions with k_pose (fid_kernels.hip: project_one, solve6_spd, lm_lambda,
+// the Rodrigues pair) and with k_stag_bundle_pose (fid_stag_pose.hip: sb_scatter_eig, sb_plane_frame, sb_dlt_entry,
+// sb_smallest_eigvec9, sb_pose_from_h, sp_undistort, wave_sum_f64).
+//
+// ------------------------------------------------------------------------------------------------ K19: map pose
+// cv::aruco::estimatePoseBoard: cv::solvePnP (ITERATIVE) over the four corners of every marker of a frame that the map names.
+// One wave per frame (blockIdx.x: a batch is one launch):
+//   (1) gather.  Lanes take the markers of the frame's list 64 at a time and binary-search the id in the map's sorted id table.
+//       A first pass marks every map entry that is hit (a bit per entry in LDS, set with an atomic or; a second hit sets the entry's
+//       bit in a second table): an id that occurs more than once in the frame is left out altogether.  The second pass compacts the
+//       survivors in list order (ballot + prefix count) and stops filling at MP_MAX_USED; the rest are counted.  Object points (the
+//       map's, double) and image points (the float corners widened) go to LDS, with the undistorted image point rounded to float
+//       (findHomography's input) and the marker's image area.
+//   (2) planarity: cvFindExtrinsicCameraParams2's test, the eigenvalues of the centred scatter matrix -- per-lane partial sums over
+//       the lane's points (p = lane, lane + 64, ...), then one xor butterfly per entry.
+//   (3) the start.  Coplanar: the points turned into their plane, the DLT homography over all of them with the float-input
+//       normalisation of HomographyEstimatorCallback::runKernel; each of the 45 entries of the 9 x 9 is a strided partial sum per
+//       lane and a butterfly.  Not coplanar: the closed-form pose of the used marker with the largest image area (the first of equals)
+//       composed with that marker's place in the map (OpenCV runs a 12 x 12 DLT there; the start is unpinned).
+//   (4) CvLevMarq as in k_pose: <= 20 iterations, lambda 10^k from -3, the same accept / reject and stop rule, plumb-bob distortion
+//       in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
+//       per-lane partial sums in residual order followed by one xor butterfly: a fixed order, reproducible from run to run, the same
+//       value in every lane.
+// LDS: 24 KB object points + 16 KB image points (the 40 KB of 1 024 points) + 16 KB of float pairs for the DLT + 7 KB of tables.
+#include <algorithm>
+
+#define MP_MAX_USED FID_MAP_MAX_USED
+#define MP_MAX_PTS (4 * MP_MAX_USED)
+#define MP_BIT_WORDS (FID_MAP_MAX_ENTRIES / 32)
+struct MpLds {
+    double obj[MP_MAX_PTS][3], img[MP_MAX_PTS][2];
+    float mn[MP_MAX_PTS][2], Mxy[MP_MAX_PTS][2];
+    double A[81], V[81], area[MP_MAX_USED];
+    int mk[MP_MAX_USED], ent[MP_MAX_USED];
+    unsigned seen[MP_BIT_WORDS], dup[MP_BIT_WORDS];
+};
+static_assert(sizeof(MpLds) <= 64 * 1024, "k_map_pose: static LDS");
+
+// index of id in the ascending table ids[0..n), or -1
+__device__ __forceinline__ int mp_find(const int *__restrict__ ids, int n, int id)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (ids[mid] < id)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return (lo < n && ids[lo] == id) ? lo : -1;
+}
+
+// HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS; every lane returns the same H
+__device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
+{
+    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
+    for (int i = lane; i < n; i += 64) {
+        cmx += s->mn[i][0];
+        cmy += s->mn[i][1];
+        cMx += s->Mxy[i][0];
+        cMy += s->Mxy[i][1];
+    }
+    cmx = wave_sum_f64(cmx) / n; cmy = wave_sum_f64(cmy) / n; cMx = wave_sum_f64(cMx) / n; cMy = wave_sum_f64(cMy) / n;
+    for (int i = lane; i < n; i += 64) {
+        smx += fabs(s->mn[i][0] - cmx);
+        smy += fabs(s->mn[i][1] - cmy);
+        sMx += fabs(s->Mxy[i][0] - cMx);
+        sMy += fabs(s->Mxy[i][1] - cMy);
+    }
+    smx = wave_sum_f64(smx); smy = wave_sum_f64(smy); sMx = wave_sum_f64(sMx); sMy = wave_sum_f64(sMy);
+    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
+    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
+    // LtL, entry (j, k), j <= k: the lane's points in their order, then the butterfly
+    for (int j = 0; j < 9; j++)
+        for (int k = j; k < 9; k++) {
+            double acc = 0;
+            for (int i = lane; i < n; i += 64) {
+                const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
+                const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
+                double lxj, lyj, lxk, lyk;
+                sb_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
+                sb_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
+                acc += lxj * lxk + lyj * lyk;
+            }
+            acc = wave_sum_f64(acc);
+            if (lane == 0) {
+                s->A[j * 9 + k] = acc;
+                s->A[k * 9 + j] = acc;
+            }
+        }
+    const int row = sb_smallest_eigvec9(s->A, s->V, lane);
+    double H0[9], T[9];
+    for (int i = 0; i < 9; i++) H0[i] = s->V[row * 9 + i];
+    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    sr_mul3(invHnorm, H0, T);
+    sr_mul3(T, Hnorm2, H0);
+    if (!(H0[8] != 0)) return false;
+    const double sc = 1. / H0[8];
+    for (int i = 0; i < 9; i++) H[i] = H0[i] * sc;
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
+                                                  int per_frame, const int *__restrict__ map_ids, const double *__restrict__ map_obj, int map_n,
+                                                  PoseCam cam, fid_map_pose_out *__restrict__ out)
+{
+    __shared__ MpLds s;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const double *K = cam.K, *kd = cam.D;
+    const fid_marker *mlist = markers + (long long)f * per_frame;
+    int nm = nmark_per_frame[(long long)f * nmark_stride_ints];
+    nm = nm < 0 ? 0 : (nm > per_frame ? per_frame : nm);
+    map_n = map_n > FID_MAP_MAX_ENTRIES ? FID_MAP_MAX_ENTRIES : map_n;
+    // ---- (1) the frame's markers that the map names, in list order, without the ids seen twice
+    for (int e = lane; e < MP_BIT_WORDS; e += 64) s.seen[e] = s.dup[e] = 0u;
+    SR_LDS_SYNC();
+    for (int m0 = 0; m0 < nm; m0 += 64) {
+        const int m = m0 + lane;
+        const int idx = m < nm ? mp_find(map_ids, map_n, mlist[m].id) : -1;
+        if (idx >= 0) {
+            const unsigned bit = 1u << (idx & 31);
+            if (atomicOr(&s.seen[idx >> 5], bit) & bit) atomicOr(&s.dup[idx >> 5], bit);
+        }
+    }
+    SR_LDS_SYNC();
+    int found = 0;
+    for (int m0 = 0; m0 < nm; m0 += 64) {
+        const int m = m0 + lane;
+        int idx = m < nm ? mp_find(map_ids, map_n, mlist[m].id) : -1;
+        if (idx >= 0 && (s.dup[idx >> 5] >> (idx & 31) & 1u)) idx = -1;
+        const unsigned long long hit = __ballot(idx >= 0);
+        if (idx >= 0) {
+            const int pos = found + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
+            if (pos < MP_MAX_USED) {
+                s.mk[pos] = m;
+                s.ent[pos] = idx;
+            }
+        }
+        found += __builtin_popcountll(hit);
+    }
+    const int n_over = found > MP_MAX_USED ? found - MP_MAX_USED : 0;
+    found -= n_over;
+    if (found == 0) {
+        if (lane == 0) {
+            fid_map_pose_out o;
+            o.n_markers = 0;
+            o.n_over = 0;
+            for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = o.cam_t[i] = 0.;
+            for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
+            o.image_error = 0.;
+            out[f] = o;
+        }
+        return;
+    }
+    SR_LDS_SYNC();
+    const int npts = 4 * found;
+    for (int p = lane; p < npts; p += 64) {
+        const int k = p >> 2, q = p & 3;
+        const fid_marker *mk = mlist + s.mk[k];
+        const double *src = map_obj + (size_t)s.ent[k] * 12 + q * 3;
+        for (int a = 0; a < 3; a++) s.obj[p][a] = src[a];
+        const double u = (double)mk->corners[2 * q], v = (double)mk->corners[2 * q + 1];
+        s.img[p][0] = u;
+        s.img[p][1] = v;
+        double x, y;
+        sp_undistort(K, kd, u, v, &x, &y);
+        s.mn[p][0] = (float)x;  // (the DLT's input: findHomography converts to float)
+        s.mn[p][1] = (float)y;
+        if (q == 0) {  // the marker's area in the image (shoelace over its four corners)
+            double a2 = 0;
+            for (int i = 0; i < 4; i++) {
+                const int i1 = (i + 1) & 3;
+                a2 += (double)mk->corners[2 * i] * (double)mk->corners[2 * i1 + 1] - (double)mk->corners[2 * i1] * (double)mk->corners[2 * i + 1];
+            }
+            s.area[k] = fabs(a2);
+        }
+    }
+    SR_LDS_SYNC();
+    // ---- (2) planarity: the centred scatter matrix of the object points and its eigenvalues (every lane the same)
+    double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
+    {
+        for (int p = lane; p < npts; p += 64)
+            for (int a = 0; a < 3; a++) Mc[a] += s.obj[p][a];
+        for (int a = 0; a < 3; a++) Mc[a] = wave_sum_f64(Mc[a]) / npts;
+        double m6[6] = {0, 0, 0, 0, 0, 0};
+        for (int p = lane; p < npts; p += 64) {
+            const double d[3] = {s.obj[p][0] - Mc[0], s.obj[p][1] - Mc[1], s.obj[p][2] - Mc[2]};
+            m6[0] += d[0] * d[0]; m6[1] += d[0] * d[1]; m6[2] += d[0] * d[2];
+            m6[3] += d[1] * d[1]; m6[4] += d[1] * d[2]; m6[5] += d[2] * d[2];
+        }
+        for (int i = 0; i < 6; i++) m6[i] = wave_sum_f64(m6[i]);
+        double MM[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
+        sb_scatter_eig(MM, W, Vt);
+    }
+    const bool planar = W[2] / W[1] < 1e-3;
+    // ---- (3) the start
+    double param[6] = {0, 0, 0, 0, 0, 0};
+    if (planar) {
+        double Rt[9], tt[3];
+        sb_plane_frame(Vt, Mc, Rt, tt);
+        for (int p = lane; p < npts; p += 64) {
+            const double *src = s.obj[p];
+            s.Mxy[p][0] = (float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
+            s.Mxy[p][1] = (float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
+        }
+        SR_LDS_SYNC();
+        double h[9], R[9];
+        if (mp_homography_dlt(&s, npts, lane, h)) {
+            double t3[3];
+            sb_pose_from_h(h, t3);
+            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
+            sr_mul3(h, Rt, R);
+        } else {
+            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+        }
+        rodrigues_m2v(R, param);
+    } else {
+        // the used marker with the largest image area, the first of equals: per lane over its markers, then a butterfly on (area, index)
+        int big = lane < found ? lane : 0;
+        double abig = s.area[big];
+        for (int k = lane + 64; k < found; k += 64)
+            if (s.area[k] > abig) {
+                abig = s.area[k];
+                big = k;
+            }
+        for (int mask = 1; mask < 64; mask <<= 1) {
+            const double ao = shfl_xor_f64(abig, mask);
+            const int bo = __shfl_xor(big, mask, WAVE);
+            if (ao > abig || (ao == abig && bo < big)) {
+                abig = ao;
+                big = bo;
+            }
+        }
+        const double *c0 = s.obj[4 * big], *c1 = s.obj[4 * big + 1], *c2 = s.obj[4 * big + 2], *c3 = s.obj[4 * big + 3];
+        // the marker's frame in the map: x along c0 -> c1, y along c3 -> c0, origin at its centre
+        double ex[3], ey[3], ez[3], cc[3];
+        for (int a = 0; a < 3; a++) {
+            ex[a] = c1[a] - c0[a];
+            ey[a] = c0[a] - c3[a];
+            cc[a] = 0.5 * (c0[a] + c2[a]);
+        }
+        const double wx = sqrt(ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2]), wy = sqrt(ey[0] * ey[0] + ey[1] * ey[1] + ey[2] * ey[2]);
+        for (int a = 0; a < 3; a++) ex[a] /= wx;
+        ez[0] = ex[1] * ey[2] - ex[2] * ey[1]; ez[1] = ex[2] * ey[0] - ex[0] * ey[2]; ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
+        const double wz = sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
+        for (int a = 0; a < 3; a++) ez[a] /= wz;
+        ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
+        double mnx[4], mny[4];
+        for (int i = 0; i < 4; i++) sp_undistort(K, kd, s.img[4 * big + i][0], s.img[4 * big + i][1], &mnx[i], &mny[i]);
+        // unit square -> quad, composed with (X, Y) -> ((X + wx / 2) / wx, (wy / 2 - Y) / wy): k_pose's start for a wx x wy marker
+        const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
+        const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
+        const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
+        const double den = dx1 * dy2 - dy1 * dx2;
+        double h[9], Rq[9], tq[3] = {0, 0, 0};
+        bool okh = den != 0. && wx > 0. && wy > 0. && wz > 0.;
+        if (okh) {
+            const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
+            const double a = x1 - x0 + gg * x1, bq = x3 - x0 + hh * x3, c = x0;
+            const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
+            const double scx = 1. / wx, scy = 1. / wy;
+            h[0] = a * scx;  h[1] = -bq * scy; h[2] = 0.5 * a + 0.5 * bq + c;
+            h[3] = d * scx;  h[4] = -e * scy;  h[5] = 0.5 * d + 0.5 * e + ff;
+            h[6] = gg * scx; h[7] = -hh * scy; h[8] = 0.5 * gg + 0.5 * hh + 1.;
+            okh = h[8] != 0.;
+            if (okh) {
+                const double sc = 1. / h[8];
+                for (int i = 0; i < 9; i++) h[i] *= sc;
+            }
+        }
+        if (okh) {
+            sb_pose_from_h(h, tq);
+            // map -> camera: X_cam = Rq B^T (X - centre) + tq, B = [ex ey ez]
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) Rq[3 * i + j] = h[3 * i] * ex[j] + h[3 * i + 1] * ey[j] + h[3 * i + 2] * ez[j];
+            for (int i = 0; i < 3; i++) param[3 + i] = tq[i] - (Rq[3 * i] * cc[0] + Rq[3 * i + 1] * cc[1] + Rq[3 * i + 2] * cc[2]);
+        } else {
+            for (int i = 0; i < 9; i++) Rq[i] = (i % 4 == 0) ? 1. : 0.;
+        }
+        rodrigues_m2v(Rq, param);
+    }
+    // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l, l + 64, ... (residual r: point r / 2, coordinate r % 2)
+    const int nres = 2 * npts;
+    double prevParam[6], S[21], gJ[6];
+    double errSq = 0, prevErrNorm = 0, errNorm = 0;
+    int lambdaLg10 = -3, iters = 0, state = 1;
+    for (int i = 0; i < 6; i++) prevParam[i] = param[i];
+    for (;;) {
+        bool needJ = false, needErr = false;
+        if (state == 1) {
+            needJ = needErr = true;
+            state = 2;
+        } else if (state == 2) {
+            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
+            double xs[6];
+            solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
+            for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
+            if (iters == 0) prevErrNorm = sqrt(errSq);
+            needErr = true;
+            state = 3;
+        } else {
+            errNorm = sqrt(errSq);
+            bool retry = false;
+            if (errNorm > prevErrNorm) {
+                if (++lambdaLg10 <= 16) {
+                    double xs[6];
+                    solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
+                    for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
+                    needErr = true;
+                    state = 3;
+                    retry = true;
+                }
+            }
+            if (!retry) {
+                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
+                double dn = 0, pn = 0;
+                for (int i = 0; i < 6; i++) {
+                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
+                    pn += prevParam[i] * prevParam[i];
+                }
+                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
+                if (++iters >= 20 || rel < FLT_EPSILON) break;
+                prevErrNorm = errNorm;
+                needJ = needErr = true;
+                state = 2;
+            }
+        }
+        if (!needErr) break;
+        // the residuals (and, with needJ, the normal equations) at param
+        double e2 = 0, Sp[21], gp[6];
+        for (int i = 0; i < 21; i++) Sp[i] = 0.;
+        for (int i = 0; i < 6; i++) gp[i] = 0.;
+        for (int r = lane; r < nres; r += 64) {
+            const int p = r >> 1, sel = r & 1;
+            const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
+            double Jrow[6];
+            const double err = project_one(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
+            e2 += err * err;
+            if (needJ) {
+                int idx = 0;
+#pragma unroll
+                for (int a = 0; a < 6; a++) {
+#pragma unroll
+                    for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
+                    gp[a] += Jrow[a] * err;
+                }
+            }
+        }
+        errSq = wave_sum_f64(e2);
+        if (needJ) {
+#pragma unroll
+            for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
+#pragma unroll
+            for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
+        }
+    }
+    // ---- getReprojectionError over the used points: projections rounded to float (vector<Point2f>), sum |d|^2 / P
+    double tot = 0;
+    for (int p = lane; p < npts; p += 64) {
+        const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
+        double Jrow[6];
+        const double dx = s.img[p][0] - (double)(float)project_one(M, param, K, kd, 0, Jrow, false);
+        const double dy = s.img[p][1] - (double)(float)project_one(M, param, K, kd, 1, Jrow, false);
+        const double e = sqrt(dx * dx + dy * dy);
+        tot += e * e;
+    }
+    tot = wave_sum_f64(tot);
+    if (lane == 0) {
+        fid_map_pose_out o;
+        o.n_markers = found;
+        o.n_over = n_over;
+        for (int i = 0; i < 3; i++) {
+            o.rvec[i] = param[i];
+            o.tvec[i] = param[3 + i];
+        }
+        double dummy[27];
+        rodrigues_v2m(param, o.R, dummy, false);
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) o.cam_R[3 * i + j] = o.R[3 * j + i];
+            o.cam_t[i] = -(o.R[i] * param[3] + o.R[3 + i] * param[4] + o.R[6 + i] * param[5]);
+        }
+        o.image_error = tot / npts;
+        out[f] = o;
+    }
+}
+
+// the kernel for F frames on stream st (fid_api.hip's enqueue_detect calls it for the batch it has just enqueued)
+static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
+                            const double K[9], const double D[5], fid_map_pose_out *d_out)
+{
+    PoseCam cam;
+    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
+    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.;
+    cam.fiducial_len = 0.;
+    hipLaunchKernelGGL(k_map_pose, dim3(F), dim3(64), 0, st, d_markers, d_n, n_stride_ints, per_frame, (const int *)c->d_map_ids,
+                       (const double *)c->d_map_obj, c->map_n, cam, d_out);
+}
+
+fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
+{
+    if (!c || n < 0 || (n > 0 && !entries)) return FID_E_INVALID_ARG;
+    if (c->in_flight) {
+        c->last_error = "a submitted batch is in flight: fid_collect first";
+        return FID_E_INVALID_ARG;
+    }
+    if (n > FID_MAP_MAX_ENTRIES) {
+        c->last_error = "a map holds at most " + std::to_string(FID_MAP_MAX_ENTRIES) + " entries (FID_MAP_MAX_ENTRIES), not " + std::to_string(n);
+        return FID_E_UNSUPPORTED;
+    }
+    std::vector<int> order((size_t)n);
+    for (int i = 0; i < n; i++) {
+        order[(size_t)i] = i;
+        const fid_map_entry &e = entries[i];
+        bool finite = e.len - e.len == 0;
+        for (int k = 0; k < 9; k++) finite = finite && e.R[k] - e.R[k] == 0;
+        for (int k = 0; k < 3; k++) finite = finite && e.t[k] - e.t[k] == 0;
+        if (!(e.len > 0) || !finite) {
+            c->last_error = "map entry " + std::to_string(i) + " (id " + std::to_string(e.id) + "): len must be positive and the transform finite";
+            return FID_E_INVALID_ARG;
+        }
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return entries[a].id < entries[b].id; });
+    for (int i = 1; i < n; i++)
+        if (entries[order[(size_t)i]].id == entries[order[(size_t)i - 1]].id) {
+            c->last_error = "map: id " + std::to_string(entries[order[(size_t)i]].id) + " is listed twice";
+            return FID_E_INVALID_ARG;
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->map_done = false;
+    if (n == 0) {
+        c->map_n = 0;
+        return FID_OK;
+    }
+    if (!c->d_map_ids) {
+        // the first map of this context: the tables at their largest, a result slot per frame of a batch (device and pinned host)
+        HIPCHK(c, hipMalloc((void **)&c->d_map_ids, sizeof(int) * FID_MAP_MAX_ENTRIES));
+        HIPCHK(c, hipMalloc((void **)&c->d_map_obj, sizeof(double) * 12 * FID_MAP_MAX_ENTRIES));
+        HIPCHK(c, hipMalloc((void **)&c->d_mposes, sizeof(fid_map_pose_out) * (size_t)(c->lim.max_batch + 1)));
+        HIPCHK(c, hipHostMalloc((void **)&c->h_mposes, sizeof(fid_map_pose_out) * (size_t)(c->lim.max_batch + 1), hipHostMallocDefault));
+    }
+    std::vector<int> ids((size_t)n);
+    std::vector<double> obj((size_t)n * 12);
+    for (int i = 0; i < n; i++) {
+        const fid_map_entry &e = entries[order[(size_t)i]];
+        ids[(size_t)i] = e.id;
+        const double h = (double)(float)(e.len / 2);  // (getSingleMarkerObjectPoints: Point3f)
+        const double cx[4] = {-h, h, h, -h}, cy[4] = {h, h, -h, -h};
+        for (int q = 0; q < 4; q++)
+            for (int a = 0; a < 3; a++) obj[(size_t)i * 12 + q * 3 + a] = e.R[3 * a] * cx[q] + e.R[3 * a + 1] * cy[q] + e.t[a];
+    }
+    HIPCHK(c, hipMemcpy(c->d_map_ids, ids.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_map_obj, obj.data(), sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice));
+    c->map_n = n;
+    return FID_OK;
+}
+
+fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], fid_map_pose_out *out, int32_t cap_frames)
+{
+    if (!c || !K || !out || c->last_frames <= 0) return FID_E_INVALID_ARG;
+    if (c->in_flight) {
+        c->last_error = "a submitted batch is in flight: fid_collect first";
+        return FID_E_INVALID_ARG;
+    }
+    if (c->map_n == 0) {
+        c->last_error = "no map: fid_set_map first";
+        return FID_E_INVALID_ARG;
+    }
+    const int F = c->last_frames;
+    if (cap_frames < F) {
+        c->last_error = "caller room for " + std::to_string(cap_frames) + " frames, the last call had " + std::to_string(F);
+        return FID_E_CAPACITY;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    double Dz[5] = {0., 0., 0., 0., 0.};
+    if (D) memcpy(Dz, D, sizeof Dz);
+    const bool same_cam = c->map_cam_valid && !memcmp(c->map_K, K, sizeof c->map_K) && !memcmp(c->map_D, Dz, sizeof Dz);
+    if (!(same_cam && c->map_done)) {  // (else: the detect call already ran k_map_pose for this camera on these markers)
+        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, K, Dz, c->d_mposes);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        memcpy(c->map_K, K, sizeof c->map_K);
+        memcpy(c->map_D, Dz, sizeof Dz);
+        c->map_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
+        c->map_done = c->map_cam_valid;
+    }
+    memcpy(out, c->h_mposes, sizeof(fid_map_pose_out) * (size_t)F);
+    return FID_OK;
+}
+
+fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const fid_marker *markers, int32_t n, fid_map_pose_out *out)
+{
+    if (!c || !K || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
+    if (c->in_flight) {
+        c->last_error = "a submitted batch is in flight: fid_collect first";
+        return FID_E_INVALID_ARG;
+    }
+    if (c->map_n == 0) {
+        c->last_error = "no map: fid_set_map first";
+        return FID_E_INVALID_ARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n > c->map_in_cap || !c->d_map_in) {
+        if (c->d_map_in) (void)hipFree(c->d_map_in);
+        c->d_map_in = nullptr;
+        c->map_in_cap = 0;
+        const int cap = (n + 256) / 256 * 256;
+        HIPCHK(c, hipMalloc((void **)&c->d_map_in, sizeof(fid_marker) * (size_t)cap + sizeof(int)));
+        c->map_in_cap = cap;
+    }
+    int *d_n = (int *)((char *)c->d_map_in + sizeof(fid_marker) * (size_t)c->map_in_cap);
+    fid_map_pose_out *d_out = c->d_mposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
+    const int nn = n;
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (nn is a stack temporary)
+    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, K, D, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FID_OK;
+}

@@ -1034,6 +1034,54 @@ __device__ __forceinline__ void sb_dlt_entry(int j, double X, double Y, double x
     *ly = j < 3 ? 0.0 : (j < 6 ? b : -y * b);
 }
 
+// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 A (LDS, both triangles filled; destroyed), by cyclic Jacobi in
+// LDS: the rotation's angle in every lane, lane k < 9 turns its entries.  V: 81 doubles of LDS, its rows the eigenvectors.  Returns
+// the row, the same in every lane.
+__device__ int sb_smallest_eigvec9(double *A, double *V, int lane)
+{
+    for (int e = lane; e < 81; e += 64) V[e] = (e / 9 == e % 9) ? 1. : 0.;
+    SR_LDS_SYNC();
+    for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) off += A[p * 9 + q] * A[p * 9 + q];
+        if (!(off >= 1e-300)) break;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) {
+                const double apq = A[p * 9 + q];
+                if (fabs(apq) < 1e-300) continue;  // (wave-uniform)
+                const double app = A[p * 9 + p], aqq = A[q * 9 + q];
+                const double theta = (aqq - app) / (2. * apq);
+                const double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                const double c = 1. / sqrt(t * t + 1.), sn = t * c;
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double akp = A[lane * 9 + p], akq = A[lane * 9 + q];
+                    A[lane * 9 + p] = c * akp - sn * akq;
+                    A[lane * 9 + q] = sn * akp + c * akq;
+                }
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double apk = A[p * 9 + lane], aqk = A[q * 9 + lane];
+                    A[p * 9 + lane] = c * apk - sn * aqk;
+                    A[q * 9 + lane] = sn * apk + c * aqk;
+                    const double vpk = V[p * 9 + lane], vqk = V[q * 9 + lane];
+                    V[p * 9 + lane] = c * vpk - sn * vqk;
+                    V[q * 9 + lane] = sn * vpk + c * vqk;
+                }
+                SR_LDS_SYNC();
+            }
+    }
+    int row = 0;
+    double wmin = A[0];
+    for (int i = 1; i < 9; i++)
+        if (A[i * 9 + i] <= wmin) {
+            wmin = A[i * 9 + i];
+            row = i;
+        }
+    return row;
+}
+
 // HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS (both already rounded to
 // float, as findHomography converts its inputs); every lane returns the same H
 __device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
@@ -1074,47 +1122,7 @@ __device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
         s->A[j * 9 + k] = acc;
         s->A[k * 9 + j] = acc;
     }
-    for (int e = lane; e < 81; e += 64) s->V[e] = (e / 9 == e % 9) ? 1. : 0.;
-    SR_LDS_SYNC();
-    // cyclic Jacobi on the 9 x 9 (rows of V = eigenvectors): the rotation's angle in every lane, lane k < 9 turns its entries
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) off += s->A[p * 9 + q] * s->A[p * 9 + q];
-        if (!(off >= 1e-300)) break;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) {
-                const double apq = s->A[p * 9 + q];
-                if (fabs(apq) < 1e-300) continue;  // (wave-uniform)
-                const double app = s->A[p * 9 + p], aqq = s->A[q * 9 + q];
-                const double theta = (aqq - app) / (2. * apq);
-                const double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-                const double c = 1. / sqrt(t * t + 1.), sn = t * c;
-                SR_LDS_SYNC();
-                if (lane < 9) {
-                    const double akp = s->A[lane * 9 + p], akq = s->A[lane * 9 + q];
-                    s->A[lane * 9 + p] = c * akp - sn * akq;
-                    s->A[lane * 9 + q] = sn * akp + c * akq;
-                }
-                SR_LDS_SYNC();
-                if (lane < 9) {
-                    const double apk = s->A[p * 9 + lane], aqk = s->A[q * 9 + lane];
-                    s->A[p * 9 + lane] = c * apk - sn * aqk;
-                    s->A[q * 9 + lane] = sn * apk + c * aqk;
-                    const double vpk = s->V[p * 9 + lane], vqk = s->V[q * 9 + lane];
-                    s->V[p * 9 + lane] = c * vpk - sn * vqk;
-                    s->V[q * 9 + lane] = sn * vpk + c * vqk;
-                }
-                SR_LDS_SYNC();
-            }
-    }
-    int row = 0;
-    double wmin = s->A[0];
-    for (int i = 1; i < 9; i++)
-        if (s->A[i * 9 + i] <= wmin) {
-            wmin = s->A[i * 9 + i];
-            row = i;
-        }
+    const int row = sb_smallest_eigvec9(s->A, s->V, lane);
     double H0[9], T[9];
     for (int i = 0; i < 9; i++) H0[i] = s->V[row * 9 + i];
     const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
@@ -1141,6 +1149,46 @@ __device__ __forceinline__ void sb_pose_from_h(double h[9], double t3[3])
     double rtmp[3], dummy[27];
     rodrigues_m2v(h, rtmp);
     rodrigues_v2m(rtmp, h, dummy, false);
+}
+
+// eigenvalues (descending, cv::SVD's order) and eigenvectors (the rows of Vt) of the centred scatter matrix MM (destroyed)
+__device__ __forceinline__ void sb_scatter_eig(double MM[3][3], double W[3], double Vt[3][3])
+{
+    jacobi3(MM, Vt);
+    W[0] = MM[0][0]; W[1] = MM[1][1]; W[2] = MM[2][2];
+    // eigenvalues descending, the rows of Vt with them (cv::SVD's order)
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        int mx = i;
+#pragma unroll
+        for (int j = i + 1; j < 3; j++)
+            if (W[j] > W[mx]) mx = j;
+        if (mx != i) {
+            const double t = W[i];
+            W[i] = W[mx];
+            W[mx] = t;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double u = Vt[i][k];
+                Vt[i][k] = Vt[mx][k];
+                Vt[mx][k] = u;
+            }
+        }
+    }
+}
+
+// the frame of a coplanar set (cvFindExtrinsicCameraParams2, planar branch): Rt turns the points into their plane (the scatter
+// matrix's eigenvectors, made right-handed; the identity when the plane is z = const already), tt = -Rt Mc
+__device__ __forceinline__ void sb_plane_frame(const double Vt[3][3], const double Mc[3], double Rt[9], double tt[3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Rt[3 * i + j] = Vt[i][j];
+    if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10)
+        for (int i = 0; i < 9; i++) Rt[i] = (i % 4 == 0) ? 1. : 0.;
+    const double det = Rt[0] * (Rt[4] * Rt[8] - Rt[5] * Rt[7]) - Rt[1] * (Rt[3] * Rt[8] - Rt[5] * Rt[6]) + Rt[2] * (Rt[3] * Rt[7] - Rt[4] * Rt[6]);
+    if (det < 0)
+        for (int i = 0; i < 9; i++) Rt[i] = -Rt[i];
+    for (int i = 0; i < 3; i++) tt[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
 }
 
 __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
@@ -1226,42 +1274,14 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
 #pragma unroll
                 for (int c = 0; c < 3; c++) MM[a][c] += d[a] * d[c];
         }
-        jacobi3(MM, Vt);
-        W[0] = MM[0][0]; W[1] = MM[1][1]; W[2] = MM[2][2];
-        // eigenvalues descending, the rows of Vt with them (cv::SVD's order)
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            int mx = i;
-#pragma unroll
-            for (int j = i + 1; j < 3; j++)
-                if (W[j] > W[mx]) mx = j;
-            if (mx != i) {
-                const double t = W[i];
-                W[i] = W[mx];
-                W[mx] = t;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const double u = Vt[i][k];
-                    Vt[i][k] = Vt[mx][k];
-                    Vt[mx][k] = u;
-                }
-            }
-        }
+        sb_scatter_eig(MM, W, Vt);
     }
     const bool planar = W[2] / W[1] < 1e-3;
     // ---- (3) the start
     double param[6] = {0, 0, 0, 0, 0, 0};
     if (planar) {
-        double Rt[9];
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) Rt[3 * i + j] = Vt[i][j];
-        if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10)
-            for (int i = 0; i < 9; i++) Rt[i] = (i % 4 == 0) ? 1. : 0.;
-        const double det = Rt[0] * (Rt[4] * Rt[8] - Rt[5] * Rt[7]) - Rt[1] * (Rt[3] * Rt[8] - Rt[5] * Rt[6]) + Rt[2] * (Rt[3] * Rt[7] - Rt[4] * Rt[6]);
-        if (det < 0)
-            for (int i = 0; i < 9; i++) Rt[i] = -Rt[i];
-        double tt[3];
-        for (int i = 0; i < 3; i++) tt[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
+        double Rt[9], tt[3];
+        sb_plane_frame(Vt, Mc, Rt, tt);
         if (lane < npts) {
             const double *src = s.obj[lane];
             s.Mxy[lane][0] = (double)(float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);

@@ -37,6 +37,9 @@ class PoseResult:
 
 
 _MARKER_DT = np.dtype([("id", "<i4"), ("corners", "<f4", (8,))])  # fid_marker
+MAP_ENTRY_DTYPE = np.dtype([("id", "<i4"), ("reserved0", "<i4"), ("len", "<f8"), ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])  # fid_map_entry
+MAP_POSE_DTYPE = np.dtype([("n_markers", "<i4"), ("n_over", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("R", "<f8", (3, 3)),
+                           ("cam_R", "<f8", (3, 3)), ("cam_t", "<f8", (3,)), ("image_error", "<f8")])  # fid_map_pose_out
 _POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("image_error", "<f8"), ("object_error", "<f8"), ("fiducial_area", "<f8")])
 
 
@@ -54,6 +57,46 @@ def _poses_to_result(arr, n) -> PoseResult:
         object_error=np.array([arr[i].object_error for i in range(n)]),
         fiducial_area=np.array([arr[i].fiducial_area for i in range(n)]),
     )
+
+
+def map_entry_from_rpy(fid: int, length: float, xyz, rpy_deg) -> np.ndarray:
+    """One map entry (MAP_ENTRY_DTYPE scalar) from a position and roll, pitch, yaw in degrees, the map file's convention
+    (fid_map_entry_from_rpy)."""
+    L = _lib.load()
+    e = np.zeros(1, MAP_ENTRY_DTYPE)
+    p = np.ascontiguousarray(xyz, dtype=np.float64).reshape(3)
+    a = np.ascontiguousarray(rpy_deg, dtype=np.float64).reshape(3)
+    rc = L.fid_map_entry_from_rpy(int(fid), float(length), p.ctypes.data, a.ctypes.data, e.ctypes.data)
+    if rc != _lib.FID_OK:
+        raise FidError(rc, (L.fid_map_last_error() or b"").decode() or L.fid_strerror(rc).decode())
+    return e[0]
+
+
+def map_entries(ids, lengths, Rs, ts) -> np.ndarray:
+    """Map entries from transforms T_map_fid given as matrices: ids (n,), lengths scalar or (n,), Rs (n, 3, 3), ts (n, 3)."""
+    ids = np.asarray(ids, np.int32).reshape(-1)
+    e = np.zeros(len(ids), MAP_ENTRY_DTYPE)
+    e["id"] = ids
+    e["len"] = lengths
+    e["R"] = np.asarray(Rs, np.float64).reshape(len(ids), 3, 3)
+    e["t"] = np.asarray(ts, np.float64).reshape(len(ids), 3)
+    return e
+
+
+def load_map(path: str, fiducial_len: float, fiducial_len_override: dict | None = None):
+    """A fiducial_slam map file (fiducial_slam/src/map.cpp:541-625; fid_map_load_file): returns (entries, n_skipped) -- the
+    entries as MAP_ENTRY_DTYPE with len = fiducial_len, or its per-id override (the node's fiducial_len_override list), and the
+    number of lines that were passed over."""
+    L = _lib.load()
+    n, skipped = C.c_int32(0), C.c_int32(0)
+    e = np.zeros(_lib.MAP_MAX_ENTRIES, MAP_ENTRY_DTYPE)
+    rc = L.fid_map_load_file(str(path).encode(), float(fiducial_len), e.ctypes.data, len(e), C.byref(n), C.byref(skipped))
+    if rc != _lib.FID_OK:
+        raise FidError(rc, (L.fid_map_last_error() or b"").decode() or L.fid_strerror(rc).decode())
+    e = e[:n.value].copy()
+    for k, v in (fiducial_len_override or {}).items():
+        e["len"][e["id"] == int(k)] = float(v)
+    return e, int(skipped.value)
 
 
 class ArucoDetector:
@@ -272,6 +315,39 @@ class ArucoDetector:
             n = max(int(self._n[f]), 0)
             res.append(_poses_view_to_result(self._poses_np[f * self.max_markers:f * self.max_markers + n]))
         return res
+
+    # -- the camera among the fiducials of a map ----------------------------------------------------
+    def set_map(self, entries) -> None:
+        """The map the camera is posed against (fid_set_map): MAP_ENTRY_DTYPE records (load_map, map_entries, map_entry_from_rpy);
+        None or an empty array clears it."""
+        e = np.zeros(0, MAP_ENTRY_DTYPE) if entries is None else np.ascontiguousarray(entries, dtype=MAP_ENTRY_DTYPE).reshape(-1)
+        self._check(self._L.fid_set_map(self._ctx, e.ctypes.data if len(e) else None, len(e)))
+
+    @staticmethod
+    def _cam(K, D):
+        Kc = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        Dc = None if D is None else np.ascontiguousarray(np.asarray(D, dtype=np.float64).reshape(-1)[:5])
+        return Kc, Dc
+
+    def map_pose_last(self, K, D) -> np.ndarray:
+        """One camera pose per frame of the last detect_* / collect call (fid_map_pose_last): MAP_POSE_DTYPE records."""
+        Kc, Dc = self._cam(K, D)
+        out = np.zeros(max(self._last_frames, 1), MAP_POSE_DTYPE)
+        self._check(self._L.fid_map_pose_last(self._ctx, Kc.ctypes.data, Dc.ctypes.data if Dc is not None else None, out.ctypes.data, len(out)))
+        return out[:self._last_frames]
+
+    def map_pose(self, K, D, corners, ids) -> np.ndarray:
+        """The same kernel on the markers of one frame handed in from the host (fid_map_pose): corners (n, 4, 2), ids (n,) in list
+        order.  Returns one MAP_POSE_DTYPE record."""
+        Kc, Dc = self._cam(K, D)
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        mk = np.zeros(len(ids), _MARKER_DT)
+        mk["id"] = ids
+        mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        out = np.zeros(1, MAP_POSE_DTYPE)
+        self._check(self._L.fid_map_pose(self._ctx, Kc.ctypes.data, Dc.ctypes.data if Dc is not None else None,
+                                         mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data))
+        return out[0]
 
     # -- stage taps for parity tests ------------------------------------------------------------
     def tap(self, which: int) -> np.ndarray:

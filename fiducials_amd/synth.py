@@ -348,3 +348,83 @@ def make_stag_board_frame(hd: int, ids, cols: int, rows: int, K, R, t, seed: int
     uv = Pc @ K.T
     ci = (uv[:, :2] / uv[:, 2:3]).reshape(len(ids), 4, 2)
     return StagBoardFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), ids, R, _rot_to_rvec(R), t, cb, ci)
+
+
+@dataclass
+class ArucoBoardFrame:
+    image: np.ndarray          # (H, W) uint8
+    ids: np.ndarray            # (n,) int32
+    R: np.ndarray              # (3, 3) map -> camera
+    rvec: np.ndarray           # (3,)
+    tvec: np.ndarray           # (3,)
+    corners_map: np.ndarray    # (n, 4, 3) the four corners of every marker in the map frame (aruco_detect.cpp:151-161 order)
+    corners_image: np.ndarray  # (n, 4, 2) their projections
+
+
+def make_aruco_board_frame(d: Dictionary, ids, placements, K, R, t, seed: int, width: int = 640, height: int = 480,
+                           noise_sigma: float = 2.0, border_bits: int = 1) -> ArucoBoardFrame:
+    """Aruco markers that sit rigidly in ONE map (a board, a corner of two walls), seen through ONE camera pose.  placements: per
+    marker (length, R_map_fid (3, 3), t_map_fid (3,)) -- the marker's frame (x right, y up, z out of its face) in the map frame;
+    R, t: the map frame in the camera frame (solvePnP's convention); K: pinhole, no distortion.  Every marker is rendered as in
+    make_frame (drawMarker raster with a one-cell white quiet zone, inverse homography, 3 x 3 samples a pixel, grey levels 25 / 230)
+    on a 128 background with a low-frequency gradient, blur sigma 0.8, seeded noise.  Markers facing away from the camera are left
+    out of the picture (their corners are still reported)."""
+    rng = np.random.default_rng(seed)
+    ids = np.asarray(ids, dtype=np.int32)
+    assert len(ids) == len(placements)
+    K = np.asarray(K, float).reshape(3, 3)
+    R = np.asarray(R, float).reshape(3, 3)
+    t = np.asarray(t, float).reshape(3)
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float32)
+    gdir, gamp, phase = rng.uniform(0, 2 * np.pi), rng.uniform(10, 30), rng.uniform(0, 2 * np.pi)
+    img = (128.0 + gamp * np.sin((np.cos(gdir) * xx / width + np.sin(gdir) * yy / height) * np.pi + phase)).astype(np.float32)
+    ncell = d.marker_size + 2 * border_bits
+    q = 1.0  # quiet zone in cells
+    cm = np.zeros((len(ids), 4, 3))
+    ci = np.zeros((len(ids), 4, 2))
+
+    def proj(Pm):
+        uv = (Pm @ R.T + t) @ K.T
+        return uv[:, :2] / uv[:, 2:3]
+
+    for mi, (length, Rf, tf) in enumerate(placements):
+        Rf = np.asarray(Rf, float).reshape(3, 3)
+        tf = np.asarray(tf, float).reshape(3)
+        hl = length / 2
+        cm[mi] = np.array([[-hl, hl, 0], [hl, hl, 0], [hl, -hl, 0], [-hl, -hl, 0]]) @ Rf.T + tf
+        ci[mi] = proj(cm[mi])
+        normal_cam = R @ Rf[:, 2]
+        centre_cam = R @ tf + t
+        if float(normal_cam @ centre_cam) >= 0:  # the face looks away
+            continue
+        ext = hl + q * length / ncell
+        pq = proj(np.array([[-ext, ext, 0], [ext, ext, 0], [ext, -ext, 0], [-ext, -ext, 0]]) @ Rf.T + tf)
+        tex = np.array([[-q, -q], [ncell + q, -q], [ncell + q, ncell + q], [-q, ncell + q]], dtype=np.float64)
+        A = []
+        for (x, y), (u, v) in zip(pq, tex):
+            A.append([x, y, 1, 0, 0, 0, -u * x, -u * y, -u])
+            A.append([0, 0, 0, x, y, 1, -v * x, -v * y, -v])
+        H = np.linalg.svd(np.array(A))[2][-1].reshape(3, 3)
+        x0, x1 = int(max(0, np.floor(pq[:, 0].min()) - 1)), int(min(width, np.ceil(pq[:, 0].max()) + 2))
+        y0, y1 = int(max(0, np.floor(pq[:, 1].min()) - 1)), int(min(height, np.ceil(pq[:, 1].max()) + 2))
+        if x1 <= x0 or y1 <= y0:
+            continue
+        ss = 3
+        sub = (np.arange(ss) + 0.5) / ss - 0.5
+        PX, PY = np.meshgrid((np.arange(x0, x1)[:, None] + sub[None, :]).reshape(-1), (np.arange(y0, y1)[:, None] + sub[None, :]).reshape(-1))
+        den = H[2, 0] * PX + H[2, 1] * PY + H[2, 2]
+        U = (H[0, 0] * PX + H[0, 1] * PY + H[0, 2]) / den
+        V = (H[1, 0] * PX + H[1, 1] * PY + H[1, 2]) / den
+        inside = (U >= -q) & (U < ncell + q) & (V >= -q) & (V < ncell + q)
+        tiny = np.full((ncell + 2, ncell + 2), 230.0, dtype=np.float32)
+        tiny[1:-1, 1:-1] = np.where(draw_marker(d, int(ids[mi]), ncell, border_bits) > 0, 230.0, 25.0)
+        val = tiny[np.clip(np.floor(V + q).astype(np.int64), 0, ncell + 1), np.clip(np.floor(U + q).astype(np.int64), 0, ncell + 1)]
+        hh, ww = y1 - y0, x1 - x0
+        cnt = inside.reshape(hh, ss, ww, ss).sum(axis=(1, 3)).astype(np.float32)
+        col = (val * inside).reshape(hh, ss, ww, ss).sum(axis=(1, 3)).astype(np.float32)
+        cov = cnt / (ss * ss)
+        img[y0:y1, x0:x1] = img[y0:y1, x0:x1] * (1 - cov) + np.where(cnt > 0, col / np.maximum(cnt, 1), 0) * cov
+    img = _blur(img, 0.8)
+    if noise_sigma > 0:
+        img = img + rng.normal(0.0, noise_sigma, size=img.shape).astype(np.float32)
+    return ArucoBoardFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), ids, R, _rot_to_rvec(R), t, cm, ci)

@@ -68,6 +68,10 @@ struct Pose {  // geometry_msgs/Pose
     double px = 0, py = 0, pz = 0;
     double ox = 0, oy = 0, oz = 0, ow = 1;
 };
+struct PoseStamped {  // geometry_msgs/PoseStamped
+    Header header;
+    Pose pose;
+};
 struct ObjectHypothesisWithPose {  // vision_msgs/ObjectHypothesisWithPose (Noetic: int64 id, float64 score, PoseWithCovariance)
     int64_t id = 0;
     double score = 0;
@@ -95,6 +99,9 @@ struct PoseOutputs {
     FiducialTransformArray fta;
     Detection2DArray vma;
     std::vector<TransformStamped> tf;
+    // with ~map_file set and at least one mapped fiducial in sight: the camera in the map (frame_id "map"), one solvePnP over the
+    // corners of every mapped marker (fid_map_pose_last); empty otherwise
+    std::vector<PoseStamped> map_pose;
 };
 
 // ROS 1 wire format of the two output messages (little-endian, packed)
@@ -130,6 +137,8 @@ class FiducialsNode {
         std::string data_dir = "fiducials_amd/data";
         std::string dictionary_file;  // non-empty: the table of ~dictionary comes from this file (loadDictionaryFile) -- the way to
                                       // run the families whose shipped tables are fillers (4X4_1000, 6X6, 7X7, ARUCO_ORIGINAL)
+        std::string map_file;  // non-empty: a fiducial_slam map file (fid_map_load_file; ~fiducial_len and ~fiducial_len_override give
+                               // the lengths); poseEstimateCallback then also reports the camera in the map (PoseOutputs::map_pose)
         int device = 0, max_width = 1920, max_height = 1080;
         Params();
     };
@@ -189,6 +198,7 @@ class FiducialsNode {
     double cameraMatrix[9] = {0}, distortionCoeffs[5] = {0};
     bool haveCamInfo = false, enable_detections = true, doPoseEstimation = true, verbose = false;
     bool vis_msgs = false, publishFiducialTf = true, publish_images = false;
+    bool haveMap = false;
     double fiducial_len = 0.14;
     int frameNum = 0;
     std::string frameId, last_error;

@@ -204,11 +204,6 @@ inline void stagImageCallback(Stag &stag, const Image &msg, const CameraInfo &ca
 // common.hpp:72-82), one vision_msgs/Detection2DArray on `stag_ros/markers_array` (stag_detect.cpp:139-209; the shipped launch
 // remaps it onto /fiducial_transforms, stag_detect.launch:10) and, with `publish_tf`, <image frame> -> <tag_tf_prefix><id>.
 // ros/stag_detect_amd is the catkin glue around this class; host/test/stag_test.cpp runs it on the GPU box.
-struct PoseStamped {  // geometry_msgs/PoseStamped
-    Header header;
-    Pose pose;
-};
-
 class StagNode {
    public:
     struct Params {  // StagNode::loadParameters (stag_detect.cpp:88-108) with its defaults

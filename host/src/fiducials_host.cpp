@@ -188,6 +188,28 @@ FiducialsNode::FiducialsNode(const Params &p)
     const fid_status rc = fid_create(&detectorParams, &fd, &lim, p.device, &ctx);
     if (rc != FID_OK) throw std::runtime_error(std::string("fid_create: ") + fid_strerror(rc));
     markers.resize(1024);
+    if (!p.map_file.empty()) {
+        std::vector<fid_map_entry> entries(FID_MAP_MAX_ENTRIES);
+        int32_t n = 0, skipped = 0;
+        fid_status mrc = fid_map_load_file(p.map_file.c_str(), fiducial_len, entries.data(), (int32_t)entries.size(), &n, &skipped);
+        if (mrc == FID_OK) {
+            for (int32_t i = 0; i < n; i++) {  // the per-id lengths (:241-244)
+                auto it = fiducialLens.find(entries[(size_t)i].id);
+                if (it != fiducialLens.end()) entries[(size_t)i].len = it->second;
+            }
+            mrc = fid_set_map(ctx, entries.data(), n);
+            if (mrc != FID_OK) last_error = fid_last_error(ctx);
+        } else {
+            last_error = fid_map_last_error();
+        }
+        if (mrc != FID_OK) {
+            const std::string what = "map_file " + p.map_file + ": " + last_error;
+            fid_destroy(ctx);
+            throw std::runtime_error(what);
+        }
+        if (skipped > 0) last_error = "map_file " + p.map_file + ": " + std::to_string(skipped) + " invalid line(s) passed over";
+        haveMap = n > 0;
+    }
 }
 
 FiducialsNode::~FiducialsNode()
@@ -556,6 +578,51 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
                 ts.header.nsec = msg.header.nsec;
                 ts.child_frame_id = "fiducial_" + std::to_string(ids[i]);
                 po.tf.push_back(ts);
+            }
+        }
+        if (haveMap && n > 0) {
+            // the camera among the map's fiducials: the markers of the last image are still on the device (fid_map_pose_last; the
+            // detect call has run the kernel already once the camera is known); with ids ignored, the list without them
+            fid_map_pose_out mp;
+            fid_status mrc;
+            if (ignoreIds.empty()) {
+                mrc = fid_map_pose_last(ctx, cameraMatrix, distortionCoeffs, &mp, 1);
+            } else {
+                std::vector<fid_marker> kept;
+                for (int i = 0; i < n; i++)
+                    if (std::count(ignoreIds.begin(), ignoreIds.end(), ids[i]) == 0) kept.push_back(markers[(size_t)i]);
+                mrc = fid_map_pose(ctx, cameraMatrix, distortionCoeffs, kept.data(), (int32_t)kept.size(), &mp);
+            }
+            if (mrc != FID_OK) {
+                last_error = fid_last_error(ctx);
+                return false;
+            }
+            if (mp.n_markers > 0) {
+                // the camera in the map: cam_R as a unit quaternion, cam_t
+                const double *R = mp.cam_R;
+                double q[4];  // x y z w
+                const double tr = R[0] + R[4] + R[8];
+                if (tr > 0) {
+                    const double s4 = 2.0 * std::sqrt(tr + 1.0);
+                    q[3] = 0.25 * s4; q[0] = (R[7] - R[5]) / s4; q[1] = (R[2] - R[6]) / s4; q[2] = (R[3] - R[1]) / s4;
+                } else if (R[0] > R[4] && R[0] > R[8]) {
+                    const double s4 = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
+                    q[3] = (R[7] - R[5]) / s4; q[0] = 0.25 * s4; q[1] = (R[1] + R[3]) / s4; q[2] = (R[2] + R[6]) / s4;
+                } else if (R[4] > R[8]) {
+                    const double s4 = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
+                    q[3] = (R[2] - R[6]) / s4; q[0] = (R[1] + R[3]) / s4; q[1] = 0.25 * s4; q[2] = (R[5] + R[7]) / s4;
+                } else {
+                    const double s4 = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
+                    q[3] = (R[3] - R[1]) / s4; q[0] = (R[2] + R[6]) / s4; q[1] = (R[5] + R[7]) / s4; q[2] = 0.25 * s4;
+                }
+                PoseStamped ps;
+                ps.header.frame_id = "map";
+                ps.header.sec = msg.header.sec;
+                ps.header.nsec = msg.header.nsec;
+                ps.header.seq = msg.header.seq;
+                ps.pose.px = mp.cam_t[0]; ps.pose.py = mp.cam_t[1]; ps.pose.pz = mp.cam_t[2];
+                ps.pose.ox = q[0]; ps.pose.oy = q[1]; ps.pose.oz = q[2]; ps.pose.ow = q[3];
+                po.map_pose.push_back(ps);
             }
         }
     }

@@ -48,7 +48,8 @@ extern "C" {
  * RGBA16 [| FID_ENC_BIGENDIAN], FID_ENC_YUV422): the conversion cv_bridge::toCvCopy(msg, BGR8) + BGR2GRAY is folded into the
  * device's first kernel, so what crosses PCIe is the message's own bytes; + fid_encoding_from_string (round 6).  Added under 7
  * (entry points only): fid_stag_detect_markers_device, fid_stag_detect_markers_batch_device, FID_STAG_TAP_GRAY; the tag bundle
- * family (fid_stag_tag, fid_stag_layout_load_file, fid_stag_set_layout, fid_stag_bundle_pose*, fid_stag_detect_bundles_batch*). */
+ * family (fid_stag_tag, fid_stag_layout_load_file, fid_stag_set_layout, fid_stag_bundle_pose*, fid_stag_detect_bundles_batch*); the
+ * fiducial map family (fid_map_entry, fid_map_load_file, fid_map_entry_from_rpy, fid_set_map, fid_map_pose_last, fid_map_pose). */
 #define FID_ABI_VERSION 7
 
 typedef enum fid_status {
@@ -213,6 +214,55 @@ fid_status fid_pose(fid_ctx *ctx, const double K[9], const double D[5], const fi
  * poses for frame f start at out[f * cap_per_frame]. */
 fid_status fid_pose_last(fid_ctx *ctx, const double K[9], const double D[5], double fiducial_len,
                          fid_pose_out *out, int32_t cap_per_frame);
+
+/* ---- one camera pose per frame from a map of fiducials (additions to ABI 7: entry points and structs only).  What a consumer of
+ * the per-marker poses does next: locate the camera among fiducials whose places are known -- a fiducial_slam map file
+ * (fiducial_slam/src/map.cpp:541-625), or a board / rigid body that carries several markers.  The arithmetic is
+ * cv::aruco::estimatePoseBoard's: ONE cv::solvePnP (ITERATIVE) over the four corners of every detected marker that the map names.
+ * A context without a map behaves exactly as before: no extra launch, no allocation. */
+#define FID_MAP_MAX_ENTRIES 4096
+#define FID_MAP_MAX_USED 256 /* mapped markers of one frame that enter the pose (1 024 points); the rest are counted in n_over */
+typedef struct fid_map_entry {
+    int32_t id;
+    int32_t reserved0;
+    double len;  /* side length; the corners are (-h, h, 0), (h, h, 0), (h, -h, 0), (-h, -h, 0) in the fiducial's frame with
+                    h = (double)(float)(len / 2) (getSingleMarkerObjectPoints, aruco_detect.cpp:151-161: Point3f) */
+    double R[9]; /* T_map_fid: the fiducial's frame in the map frame, row-major rotation ... */
+    double t[3]; /* ... and translation */
+} fid_map_entry;
+/* the file fiducial_slam writes and reads (map.cpp:541-625): one line per fiducial, `id x y z roll pitch yaw variance numObs
+ * [links...]`, angles in degrees, rotation = tf2::Quaternion::setRPY(roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll).  A line is
+ * valid when sscanf would fill 9 or 10 fields; other lines are skipped and counted in *n_skipped (the reference warns and carries
+ * on).  variance, numObs and the links are read and dropped; len = fiducial_len for every entry (the caller applies its
+ * fiducial_len_override list afterwards).  Host code, no device.  FID_E_INVALID_ARG: the file cannot be opened, an id appears
+ * twice, fiducial_len <= 0; FID_E_CAPACITY: more entries than cap (*n = the number the file holds).  fid_map_last_error() says
+ * what, for the calling thread. */
+fid_status fid_map_load_file(const char *path, double fiducial_len, fid_map_entry *entries, int32_t cap, int32_t *n, int32_t *n_skipped);
+const char *fid_map_last_error(void);
+/* one entry from a position and roll, pitch, yaw in degrees (the file's convention): a board built in code */
+fid_status fid_map_entry_from_rpy(int32_t id, double len, const double xyz[3], const double rpy_deg[3], fid_map_entry *out);
+/* the context's map, copied to the device (ids sorted, the four object points of every entry in the map frame, double).  n = 0
+ * clears it.  Refused, the map unchanged: FID_E_UNSUPPORTED for more than FID_MAP_MAX_ENTRIES entries; FID_E_INVALID_ARG for
+ * len <= 0 (or not finite), an id listed twice, a batch in flight; fid_last_error names the bound. */
+fid_status fid_set_map(fid_ctx *ctx, const fid_map_entry *entries, int32_t n);
+typedef struct fid_map_pose_out {
+    int32_t n_markers;   /* markers used; 0 = no pose, everything else zero */
+    int32_t n_over;      /* mapped markers beyond the first FID_MAP_MAX_USED, not used (ids seen twice are dropped uncounted) */
+    double rvec[3], tvec[3];
+    double R[9];         /* cv::Rodrigues(rvec), row-major: the map frame in the camera frame (solvePnP's convention) */
+    double cam_R[9];     /* the camera in the map frame: R^T ... */
+    double cam_t[3];     /* ... and -R^T tvec */
+    double image_error;  /* getReprojectionError (aruco_detect.cpp:203-221) over the used points: mean squared error, px^2 */
+} fid_map_pose_out;
+/* the camera pose of every frame of the last fid_detect* / fid_collect, one record per frame (cap_frames >= the frame count, else
+ * FID_E_CAPACITY).  Markers of the frame's list in list order, corners 0..3 of each; ids the map does not name are skipped; an
+ * id that occurs more than once in the frame is left out altogether.  Coplanar points (cvFindExtrinsicCameraParams2's test): the
+ * homography start over all of them; otherwise the closed-form pose of the mapped marker with the largest image area composed
+ * with its place in the map; then CvLevMarq.  As with fid_pose_last: once called, the next fid_detect* / fid_submit* runs the
+ * kernel for the same camera in its own stream, and the call after it is a copy.  No map: FID_E_INVALID_ARG. */
+fid_status fid_map_pose_last(fid_ctx *ctx, const double K[9], const double D[5], fid_map_pose_out *out, int32_t cap_frames);
+/* the same kernel on n markers of one frame handed in from host memory; the last detect call's results stay as they are */
+fid_status fid_map_pose(fid_ctx *ctx, const double K[9], const double D[5], const fid_marker *markers, int32_t n, fid_map_pose_out *out);
 
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
