@@ -113,6 +113,8 @@ SYMBOLS = [
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
     "fid_to_bgr", "fid_image_to_bgr8", "fid_encoding_from_string", "fid_draw_detected_markers", "fid_dict_load_file", "fid_dict_last_error",
     "fid_to_bgr_device", "fid_draw_detected_markers_device", "fid_jpeg_marker_image",
+    "fid_jpeg_enc_create", "fid_jpeg_enc_destroy", "fid_jpeg_enc_last_error", "fid_jpeg_enc_set", "fid_jpeg_encode_device", "fid_jpeg_encode",
+    "fid_jpeg_enc_header", "fid_jpeg_marker_jpeg", "fid_jpeg_enc_tap_bytes", "fid_jpeg_enc_tap_read", "fid_jpeg_enc_last_ms",
 ]
 
 _LIB = None
@@ -291,6 +293,22 @@ def load():
         L.fid_to_bgr_device.argtypes = [vp, i32, i32, i32, i32, i64, C.c_int, vp, i32, i64]
         L.fid_draw_detected_markers_device.argtypes = [vp, i32, i32, i32, i32, i64, C.POINTER(FidMarker), i32, C.POINTER(i32), C.c_uint32]
         L.fid_jpeg_marker_image.argtypes = [vp, i32, C.c_int, C.POINTER(FidMarker), i32, C.c_uint32, vp, i64]
+    if hasattr(L, "fid_jpeg_enc_create"):  # (JPEG encoding on the device; FID_LIB may name a build from before it)
+        L.fid_jpeg_enc_create.argtypes = [i32, i32, i32, i32, i64, C.POINTER(vp)]
+        L.fid_jpeg_enc_destroy.argtypes = [vp]
+        L.fid_jpeg_enc_destroy.restype = None
+        L.fid_jpeg_enc_last_error.argtypes = [vp]
+        L.fid_jpeg_enc_last_error.restype = C.c_char_p
+        L.fid_jpeg_enc_last_ms.argtypes = [vp]
+        L.fid_jpeg_enc_last_ms.restype = C.c_float
+        L.fid_jpeg_enc_set.argtypes = [vp, i32, i32]
+        L.fid_jpeg_encode_device.argtypes = [vp, vp, i32, i32, i32, i32, i64, C.c_int, vp, i64, C.POINTER(i64)]
+        L.fid_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, i32, i64, C.c_int, vp, i64, C.POINTER(i64)]
+        L.fid_jpeg_enc_header.argtypes = [i32, i32, i32, i32, i32, vp, i64, C.POINTER(i64)]
+        L.fid_jpeg_marker_jpeg.argtypes = [vp, i32, C.c_int, C.POINTER(FidMarker), i32, C.c_uint32, vp, vp, i64, C.POINTER(i64)]
+        L.fid_jpeg_enc_tap_bytes.argtypes = [vp, i32]
+        L.fid_jpeg_enc_tap_bytes.restype = i64
+        L.fid_jpeg_enc_tap_read.argtypes = [vp, i32, vp, i64]
     L.fid_dict_load_file.argtypes = [C.c_char_p, i32, vp, i64, C.POINTER(FidDict)]
     L.fid_dict_last_error.argtypes = []
     L.fid_dict_last_error.restype = C.c_char_p

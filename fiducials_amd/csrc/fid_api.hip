@@ -1854,6 +1854,7 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_jpeg.hip"
 #include "fid_png.hip"
 #include "fid_draw.hip"
+#include "fid_jpeg_enc.hip"
 #include "fid_dict.hip"
 #include "fid_stag_layout.hip"
 #include "fid_map.hip"

@@ -84,3 +84,98 @@ class JpegDecoder:
 
     def last_rounds(self) -> int:
         return int(self._L.fid_jpeg_last_rounds(self._ctx))
+
+    def marker_jpeg(self, frame: int, base: str, markers, encoder: "JpegEncoder", flags: int = 0) -> bytes:
+        """The marker image of frame `frame` of the last decode (what fid_jpeg_marker_image returns: the decoded `base` image as
+        BGR with the outlines of `markers`, an (n, 4, 2) array of corners) as the JPEG file `encoder` makes of it on the device."""
+        q = np.asarray(markers, np.float32).reshape(-1, 8)
+        mk = (_lib.FidMarker * max(len(q), 1))()
+        for i in range(len(q)):
+            mk[i].id = i
+            for j in range(8):
+                mk[i].corners[j] = float(q[i, j])
+        out = np.empty(encoder.max_file_bytes, np.uint8)
+        nb = C.c_int64()
+        self._check(self._L.fid_jpeg_marker_jpeg(self._ctx, frame, _lib.ENC[base], mk, len(q), flags, encoder._ctx, out.ctypes.data, out.nbytes,
+                                                 C.byref(nb)))
+        return out[:nb.value].tobytes()
+
+
+def header(quality: int, subsampling: int, width: int, height: int, components: int) -> bytes:
+    """The bytes in front of the entropy-coded data of the file the encoder writes (host code, no device)."""
+    L = _lib.load()
+    out = np.empty(1024, np.uint8)
+    nb = C.c_int64()
+    rc = L.fid_jpeg_enc_header(quality, subsampling, width, height, components, out.ctypes.data, out.nbytes, C.byref(nb))
+    if rc != _lib.FID_OK:
+        raise FidError(rc, L.fid_strerror(rc).decode())
+    return out[:nb.value].tobytes()
+
+
+class JpegEncoder:
+    """cv::imencode(".jpg") on the device -- Python mirror of the `fid_jpeg_enc_*` entry points: the file libjpeg(-turbo) writes
+    with its defaults at `quality` and chroma `subsampling` (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0), byte for byte."""
+
+    def __init__(self, max_width: int = 1920, max_height: int = 1080, max_batch: int = 1, quality: int = 80, subsampling: int = 2, device: int = 0,
+                 max_file_bytes: int = 0):
+        self._L = _lib.load()
+        self._ctx = C.c_void_p()
+        rc = self._L.fid_jpeg_enc_create(device, max_width, max_height, max_batch, max_file_bytes, C.byref(self._ctx))
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        self.max_width, self.max_height, self.max_batch = max_width, max_height, max_batch
+        # (the default of fid_jpeg_enc_create: two bytes a pixel of the MCU-padded frame + 64 KiB + the header)
+        self.max_file_bytes = max_file_bytes or ((max_width + 15) // 16 * 16) * ((max_height + 15) // 16 * 16) * 2 + 65536 + 640
+        self.set(quality, subsampling)
+
+    def close(self):
+        if self._ctx:
+            self._L.fid_jpeg_enc_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _check(self, rc):
+        if rc != _lib.FID_OK:
+            raise FidError(rc, (self._L.fid_jpeg_enc_last_error(self._ctx) or b"").decode() or self._L.fid_strerror(rc).decode())
+
+    def set(self, quality: int, subsampling: int):
+        self._check(self._L.fid_jpeg_enc_set(self._ctx, quality, subsampling))
+        self.quality, self.subsampling = quality, subsampling
+
+    def _files(self, call, n):
+        out = np.empty((n, self.max_file_bytes), np.uint8)
+        sizes = (C.c_int64 * n)()
+        self._check(call(out.ctypes.data, self.max_file_bytes, sizes))
+        return [out[f, :sizes[f]].tobytes() for f in range(n)]
+
+    def encode(self, frames, encoding: str = "bgr8"):
+        """frames: (n, H, W) mono8 or (n, H, W, 3) bgr8 / rgb8 (or one frame without the leading axis) -> a list of `bytes`."""
+        a = np.ascontiguousarray(frames, np.uint8)
+        if a.ndim == (2 if encoding == "mono8" else 3):
+            a = a[None]
+        n, h, w = a.shape[:3]
+        bpp = _lib.ENC_BYTES_PER_PIXEL[encoding]
+        return self._files(lambda out, cap, sizes: self._L.fid_jpeg_encode(self._ctx, a.ctypes.data, n, w, h, w * bpp, h * w * bpp, _lib.ENC[encoding], out,
+                                                                           cap, sizes), n)
+
+    def encode_device(self, ptr: int, n: int, width: int, height: int, stride: int, frame_stride: int, encoding: str = "bgr8"):
+        """n frames in device memory (a torch tensor's data_ptr(), JpegDecoder.device_ptr()) -> a list of `bytes`."""
+        return self._files(lambda out, cap, sizes: self._L.fid_jpeg_encode_device(self._ctx, C.c_void_p(ptr), n, width, height, stride, frame_stride,
+                                                                                  _lib.ENC[encoding], out, cap, sizes), n)
+
+    def last_ms(self) -> float:
+        """device time of the last call's launches (events on the context's stream), ms"""
+        return float(self._L.fid_jpeg_enc_last_ms(self._ctx))
+
+    def tap(self, frame: int = 0) -> np.ndarray:
+        """int16 quantised coefficients of the last call's frame `frame`, natural order, component after component,
+        [blocks_h][blocks_w][64] each (the layout of the decoder's TAP_COEFS)"""
+        nb = self._L.fid_jpeg_enc_tap_bytes(self._ctx, frame)
+        out = np.empty(nb // 2, np.int16)
+        self._check(self._L.fid_jpeg_enc_tap_read(self._ctx, frame, out.ctypes.data, nb))
+        return out

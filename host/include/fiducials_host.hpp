@@ -9,6 +9,7 @@
 #include <array>
 #include <cstdint>
 #include <map>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -168,6 +169,13 @@ class FiducialsNode {
     // the host.  The vertices are those of the two-argument form.  image->data is empty unless an image is published; with
     // publish_images off or image == nullptr the call is the two-argument form.
     bool compressedImageCallback(const CompressedImage &msg, FiducialArray *out, Image *image);
+    // ... and with what /fiducial_images/compressed carries (image_transport offers that topic for every image publisher,
+    // aruco_detect.cpp:662): the same marker image as the JPEG file compressed_image_transport's publisher makes of it
+    // (cv::imencode(".jpg") at its default quality), format "bgr8; jpeg compressed bgr8".  For a JPEG frame the image is drawn AND
+    // compressed on the device (fid_jpeg_marker_jpeg): only the file crosses to the host.  A PNG frame's image is drawn on the host
+    // and compressed on the device (fid_jpeg_encode).  image->data is empty unless an image is published.
+    bool compressedImageCallback(const CompressedImage &msg, FiducialArray *out, CompressedImage *image);
+    bool compressedImageCallback(const CompressedImage &msg, FiducialArray *out, std::nullptr_t) { return compressedImageCallback(msg, out, (Image *)nullptr); }
     bool poseEstimateCallback(const FiducialArray &msg, FiducialTransformArray *out);  // :397-538 (fiducial_msgs view)
     bool poseEstimateCallback(const FiducialArray &msg, PoseOutputs *out);             // ... everything it publishes
     bool enableDetectionsCallback(bool data, std::string *message);  // :573-588
@@ -184,7 +192,10 @@ class FiducialsNode {
     void handleLenOverrideString(const std::string &str);      // :627-660
     bool publishVertices(const Header &h, int32_t n, FiducialArray *out);  // the tail of imageCallback (:342-379)
     fid_ctx *ctx = nullptr;
+    bool compressedFrame(const CompressedImage &msg, FiducialArray *out, Image *image, CompressedImage *cimage);
+    bool publishCompressed(const Header &h, const uint8_t *raw, int32_t w, int32_t ht, int32_t n, CompressedImage *cimage);
     fid_jpeg_ctx *jctx = nullptr;  // made when the first compressed frame arrives
+    fid_jpeg_enc_ctx *ectx = nullptr;  // made when the first compressed marker image is asked for
     std::vector<uint8_t> png_frame;  // a PNG frame decoded on the host (fid_png_decode), reused from frame to frame
     std::vector<uint8_t> converted;  // (round 5: the BGR8 copy of a 16-bit / Bayer frame made before the detection; unused since ABI 7)
     bool raw_encoding = false;       // the last frame came in a raw-camera encoding (Bayer / 16 bit / UYVY): detected on the message bytes

@@ -257,6 +257,7 @@ class StagNode {
     ~StagNode()
     {
         if (jctx) fid_jpeg_destroy(jctx);
+        if (ectx) fid_jpeg_enc_destroy(ectx);
     }
 
     // StagNode::cameraInfoCallback (:219-263): the first message is kept, later ones are ignored
@@ -324,9 +325,54 @@ class StagNode {
     // with the marker outlines of fid_draw_detected_markers (cv::line LINE_8; the reference's circles and text are not drawn,
     // include/fid_abi.h) -- made on the device for a JPEG (fid_jpeg_marker_image on the gray already decoded there), on the host
     // for a PNG.  image->data is empty unless an image is published.
-    bool compressedImageCallback(const CompressedImage &msg, Outputs *out, Image *image)
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out, Image *image) { return compressedFrame(msg, out, image, nullptr); }
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out, std::nullptr_t) { return compressedFrame(msg, out, nullptr, nullptr); }
+    // ... and what stag_ros/image_markers/compressed carries (image_transport offers it for every image publisher): the same image
+    // as the JPEG file compressed_image_transport's publisher makes of it (cv::imencode(".jpg")), format "bgr8; jpeg compressed
+    // bgr8".  For a JPEG frame it is drawn AND compressed on the device (fid_jpeg_marker_jpeg): only the file crosses to the host;
+    // a PNG frame's image is drawn on the host and compressed on the device (fid_jpeg_encode).
+    bool compressedImageCallback(const CompressedImage &msg, Outputs *out, CompressedImage *image) { return compressedFrame(msg, out, nullptr, image); }
+
+    const std::vector<Marker> lastMarkers() const { return stag.getMarkerList(); }
+    const std::string &lastError() const { return last_error; }
+
+    Params params;
+    bool got_camera_info = false;
+    double K[9] = {0}, D[5] = {0};
+
+   private:
+    bool publishCompressed(const Header &h, const uint8_t *raw, int32_t w, int32_t ht, const std::vector<fid_marker> &mk, CompressedImage *cimage)
+    {
+        const int64_t room = (int64_t)maxW * maxH * 2 + 65536;  // (a file that needs more is not published)
+        if (!ectx) {
+            const fid_status rc = fid_jpeg_enc_create(dev, maxW, maxH, 1, room, &ectx);
+            if (rc != FID_OK) {
+                ectx = nullptr;
+                last_error = std::string("fid_jpeg_enc_create: ") + fid_strerror(rc);
+                return false;
+            }
+        }
+        cimage->header = h;
+        cimage->format = "bgr8; jpeg compressed bgr8";
+        cimage->data.resize((size_t)room);
+        int64_t nb = 0;
+        const fid_status rc = raw ? fid_jpeg_encode(ectx, raw, 1, w, ht, w * 3, 0, FID_ENC_BGR8, cimage->data.data(), room, &nb)
+                                  : fid_jpeg_marker_jpeg(jctx, 0, FID_ENC_MONO8, mk.data(), (int32_t)mk.size(), 0, ectx, cimage->data.data(), room, &nb);
+        if (rc != FID_OK) {
+            last_error = std::string("marker image: ") + fid_strerror(rc) + " (" + (raw ? fid_jpeg_enc_last_error(ectx) : fid_jpeg_last_error(jctx)) + ")";
+            cimage->data.clear();
+            return false;
+        }
+        cimage->data.resize((size_t)nb);
+        return true;
+    }
+
+    bool compressedFrame(const CompressedImage &msg, Outputs *out, Image *image, CompressedImage *cimage)
     {
         if (image) image->data.clear();
+        if (cimage) cimage->data.clear();
+        Image drawn;  // (a PNG frame's marker image on its way to the encoder)
+        if (cimage && !image) image = &drawn;
         out->markers.clear();
         out->bundles.clear();
         out->tf.clear();
@@ -361,6 +407,7 @@ class StagNode {
                     last_error = std::string("marker image: ") + fid_strerror(rcd);
                     image->data.clear();
                 }
+                if (cimage && !image->data.empty()) publishCompressed(msg.header, image->data.data(), pi.width, pi.height, mk, cimage);
             }
             return true;
         }
@@ -381,6 +428,10 @@ class StagNode {
         const void *gray = fid_jpeg_device_ptr(jctx, &w, &h, &stride, &fstride);
         stag.detectMarkersDevice(gray, w, h, stride, FID_ENC_MONO8);
         publishMarkers(msg.header, out);
+        if (params.show_markers && cimage) {  // drawn and compressed on the device: the raw marker image never crosses to the host
+            publishCompressed(msg.header, nullptr, w, h, markersToDraw(), cimage);
+            return true;
+        }
         if (params.show_markers && image) {
             startMarkerImage(image, msg.header, w, h);
             const std::vector<fid_marker> mk = markersToDraw();
@@ -394,14 +445,6 @@ class StagNode {
         return true;
     }
 
-    const std::vector<Marker> lastMarkers() const { return stag.getMarkerList(); }
-    const std::string &lastError() const { return last_error; }
-
-    Params params;
-    bool got_camera_info = false;
-    double K[9] = {0}, D[5] = {0};
-
-   private:
     // the markers of the last detection as the drawer takes them (corners cast to float, as the ROS glue does)
     std::vector<fid_marker> markersToDraw() const
     {
@@ -508,6 +551,7 @@ class StagNode {
     std::vector<uint8_t> gray_;
     int maxW = 0, maxH = 0, dev = 0;
     fid_jpeg_ctx *jctx = nullptr;  // made when the first compressed JPEG frame arrives
+    fid_jpeg_enc_ctx *ectx = nullptr;  // made when the first compressed marker image is asked for
     std::string last_error;
 };
 

@@ -215,6 +215,7 @@ FiducialsNode::FiducialsNode(const Params &p)
 FiducialsNode::~FiducialsNode()
 {
     if (jctx) fid_jpeg_destroy(jctx);
+    if (ectx) fid_jpeg_enc_destroy(ectx);
     fid_destroy(ctx);
 }
 
@@ -415,7 +416,49 @@ static void startMarkerImage(Image *image, const Header &h, int32_t w, int32_t h
 
 bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, FiducialArray *out, Image *image)
 {
+    return compressedFrame(msg, out, image, nullptr);
+}
+
+bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, FiducialArray *out, CompressedImage *image)
+{
+    return compressedFrame(msg, out, nullptr, image);
+}
+
+// /fiducial_images/compressed: the marker image as the JPEG file compressed_image_transport's publisher makes of it
+// (cv::imencode(".jpg")), written by the device encoder.  raw: the BGR8 marker image in host memory (a PNG frame's), or nullptr =
+// the marker image of the JPEG frame just decoded and detected, which is drawn and compressed where it lies.
+bool FiducialsNode::publishCompressed(const Header &h, const uint8_t *raw, int32_t w, int32_t ht, int32_t n, CompressedImage *cimage)
+{
+    const int64_t room = (int64_t)maxW * maxH * 2 + 65536;  // (ten times a camera frame at the plugin's quality; a file that needs more is not published)
+    if (!ectx) {
+        const fid_status rc = fid_jpeg_enc_create(dev, maxW, maxH, 1, room, &ectx);
+        if (rc != FID_OK) {
+            ectx = nullptr;
+            last_error = std::string("fid_jpeg_enc_create: ") + fid_strerror(rc);
+            return false;
+        }
+    }
+    cimage->header = h;
+    cimage->format = "bgr8; jpeg compressed bgr8";
+    cimage->data.resize((size_t)room);
+    int64_t nb = 0;
+    const fid_status rc = raw ? fid_jpeg_encode(ectx, raw, 1, w, ht, w * 3, 0, FID_ENC_BGR8, cimage->data.data(), room, &nb)
+                              : fid_jpeg_marker_jpeg(jctx, 0, FID_ENC_BGR8, markers.data(), n, 0, ectx, cimage->data.data(), room, &nb);
+    if (rc != FID_OK) {
+        last_error = std::string("overlay: ") + fid_strerror(rc) + " (" + (raw ? fid_jpeg_enc_last_error(ectx) : fid_jpeg_last_error(jctx)) + ")";
+        cimage->data.clear();
+        return false;
+    }
+    cimage->data.resize((size_t)nb);
+    return true;
+}
+
+bool FiducialsNode::compressedFrame(const CompressedImage &msg, FiducialArray *out, Image *image, CompressedImage *cimage)
+{
     if (image) image->data.clear();  // (filled only when the frame's marker image is published)
+    if (cimage) cimage->data.clear();
+    Image drawn;  // (a PNG frame's marker image on its way to the encoder)
+    if (cimage && !image) image = &drawn;
     if (enable_detections == false) return false;
     // with ~publish_images the frame is decoded to BGR8 -- what cv::imdecode hands to toCvCopy(BGR8), the image the outlines are
     // drawn on (:381-387) -- and the detector makes its gray from that; without, it is decoded straight to gray.  Both grays are
@@ -467,6 +510,7 @@ bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, Fiducial
                     image->data.clear();
                 }
             }
+            if (cimage && !image->data.empty()) publishCompressed(msg.header, image->data.data(), pi.width, pi.height, n, cimage);
         }
         return true;
     }
@@ -486,6 +530,10 @@ bool FiducialsNode::compressedImageCallback(const CompressedImage &msg, Fiducial
         return false;
     }
     publishVertices(msg.header, n, out);
+    if (want && cimage) {  // drawn and compressed on the device: the raw marker image never crosses to the host
+        publishCompressed(msg.header, nullptr, w, h, n, cimage);
+        return true;
+    }
     if (want) {  // drawn on the device where the frame lies (every detected marker, ignored ids included, as for a raw frame)
         startMarkerImage(image, msg.header, w, h);
         rc = fid_jpeg_marker_image(jctx, 0, FID_ENC_BGR8, markers.data(), n, 0, image->data.data(), (int64_t)image->data.size());

@@ -646,6 +646,67 @@ fid_status fid_jpeg_marker_image(fid_jpeg_ctx *ctx, int32_t frame, fid_encoding 
                                  uint32_t flags, uint8_t *host_bgr, int64_t host_bytes);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * JPEG encoding on the device (additions to ABI 7: entry points only).  image_transport offers <topic>/compressed for every image
+ * publisher -- the node's /fiducial_images among them (aruco_detect.cpp:662) -- and compressed_image_transport fills it with
+ * cv::imencode(".jpg", bgr, {IMWRITE_JPEG_QUALITY, q}) = libjpeg(-turbo) with its defaults on one host core.  These entry points
+ * write that file on the device, byte for byte (what PIL.Image.save(b, "JPEG", quality = q, subsampling = s) writes as well):
+ * baseline sequential DCT, 8 bit, JDCT_ISLOW, the Annex K Huffman tables, no optimised tables, no restart markers, no progressive
+ * scans; three components in one interleaved scan, a mono8 frame as one component.  Frames that live in HBM (a decoded batch, the
+ * marker image, a caller's frames) leave it as files, a tenth to a twentieth of their raw size.
+ * A fresh context has quality 80 and 4:2:0: what this project takes as compressed_image_transport's defaults for its ~jpeg_quality
+ * and the sampling cv::imencode picks (bench.py, tools/gpu_jpeg_bench.py).  That plugin's source is not part of the reference tree,
+ * so the two values are an assumption about the deployment, not a citation; fid_jpeg_enc_set changes them.
+ * A file is whole or absent: one that does not fit max_file_bytes (or the caller's room) is FID_E_CAPACITY, fid_jpeg_enc_last_error
+ * names the size it needs, and nothing of it is returned.  The worst case is 6.5 bytes a sample (derived in fid_jpeg_enc.hip); a
+ * context does not reserve it: max_file_bytes = 0 selects two bytes a pixel of the MCU-padded frame + 64 KiB + the header, the
+ * entropy-coded size a fid_jpeg_create context of the same frame size accepts.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fid_jpeg_enc_ctx fid_jpeg_enc_ctx;
+/* replaces: the jpeg_compress_struct cv::imencode sets up per call.  FID_E_INVALID_ARG: sizes below 1 or above 16384, no such device */
+fid_status fid_jpeg_enc_create(int32_t device, int32_t max_width, int32_t max_height, int32_t max_batch, int64_t max_file_bytes,
+                               fid_jpeg_enc_ctx **out);
+void fid_jpeg_enc_destroy(fid_jpeg_enc_ctx *ctx);
+const char *fid_jpeg_enc_last_error(fid_jpeg_enc_ctx *ctx);
+/* device time of the last encode call's seven launches, from events on the context's stream, in ms (diagnostic, as fid_last_stage_ms) */
+float fid_jpeg_enc_last_ms(fid_jpeg_enc_ctx *ctx);
+/* jpeg_set_quality(quality, TRUE) and the sampling factors: quality 1 .. 100; subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's
+ * numbering; ignored for mono8 frames).  FID_E_INVALID_ARG outside that, settings unchanged. */
+fid_status fid_jpeg_enc_set(fid_jpeg_enc_ctx *ctx, int32_t quality, int32_t subsampling);
+/* cv::imencode(".jpg") of nframes frames in DEVICE memory, under the contract of fid_detect_device (complete when the call is made,
+ * read until it returns) and the pointer checks of fid_to_bgr_device.  enc: FID_ENC_MONO8 (one component), FID_ENC_BGR8 or
+ * FID_ENC_RGB8.  File f is copied to host_out + f * host_file_stride, nbytes_out[f] bytes of it -- the copy is as long as the file,
+ * not as its room.  Refused: FID_E_UNSUPPORTED for another encoding; FID_E_INVALID_ARG for a NULL pointer, no frames or more than
+ * max_batch, a frame larger than the context, stride_bytes below a row, a negative frame stride, frames that are not memory of the
+ * context's device or reach past their allocation; FID_E_CAPACITY when a file needs more than max_file_bytes or host_file_stride
+ * (nbytes_out is set up to that frame, nothing is copied). */
+fid_status fid_jpeg_encode_device(fid_jpeg_enc_ctx *ctx, const void *d_frames, int32_t nframes, int32_t width, int32_t height,
+                                  int32_t stride_bytes, int64_t frame_stride_bytes, fid_encoding enc, uint8_t *host_out,
+                                  int64_t host_file_stride, int64_t *nbytes_out);
+/* the same from frames in host memory (copied to the device first) */
+fid_status fid_jpeg_encode(fid_jpeg_enc_ctx *ctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height, int32_t stride_bytes,
+                           int64_t frame_stride_bytes, fid_encoding enc, uint8_t *host_out, int64_t host_file_stride, int64_t *nbytes_out);
+/* the bytes in front of the entropy-coded data (jcmarker.c write_file_header / write_frame_header / write_scan_header): SOI, JFIF
+ * 1.01 APP0 (no units, density 1 x 1), a DQT segment per table, SOF0 (ids 1, 2, 3; tables 0, 1, 1), DHT segments DC0, AC0, DC1,
+ * AC1, SOS -- 623 bytes for three components, 328 for one.  Host code, no device.  *nbytes is set whenever the arguments are valid;
+ * FID_E_CAPACITY if cap is less (or out NULL); FID_E_INVALID_ARG for a quality outside 1 .. 100, a subsampling outside 0 .. 2,
+ * components other than 1 or 3, a side outside 1 .. 65535. */
+fid_status fid_jpeg_enc_header(int32_t quality, int32_t subsampling, int32_t width, int32_t height, int32_t components, uint8_t *out,
+                               int64_t cap, int64_t *nbytes);
+/* replaces: fid_jpeg_marker_image + cv::imencode on the host (the compressed publisher of /fiducial_images).  The marker image of
+ * frame `frame` of the last fid_jpeg_decode, as fid_jpeg_marker_image makes it, compressed by enc_ctx before it crosses the link:
+ * the raw image never reaches the host.  Refusals of fid_jpeg_marker_image, and FID_E_INVALID_ARG for an encoder context on another
+ * device or smaller than the frame, FID_E_CAPACITY when the file needs more than cap or the encoder's max_file_bytes
+ * (fid_jpeg_last_error names the size). */
+fid_status fid_jpeg_marker_jpeg(fid_jpeg_ctx *ctx, int32_t frame, fid_encoding base, const fid_marker *markers, int32_t n, uint32_t flags,
+                                fid_jpeg_enc_ctx *enc_ctx, uint8_t *out, int64_t cap, int64_t *nbytes);
+/* the quantised coefficients of frame `frame` of the last encode call: int16, natural order, DC not predicted, component after
+ * component, [blocks_h][blocks_w][64] each with the MCU-padded block counts of fid_jpeg_info -- the layout of FID_JPEG_TAP_COEFS
+ * (a dummy block is zero but for the DC of the block in front of it in its MCU), so that a file that differs can be put down to the
+ * transform or to the entropy coder.  bytes: 0 if there is no such frame. */
+int64_t fid_jpeg_enc_tap_bytes(fid_jpeg_enc_ctx *ctx, int32_t frame);
+fid_status fid_jpeg_enc_tap_read(fid_jpeg_enc_ctx *ctx, int32_t frame, void *dst, int64_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * aruco::getPredefinedDictionary(dicno) (aruco_detect.cpp:671, ~dictionary :611) from a table file the DEPLOYER has.  OpenCV's
  * tables are third-party data that ship neither with the reference nor with this repository (fiducials_amd/data/ holds the
  * codewords the reference's fixtures pin + labelled fillers); a caller that links OpenCV passes Dictionary::bytesList to
