@@ -16,7 +16,8 @@
 //   K5 k_sort_cands / k_near / k_resolve   a5  OpenCV order, corner reorder, too-close filter
 //   K6 k_identify       a6/a7 one wave per candidate: homography (LU on 64 lanes), unwarp, Otsu, bits, Hamming
 //   K7 k_filter_markers / k_subpix        a8/a9
-//   K8 k_pose           a11-a13 eight lanes per marker: planar init + Levenberg-Marquardt
+//   K8 k_pose           a11-a13 eight lanes per marker: planar init + Levenberg-Marquardt (fid_pnp.h: the solvePnP device
+//                       library of the four pose kernels)
 //
 // Wavefront = 64 everywhere.  Integer stages are bit-exact by construction; floating-point stages
 // replay the reference's operation order (this TU is built with -ffp-contract=off).
@@ -5023,323 +5024,14 @@ __global__ __launch_bounds__(64) void k_refine_contour_pts(const uint32_t *__res
 // calibration.cpp cvFindExtrinsicCameraParams2 does it: undistort (5 fixed-point iterations) -> homography
 // between the marker square and the normalised image points -> R,t -> Levenberg-Marquardt on the distorted
 // reprojection error with CvLevMarq's state machine (lambda 1e-3, x10 / /10, 20 iterations, eps FLT_EPSILON,
-// analytic Jacobians of cvProjectPoints2 / cvRodrigues2), followed by getReprojectionError /
-// calcFiducialArea / object_error of aruco_detect.cpp:203-221,179-200,493-495.
-// Eight lanes per marker: lane g owns residual g (corner g>>1, x or y); J^T J is reduced with xor-shuffles.
+// analytic Jacobians of cvProjectPoints2 / cvRodrigues2) -- all of it from fid_pnp.h, the solvePnP device library
+// that the STag and map pose kernels use too -- followed by getReprojectionError / calcFiducialArea / object_error
+// of aruco_detect.cpp:203-221,179-200,493-495.
+// Eight lanes per marker: lane g owns residual g (corner g>>1, x or y); J^T J is reduced over the group (grp_sum8).
 // What is only an initial guess or a damped linear solve is computed in closed form (square-to-quad
 // homography instead of the 9x9 DLT eigenproblem, LDL^T instead of SVD back-substitution): the converged
 // minimum is what is compared (tolerance in tests/, measured ~1e-12).
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask)
-{
-    unsigned long long u = __double_as_longlong(v);
-    unsigned lo = __shfl_xor((unsigned)u, mask, WAVE);
-    unsigned hi = __shfl_xor((unsigned)(u >> 32), mask, WAVE);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-// a double from the lane a DPP control names (two v_mov_b32 with a DPP operand: no trip through the LDS crossbar)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const unsigned long long u = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-// sum over an aligned group of eight lanes, in every lane of the group.  The same three additions with the same operands as the
-// xor-shuffle form (lane ^ 1: quad_perm [1,0,3,2]; lane ^ 2: quad_perm [2,3,0,1]; the other quad of the group: row_half_mirror
-// -- after the second step every lane of a quad holds the same value, so lane 7 - i serves as well as lane i ^ 4), without the
-// six ds_bpermute round trips: Levenberg-Marquardt reduces 28 such sums per iteration, 84 dependent LDS latencies that were
-// most of k_pose's time.
-__device__ __forceinline__ double grp_sum8(double v)
-{
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    return v;
-}
-
-struct PoseCam {
-    double K[9];
-    double D[5];
-    double fiducial_len;
-    template <class V>
-    __host__ __device__ __forceinline__ void visit(V &&v)
-    {
-        v(K); v(D); v(fiducial_len);
-    }
-};
-// CvLevMarq's damping factor exp(lambdaLg10 * log(10.)) for lambdaLg10 = -16 .. 16 as the HOST's libm gives it (glibc's exp / log,
-// what the reference runs on; generated with Python's math.exp(k * math.log(10.0)), hexadecimal literals = the exact doubles):
-// a table look-up instead of a device exp() in every Levenberg-Marquardt step -- and the reference's values, not the device
-// library's.
-__device__ __forceinline__ double lm_lambda(int lg10)
-{
-    static const double t[33] = {0x1.cd2b297d889a0p-54, 0x1.203af9ee755f8p-50, 0x1.6849b86a12b93p-47, 0x1.c25c268497664p-44, 0x1.19799812dea04p-40, 0x1.5fd7fe179648cp-37, 0x1.b7cdfd9d7bd9cp-34, 0x1.12e0be826d687p-30, 0x1.5798ee2308c2fp-27, 0x1.ad7f29abcaf44p-24, 0x1.0c6f7a0b5ed87p-20, 0x1.4f8b588e368e5p-17, 0x1.a36e2eb1c4326p-14, 0x1.0624dd2f1a9f9p-10, 0x1.47ae147ae1478p-7, 0x1.9999999999998p-4, 0x1.0000000000000p+0, 0x1.4000000000001p+3, 0x1.9000000000003p+6, 0x1.f400000000006p+9, 0x1.3880000000005p+13, 0x1.86a000000000ep+16, 0x1.e84800000000bp+19, 0x1.312d000000003p+23, 0x1.7d7840000000cp+26, 0x1.dcd6500000018p+29, 0x1.2a05f20000015p+33, 0x1.74876e800000ap+36, 0x1.d1a94a2000015p+39, 0x1.2309ce5400013p+43, 0x1.6bcc41e900008p+46, 0x1.c6bf52634002fp+49, 0x1.1c37937e08011p+53};
-    lg10 = lg10 < -16 ? -16 : (lg10 > 16 ? 16 : lg10);
-    return t[lg10 + 16];
-}
-
-// symmetric 3x3 eigen-decomposition by cyclic Jacobi, fully unrolled (static register indexing)
-__device__ __forceinline__ void jacobi3(double A[3][3], double V[3][3])
-{
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1. : 0.;
-    for (int sweep = 0; sweep < 30; sweep++) {
-        double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        double dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
-        if (off <= 1e-60 * dg || off < 1e-300) break;
-#pragma unroll
-        for (int p = 0; p < 3; p++)
-#pragma unroll
-            for (int q = p + 1; q < 3; q++) {
-                double apq = A[p][q];
-                if (fabs(apq) < 1e-300) continue;
-                double theta = (A[q][q] - A[p][p]) / (2. * apq);
-                double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-                double c = 1. / sqrt(t * t + 1.), s = t * c;
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    double akp = A[k][p], akq = A[k][q];
-                    A[k][p] = c * akp - s * akq;
-                    A[k][q] = s * akp + c * akq;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    double apk = A[p][k], aqk = A[q][k];
-                    A[p][k] = c * apk - s * aqk;
-                    A[q][k] = s * apk + c * aqk;
-                }
-#pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    double vpk = V[p][k], vqk = V[q][k];
-                    V[p][k] = c * vpk - s * vqk;
-                    V[q][k] = s * vpk + c * vqk;
-                }
-            }
-    }
-}
-
-// R <- U * Vt of its SVD  ( = R * (RtR)^(-1/2) ), as cvRodrigues2 does before reading the axis
-__device__ __forceinline__ void orthonormalize3(double R[9])
-{
-    double A[3][3], V[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) A[i][j] = R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j];
-    jacobi3(A, V);
-    double Pm[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Pm[i][j] = 0;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        double w = A[k][k];
-        double is = w > 1e-300 ? 1. / sqrt(w) : 0.;
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 3; j++) Pm[i][j] += V[k][i] * V[k][j] * is;
-    }
-    double T[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) T[i * 3 + j] = R[i * 3] * Pm[0][j] + R[i * 3 + 1] * Pm[1][j] + R[i * 3 + 2] * Pm[2][j];
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = T[i];
-}
-
-__device__ __forceinline__ void rodrigues_m2v(const double Rin[9], double r[3])
-{
-    double R[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = Rin[i];
-    orthonormalize3(R);
-    double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    double c = (R[0] + R[4] + R[8] - 1) * 0.5;
-    c = c > 1. ? 1. : c < -1. ? -1. : c;
-    double theta = acos(c);
-    if (s < 1e-5) {
-        double t;
-        if (c > 0)
-            rx = ry = rz = 0;
-        else {
-            t = (R[0] + 1) * 0.5;
-            rx = sqrt(t > 0. ? t : 0.);
-            t = (R[4] + 1) * 0.5;
-            ry = sqrt(t > 0. ? t : 0.) * (R[1] < 0 ? -1. : 1.);
-            t = (R[8] + 1) * 0.5;
-            rz = sqrt(t > 0. ? t : 0.) * (R[2] < 0 ? -1. : 1.);
-            if (fabs(rx) < fabs(ry) && fabs(rx) < fabs(rz) && (R[5] > 0) != (ry * rz > 0)) rz = -rz;
-            theta /= sqrt(rx * rx + ry * ry + rz * rz);
-            rx *= theta;
-            ry *= theta;
-            rz *= theta;
-        }
-    } else {
-        double vth = 1 / (2 * s);
-        vth *= theta;
-        rx *= vth;
-        ry *= vth;
-        rz *= vth;
-    }
-    r[0] = rx;
-    r[1] = ry;
-    r[2] = rz;
-}
-
-// cvRodrigues2 vector -> matrix with dR/dr (J[i*9+k] = dR_k / dr_i)
-__device__ __forceinline__ void rodrigues_v2m(const double r_in[3], double R[9], double J[27], bool wantJ)
-{
-    double rx = r_in[0], ry = r_in[1], rz = r_in[2];
-    double theta = sqrt(rx * rx + ry * ry + rz * rz);
-    if (theta < DBL_EPSILON) {
-#pragma unroll
-        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
-        if (wantJ) {
-#pragma unroll
-            for (int i = 0; i < 27; i++) J[i] = 0;
-            J[5] = J[15] = J[19] = -1;
-            J[7] = J[11] = J[21] = 1;
-        }
-        return;
-    }
-    double c, s;
-    sincos(theta, &s, &c);  // (one argument reduction for the pair)
-    const double c1 = 1. - c, itheta = theta ? 1. / theta : 0.;
-    rx *= itheta;
-    ry *= itheta;
-    rz *= itheta;
-    const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
-    const double r_x[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
-#pragma unroll
-    for (int k = 0; k < 9; k++) R[k] = c * ((k % 4 == 0) ? 1. : 0.) + c1 * rrt[k] + s * r_x[k];
-    if (wantJ) {
-        const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        const double drrt[27] = {rx + rx, ry, rz, ry, 0,       0,  rz, 0,  0,       0, rx, 0, rx, ry + ry,
-                                 rz,      0,  rz, 0,  0,       0,  rx, 0,  0,       ry, rx, ry, rz + rz};
-        const double d_r_x_[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            double ri = i == 0 ? rx : i == 1 ? ry : rz;
-            double a0 = -s * ri, a1 = (s - 2 * c1 * itheta) * ri, a2 = c1 * itheta;
-            double a3 = (c - s * itheta) * ri, a4 = s * itheta;
-#pragma unroll
-            for (int k = 0; k < 9; k++)
-                J[i * 9 + k] = a0 * I[k] + a1 * rrt[k] + a2 * drrt[i * 9 + k] + a3 * r_x[k] + a4 * d_r_x_[i * 9 + k];
-        }
-    }
-}
-
-// cvProjectPoints2Internal for ONE object point and ONE image coordinate (sel = 0: x, 1: y);
-// Jrow[0..2] = d/d rvec, Jrow[3..5] = d/d tvec
-__device__ __forceinline__ double project_one(const double M[3], const double param[6], const double K[9], const double k[5],
-                                               int sel, double Jrow[6], bool wantJ)
-{
-    double R[9], dRdr[27];
-    rodrigues_v2m(param, R, dRdr, wantJ);
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    const double X = M[0], Y = M[1], Z = M[2];
-    double x = R[0] * X + R[1] * Y + R[2] * Z + param[3];
-    double y = R[3] * X + R[4] * Y + R[5] * Z + param[4];
-    double z = R[6] * X + R[7] * Y + R[8] * Z + param[5];
-    z = z ? 1. / z : 1;
-    x *= z;
-    y *= z;
-    double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
-    const double icdist2 = 1.;
-    double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2;
-    double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1;
-    double out = sel == 0 ? xd * fx + cx : yd * fy + cy;
-    if (wantJ) {
-        const double dxdt[3] = {z, 0, -x * z}, dydt[3] = {0, z, -y * z};
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double dr2dt = 2 * x * dxdt[j] + 2 * y * dydt[j];
-            double dcdist_dt = k[0] * dr2dt + 2 * k[1] * r2 * dr2dt + 3 * k[4] * r4 * dr2dt;
-            double da1dt = 2 * (x * dydt[j] + y * dxdt[j]);
-            double dmxdt = (dxdt[j] * cdist * icdist2 + x * dcdist_dt * icdist2 + k[2] * da1dt + k[3] * (dr2dt + 4 * x * dxdt[j]));
-            double dmydt = (dydt[j] * cdist * icdist2 + y * dcdist_dt * icdist2 + k[2] * (dr2dt + 4 * y * dydt[j]) + k[3] * da1dt);
-            Jrow[3 + j] = sel == 0 ? fx * dmxdt : fy * dmydt;
-        }
-        const double dx0dr[3] = {X * dRdr[0] + Y * dRdr[1] + Z * dRdr[2], X * dRdr[9] + Y * dRdr[10] + Z * dRdr[11],
-                                 X * dRdr[18] + Y * dRdr[19] + Z * dRdr[20]};
-        const double dy0dr[3] = {X * dRdr[3] + Y * dRdr[4] + Z * dRdr[5], X * dRdr[12] + Y * dRdr[13] + Z * dRdr[14],
-                                 X * dRdr[21] + Y * dRdr[22] + Z * dRdr[23]};
-        const double dz0dr[3] = {X * dRdr[6] + Y * dRdr[7] + Z * dRdr[8], X * dRdr[15] + Y * dRdr[16] + Z * dRdr[17],
-                                 X * dRdr[24] + Y * dRdr[25] + Z * dRdr[26]};
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double dxdr = z * (dx0dr[j] - x * dz0dr[j]);
-            double dydr = z * (dy0dr[j] - y * dz0dr[j]);
-            double dr2dr = 2 * x * dxdr + 2 * y * dydr;
-            double dcdist_dr = (k[0] + 2 * k[1] * r2 + 3 * k[4] * r4) * dr2dr;
-            double da1dr = 2 * (x * dydr + y * dxdr);
-            double dmxdr = (dxdr * cdist * icdist2 + x * dcdist_dr * icdist2 + k[2] * da1dr + k[3] * (dr2dr + 4 * x * dxdr));
-            double dmydr = (dydr * cdist * icdist2 + y * dcdist_dr * icdist2 + k[2] * (dr2dr + 4 * y * dydr) + k[3] * da1dr);
-            Jrow[j] = sel == 0 ? fx * dmxdr : fy * dmydr;
-        }
-    }
-    return out;
-}
-
-// solve (JtJ with its diagonal scaled by 1 + lambda) x = JtErr, JtJ symmetric positive definite (packed upper
-// triangle, row-major: index of (a, b), a <= b, is a*6 - a*(a-1)/2 + (b - a)); LDL^T, unrolled
-__device__ __forceinline__ void solve6_spd(const double S[21], const double g[6], double lambda, double x[6])
-{
-    double A[6][6];
-    {
-        int idx = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-            for (int b = a; b < 6; b++) {
-                A[a][b] = S[idx];
-                A[b][a] = S[idx];
-                idx++;
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) A[i][i] *= 1. + lambda;
-    double L[6][6], Dg[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double d = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * Dg[k];
-        Dg[j] = d;
-        double id = d != 0. ? 1. / d : 0.;
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-            double v = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * Dg[k];
-            L[i][j] = v * id;
-        }
-    }
-    double yv[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double v = g[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) v -= L[i][k] * yv[k];
-        yv[i] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double v = Dg[i] != 0. ? yv[i] / Dg[i] : 0.;
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) v -= L[k][i] * x[k];
-        x[i] = v;
-    }
-}
+#include "fid_pnp.h"
 
 __device__ double dist2f_d(float x1f, float y1f, float x2f, float y2f)
 {
@@ -5374,149 +5066,44 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
         // object point of this lane: (-h, h), (h, h), (h, -h), (-h, -h)   aruco_detect.cpp:151-161
         const double M[3] = {(double)((pi == 1 || pi == 2) ? hx : -hx), (double)((pi < 2) ? hx : -hx), 0.};
         const double mobs = (double)mk.corners[g];
-        // ---- cvUndistortPoints (5 iterations) on every corner (each lane needs all four for the homography)
-        double mnx[4], mny[4];
+        // ---- the start: cvUndistortPoints on every corner (each lane needs all four), rounded to float as findHomography converts
+        // its inputs; the square-to-quad homography; R, t from its columns
+        double param[6] = {0, 0, 0, 0, 0, 0};
         {
-            const double fx = K[0], fy = K[4], ifx = 1. / fx, ify = 1. / fy, cx = K[2], cy = K[5];
+            double mnx[4], mny[4], h[9];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                double x = mk.corners[2 * i], y = mk.corners[2 * i + 1], u = x, v = y;
-                x = (x - cx) * ifx;
-                y = (y - cy) * ify;
-                const double x0 = x, y0 = y;
-                for (int j = 0; j < 5; j++) {
-                    double r2 = x * x + y * y;
-                    double icdist = (1) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
-                    if (icdist < 0) {
-                        x = (u - cx) * ifx;
-                        y = (v - cy) * ify;
-                        break;
-                    }
-                    double deltaX = 2 * kd[2] * x * y + kd[3] * (r2 + 2 * x * x);
-                    double deltaY = kd[2] * (r2 + 2 * y * y) + 2 * kd[3] * x * y;
-                    x = (x0 - deltaX) * icdist;
-                    y = (y0 - deltaY) * icdist;
-                }
-                // findHomography converts its inputs to float
+                double x, y;
+                pnp_undistort(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &x, &y);
                 mnx[i] = (double)(float)x;
                 mny[i] = (double)(float)y;
             }
-        }
-        double param[6];
-        {
-            // homography marker plane -> normalised image: unit square (0,0),(1,0),(1,1),(0,1) -> quad (Heckbert),
-            // composed with (X, Y) -> ((X + h) / 2h, (h - Y) / 2h)
-            const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
-            const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
-            const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
-            const double den = dx1 * dy2 - dy1 * dx2;
-            double h[9];
-            bool okh = den != 0.;
-            if (okh) {
-                const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
-                const double a = x1 - x0 + gg * x1, b = x3 - x0 + hh * x3, c = x0;
-                const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
-                const double hq = (double)hx;
-                const double s = 1. / (2. * hq);
-                // H = Hunit * [[s, 0, .5], [0, -s, .5], [0, 0, 1]]
-                h[0] = a * s;  h[1] = -b * s;  h[2] = 0.5 * a + 0.5 * b + c;
-                h[3] = d * s;  h[4] = -e * s;  h[5] = 0.5 * d + 0.5 * e + ff;
-                h[6] = gg * s; h[7] = -hh * s; h[8] = 0.5 * gg + 0.5 * hh + 1.;
-                okh = h[8] != 0.;
-                if (okh) {
-                    const double sc = 1. / h[8];
-#pragma unroll
-                    for (int i = 0; i < 9; i++) h[i] *= sc;
-                }
-            }
-            double R[9];
-            param[3] = param[4] = param[5] = 0.;
-            if (okh) {
-                const double h1_norm = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]);
-                const double h2_norm = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
-                const double s1 = 1. / fmax(h1_norm, DBL_EPSILON), s2 = 1. / fmax(h2_norm, DBL_EPSILON);
-                const double stt = 2. / fmax(h1_norm + h2_norm, DBL_EPSILON);
-                param[3] = h[2] * stt;
-                param[4] = h[5] * stt;
-                param[5] = h[8] * stt;
-                h[0] *= s1; h[3] *= s1; h[6] *= s1;
-                h[1] *= s2; h[4] *= s2; h[7] *= s2;
-                h[2] = h[3] * h[7] - h[6] * h[4];
-                h[5] = h[6] * h[1] - h[0] * h[7];
-                h[8] = h[0] * h[4] - h[3] * h[1];
-                double rtmp[3], dummy[27];
-                rodrigues_m2v(h, rtmp);
-                rodrigues_v2m(rtmp, R, dummy, false);
+            const double hq = (double)hx;
+            const double s = 1. / (2. * hq);
+            if (pnp_quad_homography(mnx, mny, s, s, h)) {
+                pnp_pose_from_h(h, param + 3);
             } else {
 #pragma unroll
-                for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+                for (int i = 0; i < 9; i++) h[i] = (i % 4 == 0) ? 1. : 0.;
             }
-            rodrigues_m2v(R, param);
+            rodrigues_m2v(h, param);
         }
-        // ---- CvLevMarq
-        double prevParam[6], S[21], gJ[6], Jrow[6];
-        double err = 0, prevErrNorm = 0, errNorm = 0;
-        int lambdaLg10 = -3, iters = 0, state = 1;
-        // (CvLevMarq: lambda = exp(lambdaLg10 * log(10.)): lm_lambda)
+        // ---- CvLevMarq over the 8 residuals, the sums over the marker's eight lanes
+        double S[21], gJ[6], Jrow[6], err = 0;
+        bool needJ = true;
+        LevMarq lm;
+        do {
+            err = project_one(M, param, K, kd, sel, Jrow, needJ) - mobs;
+            if (needJ) {
+                int idx = 0;
 #pragma unroll
-        for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-        for (;;) {
-            bool needJ = false, needErr = false;
-            if (state == 1) {
-                needJ = needErr = true;
-                state = 2;
-            } else if (state == 2) {
-                {
-                    int idx = 0;
+                for (int a = 0; a < 6; a++) {
 #pragma unroll
-                    for (int a = 0; a < 6; a++) {
-#pragma unroll
-                        for (int b = a; b < 6; b++) S[idx++] = grp_sum8(Jrow[a] * Jrow[b]);
-                        gJ[a] = grp_sum8(Jrow[a] * err);
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-                double xs[6];
-                solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-#pragma unroll
-                for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-                if (iters == 0) prevErrNorm = sqrt(grp_sum8(err * err));
-                needErr = true;
-                state = 3;
-            } else {
-                errNorm = sqrt(grp_sum8(err * err));
-                bool retry = false;
-                if (errNorm > prevErrNorm) {
-                    if (++lambdaLg10 <= 16) {
-                        double xs[6];
-                        solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-#pragma unroll
-                        for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-                        needErr = true;
-                        state = 3;
-                        retry = true;
-                    }
-                }
-                if (!retry) {
-                    lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
-                    double dn = 0, pn = 0;
-#pragma unroll
-                    for (int i = 0; i < 6; i++) {
-                        dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
-                        pn += prevParam[i] * prevParam[i];
-                    }
-                    double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
-                    if (++iters >= 20 || rel < FLT_EPSILON) break;
-                    prevErrNorm = errNorm;
-                    needJ = needErr = true;
-                    state = 2;
+                    for (int b = a; b < 6; b++) S[idx++] = grp_sum8(Jrow[a] * Jrow[b]);
+                    gJ[a] = grp_sum8(Jrow[a] * err);
                 }
             }
-            if (!needErr) break;
-            double pr = project_one(M, param, K, kd, sel, Jrow, needJ);
-            err = pr - mobs;
-        }
+        } while (lm.step(param, S, gJ, [&] { return grp_sum8(err * err); }, needJ));
         // ---- getReprojectionError: projections rounded to float (vector<Point2f>), error = sum |d|^2 / 4
         double prj = project_one(M, param, K, kd, sel, Jrow, false);
         double dcoord = mobs - (double)(float)prj;

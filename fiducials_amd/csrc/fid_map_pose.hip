@@ -1,7 +1,5 @@
 // fid_map_pose.hip -- one camera pose per frame from a map of fiducials (fid_abi.h).  Part of the fid_api.hip translation unit,
-// behind fid_stag.hip: the kernel shares its device functions with k_pose (fid_kernels.hip: project_one, solve6_spd, lm_lambda,
-// the Rodrigues pair) and with k_stag_bundle_pose (fid_stag_pose.hip: sb_scatter_eig, sb_plane_frame, sb_dlt_entry,
-// sb_smallest_eigvec9, sb_pose_from_h, sp_undistort, wave_sum_f64).
+// behind fid_stag.hip.  solvePnP's pieces -- the starts, the projection, CvLevMarq -- come from fid_pnp.h.
 //
 // ------------------------------------------------------------------------------------------------ K19: map pose
 // cv::aruco::estimatePoseBoard: cv::solvePnP (ITERATIVE) over the four corners of every marker of a frame that the map names.
@@ -18,8 +16,7 @@
 //       normalisation of HomographyEstimatorCallback::runKernel; each of the 45 entries of the 9 x 9 is a strided partial sum per
 //       lane and a butterfly.  Not coplanar: the closed-form pose of the used marker with the largest image area (the first of equals)
 //       composed with that marker's place in the map (OpenCV runs a 12 x 12 DLT there; the start is unpinned).
-//   (4) CvLevMarq as in k_pose: <= 20 iterations, lambda 10^k from -3, the same accept / reject and stop rule, plumb-bob distortion
-//       in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
+//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_pose), plumb-bob distortion in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
 //       per-lane partial sums in residual order followed by one xor butterfly: a fixed order, reproducible from run to run, the same
 //       value in every lane.
 // LDS: 24 KB object points + 16 KB image points (the 40 KB of 1 024 points) + 16 KB of float pairs for the DLT + 7 KB of tables.
@@ -79,8 +76,8 @@ __device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
                 const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
                 const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
                 double lxj, lyj, lxk, lyk;
-                sb_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
-                sb_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
+                pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
+                pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
                 acc += lxj * lxk + lyj * lyk;
             }
             acc = wave_sum_f64(acc);
@@ -89,17 +86,7 @@ __device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
                 s->A[k * 9 + j] = acc;
             }
         }
-    const int row = sb_smallest_eigvec9(s->A, s->V, lane);
-    double H0[9], T[9];
-    for (int i = 0; i < 9; i++) H0[i] = s->V[row * 9 + i];
-    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
-    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
-    sr_mul3(invHnorm, H0, T);
-    sr_mul3(T, Hnorm2, H0);
-    if (!(H0[8] != 0)) return false;
-    const double sc = 1. / H0[8];
-    for (int i = 0; i < 9; i++) H[i] = H0[i] * sc;
-    return true;
+    return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
 __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
@@ -165,7 +152,7 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         s.img[p][0] = u;
         s.img[p][1] = v;
         double x, y;
-        sp_undistort(K, kd, u, v, &x, &y);
+        pnp_undistort(K, kd, u, v, &x, &y);
         s.mn[p][0] = (float)x;  // (the DLT's input: findHomography converts to float)
         s.mn[p][1] = (float)y;
         if (q == 0) {  // the marker's area in the image (shoelace over its four corners)
@@ -192,14 +179,14 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         }
         for (int i = 0; i < 6; i++) m6[i] = wave_sum_f64(m6[i]);
         double MM[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
-        sb_scatter_eig(MM, W, Vt);
+        pnp_scatter_eig(MM, W, Vt);
     }
     const bool planar = W[2] / W[1] < 1e-3;
     // ---- (3) the start
     double param[6] = {0, 0, 0, 0, 0, 0};
     if (planar) {
         double Rt[9], tt[3];
-        sb_plane_frame(Vt, Mc, Rt, tt);
+        pnp_plane_frame(Vt, Mc, Rt, tt);
         for (int p = lane; p < npts; p += 64) {
             const double *src = s.obj[p];
             s.Mxy[p][0] = (float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
@@ -209,9 +196,9 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         double h[9], R[9];
         if (mp_homography_dlt(&s, npts, lane, h)) {
             double t3[3];
-            sb_pose_from_h(h, t3);
+            pnp_pose_from_h(h, t3);
             for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
-            sr_mul3(h, Rt, R);
+            pnp_mul3(h, Rt, R);
         } else {
             for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
         }
@@ -233,103 +220,19 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
                 big = bo;
             }
         }
-        const double *c0 = s.obj[4 * big], *c1 = s.obj[4 * big + 1], *c2 = s.obj[4 * big + 2], *c3 = s.obj[4 * big + 3];
-        // the marker's frame in the map: x along c0 -> c1, y along c3 -> c0, origin at its centre
-        double ex[3], ey[3], ez[3], cc[3];
-        for (int a = 0; a < 3; a++) {
-            ex[a] = c1[a] - c0[a];
-            ey[a] = c0[a] - c3[a];
-            cc[a] = 0.5 * (c0[a] + c2[a]);
-        }
-        const double wx = sqrt(ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2]), wy = sqrt(ey[0] * ey[0] + ey[1] * ey[1] + ey[2] * ey[2]);
-        for (int a = 0; a < 3; a++) ex[a] /= wx;
-        ez[0] = ex[1] * ey[2] - ex[2] * ey[1]; ez[1] = ex[2] * ey[0] - ex[0] * ey[2]; ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
-        const double wz = sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
-        for (int a = 0; a < 3; a++) ez[a] /= wz;
-        ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
-        double mnx[4], mny[4];
-        for (int i = 0; i < 4; i++) sp_undistort(K, kd, s.img[4 * big + i][0], s.img[4 * big + i][1], &mnx[i], &mny[i]);
-        // unit square -> quad, composed with (X, Y) -> ((X + wx / 2) / wx, (wy / 2 - Y) / wy): k_pose's start for a wx x wy marker
-        const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
-        const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
-        const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
-        const double den = dx1 * dy2 - dy1 * dx2;
-        double h[9], Rq[9], tq[3] = {0, 0, 0};
-        bool okh = den != 0. && wx > 0. && wy > 0. && wz > 0.;
-        if (okh) {
-            const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
-            const double a = x1 - x0 + gg * x1, bq = x3 - x0 + hh * x3, c = x0;
-            const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
-            const double scx = 1. / wx, scy = 1. / wy;
-            h[0] = a * scx;  h[1] = -bq * scy; h[2] = 0.5 * a + 0.5 * bq + c;
-            h[3] = d * scx;  h[4] = -e * scy;  h[5] = 0.5 * d + 0.5 * e + ff;
-            h[6] = gg * scx; h[7] = -hh * scy; h[8] = 0.5 * gg + 0.5 * hh + 1.;
-            okh = h[8] != 0.;
-            if (okh) {
-                const double sc = 1. / h[8];
-                for (int i = 0; i < 9; i++) h[i] *= sc;
-            }
-        }
-        if (okh) {
-            sb_pose_from_h(h, tq);
-            // map -> camera: X_cam = Rq B^T (X - centre) + tq, B = [ex ey ez]
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) Rq[3 * i + j] = h[3 * i] * ex[j] + h[3 * i + 1] * ey[j] + h[3 * i + 2] * ez[j];
-            for (int i = 0; i < 3; i++) param[3 + i] = tq[i] - (Rq[3 * i] * cc[0] + Rq[3 * i + 1] * cc[1] + Rq[3 * i + 2] * cc[2]);
-        } else {
-            for (int i = 0; i < 9; i++) Rq[i] = (i % 4 == 0) ? 1. : 0.;
-        }
-        rodrigues_m2v(Rq, param);
+        const double *c0 = s.obj[4 * big], *c2 = s.obj[4 * big + 2];
+        const double cc[3] = {0.5 * (c0[0] + c2[0]), 0.5 * (c0[1] + c2[1]), 0.5 * (c0[2] + c2[2])};
+        pnp_start_largest(c0, s.obj[4 * big + 1], s.obj[4 * big + 3], cc, s.img + 4 * big, K, kd, param);
     }
     // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l, l + 64, ... (residual r: point r / 2, coordinate r % 2)
     const int nres = 2 * npts;
-    double prevParam[6], S[21], gJ[6];
-    double errSq = 0, prevErrNorm = 0, errNorm = 0;
-    int lambdaLg10 = -3, iters = 0, state = 1;
-    for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-    for (;;) {
-        bool needJ = false, needErr = false;
-        if (state == 1) {
-            needJ = needErr = true;
-            state = 2;
-        } else if (state == 2) {
-            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-            double xs[6];
-            solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-            for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-            if (iters == 0) prevErrNorm = sqrt(errSq);
-            needErr = true;
-            state = 3;
-        } else {
-            errNorm = sqrt(errSq);
-            bool retry = false;
-            if (errNorm > prevErrNorm) {
-                if (++lambdaLg10 <= 16) {
-                    double xs[6];
-                    solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-                    for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-                    needErr = true;
-                    state = 3;
-                    retry = true;
-                }
-            }
-            if (!retry) {
-                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
-                double dn = 0, pn = 0;
-                for (int i = 0; i < 6; i++) {
-                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
-                    pn += prevParam[i] * prevParam[i];
-                }
-                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
-                if (++iters >= 20 || rel < FLT_EPSILON) break;
-                prevErrNorm = errNorm;
-                needJ = needErr = true;
-                state = 2;
-            }
-        }
-        if (!needErr) break;
+    double S[21], gJ[6], e2 = 0;
+    bool needJ = true;
+    LevMarq lm;
+    do {
         // the residuals (and, with needJ, the normal equations) at param
-        double e2 = 0, Sp[21], gp[6];
+        double Sp[21], gp[6];
+        e2 = 0;
         for (int i = 0; i < 21; i++) Sp[i] = 0.;
         for (int i = 0; i < 6; i++) gp[i] = 0.;
         for (int r = lane; r < nres; r += 64) {
@@ -348,14 +251,13 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
                 }
             }
         }
-        errSq = wave_sum_f64(e2);
         if (needJ) {
 #pragma unroll
             for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
 #pragma unroll
             for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
         }
-    }
+    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(e2); }, needJ));
     // ---- getReprojectionError over the used points: projections rounded to float (vector<Point2f>), sum |d|^2 / P
     double tot = 0;
     for (int p = lane; p < npts; p += 64) {

@@ -1,0 +1,627 @@
+// fid_pnp.h -- cv::solvePnP (SOLVEPNP_ITERATIVE) as a device library: what k_pose (fid_kernels.hip K8), k_stag_pose and
+// k_stag_bundle_pose (fid_stag_pose.hip K17, K18) and k_map_pose (fid_map_pose.hip K19) have in common.  Included once, ahead
+// of K8, in the fid_api.hip translation unit (needs WAVE and <float.h> from fid_kernels.hip's head).
+//
+//   lane-group sums      shfl_xor_f64, dpp_f64, grp_sum8, grp_sum16, wave_sum_f64
+//   the camera           PoseCam
+//   rotations            jacobi3, rodrigues_m2v, rodrigues_v2m (cvRodrigues2 with dR/dr), pnp_mul3
+//   projection           project_one (cvProjectPoints2 for one residual, plumb-bob distortion, analytic Jacobian row)
+//   cvUndistortPoints    pnp_undistort
+//   the start            pnp_quad_homography, pnp_pose_from_h (four corners, closed form); pnp_scatter_eig, pnp_plane_frame,
+//                        pnp_dlt_entry, pnp_smallest_eigvec9, pnp_dlt_finish (coplanar sets: findHomography's DLT);
+//                        pnp_start_largest (sets that are not coplanar)
+//   CvLevMarq            lm_lambda, solve6_spd, LevMarq
+//
+// A kernel gathers its points, makes the start, and runs
+//     LevMarq lm;
+//     bool needJ = true;
+//     do { residuals at param; with needJ: reduce S, gJ } while (lm.step(param, S, gJ, errSq, needJ));  (errSq: a callable, see LevMarq)
+// with its OWN reduction over its lanes -- the order of a floating-point sum is part of a kernel's result, so the reductions
+// are not shared: eight lanes (DPP), sixteen lanes, a wave with two residuals per lane, a wave with strided partial sums.
+#pragma once
+
+// LDS hand-over inside ONE wave: what a lane wrote before is what every lane reads after (named after k_stag_refine, its first user)
+#define SR_LDS_SYNC()                                          \
+    do {                                                       \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
+        __builtin_amdgcn_wave_barrier();                       \
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
+    } while (0)
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int mask)
+{
+    unsigned long long u = __double_as_longlong(v);
+    unsigned lo = __shfl_xor((unsigned)u, mask, WAVE);
+    unsigned hi = __shfl_xor((unsigned)(u >> 32), mask, WAVE);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+// a double from the lane a DPP control names (two v_mov_b32 with a DPP operand: no trip through the LDS crossbar)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v)
+{
+    const unsigned long long u = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
+    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+// sum over an aligned group of eight lanes, in every lane of the group.  The same three additions with the same operands as the
+// xor-shuffle form (lane ^ 1: quad_perm [1,0,3,2]; lane ^ 2: quad_perm [2,3,0,1]; the other quad of the group: row_half_mirror
+// -- after the second step every lane of a quad holds the same value, so lane 7 - i serves as well as lane i ^ 4), without the
+// six ds_bpermute round trips: Levenberg-Marquardt reduces 28 such sums per iteration, 84 dependent LDS latencies that were
+// most of k_pose's time.
+__device__ __forceinline__ double grp_sum8(double v)
+{
+    v += dpp_f64<0xB1>(v);
+    v += dpp_f64<0x4E>(v);
+    v += dpp_f64<0x141>(v);
+    return v;
+}
+__device__ __forceinline__ double grp_sum16(double v)
+{
+    v += shfl_xor_f64(v, 1);
+    v += shfl_xor_f64(v, 2);
+    v += shfl_xor_f64(v, 4);
+    v += shfl_xor_f64(v, 8);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+    v += shfl_xor_f64(v, 1);
+    v += shfl_xor_f64(v, 2);
+    v += shfl_xor_f64(v, 4);
+    v += shfl_xor_f64(v, 8);
+    v += shfl_xor_f64(v, 16);
+    v += shfl_xor_f64(v, 32);
+    return v;
+}
+
+struct PoseCam {
+    double K[9];
+    double D[5];
+    double fiducial_len;
+    template <class V>
+    __host__ __device__ __forceinline__ void visit(V &&v)
+    {
+        v(K); v(D); v(fiducial_len);
+    }
+};
+// CvLevMarq's damping factor exp(lambdaLg10 * log(10.)) for lambdaLg10 = -16 .. 16 as the HOST's libm gives it (glibc's exp / log,
+// what the reference runs on; generated with Python's math.exp(k * math.log(10.0)), hexadecimal literals = the exact doubles):
+// a table look-up instead of a device exp() in every Levenberg-Marquardt step -- and the reference's values, not the device
+// library's.
+__device__ __forceinline__ double lm_lambda(int lg10)
+{
+    static const double t[33] = {0x1.cd2b297d889a0p-54, 0x1.203af9ee755f8p-50, 0x1.6849b86a12b93p-47, 0x1.c25c268497664p-44, 0x1.19799812dea04p-40, 0x1.5fd7fe179648cp-37, 0x1.b7cdfd9d7bd9cp-34, 0x1.12e0be826d687p-30, 0x1.5798ee2308c2fp-27, 0x1.ad7f29abcaf44p-24, 0x1.0c6f7a0b5ed87p-20, 0x1.4f8b588e368e5p-17, 0x1.a36e2eb1c4326p-14, 0x1.0624dd2f1a9f9p-10, 0x1.47ae147ae1478p-7, 0x1.9999999999998p-4, 0x1.0000000000000p+0, 0x1.4000000000001p+3, 0x1.9000000000003p+6, 0x1.f400000000006p+9, 0x1.3880000000005p+13, 0x1.86a000000000ep+16, 0x1.e84800000000bp+19, 0x1.312d000000003p+23, 0x1.7d7840000000cp+26, 0x1.dcd6500000018p+29, 0x1.2a05f20000015p+33, 0x1.74876e800000ap+36, 0x1.d1a94a2000015p+39, 0x1.2309ce5400013p+43, 0x1.6bcc41e900008p+46, 0x1.c6bf52634002fp+49, 0x1.1c37937e08011p+53};
+    lg10 = lg10 < -16 ? -16 : (lg10 > 16 ? 16 : lg10);
+    return t[lg10 + 16];
+}
+
+// symmetric 3x3 eigen-decomposition by cyclic Jacobi, fully unrolled (static register indexing)
+__device__ __forceinline__ void jacobi3(double A[3][3], double V[3][3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) V[i][j] = i == j ? 1. : 0.;
+    for (int sweep = 0; sweep < 30; sweep++) {
+        double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
+        double dg = A[0][0] * A[0][0] + A[1][1] * A[1][1] + A[2][2] * A[2][2];
+        if (off <= 1e-60 * dg || off < 1e-300) break;
+#pragma unroll
+        for (int p = 0; p < 3; p++)
+#pragma unroll
+            for (int q = p + 1; q < 3; q++) {
+                double apq = A[p][q];
+                if (fabs(apq) < 1e-300) continue;
+                double theta = (A[q][q] - A[p][p]) / (2. * apq);
+                double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                double c = 1. / sqrt(t * t + 1.), s = t * c;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    double akp = A[k][p], akq = A[k][q];
+                    A[k][p] = c * akp - s * akq;
+                    A[k][q] = s * akp + c * akq;
+                }
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    double apk = A[p][k], aqk = A[q][k];
+                    A[p][k] = c * apk - s * aqk;
+                    A[q][k] = s * apk + c * aqk;
+                }
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    double vpk = V[p][k], vqk = V[q][k];
+                    V[p][k] = c * vpk - s * vqk;
+                    V[q][k] = s * vpk + c * vqk;
+                }
+            }
+    }
+}
+
+// R <- U * Vt of its SVD  ( = R * (RtR)^(-1/2) ), as cvRodrigues2 does before reading the axis
+__device__ __forceinline__ void orthonormalize3(double R[9])
+{
+    double A[3][3], V[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) A[i][j] = R[i] * R[j] + R[3 + i] * R[3 + j] + R[6 + i] * R[6 + j];
+    jacobi3(A, V);
+    double Pm[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Pm[i][j] = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        double w = A[k][k];
+        double is = w > 1e-300 ? 1. / sqrt(w) : 0.;
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Pm[i][j] += V[k][i] * V[k][j] * is;
+    }
+    double T[9];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) T[i * 3 + j] = R[i * 3] * Pm[0][j] + R[i * 3 + 1] * Pm[1][j] + R[i * 3 + 2] * Pm[2][j];
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = T[i];
+}
+
+__device__ __forceinline__ void rodrigues_m2v(const double Rin[9], double r[3])
+{
+    double R[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) R[i] = Rin[i];
+    orthonormalize3(R);
+    double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
+    double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
+    double c = (R[0] + R[4] + R[8] - 1) * 0.5;
+    c = c > 1. ? 1. : c < -1. ? -1. : c;
+    double theta = acos(c);
+    if (s < 1e-5) {
+        double t;
+        if (c > 0)
+            rx = ry = rz = 0;
+        else {
+            t = (R[0] + 1) * 0.5;
+            rx = sqrt(t > 0. ? t : 0.);
+            t = (R[4] + 1) * 0.5;
+            ry = sqrt(t > 0. ? t : 0.) * (R[1] < 0 ? -1. : 1.);
+            t = (R[8] + 1) * 0.5;
+            rz = sqrt(t > 0. ? t : 0.) * (R[2] < 0 ? -1. : 1.);
+            if (fabs(rx) < fabs(ry) && fabs(rx) < fabs(rz) && (R[5] > 0) != (ry * rz > 0)) rz = -rz;
+            theta /= sqrt(rx * rx + ry * ry + rz * rz);
+            rx *= theta;
+            ry *= theta;
+            rz *= theta;
+        }
+    } else {
+        double vth = 1 / (2 * s);
+        vth *= theta;
+        rx *= vth;
+        ry *= vth;
+        rz *= vth;
+    }
+    r[0] = rx;
+    r[1] = ry;
+    r[2] = rz;
+}
+
+// cvRodrigues2 vector -> matrix with dR/dr (J[i*9+k] = dR_k / dr_i)
+__device__ __forceinline__ void rodrigues_v2m(const double r_in[3], double R[9], double J[27], bool wantJ)
+{
+    double rx = r_in[0], ry = r_in[1], rz = r_in[2];
+    double theta = sqrt(rx * rx + ry * ry + rz * rz);
+    if (theta < DBL_EPSILON) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+        if (wantJ) {
+#pragma unroll
+            for (int i = 0; i < 27; i++) J[i] = 0;
+            J[5] = J[15] = J[19] = -1;
+            J[7] = J[11] = J[21] = 1;
+        }
+        return;
+    }
+    double c, s;
+    sincos(theta, &s, &c);  // (one argument reduction for the pair)
+    const double c1 = 1. - c, itheta = theta ? 1. / theta : 0.;
+    rx *= itheta;
+    ry *= itheta;
+    rz *= itheta;
+    const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};
+    const double r_x[9] = {0, -rz, ry, rz, 0, -rx, -ry, rx, 0};
+#pragma unroll
+    for (int k = 0; k < 9; k++) R[k] = c * ((k % 4 == 0) ? 1. : 0.) + c1 * rrt[k] + s * r_x[k];
+    if (wantJ) {
+        const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        const double drrt[27] = {rx + rx, ry, rz, ry, 0,       0,  rz, 0,  0,       0, rx, 0, rx, ry + ry,
+                                 rz,      0,  rz, 0,  0,       0,  rx, 0,  0,       ry, rx, ry, rz + rz};
+        const double d_r_x_[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            double ri = i == 0 ? rx : i == 1 ? ry : rz;
+            double a0 = -s * ri, a1 = (s - 2 * c1 * itheta) * ri, a2 = c1 * itheta;
+            double a3 = (c - s * itheta) * ri, a4 = s * itheta;
+#pragma unroll
+            for (int k = 0; k < 9; k++)
+                J[i * 9 + k] = a0 * I[k] + a1 * rrt[k] + a2 * drrt[i * 9 + k] + a3 * r_x[k] + a4 * d_r_x_[i * 9 + k];
+        }
+    }
+}
+
+// cvProjectPoints2Internal for ONE object point and ONE image coordinate (sel = 0: x, 1: y);
+// Jrow[0..2] = d/d rvec, Jrow[3..5] = d/d tvec
+__device__ __forceinline__ double project_one(const double M[3], const double param[6], const double K[9], const double k[5],
+                                               int sel, double Jrow[6], bool wantJ)
+{
+    double R[9], dRdr[27];
+    rodrigues_v2m(param, R, dRdr, wantJ);
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const double X = M[0], Y = M[1], Z = M[2];
+    double x = R[0] * X + R[1] * Y + R[2] * Z + param[3];
+    double y = R[3] * X + R[4] * Y + R[5] * Z + param[4];
+    double z = R[6] * X + R[7] * Y + R[8] * Z + param[5];
+    z = z ? 1. / z : 1;
+    x *= z;
+    y *= z;
+    double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+    double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+    double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+    const double icdist2 = 1.;
+    double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2;
+    double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1;
+    double out = sel == 0 ? xd * fx + cx : yd * fy + cy;
+    if (wantJ) {
+        const double dxdt[3] = {z, 0, -x * z}, dydt[3] = {0, z, -y * z};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            double dr2dt = 2 * x * dxdt[j] + 2 * y * dydt[j];
+            double dcdist_dt = k[0] * dr2dt + 2 * k[1] * r2 * dr2dt + 3 * k[4] * r4 * dr2dt;
+            double da1dt = 2 * (x * dydt[j] + y * dxdt[j]);
+            double dmxdt = (dxdt[j] * cdist * icdist2 + x * dcdist_dt * icdist2 + k[2] * da1dt + k[3] * (dr2dt + 4 * x * dxdt[j]));
+            double dmydt = (dydt[j] * cdist * icdist2 + y * dcdist_dt * icdist2 + k[2] * (dr2dt + 4 * y * dydt[j]) + k[3] * da1dt);
+            Jrow[3 + j] = sel == 0 ? fx * dmxdt : fy * dmydt;
+        }
+        const double dx0dr[3] = {X * dRdr[0] + Y * dRdr[1] + Z * dRdr[2], X * dRdr[9] + Y * dRdr[10] + Z * dRdr[11],
+                                 X * dRdr[18] + Y * dRdr[19] + Z * dRdr[20]};
+        const double dy0dr[3] = {X * dRdr[3] + Y * dRdr[4] + Z * dRdr[5], X * dRdr[12] + Y * dRdr[13] + Z * dRdr[14],
+                                 X * dRdr[21] + Y * dRdr[22] + Z * dRdr[23]};
+        const double dz0dr[3] = {X * dRdr[6] + Y * dRdr[7] + Z * dRdr[8], X * dRdr[15] + Y * dRdr[16] + Z * dRdr[17],
+                                 X * dRdr[24] + Y * dRdr[25] + Z * dRdr[26]};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            double dxdr = z * (dx0dr[j] - x * dz0dr[j]);
+            double dydr = z * (dy0dr[j] - y * dz0dr[j]);
+            double dr2dr = 2 * x * dxdr + 2 * y * dydr;
+            double dcdist_dr = (k[0] + 2 * k[1] * r2 + 3 * k[4] * r4) * dr2dr;
+            double da1dr = 2 * (x * dydr + y * dxdr);
+            double dmxdr = (dxdr * cdist * icdist2 + x * dcdist_dr * icdist2 + k[2] * da1dr + k[3] * (dr2dr + 4 * x * dxdr));
+            double dmydr = (dydr * cdist * icdist2 + y * dcdist_dr * icdist2 + k[2] * (dr2dr + 4 * y * dydr) + k[3] * da1dr);
+            Jrow[j] = sel == 0 ? fx * dmxdr : fy * dmydr;
+        }
+    }
+    return out;
+}
+
+// solve (JtJ with its diagonal scaled by 1 + lambda) x = JtErr, JtJ symmetric positive definite (packed upper
+// triangle, row-major: index of (a, b), a <= b, is a*6 - a*(a-1)/2 + (b - a)); LDL^T, unrolled
+__device__ __forceinline__ void solve6_spd(const double S[21], const double g[6], double lambda, double x[6])
+{
+    double A[6][6];
+    {
+        int idx = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) {
+                A[a][b] = S[idx];
+                A[b][a] = S[idx];
+                idx++;
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) A[i][i] *= 1. + lambda;
+    double L[6][6], Dg[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double d = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * Dg[k];
+        Dg[j] = d;
+        double id = d != 0. ? 1. / d : 0.;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * Dg[k];
+            L[i][j] = v * id;
+        }
+    }
+    double yv[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        double v = g[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) v -= L[i][k] * yv[k];
+        yv[i] = v;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {
+        double v = Dg[i] != 0. ? yv[i] / Dg[i] : 0.;
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) v -= L[k][i] * x[k];
+        x[i] = v;
+    }
+}
+
+__device__ void pnp_mul3(const double a[9], const double b[9], double d[9])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) d[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
+}
+
+__device__ void pnp_undistort(const double K[9], const double kd[5], double u, double v, double *ox, double *oy)
+{
+    const double fx = K[0], fy = K[4], ifx = 1. / fx, ify = 1. / fy, cx = K[2], cy = K[5];
+    double x = (u - cx) * ifx, y = (v - cy) * ify;
+    const double x0 = x, y0 = y;
+    for (int j = 0; j < 5; j++) {
+        const double r2 = x * x + y * y;
+        const double icdist = (1) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
+        if (icdist < 0) {
+            x = (u - cx) * ifx;
+            y = (v - cy) * ify;
+            break;
+        }
+        const double deltaX = 2 * kd[2] * x * y + kd[3] * (r2 + 2 * x * x);
+        const double deltaY = kd[2] * (r2 + 2 * y * y) + 2 * kd[3] * x * y;
+        x = (x0 - deltaX) * icdist;
+        y = (y0 - deltaY) * icdist;
+    }
+    *ox = x;
+    *oy = y;
+}
+
+// homography marker plane -> normalised image through the four corners (mnx, mny): unit square (0,0),(1,0),(1,1),(0,1) -> quad
+// (Heckbert), composed with (X, Y) -> (X scx + 1/2, 1/2 - Y scy) -- scx = scy = 1 / 2h for the square (-h, h) (h, h) (h, -h)
+// (-h, -h), 1 / wx and 1 / wy for a wx x wy rectangle about its centre -- and scaled to h[8] = 1.  False: no such homography.
+__device__ __forceinline__ bool pnp_quad_homography(const double mnx[4], const double mny[4], double scx, double scy, double h[9])
+{
+    const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
+    const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
+    const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
+    const double den = dx1 * dy2 - dy1 * dx2;
+    if (!(den != 0.)) return false;
+    const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
+    const double a = x1 - x0 + gg * x1, b = x3 - x0 + hh * x3, c = x0;
+    const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
+    // H = Hunit * [[scx, 0, .5], [0, -scy, .5], [0, 0, 1]]
+    h[0] = a * scx;  h[1] = -b * scy;  h[2] = 0.5 * a + 0.5 * b + c;
+    h[3] = d * scx;  h[4] = -e * scy;  h[5] = 0.5 * d + 0.5 * e + ff;
+    h[6] = gg * scx; h[7] = -hh * scy; h[8] = 0.5 * gg + 0.5 * hh + 1.;
+    if (!(h[8] != 0.)) return false;
+    const double sc = 1. / h[8];
+#pragma unroll
+    for (int i = 0; i < 9; i++) h[i] *= sc;
+    return true;
+}
+
+// rotation and translation from a plane -> normalised-image homography (cvFindExtrinsicCameraParams2, planar branch)
+__device__ __forceinline__ void pnp_pose_from_h(double h[9], double t3[3])
+{
+    const double h1n = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]), h2n = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
+    const double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), stt = 2. / fmax(h1n + h2n, DBL_EPSILON);
+    t3[0] = h[2] * stt; t3[1] = h[5] * stt; t3[2] = h[8] * stt;
+    h[0] *= s1; h[3] *= s1; h[6] *= s1;
+    h[1] *= s2; h[4] *= s2; h[7] *= s2;
+    h[2] = h[3] * h[7] - h[6] * h[4];
+    h[5] = h[6] * h[1] - h[0] * h[7];
+    h[8] = h[0] * h[4] - h[3] * h[1];
+    double rtmp[3], dummy[27];
+    rodrigues_m2v(h, rtmp);
+    rodrigues_v2m(rtmp, h, dummy, false);
+}
+
+// eigenvalues (descending, cv::SVD's order) and eigenvectors (the rows of Vt) of the centred scatter matrix MM (destroyed)
+__device__ __forceinline__ void pnp_scatter_eig(double MM[3][3], double W[3], double Vt[3][3])
+{
+    jacobi3(MM, Vt);
+    W[0] = MM[0][0]; W[1] = MM[1][1]; W[2] = MM[2][2];
+    // eigenvalues descending, the rows of Vt with them (cv::SVD's order)
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        int mx = i;
+#pragma unroll
+        for (int j = i + 1; j < 3; j++)
+            if (W[j] > W[mx]) mx = j;
+        if (mx != i) {
+            const double t = W[i];
+            W[i] = W[mx];
+            W[mx] = t;
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double u = Vt[i][k];
+                Vt[i][k] = Vt[mx][k];
+                Vt[mx][k] = u;
+            }
+        }
+    }
+}
+
+// the frame of a coplanar set (cvFindExtrinsicCameraParams2, planar branch): Rt turns the points into their plane (the scatter
+// matrix's eigenvectors, made right-handed; the identity when the plane is z = const already), tt = -Rt Mc
+__device__ __forceinline__ void pnp_plane_frame(const double Vt[3][3], const double Mc[3], double Rt[9], double tt[3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) Rt[3 * i + j] = Vt[i][j];
+    if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10)
+        for (int i = 0; i < 9; i++) Rt[i] = (i % 4 == 0) ? 1. : 0.;
+    const double det = Rt[0] * (Rt[4] * Rt[8] - Rt[5] * Rt[7]) - Rt[1] * (Rt[3] * Rt[8] - Rt[5] * Rt[6]) + Rt[2] * (Rt[3] * Rt[7] - Rt[4] * Rt[6]);
+    if (det < 0)
+        for (int i = 0; i < 9; i++) Rt[i] = -Rt[i];
+    for (int i = 0; i < 3; i++) tt[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
+}
+
+// the start for a set that is not coplanar: the closed-form pose of ONE marker -- the one the kernel found largest in the image
+// -- composed with that marker's place in the set's frame.  c0, c1, c3: its object corners (c2 is not needed), cc: its centre,
+// uv: its four image corners.  The marker's frame: x along c0 -> c1, y along c3 -> c0, origin at cc.
+__device__ __forceinline__ void pnp_start_largest(const double *c0, const double *c1, const double *c3, const double cc[3], const double (*uv)[2],
+                                                  const double K[9], const double kd[5], double param[6])
+{
+    double ex[3], ey[3], ez[3];
+    for (int a = 0; a < 3; a++) {
+        ex[a] = c1[a] - c0[a];
+        ey[a] = c0[a] - c3[a];
+    }
+    const double wx = sqrt(ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2]), wy = sqrt(ey[0] * ey[0] + ey[1] * ey[1] + ey[2] * ey[2]);
+    for (int a = 0; a < 3; a++) ex[a] /= wx;
+    ez[0] = ex[1] * ey[2] - ex[2] * ey[1]; ez[1] = ex[2] * ey[0] - ex[0] * ey[2]; ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
+    const double wz = sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
+    for (int a = 0; a < 3; a++) ez[a] /= wz;
+    ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
+    double mnx[4], mny[4];
+    for (int i = 0; i < 4; i++) pnp_undistort(K, kd, uv[i][0], uv[i][1], &mnx[i], &mny[i]);
+    double h[9], Rq[9], tq[3];
+    for (int i = 0; i < 3; i++) param[3 + i] = 0.;
+    if (wx > 0. && wy > 0. && wz > 0. && pnp_quad_homography(mnx, mny, 1. / wx, 1. / wy, h)) {
+        pnp_pose_from_h(h, tq);
+        // set -> camera: X_cam = Rq B^T (X - centre) + tq, B = [ex ey ez]
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) Rq[3 * i + j] = h[3 * i] * ex[j] + h[3 * i + 1] * ey[j] + h[3 * i + 2] * ez[j];
+        for (int i = 0; i < 3; i++) param[3 + i] = tq[i] - (Rq[3 * i] * cc[0] + Rq[3 * i + 1] * cc[1] + Rq[3 * i + 2] * cc[2]);
+    } else {
+        for (int i = 0; i < 9; i++) Rq[i] = (i % 4 == 0) ? 1. : 0.;
+    }
+    rodrigues_m2v(Rq, param);
+}
+
+// entry j of the two DLT rows of one correspondence: Lx = {X, Y, 1, 0, 0, 0, -x X, -x Y, -x}, Ly = {0, 0, 0, X, Y, 1, -y X, -y Y, -y}
+__device__ __forceinline__ void pnp_dlt_entry(int j, double X, double Y, double x, double y, double *lx, double *ly)
+{
+    const double b = j % 3 == 0 ? X : (j % 3 == 1 ? Y : 1.0);
+    *lx = j < 3 ? b : (j < 6 ? 0.0 : -x * b);
+    *ly = j < 3 ? 0.0 : (j < 6 ? b : -y * b);
+}
+
+// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 A (LDS, both triangles filled; destroyed), by cyclic Jacobi in
+// LDS: the rotation's angle in every lane, lane k < 9 turns its entries.  V: 81 doubles of LDS, its rows the eigenvectors.  Returns
+// the row, the same in every lane.
+__device__ int pnp_smallest_eigvec9(double *A, double *V, int lane)
+{
+    for (int e = lane; e < 81; e += 64) V[e] = (e / 9 == e % 9) ? 1. : 0.;
+    SR_LDS_SYNC();
+    for (int sweep = 0; sweep < 60; sweep++) {
+        double off = 0;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) off += A[p * 9 + q] * A[p * 9 + q];
+        if (!(off >= 1e-300)) break;
+        for (int p = 0; p < 9; p++)
+            for (int q = p + 1; q < 9; q++) {
+                const double apq = A[p * 9 + q];
+                if (fabs(apq) < 1e-300) continue;  // (wave-uniform)
+                const double app = A[p * 9 + p], aqq = A[q * 9 + q];
+                const double theta = (aqq - app) / (2. * apq);
+                const double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
+                const double c = 1. / sqrt(t * t + 1.), sn = t * c;
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double akp = A[lane * 9 + p], akq = A[lane * 9 + q];
+                    A[lane * 9 + p] = c * akp - sn * akq;
+                    A[lane * 9 + q] = sn * akp + c * akq;
+                }
+                SR_LDS_SYNC();
+                if (lane < 9) {
+                    const double apk = A[p * 9 + lane], aqk = A[q * 9 + lane];
+                    A[p * 9 + lane] = c * apk - sn * aqk;
+                    A[q * 9 + lane] = sn * apk + c * aqk;
+                    const double vpk = V[p * 9 + lane], vqk = V[q * 9 + lane];
+                    V[p * 9 + lane] = c * vpk - sn * vqk;
+                    V[q * 9 + lane] = sn * vpk + c * vqk;
+                }
+                SR_LDS_SYNC();
+            }
+    }
+    int row = 0;
+    double wmin = A[0];
+    for (int i = 1; i < 9; i++)
+        if (A[i * 9 + i] <= wmin) {
+            wmin = A[i * 9 + i];
+            row = i;
+        }
+    return row;
+}
+
+// the tail of HomographyEstimatorCallback::runKernel (fundam.cpp): LtL is in A (LDS, both triangles); the eigenvector of its
+// smallest eigenvalue, de-normalised by the two point sets' centroids (c..) and scales (s..; m: image, M: plane), scaled to
+// H[8] = 1.  The ACCUMULATION of LtL stays with the kernels on purpose: k_stag_bundle_pose sums every entry serially over the
+// points on lanes < 45, k_map_pose sums strided per-lane partials and butterflies them -- the float sums land on different bits,
+// and each kernel's bits are its result.
+__device__ __forceinline__ bool pnp_dlt_finish(double *A, double *V, int lane, double cmx, double cmy, double smx, double smy, double cMx, double cMy,
+                                               double sMx, double sMy, double H[9])
+{
+    const int row = pnp_smallest_eigvec9(A, V, lane);
+    double H0[9], T[9];
+    for (int i = 0; i < 9; i++) H0[i] = V[row * 9 + i];
+    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
+    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
+    pnp_mul3(invHnorm, H0, T);
+    pnp_mul3(T, Hnorm2, H0);
+    if (!(H0[8] != 0)) return false;
+    const double sc = 1. / H0[8];
+    for (int i = 0; i < 9; i++) H[i] = H0[i] * sc;
+    return true;
+}
+
+// CvLevMarq (calibration.cpp: cvFindExtrinsicCameraParams2's solver, TermCriteria(20, FLT_EPSILON)) for the six pose parameters,
+// restated once: its states (CALC_J: the normal equations at param are there; CHECK_ERR: the error at the moved param is there;
+// its STARTED is the caller's first evaluation, with the Jacobian), lambda = 10^lambdaLg10 from -3 kept inside [-16, 16], the retry
+// with ten times the damping while the error grows, the stop on the relative step or after 20 accepted steps.  Every lane of a
+// group runs the same machine on the same sums.
+//     step() is called after every evaluation of the residuals at param -- the first with the Jacobian -- and moves param; true: it
+//     needs the residuals at the new param, and with needJ the normal equations S = J^T J (packed upper triangle, solve6_spd's
+//     order) and gJ = J^T e as well.  errSq() reduces |e|^2 of the last residuals; it is a callable because CvLevMarq does not read
+//     the norm after every evaluation (not after an accepted step past the first), and a reduction that is not read is not made.
+//     False: converged, param is the result.
+struct LevMarq {
+    enum { CALC_J = 2, CHECK_ERR = 3 };
+    double prevParam[6], prevErrNorm = 0.;
+    int lambdaLg10 = -3, iters = 0, state = CALC_J;
+    template <class ErrSq>
+    __device__ __forceinline__ bool step(double param[6], const double S[21], const double gJ[6], ErrSq &&errSq, bool &needJ)
+    {
+        if (state == CALC_J) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
+            if (iters == 0) prevErrNorm = sqrt(errSq());
+            state = CHECK_ERR;
+        } else {
+            const double errNorm = sqrt(errSq());
+            if (!(errNorm > prevErrNorm && ++lambdaLg10 <= 16)) {  // accepted (or the damping is at its end)
+                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
+                double dn = 0, pn = 0;
+#pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
+                    pn += prevParam[i] * prevParam[i];
+                }
+                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
+                if (++iters >= 20 || rel < FLT_EPSILON) return false;
+                prevErrNorm = errNorm;
+                needJ = true;
+                state = CALC_J;
+                return true;
+            }
+        }
+        // param <- prevParam - (J^T J + lambda diag(J^T J))^-1 J^T e: the first move from prevParam, or the retry with more damping
+        double xs[6];
+        solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
+#pragma unroll
+        for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
+        needJ = false;
+        return true;
+    }
+};

@@ -2,6 +2,7 @@
 // (rows s2, s3) and, at the end, the host side + C-ABI; the stages in between are included from
 //   fid_stag_route.hip  s4      edge routing             fid_stag_lines.hip  s5, s6  validation, EDLines
 //   fid_stag_quads.hip  s7, s8  quads, decoding          fid_stag_pose.hip   s9, s10 pose refinement, marker pose
+//   (solvePnP's pieces for s10 and the bundle pose: fid_pnp.h, included by fid_kernels.hip ahead of this file)
 // Front end = what Stag::detectMarkers -> QuadDetector::detectQuads -> EDInterface::runEDPFandEDLines -> DetectEdgesByEDPF
 // (/root/reference/stag_detect/src/stag/ED/ED.cpp:144-187) runs before the edge routing:
 //   K9- k_stag_ingest        a frame in device memory (fid_stag_detect_markers_device / _batch_device) -> the context's gray

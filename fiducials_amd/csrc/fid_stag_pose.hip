@@ -217,12 +217,6 @@ __device__ bool sr_fit_from_scatter(SrM S, SrEllipse *e)
     return true;
 }
 
-__device__ void sr_mul3(const double a[9], const double b[9], double d[9])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) d[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
-}
-
 // cv::Mat::inv() of a 3 x 3 (closed form, as OpenCV's invert() does for n <= 3)
 __device__ void sr_inv3(const double S[9], double D[9])
 {
@@ -245,8 +239,8 @@ __device__ double sr_cost(const double x[9], const double Cm[9])
             H[3 * i + j] = x[i + j * 3];
             HT[3 * j + i] = x[i + j * 3];
         }
-    sr_mul3(HT, Cm, T);
-    sr_mul3(T, H, P);
+    pnp_mul3(HT, Cm, T);
+    pnp_mul3(T, H, P);
     SrEllipse e;
     sr_conic_to_ellipse(P[0], -P[1] * 2, P[4], P[2] * 2, -P[5] * 2, P[8], &e);
     double acc = 0;
@@ -276,7 +270,7 @@ __device__ __forceinline__ double sr_row_from(double v, int lane_in_row, int lan
 __device__ double sr_cost_rows(const double xa[3], const double xb[3], const double cmb[3], int lane)
 {
     const int r = lane & 15, a = r >> 2, b = r & 3;
-    // T[a][b], then the row a of T from the quad, then P[a][b]  (sr_mul3's expression: a0 b0 + a1 b1 + a2 b2)
+    // T[a][b], then the row a of T from the quad, then P[a][b]  (pnp_mul3's expression: a0 b0 + a1 b1 + a2 b2)
     const double T = xa[0] * cmb[0] + xa[1] * cmb[1] + xa[2] * cmb[2];
     const double t0 = dpp_f64<0x00>(T), t1 = dpp_f64<0x55>(T), t2 = dpp_f64<0xAA>(T);
     const double Pab = t0 * xb[0] + t1 * xb[1] + t2 * xb[2];
@@ -386,13 +380,6 @@ __device__ __forceinline__ double sr_wave_max_nonneg_f64(double v)  // v >= 0 in
 struct SrSimplex {
     double p[10][9], y[10], sum[9];
 };
-
-#define SR_LDS_SYNC()                                          \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
-    } while (0)
 
 __device__ void sr_downhill(double x[9], const double step[9], const double Cm[9], int lane, SrSimplex *S, int *evals = nullptr)
 {
@@ -809,41 +796,10 @@ struct k_stag_refine_fn {
 // ------------------------------------------------------------------------------------------------ K17: marker pose
 // StagNode::imageCallback -> Common::solvePnpSingle (stag_detect.cpp:140-165, common.hpp:34-46): cv::solvePnP (ITERATIVE) on
 // FIVE coplanar points, the marker centre (0, 0, 0) and the four corners (-h, h) (h, h) (h, -h) (-h, -h), h = float(marker_size /
-// 2).  Same scheme as the aruco pose kernel (fid_kernels.hip K8): closed-form start from the four corners, then the reference's
-// Levenberg-Marquardt (CvLevMarq: <= 20 iterations, lambda 1e-3 x 10^k, same accept / reject rule) on the reprojection error
-// of all five points with distortion; a 16-lane group per marker, lane g < 10 owns residual g.  Tolerance row (the reference
+// 2).  Same scheme as the aruco pose kernel (fid_kernels.hip K8), from the same library (fid_pnp.h): closed-form start from the
+// four corners, then the reference's Levenberg-Marquardt (LevMarq) on the reprojection error of all five points with
+// distortion; a 16-lane group per marker, lane g < 10 owns residual g, the sums by grp_sum16.  Tolerance row (the reference
 // starts from a 5-point DLT + refinement; both land on the same minimum).
-__device__ __forceinline__ double grp_sum16(double v)
-{
-    v += shfl_xor_f64(v, 1);
-    v += shfl_xor_f64(v, 2);
-    v += shfl_xor_f64(v, 4);
-    v += shfl_xor_f64(v, 8);
-    return v;
-}
-
-__device__ void sp_undistort(const double K[9], const double kd[5], double u, double v, double *ox, double *oy)
-{
-    const double fx = K[0], fy = K[4], ifx = 1. / fx, ify = 1. / fy, cx = K[2], cy = K[5];
-    double x = (u - cx) * ifx, y = (v - cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
-        if (icdist < 0) {
-            x = (u - cx) * ifx;
-            y = (v - cy) * ify;
-            break;
-        }
-        const double deltaX = 2 * kd[2] * x * y + kd[3] * (r2 + 2 * x * x);
-        const double deltaY = kd[2] * (r2 + 2 * y * y) + 2 * kd[3] * x * y;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
-    }
-    *ox = x;
-    *oy = y;
-}
-
 __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam,
                                                   double marker_size, fid_stag_pose_out *__restrict__ out)
 {
@@ -862,113 +818,36 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
         M[1] = (pi <= 2) ? hx : -hx;
     }
     const double mobs = pi == 0 ? mk.center[sel] : mk.corners[2 * (pi - 1) + sel];
-    double param[6];
+    // ---- the start: closed form through the four corners
+    double param[6] = {0, 0, 0, 0, 0, 0};
     {
-        double mnx[4], mny[4];
-        for (int i = 0; i < 4; i++) {
-            double x, y;
-            sp_undistort(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &x, &y);
-            mnx[i] = x;
-            mny[i] = y;
-        }
-        // homography marker plane -> normalised image through the four corners (unit square -> quad, composed with
-        // (X, Y) -> ((X + h) / 2h, (h - Y) / 2h)), then R, t from its columns
-        const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
-        const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
-        const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
-        const double den = dx1 * dy2 - dy1 * dx2;
-        double h[9];
-        bool okh = den != 0.;
-        if (okh) {
-            const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
-            const double a = x1 - x0 + gg * x1, b = x3 - x0 + hh * x3, c = x0;
-            const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
-            const double sc0 = 1. / (2. * hx);
-            h[0] = a * sc0;  h[1] = -b * sc0;  h[2] = 0.5 * a + 0.5 * b + c;
-            h[3] = d * sc0;  h[4] = -e * sc0;  h[5] = 0.5 * d + 0.5 * e + ff;
-            h[6] = gg * sc0; h[7] = -hh * sc0; h[8] = 0.5 * gg + 0.5 * hh + 1.;
-            okh = h[8] != 0.;
-            if (okh) {
-                const double sc = 1. / h[8];
-                for (int i = 0; i < 9; i++) h[i] *= sc;
-            }
-        }
-        double R[9];
-        param[3] = param[4] = param[5] = 0.;
-        if (okh) {
-            const double h1n = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]), h2n = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
-            const double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), stt = 2. / fmax(h1n + h2n, DBL_EPSILON);
-            param[3] = h[2] * stt; param[4] = h[5] * stt; param[5] = h[8] * stt;
-            h[0] *= s1; h[3] *= s1; h[6] *= s1;
-            h[1] *= s2; h[4] *= s2; h[7] *= s2;
-            h[2] = h[3] * h[7] - h[6] * h[4];
-            h[5] = h[6] * h[1] - h[0] * h[7];
-            h[8] = h[0] * h[4] - h[3] * h[1];
-            double rtmp[3], dummy[27];
-            rodrigues_m2v(h, rtmp);
-            rodrigues_v2m(rtmp, R, dummy, false);
+        double mnx[4], mny[4], h[9];
+        for (int i = 0; i < 4; i++) pnp_undistort(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &mnx[i], &mny[i]);
+        const double sc0 = 1. / (2. * hx);
+        if (pnp_quad_homography(mnx, mny, sc0, sc0, h)) {
+            pnp_pose_from_h(h, param + 3);
         } else {
-            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+            for (int i = 0; i < 9; i++) h[i] = (i % 4 == 0) ? 1. : 0.;
         }
-        rodrigues_m2v(R, param);
+        rodrigues_m2v(h, param);
     }
-    // ---- CvLevMarq over the 10 residuals
-    double prevParam[6], S[21], gJ[6], Jrow[6] = {0, 0, 0, 0, 0, 0};
-    double err = 0, prevErrNorm = 0, errNorm = 0;
-    int lambdaLg10 = -3, iters = 0, state = 1;
-    // (CvLevMarq: lambda = exp(lambdaLg10 * log(10.)): lm_lambda)
-    for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-    for (;;) {
-        bool needJ = false, needErr = false;
-        if (state == 1) {
-            needJ = needErr = true;
-            state = 2;
-        } else if (state == 2) {
+    // ---- CvLevMarq over the 10 residuals, the sums over the marker's sixteen lanes
+    double S[21], gJ[6], Jrow[6] = {0, 0, 0, 0, 0, 0}, err = 0;
+    bool needJ = true;
+    LevMarq lm;
+    do {
+        const double pr = project_one(M, param, K, kd, sel, Jrow, needJ);
+        err = act ? pr - mobs : 0.;
+        if (!act)
+            for (int i = 0; i < 6; i++) Jrow[i] = 0.;
+        if (needJ) {
             int idx = 0;
             for (int a = 0; a < 6; a++) {
                 for (int b = a; b < 6; b++) S[idx++] = grp_sum16(Jrow[a] * Jrow[b]);
                 gJ[a] = grp_sum16(Jrow[a] * err);
             }
-            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-            double xs[6];
-            solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-            for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-            if (iters == 0) prevErrNorm = sqrt(grp_sum16(err * err));
-            needErr = true;
-            state = 3;
-        } else {
-            errNorm = sqrt(grp_sum16(err * err));
-            bool retry = false;
-            if (errNorm > prevErrNorm) {
-                if (++lambdaLg10 <= 16) {
-                    double xs[6];
-                    solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-                    for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-                    needErr = true;
-                    state = 3;
-                    retry = true;
-                }
-            }
-            if (!retry) {
-                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
-                double dn = 0, pn = 0;
-                for (int i = 0; i < 6; i++) {
-                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
-                    pn += prevParam[i] * prevParam[i];
-                }
-                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
-                if (++iters >= 20 || rel < FLT_EPSILON) break;
-                prevErrNorm = errNorm;
-                needJ = needErr = true;
-                state = 2;
-            }
         }
-        if (!needErr) break;
-        const double pr = project_one(M, param, K, kd, sel, Jrow, needJ);
-        err = act ? pr - mobs : 0.;
-        if (!act)
-            for (int i = 0; i < 6; i++) Jrow[i] = 0.;
-    }
+    } while (lm.step(param, S, gJ, [&] { return grp_sum16(err * err); }, needJ));
     if (g == 0) {
         fid_stag_pose_out o;
         o.id = mk.id;
@@ -1003,10 +882,9 @@ struct k_stag_pose_fn {
 //       eigenproblem by cyclic Jacobi in LDS, lane k the k-th row / column of a rotation), R and t from its columns.  Not coplanar
 //       (tags on several faces): the closed-form four-corner pose of the found tag that is largest in the image, composed with that
 //       tag's place in the bundle (OpenCV runs a 12 x 12 DLT there; parity unpinned);
-//   (4) CvLevMarq as in k_stag_pose: <= 20 iterations, lambda 10^k from -3, the same accept / reject and stop rule, plumb-bob
-//       distortion in the projection and its Jacobian.  Up to 120 residuals strided over the 64 lanes; J^T J (21), J^T e (6) and
-//       the norms are per-lane partial sums and one xor-butterfly over the wave -- a fixed order: reproducible from run to run,
-//       the same value in every lane.
+//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_stag_pose), plumb-bob distortion in the projection and its Jacobian.  Up to 120
+//       residuals strided over the 64 lanes; J^T J (21), J^T e (6) and the norms are per-lane partial sums and one xor-butterfly
+//       over the wave -- a fixed order: reproducible from run to run, the same value in every lane.
 #define SB_MAX_TAGS 12  // FID_STAG_MAX_TAGS_PER_BUNDLE
 #define SB_MAX_PTS (5 * SB_MAX_TAGS)
 struct SbLds {
@@ -1014,73 +892,6 @@ struct SbLds {
     double A[81], V[81], area[SB_MAX_TAGS];
     int ids[SB_MAX_TAGS], tagof[SB_MAX_TAGS], mk[SB_MAX_TAGS];
 };
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    v += shfl_xor_f64(v, 1);
-    v += shfl_xor_f64(v, 2);
-    v += shfl_xor_f64(v, 4);
-    v += shfl_xor_f64(v, 8);
-    v += shfl_xor_f64(v, 16);
-    v += shfl_xor_f64(v, 32);
-    return v;
-}
-
-// entry j of the two DLT rows of one correspondence: Lx = {X, Y, 1, 0, 0, 0, -x X, -x Y, -x}, Ly = {0, 0, 0, X, Y, 1, -y X, -y Y, -y}
-__device__ __forceinline__ void sb_dlt_entry(int j, double X, double Y, double x, double y, double *lx, double *ly)
-{
-    const double b = j % 3 == 0 ? X : (j % 3 == 1 ? Y : 1.0);
-    *lx = j < 3 ? b : (j < 6 ? 0.0 : -x * b);
-    *ly = j < 3 ? 0.0 : (j < 6 ? b : -y * b);
-}
-
-// the eigenvector of the smallest eigenvalue of the symmetric 9 x 9 A (LDS, both triangles filled; destroyed), by cyclic Jacobi in
-// LDS: the rotation's angle in every lane, lane k < 9 turns its entries.  V: 81 doubles of LDS, its rows the eigenvectors.  Returns
-// the row, the same in every lane.
-__device__ int sb_smallest_eigvec9(double *A, double *V, int lane)
-{
-    for (int e = lane; e < 81; e += 64) V[e] = (e / 9 == e % 9) ? 1. : 0.;
-    SR_LDS_SYNC();
-    for (int sweep = 0; sweep < 60; sweep++) {
-        double off = 0;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) off += A[p * 9 + q] * A[p * 9 + q];
-        if (!(off >= 1e-300)) break;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) {
-                const double apq = A[p * 9 + q];
-                if (fabs(apq) < 1e-300) continue;  // (wave-uniform)
-                const double app = A[p * 9 + p], aqq = A[q * 9 + q];
-                const double theta = (aqq - app) / (2. * apq);
-                const double t = (theta >= 0 ? 1. : -1.) / (fabs(theta) + sqrt(theta * theta + 1.));
-                const double c = 1. / sqrt(t * t + 1.), sn = t * c;
-                SR_LDS_SYNC();
-                if (lane < 9) {
-                    const double akp = A[lane * 9 + p], akq = A[lane * 9 + q];
-                    A[lane * 9 + p] = c * akp - sn * akq;
-                    A[lane * 9 + q] = sn * akp + c * akq;
-                }
-                SR_LDS_SYNC();
-                if (lane < 9) {
-                    const double apk = A[p * 9 + lane], aqk = A[q * 9 + lane];
-                    A[p * 9 + lane] = c * apk - sn * aqk;
-                    A[q * 9 + lane] = sn * apk + c * aqk;
-                    const double vpk = V[p * 9 + lane], vqk = V[q * 9 + lane];
-                    V[p * 9 + lane] = c * vpk - sn * vqk;
-                    V[q * 9 + lane] = sn * vpk + c * vqk;
-                }
-                SR_LDS_SYNC();
-            }
-    }
-    int row = 0;
-    double wmin = A[0];
-    for (int i = 1; i < 9; i++)
-        if (A[i * 9 + i] <= wmin) {
-            wmin = A[i * 9 + i];
-            row = i;
-        }
-    return row;
-}
 
 // HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS (both already rounded to
 // float, as findHomography converts its inputs); every lane returns the same H
@@ -1115,80 +926,14 @@ __device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
             const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
             const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
             double lxj, lyj, lxk, lyk;
-            sb_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
-            sb_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
+            pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
+            pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
             acc += lxj * lxk + lyj * lyk;
         }
         s->A[j * 9 + k] = acc;
         s->A[k * 9 + j] = acc;
     }
-    const int row = sb_smallest_eigvec9(s->A, s->V, lane);
-    double H0[9], T[9];
-    for (int i = 0; i < 9; i++) H0[i] = s->V[row * 9 + i];
-    const double invHnorm[9] = {1. / smx, 0, cmx, 0, 1. / smy, cmy, 0, 0, 1};
-    const double Hnorm2[9] = {sMx, 0, -cMx * sMx, 0, sMy, -cMy * sMy, 0, 0, 1};
-    sr_mul3(invHnorm, H0, T);
-    sr_mul3(T, Hnorm2, H0);
-    if (!(H0[8] != 0)) return false;
-    const double sc = 1. / H0[8];
-    for (int i = 0; i < 9; i++) H[i] = H0[i] * sc;
-    return true;
-}
-
-// rotation and translation from a plane -> normalised-image homography (cvFindExtrinsicCameraParams2, planar branch)
-__device__ __forceinline__ void sb_pose_from_h(double h[9], double t3[3])
-{
-    const double h1n = sqrt(h[0] * h[0] + h[3] * h[3] + h[6] * h[6]), h2n = sqrt(h[1] * h[1] + h[4] * h[4] + h[7] * h[7]);
-    const double s1 = 1. / fmax(h1n, DBL_EPSILON), s2 = 1. / fmax(h2n, DBL_EPSILON), stt = 2. / fmax(h1n + h2n, DBL_EPSILON);
-    t3[0] = h[2] * stt; t3[1] = h[5] * stt; t3[2] = h[8] * stt;
-    h[0] *= s1; h[3] *= s1; h[6] *= s1;
-    h[1] *= s2; h[4] *= s2; h[7] *= s2;
-    h[2] = h[3] * h[7] - h[6] * h[4];
-    h[5] = h[6] * h[1] - h[0] * h[7];
-    h[8] = h[0] * h[4] - h[3] * h[1];
-    double rtmp[3], dummy[27];
-    rodrigues_m2v(h, rtmp);
-    rodrigues_v2m(rtmp, h, dummy, false);
-}
-
-// eigenvalues (descending, cv::SVD's order) and eigenvectors (the rows of Vt) of the centred scatter matrix MM (destroyed)
-__device__ __forceinline__ void sb_scatter_eig(double MM[3][3], double W[3], double Vt[3][3])
-{
-    jacobi3(MM, Vt);
-    W[0] = MM[0][0]; W[1] = MM[1][1]; W[2] = MM[2][2];
-    // eigenvalues descending, the rows of Vt with them (cv::SVD's order)
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        int mx = i;
-#pragma unroll
-        for (int j = i + 1; j < 3; j++)
-            if (W[j] > W[mx]) mx = j;
-        if (mx != i) {
-            const double t = W[i];
-            W[i] = W[mx];
-            W[mx] = t;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double u = Vt[i][k];
-                Vt[i][k] = Vt[mx][k];
-                Vt[mx][k] = u;
-            }
-        }
-    }
-}
-
-// the frame of a coplanar set (cvFindExtrinsicCameraParams2, planar branch): Rt turns the points into their plane (the scatter
-// matrix's eigenvectors, made right-handed; the identity when the plane is z = const already), tt = -Rt Mc
-__device__ __forceinline__ void sb_plane_frame(const double Vt[3][3], const double Mc[3], double Rt[9], double tt[3])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) Rt[3 * i + j] = Vt[i][j];
-    if (Rt[2] * Rt[2] + Rt[5] * Rt[5] < 1e-10)
-        for (int i = 0; i < 9; i++) Rt[i] = (i % 4 == 0) ? 1. : 0.;
-    const double det = Rt[0] * (Rt[4] * Rt[8] - Rt[5] * Rt[7]) - Rt[1] * (Rt[3] * Rt[8] - Rt[5] * Rt[6]) + Rt[2] * (Rt[3] * Rt[7] - Rt[4] * Rt[6]);
-    if (det < 0)
-        for (int i = 0; i < 9; i++) Rt[i] = -Rt[i];
-    for (int i = 0; i < 3; i++) tt[i] = -(Rt[i * 3] * Mc[0] + Rt[i * 3 + 1] * Mc[1] + Rt[i * 3 + 2] * Mc[2]);
+    return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
 __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
@@ -1247,7 +992,7 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         s.img[lane][0] = u;
         s.img[lane][1] = v;
         double x, y;
-        sp_undistort(K, kd, u, v, &x, &y);
+        pnp_undistort(K, kd, u, v, &x, &y);
         s.mn[lane][0] = (double)(float)x;  // (the DLT's input: findHomography converts to float)
         s.mn[lane][1] = (double)(float)y;
         if (q == 0) {  // the tag's area in the image (shoelace over its four corners)
@@ -1274,14 +1019,14 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
 #pragma unroll
                 for (int c = 0; c < 3; c++) MM[a][c] += d[a] * d[c];
         }
-        sb_scatter_eig(MM, W, Vt);
+        pnp_scatter_eig(MM, W, Vt);
     }
     const bool planar = W[2] / W[1] < 1e-3;
     // ---- (3) the start
     double param[6] = {0, 0, 0, 0, 0, 0};
     if (planar) {
         double Rt[9], tt[3];
-        sb_plane_frame(Vt, Mc, Rt, tt);
+        pnp_plane_frame(Vt, Mc, Rt, tt);
         if (lane < npts) {
             const double *src = s.obj[lane];
             s.Mxy[lane][0] = (double)(float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
@@ -1291,9 +1036,9 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         double h[9], R[9];
         if (sb_homography_dlt(&s, npts, lane, h)) {
             double t3[3];
-            sb_pose_from_h(h, t3);
+            pnp_pose_from_h(h, t3);
             for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
-            sr_mul3(h, Rt, R);
+            pnp_mul3(h, Rt, R);
         } else {
             for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
         }
@@ -1302,52 +1047,8 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         int big = 0;
         for (int p = 1; p < found; p++)
             if (s.area[p] > s.area[big]) big = p;
-        const double *c0 = s.obj[5 * big + 1], *c1 = s.obj[5 * big + 2], *c3 = s.obj[5 * big + 4], *cc = s.obj[5 * big];
-        // the tag's frame in the bundle: x along c0 -> c1, y along c3 -> c0, origin at its centre
-        double ex[3], ey[3], ez[3];
-        for (int a = 0; a < 3; a++) {
-            ex[a] = c1[a] - c0[a];
-            ey[a] = c0[a] - c3[a];
-        }
-        const double wx = sqrt(ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2]), wy = sqrt(ey[0] * ey[0] + ey[1] * ey[1] + ey[2] * ey[2]);
-        for (int a = 0; a < 3; a++) ex[a] /= wx;
-        ez[0] = ex[1] * ey[2] - ex[2] * ey[1]; ez[1] = ex[2] * ey[0] - ex[0] * ey[2]; ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
-        const double wz = sqrt(ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2]);
-        for (int a = 0; a < 3; a++) ez[a] /= wz;
-        ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
-        double mnx[4], mny[4];
-        for (int i = 0; i < 4; i++) sp_undistort(K, kd, s.img[5 * big + 1 + i][0], s.img[5 * big + 1 + i][1], &mnx[i], &mny[i]);
-        // unit square -> quad, composed with (X, Y) -> ((X + wx / 2) / wx, (wy / 2 - Y) / wy): k_stag_pose's start for a wx x wy tag
-        const double x0 = mnx[0], y0 = mny[0], x1 = mnx[1], y1 = mny[1], x2 = mnx[2], y2 = mny[2], x3 = mnx[3], y3 = mny[3];
-        const double dx1 = x1 - x2, dx2 = x3 - x2, sx = x0 - x1 + x2 - x3;
-        const double dy1 = y1 - y2, dy2 = y3 - y2, sy = y0 - y1 + y2 - y3;
-        const double den = dx1 * dy2 - dy1 * dx2;
-        double h[9], Rq[9], tq[3] = {0, 0, 0};
-        bool okh = den != 0. && wx > 0. && wy > 0. && wz > 0.;
-        if (okh) {
-            const double gg = (sx * dy2 - sy * dx2) / den, hh = (dx1 * sy - dy1 * sx) / den;
-            const double a = x1 - x0 + gg * x1, bq = x3 - x0 + hh * x3, c = x0;
-            const double d = y1 - y0 + gg * y1, e = y3 - y0 + hh * y3, ff = y0;
-            const double scx = 1. / wx, scy = 1. / wy;
-            h[0] = a * scx;  h[1] = -bq * scy; h[2] = 0.5 * a + 0.5 * bq + c;
-            h[3] = d * scx;  h[4] = -e * scy;  h[5] = 0.5 * d + 0.5 * e + ff;
-            h[6] = gg * scx; h[7] = -hh * scy; h[8] = 0.5 * gg + 0.5 * hh + 1.;
-            okh = h[8] != 0.;
-            if (okh) {
-                const double sc = 1. / h[8];
-                for (int i = 0; i < 9; i++) h[i] *= sc;
-            }
-        }
-        if (okh) {
-            sb_pose_from_h(h, tq);
-            // bundle -> camera: X_cam = Rq B^T (X - centre) + tq, B = [ex ey ez]
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) Rq[3 * i + j] = h[3 * i] * ex[j] + h[3 * i + 1] * ey[j] + h[3 * i + 2] * ez[j];
-            for (int i = 0; i < 3; i++) param[3 + i] = tq[i] - (Rq[3 * i] * cc[0] + Rq[3 * i + 1] * cc[1] + Rq[3 * i + 2] * cc[2]);
-        } else {
-            for (int i = 0; i < 9; i++) Rq[i] = (i % 4 == 0) ? 1. : 0.;
-        }
-        rodrigues_m2v(Rq, param);
+        // (a tag's points: its centre, then c0..c3)
+        pnp_start_largest(s.obj[5 * big + 1], s.obj[5 * big + 2], s.obj[5 * big + 4], s.obj[5 * big], s.img + 5 * big + 1, K, kd, param);
     }
     // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l and l + 64
     const int nres = 2 * npts;
@@ -1355,56 +1056,10 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
     const int r0 = act0 ? lane : 0, r1 = act1 ? lane + 64 : 0;
     const double M0[3] = {s.obj[r0 >> 1][0], s.obj[r0 >> 1][1], s.obj[r0 >> 1][2]}, M1[3] = {s.obj[r1 >> 1][0], s.obj[r1 >> 1][1], s.obj[r1 >> 1][2]};
     const double mobs0 = s.img[r0 >> 1][r0 & 1], mobs1 = s.img[r1 >> 1][r1 & 1];
-    double prevParam[6], S[21], gJ[6], J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0};
-    double err0 = 0, err1 = 0, prevErrNorm = 0, errNorm = 0;
-    int lambdaLg10 = -3, iters = 0, state = 1;
-    for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-    for (;;) {
-        bool needJ = false, needErr = false;
-        if (state == 1) {
-            needJ = needErr = true;
-            state = 2;
-        } else if (state == 2) {
-            int idx = 0;
-            for (int a = 0; a < 6; a++) {
-                for (int c = a; c < 6; c++) S[idx++] = wave_sum_f64(J0[a] * J0[c] + J1[a] * J1[c]);
-                gJ[a] = wave_sum_f64(J0[a] * err0 + J1[a] * err1);
-            }
-            for (int i = 0; i < 6; i++) prevParam[i] = param[i];
-            double xs[6];
-            solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-            for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-            if (iters == 0) prevErrNorm = sqrt(wave_sum_f64(err0 * err0 + err1 * err1));
-            needErr = true;
-            state = 3;
-        } else {
-            errNorm = sqrt(wave_sum_f64(err0 * err0 + err1 * err1));
-            bool retry = false;
-            if (errNorm > prevErrNorm) {
-                if (++lambdaLg10 <= 16) {
-                    double xs[6];
-                    solve6_spd(S, gJ, lm_lambda(lambdaLg10), xs);
-                    for (int i = 0; i < 6; i++) param[i] = prevParam[i] - xs[i];
-                    needErr = true;
-                    state = 3;
-                    retry = true;
-                }
-            }
-            if (!retry) {
-                lambdaLg10 = lambdaLg10 - 1 > -16 ? lambdaLg10 - 1 : -16;
-                double dn = 0, pn = 0;
-                for (int i = 0; i < 6; i++) {
-                    dn += (param[i] - prevParam[i]) * (param[i] - prevParam[i]);
-                    pn += prevParam[i] * prevParam[i];
-                }
-                const double rel = sqrt(dn) / (sqrt(pn) + DBL_EPSILON);
-                if (++iters >= 20 || rel < FLT_EPSILON) break;
-                prevErrNorm = errNorm;
-                needJ = needErr = true;
-                state = 2;
-            }
-        }
-        if (!needErr) break;
+    double S[21], gJ[6], J0[6] = {0, 0, 0, 0, 0, 0}, J1[6] = {0, 0, 0, 0, 0, 0}, err0 = 0, err1 = 0;
+    bool needJ = true;
+    LevMarq lm;
+    do {
         if (act0) {
             err0 = project_one(M0, param, K, kd, r0 & 1, J0, needJ) - mobs0;
         } else {
@@ -1417,7 +1072,14 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
             err1 = 0.;
             for (int i = 0; i < 6; i++) J1[i] = 0.;
         }
-    }
+        if (needJ) {
+            int idx = 0;
+            for (int a = 0; a < 6; a++) {
+                for (int c = a; c < 6; c++) S[idx++] = wave_sum_f64(J0[a] * J0[c] + J1[a] * J1[c]);
+                gJ[a] = wave_sum_f64(J0[a] * err0 + J1[a] * err1);
+            }
+        }
+    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(err0 * err0 + err1 * err1); }, needJ));
     if (lane == 0) {
         fid_stag_bundle_pose_out o;
         o.bundle = b;
