@@ -1592,13 +1592,28 @@ __device__ __forceinline__ unsigned win_raw(const uint32_t *s_winw, int lane4, i
     return (t3[0] & 7u) | ((t3[1] & 1u) << 3) | ((t3[1] & 4u) << 2) | ((t3[2] & 7u) << 5);
 }
 
+// A wave's registers are allocated by the kernel DESCRIPTOR's count (granule 8), not by what the code uses.  For a kernel with a
+// large static LDS footprint the compiler raises that count to the floor of the occupancy the LDS alone allows at the LARGEST
+// workgroup the kernel admits: with __launch_bounds__(128), k_seed_walk's four 34 KB workgroups of two waves are 2 waves per SIMD,
+// the descriptor said 169 registers (176 allocated) for code that used 116, and k_walk_full's said 97 for 76 -- registers the
+// waves never touch, which keep the other sub-batch's kernels off the CU.  The walkers therefore declare the size they are
+// launched with as the LOWER bound of their workgroup and a larger upper bound, chosen so that the LDS-derived floor lies below the
+// registers in use: the descriptor then says what the kernel uses (tests/test_kernel_allocations.py).  The upper bound is never
+// launched; every launch site uses the lower one.  (The register allocator follows the occupancy the bounds allow: under them
+// k_seed_walk's loop-invariant addresses of a checkpoint are recomputed there instead of held, 72 registers; the step loops are
+// the same instructions.)
+#define WALKER_WG_ATTR(nt, nt_max) __attribute__((amdgpu_flat_work_group_size(nt, nt_max)))
+
 // MODE 0: a walker follows a whole border from a probe survivor and applies the canonical-start test as it goes.
 // MODE 2: as MODE 0, but the walker stops in front of the first seed state it meets (its seed cycle has the border already).
 template <int MODE>
 // Four independent walker waves per workgroup (one per SIMD: one-wave workgroups were all placed on the same SIMD of a
 // CU, which capped a CU at one SIMD's issue rate); they share nothing but the step table.
 #define WALK_WAVES 4
-__global__ __launch_bounds__(64 * WALK_WAVES) void k_walk_full(const uint32_t *__restrict__ masks, const uint2 *__restrict__ surv,
+#ifndef WALK_WG_MAX
+#define WALK_WG_MAX 448
+#endif
+__global__ WALKER_WG_ATTR(64 * WALK_WAVES, WALK_WG_MAX) void k_walk_full(const uint32_t *__restrict__ masks, const uint2 *__restrict__ surv,
                                                    uint4 *__restrict__ contours, uint32_t *__restrict__ chunk_tab,
                                                    uint32_t *__restrict__ pool, DevSegC *__restrict__ segs, DevPend *__restrict__ pend,
                                                    DevCounts *__restrict__ counts, DevGlobal *__restrict__ G, const DevParams P)
@@ -2458,7 +2473,7 @@ __device__ __forceinline__ void build_step_lut2(uint8_t *lut, int tid, int nthre
 //   * the cycle test compares one packed state key; the segment record leaves as two 16-byte stores
 #define SW_WAVES 2
 #ifndef SW_VGPR_ATTR
-#define SW_VGPR_ATTR
+#define SW_VGPR_ATTR WALKER_WG_ATTR(64 * SW_WAVES, 512)
 #endif
 #ifndef SW_CKPT
 #define SW_CKPT 8
@@ -2466,7 +2481,7 @@ __device__ __forceinline__ void build_step_lut2(uint8_t *lut, int tid, int nthre
 #ifndef SW_RUN
 #define SW_RUN 32
 #endif
-__global__ __launch_bounds__(64 * SW_WAVES) SW_VGPR_ATTR void k_seed_walk(const uint32_t *__restrict__ masks, const uint2 *__restrict__ seedq,
+__global__ SW_VGPR_ATTR void k_seed_walk(const uint32_t *__restrict__ masks, const uint2 *__restrict__ seedq,
                                                               uint32_t *__restrict__ chunk_tab, uint32_t *__restrict__ pool,
                                                               DevSegC *__restrict__ segs, DevCounts *__restrict__ counts,
                                                               DevGlobal *__restrict__ G, const DevParams P)
@@ -2837,7 +2852,7 @@ __global__ __launch_bounds__(256) void k_seg_link2(const uint2 *__restrict__ see
 // 24 KB per workgroup crowd the CUs' LDS while another batch's k_resolve (70 KB) waits for room: the two-context rate fell from
 // 32.7 to 31.5 k frames/s with the list on, and a batch does not wait for one cycle's walk anyway.
 template <unsigned SC_HOPS>
-__global__ __launch_bounds__(64) void k_seg_cycles(const uint2 *__restrict__ seedq, const DevSegC *__restrict__ segs,
+__global__ WALKER_WG_ATTR(64, 256) void k_seg_cycles(const uint2 *__restrict__ seedq, const DevSegC *__restrict__ segs,
                                                     const DevPend *__restrict__ pend, const uint4 *__restrict__ wres,
                                                     uint4 *__restrict__ contours, uint4 *__restrict__ cinfo, uint32_t *__restrict__ cbase,
                                                     uint4 *__restrict__ recs, DevCounts *__restrict__ counts, DevGlobal *__restrict__ G,

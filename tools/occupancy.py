@@ -5,6 +5,11 @@ which while the bench runs.
 Static half (runs anywhere, no GPU): the gfx950 code object is taken out of fiducials_amd/lib/libfid_amd.so (.hip_fatbin ->
 clang-offload-bundler) and its metadata note read with llvm-readelf --notes: per kernel .vgpr_count, .agpr_count, .sgpr_count,
 .group_segment_fixed_size (static LDS), .max_flat_workgroup_size, .private_segment_fixed_size (scratch).
+The registers a wave is ALLOCATED are not the notes' .vgpr_count (what the code uses) but the kernel descriptor's: the 64-byte
+object <kernel>.kd, compute_pgm_rsrc1 bits 0..5 = granulated count, (g + 1) * 8 registers (arch + accumulation, one unified file).
+For a kernel with a large static LDS footprint the compiler raises that count to the floor of the occupancy its LDS allows, so the
+two differ (round 9: k_seed_walk used 116 and was allocated 176).  The sheet's arithmetic runs on `vgpr_alloc`, the descriptor's
+figure; `vgpr` / `agpr` stay the notes' counts, printed beside it.
 
 Dynamic half (optional, `--trace <kernel_trace.csv> [...]`): rocprofv3 --kernel-trace CSVs carry, per DISPATCH, Workgroup_Size,
 Grid_Size, LDS_Block_Size (static + dynamic, what the launch asked for) and the start / end timestamps.  From them:
@@ -39,6 +44,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
 LDS_PER_CU = 160 * 1024
 CUS = 256
+# kernels whose .max_flat_workgroup_size is an upper bound that is never launched (fid_kernels.hip, WALKER_WG_ATTR): the block their
+# launch sites use, for the rows of a sheet made without a trace
+LAUNCH_BLOCK = {"k_seed_walk": 128, "k_walk_full": 256, "k_seg_cycles": 64}
 
 
 def short(name: str) -> str:
@@ -71,6 +79,25 @@ def read_notes(co: str) -> dict:
         out[k[".name"]] = {f: int(k.get("." + f, 0)) for f in ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size",
                                                                "private_segment_fixed_size", "max_flat_workgroup_size", "vgpr_spill_count",
                                                                "sgpr_spill_count")}
+    return out
+
+
+def read_descriptors(co: str) -> dict:
+    """Per kernel the registers a wave is allocated, from compute_pgm_rsrc1 of its descriptor (<kernel>.kd, 64 bytes in .rodata:
+    compute_pgm_rsrc1 at byte 48, GRANULATED_WORKITEM_VGPR_COUNT in bits 0..5, granule 8 on gfx90a and later)."""
+    import struct
+
+    txt = subprocess.check_output([f"{LLVM}/llvm-readelf", "-S", "--symbols", "-W", co], text=True)
+    secs = {}
+    for m in re.finditer(r"^\s*\[\s*(\d+)\]\s+(\S+)\s+\S+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", txt, re.M):
+        secs[int(m.group(1))] = (int(m.group(3), 16), int(m.group(4), 16))  # index -> (address, file offset)
+    blob = open(co, "rb").read()
+    out = {}
+    for m in re.finditer(r"^\s*\d+:\s+([0-9a-f]+)\s+64\s+OBJECT\s+\S+\s+\S+\s+(\d+)\s+(\S+)\.kd\s*$", txt, re.M):
+        addr, off = secs[int(m.group(2))]
+        at = int(m.group(1), 16) - addr + off
+        rsrc1 = struct.unpack_from("<I", blob, at + 48)[0]
+        out[m.group(3)] = ((rsrc1 & 0x3f) + 1) * 8
     return out
 
 
@@ -218,6 +245,9 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         co = code_object(a.lib, td)
         notes = read_notes(co)
+        alloc = read_descriptors(co)
+        for mangled, meta in notes.items():
+            meta["vgpr_alloc"] = alloc[mangled]
         tx = os.path.join(td, "text.bin")
         subprocess.check_call([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.text", co, tx])
         text_sha = hashlib.sha256(open(tx, "rb").read()).hexdigest()
@@ -239,7 +269,7 @@ def main():
         wgs[(d["name"], d["block"], d["lds"])].append(d["wgs"])
     kernels = {}
     for name, meta in sorted(static.items()):
-        e = {"vgpr": meta.get("vgpr_count", 0), "agpr": meta.get("agpr_count", 0), "sgpr": meta.get("sgpr_count", 0),
+        e = {"vgpr_alloc": meta["vgpr_alloc"], "vgpr": meta.get("vgpr_count", 0), "agpr": meta.get("agpr_count", 0), "sgpr": meta.get("sgpr_count", 0),
              "lds_static": meta.get("group_segment_fixed_size", 0), "scratch": meta.get("private_segment_fixed_size", 0),
              "max_block": meta.get("max_flat_workgroup_size", 0)}
         if meta.get("vgpr_spill_count") or meta.get("sgpr_spill_count"):
@@ -252,7 +282,7 @@ def main():
                 dyns = sorted(d for b, d in dyn.get(base, ()) if b == block) or [0]
                 for dl in dyns:
                     total = max(lds, e["lds_static"]) + dl
-                    r = residency(e["vgpr"], e["agpr"], e["sgpr"], total, block)
+                    r = residency(e["vgpr_alloc"], 0, e["sgpr"], total, block)
                     w = sorted(wgs[(name, block, lds)])
                     r.update({"block": block, "lds_static": max(lds, e["lds_static"]), "lds_dynamic": dl, "lds_per_wg": total, "dispatches": n,
                               "wgs_per_launch_median": w[len(w) // 2], "wgs_per_launch_max": w[-1]})
@@ -261,15 +291,16 @@ def main():
                     r["rounds_to_drain"] = round(w[len(w) // 2] / max(r["wg_per_cu"] * CUS, 1), 2)
                     launches.append(r)
         else:
-            r = residency(e["vgpr"], e["agpr"], e["sgpr"], e["lds_static"], e["max_block"] or 256)
-            r.update({"block": e["max_block"] or 256, "lds_per_wg": e["lds_static"], "dispatches": 0, "note": "not in the trace: static LDS and launch bound only"})
+            blk = LAUNCH_BLOCK.get(base, e["max_block"] or 256)
+            r = residency(e["vgpr_alloc"], 0, e["sgpr"], e["lds_static"], blk)
+            r.update({"block": blk, "lds_per_wg": e["lds_static"], "dispatches": 0, "note": "not in the trace: static LDS and launch bound only"})
             launches.append(r)
         e["launches"] = launches
         kernels[name] = e
     out = {"library_sha256": hashlib.sha256(open(a.lib, "rb").read()).hexdigest(), "device_text_sha256": text_sha, "label": a.label,
-           "rules": {"vgpr": "min(8, 512 // ceil8(vgpr + agpr)) waves per SIMD", "lds": "163840 // ceil512(LDS per workgroup) workgroups per CU",
+           "rules": {"vgpr": "min(8, 512 // vgpr_alloc) waves per SIMD; vgpr_alloc = (compute_pgm_rsrc1[5:0] + 1) * 8 of <kernel>.kd", "lds": "163840 // ceil512(LDS per workgroup) workgroups per CU",
                      "waves": "32 per CU", "sgpr": "min(8, 800 // (ceil16(sgpr) + 16)) waves per SIMD",
-                     "source": "/opt/skills/guides/MI355X_MICROARCH.md: Register files; Residency and cooperative launch"},
+                     "source": "MI355X_MICROARCH.md: Register files; Residency and cooperative launch"},
            "traces": [os.path.basename(p) for p in a.trace], "kernels": kernels}
     if disp:
         # (per trace file: the STag batch and the aruco bench are different runs, and the heavier one would crowd the other out of a joint top list)
@@ -282,7 +313,7 @@ def main():
         if not k:
             return None
         l = k["launches"][0]
-        return {"vgpr": k["vgpr"], "agpr": k["agpr"], "sgpr": k["sgpr"], "lds": l.get("lds_per_wg", k["lds_static"]), "block": l["block"]}
+        return {"vgpr": k["vgpr_alloc"], "agpr": 0, "sgpr": k["sgpr"], "lds": l.get("lds_per_wg", k["lds_static"]), "block": l["block"]}
 
     thr = shape("k_threshold_stream<3,4,13,3,false>")
     if thr and thr["lds"] > 0:
