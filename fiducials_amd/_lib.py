@@ -57,6 +57,11 @@ class FidMapPoseOut(C.Structure):
                 ("cam_R", C.c_double * 9), ("cam_t", C.c_double * 3), ("image_error", C.c_double)]
 
 
+class FidCamera(C.Structure):
+    """fid_camera: the camera as a value -- model (CAM_*), the number of coefficients given, K row-major, D (zero beyond n_dist)."""
+    _fields_ = [("model", C.c_int32), ("n_dist", C.c_int32), ("K", C.c_double * 9), ("D", C.c_double * 12)]
+
+
 class FidLimits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_starts_per_frame", C.c_int32), ("max_contours_per_frame", C.c_int32),
@@ -97,6 +102,7 @@ def encoding_value(encoding: str, is_bigendian: bool = False) -> int:
     return v | ENC_BIGENDIAN if is_bigendian and 9 <= v <= 13 else v
 
 
+CAM_PLUMB_BOB, CAM_RATIONAL, CAM_EQUIDISTANT = 0, 1, 2  # fid_camera_model
 MAP_MAX_ENTRIES, MAP_MAX_USED = 4096, 256  # FID_MAP_MAX_ENTRIES, FID_MAP_MAX_USED
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
@@ -108,6 +114,9 @@ SYMBOLS = [
     "fid_stag_create", "fid_stag_destroy", "fid_stag_edge_frontend", "fid_stag_detect_edges", "fid_stag_detect_edges_validated", "fid_stag_detect_lines", "fid_stag_detect_lines_validated", "fid_stag_detect_quads", "fid_stag_host_tables", "fid_stag_load_library", "fid_stag_detect_markers_unrefined", "fid_stag_detect_markers", "fid_stag_pose_last", "fid_stag_detect_markers_batch", "fid_stag_tap_bytes", "fid_stag_tap_read", "fid_stag_queue_stats", "fid_stag_detect_markers_device", "fid_stag_detect_markers_batch_device",
     "fid_stag_tag_from_three_corners", "fid_stag_layout_load_file", "fid_stag_layout_last_error", "fid_stag_set_layout", "fid_stag_bundle_pose_last", "fid_stag_bundle_pose", "fid_stag_detect_bundles_batch", "fid_stag_detect_bundles_batch_device",
     "fid_map_load_file", "fid_map_last_error", "fid_map_entry_from_rpy", "fid_set_map", "fid_map_pose_last", "fid_map_pose",
+    "fid_camera_from_info", "fid_camera_last_error", "fid_pose_cam", "fid_pose_last_cam", "fid_map_pose_last_cam", "fid_map_pose_cam", "fid_project_points_cam",
+    "fid_stag_pose_last_cam", "fid_stag_detect_markers_batch_cam", "fid_stag_detect_markers_batch_device_cam", "fid_stag_bundle_pose_last_cam",
+    "fid_stag_bundle_pose_cam", "fid_stag_detect_bundles_batch_cam", "fid_stag_detect_bundles_batch_device_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
@@ -268,6 +277,24 @@ def load():
     L.fid_set_map.argtypes = [vp, vp, i32]
     L.fid_map_pose_last.argtypes = [vp, vp, vp, vp, i32]
     L.fid_map_pose.argtypes = [vp, vp, vp, vp, i32, vp]
+    if hasattr(L, "fid_camera_from_info"):  # (the camera as a value; FID_LIB may name a build from before it)
+        # the _cam twins: const fid_camera * in place of K[9], D[5]
+        cam = C.POINTER(FidCamera)
+        L.fid_camera_from_info.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, cam]
+        L.fid_camera_last_error.argtypes = []
+        L.fid_camera_last_error.restype = C.c_char_p
+        L.fid_pose_cam.argtypes = [vp, cam, C.POINTER(FidMarker), C.POINTER(C.c_double), i32, C.c_double, C.POINTER(FidPoseOut)]
+        L.fid_pose_last_cam.argtypes = [vp, cam, C.c_double, C.POINTER(FidPoseOut), i32]
+        L.fid_map_pose_last_cam.argtypes = [vp, cam, vp, i32]
+        L.fid_map_pose_cam.argtypes = [vp, cam, vp, i32, vp]
+        L.fid_project_points_cam.argtypes = [vp, cam, vp, vp, vp, i32, vp, vp]
+        L.fid_stag_pose_last_cam.argtypes = [vp, cam, C.c_double, vp, i32, C.POINTER(i32)]
+        L.fid_stag_detect_markers_batch_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, cam, C.c_double, vp, vp, i32, vp]
+        L.fid_stag_detect_markers_batch_device_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, cam, C.c_double, vp, vp, i32, vp]
+        L.fid_stag_bundle_pose_last_cam.argtypes = [vp, cam, vp, i32, C.POINTER(i32)]
+        L.fid_stag_bundle_pose_cam.argtypes = [vp, cam, vp, i32, vp, i32, C.POINTER(i32)]
+        L.fid_stag_detect_bundles_batch_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, cam, C.c_double, vp, vp, i32, vp, vp, vp]
+        L.fid_stag_detect_bundles_batch_device_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, cam, C.c_double, vp, vp, i32, vp, vp, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

@@ -153,7 +153,8 @@ struct fid_ctx {
     // (under the other sub-batch's tail instead of after everything, and without a second host round trip); fid_pose_last with the
     // same camera then only hands the results over.  Same kernel, same arithmetic, same results.
     bool pose_cam_valid = false, pose_done = false;
-    double pose_K[9] = {}, pose_D[5] = {}, pose_len = 0.;
+    fid_camera pose_cam = {};  // (normalised: D beyond n_dist zero; the model is part of "the same camera")
+    double pose_len = 0.;
     // the map of fiducials (fid_set_map; nothing of it exists until the first one is set): its ids ascending, per entry the four
     // object points in the map frame; a fid_map_pose_out per frame of a batch and one more for fid_map_pose, on the device and in
     // pinned host memory; room for markers handed in from the host.  map_cam_* / map_done: as pose_cam_* / pose_done, for k_map_pose
@@ -164,7 +165,7 @@ struct fid_ctx {
     fid_marker *d_map_in = nullptr;
     int map_in_cap = 0;
     bool map_cam_valid = false, map_done = false;
-    double map_K[9] = {}, map_D[5] = {};
+    fid_camera map_cam = {};
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -178,7 +179,7 @@ struct fid_ctx {
 
 // k_map_pose for F frames on a stream (fid_map_pose.hip, at the end of this translation unit)
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
-                            const double K[9], const double D[5], fid_map_pose_out *d_out);
+                            const fid_camera &camera, fid_map_pose_out *d_out);
 
 namespace {
 
@@ -858,15 +859,13 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         }
         mark(ST_SUBPIX + 1);
         if (c->pose_cam_valid) {
-            PoseCam cam;
-            for (int i = 0; i < 9; i++) cam.K[i] = c->pose_K[i];
-            for (int i = 0; i < 5; i++) cam.D[i] = c->pose_D[i];
-            cam.fiducial_len = c->pose_len;
+            const PoseCam cam = pose_cam_from(c->pose_cam, c->pose_len);
             int blocks = (Fs * P.maxMarkers + 7) / 8;  // eight lanes per marker, eight markers per wave
             blocks = blocks < 1 ? 1 : (blocks > 256 * 16 ? 256 * 16 : blocks);
             if (c->profile) (void)hipEventRecord(ev[18], st);
-            hipLaunchKernelGGL(k_pose, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers, (const int *)&counts[0].nmark,
-                               (int)(sizeof(DevCounts) / sizeof(int)), (const double *)nullptr, Fs, P.maxMarkers, cam, c->d_poses + f0 * MM);
+            POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers,
+                                                            (const int *)&counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)),
+                                                            (const double *)nullptr, Fs, P.maxMarkers, cam, c->d_poses + f0 * MM));
             if (c->profile) (void)hipEventRecord(ev[19], st);
         }
         chain_point(99);
@@ -902,7 +901,7 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     const bool map_ahead = c->map_n > 0 && c->map_cam_valid;
     if (map_ahead) {
         // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
-        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_K, c->map_D, c->d_mposes);
+        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_cam, c->d_mposes);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_cam_valid ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
@@ -1570,18 +1569,16 @@ fid_status fid_detect(fid_ctx *c, const uint8_t *img, int32_t width, int32_t hei
 }
 
 static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d_n, int n_stride_ints, const double *d_lens,
-                           int F, int per_frame, const double K[9], const double D[5], double fiducial_len, fid_pose_out *d_out)
+                           int F, int per_frame, const fid_camera &camera, double fiducial_len, fid_pose_out *d_out)
 {
-    PoseCam cam;
-    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
-    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.;
-    cam.fiducial_len = fiducial_len;
+    const PoseCam cam = pose_cam_from(camera, fiducial_len);
     int total = F * per_frame;
     int blocks = (total + 7) / 8;  // eight lanes per marker, eight markers per wave
     if (blocks < 1) blocks = 1;
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (c->profile) (void)hipEventRecord(c->ev[ST_POSE], c->stream);
-    hipLaunchKernelGGL(k_pose, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens, F, per_frame, cam, d_out);
+    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens, F,
+                                                    per_frame, cam, d_out));
     if (c->profile) (void)hipEventRecord(c->ev[ST_POSE + 1], c->stream);
     HIPCHK(c, hipGetLastError());
     return FID_OK;
@@ -1590,25 +1587,30 @@ static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d
 fid_status fid_pose_last(fid_ctx *c, const double K[9], const double D[5], double fiducial_len, fid_pose_out *out,
                          int32_t cap_per_frame)
 {
-    if (!c || !K || !out || c->last_frames <= 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_pose_last_cam(c, &cam, fiducial_len, out, cap_per_frame);
+}
+
+fid_status fid_pose_last_cam(fid_ctx *c, const fid_camera *camera, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame)
+{
+    if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
     if (c->in_flight) {
         c->last_error = "a submitted batch is in flight: fid_collect first";
         return FID_E_INVALID_ARG;
     }
     HIPCHK(c, hipSetDevice(c->device));
     const int F = c->last_frames, MM = c->P.maxMarkers;
-    double Dz[5] = {0., 0., 0., 0., 0.};
-    if (D) memcpy(Dz, D, sizeof Dz);
-    const bool same_cam = c->pose_cam_valid && !memcmp(c->pose_K, K, sizeof c->pose_K) && !memcmp(c->pose_D, Dz, sizeof Dz) && c->pose_len == fiducial_len;
+    const fid_camera cam = fid_camera_normalised(*camera);
+    const bool same_cam = c->pose_cam_valid && !memcmp(&c->pose_cam, &cam, sizeof cam) && c->pose_len == fiducial_len;
     fid_status rc = FID_OK;
     if (!(same_cam && c->pose_done)) {  // (else: the detect call already ran k_pose for this camera on these markers)
-        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, K, D, fiducial_len, c->d_poses);
+        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, cam, fiducial_len, c->d_poses);
         if (rc != FID_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_poses, c->d_poses, sizeof(fid_pose_out) * (size_t)F * MM, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->profile) (void)hipEventElapsedTime(&c->stage_ms[ST_POSE], c->ev[ST_POSE], c->ev[ST_POSE + 1]);
-        memcpy(c->pose_K, K, sizeof c->pose_K);
-        memcpy(c->pose_D, Dz, sizeof Dz);
+        c->pose_cam = cam;
         c->pose_len = fiducial_len;
         c->pose_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
         c->pose_done = c->pose_cam_valid;
@@ -1627,7 +1629,15 @@ fid_status fid_pose_last(fid_ctx *c, const double K[9], const double D[5], doubl
 fid_status fid_pose(fid_ctx *c, const double K[9], const double D[5], const fid_marker *markers, const double *len_per_marker,
                     int32_t n, double fiducial_len, fid_pose_out *out)
 {
-    if (!c || !K || (n > 0 && (!markers || !out)) || n < 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_pose_cam(c, &cam, markers, len_per_marker, n, fiducial_len, out);
+}
+
+fid_status fid_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                        double fiducial_len, fid_pose_out *out)
+{
+    if (!c || !fid_camera_usable(camera) || (n > 0 && (!markers || !out)) || n < 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
     if (n == 0) return FID_OK;
     if (len_per_marker)
         for (int i = 0; i < n; i++)
@@ -1653,10 +1663,98 @@ fid_status fid_pose(fid_ctx *c, const double K[9], const double D[5], const fid_
     int nn = n;
     HIPCHK(c, hipMemcpyAsync(c->d_pose_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // lens/nn are stack/heap temporaries
-    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, K, D, fiducial_len, d_out);
+    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, *camera, fiducial_len, d_out);
     if (rc != FID_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_pose_out) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FID_OK;
+}
+
+fid_status fid_project_points_cam(fid_ctx *c, const fid_camera *camera, const double rvec[3], const double tvec[3], const double *obj_xyz,
+                                  int32_t n, double *uv, double *jac)
+{
+    if (!c || !fid_camera_usable(camera) || !rvec || !tvec || n < 0 || (n > 0 && (!obj_xyz || !uv))) return FID_E_INVALID_ARG;
+    if (n == 0) return FID_OK;
+    if (c->in_flight) {
+        c->last_error = "a submitted batch is in flight: fid_collect first";
+        return FID_E_INVALID_ARG;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    // one block of device memory for the call: the points, the projections, the Jacobian rows (a utility, not a hot path)
+    const size_t nn = (size_t)n;
+    double *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, sizeof(double) * nn * (3 + 2 + 12)));
+    double *d_obj = d, *d_uv = d + 3 * nn, *d_jac = d + 5 * nn;
+    const PoseCam cam = pose_cam_from(*camera, 0.);
+    PosePar par;
+    for (int i = 0; i < 3; i++) {
+        par.v[i] = rvec[i];
+        par.v[3 + i] = tvec[i];
+    }
+    hipError_t e = hipMemcpyAsync(d_obj, obj_xyz, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_project_points<CAM_MODEL>, dim3((unsigned)((2 * nn + 63) / 64)), dim3(64), 0, c->stream, cam, par,
+                                                        (const double *)d_obj, (int)n, d_uv, jac ? d_jac : (double *)nullptr));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(uv, d_uv, sizeof(double) * 2 * nn, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && jac) e = hipMemcpyAsync(jac, d_jac, sizeof(double) * 12 * nn, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    HIPCHK(c, e);
+    return FID_OK;
+}
+
+// sensor_msgs/CameraInfo -> fid_camera (fid_abi.h has the table).  Host code.
+static thread_local std::string g_camera_error;
+const char *fid_camera_last_error(void) { return g_camera_error.c_str(); }
+fid_status fid_camera_from_info(const char *distortion_model, const double K[9], const double *D, int32_t n_D, fid_camera *out)
+{
+    g_camera_error.clear();
+    if (!distortion_model || !K || !out || n_D < 0 || (n_D > 0 && !D)) {
+        g_camera_error = "camera: a NULL pointer or a negative coefficient count";
+        return FID_E_INVALID_ARG;
+    }
+    const std::string m(distortion_model);
+    const std::string given = "distortion_model \"" + m + "\" with " + std::to_string(n_D) + " coefficients";
+    int model = -1, n_dist = 0;
+    if (m.empty() || m == "plumb_bob") {
+        if (n_D == 4 || n_D == 5) model = FID_CAM_PLUMB_BOB, n_dist = n_D;
+    } else if (m == "rational_polynomial") {
+        if (n_D == 8 || n_D == 12) model = FID_CAM_RATIONAL, n_dist = n_D;
+        if (n_D == 14) {
+            if (D[12] == 0. && D[13] == 0.) {
+                model = FID_CAM_RATIONAL, n_dist = 12;
+            } else if (D[12] - D[12] == 0. && D[13] - D[13] == 0.) {
+                g_camera_error = "camera: " + given + " has a tilted sensor (taux = " + std::to_string(D[12]) + ", tauy = " + std::to_string(D[13]) +
+                                 "), which is not supported";
+                return FID_E_UNSUPPORTED;
+            }
+        }
+    } else if (m == "equidistant" || m == "fisheye") {
+        if (n_D == 4) model = FID_CAM_EQUIDISTANT, n_dist = 4;
+    }
+    bool finite = true;
+    for (int i = 0; i < 9; i++) finite = finite && K[i] - K[i] == 0.;
+    for (int i = 0; i < n_D; i++) finite = finite && D[i] - D[i] == 0.;
+    if (!finite) {
+        g_camera_error = "camera: K or D holds a value that is not finite";
+        return FID_E_INVALID_ARG;
+    }
+    if (model < 0) {
+        g_camera_error = "camera: " + given + " is not supported (plumb_bob: 4 or 5, rational_polynomial: 8, 12 or 14 with zero tilt, equidistant / fisheye: 4)";
+        return FID_E_UNSUPPORTED;
+    }
+    if (K[0] == 0. || K[4] == 0.) {
+        g_camera_error = "camera: fx and fy must not be zero";
+        return FID_E_INVALID_ARG;
+    }
+    fid_camera cam;
+    cam.model = model;
+    cam.n_dist = n_dist;
+    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
+    for (int i = 0; i < 12; i++) cam.D[i] = i < n_dist ? D[i] : 0.;
+    *out = cam;
     return FID_OK;
 }
 

@@ -5055,6 +5055,23 @@ __device__ double dist2f_d(float x1f, float y1f, float x2f, float y2f)
     return sqrt(dx * dx + dy * dy);
 }
 
+// calcFiducialArea (Heron on two triangles), as k_pose's record has it
+__device__ double fiducial_area_d(const float *c)
+{
+    double a1 = dist2f_d(c[0], c[1], c[2], c[3]);
+    double b1 = dist2f_d(c[0], c[1], c[6], c[7]);
+    double c1 = dist2f_d(c[2], c[3], c[6], c[7]);
+    double a2 = dist2f_d(c[2], c[3], c[4], c[5]);
+    double b2 = dist2f_d(c[4], c[5], c[6], c[7]);
+    double c2 = c1;
+    double s1 = (a1 + b1 + c1) / 2.0, s2 = (a2 + b2 + c2) / 2.0;
+    a1 = sqrt(s1 * (s1 - a1) * (s1 - b1) * (s1 - c1));
+    a2 = sqrt(s2 * (s2 - a2) * (s2 - b2) * (s2 - c2));
+    return a1 + a2;
+}
+
+// MODEL: the camera model (fid_camera_model) -- the host launches the instantiation of the caller's camera (POSE_CAM_DISPATCH)
+template <int MODEL>
 __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame,
                                               int nmark_stride_ints, const double *__restrict__ lens, int nframes,
                                               int per_frame, PoseCam cam, fid_pose_out *__restrict__ out)
@@ -5084,12 +5101,14 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
         // ---- the start: cvUndistortPoints on every corner (each lane needs all four), rounded to float as findHomography converts
         // its inputs; the square-to-quad homography; R, t from its columns
         double param[6] = {0, 0, 0, 0, 0, 0};
+        bool posable = true;  // (group-uniform: every lane undistorts all four corners)
         {
             double mnx[4], mny[4], h[9];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 double x, y;
-                pnp_undistort(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &x, &y);
+                const bool ok = pnp_undistort<MODEL>(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &x, &y);
+                if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = posable && ok;
                 mnx[i] = (double)(float)x;
                 mny[i] = (double)(float)y;
             }
@@ -5103,12 +5122,25 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
             }
             rodrigues_m2v(h, param);
         }
+        if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+            if (!posable) {  // a corner beyond the model (fid_abi.h: "a marker that cannot be posed"): the documented record
+                if (g == 0) {
+                    fid_pose_out o;
+                    for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
+                    o.image_error = -1.;
+                    o.object_error = 0.;
+                    o.fiducial_area = fiducial_area_d(mk.corners);
+                    out[item] = o;
+                }
+                continue;
+            }
+        }
         // ---- CvLevMarq over the 8 residuals, the sums over the marker's eight lanes
         double S[21], gJ[6], Jrow[6], err = 0;
         bool needJ = true;
         LevMarq lm;
         do {
-            err = project_one(M, param, K, kd, sel, Jrow, needJ) - mobs;
+            err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - mobs;
             if (needJ) {
                 int idx = 0;
 #pragma unroll
@@ -5120,7 +5152,7 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
             }
         } while (lm.step(param, S, gJ, [&] { return grp_sum8(err * err); }, needJ));
         // ---- getReprojectionError: projections rounded to float (vector<Point2f>), error = sum |d|^2 / 4
-        double prj = project_one(M, param, K, kd, sel, Jrow, false);
+        double prj = project_one<MODEL>(M, param, K, kd, sel, Jrow, false);
         double dcoord = mobs - (double)(float)prj;
         double d2 = dcoord * dcoord;
         double pt2 = d2 + dpp_f64<0xB1>(d2);  // dx^2 + dy^2 of this corner (the lane beside this one: quad_perm [1,0,3,2])
@@ -5153,4 +5185,23 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
             out[item] = o;
         }
     }
+}
+
+// cv::projectPoints for n object points under one pose: project_one as a kernel, a thread per image coordinate.  uv: n x 2;
+// jac: NULL or n x 2 x 6 (d/d rvec, d/d tvec)
+struct PosePar {
+    double v[6];
+};
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_project_points(PoseCam cam, PosePar par, const double *__restrict__ obj, int n, double *__restrict__ uv,
+                                                        double *__restrict__ jac)
+{
+    const int r = blockIdx.x * 64 + threadIdx.x;
+    if (r >= 2 * n) return;
+    const int p = r >> 1, sel = r & 1;
+    const double M[3] = {obj[3 * p], obj[3 * p + 1], obj[3 * p + 2]};
+    double Jrow[6] = {0, 0, 0, 0, 0, 0};
+    uv[r] = project_one<MODEL>(M, par.v, cam.K, cam.D, sel, Jrow, jac != nullptr);
+    if (jac)
+        for (int i = 0; i < 6; i++) jac[(size_t)r * 6 + i] = Jrow[i];
 }

@@ -16,7 +16,7 @@
 //       normalisation of HomographyEstimatorCallback::runKernel; each of the 45 entries of the 9 x 9 is a strided partial sum per
 //       lane and a butterfly.  Not coplanar: the closed-form pose of the used marker with the largest image area (the first of equals)
 //       composed with that marker's place in the map (OpenCV runs a 12 x 12 DLT there; the start is unpinned).
-//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_pose), plumb-bob distortion in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
+//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_pose), the camera model's distortion (the template parameter) in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
 //       per-lane partial sums in residual order followed by one xor butterfly: a fixed order, reproducible from run to run, the same
 //       value in every lane.
 // LDS: 24 KB object points + 16 KB image points (the 40 KB of 1 024 points) + 16 KB of float pairs for the DLT + 7 KB of tables.
@@ -89,6 +89,7 @@ __device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
     return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
+template <int MODEL>
 __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
                                                   int per_frame, const int *__restrict__ map_ids, const double *__restrict__ map_obj, int map_n,
                                                   PoseCam cam, fid_map_pose_out *__restrict__ out)
@@ -143,6 +144,7 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
     }
     SR_LDS_SYNC();
     const int npts = 4 * found;
+    bool posable = true;
     for (int p = lane; p < npts; p += 64) {
         const int k = p >> 2, q = p & 3;
         const fid_marker *mk = mlist + s.mk[k];
@@ -152,7 +154,8 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         s.img[p][0] = u;
         s.img[p][1] = v;
         double x, y;
-        pnp_undistort(K, kd, u, v, &x, &y);
+        const bool ok = pnp_undistort<MODEL>(K, kd, u, v, &x, &y);
+        if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = posable && ok;
         s.mn[p][0] = (float)x;  // (the DLT's input: findHomography converts to float)
         s.mn[p][1] = (float)y;
         if (q == 0) {  // the marker's area in the image (shoelace over its four corners)
@@ -165,6 +168,20 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         }
     }
     SR_LDS_SYNC();
+    if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+        if (__ballot(!posable) != 0ull) {  // a corner beyond the model (fid_abi.h: "a marker that cannot be posed") voids the frame's record
+            if (lane == 0) {
+                fid_map_pose_out o;
+                o.n_markers = found;
+                o.n_over = n_over;
+                for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = o.cam_t[i] = 0.;
+                for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
+                o.image_error = -1.;
+                out[f] = o;
+            }
+            return;
+        }
+    }
     // ---- (2) planarity: the centred scatter matrix of the object points and its eigenvalues (every lane the same)
     double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
     {
@@ -222,7 +239,7 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         }
         const double *c0 = s.obj[4 * big], *c2 = s.obj[4 * big + 2];
         const double cc[3] = {0.5 * (c0[0] + c2[0]), 0.5 * (c0[1] + c2[1]), 0.5 * (c0[2] + c2[2])};
-        pnp_start_largest(c0, s.obj[4 * big + 1], s.obj[4 * big + 3], cc, s.img + 4 * big, K, kd, param);
+        pnp_start_largest<MODEL>(c0, s.obj[4 * big + 1], s.obj[4 * big + 3], cc, s.img + 4 * big, K, kd, param);
     }
     // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l, l + 64, ... (residual r: point r / 2, coordinate r % 2)
     const int nres = 2 * npts;
@@ -239,7 +256,7 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
             const int p = r >> 1, sel = r & 1;
             const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
             double Jrow[6];
-            const double err = project_one(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
+            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
             e2 += err * err;
             if (needJ) {
                 int idx = 0;
@@ -263,8 +280,8 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
     for (int p = lane; p < npts; p += 64) {
         const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
         double Jrow[6];
-        const double dx = s.img[p][0] - (double)(float)project_one(M, param, K, kd, 0, Jrow, false);
-        const double dy = s.img[p][1] - (double)(float)project_one(M, param, K, kd, 1, Jrow, false);
+        const double dx = s.img[p][0] - (double)(float)project_one<MODEL>(M, param, K, kd, 0, Jrow, false);
+        const double dy = s.img[p][1] - (double)(float)project_one<MODEL>(M, param, K, kd, 1, Jrow, false);
         const double e = sqrt(dx * dx + dy * dy);
         tot += e * e;
     }
@@ -290,14 +307,11 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
 
 // the kernel for F frames on stream st (fid_api.hip's enqueue_detect calls it for the batch it has just enqueued)
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
-                            const double K[9], const double D[5], fid_map_pose_out *d_out)
+                            const fid_camera &camera, fid_map_pose_out *d_out)
 {
-    PoseCam cam;
-    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
-    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.;
-    cam.fiducial_len = 0.;
-    hipLaunchKernelGGL(k_map_pose, dim3(F), dim3(64), 0, st, d_markers, d_n, n_stride_ints, per_frame, (const int *)c->d_map_ids,
-                       (const double *)c->d_map_obj, c->map_n, cam, d_out);
+    const PoseCam cam = pose_cam_from(camera, 0.);
+    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_map_pose<CAM_MODEL>, dim3(F), dim3(64), 0, st, d_markers, d_n, n_stride_ints, per_frame,
+                                                    (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, cam, d_out));
 }
 
 fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
@@ -361,7 +375,14 @@ fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
 
 fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], fid_map_pose_out *out, int32_t cap_frames)
 {
-    if (!c || !K || !out || c->last_frames <= 0) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_map_pose_last_cam(c, &cam, out, cap_frames);
+}
+
+fid_status fid_map_pose_last_cam(fid_ctx *c, const fid_camera *camera, fid_map_pose_out *out, int32_t cap_frames)
+{
+    if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0) return FID_E_INVALID_ARG;
     if (c->in_flight) {
         c->last_error = "a submitted batch is in flight: fid_collect first";
         return FID_E_INVALID_ARG;
@@ -376,16 +397,14 @@ fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], f
         return FID_E_CAPACITY;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    double Dz[5] = {0., 0., 0., 0., 0.};
-    if (D) memcpy(Dz, D, sizeof Dz);
-    const bool same_cam = c->map_cam_valid && !memcmp(c->map_K, K, sizeof c->map_K) && !memcmp(c->map_D, Dz, sizeof Dz);
+    const fid_camera cam = fid_camera_normalised(*camera);
+    const bool same_cam = c->map_cam_valid && !memcmp(&c->map_cam, &cam, sizeof cam);
     if (!(same_cam && c->map_done)) {  // (else: the detect call already ran k_map_pose for this camera on these markers)
-        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, K, Dz, c->d_mposes);
+        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, cam, c->d_mposes);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(c->map_K, K, sizeof c->map_K);
-        memcpy(c->map_D, Dz, sizeof Dz);
+        c->map_cam = cam;
         c->map_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
         c->map_done = c->map_cam_valid;
     }
@@ -395,7 +414,14 @@ fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], f
 
 fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const fid_marker *markers, int32_t n, fid_map_pose_out *out)
 {
-    if (!c || !K || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_map_pose_cam(c, &cam, markers, n, out);
+}
+
+fid_status fid_map_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out)
+{
+    if (!c || !fid_camera_usable(camera) || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
     if (c->in_flight) {
         c->last_error = "a submitted batch is in flight: fid_collect first";
         return FID_E_INVALID_ARG;
@@ -419,7 +445,7 @@ fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const 
     if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (nn is a stack temporary)
-    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, K, D, d_out);
+    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, d_out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -3,10 +3,11 @@
 // of K8, in the fid_api.hip translation unit (needs WAVE and <float.h> from fid_kernels.hip's head).
 //
 //   lane-group sums      shfl_xor_f64, dpp_f64, grp_sum8, grp_sum16, wave_sum_f64
-//   the camera           PoseCam
+//   the camera           PoseCam, pose_cam_from (fid_camera -> PoseCam), POSE_CAM_DISPATCH (the host picks the instantiation)
 //   rotations            jacobi3, rodrigues_m2v, rodrigues_v2m (cvRodrigues2 with dR/dr), pnp_mul3
-//   projection           project_one (cvProjectPoints2 for one residual, plumb-bob distortion, analytic Jacobian row)
-//   cvUndistortPoints    pnp_undistort
+//   projection           project_one<MODEL> (cvProjectPoints2 for one residual with its analytic Jacobian row: plumb-bob, rational
+//                        with thin prism, or the cv::fisheye equidistant model)
+//   cvUndistortPoints    pnp_undistort<MODEL> (false: the equidistant model has no pinhole point for this pixel)
 //   the start            pnp_quad_homography, pnp_pose_from_h (four corners, closed form); pnp_scatter_eig, pnp_plane_frame,
 //                        pnp_dlt_entry, pnp_smallest_eigvec9, pnp_dlt_finish (coplanar sets: findHomography's DLT);
 //                        pnp_start_largest (sets that are not coplanar)
@@ -18,6 +19,11 @@
 //     do { residuals at param; with needJ: reduce S, gJ } while (lm.step(param, S, gJ, errSq, needJ));  (errSq: a callable, see LevMarq)
 // with its OWN reduction over its lanes -- the order of a floating-point sum is part of a kernel's result, so the reductions
 // are not shared: eight lanes (DPP), sixteen lanes, a wave with two residuals per lane, a wave with strided partial sums.
+//
+// The camera model (fid_camera_model, fid_abi.h) is a TEMPLATE parameter of project_one, pnp_undistort, pnp_start_largest and of the
+// four kernels: nothing inside the Levenberg-Marquardt loop asks for it at run time.  The FID_CAM_PLUMB_BOB instantiation is the code
+// as it was before the models came (the same expressions in the same order); FID_CAM_RATIONAL adds OpenCV 4.2's terms so that with
+// k4..k6 and s1..s4 zero every intermediate value equals the plumb-bob one (x * 1.0, + 0.0).
 #pragma once
 
 // LDS hand-over inside ONE wave: what a lane wrote before is what every lane reads after (named after k_stag_refine, its first user)
@@ -77,14 +83,67 @@ __device__ __forceinline__ double wave_sum_f64(double v)
 
 struct PoseCam {
     double K[9];
-    double D[5];
+    double D[12];  // plumb-bob: k1 k2 p1 p2 k3; rational: + k4 k5 k6 s1 s2 s3 s4; equidistant: k1..k4 -- zero beyond what the model has
     double fiducial_len;
+    int model;  // fid_camera_model: which instantiation the host launched (the kernels do not read it)
     template <class V>
     __host__ __device__ __forceinline__ void visit(V &&v)
     {
-        v(K); v(D); v(fiducial_len);
+        v(K); v(D); v(fiducial_len); v(model);
     }
 };
+// the caller's camera as the kernels take it; D beyond n_dist is zero whatever the caller left there
+static inline PoseCam pose_cam_from(const fid_camera &c, double fiducial_len)
+{
+    PoseCam p;
+    for (int i = 0; i < 9; i++) p.K[i] = c.K[i];
+    for (int i = 0; i < 12; i++) p.D[i] = i < c.n_dist ? c.D[i] : 0.;
+    p.fiducial_len = fiducial_len;
+    p.model = c.model;
+    return p;
+}
+// {FID_CAM_PLUMB_BOB, 5, K, D}: what the entry points without a fid_camera hand to their _cam twins (D == NULL: no distortion)
+static inline fid_camera fid_camera_plumb_bob(const double K[9], const double D[5])
+{
+    fid_camera c;
+    c.model = FID_CAM_PLUMB_BOB;
+    c.n_dist = 5;
+    for (int i = 0; i < 9; i++) c.K[i] = K[i];
+    for (int i = 0; i < 12; i++) c.D[i] = (D && i < 5) ? D[i] : 0.;
+    return c;
+}
+// a fid_camera as it is remembered and compared: D beyond n_dist zeroed
+static inline fid_camera fid_camera_normalised(const fid_camera &in)
+{
+    fid_camera c = in;
+    for (int i = 0; i < 12; i++)
+        if (i >= c.n_dist) c.D[i] = 0.;
+    return c;
+}
+static inline bool fid_camera_usable(const fid_camera *c)
+{
+    return c && c->model >= FID_CAM_PLUMB_BOB && c->model <= FID_CAM_EQUIDISTANT && c->n_dist >= 0 && c->n_dist <= 12;
+}
+// the host's choice of instantiation: STMT is expanded once per model with the constant CAM_MODEL in scope
+#define POSE_CAM_DISPATCH(model, STMT)                         \
+    do {                                                       \
+        switch (model) {                                       \
+        case FID_CAM_RATIONAL: {                               \
+            constexpr int CAM_MODEL = FID_CAM_RATIONAL;        \
+            STMT;                                              \
+        } break;                                               \
+        case FID_CAM_EQUIDISTANT: {                            \
+            constexpr int CAM_MODEL = FID_CAM_EQUIDISTANT;     \
+            STMT;                                              \
+        } break;                                               \
+        default: {                                             \
+            constexpr int CAM_MODEL = FID_CAM_PLUMB_BOB;       \
+            STMT;                                              \
+        } break;                                               \
+        }                                                      \
+    } while (0)
+// the equidistant model's pinhole normalisation ends at 90 degrees off the axis; a corner at or beyond this angle cannot be posed
+#define PNP_FISHEYE_MAX_THETA (89. * 3.14159265358979323846 / 180.)
 // CvLevMarq's damping factor exp(lambdaLg10 * log(10.)) for lambdaLg10 = -16 .. 16 as the HOST's libm gives it (glibc's exp / log,
 // what the reference runs on; generated with Python's math.exp(k * math.log(10.0)), hexadecimal literals = the exact doubles):
 // a table look-up instead of a device exp() in every Levenberg-Marquardt step -- and the reference's values, not the device
@@ -254,8 +313,13 @@ __device__ __forceinline__ void rodrigues_v2m(const double r_in[3], double R[9],
 }
 
 // cvProjectPoints2Internal for ONE object point and ONE image coordinate (sel = 0: x, 1: y);
-// Jrow[0..2] = d/d rvec, Jrow[3..5] = d/d tvec
-__device__ __forceinline__ double project_one(const double M[3], const double param[6], const double K[9], const double k[5],
+// Jrow[0..2] = d/d rvec, Jrow[3..5] = d/d tvec.  k: PoseCam::D.
+//   FID_CAM_PLUMB_BOB    k1 k2 p1 p2 k3
+//   FID_CAM_RATIONAL     + the denominator 1 + k4 r2 + k5 r4 + k6 r6 (icdist2) and the thin prism s1..s4, OpenCV 4.2's expressions
+//   FID_CAM_EQUIDISTANT  cv::fisheye: theta = atan r, theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+//                        (u, v) = (fx a, fy b) theta_d / r + (cx, cy) (the scale is 1 where r <= 1e-8); no skew
+template <int MODEL>
+__device__ __forceinline__ double project_one(const double M[3], const double param[6], const double K[9], const double k[12],
                                                int sel, double Jrow[6], bool wantJ)
 {
     double R[9], dRdr[27];
@@ -268,43 +332,101 @@ __device__ __forceinline__ double project_one(const double M[3], const double pa
     z = z ? 1. / z : 1;
     x *= z;
     y *= z;
-    double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-    double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
-    double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
-    const double icdist2 = 1.;
-    double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2;
-    double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1;
-    double out = sel == 0 ? xd * fx + cx : yd * fy + cy;
-    if (wantJ) {
-        const double dxdt[3] = {z, 0, -x * z}, dydt[3] = {0, z, -y * z};
+    if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+        const double r2 = x * x + y * y, r = sqrt(r2);
+        const double th = atan(r), th2 = th * th;
+        const double poly = 1 + th2 * (k[0] + th2 * (k[1] + th2 * (k[2] + th2 * k[3])));
+        const double thd = th * poly;
+        const bool tiny = !(r > 1e-8);
+        const double scale = tiny ? 1. : thd / r;
+        const double out = sel == 0 ? fx * (x * scale) + cx : fy * (y * scale) + cy;
+        if (wantJ) {
+            // d scale = g * (x dx + y dy):  d scale / d r = (theta_d' / (1 + r2) - scale) / r,  d r = (x dx + y dy) / r
+            const double dpoly = 1 + th2 * (3 * k[0] + th2 * (5 * k[1] + th2 * (7 * k[2] + th2 * (9 * k[3]))));
+            const double g = tiny ? 0. : (dpoly / (1 + r2) - scale) / r2;
+            const double dxdt[3] = {z, 0, -x * z}, dydt[3] = {0, z, -y * z};
 #pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double dr2dt = 2 * x * dxdt[j] + 2 * y * dydt[j];
-            double dcdist_dt = k[0] * dr2dt + 2 * k[1] * r2 * dr2dt + 3 * k[4] * r4 * dr2dt;
-            double da1dt = 2 * (x * dydt[j] + y * dxdt[j]);
-            double dmxdt = (dxdt[j] * cdist * icdist2 + x * dcdist_dt * icdist2 + k[2] * da1dt + k[3] * (dr2dt + 4 * x * dxdt[j]));
-            double dmydt = (dydt[j] * cdist * icdist2 + y * dcdist_dt * icdist2 + k[2] * (dr2dt + 4 * y * dydt[j]) + k[3] * da1dt);
-            Jrow[3 + j] = sel == 0 ? fx * dmxdt : fy * dmydt;
-        }
-        const double dx0dr[3] = {X * dRdr[0] + Y * dRdr[1] + Z * dRdr[2], X * dRdr[9] + Y * dRdr[10] + Z * dRdr[11],
-                                 X * dRdr[18] + Y * dRdr[19] + Z * dRdr[20]};
-        const double dy0dr[3] = {X * dRdr[3] + Y * dRdr[4] + Z * dRdr[5], X * dRdr[12] + Y * dRdr[13] + Z * dRdr[14],
-                                 X * dRdr[21] + Y * dRdr[22] + Z * dRdr[23]};
-        const double dz0dr[3] = {X * dRdr[6] + Y * dRdr[7] + Z * dRdr[8], X * dRdr[15] + Y * dRdr[16] + Z * dRdr[17],
-                                 X * dRdr[24] + Y * dRdr[25] + Z * dRdr[26]};
+            for (int j = 0; j < 3; j++) {
+                const double ds = g * (x * dxdt[j] + y * dydt[j]);
+                Jrow[3 + j] = sel == 0 ? fx * (dxdt[j] * scale + x * ds) : fy * (dydt[j] * scale + y * ds);
+            }
+            const double dx0dr[3] = {X * dRdr[0] + Y * dRdr[1] + Z * dRdr[2], X * dRdr[9] + Y * dRdr[10] + Z * dRdr[11],
+                                     X * dRdr[18] + Y * dRdr[19] + Z * dRdr[20]};
+            const double dy0dr[3] = {X * dRdr[3] + Y * dRdr[4] + Z * dRdr[5], X * dRdr[12] + Y * dRdr[13] + Z * dRdr[14],
+                                     X * dRdr[21] + Y * dRdr[22] + Z * dRdr[23]};
+            const double dz0dr[3] = {X * dRdr[6] + Y * dRdr[7] + Z * dRdr[8], X * dRdr[15] + Y * dRdr[16] + Z * dRdr[17],
+                                     X * dRdr[24] + Y * dRdr[25] + Z * dRdr[26]};
 #pragma unroll
-        for (int j = 0; j < 3; j++) {
-            double dxdr = z * (dx0dr[j] - x * dz0dr[j]);
-            double dydr = z * (dy0dr[j] - y * dz0dr[j]);
-            double dr2dr = 2 * x * dxdr + 2 * y * dydr;
-            double dcdist_dr = (k[0] + 2 * k[1] * r2 + 3 * k[4] * r4) * dr2dr;
-            double da1dr = 2 * (x * dydr + y * dxdr);
-            double dmxdr = (dxdr * cdist * icdist2 + x * dcdist_dr * icdist2 + k[2] * da1dr + k[3] * (dr2dr + 4 * x * dxdr));
-            double dmydr = (dydr * cdist * icdist2 + y * dcdist_dr * icdist2 + k[2] * (dr2dr + 4 * y * dydr) + k[3] * da1dr);
-            Jrow[j] = sel == 0 ? fx * dmxdr : fy * dmydr;
+            for (int j = 0; j < 3; j++) {
+                const double dxdr = z * (dx0dr[j] - x * dz0dr[j]);
+                const double dydr = z * (dy0dr[j] - y * dz0dr[j]);
+                const double ds = g * (x * dxdr + y * dydr);
+                Jrow[j] = sel == 0 ? fx * (dxdr * scale + x * ds) : fy * (dydr * scale + y * ds);
+            }
         }
+        return out;
+    } else {
+        double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
+        double a1 = 2 * x * y, a2 = r2 + 2 * x * x, a3 = r2 + 2 * y * y;
+        double cdist = 1 + k[0] * r2 + k[1] * r4 + k[4] * r6;
+        double icdist2 = 1.;
+        if constexpr (MODEL == FID_CAM_RATIONAL) icdist2 = 1. / (1 + k[5] * r2 + k[6] * r4 + k[7] * r6);
+        double xd = x * cdist * icdist2 + k[2] * a1 + k[3] * a2;
+        double yd = y * cdist * icdist2 + k[2] * a3 + k[3] * a1;
+        if constexpr (MODEL == FID_CAM_RATIONAL) {
+            xd = xd + k[8] * r2 + k[9] * r4;
+            yd = yd + k[10] * r2 + k[11] * r4;
+        }
+        double out = sel == 0 ? xd * fx + cx : yd * fy + cy;
+        if (wantJ) {
+            const double dxdt[3] = {z, 0, -x * z}, dydt[3] = {0, z, -y * z};
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                double dr2dt = 2 * x * dxdt[j] + 2 * y * dydt[j];
+                double dcdist_dt = k[0] * dr2dt + 2 * k[1] * r2 * dr2dt + 3 * k[4] * r4 * dr2dt;
+                double da1dt = 2 * (x * dydt[j] + y * dxdt[j]);
+                double dmxdt, dmydt;
+                if constexpr (MODEL == FID_CAM_RATIONAL) {
+                    double dicdist2_dt = -icdist2 * icdist2 * (k[5] * dr2dt + 2 * k[6] * r2 * dr2dt + 3 * k[7] * r4 * dr2dt);
+                    dmxdt = (dxdt[j] * cdist * icdist2 + x * dcdist_dt * icdist2 + x * cdist * dicdist2_dt + k[2] * da1dt + k[3] * (dr2dt + 4 * x * dxdt[j]) +
+                             k[8] * dr2dt + 2 * r2 * k[9] * dr2dt);
+                    dmydt = (dydt[j] * cdist * icdist2 + y * dcdist_dt * icdist2 + y * cdist * dicdist2_dt + k[2] * (dr2dt + 4 * y * dydt[j]) + k[3] * da1dt +
+                             k[10] * dr2dt + 2 * r2 * k[11] * dr2dt);
+                } else {
+                    dmxdt = (dxdt[j] * cdist * icdist2 + x * dcdist_dt * icdist2 + k[2] * da1dt + k[3] * (dr2dt + 4 * x * dxdt[j]));
+                    dmydt = (dydt[j] * cdist * icdist2 + y * dcdist_dt * icdist2 + k[2] * (dr2dt + 4 * y * dydt[j]) + k[3] * da1dt);
+                }
+                Jrow[3 + j] = sel == 0 ? fx * dmxdt : fy * dmydt;
+            }
+            const double dx0dr[3] = {X * dRdr[0] + Y * dRdr[1] + Z * dRdr[2], X * dRdr[9] + Y * dRdr[10] + Z * dRdr[11],
+                                     X * dRdr[18] + Y * dRdr[19] + Z * dRdr[20]};
+            const double dy0dr[3] = {X * dRdr[3] + Y * dRdr[4] + Z * dRdr[5], X * dRdr[12] + Y * dRdr[13] + Z * dRdr[14],
+                                     X * dRdr[21] + Y * dRdr[22] + Z * dRdr[23]};
+            const double dz0dr[3] = {X * dRdr[6] + Y * dRdr[7] + Z * dRdr[8], X * dRdr[15] + Y * dRdr[16] + Z * dRdr[17],
+                                     X * dRdr[24] + Y * dRdr[25] + Z * dRdr[26]};
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                double dxdr = z * (dx0dr[j] - x * dz0dr[j]);
+                double dydr = z * (dy0dr[j] - y * dz0dr[j]);
+                double dr2dr = 2 * x * dxdr + 2 * y * dydr;
+                double dcdist_dr = (k[0] + 2 * k[1] * r2 + 3 * k[4] * r4) * dr2dr;
+                double da1dr = 2 * (x * dydr + y * dxdr);
+                double dmxdr, dmydr;
+                if constexpr (MODEL == FID_CAM_RATIONAL) {
+                    double dicdist2_dr = -icdist2 * icdist2 * (k[5] + 2 * k[6] * r2 + 3 * k[7] * r4) * dr2dr;
+                    dmxdr = (dxdr * cdist * icdist2 + x * dcdist_dr * icdist2 + x * cdist * dicdist2_dr + k[2] * da1dr + k[3] * (dr2dr + 4 * x * dxdr) +
+                             (k[8] + 2 * r2 * k[9]) * dr2dr);
+                    dmydr = (dydr * cdist * icdist2 + y * dcdist_dr * icdist2 + y * cdist * dicdist2_dr + k[2] * (dr2dr + 4 * y * dydr) + k[3] * da1dr +
+                             (k[10] + 2 * r2 * k[11]) * dr2dr);
+                } else {
+                    dmxdr = (dxdr * cdist * icdist2 + x * dcdist_dr * icdist2 + k[2] * da1dr + k[3] * (dr2dr + 4 * x * dxdr));
+                    dmydr = (dydr * cdist * icdist2 + y * dcdist_dr * icdist2 + k[2] * (dr2dr + 4 * y * dydr) + k[3] * da1dr);
+                }
+                Jrow[j] = sel == 0 ? fx * dmxdr : fy * dmydr;
+            }
+        }
+        return out;
     }
-    return out;
 }
 
 // solve (JtJ with its diagonal scaled by 1 + lambda) x = JtErr, JtJ symmetric positive definite (packed upper
@@ -364,26 +486,59 @@ __device__ void pnp_mul3(const double a[9], const double b[9], double d[9])
         for (int j = 0; j < 3; j++) d[3 * i + j] = a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j] + a[3 * i + 2] * b[6 + j];
 }
 
-__device__ void pnp_undistort(const double K[9], const double kd[5], double u, double v, double *ox, double *oy)
+// cvUndistortPoints for one pixel: the normalised pinhole point (ox, oy).  Plumb-bob and rational: cvUndistortPointsInternal's five
+// fixed-point iterations, always true.  Equidistant: theta_d = |((u - cx) / fx, (v - cy) / fy)|, theta by Newton from theta_d (at most
+// ten steps, until |step| < 1e-8), the point = the distorted one times tan(theta) / theta_d; false -- and (ox, oy) the distorted
+// point -- where Newton has not converged or theta is not inside [0, PNP_FISHEYE_MAX_THETA): the marker cannot be posed.
+template <int MODEL>
+__device__ bool pnp_undistort(const double K[9], const double kd[12], double u, double v, double *ox, double *oy)
 {
     const double fx = K[0], fy = K[4], ifx = 1. / fx, ify = 1. / fy, cx = K[2], cy = K[5];
     double x = (u - cx) * ifx, y = (v - cy) * ify;
-    const double x0 = x, y0 = y;
-    for (int j = 0; j < 5; j++) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
-        if (icdist < 0) {
-            x = (u - cx) * ifx;
-            y = (v - cy) * ify;
-            break;
+    if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+        const double thd = sqrt(x * x + y * y);
+        double th = thd;
+        bool ok = false;
+        for (int j = 0; j < 10 && !ok; j++) {
+            const double th2 = th * th;
+            const double f = th * (1 + th2 * (kd[0] + th2 * (kd[1] + th2 * (kd[2] + th2 * kd[3])))) - thd;
+            const double df = 1 + th2 * (3 * kd[0] + th2 * (5 * kd[1] + th2 * (7 * kd[2] + th2 * (9 * kd[3]))));
+            const double step = f / df;
+            th -= step;
+            ok = fabs(step) < 1e-8;
         }
-        const double deltaX = 2 * kd[2] * x * y + kd[3] * (r2 + 2 * x * x);
-        const double deltaY = kd[2] * (r2 + 2 * y * y) + 2 * kd[3] * x * y;
-        x = (x0 - deltaX) * icdist;
-        y = (y0 - deltaY) * icdist;
+        ok = ok && th >= 0. && th < PNP_FISHEYE_MAX_THETA;
+        const double sc = (ok && thd > 1e-8) ? tan(th) / thd : 1.;
+        *ox = x * sc;
+        *oy = y * sc;
+        return ok;
+    } else {
+        const double x0 = x, y0 = y;
+        for (int j = 0; j < 5; j++) {
+            const double r2 = x * x + y * y;
+            double icdist;
+            if constexpr (MODEL == FID_CAM_RATIONAL)
+                icdist = (1 + ((kd[7] * r2 + kd[6]) * r2 + kd[5]) * r2) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
+            else
+                icdist = (1) / (1 + ((kd[4] * r2 + kd[1]) * r2 + kd[0]) * r2);
+            if (icdist < 0) {
+                x = (u - cx) * ifx;
+                y = (v - cy) * ify;
+                break;
+            }
+            double deltaX = 2 * kd[2] * x * y + kd[3] * (r2 + 2 * x * x);
+            double deltaY = kd[2] * (r2 + 2 * y * y) + 2 * kd[3] * x * y;
+            if constexpr (MODEL == FID_CAM_RATIONAL) {
+                deltaX = deltaX + kd[8] * r2 + kd[9] * r2 * r2;
+                deltaY = deltaY + kd[10] * r2 + kd[11] * r2 * r2;
+            }
+            x = (x0 - deltaX) * icdist;
+            y = (y0 - deltaY) * icdist;
+        }
+        *ox = x;
+        *oy = y;
+        return true;
     }
-    *ox = x;
-    *oy = y;
 }
 
 // homography marker plane -> normalised image through the four corners (mnx, mny): unit square (0,0),(1,0),(1,1),(0,1) -> quad
@@ -469,8 +624,9 @@ __device__ __forceinline__ void pnp_plane_frame(const double Vt[3][3], const dou
 // the start for a set that is not coplanar: the closed-form pose of ONE marker -- the one the kernel found largest in the image
 // -- composed with that marker's place in the set's frame.  c0, c1, c3: its object corners (c2 is not needed), cc: its centre,
 // uv: its four image corners.  The marker's frame: x along c0 -> c1, y along c3 -> c0, origin at cc.
+template <int MODEL>
 __device__ __forceinline__ void pnp_start_largest(const double *c0, const double *c1, const double *c3, const double cc[3], const double (*uv)[2],
-                                                  const double K[9], const double kd[5], double param[6])
+                                                  const double K[9], const double kd[12], double param[6])
 {
     double ex[3], ey[3], ez[3];
     for (int a = 0; a < 3; a++) {
@@ -484,7 +640,7 @@ __device__ __forceinline__ void pnp_start_largest(const double *c0, const double
     for (int a = 0; a < 3; a++) ez[a] /= wz;
     ey[0] = ez[1] * ex[2] - ez[2] * ex[1]; ey[1] = ez[2] * ex[0] - ez[0] * ex[2]; ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
     double mnx[4], mny[4];
-    for (int i = 0; i < 4; i++) pnp_undistort(K, kd, uv[i][0], uv[i][1], &mnx[i], &mny[i]);
+    for (int i = 0; i < 4; i++) (void)pnp_undistort<MODEL>(K, kd, uv[i][0], uv[i][1], &mnx[i], &mny[i]);
     double h[9], Rq[9], tq[3];
     for (int i = 0; i < 3; i++) param[3 + i] = 0.;
     if (wx > 0. && wy > 0. && wz > 0. && pnp_quad_homography(mnx, mny, 1. / wx, 1. / wy, h)) {

@@ -907,7 +907,7 @@ struct StagJob {
     fid_stag_marker *out = nullptr;
     int cap = 0;
     int32_t *n_out = nullptr;
-    const double *K = nullptr, *D = nullptr;
+    const fid_camera *cam = nullptr;  // NULL: no pose step
     double marker_size = 0;
     fid_stag_pose_out *poses = nullptr;
     int pose_cap = 0;
@@ -1503,22 +1503,16 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
             if (j.out && STAG_MEMCPY(c->hp->markers, c->d_markers, (size_t)nm * sizeof(fid_stag_marker), hipMemcpyDeviceToHost, st) != hipSuccess)
                 return stag_finish(j, FID_E_HIP);
             if (j.last == SS_POSE) {
-                PoseCam cam;
-                for (int i = 0; i < 9; i++) cam.K[i] = j.K[i];
-                for (int i = 0; i < 5; i++) cam.D[i] = j.D ? j.D[i] : 0.0;
-                cam.fiducial_len = j.marker_size;
-                STAG_LAUNCH(k_stag_pose, dim3((nm + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam, j.marker_size, c->d_poses);
+                const PoseCam cam = pose_cam_from(*j.cam, j.marker_size);
+                STAG_LAUNCH_CAM(k_stag_pose, cam.model, dim3((nm + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam, j.marker_size, c->d_poses);
                 if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
                 if (STAG_MEMCPY(c->hp->poses, c->d_poses, (size_t)nm * sizeof(fid_stag_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
                     return stag_finish(j, FID_E_HIP);
             }
-            if (j.bposes && j.K && c->n_bundles > 0) {
+            if (j.bposes && j.cam && c->n_bundles > 0) {
                 // Common::solvePnpBundle for every bundle of the layout, one wave each; the slots come back through the pinned block
-                PoseCam bcam;
-                for (int i = 0; i < 9; i++) bcam.K[i] = j.K[i];
-                for (int i = 0; i < 5; i++) bcam.D[i] = j.D ? j.D[i] : 0.0;
-                bcam.fiducial_len = 0.0;
-                STAG_LAUNCH(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
+                const PoseCam bcam = pose_cam_from(*j.cam, 0.0);
+                STAG_LAUNCH_CAM(k_stag_bundle_pose, bcam.model, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
                 if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
                 if (STAG_MEMCPY(c->hp->bposes, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
                     return stag_finish(j, FID_E_HIP);
@@ -1550,23 +1544,17 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 return stag_finish(j, FID_E_HIP);
         }
         if (j.last == SS_POSE && c->n_markers > 0) {
-            PoseCam cam;
-            for (int i = 0; i < 9; i++) cam.K[i] = j.K[i];
-            for (int i = 0; i < 5; i++) cam.D[i] = j.D ? j.D[i] : 0.0;
-            cam.fiducial_len = j.marker_size;
-            STAG_LAUNCH(k_stag_pose, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam, j.marker_size, c->d_poses);
+            const PoseCam cam = pose_cam_from(*j.cam, j.marker_size);
+            STAG_LAUNCH_CAM(k_stag_pose, cam.model, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam, j.marker_size, c->d_poses);
             if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
             if (STAG_MEMCPY(pin ? c->hp->poses : j.poses, c->d_poses, (size_t)c->n_markers * sizeof(fid_stag_pose_out), hipMemcpyDeviceToHost, st) !=
                 hipSuccess)
                 return stag_finish(j, FID_E_HIP);
         }
-        if (j.bposes && j.K && c->n_bundles > 0 && c->n_markers > 0) {
+        if (j.bposes && j.cam && c->n_bundles > 0 && c->n_markers > 0) {
             // Common::solvePnpBundle for every bundle of the layout, one wave each; the slots come back through the pinned block
-            PoseCam bcam;
-            for (int i = 0; i < 9; i++) bcam.K[i] = j.K[i];
-            for (int i = 0; i < 5; i++) bcam.D[i] = j.D ? j.D[i] : 0.0;
-            bcam.fiducial_len = 0.0;
-            STAG_LAUNCH(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
+            const PoseCam bcam = pose_cam_from(*j.cam, 0.0);
+            STAG_LAUNCH_CAM(k_stag_bundle_pose, bcam.model, dim3(c->n_bundles), dim3(64), 0, st, c->d_markers, c->d_nmarkers, c->d_ltags, c->d_lstart, bcam, c->d_bposes);
             if (hipGetLastError() != hipSuccess) return stag_finish(j, FID_E_HIP);
             if (STAG_MEMCPY(c->hp->bposes, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess)
                 return stag_finish(j, FID_E_HIP);
@@ -1729,17 +1717,22 @@ fid_status fid_stag_detect_markers(fid_stag_ctx *c, const uint8_t *gray, int32_t
 fid_status fid_stag_pose_last(fid_stag_ctx *c, const double K[9], const double D[5], double marker_size, fid_stag_pose_out *out, int32_t cap,
                               int32_t *n_out)
 {
-    if (!c || !K || !out || !c->decoded || !(marker_size > 0)) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_pose_last_cam(c, &cam, marker_size, out, cap, n_out);
+}
+
+fid_status fid_stag_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, double marker_size, fid_stag_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !fid_camera_usable(camera) || !out || !c->decoded || !(marker_size > 0)) return FID_E_INVALID_ARG;
     if (n_out) *n_out = c->n_markers;
     if (c->n_markers > cap) return FID_E_CAPACITY;
     if (c->n_markers == 0) return FID_OK;
     if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
-    PoseCam cam;
-    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
-    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.0;
-    cam.fiducial_len = marker_size;
+    const PoseCam cam = pose_cam_from(*camera, marker_size);
     hipStream_t st = stag_stream(c);
-    hipLaunchKernelGGL(k_stag_pose, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam, marker_size, c->d_poses);
+    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam,
+                                                    marker_size, c->d_poses));
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
     if (hipMemcpyAsync(out, c->d_poses, (size_t)c->n_markers * sizeof(fid_stag_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
     return hipStreamSynchronize(st) == hipSuccess ? FID_OK : FID_E_HIP;
@@ -1792,15 +1785,13 @@ fid_status fid_stag_set_layout(fid_stag_ctx *c, const fid_stag_tag *tags, int32_
 }
 
 // the bundle kernel on a marker list in device memory, its slots read back and handed over in bundle order
-static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const double K[9], const double D[5], const fid_stag_marker *d_markers, const int *d_n,
+static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const fid_camera &camera, const fid_stag_marker *d_markers, const int *d_n,
                                        fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
 {
-    PoseCam cam;
-    for (int i = 0; i < 9; i++) cam.K[i] = K[i];
-    for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.0;
-    cam.fiducial_len = 0.0;
+    const PoseCam cam = pose_cam_from(camera, 0.0);
     hipStream_t st = stag_stream(c);
-    hipLaunchKernelGGL(k_stag_bundle_pose, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags, c->d_lstart, cam, c->d_bposes);
+    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags, c->d_lstart,
+                                                    cam, c->d_bposes));
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
     fid_stag_bundle_pose_out slots[FID_STAG_MAX_BUNDLES];
     if (hipMemcpyAsync(slots, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
@@ -1815,17 +1806,32 @@ static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const double K[9], const
 
 fid_status fid_stag_bundle_pose_last(fid_stag_ctx *c, const double K[9], const double D[5], fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
 {
-    if (!c || !K || !out || cap < 0 || !c->decoded) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_bundle_pose_last_cam(c, &cam, out, cap, n_out);
+}
+
+fid_status fid_stag_bundle_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !fid_camera_usable(camera) || !out || cap < 0 || !c->decoded) return FID_E_INVALID_ARG;
     if (n_out) *n_out = 0;
     if (c->n_bundles == 0 || c->n_markers == 0) return FID_OK;  // (no layout: nothing is launched)
     if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
-    return stag_bundle_pose_run(c, K, D, c->d_markers, c->d_nmarkers, out, cap, n_out);
+    return stag_bundle_pose_run(c, *camera, c->d_markers, c->d_nmarkers, out, cap, n_out);
 }
 
 fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double D[5], const fid_stag_marker *markers, int32_t n,
                                 fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
 {
-    if (!c || !K || !out || cap < 0 || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
+    if (!K) return FID_E_INVALID_ARG;
+    const fid_camera cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_bundle_pose_cam(c, &cam, markers, n, out, cap, n_out);
+}
+
+fid_status fid_stag_bundle_pose_cam(fid_stag_ctx *c, const fid_camera *camera, const fid_stag_marker *markers, int32_t n,
+                                    fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    if (!c || !fid_camera_usable(camera) || !out || cap < 0 || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
     if (n > STAG_LAYOUT_TAGS) return FID_E_CAPACITY;
     if (n_out) *n_out = 0;
     if (c->n_bundles == 0 || n == 0) return FID_OK;
@@ -1835,7 +1841,7 @@ fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double
     if (hipMemcpyAsync(c->d_hmarkers, markers, (size_t)n * sizeof(fid_stag_marker), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(c->d_hn, &nn, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return FID_E_HIP;
-    return stag_bundle_pose_run(c, K, D, c->d_hmarkers, c->d_hn, out, cap, n_out);
+    return stag_bundle_pose_run(c, *camera, c->d_hmarkers, c->d_hn, out, cap, n_out);
 }
 
 // Frames as a grid dimension (round 3; fid_stag_batch.h).  The contexts are cut into GROUPS of up to STAG_MAXF; a group takes
@@ -1846,7 +1852,7 @@ fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double
 // that round).  Results are those of frame-by-frame calls: same kernels bodies, same per-frame buffers, no shared state.
 // frames: host memory, or (dev_frames) device memory in encoding enc -- then a group's first launch is k_stag_ingest, no staging.
 static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
-                                    int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5],
+                                    int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const fid_camera *cam,
                                     double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
                                     fid_stag_bundle_pose_out *bposes, int32_t *n_bposes)
 {
@@ -1855,6 +1861,10 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
     constexpr int kGroupMax = std::min({StagTab<k_stag_route_walk_fn>::kMax, StagTab<k_stag_route_extract_fn>::kMax, StagTab<k_stag_route_extract_small_fn>::kMax, StagTab<k_stag_route_extract_big_fn>::kMax, StagTab<k_stag_route_gather_fn>::kMax,
                                         StagTab<k_stag_quads_fn>::kMax, StagTab<k_stag_decode_fn>::kMax, StagTab<k_stag_validate_lines_fn>::kMax,
                                         StagTab<k_stag_split_lines_fn>::kMax, StagTab<k_stag_refine_fn>::kMax, (int)STAG_MAXF});
+    // (the pose kernels carry a PoseCam by value -- 23 words since it holds twelve coefficients and the model -- and still take a
+    //  full group in one launch)
+    static_assert(StagTab<k_stag_pose_fn<FID_CAM_RATIONAL>>::kMax >= STAG_MAXF && StagTab<k_stag_bundle_pose_fn<FID_CAM_RATIONAL>>::kMax >= STAG_MAXF,
+                  "the pose kernels' argument table no longer holds STAG_MAXF frames");
     // Group size.  More frames per launch make the whole-image passes cheaper per frame (a group of 16 costs 305 us of kernel time a
     // frame, 32: 212, 64: 164 -- profiles/r06_stag_group_sizes.txt) and the latency-bound kernels carry more frames for the same
     // duration while workgroup slots last; more GROUPS keep more kernels in flight, one's long walks under another's image passes.
@@ -1922,8 +1932,8 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
                         }
                         j.width = width; j.height = height; j.stride = stride;
                         j.out = markers + (size_t)f * cap_per_frame; j.cap = cap_per_frame; j.n_out = n_per_frame + f;
-                        j.last = (K && poses) ? SS_POSE : SS_MARKERS;
-                        j.K = K; j.D = D; j.marker_size = marker_size;
+                        j.last = (cam && poses) ? SS_POSE : SS_MARKERS;
+                        j.cam = cam; j.marker_size = marker_size;
                         j.poses = poses ? poses + (size_t)f * cap_per_frame : nullptr; j.pose_cap = cap_per_frame;
                         if (bposes) { j.bposes = bposes + (size_t)f * ctxs[0]->n_bundles; j.n_bposes = n_bposes + f; }
                         G.jobs[k] = j;
@@ -2025,7 +2035,7 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
 
 // the two batch entry points' common part, their arguments checked (frames: host memory; dev_frames: device memory in encoding enc)
 static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, const uint8_t *dev_frames, int enc, int32_t nframes,
-                             int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+                             int32_t width, int32_t height, int32_t stride, int64_t frame_stride, const fid_camera *cam, double marker_size,
                              fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
                              fid_stag_bundle_pose_out *bposes = nullptr, int32_t *n_bposes = nullptr)
 {
@@ -2034,7 +2044,7 @@ static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint
         for (int f = 0; f < nframes; f++) n_bposes[f] = 0;
     // frames as a grid dimension (default); FID_STAG_BATCH=contexts: round 2's road, a stream per context and host threads
     if (!(getenv("FID_STAG_BATCH") && !strcmp(getenv("FID_STAG_BATCH"), "contexts")))
-        return stag_batch_groups(ctxs, nctx, frames, dev_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
+        return stag_batch_groups(ctxs, nctx, frames, dev_frames, enc, nframes, width, height, stride, frame_stride, cam, marker_size, markers, poses,
                                  cap_per_frame, n_per_frame, bposes, n_bposes);
     int nthreads = 4;
     if (const char *e = getenv("FID_STAG_THREADS")) nthreads = atoi(e);
@@ -2065,8 +2075,8 @@ static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint
                         }
                         j.width = width; j.height = height; j.stride = stride;
                         j.out = markers + (size_t)f * cap_per_frame; j.cap = cap_per_frame; j.n_out = n_per_frame + f;
-                        j.last = (K && poses) ? SS_POSE : SS_MARKERS;
-                        j.K = K; j.D = D; j.marker_size = marker_size;
+                        j.last = (cam && poses) ? SS_POSE : SS_MARKERS;
+                        j.cam = cam; j.marker_size = marker_size;
                         j.poses = poses ? poses + (size_t)f * cap_per_frame : nullptr; j.pose_cap = cap_per_frame;
                         if (bposes) { j.bposes = bposes + (size_t)f * ctxs[0]->n_bundles; j.n_bposes = n_bposes + f; }
                         jobs[k] = j;
@@ -2111,16 +2121,25 @@ static fid_status stag_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint
 // takes the next one off a shared counter.  One thread keeps about a thousand frames a second going (a frame is ~60 launches,
 // ~15 copies and a 2 MB staging memcpy: 0.9 ms of host time), so the contexts are dealt out to FID_STAG_THREADS threads
 // (default 4, at most one per context).  Results are those of frame-by-frame calls (a frame never sees another frame's data).
+fid_status fid_stag_detect_markers_batch_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
+                                         int32_t stride, int64_t frame_stride, const fid_camera *cam, double marker_size,
+                                         fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
+{
+    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || (cam && !fid_camera_usable(cam))) return FID_E_INVALID_ARG;
+    for (int t = 0; t < nctx; t++)
+        if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
+    if (cam && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, cam, marker_size, markers, poses,
+                      cap_per_frame, n_per_frame);
+}
+
 fid_status fid_stag_detect_markers_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
                                          int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
                                          fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame)
 {
-    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0) return FID_E_INVALID_ARG;
-    for (int t = 0; t < nctx; t++)
-        if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
-    if (K && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
-    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
-                      cap_per_frame, n_per_frame);
+    fid_camera cam = {};
+    if (K) cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_detect_markers_batch_cam(ctxs, nctx, frames, nframes, width, height, stride, frame_stride, (K ? &cam : nullptr), marker_size, markers, poses, cap_per_frame, n_per_frame);
 }
 
 // ---- frames in device memory (fid_stag_detect_markers_device / _batch_device).  Everything such a call can be refused for is
@@ -2173,15 +2192,15 @@ fid_status fid_stag_detect_markers_device(fid_stag_ctx *c, const void *d_img, in
     return stag_run(c, j);
 }
 
-fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
-                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+fid_status fid_stag_detect_markers_batch_device_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const fid_camera *cam,
                                                 double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
                                                 int32_t *n_per_frame)
 {
-    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0) return FID_E_INVALID_ARG;
+    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || (cam && !fid_camera_usable(cam))) return FID_E_INVALID_ARG;
     for (int t = 0; t < nctx; t++)
         if (!ctxs[t] || !ctxs[t]->d_words || width > ctxs[t]->maxW || height > ctxs[t]->maxH || ctxs[t]->device != ctxs[0]->device) return FID_E_INVALID_ARG;
-    if (K && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
+    if (cam && poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
     if (stag_enc_bpp(enc) == 0) return FID_E_UNSUPPORTED;
     if (nframes > 0) {
         const fid_status rc = stag_check_device_frames((const uint8_t *)d_frames, ctxs[0]->device, nframes, width, height, stride, frame_stride, enc);
@@ -2189,8 +2208,18 @@ fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32
     } else if (!d_frames) {
         return FID_E_INVALID_ARG;
     }
-    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers,
+    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, cam, marker_size, markers,
                       poses, cap_per_frame, n_per_frame);
+}
+
+fid_status fid_stag_detect_markers_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+                                                double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                                int32_t *n_per_frame)
+{
+    fid_camera cam = {};
+    if (K) cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_detect_markers_batch_device_cam(ctxs, nctx, d_frames, nframes, width, height, stride, frame_stride, enc, (K ? &cam : nullptr), marker_size, markers, poses, cap_per_frame, n_per_frame);
 }
 
 
@@ -2205,28 +2234,38 @@ static fid_status stag_same_layout(fid_stag_ctx *const *ctxs, int32_t nctx)
     return FID_OK;
 }
 
-fid_status fid_stag_detect_bundles_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
-                                         int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+fid_status fid_stag_detect_bundles_batch_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
+                                         int32_t stride, int64_t frame_stride, const fid_camera *cam, double marker_size,
                                          fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
                                          fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
 {
-    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !K || !bundle_poses || !n_bundles_per_frame)
+    if (!ctxs || nctx <= 0 || !frames || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !fid_camera_usable(cam) || !bundle_poses || !n_bundles_per_frame)
         return FID_E_INVALID_ARG;
     for (int t = 0; t < nctx; t++)
         if (!ctxs[t] || !ctxs[t]->d_words) return FID_E_INVALID_ARG;
     if (poses && !(marker_size > 0)) return FID_E_INVALID_ARG;
     const fid_status rc = stag_same_layout(ctxs, nctx);
     if (rc != FID_OK) return rc;
-    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, K, D, marker_size, markers, poses,
+    return stag_batch(ctxs, nctx, frames, nullptr, FID_ENC_MONO8, nframes, width, height, stride, frame_stride, cam, marker_size, markers, poses,
                       cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
 }
 
-fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
-                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+fid_status fid_stag_detect_bundles_batch(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width, int32_t height,
+                                         int32_t stride, int64_t frame_stride, const double K[9], const double D[5], double marker_size,
+                                         fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                                         fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
+{
+    fid_camera cam = {};
+    if (K) cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_detect_bundles_batch_cam(ctxs, nctx, frames, nframes, width, height, stride, frame_stride, (K ? &cam : nullptr), marker_size, markers, poses, cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
+}
+
+fid_status fid_stag_detect_bundles_batch_device_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const fid_camera *cam,
                                                 double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
                                                 int32_t *n_per_frame, fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
 {
-    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !K || !bundle_poses || !n_bundles_per_frame)
+    if (!ctxs || nctx <= 0 || nframes < 0 || !markers || !n_per_frame || cap_per_frame <= 0 || !fid_camera_usable(cam) || !bundle_poses || !n_bundles_per_frame)
         return FID_E_INVALID_ARG;
     for (int t = 0; t < nctx; t++)
         if (!ctxs[t] || !ctxs[t]->d_words || width > ctxs[t]->maxW || height > ctxs[t]->maxH || ctxs[t]->device != ctxs[0]->device) return FID_E_INVALID_ARG;
@@ -2240,8 +2279,18 @@ fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32
     } else if (!d_frames) {
         return FID_E_INVALID_ARG;
     }
-    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, K, D, marker_size, markers,
+    return stag_batch(ctxs, nctx, nullptr, (const uint8_t *)d_frames, enc, nframes, width, height, stride, frame_stride, cam, marker_size, markers,
                       poses, cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
+}
+
+fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                int32_t height, int32_t stride, int64_t frame_stride, fid_encoding enc, const double K[9], const double D[5],
+                                                double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                                int32_t *n_per_frame, fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame)
+{
+    fid_camera cam = {};
+    if (K) cam = fid_camera_plumb_bob(K, D);
+    return fid_stag_detect_bundles_batch_device_cam(ctxs, nctx, d_frames, nframes, width, height, stride, frame_stride, enc, (K ? &cam : nullptr), marker_size, markers, poses, cap_per_frame, n_per_frame, bundle_poses, n_bundles_per_frame);
 }
 
 fid_status fid_stag_queue_stats(const fid_stag_ctx *c, int32_t *queued, int32_t *rerun)

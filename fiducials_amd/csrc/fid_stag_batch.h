@@ -361,6 +361,27 @@ thread_local const char *StagSite<Fn, SITE>::name = nullptr;
         }                                                                                                  \
     } while (0)
 
+// the same for a kernel and functor that are templates on ONE constant (the pose kernels' camera model): K<T> and K_fn<T>
+#define STAG_LAUNCH_T(K, T, grid, block, lds, st, ...)                                                     \
+    do {                                                                                                   \
+        if (g_stag_rec && g_stag_rec->on) {                                                                \
+            using Site_ = StagSite<K##_fn<T>, __COUNTER__>;                                                \
+            Site_::name = #K "<" #T ">[g]";                                                                \
+            Site_::record(*g_stag_rec, grid, block, lds, __VA_ARGS__);                                     \
+        } else {                                                                                           \
+            if ((size_t)(lds) > 0) fid_launch_log(#K, dim3(block).x * dim3(block).y * dim3(block).z, (size_t)(lds)); \
+            hipLaunchKernelGGL(K<T>, grid, block, lds, st, __VA_ARGS__);                                   \
+        }                                                                                                  \
+    } while (0)
+// ... with the constant picked from a fid_camera_model at run time.  Three sites in a row in source order; one call's frames all
+// carry the same camera, so a group uses one of them.
+#define STAG_LAUNCH_CAM(K, model, grid, block, lds, st, ...)                                               \
+    do {                                                                                                   \
+        if ((model) == FID_CAM_RATIONAL) STAG_LAUNCH_T(K, FID_CAM_RATIONAL, grid, block, lds, st, __VA_ARGS__);          \
+        else if ((model) == FID_CAM_EQUIDISTANT) STAG_LAUNCH_T(K, FID_CAM_EQUIDISTANT, grid, block, lds, st, __VA_ARGS__); \
+        else STAG_LAUNCH_T(K, FID_CAM_PLUMB_BOB, grid, block, lds, st, __VA_ARGS__);                       \
+    } while (0)
+
 // ---- the small device operations of the state machine as kernels, so that a group issues each of them ONCE: fills, device
 // copies, and the few bytes of counters that go back to the host after every segment (written straight into the context's
 // pinned host block through its device alias: no copy engine round per frame)

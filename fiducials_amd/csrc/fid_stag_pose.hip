@@ -800,6 +800,7 @@ struct k_stag_refine_fn {
 // four corners, then the reference's Levenberg-Marquardt (LevMarq) on the reprojection error of all five points with
 // distortion; a 16-lane group per marker, lane g < 10 owns residual g, the sums by grp_sum16.  Tolerance row (the reference
 // starts from a 5-point DLT + refinement; both land on the same minimum).
+template <int MODEL>
 __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam,
                                                   double marker_size, fid_stag_pose_out *__restrict__ out)
 {
@@ -822,7 +823,25 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
     double param[6] = {0, 0, 0, 0, 0, 0};
     {
         double mnx[4], mny[4], h[9];
-        for (int i = 0; i < 4; i++) pnp_undistort(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &mnx[i], &mny[i]);
+        bool posable = true;  // (group-uniform: every lane undistorts all four corners)
+        for (int i = 0; i < 4; i++) {
+            const bool ok = pnp_undistort<MODEL>(K, kd, mk.corners[2 * i], mk.corners[2 * i + 1], &mnx[i], &mny[i]);
+            if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = posable && ok;
+        }
+        if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+            double cxn, cyn;
+            posable = pnp_undistort<MODEL>(K, kd, mk.center[0], mk.center[1], &cxn, &cyn) && posable;
+            if (!posable) {  // a point beyond the model (fid_abi.h: "a marker that cannot be posed"): the documented record
+                if (g == 0) {
+                    fid_stag_pose_out o;
+                    o.id = mk.id;
+                    for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
+                    for (int i = 0; i < 9; i++) o.R[i] = 0.;
+                    out[item] = o;
+                }
+                return;
+            }
+        }
         const double sc0 = 1. / (2. * hx);
         if (pnp_quad_homography(mnx, mny, sc0, sc0, h)) {
             pnp_pose_from_h(h, param + 3);
@@ -836,7 +855,7 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
     bool needJ = true;
     LevMarq lm;
     do {
-        const double pr = project_one(M, param, K, kd, sel, Jrow, needJ);
+        const double pr = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ);
         err = act ? pr - mobs : 0.;
         if (!act)
             for (int i = 0; i < 6; i++) Jrow[i] = 0.;
@@ -860,13 +879,15 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
         out[item] = o;
     }
 }
+template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out)
 {
-    k_stag_pose_impl(markers, nmarkers, cam, marker_size, out);
+    k_stag_pose_impl<MODEL>(markers, nmarkers, cam, marker_size, out);
 }
+template <int MODEL>
 struct k_stag_pose_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out) const { k_stag_pose_impl(markers, nmarkers, cam, marker_size, out); }
+    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out) const { k_stag_pose_impl<MODEL>(markers, nmarkers, cam, marker_size, out); }
 };
 
 // ------------------------------------------------------------------------------------------------ K18: bundle pose
@@ -882,7 +903,7 @@ struct k_stag_pose_fn {
 //       eigenproblem by cyclic Jacobi in LDS, lane k the k-th row / column of a rotation), R and t from its columns.  Not coplanar
 //       (tags on several faces): the closed-form four-corner pose of the found tag that is largest in the image, composed with that
 //       tag's place in the bundle (OpenCV runs a 12 x 12 DLT there; parity unpinned);
-//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_stag_pose), plumb-bob distortion in the projection and its Jacobian.  Up to 120
+//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_stag_pose), the camera model's distortion (the template parameter) in the projection and its Jacobian.  Up to 120
 //       residuals strided over the 64 lanes; J^T J (21), J^T e (6) and the norms are per-lane partial sums and one xor-butterfly
 //       over the wave -- a fixed order: reproducible from run to run, the same value in every lane.
 #define SB_MAX_TAGS 12  // FID_STAG_MAX_TAGS_PER_BUNDLE
@@ -936,6 +957,7 @@ __device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
     return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
+template <int MODEL>
 __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
                                                          const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam,
                                                          fid_stag_bundle_pose_out *__restrict__ out)
@@ -983,6 +1005,7 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
     }
     SR_LDS_SYNC();
     const int npts = 5 * found;
+    bool posable = true;
     if (lane < npts) {
         const int p = lane / 5, q = lane % 5;
         const fid_stag_tag *tg = ltags + t0 + s.tagof[p];
@@ -992,7 +1015,8 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         s.img[lane][0] = u;
         s.img[lane][1] = v;
         double x, y;
-        pnp_undistort(K, kd, u, v, &x, &y);
+        const bool ok = pnp_undistort<MODEL>(K, kd, u, v, &x, &y);
+        if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = ok;
         s.mn[lane][0] = (double)(float)x;  // (the DLT's input: findHomography converts to float)
         s.mn[lane][1] = (double)(float)y;
         if (q == 0) {  // the tag's area in the image (shoelace over its four corners)
@@ -1005,6 +1029,19 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         }
     }
     SR_LDS_SYNC();
+    if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+        if (__ballot(!posable) != 0ull) {  // a point beyond the model (fid_abi.h: "a marker that cannot be posed") voids the bundle's record
+            if (lane == 0) {
+                fid_stag_bundle_pose_out o;
+                o.bundle = b;
+                o.n_tags = found;
+                for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
+                for (int i = 0; i < 9; i++) o.R[i] = 0.;
+                out[b] = o;
+            }
+            return;
+        }
+    }
     // ---- (2) planarity: the centred scatter matrix of the object points and its eigenvalues (every lane the same)
     double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
     {
@@ -1048,7 +1085,7 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         for (int p = 1; p < found; p++)
             if (s.area[p] > s.area[big]) big = p;
         // (a tag's points: its centre, then c0..c3)
-        pnp_start_largest(s.obj[5 * big + 1], s.obj[5 * big + 2], s.obj[5 * big + 4], s.obj[5 * big], s.img + 5 * big + 1, K, kd, param);
+        pnp_start_largest<MODEL>(s.obj[5 * big + 1], s.obj[5 * big + 2], s.obj[5 * big + 4], s.obj[5 * big], s.img + 5 * big + 1, K, kd, param);
     }
     // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l and l + 64
     const int nres = 2 * npts;
@@ -1061,13 +1098,13 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
     LevMarq lm;
     do {
         if (act0) {
-            err0 = project_one(M0, param, K, kd, r0 & 1, J0, needJ) - mobs0;
+            err0 = project_one<MODEL>(M0, param, K, kd, r0 & 1, J0, needJ) - mobs0;
         } else {
             err0 = 0.;
             for (int i = 0; i < 6; i++) J0[i] = 0.;
         }
         if (act1) {
-            err1 = project_one(M1, param, K, kd, r1 & 1, J1, needJ) - mobs1;
+            err1 = project_one<MODEL>(M1, param, K, kd, r1 & 1, J1, needJ) - mobs1;
         } else {
             err1 = 0.;
             for (int i = 0; i < 6; i++) J1[i] = 0.;
@@ -1093,11 +1130,13 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         out[b] = o;
     }
 }
+template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_bundle_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out)
 {
-    k_stag_bundle_pose_impl(markers, nmarkers, ltags, lstart, cam, out);
+    k_stag_bundle_pose_impl<MODEL>(markers, nmarkers, ltags, lstart, cam, out);
 }
+template <int MODEL>
 struct k_stag_bundle_pose_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out) const { k_stag_bundle_pose_impl(markers, nmarkers, ltags, lstart, cam, out); }
+    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out) const { k_stag_bundle_pose_impl<MODEL>(markers, nmarkers, ltags, lstart, cam, out); }
 };

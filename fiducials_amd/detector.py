@@ -17,6 +17,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from . import camera as _camera
 from ._lib import FidCandidate, FidDict, FidError, FidLimits, FidMarker, FidParams, FidPoseOut
 from .dictionary import Dictionary, get_predefined_dictionary
 
@@ -272,8 +273,12 @@ class ArucoDetector:
         return self._unpack(nframes)
 
     # -- pose ---------------------------------------------------------------------------------
-    def estimate_pose_single_markers(self, corners: np.ndarray, ids: np.ndarray, fiducial_len: float, K, D,
-                                     fiducial_len_override: dict | None = None) -> PoseResult:
+    def estimate_pose_single_markers(self, corners: np.ndarray, ids: np.ndarray, fiducial_len: float, K=None, D=None,
+                                     fiducial_len_override: dict | None = None, camera=None) -> PoseResult:
+        """fid_pose for markers handed in from the host: K, D (plumb-bob), or camera= (fiducials_amd.camera.Camera: fid_pose_cam)."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
         corners = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 8)
         n = corners.shape[0]
         mk = (FidMarker * max(n, 1))()
@@ -283,11 +288,29 @@ class ArucoDetector:
             for j in range(8):
                 mk[i].corners[j] = float(corners[i, j])
             lens[i] = float((fiducial_len_override or {}).get(int(ids[i]), fiducial_len))  # :241-244
+        out = (FidPoseOut * max(n, 1))()
+        if camera is not None:
+            self._check(self._L.fid_pose_cam(self._ctx, C.byref(cam.c), mk, lens, n, float(fiducial_len), out))
+            return _poses_to_result(out, n)
         Kc = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
         Dc = (C.c_double * 5)(*np.asarray(D, dtype=np.float64).reshape(-1)[:5])
-        out = (FidPoseOut * max(n, 1))()
         self._check(self._L.fid_pose(self._ctx, Kc, Dc, mk, lens, n, float(fiducial_len), out))
         return _poses_to_result(out, n)
+
+    def project_points(self, camera, rvec, tvec, obj, jacobian: bool = False):
+        """cv::projectPoints under `camera` (fid_project_points_cam: the pose kernels' own projection run as a small kernel): obj
+        (n, 3) -> uv (n, 2); with jacobian=True also d(u, v) / d(rvec, tvec) as (n, 2, 6)."""
+        cam = _camera.resolve(None, None, camera)
+        if cam is None:
+            raise ValueError("project_points needs a camera")
+        o = np.ascontiguousarray(obj, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(rvec, dtype=np.float64).reshape(3)
+        t = np.ascontiguousarray(tvec, dtype=np.float64).reshape(3)
+        uv = np.zeros((len(o), 2))
+        jac = np.zeros((len(o), 2, 6)) if jacobian else None
+        self._check(self._L.fid_project_points_cam(self._ctx, C.byref(cam.c), r.ctypes.data, t.ctypes.data, o.ctypes.data if len(o) else None, len(o),
+                                                   uv.ctypes.data if len(o) else None, jac.ctypes.data if jacobian and len(o) else None))
+        return (uv, jac) if jacobian else uv
 
     def refine_contour_corners(self, contours, corners) -> np.ndarray:
         """aruco.cpp _refineCandidateLines (CORNER_REFINE_CONTOUR) for markers given by their contours (list of (n_i, 2) int
@@ -303,11 +326,18 @@ class ArucoDetector:
         self._check(self._L.fid_refine_contour_corners(self._ctx, pts.ctypes.data, off.ctypes.data, len(cs), q.ctypes.data, st.ctypes.data))
         return q.reshape(-1, 4, 2)
 
-    def pose_last(self, fiducial_len: float, K, D, unpack: bool = True):
-        """Poses of the markers found by the last detect_* call, computed without the corners leaving HBM."""
-        Kc = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
-        Dc = (C.c_double * 5)(*np.asarray(D, dtype=np.float64).reshape(-1)[:5])
-        self._check(self._L.fid_pose_last(self._ctx, Kc, Dc, float(fiducial_len), self._poses, self.max_markers))
+    def pose_last(self, fiducial_len: float, K=None, D=None, unpack: bool = True, camera=None):
+        """Poses of the markers found by the last detect_* call, computed without the corners leaving HBM.  K, D (plumb-bob) or
+        camera= (fid_pose_last_cam)."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        if camera is not None:
+            self._check(self._L.fid_pose_last_cam(self._ctx, C.byref(cam.c), float(fiducial_len), self._poses, self.max_markers))
+        else:
+            Kc = (C.c_double * 9)(*np.asarray(K, dtype=np.float64).reshape(9))
+            Dc = (C.c_double * 5)(*np.asarray(D, dtype=np.float64).reshape(-1)[:5])
+            self._check(self._L.fid_pose_last(self._ctx, Kc, Dc, float(fiducial_len), self._poses, self.max_markers))
         if not unpack:
             return None
         res = []
@@ -329,22 +359,31 @@ class ArucoDetector:
         Dc = None if D is None else np.ascontiguousarray(np.asarray(D, dtype=np.float64).reshape(-1)[:5])
         return Kc, Dc
 
-    def map_pose_last(self, K, D) -> np.ndarray:
-        """One camera pose per frame of the last detect_* / collect call (fid_map_pose_last): MAP_POSE_DTYPE records."""
-        Kc, Dc = self._cam(K, D)
+    def map_pose_last(self, K=None, D=None, camera=None) -> np.ndarray:
+        """One camera pose per frame of the last detect_* / collect call (fid_map_pose_last): MAP_POSE_DTYPE records.  K, D
+        (plumb-bob) or camera= (fid_map_pose_last_cam)."""
         out = np.zeros(max(self._last_frames, 1), MAP_POSE_DTYPE)
+        if camera is not None:
+            cam = _camera.resolve(K, D, camera)
+            self._check(self._L.fid_map_pose_last_cam(self._ctx, C.byref(cam.c), out.ctypes.data, len(out)))
+            return out[:self._last_frames]
+        Kc, Dc = self._cam(K, D)
         self._check(self._L.fid_map_pose_last(self._ctx, Kc.ctypes.data, Dc.ctypes.data if Dc is not None else None, out.ctypes.data, len(out)))
         return out[:self._last_frames]
 
-    def map_pose(self, K, D, corners, ids) -> np.ndarray:
+    def map_pose(self, K=None, D=None, corners=None, ids=None, camera=None) -> np.ndarray:
         """The same kernel on the markers of one frame handed in from the host (fid_map_pose): corners (n, 4, 2), ids (n,) in list
-        order.  Returns one MAP_POSE_DTYPE record."""
-        Kc, Dc = self._cam(K, D)
+        order.  Returns one MAP_POSE_DTYPE record.  K, D (plumb-bob) or camera= (fid_map_pose_cam)."""
         ids = np.asarray(ids, np.int32).reshape(-1)
         mk = np.zeros(len(ids), _MARKER_DT)
         mk["id"] = ids
         mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
         out = np.zeros(1, MAP_POSE_DTYPE)
+        if camera is not None:
+            cam = _camera.resolve(K, D, camera)
+            self._check(self._L.fid_map_pose_cam(self._ctx, C.byref(cam.c), mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data))
+            return out[0]
+        Kc, Dc = self._cam(K, D)
         self._check(self._L.fid_map_pose(self._ctx, Kc.ctypes.data, Dc.ctypes.data if Dc is not None else None,
                                          mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data))
         return out[0]

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from . import camera as _camera
 from ._lib import FidError
 
 (TAP_SMOOTH, TAP_GRAD, TAP_DIR, TAP_ANCHORS, TAP_SORTED, TAP_EDGEIMG, TAP_SEGMENTS, TAP_SEGPIX, TAP_SMOOTH2, TAP_VGRAD, TAP_VPROB,
@@ -81,10 +82,16 @@ def load_layout(path: str) -> Layout:
     return Layout(tags[:nt.value].copy(), names, standalone[:nb.value].astype(bool))
 
 
-def _compact_K_D(K, D):
-    Kp = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+def _camera_call(L, name: str, K, D, camera):
+    """The entry point a pose method calls and its camera arguments: `name` with K, D (plumb-bob; K None where the entry point
+    allows it: no pose step), or its twin `name`_cam with camera= (fiducials_amd.camera.Camera).  The third item keeps the
+    arguments' memory alive over the call."""
+    if camera is not None:
+        cam = _camera.resolve(K, D, camera)
+        return getattr(L, name + "_cam"), (C.byref(cam.c),), cam
+    Kp = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(9)
     Dp = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
-    return Kp, Dp
+    return getattr(L, name), (None if Kp is None else Kp.ctypes.data, Dp.ctypes.data), (Kp, Dp)
 
 
 class StagDetector:
@@ -185,13 +192,12 @@ class StagDetector:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return self._mbuf[:n.value].copy()
 
-    def pose_last(self, K, D, marker_size: float) -> np.ndarray:
-        """Common::solvePnpSingle for the markers of the last detect_markers*() call (POSE_DTYPE)."""
-        K = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
-        Dv = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
+    def pose_last(self, K=None, D=None, marker_size: float = 0.0, camera=None) -> np.ndarray:
+        """Common::solvePnpSingle for the markers of the last detect_markers*() call (POSE_DTYPE).  K, D (plumb-bob) or camera=."""
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_pose_last", K, D, camera)
         out = np.zeros(4096, POSE_DTYPE)
         n = C.c_int32(0)
-        rc = self._L.fid_stag_pose_last(self._ctx, K.ctypes.data, Dv.ctypes.data, float(marker_size), out.ctypes.data, len(out), C.byref(n))
+        rc = fn(self._ctx, *cargs, float(marker_size), out.ctypes.data, len(out), C.byref(n))
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return out[:n.value].copy()
@@ -205,25 +211,25 @@ class StagDetector:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         self.layout = layout if len(tags) else None
 
-    def bundle_pose_last(self, K, D) -> np.ndarray:
+    def bundle_pose_last(self, K=None, D=None, camera=None) -> np.ndarray:
         """Common::solvePnpBundle for the markers of the last detect_markers*() call, on the device (BUNDLE_POSE_DTYPE): one record per
-        bundle of which a tag was found, in bundle order."""
-        Kp, Dp = _compact_K_D(K, D)
+        bundle of which a tag was found, in bundle order.  K, D (plumb-bob) or camera=."""
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_bundle_pose_last", K, D, camera)
         out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
         n = C.c_int32(0)
-        rc = self._L.fid_stag_bundle_pose_last(self._ctx, Kp.ctypes.data, Dp.ctypes.data, out.ctypes.data, len(out), C.byref(n))
+        rc = fn(self._ctx, *cargs, out.ctypes.data, len(out), C.byref(n))
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return out[:n.value].copy()
 
-    def bundle_pose(self, K, D, markers: np.ndarray) -> np.ndarray:
-        """The same kernel on markers handed in from the host (MARKER_DTYPE; id, corners and center are read)."""
-        Kp, Dp = _compact_K_D(K, D)
+    def bundle_pose(self, K=None, D=None, markers: np.ndarray = None, camera=None) -> np.ndarray:
+        """The same kernel on markers handed in from the host (MARKER_DTYPE; id, corners and center are read).  K, D (plumb-bob) or
+        camera=."""
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_bundle_pose", K, D, camera)
         m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)
         out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
         n = C.c_int32(0)
-        rc = self._L.fid_stag_bundle_pose(self._ctx, Kp.ctypes.data, Dp.ctypes.data, m.ctypes.data if len(m) else None, len(m), out.ctypes.data,
-                                          len(out), C.byref(n))
+        rc = fn(self._ctx, *cargs, m.ctypes.data if len(m) else None, len(m), out.ctypes.data, len(out), C.byref(n))
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return out[:n.value].copy()
@@ -311,7 +317,7 @@ class StagPool:
         lay = getattr(self.dets[0], "layout", None)
         return lay.n_bundles if lay is not None else 0
 
-    def detect_bundles_batch(self, frames: np.ndarray, K, D=None, marker_size: float = 0.18, cap_per_frame: int = 64):
+    def detect_bundles_batch(self, frames: np.ndarray, K=None, D=None, marker_size: float = 0.18, cap_per_frame: int = 64, camera=None):
         """detect_markers_batch with the bundle step behind the marker pose (fid_stag_detect_bundles_batch)
         -> (markers per frame, poses per frame, bundle poses per frame)."""
         fr = np.ascontiguousarray(frames, dtype=np.uint8)
@@ -321,8 +327,8 @@ class StagPool:
         poses = np.zeros((F, cap_per_frame), POSE_DTYPE)
         bposes = np.zeros((F, nb), BUNDLE_POSE_DTYPE)
         counts, bcounts = np.zeros(max(F, 1), np.int32), np.zeros(max(F, 1), np.int32)
-        Kp, Dp = _compact_K_D(K, D)
-        rc = self._L.fid_stag_detect_bundles_batch(self._arr, len(self.dets), fr.ctypes.data, F, w, h, w, w * h, Kp.ctypes.data, Dp.ctypes.data,
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_detect_bundles_batch", K, D, camera)
+        rc = fn(self._arr, len(self.dets), fr.ctypes.data, F, w, h, w, w * h, *cargs,
                                                    float(marker_size), markers.ctypes.data, poses.ctypes.data, cap_per_frame, counts.ctypes.data,
                                                    bposes.ctypes.data, bcounts.ctypes.data)
         if rc != _lib.FID_OK:
@@ -330,8 +336,9 @@ class StagPool:
         return ([markers[f, :counts[f]] for f in range(F)], [poses[f, :counts[f]] for f in range(F)],
                 [bposes[f, :bcounts[f]] for f in range(F)])
 
-    def detect_bundles_batch_device(self, data_ptr: int, nframes: int, width: int, height: int, K, D=None, stride: int | None = None,
-                                    frame_stride: int | None = None, encoding: str = "mono8", marker_size: float = 0.18, cap_per_frame: int = 64):
+    def detect_bundles_batch_device(self, data_ptr: int, nframes: int, width: int, height: int, K=None, D=None, stride: int | None = None,
+                                    frame_stride: int | None = None, encoding: str = "mono8", marker_size: float = 0.18, cap_per_frame: int = 64,
+                                    camera=None):
         """detect_bundles_batch on frames already resident on the pool's device (fid_stag_detect_bundles_batch_device)."""
         enc = _lib.ENC.get(encoding, -1)
         bpp = _lib.ENC_BYTES_PER_PIXEL.get(encoding, 1)
@@ -342,25 +349,24 @@ class StagPool:
         poses = np.zeros((nframes, cap_per_frame), POSE_DTYPE)
         bposes = np.zeros((nframes, nb), BUNDLE_POSE_DTYPE)
         counts, bcounts = np.zeros(max(nframes, 1), np.int32), np.zeros(max(nframes, 1), np.int32)
-        Kp, Dp = _compact_K_D(K, D)
-        rc = self._L.fid_stag_detect_bundles_batch_device(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride, frame_stride,
-                                                          enc, Kp.ctypes.data, Dp.ctypes.data, float(marker_size), markers.ctypes.data,
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_detect_bundles_batch_device", K, D, camera)
+        rc = fn(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride, frame_stride,
+                                                          enc, *cargs, float(marker_size), markers.ctypes.data,
                                                           poses.ctypes.data, cap_per_frame, counts.ctypes.data, bposes.ctypes.data, bcounts.ctypes.data)
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return ([markers[f, :counts[f]] for f in range(nframes)], [poses[f, :counts[f]] for f in range(nframes)],
                 [bposes[f, :bcounts[f]] for f in range(nframes)])
 
-    def detect_markers_batch(self, frames: np.ndarray, K=None, D=None, marker_size: float = 0.18, cap_per_frame: int = 64):
+    def detect_markers_batch(self, frames: np.ndarray, K=None, D=None, marker_size: float = 0.18, cap_per_frame: int = 64, camera=None):
         fr = np.ascontiguousarray(frames, dtype=np.uint8)
         F, h, w = fr.shape
         markers = np.zeros((F, cap_per_frame), MARKER_DTYPE)
         poses = np.zeros((F, cap_per_frame), POSE_DTYPE)
         counts = np.zeros(F, np.int32)
-        Kp = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(9)
-        Dp = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
-        rc = self._L.fid_stag_detect_markers_batch(self._arr, len(self.dets), fr.ctypes.data, F, w, h, w, w * h,
-                                                   None if Kp is None else Kp.ctypes.data, Dp.ctypes.data, float(marker_size),
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_detect_markers_batch", K, D, camera)
+        rc = fn(self._arr, len(self.dets), fr.ctypes.data, F, w, h, w, w * h,
+                                                   *cargs, float(marker_size),
                                                    markers.ctypes.data, poses.ctypes.data, cap_per_frame, counts.ctypes.data)
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
@@ -368,7 +374,7 @@ class StagPool:
 
     def detect_markers_batch_device(self, data_ptr: int, nframes: int, width: int, height: int, stride: int | None = None,
                                     frame_stride: int | None = None, encoding: str = "mono8", K=None, D=None, marker_size: float = 0.18,
-                                    cap_per_frame: int = 64):
+                                    cap_per_frame: int = 64, camera=None):
         """detect_markers_batch on frames already resident on the pool's device (fid_stag_detect_markers_batch_device): frame f at
         data_ptr + f * frame_stride (default: packed frames), mono8 / bgr8 / rgb8, no host staging.  -> (markers per frame, poses
         per frame)."""
@@ -379,10 +385,9 @@ class StagPool:
         markers = np.zeros((nframes, cap_per_frame), MARKER_DTYPE)
         poses = np.zeros((nframes, cap_per_frame), POSE_DTYPE)
         counts = np.zeros(max(nframes, 1), np.int32)
-        Kp = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(9)
-        Dp = np.zeros(5) if D is None else np.ascontiguousarray(D, dtype=np.float64).reshape(-1)[:5].copy()
-        rc = self._L.fid_stag_detect_markers_batch_device(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride,
-                                                          frame_stride, enc, None if Kp is None else Kp.ctypes.data, Dp.ctypes.data,
+        fn, cargs, _keep = _camera_call(self._L, "fid_stag_detect_markers_batch_device", K, D, camera)
+        rc = fn(self._arr, len(self.dets), C.c_void_p(data_ptr), nframes, width, height, stride,
+                                                          frame_stride, enc, *cargs,
                                                           float(marker_size), markers.ctypes.data, poses.ctypes.data, cap_per_frame,
                                                           counts.ctypes.data)
         if rc != _lib.FID_OK:

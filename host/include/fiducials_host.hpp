@@ -206,7 +206,8 @@ class FiducialsNode {
     std::vector<int> ids;
     std::vector<int> ignoreIds;
     std::map<int, double> fiducialLens;
-    double cameraMatrix[9] = {0}, distortionCoeffs[5] = {0};
+    fid_camera camera = {};     // CameraInfo as the library takes it: the distortion model with its coefficients
+    std::string camInfoError;   // why the last CameraInfo was refused (a distortion model the library does not pose under)
     bool haveCamInfo = false, enable_detections = true, doPoseEstimation = true, verbose = false;
     bool vis_msgs = false, publishFiducialTf = true, publish_images = false;
     bool haveMap = false;

@@ -88,12 +88,28 @@ class Stag {
     // Common::solvePnpSingle for the markers of the last detectMarkers() (stag_detect.cpp:140-165)
     std::vector<fid_stag_pose_out> solvePnpSingle(const double K[9], const double D[5], double marker_size)
     {
+        const fid_camera cam = plumbBob(K, D);
+        return solvePnpSingle(cam, marker_size);
+    }
+    // ... under any camera model the library knows (fid_camera)
+    std::vector<fid_stag_pose_out> solvePnpSingle(const fid_camera &cam, double marker_size)
+    {
         std::vector<fid_stag_pose_out> p(markers.empty() ? 1 : markers.size());
         int32_t n = 0;
-        const fid_status rc = fid_stag_pose_last(ctx, K, D, marker_size, p.data(), (int32_t)p.size(), &n);
+        const fid_status rc = fid_stag_pose_last_cam(ctx, &cam, marker_size, p.data(), (int32_t)p.size(), &n);
         if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_pose_last: ") + fid_strerror(rc));
         p.resize((size_t)n);
         return p;
+    }
+    // {FID_CAM_PLUMB_BOB, 5, K, D}
+    static fid_camera plumbBob(const double K[9], const double D[5])
+    {
+        fid_camera cam = {};
+        cam.model = FID_CAM_PLUMB_BOB;
+        cam.n_dist = 5;
+        for (int i = 0; i < 9; i++) cam.K[i] = K[i];
+        for (int i = 0; i < 5; i++) cam.D[i] = D ? D[i] : 0.0;
+        return cam;
     }
 
     // the node's `bundles` and `tags` (stag_nodelet.h:90-91) on the device; an empty list clears them
@@ -105,9 +121,14 @@ class Stag {
     // Common::solvePnpBundle (common.hpp:48-59) for the markers of the last detectMarkers(): one record per bundle that was seen
     std::vector<fid_stag_bundle_pose_out> solvePnpBundle(const double K[9], const double D[5])
     {
+        const fid_camera cam = plumbBob(K, D);
+        return solvePnpBundle(cam);
+    }
+    std::vector<fid_stag_bundle_pose_out> solvePnpBundle(const fid_camera &cam)
+    {
         std::vector<fid_stag_bundle_pose_out> p(FID_STAG_MAX_BUNDLES);
         int32_t n = 0;
-        const fid_status rc = fid_stag_bundle_pose_last(ctx, K, D, p.data(), (int32_t)p.size(), &n);
+        const fid_status rc = fid_stag_bundle_pose_last_cam(ctx, &cam, p.data(), (int32_t)p.size(), &n);
         if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_bundle_pose_last: ") + fid_strerror(rc));
         p.resize((size_t)n);
         return p;
@@ -162,14 +183,28 @@ inline void rotationToQuaternion(const double m[9], double q[4] /* x y z w */)
     for (int a = 0; a < 4; a++) q[a] = temp[a];
 }
 
+// CameraInfo -> fid_camera.  "plumb_bob" or no model name: D[0..4], zero where the message is shorter, as before the library knew
+// other models; any other name: fid_camera_from_info decides, and what it refuses throws with its message (never a plumb-bob pose
+// from a camera of another model)
+inline fid_camera stagCameraFromInfo(const CameraInfo &msg)
+{
+    if (msg.distortion_model.empty() || msg.distortion_model == "plumb_bob") {
+        double D[5] = {0, 0, 0, 0, 0};
+        for (size_t i = 0; i < msg.D.size() && i < 5; i++) D[i] = msg.D[i];
+        return Stag::plumbBob(msg.K.data(), D);
+    }
+    fid_camera cam = {};
+    if (fid_camera_from_info(msg.distortion_model.c_str(), msg.K.data(), msg.D.data(), (int32_t)msg.D.size(), &cam) != FID_OK)
+        throw std::runtime_error(fid_camera_last_error());
+    return cam;
+}
+
 // StagNode::imageCallback with the fiducial_msgs contract: vertices + transforms of one image
 inline void stagImageCallback(Stag &stag, const Image &msg, const CameraInfo &cam, double marker_size, FiducialArray *fva, FiducialTransformArray *fta)
 {
     stag.detectMarkers(msg.data.data(), (int)msg.width, (int)msg.height, (int)msg.step);
     const std::vector<Marker> markers = stag.getMarkerList();
-    double D[5] = {0, 0, 0, 0, 0};
-    for (size_t i = 0; i < cam.D.size() && i < 5; i++) D[i] = cam.D[i];
-    const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(cam.K.data(), D, marker_size);
+    const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(stagCameraFromInfo(cam), marker_size);
     fva->header.sec = fta->header.sec = msg.header.sec;
     fva->header.nsec = fta->header.nsec = msg.header.nsec;
     fva->header.frame_id = fta->header.frame_id = cam.header.frame_id;
@@ -264,8 +299,14 @@ class StagNode {
     void cameraInfoCallback(const CameraInfo &msg)
     {
         if (got_camera_info) return;
-        for (int i = 0; i < 9; i++) K[i] = msg.K[(size_t)i];
-        for (int i = 0; i < 5; i++) D[i] = (size_t)i < msg.D.size() ? msg.D[(size_t)i] : 0.0;
+        try {
+            camera = stagCameraFromInfo(msg);
+        } catch (const std::runtime_error &e) {  // a model the library does not pose under: as if no CameraInfo had come, said why
+            last_error = std::string("No camera intrinsics: ") + e.what();
+            return;
+        }
+        for (int i = 0; i < 9; i++) K[i] = camera.K[i];
+        for (int i = 0; i < 5; i++) D[i] = camera.model == FID_CAM_EQUIDISTANT ? 0.0 : camera.D[i];
         got_camera_info = true;
     }
 
@@ -338,7 +379,8 @@ class StagNode {
 
     Params params;
     bool got_camera_info = false;
-    double K[9] = {0}, D[5] = {0};
+    double K[9] = {0}, D[5] = {0};  // (the plumb-bob view of `camera`, for callers that read them)
+    fid_camera camera = {};
 
    private:
     bool publishCompressed(const Header &h, const uint8_t *raw, int32_t w, int32_t ht, const std::vector<fid_marker> &mk, CompressedImage *cimage)
@@ -474,11 +516,11 @@ class StagNode {
     void publishMarkers(const Header &header, Outputs *out)
     {
         const std::vector<Marker> markers = stag.getMarkerList();
-        const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(K, D, (double)params.marker_size);
+        const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(camera, (double)params.marker_size);
         // with a layout: a member of a multi-tag bundle is not published on its own; a standalone tag of `tags:` is, posed from its
         // own corners and under its own frame; ids the layout does not name keep the marker_size pose
         std::vector<fid_stag_bundle_pose_out> bposes;
-        if (!params.layout_tags.empty()) bposes = stag.solvePnpBundle(K, D);
+        if (!params.layout_tags.empty()) bposes = stag.solvePnpBundle(camera);
         auto bundleOf = [this](int id) {  // getTagIndex / getBundleIndex (stag_nodelet.h:59-60)
             for (const fid_stag_tag &t : params.layout_tags)
                 if (t.id == id) return (int)t.bundle;

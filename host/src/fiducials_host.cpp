@@ -290,8 +290,20 @@ void FiducialsNode::camInfoCallback(const CameraInfo &msg)
     bool all_zero = true;
     for (double v : msg.K) all_zero = all_zero && v == 0.0;
     if (all_zero) return;  // "CameraInfo message has invalid intrinsics, K matrix all zeros"
-    for (int i = 0; i < 9; i++) cameraMatrix[i] = msg.K[i];
-    for (int i = 0; i < 5; i++) distortionCoeffs[i] = msg.D.at(i);  // (the node indexes D[0..4] unchecked)
+    fid_camera cam = {};
+    if (msg.distortion_model.empty() || msg.distortion_model == "plumb_bob") {
+        cam.model = FID_CAM_PLUMB_BOB;
+        cam.n_dist = 5;
+        for (int i = 0; i < 9; i++) cam.K[i] = msg.K[i];
+        for (int i = 0; i < 5; i++) cam.D[i] = msg.D.at(i);  // (the node indexes D[0..4] unchecked)
+    } else if (fid_camera_from_info(msg.distortion_model.c_str(), msg.K.data(), msg.D.data(), (int32_t)msg.D.size(), &cam) != FID_OK) {
+        // a model the library does not pose under (a tilted sensor, an omnidirectional camera): no intrinsics, said why -- never a
+        // plumb-bob pose from such a camera.  Vertices go on being published; the next CameraInfo is looked at again.
+        camInfoError = fid_camera_last_error();
+        return;
+    }
+    camera = cam;
+    camInfoError.clear();
     haveCamInfo = true;
     frameId = msg.header.frame_id;
 }
@@ -574,7 +586,7 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
     frameNum++;
     if (doPoseEstimation) {
         if (!haveCamInfo) {
-            if (frameNum > 5) last_error = "No camera intrinsics";
+            if (frameNum > 5) last_error = camInfoError.empty() ? "No camera intrinsics" : "No camera intrinsics: " + camInfoError;
             return false;
         }
         const int n = (int)ids.size();
@@ -584,7 +596,7 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
             if (it != fiducialLens.end()) lens[i] = it->second;
         }
         std::vector<fid_pose_out> poses(n > 0 ? n : 1);
-        const fid_status rc = fid_pose(ctx, cameraMatrix, distortionCoeffs, markers.data(), lens.data(), n, fiducial_len, poses.data());
+        const fid_status rc = fid_pose_cam(ctx, &camera, markers.data(), lens.data(), n, fiducial_len, poses.data());
         if (rc != FID_OK) {
             last_error = fid_last_error(ctx);
             return false;
@@ -634,12 +646,12 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
             fid_map_pose_out mp;
             fid_status mrc;
             if (ignoreIds.empty()) {
-                mrc = fid_map_pose_last(ctx, cameraMatrix, distortionCoeffs, &mp, 1);
+                mrc = fid_map_pose_last_cam(ctx, &camera, &mp, 1);
             } else {
                 std::vector<fid_marker> kept;
                 for (int i = 0; i < n; i++)
                     if (std::count(ignoreIds.begin(), ignoreIds.end(), ids[i]) == 0) kept.push_back(markers[(size_t)i]);
-                mrc = fid_map_pose(ctx, cameraMatrix, distortionCoeffs, kept.data(), (int32_t)kept.size(), &mp);
+                mrc = fid_map_pose_cam(ctx, &camera, kept.data(), (int32_t)kept.size(), &mp);
             }
             if (mrc != FID_OK) {
                 last_error = fid_last_error(ctx);

@@ -49,7 +49,9 @@ extern "C" {
  * device's first kernel, so what crosses PCIe is the message's own bytes; + fid_encoding_from_string (round 6).  Added under 7
  * (entry points only): fid_stag_detect_markers_device, fid_stag_detect_markers_batch_device, FID_STAG_TAP_GRAY; the tag bundle
  * family (fid_stag_tag, fid_stag_layout_load_file, fid_stag_set_layout, fid_stag_bundle_pose*, fid_stag_detect_bundles_batch*); the
- * fiducial map family (fid_map_entry, fid_map_load_file, fid_map_entry_from_rpy, fid_set_map, fid_map_pose_last, fid_map_pose). */
+ * fiducial map family (fid_map_entry, fid_map_load_file, fid_map_entry_from_rpy, fid_set_map, fid_map_pose_last, fid_map_pose); the
+ * camera model family (fid_camera, fid_camera_from_info, a <name>_cam twin of every entry point that takes K[9], D[5],
+ * fid_project_points_cam). */
 #define FID_ABI_VERSION 7
 
 typedef enum fid_status {
@@ -263,6 +265,59 @@ typedef struct fid_map_pose_out {
 fid_status fid_map_pose_last(fid_ctx *ctx, const double K[9], const double D[5], fid_map_pose_out *out, int32_t cap_frames);
 /* the same kernel on n markers of one frame handed in from host memory; the last detect call's results stay as they are */
 fid_status fid_map_pose(fid_ctx *ctx, const double K[9], const double D[5], const fid_marker *markers, int32_t n, fid_map_pose_out *out);
+
+/* ---- the camera as a value (additions to ABI 7: entry points and structs only).  K[9], D[5] is sensor_msgs/CameraInfo with
+ * distortion_model "plumb_bob"; camera drivers also publish "rational_polynomial" (eight coefficients, twelve with the thin prism)
+ * and "equidistant" (four fisheye coefficients).  A fid_camera carries the model with its coefficients, and every entry point that
+ * takes `const double K[9], const double D[5]` has a twin <name>_cam that takes `const fid_camera *cam` in their place and is
+ * otherwise the same call.  The entry points without _cam ARE their twins with {FID_CAM_PLUMB_BOB, 5, K, D}.
+ *   FID_CAM_PLUMB_BOB    D = k1 k2 p1 p2 k3: cvProjectPoints2 / cvUndistortPoints as before
+ *   FID_CAM_RATIONAL     D = k1 k2 p1 p2 k3 k4 k5 k6 [s1 s2 s3 s4]: OpenCV 4.2's cvProjectPoints2Internal and
+ *                        cvUndistortPointsInternal (five iterations) with the denominator 1 + k4 r2 + k5 r4 + k6 r6 and the thin
+ *                        prism terms; with k4..k6 and s1..s4 zero the results are those of FID_CAM_PLUMB_BOB bit for bit
+ *   FID_CAM_EQUIDISTANT  D = k1 k2 k3 k4, the cv::fisheye model.  No OpenCV call does PnP in it, so its meaning is fixed here.
+ *                        Projection: a = x / z, b = y / z, r = |(a, b)|, theta = atan r, theta_d = theta (1 + k1 theta^2 + k2 theta^4
+ *                        + k3 theta^6 + k4 theta^8), (u, v) = (fx a, fy b) theta_d / r + (cx, cy) (scale 1 where r <= 1e-8; no skew).
+ *                        Undistortion: theta_d = |((u - cx) / fx, (v - cy) / fy)|, theta by Newton from theta_d, at most 10 steps,
+ *                        until |step| < 1e-8; the normalised point is the distorted one times tan(theta) / theta_d.  The start is
+ *                        the closed form on the undistorted points, then CvLevMarq on the pixel residuals of the fisheye
+ *                        projection with its analytic Jacobian.
+ *                        A MARKER THAT CANNOT BE POSED: where Newton does not converge or a corner lies at theta >= 89 degrees
+ *                        (the pinhole normalisation the solver works in ends at 90), the record has rvec = tvec = 0 (and R = 0
+ *                        where the record has one) and, where it has an image_error, image_error = -1; object_error is 0,
+ *                        fiducial_area, id, n_markers, n_tags and bundle are what they always are.  For fid_map_pose* and
+ *                        fid_stag_bundle_pose* one such point voids the frame's / the bundle's record.  The other two models
+ *                        never produce this record. */
+typedef enum fid_camera_model { FID_CAM_PLUMB_BOB = 0, FID_CAM_RATIONAL = 1, FID_CAM_EQUIDISTANT = 2 } fid_camera_model;
+typedef struct fid_camera {
+    int32_t model;  /* fid_camera_model */
+    int32_t n_dist; /* coefficients given: 4 or 5 (plumb-bob), 8 or 12 (rational), 4 (equidistant) */
+    double K[9];    /* row-major 3x3 */
+    double D[12];   /* D beyond n_dist is zero */
+} fid_camera;
+/* sensor_msgs/CameraInfo -> fid_camera.  Host code, no device.
+ *   "plumb_bob" or ""                    n_D 4 or 5   FID_CAM_PLUMB_BOB (k3 = 0 when n_D is 4)
+ *   "rational_polynomial"                n_D 8        FID_CAM_RATIONAL: k1 k2 p1 p2 k3 k4 k5 k6
+ *   "rational_polynomial"                n_D 12       FID_CAM_RATIONAL with the thin prism s1 s2 s3 s4
+ *   "rational_polynomial"                n_D 14       as 12 when taux = tauy = 0, else FID_E_UNSUPPORTED (tilted sensor)
+ *   "equidistant" or "fisheye"           n_D 4        FID_CAM_EQUIDISTANT: k1..k4
+ *   any other string or count                         FID_E_UNSUPPORTED; fid_camera_last_error() names what was given
+ * FID_E_INVALID_ARG: a NULL pointer, fx or fy zero, a value of K or D that is not finite. */
+fid_status fid_camera_from_info(const char *distortion_model, const double K[9], const double *D, int32_t n_D, fid_camera *out);
+const char *fid_camera_last_error(void); /* of the calling thread */
+
+/* the _cam twins of the aruco entry points (FID_E_INVALID_ARG for cam == NULL, a model outside the enum, n_dist outside 0..12).
+ * fid_pose_last_cam / fid_map_pose_last_cam remember the whole fid_camera, model included: the next fid_detect* / fid_submit* runs
+ * the kernel of that model for it in its own stream. */
+fid_status fid_pose_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                        double fiducial_len, fid_pose_out *out);
+fid_status fid_pose_last_cam(fid_ctx *ctx, const fid_camera *cam, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame);
+fid_status fid_map_pose_last_cam(fid_ctx *ctx, const fid_camera *cam, fid_map_pose_out *out, int32_t cap_frames);
+fid_status fid_map_pose_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, int32_t n, fid_map_pose_out *out);
+/* cv::projectPoints (what getReprojectionError calls, aruco_detect.cpp:211) for n object points, with d(u, v) / d(rvec, tvec): the
+ * device library's projection run as a small kernel.  uv: n x 2.  jac may be NULL; else n x 2 x 6, row-major (d/d rvec, d/d tvec). */
+fid_status fid_project_points_cam(fid_ctx *ctx, const fid_camera *cam, const double rvec[3], const double tvec[3],
+                                  const double *obj_xyz, int32_t n, double *uv, double *jac);
 
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
@@ -535,6 +590,30 @@ fid_status fid_stag_detect_bundles_batch_device(fid_stag_ctx *const *ctxs, int32
                                                 const double K[9], const double D[5], double marker_size, fid_stag_marker *markers,
                                                 fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
                                                 fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
+
+/* the _cam twins of the STag entry points (fid_camera: "the camera as a value", above); cam == NULL where K == NULL is allowed */
+fid_status fid_stag_pose_last_cam(fid_stag_ctx *ctx, const fid_camera *cam, double marker_size, fid_stag_pose_out *out, int32_t cap,
+                                  int32_t *n_out);
+fid_status fid_stag_detect_markers_batch_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width,
+                                             int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, const fid_camera *cam,
+                                             double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                             int32_t *n_per_frame);
+fid_status fid_stag_detect_markers_batch_device_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                    int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, fid_encoding enc,
+                                                    const fid_camera *cam, double marker_size, fid_stag_marker *markers,
+                                                    fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame);
+fid_status fid_stag_bundle_pose_last_cam(fid_stag_ctx *ctx, const fid_camera *cam, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out);
+fid_status fid_stag_bundle_pose_cam(fid_stag_ctx *ctx, const fid_camera *cam, const fid_stag_marker *markers, int32_t n,
+                                    fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out);
+fid_status fid_stag_detect_bundles_batch_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const uint8_t *frames, int32_t nframes, int32_t width,
+                                             int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, const fid_camera *cam,
+                                             double marker_size, fid_stag_marker *markers, fid_stag_pose_out *poses, int32_t cap_per_frame,
+                                             int32_t *n_per_frame, fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
+fid_status fid_stag_detect_bundles_batch_device_cam(fid_stag_ctx *const *ctxs, int32_t nctx, const void *d_frames, int32_t nframes, int32_t width,
+                                                    int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes, fid_encoding enc,
+                                                    const fid_camera *cam, double marker_size, fid_stag_marker *markers,
+                                                    fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
+                                                    fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * JPEG ingest.  With the launch file's default `transport:=compressed` (aruco_detect/launch/aruco_detect.launch:6) the frames
