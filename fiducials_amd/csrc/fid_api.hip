@@ -115,6 +115,7 @@ struct fid_ctx {
     int resolve_serial = 0;    // FID_RESOLVE_SERIAL=1: k_resolve's single-wave path even when the near triangle fits LDS (tests)
     int resolve_reg_max = 64;  // FID_RESOLVE_REG_MAX: components of up to so many candidates are resolved in registers (0: none; tests)
     int seed_shift = 0;        // FID_SEED_SHIFT: force the seed grid spacing 8 << shift (0 = by call size)
+    int seed_kernel = 0;       // FID_SEED_KERNEL=split|fused: k_find_starts<false> + k_find_seeds, or k_find_starts<true> (0 = by the seed grid)
     uint4 *d_contours = nullptr;
     uint32_t *d_ckpts = nullptr;
     size_t ckpts_elems = 0;
@@ -658,6 +659,9 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         mark(ST_THRESH + 1);
       }
         // ---- K2
+        // the tracing seeds: on the 128 px grid of batches few word columns and rows hold any, and a kernel of their own finds them
+        // (split); on the denser grids of small calls every word column or every second one is a grid column: k_find_starts<true>
+        const bool split_seeds = c->seed_kernel ? c->seed_kernel == 1 : P.seedShift >= 4;
         long long k2blocks;
         {
             long long groups = (long long)P.nscales * P.TR * ((P.WW + 15) / 16);  // two groups per wave and iteration
@@ -669,9 +673,22 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         // queued before any walk, and (fs_barrier) the walks of all sub-batches wait for the last find_starts -- beside another
         // sub-batch's seed walk and probes a find_starts took 2.5 ms for 92 frames, beside another find_starts 1.1 ms for 164
         if (!c->whole_border_walk) {
-            hipLaunchKernelGGL(k_find_starts<true>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
-                               c->d_seedq + f0 * (size_t)P.maxContours, P);
-            mark(ST_STARTS + 1);
+            uint2 *seedq = c->d_seedq + f0 * (size_t)P.maxContours;
+            if (split_seeds) {
+                // the seeds come from a kernel of their own that only visits the grid lines (k_find_seeds), directly behind the
+                // start search on the same stream.  (On the sub-batch's auxiliary stream, beside k_find_starts<false> and joined
+                // in front of the seed walk by two events, it measured 0.2 - 0.5 % slower: profiles/r10_seed_split_ab.txt.)
+                const SeedUnits su = seed_units(P);
+                // (a wave per unit: a batch gives a frame 32 workgroups, a call of a few frames a workgroup for every four units)
+                const int smax = Fs >= 16 ? 32 : 512, sblocks = (su.n + 3) / 4 < smax ? (su.n + 3) / 4 : smax;
+                hipLaunchKernelGGL(k_find_starts<false>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
+                                   (uint2 *)nullptr, P);
+                mark(ST_STARTS + 1);
+                hipLaunchKernelGGL(k_find_seeds, dim3(sblocks, Fs), dim3(256), 0, st, masks, counts, c->d_global, seedq, P);
+            } else {
+                hipLaunchKernelGGL(k_find_starts<true>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global, seedq, P);
+                mark(ST_STARTS + 1);
+            }
             if (nsub > 1) HIPCHK(c, hipEventRecord(c->fs_done[sb], st));
             chain_point(0);
         }
@@ -1132,6 +1149,7 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     if (getenv("FID_SUB_FRAMES")) c->sub_frames = atoi(getenv("FID_SUB_FRAMES"));
     if (getenv("FID_WALK_CAP")) c->walk_blocks_cap = atoi(getenv("FID_WALK_CAP"));
     if (getenv("FID_SEED_SHIFT")) c->seed_shift = atoi(getenv("FID_SEED_SHIFT"));
+    if (const char *e = getenv("FID_SEED_KERNEL")) c->seed_kernel = !strcmp(e, "split") ? 1 : (!strcmp(e, "fused") ? 2 : 0);
     if (getenv("FID_RESOLVE_SERIAL")) c->resolve_serial = atoi(getenv("FID_RESOLVE_SERIAL"));
     if (getenv("FID_RESOLVE_REG_MAX")) {
         const int v = atoi(getenv("FID_RESOLVE_REG_MAX"));

@@ -1270,6 +1270,179 @@ __global__ __launch_bounds__(256) void k_find_starts(const uint32_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// K2b: the tracing seeds alone, for the launch sequence that runs k_find_starts<false> in front of it.  The seeds exist on the grid
+// lines only, so this kernel visits nothing else; inside k_find_starts<true> the same tests are predicated per lane on items that
+// are anywhere in the mask.  The rule is the one of the HYB blocks above (and of seed_state() / seed_empty_dir()):
+//   grid row    (y & gm) == 0: every pixel, the six directions of SEED_DIRS_ROW, a seed where cur & nbp[dd] & ~nbp[seed_empty_dir(dd)]
+//   grid column (x & gm) == 0: pixel 0 of the word, the directions of SEED_DIRS_COL (without those of SEED_DIRS_ROW on a pixel
+//               that is on a grid row as well) from the neighbour byte n8 and its rotation e8
+// and the list is the same set of records in another (equally undefined) order.
+// A wave takes one UNIT per workgroup iteration, and a unit is all rows or all columns, so no wave mixes the two tests:
+//   row unit    (scale, grid row, 64 words of it): a lane per word.  A grid row is a multiple of 32, so with the row above and the
+//               row below it is rows 0 - 2 of ONE mask tile: one 16-byte load per word column (its own, the left, the right one)
+//   column unit (scale, grid column, 64 quads of four rows): a lane per quad, one 16-byte load of the word column and, where a
+//               pixel 0 is set, of the one left of it, plus single words for the rows above and below the quad
+struct SeedUnits {
+    int nrows, ncols, nwc, nqc, nquads, urow, n;  // grid rows / columns per plane, 64-lane chunks of a row / a column, row units, all units
+};
+__host__ __device__ inline SeedUnits seed_units(const DevParams &P)
+{
+    SeedUnits u;
+    const int gm = (8 << P.seedShift) - 1, wsh = P.seedShift - 2;  // (a grid column every 1 << wsh words: seedShift >= SEED_SHIFT_MIN)
+    u.nrows = (P.H + gm) >> (P.seedShift + 3);       // rows 0, G, 2 G, ... < H
+    u.ncols = (P.WW + (1 << wsh) - 1) >> wsh;        // words 0, G / 32, ... < WW
+    u.nquads = P.H / 4 + 1;                          // padded rows 4 q .. 4 q + 3 = image rows 4 q - 1 .. 4 q + 2, the last one holds row H - 1
+    u.nwc = (P.WW + 63) >> 6;
+    u.nqc = (u.nquads + 63) >> 6;
+    u.urow = P.nscales * u.nrows * u.nwc;
+    u.n = u.urow + P.nscales * u.ncols * u.nqc;      // < 2^22 for every supported size (divmod_small)
+    return u;
+}
+__global__ __launch_bounds__(256) void k_find_seeds(const uint32_t *__restrict__ masks, DevCounts *__restrict__ counts,
+                                                     DevGlobal *__restrict__ G, uint2 *__restrict__ seedq, const DevParams P)
+{
+    __shared__ int s_wsum[4];
+    __shared__ unsigned s_base;
+    const int lane = lane_id(), wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int f = blockIdx.y;
+    const int WW = P.WW, TC = P.TC, H = P.H;
+    const SeedUnits U = seed_units(P);
+    const float rcp_nwc = 1.0f / (float)U.nwc, rcp_nqc = 1.0f / (float)U.nqc, rcp_nrows = 1.0f / (float)U.nrows, rcp_ncols = 1.0f / (float)U.ncols;
+    const long long plane = (long long)P.TR * TC * MT_ROWS;
+    const unsigned scap = (unsigned)P.maxContours;
+    const int gm = (8 << P.seedShift) - 1;
+    const uint32_t *fmasks = masks + (long long)f * P.nscales * plane;
+    uint2 *fsq = seedq + (long long)f * P.maxContours;
+    for (int i0 = (int)blockIdx.x * 4; i0 < U.n; i0 += (int)gridDim.x * 4) {
+        const int unit = i0 + wid;  // wave-uniform
+        uint32_t rowm[6] = {0, 0, 0, 0, 0, 0}, colb = 0;  // a row item's six directions x 32 pixels; a column item's four rows x 8 directions
+        int cnt = 0, x0 = 0, y0 = 0, sc = 0;
+        const bool is_row = unit < U.urow;
+        if (is_row) {
+            unsigned a, wc, s, j;
+            divmod_small((unsigned)unit, (unsigned)U.nwc, rcp_nwc, a, wc);  // unit = (s * nrows + j) * nwc + wc
+            divmod_small(a, (unsigned)U.nrows, rcp_nrows, s, j);
+            sc = __builtin_amdgcn_readfirstlane((int)s);
+            y0 = __builtin_amdgcn_readfirstlane((int)j) << (P.seedShift + 3);
+            const int w = __builtin_amdgcn_readfirstlane((int)wc) * 64 + lane;
+            x0 = w * 32;
+            if (w < WW) {
+                // padded rows y0, y0 + 1, y0 + 2 (the row above, the grid row, the row below) = rows 0, 1, 2 of the tile
+                const uint32_t *tile = fmasks + (long long)sc * plane + ((long long)(y0 >> 4) * TC + MASK_PADW + w) * MT_ROWS;
+                const uint4 c4 = *reinterpret_cast<const uint4 *>(tile);
+                const uint32_t cur = c4.y;
+                if (cur) {
+                    const uint4 p4 = *reinterpret_cast<const uint4 *>(tile - MT_ROWS);
+                    const uint4 n4 = *reinterpret_cast<const uint4 *>(tile + MT_ROWS);
+                    const uint32_t u = c4.x, d = c4.z;
+                    const uint32_t Wst = (cur << 1) | (p4.y >> 31), Est = (cur >> 1) | (n4.y << 31);
+                    const uint32_t NW = (u << 1) | (p4.x >> 31), NE = (u >> 1) | (n4.x << 31);
+                    const uint32_t SWst = (d << 1) | (p4.z >> 31), SEst = (d >> 1) | (n4.z << 31);
+                    const uint32_t nbp[8] = {Est, NE, u, NW, Wst, SWst, d, SEst};  // neighbour planes by direction
+                    int ri = 0;
+#pragma unroll
+                    for (int dd = 0; dd < 8; dd++) {
+                        if (!((SEED_DIRS_ROW >> dd) & 1u)) continue;
+                        const uint32_t m = cur & nbp[dd] & ~nbp[seed_empty_dir(dd)];
+                        rowm[ri++] = m;
+                        cnt += __popc(m);
+                    }
+                }
+            }
+        } else if (unit < U.n) {
+            unsigned a, qc, s, ci;
+            divmod_small((unsigned)(unit - U.urow), (unsigned)U.nqc, rcp_nqc, a, qc);  // unit - urow = (s * ncols + ci) * nqc + qc
+            divmod_small(a, (unsigned)U.ncols, rcp_ncols, s, ci);
+            sc = __builtin_amdgcn_readfirstlane((int)s);
+            const int w = __builtin_amdgcn_readfirstlane((int)ci) << (P.seedShift - 2);
+            const int q = __builtin_amdgcn_readfirstlane((int)qc) * 64 + lane;
+            x0 = w * 32;
+            y0 = q * 4;  // padded row of the quad's first row; image row = padded row - 1
+            if (q < U.nquads) {
+                const uint32_t *pl = fmasks + (long long)sc * plane;
+                const uint32_t *tile = pl + mask_word(TC, y0, MASK_PADW + w);
+                const uint4 c4 = *reinterpret_cast<const uint4 *>(tile);
+                if ((c4.x | c4.y | c4.z | c4.w) & 1u) {
+                    const uint4 p4 = *reinterpret_cast<const uint4 *>(tile - MT_ROWS);
+                    uint32_t upc = 0, upp = 0;
+                    if (y0 > 0) {
+                        const uint32_t *qq = pl + mask_word(TC, y0 - 1, MASK_PADW + w);
+                        upc = qq[0];
+                        upp = qq[-MT_ROWS];
+                    }
+                    const uint32_t *qq = pl + mask_word(TC, y0 + 4, MASK_PADW + w);  // exists: TR has a spare tile row
+                    const uint32_t cc[6] = {upc, c4.x, c4.y, c4.z, c4.w, qq[0]};
+                    const uint32_t pp[6] = {upp, p4.x, p4.y, p4.z, p4.w, qq[-MT_ROWS]};
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int y = y0 + k - 1;
+                        if (y < 0 || y >= H) continue;
+                        const uint32_t cur = cc[k + 1], u = cc[k], d = cc[k + 2];
+                        // bit 0 of the eight neighbour planes as one byte (bit dd = neighbour in direction dd: E NE N NW W SW S SE),
+                        // the "must be empty" neighbours the same byte rotated by seed_empty_dir (odd directions + 1, even ones + 2)
+                        uint32_t n8 = (cur >> 1) & 1u;            // E
+                        n8 |= u & 2u;                             // NE = pixel 1 of the row above
+                        n8 |= (u & 1u) << 2;                      // N
+                        n8 |= (pp[k] >> 31) << 3;                 // NW
+                        n8 |= (pp[k + 1] >> 31) << 4;             // W
+                        n8 |= (pp[k + 2] >> 31) << 5;             // SW
+                        n8 |= (d & 3u) << 6;                      // S, SE = pixels 0, 1 of the row below
+                        const uint32_t x16 = n8 | (n8 << 8);
+                        const uint32_t e8 = ((x16 >> 1) & 0xAAu) | ((x16 >> 2) & 0x55u);
+                        // (the diagonal directions of a pixel that is on both lines belong to the row)
+                        const uint32_t allowed = (y & gm) == 0 ? (SEED_DIRS_COL & ~SEED_DIRS_ROW) : SEED_DIRS_COL;
+                        const uint32_t s8 = (cur & 1u) ? (n8 & ~e8 & allowed) : 0u;
+                        colb |= s8 << (k * 8);
+                    }
+                    cnt = __popc(colb);
+                }
+            }
+        }
+        // ---- list slots: one atomic per workgroup iteration
+        const int incl = wave_iscan(cnt);
+        if (lane == 63) s_wsum[wid] = incl;
+        __syncthreads();
+        int wbase = 0, tot = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int v = s_wsum[k];
+            if (k < wid) wbase += v;
+            tot += v;
+        }
+        if (threadIdx.x == 0 && tot) s_base = atomicAdd((unsigned *)&counts[f].nseeds, (unsigned)tot);
+        __syncthreads();
+        if (tot) {
+            unsigned off = s_base + (unsigned)(wbase + incl - cnt);
+            auto emit = [&](int x, int y, int dd) {
+                if (off < scap) fsq[off] = make_uint2((uint32_t)x | ((uint32_t)y << 13) | ((uint32_t)sc << 27), (uint32_t)dd);
+                off++;
+            };
+            if (is_row) {
+                int ri = 0;
+#pragma unroll
+                for (int dd = 0; dd < 8; dd++) {
+                    if (!((SEED_DIRS_ROW >> dd) & 1u)) continue;
+                    uint32_t m = rowm[ri++];
+                    while (m) {
+                        const int b = __ffs(m) - 1;
+                        m &= m - 1;
+                        emit(x0 + b, y0, dd);
+                    }
+                }
+            } else {
+                while (colb) {
+                    const int b = __ffs(colb) - 1;
+                    colb &= colb - 1;
+                    emit(x0, y0 + (b >> 3) - 1, b & 7);
+                }
+            }
+            if (threadIdx.x == 0 && s_base + (unsigned)tot > scap) atomicOr(&G->overflow, 2u);
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Border following on the bit-packed padded mask.
 // Directions (contours.cpp icvCodeDeltas): 0 E, 1 NE, 2 N, 3 NW, 4 W, 5 SW, 6 S, 7 SE.
 
