@@ -103,6 +103,9 @@ def encoding_value(encoding: str, is_bigendian: bool = False) -> int:
 
 
 CAM_PLUMB_BOB, CAM_RATIONAL, CAM_EQUIDISTANT = 0, 1, 2  # fid_camera_model
+# fid_pose_cov / fid_map_pose_cov as numpy records (status 0: valid, 1: no pose, 2: J^T J not positive definite; cov_pose in
+# geometry_msgs/PoseWithCovariance order)
+POSE_COV_FIELDS = [("status", "<i4"), ("n_points", "<i4"), ("sigma2", "<f8"), ("cov_rt", "<f8", (6, 6)), ("cov_pose", "<f8", (6, 6))]
 MAP_MAX_ENTRIES, MAP_MAX_USED = 4096, 256  # FID_MAP_MAX_ENTRIES, FID_MAP_MAX_USED
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
@@ -117,6 +120,8 @@ SYMBOLS = [
     "fid_camera_from_info", "fid_camera_last_error", "fid_pose_cam", "fid_pose_last_cam", "fid_map_pose_last_cam", "fid_map_pose_cam", "fid_project_points_cam",
     "fid_stag_pose_last_cam", "fid_stag_detect_markers_batch_cam", "fid_stag_detect_markers_batch_device_cam", "fid_stag_bundle_pose_last_cam",
     "fid_stag_bundle_pose_cam", "fid_stag_detect_bundles_batch_cam", "fid_stag_detect_bundles_batch_device_cam",
+    "fid_pose_cov_cam", "fid_pose_last_cov_cam", "fid_map_pose_last_cov_cam", "fid_map_pose_cov_cam",
+    "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
     "fid_png_probe", "fid_png_decode", "fid_png_last_error",
@@ -295,6 +300,15 @@ def load():
         L.fid_stag_bundle_pose_cam.argtypes = [vp, cam, vp, i32, vp, i32, C.POINTER(i32)]
         L.fid_stag_detect_bundles_batch_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, cam, C.c_double, vp, vp, i32, vp, vp, vp]
         L.fid_stag_detect_bundles_batch_device_cam.argtypes = [vp, i32, vp, i32, i32, i32, i32, i64, C.c_int, cam, C.c_double, vp, vp, i32, vp, vp, vp]
+    if hasattr(L, "fid_pose_cov_cam"):  # (the pose covariance; FID_LIB may name a build from before it)
+        cam = C.POINTER(FidCamera)
+        L.fid_pose_cov_cam.argtypes = [vp, cam, C.POINTER(FidMarker), C.POINTER(C.c_double), i32, C.c_double, C.POINTER(FidPoseOut), C.c_double, vp]
+        L.fid_pose_last_cov_cam.argtypes = [vp, cam, C.c_double, C.POINTER(FidPoseOut), i32, C.c_double, vp]
+        L.fid_map_pose_last_cov_cam.argtypes = [vp, cam, vp, i32, C.c_double, vp]
+        L.fid_map_pose_cov_cam.argtypes = [vp, cam, vp, i32, vp, C.c_double, vp]
+        L.fid_stag_pose_last_cov_cam.argtypes = [vp, cam, C.c_double, vp, i32, C.POINTER(i32), C.c_double, vp]
+        L.fid_stag_bundle_pose_last_cov_cam.argtypes = [vp, cam, vp, i32, C.POINTER(i32), C.c_double, vp]
+        L.fid_stag_bundle_pose_cov_cam.argtypes = [vp, cam, vp, i32, vp, i32, C.POINTER(i32), C.c_double, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

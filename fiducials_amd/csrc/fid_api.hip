@@ -156,6 +156,16 @@ struct fid_ctx {
     bool pose_cam_valid = false, pose_done = false;
     fid_camera pose_cam = {};  // (normalised: D beyond n_dist zero; the model is part of "the same camera")
     double pose_len = 0.;
+    // the pose covariance (fid_pose_last_cov_cam; nothing of it exists until the first _cov call): whether the remembered camera's
+    // pose was asked for with its covariance and at which sigma_px -- the next fid_detect_* then runs k_pose_cov behind k_pose --,
+    // a fid_pose_cov beside every fid_pose_out of the context's largest call, on the device only (a _cov call copies out what the
+    // frames' counts need), and whether the poses at hand came with it
+    bool pose_cov = false, pose_cov_done = false;
+    double pose_sigma = 0.;
+    fid_pose_cov *d_pcov = nullptr;
+    size_t pcov_cap = 0;
+    fid_pose_cov *d_pcov_in = nullptr;  // fid_pose_cov_cam's, beside d_pose_in
+    int pcov_in_cap = 0;
     // the map of fiducials (fid_set_map; nothing of it exists until the first one is set): its ids ascending, per entry the four
     // object points in the map frame; a fid_map_pose_out per frame of a batch and one more for fid_map_pose, on the device and in
     // pinned host memory; room for markers handed in from the host.  map_cam_* / map_done: as pose_cam_* / pose_done, for k_map_pose
@@ -167,6 +177,10 @@ struct fid_ctx {
     int map_in_cap = 0;
     bool map_cam_valid = false, map_done = false;
     fid_camera map_cam = {};
+    // as pose_cov / pose_sigma / d_pcov, for k_map_pose_cov: max_batch + 1 records like d_mposes, allocated by the first _cov call
+    bool map_cov = false, map_cov_done = false;
+    double map_sigma = 0.;
+    fid_map_pose_cov *d_mcov = nullptr, *h_mcov = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -180,7 +194,8 @@ struct fid_ctx {
 
 // k_map_pose for F frames on a stream (fid_map_pose.hip, at the end of this translation unit)
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
-                            const fid_camera &camera, fid_map_pose_out *d_out);
+                            const fid_camera &camera, fid_map_pose_out *d_out, bool with_cov = false, double sigma_px = 0.,
+                            fid_map_pose_cov *d_cov = nullptr);
 
 namespace {
 
@@ -883,6 +898,11 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers,
                                                             (const int *)&counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)),
                                                             (const double *)nullptr, Fs, P.maxMarkers, cam, c->d_poses + f0 * MM));
+            if (c->pose_cov)  // (fid_pose_last_cov_cam was the last to ask: the covariance of these poses, behind them)
+                POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose_cov<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers,
+                                                                (const int *)&counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)),
+                                                                (const double *)nullptr, Fs, P.maxMarkers, cam,
+                                                                (const fid_pose_out *)(c->d_poses + f0 * MM), c->pose_sigma, c->d_pcov + f0 * MM));
             if (c->profile) (void)hipEventRecord(ev[19], st);
         }
         chain_point(99);
@@ -915,14 +935,18 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     // ---- results
     c->pose_done = false;
     c->map_done = false;
+    c->pose_cov_done = false;
+    c->map_cov_done = false;
     const bool map_ahead = c->map_n > 0 && c->map_cam_valid;
     if (map_ahead) {
         // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
-        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_cam, c->d_mposes);
+        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_cam, c->d_mposes,
+                        c->map_cov, c->map_sigma, c->d_mcov);
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_cam_valid ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
     if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
+    if (map_ahead && c->map_cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st));
     c->last_frames = F;
     c->last_W = W;
     c->last_H = H;
@@ -948,6 +972,8 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->pose_done = c->pose_cam_valid;
     c->map_done = c->map_n > 0 && c->map_cam_valid;
+    c->pose_cov_done = c->pose_done && c->pose_cov;
+    c->map_cov_done = c->map_done && c->map_cov;
     if (c->profile) {
         // a stage's time = its event-bracketed time on its own stream, summed over the sub-batches (with more than
         // one sub-batch the brackets of different streams overlap in wall time)
@@ -1307,10 +1333,10 @@ void fid_destroy(fid_ctx *c)
     void *dev[] = {c->d_in, c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
                    c->d_ident, c->d_bits, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
                    c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n,
-                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in};
+                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in, c->d_pcov, c->d_pcov_in, c->d_mcov};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {c->h_res, c->h_mposes};
+    void *host[] = {c->h_res, c->h_mposes, c->h_mcov};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     for (int i = 0; i <= ST_COUNT; i++)
@@ -1587,7 +1613,8 @@ fid_status fid_detect(fid_ctx *c, const uint8_t *img, int32_t width, int32_t hei
 }
 
 static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d_n, int n_stride_ints, const double *d_lens,
-                           int F, int per_frame, const fid_camera &camera, double fiducial_len, fid_pose_out *d_out)
+                           int F, int per_frame, const fid_camera &camera, double fiducial_len, fid_pose_out *d_out, bool with_cov = false,
+                           double sigma_px = 0., fid_pose_cov *d_cov = nullptr)
 {
     const PoseCam cam = pose_cam_from(camera, fiducial_len);
     int total = F * per_frame;
@@ -1597,6 +1624,9 @@ static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d
     if (c->profile) (void)hipEventRecord(c->ev[ST_POSE], c->stream);
     POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens, F,
                                                     per_frame, cam, d_out));
+    if (with_cov)
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose_cov<CAM_MODEL>, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens,
+                                                        F, per_frame, cam, (const fid_pose_out *)d_out, sigma_px, d_cov));
     if (c->profile) (void)hipEventRecord(c->ev[ST_POSE + 1], c->stream);
     HIPCHK(c, hipGetLastError());
     return FID_OK;
@@ -1610,9 +1640,25 @@ fid_status fid_pose_last(fid_ctx *c, const double K[9], const double D[5], doubl
     return fid_pose_last_cam(c, &cam, fiducial_len, out, cap_per_frame);
 }
 
-fid_status fid_pose_last_cam(fid_ctx *c, const fid_camera *camera, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame)
+// a fid_pose_cov beside every fid_pose_out of a call of the context's largest batch, on the device (the first _cov call allocates it:
+// max_batch x max_markers_per_frame x 592 bytes, 39 MB at 256 x 256).  The records stay there; a _cov call copies out what the
+// frames' counts need
+static fid_status ensure_pose_cov(fid_ctx *c)
+{
+    const size_t need = (size_t)c->lim.max_batch * (size_t)c->lim.max_markers_per_frame;
+    if (c->pcov_cap >= need) return FID_OK;
+    HIPCHK(c, hipMalloc((void **)&c->d_pcov, sizeof(fid_pose_cov) * need));
+    HIPCHK(c, hipMemsetAsync(c->d_pcov, 0, sizeof(fid_pose_cov) * need, c->stream));
+    c->pcov_cap = need;
+    return FID_OK;
+}
+
+// fid_pose_last_cam and fid_pose_last_cov_cam: the poses (with_cov: and their covariances) of the last call's markers
+static fid_status pose_last_run(fid_ctx *c, const fid_camera *camera, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame, bool with_cov,
+                                double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
+    if (with_cov && (!cov || !fid_sigma_usable(sigma_px))) return FID_E_INVALID_ARG;
     if (c->in_flight) {
         c->last_error = "a submitted batch is in flight: fid_collect first";
         return FID_E_INVALID_ARG;
@@ -1621,9 +1667,13 @@ fid_status fid_pose_last_cam(fid_ctx *c, const fid_camera *camera, double fiduci
     const int F = c->last_frames, MM = c->P.maxMarkers;
     const fid_camera cam = fid_camera_normalised(*camera);
     const bool same_cam = c->pose_cam_valid && !memcmp(&c->pose_cam, &cam, sizeof cam) && c->pose_len == fiducial_len;
-    fid_status rc = FID_OK;
-    if (!(same_cam && c->pose_done)) {  // (else: the detect call already ran k_pose for this camera on these markers)
-        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, cam, fiducial_len, c->d_poses);
+    // (done: the detect call already ran k_pose -- and, asked for with this sigma_px, k_pose_cov -- for this camera on these markers)
+    const bool done = same_cam && c->pose_done && (!with_cov || (c->pose_cov && c->pose_sigma == sigma_px && c->pose_cov_done));
+    fid_status rc = with_cov ? ensure_pose_cov(c) : FID_OK;
+    if (rc != FID_OK) return rc;
+    if (!done) {
+        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, cam, fiducial_len, c->d_poses, with_cov,
+                      sigma_px, c->d_pcov);
         if (rc != FID_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_poses, c->d_poses, sizeof(fid_pose_out) * (size_t)F * MM, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1632,16 +1682,40 @@ fid_status fid_pose_last_cam(fid_ctx *c, const fid_camera *camera, double fiduci
         c->pose_len = fiducial_len;
         c->pose_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
         c->pose_done = c->pose_cam_valid;
+        // (asked for without its covariance: the next call runs k_pose alone)
+        c->pose_cov = with_cov && c->pose_cam_valid;
+        c->pose_sigma = sigma_px;
+        c->pose_cov_done = c->pose_cov;
     }
+    int nmax = 0;
     for (int f = 0; f < F; f++) {
         int n = c->h_counts[f].nmark;
         if (n > cap_per_frame) {
             n = cap_per_frame;
             rc = FID_E_CAPACITY;
         }
+        nmax = n > nmax ? n : nmax;
         memcpy(out + (size_t)f * cap_per_frame, c->h_poses + (size_t)f * MM, sizeof(fid_pose_out) * n);
     }
+    if (with_cov && nmax > 0) {
+        // the first nmax records of every frame in one strided copy, straight into the caller's array (a frame with fewer markers
+        // gets records beyond its count along: they are not part of the result)
+        HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(fid_pose_cov) * (size_t)cap_per_frame, c->d_pcov, sizeof(fid_pose_cov) * (size_t)MM,
+                                   sizeof(fid_pose_cov) * (size_t)nmax, (size_t)F, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return rc;
+}
+
+fid_status fid_pose_last_cam(fid_ctx *c, const fid_camera *camera, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame)
+{
+    return pose_last_run(c, camera, fiducial_len, out, cap_per_frame, false, 0., nullptr);
+}
+
+fid_status fid_pose_last_cov_cam(fid_ctx *c, const fid_camera *camera, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame,
+                                 double sigma_px, fid_pose_cov *cov)
+{
+    return pose_last_run(c, camera, fiducial_len, out, cap_per_frame, true, sigma_px, cov);
 }
 
 fid_status fid_pose(fid_ctx *c, const double K[9], const double D[5], const fid_marker *markers, const double *len_per_marker,
@@ -1652,8 +1726,24 @@ fid_status fid_pose(fid_ctx *c, const double K[9], const double D[5], const fid_
     return fid_pose_cam(c, &cam, markers, len_per_marker, n, fiducial_len, out);
 }
 
+static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                               double fiducial_len, fid_pose_out *out, bool with_cov, double sigma_px, fid_pose_cov *cov);
+
 fid_status fid_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
                         double fiducial_len, fid_pose_out *out)
+{
+    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, false, 0., nullptr);
+}
+
+fid_status fid_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                            double fiducial_len, fid_pose_out *out, double sigma_px, fid_pose_cov *cov)
+{
+    if (!fid_sigma_usable(sigma_px) || (n > 0 && !cov)) return FID_E_INVALID_ARG;
+    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, true, sigma_px, cov);
+}
+
+static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                               double fiducial_len, fid_pose_out *out, bool with_cov, double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || (n > 0 && (!markers || !out)) || n < 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
     if (n == 0) return FID_OK;
@@ -1681,9 +1771,17 @@ fid_status fid_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *
     int nn = n;
     HIPCHK(c, hipMemcpyAsync(c->d_pose_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // lens/nn are stack/heap temporaries
-    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, *camera, fiducial_len, d_out);
+    if (with_cov && n > c->pcov_in_cap) {
+        if (c->d_pcov_in) (void)hipFree(c->d_pcov_in);
+        c->d_pcov_in = nullptr;
+        c->pcov_in_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->d_pcov_in, sizeof(fid_pose_cov) * (size_t)c->pose_cap));
+        c->pcov_in_cap = c->pose_cap;
+    }
+    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, *camera, fiducial_len, d_out, with_cov, sigma_px, c->d_pcov_in);
     if (rc != FID_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_pose_out) * n, hipMemcpyDeviceToHost, c->stream));
+    if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, c->d_pcov_in, sizeof(fid_pose_cov) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FID_OK;
 }

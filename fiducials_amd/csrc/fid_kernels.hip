@@ -5243,6 +5243,28 @@ __device__ double fiducial_area_d(const float *c)
     return a1 + a2;
 }
 
+// What k_pose and k_pose_cov share, so that the covariance is of the items and the object points the pose was solved on: whether
+// the item of a lane group is a marker of its frame, and a lane's object point
+__device__ __forceinline__ bool pose_item_live(int item, int total, int per_frame, const int *__restrict__ nmark_per_frame, int nmark_stride_ints)
+{
+    bool live = item < total;
+    int f = 0, kk = 0;
+    if (live) {
+        f = item / per_frame;
+        kk = item - f * per_frame;
+        live = kk < nmark_per_frame[(long long)f * nmark_stride_ints];
+    }
+    return live;
+}
+// half the marker length as the node's float object points have it (aruco_detect.cpp:151-161)
+__device__ __forceinline__ float pose_half_len(double len)
+{
+    const float ml = (float)len;
+    return ml / 2.f;
+}
+// object point of the lane that owns corner pi: (-h, h), (h, h), (h, -h), (-h, -h)   aruco_detect.cpp:151-161
+#define POSE_OBJECT_POINT(pi, hx) {(double)(((pi) == 1 || (pi) == 2) ? (hx) : -(hx)), (double)(((pi) < 2) ? (hx) : -(hx)), 0.}
+
 // MODEL: the camera model (fid_camera_model) -- the host launches the instantiation of the caller's camera (POSE_CAM_DISPATCH)
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame,
@@ -5255,21 +5277,12 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
     const int groups_per_block = blockDim.x >> 3;
     for (int item0 = blockIdx.x * groups_per_block; item0 < total; item0 += gridDim.x * groups_per_block) {
         const int item = item0 + (threadIdx.x >> 3);
-        bool live = item < total;
-        int f = 0, kk = 0;
-        if (live) {
-            f = item / per_frame;
-            kk = item - f * per_frame;
-            live = kk < nmark_per_frame[(long long)f * nmark_stride_ints];
-        }
-        if (!live) continue;  // group-uniform
+        if (!pose_item_live(item, total, per_frame, nmark_per_frame, nmark_stride_ints)) continue;  // group-uniform
         const fid_marker mk = markers[item];
         const double len = lens ? lens[item] : cam.fiducial_len;
         const double *K = cam.K, *kd = cam.D;
-        const float ml = (float)len;
-        const float hx = ml / 2.f;
-        // object point of this lane: (-h, h), (h, h), (h, -h), (-h, -h)   aruco_detect.cpp:151-161
-        const double M[3] = {(double)((pi == 1 || pi == 2) ? hx : -hx), (double)((pi < 2) ? hx : -hx), 0.};
+        const float hx = pose_half_len(len);
+        const double M[3] = POSE_OBJECT_POINT(pi, hx);
         const double mobs = (double)mk.corners[g];
         // ---- the start: cvUndistortPoints on every corner (each lane needs all four), rounded to float as findHomography converts
         // its inputs; the square-to-quad homography; R, t from its columns
@@ -5357,6 +5370,56 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
             o.object_error = (rerr / dist2f_d(c[0], c[1], c[4], c[5])) * (nt / cam.fiducial_len);
             out[item] = o;
         }
+    }
+}
+
+// The covariance of k_pose's poses (fid_abi.h: "pose covariance"), launched behind it on the same stream: the same items and object
+// points (pose_item_live, pose_half_len, POSE_OBJECT_POINT: k_pose's own) and for each the pose k_pose wrote (rvec, tvec: the
+// doubles Levenberg-Marquardt ended on), one more project_one with its Jacobian at that pose, J^T J and |e|^2 by the same grp_sum8,
+// then pnp_covariance in the group's first lane.  A marker that k_pose could not pose (the equidistant model's record: image_error =
+// -1) gets status 1; k_pose decided that, this kernel reads it.  A kernel of its own and not a tail inside k_pose: behind the
+// Levenberg-Marquardt loop the tail pushed k_pose past the 256 architectural registers into spills (18 registers under every
+// model, whatever part of the tail was moved into called functions), and k_pose stays untouched this way.  The 6 x 6 algebra is a
+// called function here as well (k_pose_cov_record): inlined, the equidistant instantiation spilled four registers; called, none
+// does, at the price of a 224-byte call frame in scratch memory (the sums and the pose go over by address).
+__device__ __noinline__ void k_pose_cov_record(const double S[21], double e2, const double param[6], double sigma_px, fid_pose_cov *rec)
+{
+    pnp_covariance<false>(S, e2, 4, param, sigma_px, rec, nullptr);
+}
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_pose_cov(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame,
+                                                  int nmark_stride_ints, const double *__restrict__ lens, int nframes, int per_frame,
+                                                  PoseCam cam, const fid_pose_out *__restrict__ poses, double sigma_px,
+                                                  fid_pose_cov *__restrict__ cov)
+{
+    const int total = nframes * per_frame;
+    const int g = threadIdx.x & 7;
+    const int pi = g >> 1, sel = g & 1;
+    const int groups_per_block = blockDim.x >> 3;
+    for (int item0 = blockIdx.x * groups_per_block; item0 < total; item0 += gridDim.x * groups_per_block) {
+        const int item = item0 + (threadIdx.x >> 3);
+        if (!pose_item_live(item, total, per_frame, nmark_per_frame, nmark_stride_ints)) continue;  // group-uniform
+        const fid_pose_out po = poses[item];
+        if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
+            if (po.image_error == -1.) {  // k_pose's record of a marker that cannot be posed
+                if (g == 0) pnp_cov_zero(cov + item, 1, 4, nullptr);
+                continue;
+            }
+        }
+        const double len = lens ? lens[item] : cam.fiducial_len;
+        const float hx = pose_half_len(len);
+        const double M[3] = POSE_OBJECT_POINT(pi, hx);
+        const double mobs = (double)markers[item].corners[g];
+        const double param[6] = {po.rvec[0], po.rvec[1], po.rvec[2], po.tvec[0], po.tvec[1], po.tvec[2]};
+        double Jrow[6], S[21];
+        const double ec = project_one<MODEL>(M, param, cam.K, cam.D, sel, Jrow, true) - mobs;
+        int idx = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) S[idx++] = grp_sum8(Jrow[a] * Jrow[b]);
+        const double e2 = grp_sum8(ec * ec);
+        if (g == 0) k_pose_cov_record(S, e2, param, sigma_px, cov + item);
     }
 }
 

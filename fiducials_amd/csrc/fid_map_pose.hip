@@ -89,11 +89,21 @@ __device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
     return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
-template <int MODEL>
+// COV: the covariance tail (fid_abi.h: "pose covariance") over the same points -- the selection above it is this one body's --, summed
+// as the Levenberg-Marquardt sums are; it also writes cov_cam_pose.  The COV = true form takes (double sigma_px, fid_map_pose_cov *cov)
+// as the pack CovArgs, so that the COV = false form has the parameter list it always had AND stays the kernel's own body: moved into
+// an _impl function behind two __global__ wrappers (the STag kernels' form, which they had before) the COV = false kernel came out
+// scheduled and allocated differently from the parent's.  k_map_pose_cov<MODEL> names the COV = true instantiation.
+struct MapPoseCovArgs {
+    double sigma_px;
+    fid_map_pose_cov *cov;
+};
+template <int MODEL, bool COV = false, class... CovArgs>
 __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
                                                   int per_frame, const int *__restrict__ map_ids, const double *__restrict__ map_obj, int map_n,
-                                                  PoseCam cam, fid_map_pose_out *__restrict__ out)
+                                                  PoseCam cam, fid_map_pose_out *__restrict__ out, CovArgs... cov_args)
 {
+    static_assert(sizeof...(CovArgs) == (COV ? 2 : 0), "k_map_pose: (sigma_px, cov) with COV, nothing without");
     __shared__ MpLds s;
     const int f = blockIdx.x, lane = threadIdx.x;
     const double *K = cam.K, *kd = cam.D;
@@ -139,6 +149,10 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
             for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
             o.image_error = 0.;
             out[f] = o;
+            if constexpr (COV) {
+                fid_map_pose_cov *cov = MapPoseCovArgs{cov_args...}.cov;
+                pnp_cov_zero(&cov[f].pose, 1, 0, cov[f].cov_cam_pose);
+            }
         }
         return;
     }
@@ -178,6 +192,10 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
                 for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
                 o.image_error = -1.;
                 out[f] = o;
+                if constexpr (COV) {
+                    fid_map_pose_cov *cov = MapPoseCovArgs{cov_args...}.cov;
+                    pnp_cov_zero(&cov[f].pose, 1, npts, cov[f].cov_cam_pose);
+                }
             }
             return;
         }
@@ -303,13 +321,43 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         o.image_error = tot / npts;
         out[f] = o;
     }
+    if constexpr (COV) {
+        // ---- the covariance: J and e at the returned param, strided partial sums and the butterfly as above
+        double Sp[21];
+        e2 = 0;
+        for (int i = 0; i < 21; i++) Sp[i] = 0.;
+        for (int r = lane; r < nres; r += 64) {
+            const int p = r >> 1, sel = r & 1;
+            const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
+            double Jrow[6];
+            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, true) - s.img[p][sel];
+            e2 += err * err;
+            int idx = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++)
+#pragma unroll
+                for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
+        }
+#pragma unroll
+        for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
+        e2 = wave_sum_f64(e2);
+        const MapPoseCovArgs ca = {cov_args...};
+        if (lane == 0) pnp_covariance<true>(S, e2, npts, param, ca.sigma_px, &ca.cov[f].pose, ca.cov[f].cov_cam_pose);
+    }
 }
+template <int MODEL>
+constexpr auto k_map_pose_cov = k_map_pose<MODEL, true, double, fid_map_pose_cov *>;
 
 // the kernel for F frames on stream st (fid_api.hip's enqueue_detect calls it for the batch it has just enqueued)
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
-                            const fid_camera &camera, fid_map_pose_out *d_out)
+                            const fid_camera &camera, fid_map_pose_out *d_out, bool with_cov, double sigma_px, fid_map_pose_cov *d_cov)
 {
     const PoseCam cam = pose_cam_from(camera, 0.);
+    if (with_cov) {
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_map_pose_cov<CAM_MODEL>, dim3(F), dim3(64), 0, st, d_markers, d_n, n_stride_ints, per_frame,
+                                                        (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, cam, d_out, sigma_px, d_cov));
+        return;
+    }
     POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_map_pose<CAM_MODEL>, dim3(F), dim3(64), 0, st, d_markers, d_n, n_stride_ints, per_frame,
                                                     (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, cam, d_out));
 }
@@ -380,9 +428,21 @@ fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], f
     return fid_map_pose_last_cam(c, &cam, out, cap_frames);
 }
 
-fid_status fid_map_pose_last_cam(fid_ctx *c, const fid_camera *camera, fid_map_pose_out *out, int32_t cap_frames)
+// max_batch + 1 fid_map_pose_cov beside d_mposes / h_mposes (the first _cov call allocates them)
+static fid_status ensure_map_cov(fid_ctx *c)
+{
+    if (c->d_mcov && c->h_mcov) return FID_OK;
+    if (!c->d_mcov) HIPCHK(c, hipMalloc((void **)&c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)(c->lim.max_batch + 1)));
+    HIPCHK(c, hipHostMalloc((void **)&c->h_mcov, sizeof(fid_map_pose_cov) * (size_t)(c->lim.max_batch + 1), hipHostMallocDefault));
+    return FID_OK;
+}
+
+// fid_map_pose_last_cam and fid_map_pose_last_cov_cam: the camera pose (with_cov: and its covariance) of every frame of the last call
+static fid_status map_pose_last_run(fid_ctx *c, const fid_camera *camera, fid_map_pose_out *out, int32_t cap_frames, bool with_cov, double sigma_px,
+                                    fid_map_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0) return FID_E_INVALID_ARG;
+    if (with_cov && (!cov || !fid_sigma_usable(sigma_px))) return FID_E_INVALID_ARG;
     if (c->in_flight) {
         c->last_error = "a submitted batch is in flight: fid_collect first";
         return FID_E_INVALID_ARG;
@@ -397,19 +457,43 @@ fid_status fid_map_pose_last_cam(fid_ctx *c, const fid_camera *camera, fid_map_p
         return FID_E_CAPACITY;
     }
     HIPCHK(c, hipSetDevice(c->device));
+    if (with_cov) {
+        const fid_status rca = ensure_map_cov(c);
+        if (rca != FID_OK) return rca;
+    }
     const fid_camera cam = fid_camera_normalised(*camera);
     const bool same_cam = c->map_cam_valid && !memcmp(&c->map_cam, &cam, sizeof cam);
-    if (!(same_cam && c->map_done)) {  // (else: the detect call already ran k_map_pose for this camera on these markers)
-        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, cam, c->d_mposes);
+    // (done: the detect call already ran k_map_pose -- asked for with this sigma_px, its COV form -- for this camera on these markers)
+    const bool done = same_cam && c->map_done && (!with_cov || (c->map_cov && c->map_sigma == sigma_px && c->map_cov_done));
+    if (!done) {
+        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, cam, c->d_mposes,
+                        with_cov, sigma_px, c->d_mcov);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
+        if (with_cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->map_cam = cam;
         c->map_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
         c->map_done = c->map_cam_valid;
+        // (asked for without its covariance: the next call runs k_map_pose's COV = false form)
+        c->map_cov = with_cov && c->map_cam_valid;
+        c->map_sigma = sigma_px;
+        c->map_cov_done = c->map_cov;
     }
     memcpy(out, c->h_mposes, sizeof(fid_map_pose_out) * (size_t)F);
+    if (with_cov) memcpy(cov, c->h_mcov, sizeof(fid_map_pose_cov) * (size_t)F);
     return FID_OK;
+}
+
+fid_status fid_map_pose_last_cam(fid_ctx *c, const fid_camera *camera, fid_map_pose_out *out, int32_t cap_frames)
+{
+    return map_pose_last_run(c, camera, out, cap_frames, false, 0., nullptr);
+}
+
+fid_status fid_map_pose_last_cov_cam(fid_ctx *c, const fid_camera *camera, fid_map_pose_out *out, int32_t cap_frames, double sigma_px,
+                                     fid_map_pose_cov *cov)
+{
+    return map_pose_last_run(c, camera, out, cap_frames, true, sigma_px, cov);
 }
 
 fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const fid_marker *markers, int32_t n, fid_map_pose_out *out)
@@ -419,7 +503,23 @@ fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const 
     return fid_map_pose_cam(c, &cam, markers, n, out);
 }
 
+static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
+                                   double sigma_px, fid_map_pose_cov *cov);
+
 fid_status fid_map_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out)
+{
+    return map_pose_cam_run(c, camera, markers, n, out, false, 0., nullptr);
+}
+
+fid_status fid_map_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, double sigma_px,
+                                fid_map_pose_cov *cov)
+{
+    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
+    return map_pose_cam_run(c, camera, markers, n, out, true, sigma_px, cov);
+}
+
+static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
+                                   double sigma_px, fid_map_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
     if (c->in_flight) {
@@ -445,9 +545,15 @@ fid_status fid_map_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_mark
     if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // (nn is a stack temporary)
-    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, d_out);
+    if (with_cov) {
+        const fid_status rca = ensure_map_cov(c);
+        if (rca != FID_OK) return rca;
+    }
+    fid_map_pose_cov *d_cov = with_cov ? c->d_mcov + c->lim.max_batch : nullptr;
+    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, d_out, with_cov, sigma_px, d_cov);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
+    if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, d_cov, sizeof(fid_map_pose_cov), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FID_OK;
 }

@@ -12,6 +12,7 @@
 //                        pnp_dlt_entry, pnp_smallest_eigvec9, pnp_dlt_finish (coplanar sets: findHomography's DLT);
 //                        pnp_start_largest (sets that are not coplanar)
 //   CvLevMarq            lm_lambda, solve6_spd, LevMarq
+//   the covariance       pnp_covariance, pnp_cov_zero (sigma^2 (J^T J)^-1 at the returned pose, in the ROS pose convention)
 //
 // A kernel gathers its points, makes the start, and runs
 //     LevMarq lm;
@@ -124,6 +125,8 @@ static inline bool fid_camera_usable(const fid_camera *c)
 {
     return c && c->model >= FID_CAM_PLUMB_BOB && c->model <= FID_CAM_EQUIDISTANT && c->n_dist >= 0 && c->n_dist <= 12;
 }
+// sigma_px of a _cov entry point: zero (the a-posteriori estimate) or positive, and finite
+static inline bool fid_sigma_usable(double sigma_px) { return sigma_px >= 0. && sigma_px - sigma_px == 0.; }
 // the host's choice of instantiation: STMT is expanded once per model with the constant CAM_MODEL in scope
 #define POSE_CAM_DISPATCH(model, STMT)                         \
     do {                                                       \
@@ -477,6 +480,200 @@ __device__ __forceinline__ void solve6_spd(const double S[21], const double g[6]
 #pragma unroll
         for (int k = i + 1; k < 6; k++) v -= L[k][i] * x[k];
         x[i] = v;
+    }
+}
+
+// The covariance of a returned pose (fid_abi.h: "pose covariance").  S: the 21 packed sums of J^T J at p (solve6_spd's order), e2:
+// |e|^2 at p, n_points: N, p: (rvec, tvec), sigma_px: the caller's pixel sigma (0: the a-posteriori sigma^2 = e2 / (2 N - 6)).
+// (J^T J)^-1 by the LDL^T of solve6_spd without damping -- L^-1 by forward substitution, then L^-T D^-1 L^-1, one triangle --,
+// times sigma^2 as the last step: cov_rt.  cov_pose = A cov_rt A^T with A = [[0, I], [J_l(rvec), 0]] and, with CAM, cov_cam_pose =
+// B cov_pose B^T with B = [[-R^T, -R^T [t]x], [0, -R^T]], both in their 3 x 3 blocks (the zero blocks are not multiplied).  Every
+// matrix is written as one triangle and its mirror.  Everything in registers with static indices; the record goes straight to
+// memory, entry by entry, so that no 6 x 6 result is held beyond its use.  One lane calls it.
+__device__ __forceinline__ void pnp_cov_zero(fid_pose_cov *o, int status, int n_points, double *cov_cam_pose)
+{
+    o->status = status;
+    o->n_points = n_points;
+    o->sigma2 = 0.;
+    for (int i = 0; i < 36; i++) o->cov_rt[i] = o->cov_pose[i] = 0.;
+    if (cov_cam_pose)
+        for (int i = 0; i < 36; i++) cov_cam_pose[i] = 0.;
+}
+template <bool CAM>
+__device__ __forceinline__ void pnp_covariance(const double S[21], double e2, int n_points, const double p[6], double sigma_px, fid_pose_cov *o,
+                                               double *cov_cam_pose)
+{
+    // ---- LDL^T of J^T J (solve6_spd's factorisation, lambda = 0)
+    double A[6][6];
+    {
+        int idx = 0;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = a; b < 6; b++) {
+                A[a][b] = S[idx];
+                A[b][a] = S[idx];
+                idx++;
+            }
+    }
+    double L[6][6], Dg[6], iD[6];
+    bool good = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double d = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) d -= L[j][k] * L[j][k] * Dg[k];
+        good = good && d > 0. && d - d == 0.;  // (a pivot that is not positive, or not finite: status 2)
+        const double id = 1. / d;
+        Dg[j] = d;
+        iD[j] = id;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * Dg[k];
+            L[i][j] = v * id;
+        }
+    }
+    if (!good) {
+        pnp_cov_zero(o, 2, n_points, CAM ? cov_cam_pose : nullptr);
+        return;
+    }
+    // ---- M = L^-1 (unit lower triangle), C = M^T D^-1 M
+    double M[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; j++)
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = -L[i][j];
+#pragma unroll
+            for (int k = j + 1; k < i; k++) v -= L[i][k] * M[k][j];
+            M[i][j] = v;
+        }
+    const double sigma2 = sigma_px > 0. ? sigma_px * sigma_px : e2 / (double)(2 * n_points - 6);
+    double C[6][6];  // cov_rt
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = a; b < 6; b++) {
+            // sum over k >= b of M[k][a] M[k][b] / D[k], M[k][k] = 1
+            double v = (a == b ? 1. : M[b][a]) * iD[b];
+#pragma unroll
+            for (int k = b + 1; k < 6; k++) v += M[k][a] * M[k][b] * iD[k];
+            v *= sigma2;
+            C[a][b] = v;
+            C[b][a] = v;
+        }
+    o->status = 0;
+    o->n_points = n_points;
+    o->sigma2 = sigma2;
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) o->cov_rt[6 * a + b] = C[a][b];
+    // ---- J_l(rvec) = I + (1 - cos th) / th^2 [r]x + (th - sin th) / th^3 [r]x^2, [r]x^2 = r r^T - th^2 I
+    double Jl[3][3];
+    {
+        const double rx = p[0], ry = p[1], rz = p[2];
+        const double th2 = rx * rx + ry * ry + rz * rz, th = sqrt(th2);
+        double ca = 0.5, cb = 1. / 6.;
+        if (!(th < 1e-4)) {
+            double sn, cs;
+            sincos(th, &sn, &cs);
+            ca = (1. - cs) / th2;
+            cb = (th - sn) / (th2 * th);
+        }
+        Jl[0][0] = 1. + cb * (rx * rx - th2); Jl[0][1] = -ca * rz + cb * rx * ry;   Jl[0][2] = ca * ry + cb * rx * rz;
+        Jl[1][0] = ca * rz + cb * rx * ry;    Jl[1][1] = 1. + cb * (ry * ry - th2); Jl[1][2] = -ca * rx + cb * ry * rz;
+        Jl[2][0] = -ca * ry + cb * rx * rz;   Jl[2][1] = ca * rx + cb * ry * rz;    Jl[2][2] = 1. + cb * (rz * rz - th2);
+    }
+    // ---- cov_pose = [[Ctt, Ctr Jl^T], [Jl Crt, Jl Crr Jl^T]]
+    double P[6][6];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            P[i][j] = C[3 + i][3 + j];
+            const double v = C[3 + i][0] * Jl[j][0] + C[3 + i][1] * Jl[j][1] + C[3 + i][2] * Jl[j][2];
+            P[i][3 + j] = v;
+            P[3 + j][i] = v;
+        }
+    {
+        double T[3][3];  // Jl Crr
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) T[i][j] = Jl[i][0] * C[0][j] + Jl[i][1] * C[1][j] + Jl[i][2] * C[2][j];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = i; j < 3; j++) {
+                const double v = T[i][0] * Jl[j][0] + T[i][1] * Jl[j][1] + T[i][2] * Jl[j][2];
+                P[3 + i][3 + j] = v;
+                P[3 + j][3 + i] = v;
+            }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; a++)
+#pragma unroll
+        for (int b = 0; b < 6; b++) o->cov_pose[6 * a + b] = P[a][b];
+    if constexpr (CAM) {
+        // ---- cov_cam_pose = B cov_pose B^T, B = [[Q, W], [0, Q]], Q = -R^T, W = Q [t]x
+        double R[9], dummy[27];
+        rodrigues_v2m(p, R, dummy, false);
+        const double tx = p[3], ty = p[4], tz = p[5];
+        const double tX[3][3] = {{0., -tz, ty}, {tz, 0., -tx}, {-ty, tx, 0.}};
+        double Q[3][3], W[3][3], X1[3][3], X2[3][3], G[6][6];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) Q[i][j] = -R[3 * j + i];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) W[i][j] = Q[i][0] * tX[0][j] + Q[i][1] * tX[1][j] + Q[i][2] * tX[2][j];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                X1[i][j] = Q[i][0] * P[0][j] + Q[i][1] * P[1][j] + Q[i][2] * P[2][j] + W[i][0] * P[3][j] + W[i][1] * P[4][j] + W[i][2] * P[5][j];
+                X2[i][j] = Q[i][0] * P[0][3 + j] + Q[i][1] * P[1][3 + j] + Q[i][2] * P[2][3 + j] + W[i][0] * P[3][3 + j] + W[i][1] * P[4][3 + j] +
+                           W[i][2] * P[5][3 + j];
+            }
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = i; j < 3; j++) {
+                const double v = X1[i][0] * Q[j][0] + X1[i][1] * Q[j][1] + X1[i][2] * Q[j][2] + X2[i][0] * W[j][0] + X2[i][1] * W[j][1] + X2[i][2] * W[j][2];
+                G[i][j] = v;
+                G[j][i] = v;
+            }
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const double v = X2[i][0] * Q[j][0] + X2[i][1] * Q[j][1] + X2[i][2] * Q[j][2];
+                G[i][3 + j] = v;
+                G[3 + j][i] = v;
+            }
+        }
+        {
+            double T[3][3];  // Q P_rr
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = 0; j < 3; j++) T[i][j] = Q[i][0] * P[3][3 + j] + Q[i][1] * P[4][3 + j] + Q[i][2] * P[5][3 + j];
+#pragma unroll
+            for (int i = 0; i < 3; i++)
+#pragma unroll
+                for (int j = i; j < 3; j++) {
+                    const double v = T[i][0] * Q[j][0] + T[i][1] * Q[j][1] + T[i][2] * Q[j][2];
+                    G[3 + i][3 + j] = v;
+                    G[3 + j][3 + i] = v;
+                }
+        }
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int b = 0; b < 6; b++) cov_cam_pose[6 * a + b] = G[a][b];
     }
 }
 

@@ -666,6 +666,8 @@ struct fid_stag_ctx {
     fid_stag_tag *d_ltags = nullptr;
     int *d_lstart = nullptr, *d_hn = nullptr;
     fid_stag_bundle_pose_out *d_bposes = nullptr;
+    fid_pose_cov *d_cov = nullptr;  // the _cov entry points' records, for markers or bundles (outside the slab: the first _cov call allocates it)
+    int cov_cap = 0;
     fid_stag_marker *d_hmarkers = nullptr;
     std::vector<fid_stag_tag> layout;  // as it lies on the device
     int n_bundles = 0;
@@ -870,6 +872,7 @@ void fid_stag_destroy(fid_stag_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->d_words && c->d_words != c->d_words_slab) (void)hipFree(c->d_words);  // (a library larger than the slab's room for it)
     if (c->d_slab) (void)hipFree(c->d_slab);
+    if (c->d_cov) (void)hipFree(c->d_cov);
     if (c->hp) {
         std::lock_guard<std::mutex> g(g_stag_alias_mutex);
         for (size_t k = 0; k < g_stag_aliases.size(); k++)
@@ -1722,7 +1725,38 @@ fid_status fid_stag_pose_last(fid_stag_ctx *c, const double K[9], const double D
     return fid_stag_pose_last_cam(c, &cam, marker_size, out, cap, n_out);
 }
 
+static fid_status stag_pose_last_run(fid_stag_ctx *c, const fid_camera *camera, double marker_size, fid_stag_pose_out *out, int32_t cap, int32_t *n_out,
+                                     bool with_cov, double sigma_px, fid_pose_cov *cov);
+
 fid_status fid_stag_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, double marker_size, fid_stag_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    return stag_pose_last_run(c, camera, marker_size, out, cap, n_out, false, 0., nullptr);
+}
+
+fid_status fid_stag_pose_last_cov_cam(fid_stag_ctx *c, const fid_camera *camera, double marker_size, fid_stag_pose_out *out, int32_t cap, int32_t *n_out,
+                                      double sigma_px, fid_pose_cov *cov)
+{
+    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
+    return stag_pose_last_run(c, camera, marker_size, out, cap, n_out, true, sigma_px, cov);
+}
+
+// room for n fid_pose_cov (the first _cov call of a context allocates it; a context that never asks has none)
+static fid_status stag_ensure_cov(fid_stag_ctx *c, int n)
+{
+    if (n <= c->cov_cap) return FID_OK;
+    hipStream_t st = stag_stream(c);
+    if (hipStreamSynchronize(st) != hipSuccess) return FID_E_HIP;
+    if (c->d_cov) (void)hipFree(c->d_cov);
+    c->d_cov = nullptr;
+    c->cov_cap = 0;
+    const int want = (n + 63) / 64 * 64;
+    if (hipMalloc((void **)&c->d_cov, (size_t)want * sizeof(fid_pose_cov)) != hipSuccess) return FID_E_OUT_OF_MEMORY;
+    c->cov_cap = want;
+    return FID_OK;
+}
+
+static fid_status stag_pose_last_run(fid_stag_ctx *c, const fid_camera *camera, double marker_size, fid_stag_pose_out *out, int32_t cap, int32_t *n_out,
+                                     bool with_cov, double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || !c->decoded || !(marker_size > 0)) return FID_E_INVALID_ARG;
     if (n_out) *n_out = c->n_markers;
@@ -1731,10 +1765,18 @@ fid_status fid_stag_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, dou
     if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
     const PoseCam cam = pose_cam_from(*camera, marker_size);
     hipStream_t st = stag_stream(c);
-    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers, c->d_nmarkers, cam,
-                                                    marker_size, c->d_poses));
+    if (with_cov) {
+        const fid_status rca = stag_ensure_cov(c, c->n_markers);
+        if (rca != FID_OK) return rca;
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose_cov<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers,
+                                                        c->d_nmarkers, cam, marker_size, c->d_poses, sigma_px, c->d_cov));
+    } else {
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers,
+                                                        c->d_nmarkers, cam, marker_size, c->d_poses));
+    }
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
     if (hipMemcpyAsync(out, c->d_poses, (size_t)c->n_markers * sizeof(fid_stag_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
+    if (with_cov && hipMemcpyAsync(cov, c->d_cov, (size_t)c->n_markers * sizeof(fid_pose_cov), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
     return hipStreamSynchronize(st) == hipSuccess ? FID_OK : FID_E_HIP;
 }
 
@@ -1786,21 +1828,37 @@ fid_status fid_stag_set_layout(fid_stag_ctx *c, const fid_stag_tag *tags, int32_
 
 // the bundle kernel on a marker list in device memory, its slots read back and handed over in bundle order
 static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const fid_camera &camera, const fid_stag_marker *d_markers, const int *d_n,
-                                       fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+                                       fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out, bool with_cov = false, double sigma_px = 0.,
+                                       fid_pose_cov *cov = nullptr)
 {
     const PoseCam cam = pose_cam_from(camera, 0.0);
     hipStream_t st = stag_stream(c);
-    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags, c->d_lstart,
-                                                    cam, c->d_bposes));
+    if (with_cov) {
+        const fid_status rca = stag_ensure_cov(c, FID_STAG_MAX_BUNDLES);
+        if (rca != FID_OK) return rca;
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose_cov<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags,
+                                                        c->d_lstart, cam, c->d_bposes, sigma_px, c->d_cov));
+    } else {
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags,
+                                                        c->d_lstart, cam, c->d_bposes));
+    }
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
     fid_stag_bundle_pose_out slots[FID_STAG_MAX_BUNDLES];
     if (hipMemcpyAsync(slots, c->d_bposes, (size_t)c->n_bundles * sizeof(fid_stag_bundle_pose_out), hipMemcpyDeviceToHost, st) != hipSuccess) return FID_E_HIP;
+    std::vector<fid_pose_cov> cslots(with_cov ? (size_t)c->n_bundles : 0);
+    if (with_cov && hipMemcpyAsync(cslots.data(), c->d_cov, (size_t)c->n_bundles * sizeof(fid_pose_cov), hipMemcpyDeviceToHost, st) != hipSuccess)
+        return FID_E_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return FID_E_HIP;
     int n = 0;
     for (int b = 0; b < c->n_bundles; b++) n += slots[b].n_tags > 0;
     if (n_out) *n_out = n;
     if (n > cap) return FID_E_CAPACITY;
     (void)stag_hand_over_bundles(slots, c->n_bundles, out, nullptr);
+    if (with_cov) {  // (the same indexing as the records handed over: the bundles of which a tag was found, in bundle order)
+        int k = 0;
+        for (int b = 0; b < c->n_bundles; b++)
+            if (slots[b].n_tags > 0) cov[k++] = cslots[(size_t)b];
+    }
     return FID_OK;
 }
 
@@ -1811,13 +1869,26 @@ fid_status fid_stag_bundle_pose_last(fid_stag_ctx *c, const double K[9], const d
     return fid_stag_bundle_pose_last_cam(c, &cam, out, cap, n_out);
 }
 
-fid_status fid_stag_bundle_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+static fid_status stag_bundle_pose_last_run(fid_stag_ctx *c, const fid_camera *camera, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out,
+                                            bool with_cov, double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || cap < 0 || !c->decoded) return FID_E_INVALID_ARG;
     if (n_out) *n_out = 0;
     if (c->n_bundles == 0 || c->n_markers == 0) return FID_OK;  // (no layout: nothing is launched)
     if (hipSetDevice(c->device) != hipSuccess) return FID_E_HIP;
-    return stag_bundle_pose_run(c, *camera, c->d_markers, c->d_nmarkers, out, cap, n_out);
+    return stag_bundle_pose_run(c, *camera, c->d_markers, c->d_nmarkers, out, cap, n_out, with_cov, sigma_px, cov);
+}
+
+fid_status fid_stag_bundle_pose_last_cam(fid_stag_ctx *c, const fid_camera *camera, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    return stag_bundle_pose_last_run(c, camera, out, cap, n_out, false, 0., nullptr);
+}
+
+fid_status fid_stag_bundle_pose_last_cov_cam(fid_stag_ctx *c, const fid_camera *camera, fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out,
+                                             double sigma_px, fid_pose_cov *cov)
+{
+    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
+    return stag_bundle_pose_last_run(c, camera, out, cap, n_out, true, sigma_px, cov);
 }
 
 fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double D[5], const fid_stag_marker *markers, int32_t n,
@@ -1828,8 +1899,24 @@ fid_status fid_stag_bundle_pose(fid_stag_ctx *c, const double K[9], const double
     return fid_stag_bundle_pose_cam(c, &cam, markers, n, out, cap, n_out);
 }
 
+static fid_status stag_bundle_pose_cam_run(fid_stag_ctx *c, const fid_camera *camera, const fid_stag_marker *markers, int32_t n,
+                                           fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out, bool with_cov, double sigma_px, fid_pose_cov *cov);
+
 fid_status fid_stag_bundle_pose_cam(fid_stag_ctx *c, const fid_camera *camera, const fid_stag_marker *markers, int32_t n,
                                     fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out)
+{
+    return stag_bundle_pose_cam_run(c, camera, markers, n, out, cap, n_out, false, 0., nullptr);
+}
+
+fid_status fid_stag_bundle_pose_cov_cam(fid_stag_ctx *c, const fid_camera *camera, const fid_stag_marker *markers, int32_t n,
+                                        fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out, double sigma_px, fid_pose_cov *cov)
+{
+    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
+    return stag_bundle_pose_cam_run(c, camera, markers, n, out, cap, n_out, true, sigma_px, cov);
+}
+
+static fid_status stag_bundle_pose_cam_run(fid_stag_ctx *c, const fid_camera *camera, const fid_stag_marker *markers, int32_t n,
+                                           fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out, bool with_cov, double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || !out || cap < 0 || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
     if (n > STAG_LAYOUT_TAGS) return FID_E_CAPACITY;
@@ -1841,7 +1928,7 @@ fid_status fid_stag_bundle_pose_cam(fid_stag_ctx *c, const fid_camera *camera, c
     if (hipMemcpyAsync(c->d_hmarkers, markers, (size_t)n * sizeof(fid_stag_marker), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(c->d_hn, &nn, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return FID_E_HIP;
-    return stag_bundle_pose_run(c, *camera, c->d_hmarkers, c->d_hn, out, cap, n_out);
+    return stag_bundle_pose_run(c, *camera, c->d_hmarkers, c->d_hn, out, cap, n_out, with_cov, sigma_px, cov);
 }
 
 // Frames as a grid dimension (round 3; fid_stag_batch.h).  The contexts are cut into GROUPS of up to STAG_MAXF; a group takes

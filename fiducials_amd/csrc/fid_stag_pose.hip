@@ -800,9 +800,12 @@ struct k_stag_refine_fn {
 // four corners, then the reference's Levenberg-Marquardt (LevMarq) on the reprojection error of all five points with
 // distortion; a 16-lane group per marker, lane g < 10 owns residual g, the sums by grp_sum16.  Tolerance row (the reference
 // starts from a 5-point DLT + refinement; both land on the same minimum).
-template <int MODEL>
+// COV: the covariance tail behind the result write (fid_abi.h: "pose covariance"; k_stag_pose_cov): one more Jacobian at the returned
+// pose, J^T J and |e|^2 by this kernel's grp_sum16, then pnp_covariance in the group's first lane
+template <int MODEL, bool COV = false>
 __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam,
-                                                  double marker_size, fid_stag_pose_out *__restrict__ out)
+                                                  double marker_size, fid_stag_pose_out *__restrict__ out, double sigma_px = 0.,
+                                                  fid_pose_cov *__restrict__ cov = nullptr)
 {
     const int item = blockIdx.x * 4 + (threadIdx.x >> 4), g = threadIdx.x & 15;
     if (item >= *nmarkers) return;  // group-uniform
@@ -838,6 +841,7 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
                     for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
                     for (int i = 0; i < 9; i++) o.R[i] = 0.;
                     out[item] = o;
+                    if constexpr (COV) pnp_cov_zero(cov + item, 1, 5, nullptr);
                 }
                 return;
             }
@@ -878,6 +882,23 @@ __device__ __forceinline__ void k_stag_pose_impl(const fid_stag_marker *__restri
         rodrigues_v2m(param, o.R, dummy, false);  // cv::Rodrigues(rVec, rMat) of solvePnpSingle
         out[item] = o;
     }
+    if constexpr (COV) {
+        // ---- the covariance: J and e at the returned param, J^T J and |e|^2 over the marker's sixteen lanes
+        const double pr = project_one<MODEL>(M, param, K, kd, sel, Jrow, true);
+        const double ec = act ? pr - mobs : 0.;
+        if (!act)
+            for (int i = 0; i < 6; i++) Jrow[i] = 0.;
+        int idx = 0;
+        for (int a = 0; a < 6; a++)
+            for (int b = a; b < 6; b++) S[idx++] = grp_sum16(Jrow[a] * Jrow[b]);
+        const double e2 = grp_sum16(ec * ec);
+        if (g == 0) pnp_covariance<false>(S, e2, 5, param, sigma_px, cov + item, nullptr);
+    }
+}
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_stag_pose_cov(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out, double sigma_px, fid_pose_cov *__restrict__ cov)
+{
+    k_stag_pose_impl<MODEL, true>(markers, nmarkers, cam, marker_size, out, sigma_px, cov);
 }
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out)
@@ -957,10 +978,12 @@ __device__ bool sb_homography_dlt(SbLds *s, int n, int lane, double H[9])
     return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
 }
 
-template <int MODEL>
+// COV: the covariance tail (fid_abi.h: "pose covariance"; k_stag_bundle_pose_cov) over the same points, with this kernel's wave sum
+template <int MODEL, bool COV = false>
 __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
                                                          const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam,
-                                                         fid_stag_bundle_pose_out *__restrict__ out)
+                                                         fid_stag_bundle_pose_out *__restrict__ out, double sigma_px = 0.,
+                                                         fid_pose_cov *__restrict__ cov = nullptr)
 {
     __shared__ SbLds s;
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -1000,6 +1023,7 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
             for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
             for (int i = 0; i < 9; i++) o.R[i] = 0.;
             out[b] = o;
+            if constexpr (COV) pnp_cov_zero(cov + b, 1, 0, nullptr);
         }
         return;
     }
@@ -1038,6 +1062,7 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
                 for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = 0.;
                 for (int i = 0; i < 9; i++) o.R[i] = 0.;
                 out[b] = o;
+                if constexpr (COV) pnp_cov_zero(cov + b, 1, npts, nullptr);
             }
             return;
         }
@@ -1129,6 +1154,31 @@ __device__ __forceinline__ void k_stag_bundle_pose_impl(const fid_stag_marker *_
         rodrigues_v2m(param, o.R, dummy, false);
         out[b] = o;
     }
+    if constexpr (COV) {
+        // ---- the covariance: J and e at the returned param, J^T J and |e|^2 over the wave (two residuals per lane)
+        if (act0) {
+            err0 = project_one<MODEL>(M0, param, K, kd, r0 & 1, J0, true) - mobs0;
+        } else {
+            err0 = 0.;
+            for (int i = 0; i < 6; i++) J0[i] = 0.;
+        }
+        if (act1) {
+            err1 = project_one<MODEL>(M1, param, K, kd, r1 & 1, J1, true) - mobs1;
+        } else {
+            err1 = 0.;
+            for (int i = 0; i < 6; i++) J1[i] = 0.;
+        }
+        int idx = 0;
+        for (int a = 0; a < 6; a++)
+            for (int c = a; c < 6; c++) S[idx++] = wave_sum_f64(J0[a] * J0[c] + J1[a] * J1[c]);
+        const double e2 = wave_sum_f64(err0 * err0 + err1 * err1);
+        if (lane == 0) pnp_covariance<false>(S, e2, npts, param, sigma_px, cov + b, nullptr);
+    }
+}
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_stag_bundle_pose_cov(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out, double sigma_px, fid_pose_cov *__restrict__ cov)
+{
+    k_stag_bundle_pose_impl<MODEL, true>(markers, nmarkers, ltags, lstart, cam, out, sigma_px, cov);
 }
 template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_bundle_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out)

@@ -41,6 +41,8 @@ _MARKER_DT = np.dtype([("id", "<i4"), ("corners", "<f4", (8,))])  # fid_marker
 MAP_ENTRY_DTYPE = np.dtype([("id", "<i4"), ("reserved0", "<i4"), ("len", "<f8"), ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])  # fid_map_entry
 MAP_POSE_DTYPE = np.dtype([("n_markers", "<i4"), ("n_over", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("R", "<f8", (3, 3)),
                            ("cam_R", "<f8", (3, 3)), ("cam_t", "<f8", (3,)), ("image_error", "<f8")])  # fid_map_pose_out
+POSE_COV_DTYPE = np.dtype(_lib.POSE_COV_FIELDS)  # fid_pose_cov
+MAP_POSE_COV_DTYPE = np.dtype([("pose", POSE_COV_DTYPE), ("cov_cam_pose", "<f8", (6, 6))])  # fid_map_pose_cov
 _POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("image_error", "<f8"), ("object_error", "<f8"), ("fiducial_area", "<f8")])
 
 
@@ -297,6 +299,43 @@ class ArucoDetector:
         self._check(self._L.fid_pose(self._ctx, Kc, Dc, mk, lens, n, float(fiducial_len), out))
         return _poses_to_result(out, n)
 
+    def estimate_pose_single_markers_cov(self, corners: np.ndarray, ids: np.ndarray, fiducial_len: float, K=None, D=None,
+                                         fiducial_len_override: dict | None = None, camera=None, sigma_px: float = 1.0):
+        """estimate_pose_single_markers with the covariance of every pose (fid_pose_cov_cam): (PoseResult, POSE_COV_DTYPE records).
+        sigma_px: the corner noise in pixels; 0 takes the a-posteriori estimate from the residuals."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        corners = np.ascontiguousarray(corners, dtype=np.float32).reshape(-1, 8)
+        n = corners.shape[0]
+        mk = (FidMarker * max(n, 1))()
+        lens = (C.c_double * max(n, 1))()
+        for i in range(n):
+            mk[i].id = int(ids[i])
+            for j in range(8):
+                mk[i].corners[j] = float(corners[i, j])
+            lens[i] = float((fiducial_len_override or {}).get(int(ids[i]), fiducial_len))
+        out = (FidPoseOut * max(n, 1))()
+        cov = np.zeros(max(n, 1), POSE_COV_DTYPE)
+        self._check(self._L.fid_pose_cov_cam(self._ctx, C.byref(cam.c), mk, lens, n, float(fiducial_len), out, float(sigma_px), cov.ctypes.data))
+        return _poses_to_result(out, n), cov[:n]
+
+    def pose_cov_last(self, fiducial_len: float, K=None, D=None, camera=None, sigma_px: float = 1.0):
+        """pose_last with the covariance of every pose (fid_pose_last_cov_cam): (list of PoseResult, list of POSE_COV_DTYPE arrays), one
+        of each per frame.  The camera and sigma_px are remembered: the next detect_* call computes both in its own stream."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        cov = np.zeros(max(self._last_frames, 1) * self.max_markers, POSE_COV_DTYPE)
+        self._check(self._L.fid_pose_last_cov_cam(self._ctx, C.byref(cam.c), float(fiducial_len), self._poses, self.max_markers, float(sigma_px),
+                                                  cov.ctypes.data))
+        res, covs = [], []
+        for f in range(self._last_frames):
+            n = max(int(self._n[f]), 0)
+            res.append(_poses_view_to_result(self._poses_np[f * self.max_markers:f * self.max_markers + n]))
+            covs.append(cov[f * self.max_markers:f * self.max_markers + n])
+        return res, covs
+
     def project_points(self, camera, rvec, tvec, obj, jacobian: bool = False):
         """cv::projectPoints under `camera` (fid_project_points_cam: the pose kernels' own projection run as a small kernel): obj
         (n, 3) -> uv (n, 2); with jacobian=True also d(u, v) / d(rvec, tvec) as (n, 2, 6)."""
@@ -387,6 +426,32 @@ class ArucoDetector:
         self._check(self._L.fid_map_pose(self._ctx, Kc.ctypes.data, Dc.ctypes.data if Dc is not None else None,
                                          mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data))
         return out[0]
+
+    def map_pose_cov_last(self, K=None, D=None, camera=None, sigma_px: float = 1.0):
+        """map_pose_last with its covariance (fid_map_pose_last_cov_cam): (MAP_POSE_DTYPE records, MAP_POSE_COV_DTYPE records), one
+        of each per frame; cov["cov_cam_pose"] is the camera's covariance in the map frame."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        out = np.zeros(max(self._last_frames, 1), MAP_POSE_DTYPE)
+        cov = np.zeros(len(out), MAP_POSE_COV_DTYPE)
+        self._check(self._L.fid_map_pose_last_cov_cam(self._ctx, C.byref(cam.c), out.ctypes.data, len(out), float(sigma_px), cov.ctypes.data))
+        return out[:self._last_frames], cov[:self._last_frames]
+
+    def map_pose_cov(self, K=None, D=None, corners=None, ids=None, camera=None, sigma_px: float = 1.0):
+        """map_pose with its covariance (fid_map_pose_cov_cam): one MAP_POSE_DTYPE record and one MAP_POSE_COV_DTYPE record."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        mk = np.zeros(len(ids), _MARKER_DT)
+        mk["id"] = ids
+        mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        out = np.zeros(1, MAP_POSE_DTYPE)
+        cov = np.zeros(1, MAP_POSE_COV_DTYPE)
+        self._check(self._L.fid_map_pose_cov_cam(self._ctx, C.byref(cam.c), mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data,
+                                                 float(sigma_px), cov.ctypes.data))
+        return out[0], cov[0]
 
     # -- stage taps for parity tests ------------------------------------------------------------
     def tap(self, which: int) -> np.ndarray:

@@ -19,6 +19,7 @@ MARKER_DTYPE = np.dtype([("id", "i4"), ("shift", "i4"), ("corners", "f8", (4, 2)
                          ("lineInf", "f8", (3,)), ("projectiveDistortion", "f8"), ("code", "u8")])
 POSE_DTYPE = np.dtype([("id", "i4"), ("reserved", "i4"), ("rvec", "f8", (3,)), ("tvec", "f8", (3,)), ("R", "f8", (3, 3))])
 TAG_DTYPE = np.dtype([("id", "i4"), ("bundle", "i4"), ("corners", "f8", (4, 3)), ("center", "f8", (3,))])  # fid_stag_tag
+POSE_COV_DTYPE = np.dtype(_lib.POSE_COV_FIELDS)  # fid_pose_cov
 BUNDLE_POSE_DTYPE = np.dtype([("bundle", "i4"), ("n_tags", "i4"), ("rvec", "f8", (3,)), ("tvec", "f8", (3,)), ("R", "f8", (3, 3))])
 MAX_BUNDLES, MAX_TAGS_PER_BUNDLE, FRAME_LEN = 64, 12, 64  # FID_STAG_MAX_BUNDLES, FID_STAG_MAX_TAGS_PER_BUNDLE, FID_STAG_FRAME_LEN
 QUAD_DTYPE = np.dtype([("corners", "f8", (4, 2)), ("lineInf", "f8", (3,)), ("projectiveDistortion", "f8")])
@@ -233,6 +234,50 @@ class StagDetector:
         if rc != _lib.FID_OK:
             raise FidError(rc, self._L.fid_strerror(rc).decode())
         return out[:n.value].copy()
+
+    # -- the covariance of the poses (fid_abi.h: "pose covariance"): the twin's records and POSE_COV_DTYPE records beside them
+    @staticmethod
+    def _cov_camera(K, D, camera):
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        return cam
+
+    def pose_cov_last(self, K=None, D=None, marker_size: float = 0.0, camera=None, sigma_px: float = 1.0):
+        """pose_last with the covariance of every pose (fid_stag_pose_last_cov_cam): (POSE_DTYPE, POSE_COV_DTYPE) arrays."""
+        cam = self._cov_camera(K, D, camera)
+        out = np.zeros(4096, POSE_DTYPE)
+        cov = np.zeros(len(out), POSE_COV_DTYPE)
+        n = C.c_int32(0)
+        rc = self._L.fid_stag_pose_last_cov_cam(self._ctx, C.byref(cam.c), float(marker_size), out.ctypes.data, len(out), C.byref(n), float(sigma_px),
+                                                cov.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return out[:n.value].copy(), cov[:n.value].copy()
+
+    def bundle_pose_cov_last(self, K=None, D=None, camera=None, sigma_px: float = 1.0):
+        """bundle_pose_last with the covariance of every bundle pose (fid_stag_bundle_pose_last_cov_cam)."""
+        cam = self._cov_camera(K, D, camera)
+        out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
+        cov = np.zeros(len(out), POSE_COV_DTYPE)
+        n = C.c_int32(0)
+        rc = self._L.fid_stag_bundle_pose_last_cov_cam(self._ctx, C.byref(cam.c), out.ctypes.data, len(out), C.byref(n), float(sigma_px), cov.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return out[:n.value].copy(), cov[:n.value].copy()
+
+    def bundle_pose_cov(self, K=None, D=None, markers: np.ndarray = None, camera=None, sigma_px: float = 1.0):
+        """bundle_pose with the covariance of every bundle pose (fid_stag_bundle_pose_cov_cam)."""
+        cam = self._cov_camera(K, D, camera)
+        m = np.ascontiguousarray(markers, dtype=MARKER_DTYPE)
+        out = np.zeros(MAX_BUNDLES, BUNDLE_POSE_DTYPE)
+        cov = np.zeros(len(out), POSE_COV_DTYPE)
+        n = C.c_int32(0)
+        rc = self._L.fid_stag_bundle_pose_cov_cam(self._ctx, C.byref(cam.c), m.ctypes.data if len(m) else None, len(m), out.ctypes.data, len(out),
+                                                  C.byref(n), float(sigma_px), cov.ctypes.data)
+        if rc != _lib.FID_OK:
+            raise FidError(rc, self._L.fid_strerror(rc).decode())
+        return out[:n.value].copy(), cov[:n.value].copy()
 
     def queue_stats(self) -> tuple[int, int]:
         """(frames enqueued ahead of their own counts, how many of them had to be run again on the counted road)."""

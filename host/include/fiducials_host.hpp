@@ -79,6 +79,11 @@ struct ObjectHypothesisWithPose {  // vision_msgs/ObjectHypothesisWithPose (Noet
     Pose pose;
     std::array<double, 36> covariance{};
 };
+struct PoseWithCovarianceStamped {  // geometry_msgs/PoseWithCovarianceStamped
+    Header header;
+    Pose pose;
+    std::array<double, 36> covariance{};  // x, y, z, rotation about X, Y, Z (of the parent frame), row-major
+};
 struct Detection2D {  // vision_msgs/Detection2D: the node fills `results` only (header, bbox and source_img stay default)
     Header header;
     std::vector<ObjectHypothesisWithPose> results;
@@ -103,6 +108,9 @@ struct PoseOutputs {
     // with ~map_file set and at least one mapped fiducial in sight: the camera in the map (frame_id "map"), one solvePnP over the
     // corners of every mapped marker (fid_map_pose_last); empty otherwise
     std::vector<PoseStamped> map_pose;
+    // with ~pose_covariance set: the same pose with cov_cam_pose of fid_map_pose_last_cov_cam (frame_id "map"), beside map_pose,
+    // which stays what it is; empty otherwise
+    std::vector<PoseWithCovarianceStamped> map_pose_cov;
 };
 
 // ROS 1 wire format of the two output messages (little-endian, packed)
@@ -140,6 +148,10 @@ class FiducialsNode {
                                       // run the families whose shipped tables are fillers (4X4_1000, 6X6, 7X7, ARUCO_ORIGINAL)
         std::string map_file;  // non-empty: a fiducial_slam map file (fid_map_load_file; ~fiducial_len and ~fiducial_len_override give
                                // the lengths); poseEstimateCallback then also reports the camera in the map (PoseOutputs::map_pose)
+        // fill ObjectHypothesisWithPose::covariance with the pose's covariance (fid_abi.h, "pose covariance": cov_pose; 36 zeros for
+        // a record whose status is not 0) and report PoseOutputs::map_pose_cov; off: every output is what it was
+        bool pose_covariance = false;
+        double pose_covariance_sigma_px = 1.0;  // the corner noise in pixels; 0: the a-posteriori estimate from the residuals
         int device = 0, max_width = 1920, max_height = 1080;
         Params();
     };
@@ -211,6 +223,8 @@ class FiducialsNode {
     bool haveCamInfo = false, enable_detections = true, doPoseEstimation = true, verbose = false;
     bool vis_msgs = false, publishFiducialTf = true, publish_images = false;
     bool haveMap = false;
+    bool poseCovariance = false;
+    double poseCovarianceSigmaPx = 1.0;
     double fiducial_len = 0.14;
     int frameNum = 0;
     std::string frameId, last_error;

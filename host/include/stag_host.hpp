@@ -5,6 +5,7 @@
 // step) and points are plain structs.
 #ifndef STAG_HOST_HPP
 #define STAG_HOST_HPP
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -101,6 +102,18 @@ class Stag {
         p.resize((size_t)n);
         return p;
     }
+    // ... with the covariance of every pose (fid_stag_pose_last_cov_cam; sigma_px 0: a-posteriori); the poses are solvePnpSingle's
+    std::vector<fid_stag_pose_out> solvePnpSingleCov(const fid_camera &cam, double marker_size, double sigma_px, std::vector<fid_pose_cov> *cov)
+    {
+        std::vector<fid_stag_pose_out> p(markers.empty() ? 1 : markers.size());
+        cov->assign(p.size(), fid_pose_cov());
+        int32_t n = 0;
+        const fid_status rc = fid_stag_pose_last_cov_cam(ctx, &cam, marker_size, p.data(), (int32_t)p.size(), &n, sigma_px, cov->data());
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_pose_last_cov: ") + fid_strerror(rc));
+        p.resize((size_t)n);
+        cov->resize((size_t)n);
+        return p;
+    }
     // {FID_CAM_PLUMB_BOB, 5, K, D}
     static fid_camera plumbBob(const double K[9], const double D[5])
     {
@@ -131,6 +144,17 @@ class Stag {
         const fid_status rc = fid_stag_bundle_pose_last_cam(ctx, &cam, p.data(), (int32_t)p.size(), &n);
         if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_bundle_pose_last: ") + fid_strerror(rc));
         p.resize((size_t)n);
+        return p;
+    }
+    std::vector<fid_stag_bundle_pose_out> solvePnpBundleCov(const fid_camera &cam, double sigma_px, std::vector<fid_pose_cov> *cov)
+    {
+        std::vector<fid_stag_bundle_pose_out> p(FID_STAG_MAX_BUNDLES);
+        cov->assign(p.size(), fid_pose_cov());
+        int32_t n = 0;
+        const fid_status rc = fid_stag_bundle_pose_last_cov_cam(ctx, &cam, p.data(), (int32_t)p.size(), &n, sigma_px, cov->data());
+        if (rc != FID_OK) throw std::runtime_error(std::string("fid_stag_bundle_pose_last_cov: ") + fid_strerror(rc));
+        p.resize((size_t)n);
+        cov->resize((size_t)n);
         return p;
     }
 
@@ -256,6 +280,11 @@ class StagNode {
         std::vector<std::string> layout_frames;
         std::vector<uint8_t> layout_standalone;
         std::string bundles_topic = "stag_ros/bundles";
+        // fill ObjectHypothesisWithPose::covariance of `array` with the pose's covariance (fid_abi.h, "pose covariance": cov_pose of
+        // the pose that is published -- the marker's, or its bundle's for a standalone tag; 36 zeros for a record whose status is not
+        // 0); off: every output is what it was
+        bool pose_covariance = false;
+        double pose_covariance_sigma_px = 1.0;  // the corner noise in pixels; 0: the a-posteriori estimate from the residuals
     };
     struct Outputs {
         std::vector<PoseStamped> markers;  // Common::publishTransform, one message per marker, in marker order
@@ -516,11 +545,15 @@ class StagNode {
     void publishMarkers(const Header &header, Outputs *out)
     {
         const std::vector<Marker> markers = stag.getMarkerList();
-        const std::vector<fid_stag_pose_out> poses = stag.solvePnpSingle(camera, (double)params.marker_size);
+        std::vector<fid_pose_cov> covs, bcovs;
+        const std::vector<fid_stag_pose_out> poses = params.pose_covariance
+                                                         ? stag.solvePnpSingleCov(camera, (double)params.marker_size, params.pose_covariance_sigma_px, &covs)
+                                                         : stag.solvePnpSingle(camera, (double)params.marker_size);
         // with a layout: a member of a multi-tag bundle is not published on its own; a standalone tag of `tags:` is, posed from its
         // own corners and under its own frame; ids the layout does not name keep the marker_size pose
         std::vector<fid_stag_bundle_pose_out> bposes;
-        if (!params.layout_tags.empty()) bposes = stag.solvePnpBundle(camera);
+        if (!params.layout_tags.empty())
+            bposes = params.pose_covariance ? stag.solvePnpBundleCov(camera, params.pose_covariance_sigma_px, &bcovs) : stag.solvePnpBundle(camera);
         auto bundleOf = [this](int id) {  // getTagIndex / getBundleIndex (stag_nodelet.h:59-60)
             for (const fid_stag_tag &t : params.layout_tags)
                 if (t.id == id) return (int)t.bundle;
@@ -537,12 +570,16 @@ class StagNode {
         out->array.header = header;
         for (size_t i = 0; i < markers.size(); i++) {
             Pose pose = poseOf(poses[i].R, poses[i].tvec);
+            const fid_pose_cov *pcov = params.pose_covariance ? &covs[i] : nullptr;
             std::string id = std::to_string(markers[i].id);
             const int b = bundleOf(markers[i].id);
             if (b >= 0) {
                 if (!params.layout_standalone[(size_t)b]) continue;
-                for (const fid_stag_bundle_pose_out &bp : bposes)
-                    if (bp.bundle == b) pose = poseOf(bp.R, bp.tvec);
+                for (size_t k = 0; k < bposes.size(); k++)
+                    if (bposes[k].bundle == b) {
+                        pose = poseOf(bposes[k].R, bposes[k].tvec);
+                        if (params.pose_covariance) pcov = &bcovs[k];
+                    }
                 id = params.layout_frames[(size_t)b];
             }
             if (params.publish_tf) {  // Common::publishTransform: tf first, then the PoseStamped
@@ -564,6 +601,7 @@ class StagNode {
             ObjectHypothesisWithPose hyp;
             hyp.id = markers[i].id;
             hyp.pose = pose;
+            if (pcov && pcov->status == 0) std::copy(pcov->cov_pose, pcov->cov_pose + 36, hyp.covariance.begin());
             det.results.push_back(hyp);
             out->array.detections.push_back(det);
         }

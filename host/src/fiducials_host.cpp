@@ -171,6 +171,8 @@ FiducialsNode::FiducialsNode(const Params &p)
     verbose = p.verbose;
     publish_images = p.publish_images;      // (:609)
     vis_msgs = p.vis_msgs;                  // (:616)
+    poseCovariance = p.pose_covariance;
+    poseCovarianceSigmaPx = p.pose_covariance_sigma_px;
     publishFiducialTf = p.publish_fiducial_tf;  // (:614)
     handleIgnoreString(p.ignore_fiducials);
     handleLenOverrideString(p.fiducial_len_override);
@@ -596,7 +598,10 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
             if (it != fiducialLens.end()) lens[i] = it->second;
         }
         std::vector<fid_pose_out> poses(n > 0 ? n : 1);
-        const fid_status rc = fid_pose_cam(ctx, &camera, markers.data(), lens.data(), n, fiducial_len, poses.data());
+        std::vector<fid_pose_cov> covs(poseCovariance ? (size_t)(n > 0 ? n : 1) : 0);
+        const fid_status rc = poseCovariance ? fid_pose_cov_cam(ctx, &camera, markers.data(), lens.data(), n, fiducial_len, poses.data(),
+                                                                poseCovarianceSigmaPx, covs.data())
+                                             : fid_pose_cam(ctx, &camera, markers.data(), lens.data(), n, fiducial_len, poses.data());
         if (rc != FID_OK) {
             last_error = fid_last_error(ctx);
             return false;
@@ -616,6 +621,7 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
                 vmh.score = std::exp(-2 * poses[i].object_error);  // [0, infinity] -> [1, 0]
                 vmh.pose.px = t[0]; vmh.pose.py = t[1]; vmh.pose.pz = t[2];
                 vmh.pose.ox = qx; vmh.pose.oy = qy; vmh.pose.oz = qz; vmh.pose.ow = qw;
+                if (poseCovariance && covs[(size_t)i].status == 0) std::copy(covs[(size_t)i].cov_pose, covs[(size_t)i].cov_pose + 36, vmh.covariance.begin());
                 Detection2D vm;
                 vm.results.push_back(vmh);
                 po.vma.detections.push_back(vm);
@@ -644,14 +650,16 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
             // the camera among the map's fiducials: the markers of the last image are still on the device (fid_map_pose_last; the
             // detect call has run the kernel already once the camera is known); with ids ignored, the list without them
             fid_map_pose_out mp;
+            fid_map_pose_cov mcov;
             fid_status mrc;
             if (ignoreIds.empty()) {
-                mrc = fid_map_pose_last_cam(ctx, &camera, &mp, 1);
+                mrc = poseCovariance ? fid_map_pose_last_cov_cam(ctx, &camera, &mp, 1, poseCovarianceSigmaPx, &mcov) : fid_map_pose_last_cam(ctx, &camera, &mp, 1);
             } else {
                 std::vector<fid_marker> kept;
                 for (int i = 0; i < n; i++)
                     if (std::count(ignoreIds.begin(), ignoreIds.end(), ids[i]) == 0) kept.push_back(markers[(size_t)i]);
-                mrc = fid_map_pose_cam(ctx, &camera, kept.data(), (int32_t)kept.size(), &mp);
+                mrc = poseCovariance ? fid_map_pose_cov_cam(ctx, &camera, kept.data(), (int32_t)kept.size(), &mp, poseCovarianceSigmaPx, &mcov)
+                                     : fid_map_pose_cam(ctx, &camera, kept.data(), (int32_t)kept.size(), &mp);
             }
             if (mrc != FID_OK) {
                 last_error = fid_last_error(ctx);
@@ -683,6 +691,13 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
                 ps.pose.px = mp.cam_t[0]; ps.pose.py = mp.cam_t[1]; ps.pose.pz = mp.cam_t[2];
                 ps.pose.ox = q[0]; ps.pose.oy = q[1]; ps.pose.oz = q[2]; ps.pose.ow = q[3];
                 po.map_pose.push_back(ps);
+                if (poseCovariance) {
+                    PoseWithCovarianceStamped pc;
+                    pc.header = ps.header;
+                    pc.pose = ps.pose;
+                    if (mcov.pose.status == 0) std::copy(mcov.cov_cam_pose, mcov.cov_cam_pose + 36, pc.covariance.begin());
+                    po.map_pose_cov.push_back(pc);
+                }
             }
         }
     }

@@ -319,6 +319,72 @@ fid_status fid_map_pose_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marke
 fid_status fid_project_points_cam(fid_ctx *ctx, const fid_camera *cam, const double rvec[3], const double tvec[3],
                                   const double *obj_xyz, int32_t n, double *uv, double *jac);
 
+/* ---- pose covariance (additions to ABI 7: entry points and structs only).  How well the image determines a returned pose, from
+ * the same Jacobian the solver used, evaluated once more at the pose it returns.
+ *
+ * Notation:
+ * - `p = (rvec, tvec)` is the pose the kernel returns.
+ * - `N` is the number of points used.
+ * - `J` (2N x 6) is `d(u, v)/dp` at `p`. These are `project_one`'s analytic rows, i.e. `d/d rvec`, `d/d tvec` of the unrounded
+ *   projection under the caller's camera model.
+ * - `e` are the unrounded residuals at `p`.
+ *
+ * **Variance.**
+ * - `sigma_px > 0`: sigma^2 = `sigma_px^2`.
+ * - `sigma_px == 0`: sigma^2 = |e|^2 / (2N - 6). This is the a-posteriori estimate; 2N - 6 >= 2 always holds here.
+ * - `sigma_px` negative or not finite: `FID_E_INVALID_ARG`.
+ *
+ * **`cov_rt`.**
+ * - `cov_rt = sigma^2 (J^T J)^-1`, in `(rvec, tvec)` order, row-major.
+ * - Evaluate `J` at the returned `p`. `CvLevMarq` leaves its last normal equations at an earlier iterate, so do not reuse them.
+ * - Compute the inverse by LDL^T in f64. `solve6_spd`'s factorisation with lambda = 0 serves.
+ * - Multiply by sigma^2 as the last step.
+ *
+ * **`cov_pose`.**
+ * - This is the same uncertainty in `geometry_msgs/PoseWithCovariance` order: x, y, z, rotation about X, Y, Z.
+ * - The rotation perturbation is taken in the parent frame (the camera): `R(p + dp) ~ Exp(dtheta) R(p)`.
+ * - With `J_l(r) = I + (1 - cos theta)/theta^2 [r]x + (theta - sin theta)/theta^3 [r]x^2` and `theta = |r|`:
+ *   `dtheta = J_l(rvec) dr`.
+ * - For theta < 1e-4 use the series `I + 1/2 [r]x + 1/6 [r]x^2`.
+ * - `A = [[0, I3], [J_l, 0]]` and `cov_pose = A cov_rt A^T`.
+ *
+ * **`cov_cam_pose`** (map pose only).
+ * - This is the camera in the map frame, `(cam_R, cam_t) = (R^T, -R^T t)`, in the same order and convention with the map as parent.
+ * - `B = [[-R^T, -R^T [t]x], [0, -R^T]]` and `cov_cam_pose = B cov_pose B^T`.
+ *
+ * **Symmetry.** All three matrices are exactly symmetric. Compute one triangle and mirror it, so `c[i][j] == c[j][i]` bit for bit.
+ *
+ * **`status`.**
+ * - 0: valid.
+ * - 1: the record carries no pose, so every matrix is zero. This covers the equidistant model's "cannot be posed" record,
+ *   `n_markers == 0`, and a bundle with no tag found.  (The fid_stag_bundle_pose* entry points hand over only the bundles of which
+ *   a tag was found, as their twins do, so that last case never reaches their caller: from them status 1 means "cannot be posed".)
+ * - 2: an LDL^T pivot is <= 0 or not finite, so every matrix is zero.
+ *
+ * Each entry point below is the _cam call of the same name plus `sigma_px` and a covariance array parallel to the pose array, with
+ * the same indexing.  The pose records they fill are byte-identical to what the calls without _cov fill for the same inputs.
+ * fid_pose_last_cov_cam and fid_map_pose_last_cov_cam remember the camera as their twins do, and that the covariance was asked for
+ * and with which sigma_px: the next fid_detect* / fid_submit* runs the covariance form in its own stream, and the call after it is a
+ * copy (fid_pose_last_cov_cam: of the records the frames' counts need; the array on the device, max_batch x max_markers_per_frame
+ * x 592 bytes, comes with the first such call).  Where a frame has fewer markers than another of the call, the records beyond its
+ * count are not part of the result.  A later call without _cov still gets its usual bytes.  On a context with a batch in flight: FID_E_INVALID_ARG.  A context
+ * that never calls one of them allocates and launches what it always did. */
+typedef struct fid_pose_cov {
+    int32_t status, n_points;
+    double sigma2;          /* the variance used, px^2 */
+    double cov_rt[36];
+    double cov_pose[36];
+} fid_pose_cov;
+typedef struct fid_map_pose_cov { fid_pose_cov pose; double cov_cam_pose[36]; } fid_map_pose_cov;
+fid_status fid_pose_cov_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                            double fiducial_len, fid_pose_out *out, double sigma_px, fid_pose_cov *cov);
+fid_status fid_pose_last_cov_cam(fid_ctx *ctx, const fid_camera *cam, double fiducial_len, fid_pose_out *out, int32_t cap_per_frame,
+                                 double sigma_px, fid_pose_cov *cov);
+fid_status fid_map_pose_last_cov_cam(fid_ctx *ctx, const fid_camera *cam, fid_map_pose_out *out, int32_t cap_frames, double sigma_px,
+                                     fid_map_pose_cov *cov);
+fid_status fid_map_pose_cov_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, int32_t n, fid_map_pose_out *out,
+                                double sigma_px, fid_map_pose_cov *cov);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
@@ -614,6 +680,14 @@ fid_status fid_stag_detect_bundles_batch_device_cam(fid_stag_ctx *const *ctxs, i
                                                     const fid_camera *cam, double marker_size, fid_stag_marker *markers,
                                                     fid_stag_pose_out *poses, int32_t cap_per_frame, int32_t *n_per_frame,
                                                     fid_stag_bundle_pose_out *bundle_poses, int32_t *n_bundles_per_frame);
+
+/* the pose covariance of the STag poses ("pose covariance", above): the _cam call plus sigma_px and the parallel array */
+fid_status fid_stag_pose_last_cov_cam(fid_stag_ctx *ctx, const fid_camera *cam, double marker_size, fid_stag_pose_out *out, int32_t cap,
+                                      int32_t *n_out, double sigma_px, fid_pose_cov *cov);
+fid_status fid_stag_bundle_pose_last_cov_cam(fid_stag_ctx *ctx, const fid_camera *cam, fid_stag_bundle_pose_out *out, int32_t cap,
+                                             int32_t *n_out, double sigma_px, fid_pose_cov *cov);
+fid_status fid_stag_bundle_pose_cov_cam(fid_stag_ctx *ctx, const fid_camera *cam, const fid_stag_marker *markers, int32_t n,
+                                        fid_stag_bundle_pose_out *out, int32_t cap, int32_t *n_out, double sigma_px, fid_pose_cov *cov);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * JPEG ingest.  With the launch file's default `transport:=compressed` (aruco_detect/launch/aruco_detect.launch:6) the frames

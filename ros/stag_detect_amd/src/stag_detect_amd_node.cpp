@@ -133,6 +133,8 @@ class RosStagNode {
         pnh_.param("max_width", max_width, 1920);
         pnh_.param("max_height", max_height, 1080);
         pnh_.param("device", device, 0);
+        pnh_.param("pose_covariance", p.pose_covariance, p.pose_covariance);  // the hypotheses of markers_array carry their covariance
+        pnh_.param("pose_covariance_sigma_px", p.pose_covariance_sigma_px, p.pose_covariance_sigma_px);  // corner noise, pixels; 0: from the residuals
         pnh_.param("layout_file", p.layout_file, std::string());
         if (p.layout_file.empty()) loadTagsBundles(pnh_, &p);
         node_.reset(new fa::StagNode(p, data_dir, max_width, max_height, device));  // (throws std::invalid_argument like Stag::Stag)
@@ -272,6 +274,7 @@ class RosStagNode {
                 r.id = h.id;
                 r.score = h.score;
                 r.pose.pose = to_ros(h.pose);
+                for (size_t k = 0; k < 36; k++) r.pose.covariance[k] = h.covariance[k];  // (zeros unless ~pose_covariance)
                 o.results.push_back(r);
             }
             arr.detections.push_back(o);

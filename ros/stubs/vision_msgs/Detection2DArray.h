@@ -1,15 +1,12 @@
 #ifndef VISION_MSGS_DETECTION2DARRAY_STUB_H
 #define VISION_MSGS_DETECTION2DARRAY_STUB_H
+#include <geometry_msgs/PoseWithCovariance.h>
 #include <geometry_msgs/Transform.h>
 #include <sensor_msgs/Image.h>
 #include <std_msgs/Header.h>
 #include <array>
 #include <vector>
 namespace geometry_msgs {
-struct PoseWithCovariance {
-    Pose pose;
-    std::array<double, 36> covariance{};
-};
 struct Pose2D {
     double x = 0, y = 0, theta = 0;
 };
