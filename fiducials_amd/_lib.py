@@ -5,6 +5,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import build as _build
 
 
@@ -62,6 +64,11 @@ class FidCamera(C.Structure):
     _fields_ = [("model", C.c_int32), ("n_dist", C.c_int32), ("K", C.c_double * 9), ("D", C.c_double * 12)]
 
 
+class FidMapRobustOpts(C.Structure):
+    """fid_map_robust_opts: inlier_px (finite, > 0), min_markers (>= 1)."""
+    _fields_ = [("inlier_px", C.c_double), ("min_markers", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class FidLimits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_starts_per_frame", C.c_int32), ("max_contours_per_frame", C.c_int32),
@@ -107,6 +114,13 @@ CAM_PLUMB_BOB, CAM_RATIONAL, CAM_EQUIDISTANT = 0, 1, 2  # fid_camera_model
 # geometry_msgs/PoseWithCovariance order)
 POSE_COV_FIELDS = [("status", "<i4"), ("n_points", "<i4"), ("sigma2", "<f8"), ("cov_rt", "<f8", (6, 6)), ("cov_pose", "<f8", (6, 6))]
 MAP_MAX_ENTRIES, MAP_MAX_USED = 4096, 256  # FID_MAP_MAX_ENTRIES, FID_MAP_MAX_USED
+# fid_map_robust_out as a numpy record (fid_abi.h: "map pose that survives wrong markers"); status: MAP_ROBUST_*
+MAP_ROBUST_OK, MAP_ROBUST_NO_CONSENSUS, MAP_ROBUST_NO_MARKERS = 0, 1, 2
+MAP_ROBUST_HYPOTHESES, MAP_ROBUST_SOLVES = 64, 4  # FID_MAP_ROBUST_HYPOTHESES, FID_MAP_ROBUST_SOLVES
+MAP_ROBUST_INLIER_PX = 4.0  # the header's RECOMMENDED inlier_px (the ABI has no default)
+MAP_ROBUST_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_inliers", "<i4"), ("n_outliers", "<i4"), ("hypothesis", "<i4"),
+                             ("rounds", "<i4"), ("stable", "<i4"), ("reserved0", "<i4"), ("score", "<f8"), ("worst_inlier_px", "<f8"),
+                             ("best_outlier_px", "<f8"), ("outlier_mask", "<u8", (4,)), ("outlier_index", "<i4", (16,))])
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -121,6 +135,7 @@ SYMBOLS = [
     "fid_stag_pose_last_cam", "fid_stag_detect_markers_batch_cam", "fid_stag_detect_markers_batch_device_cam", "fid_stag_bundle_pose_last_cam",
     "fid_stag_bundle_pose_cam", "fid_stag_detect_bundles_batch_cam", "fid_stag_detect_bundles_batch_device_cam",
     "fid_pose_cov_cam", "fid_pose_last_cov_cam", "fid_map_pose_last_cov_cam", "fid_map_pose_cov_cam",
+    "fid_map_pose_robust_cam", "fid_map_pose_robust_last_cam",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -309,6 +324,10 @@ def load():
         L.fid_stag_pose_last_cov_cam.argtypes = [vp, cam, C.c_double, vp, i32, C.POINTER(i32), C.c_double, vp]
         L.fid_stag_bundle_pose_last_cov_cam.argtypes = [vp, cam, vp, i32, C.POINTER(i32), C.c_double, vp]
         L.fid_stag_bundle_pose_cov_cam.argtypes = [vp, cam, vp, i32, vp, i32, C.POINTER(i32), C.c_double, vp]
+    if hasattr(L, "fid_map_pose_robust_cam"):  # (the consensus map pose; FID_LIB may name a build from before it)
+        cam = C.POINTER(FidCamera)
+        L.fid_map_pose_robust_cam.argtypes = [vp, cam, vp, i32, C.POINTER(FidMapRobustOpts), vp, vp]
+        L.fid_map_pose_robust_last_cam.argtypes = [vp, cam, C.POINTER(FidMapRobustOpts), vp, vp, i32]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

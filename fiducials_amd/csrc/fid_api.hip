@@ -181,6 +181,13 @@ struct fid_ctx {
     bool map_cov = false, map_cov_done = false;
     double map_sigma = 0.;
     fid_map_pose_cov *d_mcov = nullptr, *h_mcov = nullptr;
+    // k_map_pose_robust (fid_map_pose_robust.hip): max_batch + 1 pose and robust records of its own, allocated by the first robust call;
+    // rob_cam_* / rob_opts / rob_done: as map_cam_* / map_done
+    fid_map_pose_out *d_rposes = nullptr, *h_rposes = nullptr;
+    fid_map_robust_out *d_mrob = nullptr, *h_mrob = nullptr;
+    bool rob_cam_valid = false, rob_done = false;
+    fid_camera rob_cam = {};
+    fid_map_robust_opts rob_opts = {};
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -196,6 +203,9 @@ struct fid_ctx {
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
                             const fid_camera &camera, fid_map_pose_out *d_out, bool with_cov = false, double sigma_px = 0.,
                             fid_map_pose_cov *d_cov = nullptr);
+// k_map_pose_robust for F frames on a stream (fid_map_pose_robust.hip, behind fid_map_pose.hip)
+static void map_pose_robust_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
+                                   const fid_camera &camera, const fid_map_robust_opts &opts, fid_map_pose_out *d_out, fid_map_robust_out *d_rout);
 
 namespace {
 
@@ -937,7 +947,9 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     c->map_done = false;
     c->pose_cov_done = false;
     c->map_cov_done = false;
+    c->rob_done = false;
     const bool map_ahead = c->map_n > 0 && c->map_cam_valid;
+    const bool rob_ahead = c->map_n > 0 && c->rob_cam_valid && c->d_mrob;
     if (map_ahead) {
         // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
         map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_cam, c->d_mposes,
@@ -947,6 +959,14 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_cam_valid ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
     if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
     if (map_ahead && c->map_cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st));
+    if (rob_ahead) {
+        // fid_map_pose_robust_last_cam asked before: the consensus pose of these frames, for the same camera and options
+        map_pose_robust_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->rob_cam,
+                               c->rob_opts, c->d_rposes, c->d_mrob);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_rposes, c->d_rposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->h_mrob, c->d_mrob, sizeof(fid_map_robust_out) * (size_t)F, hipMemcpyDeviceToHost, st));
+    }
     c->last_frames = F;
     c->last_W = W;
     c->last_H = H;
@@ -974,6 +994,7 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
     c->map_done = c->map_n > 0 && c->map_cam_valid;
     c->pose_cov_done = c->pose_done && c->pose_cov;
     c->map_cov_done = c->map_done && c->map_cov;
+    c->rob_done = c->map_n > 0 && c->rob_cam_valid && c->d_mrob;
     if (c->profile) {
         // a stage's time = its event-bracketed time on its own stream, summed over the sub-batches (with more than
         // one sub-batch the brackets of different streams overlap in wall time)
@@ -1333,10 +1354,10 @@ void fid_destroy(fid_ctx *c)
     void *dev[] = {c->d_in, c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
                    c->d_ident, c->d_bits, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
                    c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n,
-                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in, c->d_pcov, c->d_pcov_in, c->d_mcov};
+                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in, c->d_pcov, c->d_pcov_in, c->d_mcov, c->d_rposes, c->d_mrob};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {c->h_res, c->h_mposes, c->h_mcov};
+    void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     for (int i = 0; i <= ST_COUNT; i++)
@@ -2073,3 +2094,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_stag_layout.hip"
 #include "fid_map.hip"
 #include "fid_map_pose.hip"
+#include "fid_map_pose_robust.hip"

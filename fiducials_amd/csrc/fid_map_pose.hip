@@ -394,6 +394,7 @@ fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->map_done = false;
+    c->rob_done = false;
     if (n == 0) {
         c->map_n = 0;
         return FID_OK;

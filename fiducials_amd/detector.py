@@ -43,6 +43,28 @@ MAP_POSE_DTYPE = np.dtype([("n_markers", "<i4"), ("n_over", "<i4"), ("rvec", "<f
                            ("cam_R", "<f8", (3, 3)), ("cam_t", "<f8", (3,)), ("image_error", "<f8")])  # fid_map_pose_out
 POSE_COV_DTYPE = np.dtype(_lib.POSE_COV_FIELDS)  # fid_pose_cov
 MAP_POSE_COV_DTYPE = np.dtype([("pose", POSE_COV_DTYPE), ("cov_cam_pose", "<f8", (6, 6))])  # fid_map_pose_cov
+MAP_ROBUST_DTYPE = _lib.MAP_ROBUST_DTYPE  # fid_map_robust_out
+
+
+def map_robust_outlier_positions(rec) -> np.ndarray:
+    """The used-marker indices k (0 .. n_used - 1) whose bit is set in a MAP_ROBUST_DTYPE record's outlier_mask."""
+    mask = np.asarray(rec["outlier_mask"], np.uint64).reshape(4)
+    return np.array([k for k in range(int(rec["n_used"])) if (int(mask[k >> 6]) >> (k & 63)) & 1], np.int64)
+
+
+def map_robust_outlier_ids(rec, ids, map_ids) -> np.ndarray:
+    """The fiducial ids a MAP_ROBUST_DTYPE record leaves out, in list order: ids is the frame's id list as it was handed to the
+    call, map_ids the ids the context's map names.  The used markers are recounted as the kernel counts them (list order, ids the
+    map does not name skipped, an id seen twice left out altogether, the first MAP_MAX_USED kept) and the record's mask is read
+    against them."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    named = set(int(i) for i in np.asarray(map_ids).reshape(-1))
+    vals, counts = np.unique(ids, return_counts=True)
+    twice = set(int(v) for v, c in zip(vals, counts) if c > 1)
+    used = [int(i) for i in ids if int(i) in named and int(i) not in twice][:_lib.MAP_MAX_USED]
+    if len(used) != int(rec["n_used"]):
+        raise ValueError(f"the record counts {int(rec['n_used'])} used markers, this id list and map give {len(used)}")
+    return np.array([used[k] for k in map_robust_outlier_positions(rec)], np.int64)
 _POSE_DT = np.dtype([("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("image_error", "<f8"), ("object_error", "<f8"), ("fiducial_area", "<f8")])
 
 
@@ -452,6 +474,42 @@ class ArucoDetector:
         self._check(self._L.fid_map_pose_cov_cam(self._ctx, C.byref(cam.c), mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data,
                                                  float(sigma_px), cov.ctypes.data))
         return out[0], cov[0]
+
+    @staticmethod
+    def _robust_opts(inlier_px, min_markers):
+        if inlier_px is None:
+            raise ValueError("map_pose_robust needs inlier_px (recommended: _lib.MAP_ROBUST_INLIER_PX); the ABI has no default")
+        return _lib.FidMapRobustOpts(float(inlier_px), int(min_markers), 0)
+
+    def map_pose_robust(self, K=None, D=None, corners=None, ids=None, camera=None, inlier_px=None, min_markers: int = 2):
+        """The map pose by consensus on the markers of one frame handed in from the host (fid_map_pose_robust_cam): the pose from
+        the largest set of markers that agree within inlier_px pixels, and which markers were left out.  Returns one
+        MAP_POSE_DTYPE record and one MAP_ROBUST_DTYPE record; map_robust_outlier_ids turns the latter into ids."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        opts = self._robust_opts(inlier_px, min_markers)
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        mk = np.zeros(len(ids), _MARKER_DT)
+        mk["id"] = ids
+        mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        out = np.zeros(1, MAP_POSE_DTYPE)
+        rob = np.zeros(1, MAP_ROBUST_DTYPE)
+        self._check(self._L.fid_map_pose_robust_cam(self._ctx, C.byref(cam.c), mk.ctypes.data if len(mk) else None, len(mk), C.byref(opts),
+                                                    out.ctypes.data, rob.ctypes.data))
+        return out[0], rob[0]
+
+    def map_pose_robust_last(self, K=None, D=None, camera=None, inlier_px=None, min_markers: int = 2):
+        """map_pose_robust for every frame of the last detect_* / collect call, on the markers where they lie
+        (fid_map_pose_robust_last_cam): (MAP_POSE_DTYPE records, MAP_ROBUST_DTYPE records), one of each per frame."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        opts = self._robust_opts(inlier_px, min_markers)
+        out = np.zeros(max(self._last_frames, 1), MAP_POSE_DTYPE)
+        rob = np.zeros(len(out), MAP_ROBUST_DTYPE)
+        self._check(self._L.fid_map_pose_robust_last_cam(self._ctx, C.byref(cam.c), C.byref(opts), out.ctypes.data, rob.ctypes.data, len(out)))
+        return out[:self._last_frames], rob[:self._last_frames]
 
     # -- stage taps for parity tests ------------------------------------------------------------
     def tap(self, which: int) -> np.ndarray:

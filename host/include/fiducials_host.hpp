@@ -111,6 +111,9 @@ struct PoseOutputs {
     // with ~pose_covariance set: the same pose with cov_cam_pose of fid_map_pose_last_cov_cam (frame_id "map"), beside map_pose,
     // which stays what it is; empty otherwise
     std::vector<PoseWithCovarianceStamped> map_pose_cov;
+    // with ~map_outlier_px > 0: the fiducial ids that the consensus map pose left out (fid_map_robust_out's outlier_mask read against
+    // the used markers), in list order; on no consensus every used id.  Empty otherwise
+    std::vector<int32_t> map_outliers;
 };
 
 // ROS 1 wire format of the two output messages (little-endian, packed)
@@ -152,6 +155,12 @@ class FiducialsNode {
         // a record whose status is not 0) and report PoseOutputs::map_pose_cov; off: every output is what it was
         bool pose_covariance = false;
         double pose_covariance_sigma_px = 1.0;  // the corner noise in pixels; 0: the a-posteriori estimate from the residuals
+        // > 0: map_pose is the consensus pose (fid_abi.h, "map pose that survives wrong markers": fid_map_pose_robust_last_cam with
+        // this inlier_px -- the header recommends 4.0 -- and map_min_markers), empty on no consensus; the ids left out go to
+        // PoseOutputs::map_outliers, and map_pose_cov comes from fid_map_pose_cov_cam on the inliers.  0: off, every output is
+        // byte for byte what it was
+        double map_outlier_px = 0.0;
+        int map_min_markers = 2;
         int device = 0, max_width = 1920, max_height = 1080;
         Params();
     };
@@ -223,6 +232,9 @@ class FiducialsNode {
     bool haveCamInfo = false, enable_detections = true, doPoseEstimation = true, verbose = false;
     bool vis_msgs = false, publishFiducialTf = true, publish_images = false;
     bool haveMap = false;
+    std::vector<int> mapIds;  // the ids the map names, ascending (the used markers of a frame are recounted against it)
+    double mapOutlierPx = 0.0;
+    int mapMinMarkers = 2;
     bool poseCovariance = false;
     double poseCovarianceSigmaPx = 1.0;
     double fiducial_len = 0.14;

@@ -173,6 +173,8 @@ FiducialsNode::FiducialsNode(const Params &p)
     vis_msgs = p.vis_msgs;                  // (:616)
     poseCovariance = p.pose_covariance;
     poseCovarianceSigmaPx = p.pose_covariance_sigma_px;
+    mapOutlierPx = p.map_outlier_px;
+    mapMinMarkers = p.map_min_markers;
     publishFiducialTf = p.publish_fiducial_tf;  // (:614)
     handleIgnoreString(p.ignore_fiducials);
     handleLenOverrideString(p.fiducial_len_override);
@@ -211,6 +213,8 @@ FiducialsNode::FiducialsNode(const Params &p)
         }
         if (skipped > 0) last_error = "map_file " + p.map_file + ": " + std::to_string(skipped) + " invalid line(s) passed over";
         haveMap = n > 0;
+        for (int32_t i = 0; i < n; i++) mapIds.push_back(entries[(size_t)i].id);
+        std::sort(mapIds.begin(), mapIds.end());
     }
 }
 
@@ -652,7 +656,35 @@ bool FiducialsNode::poseEstimateCallback(const FiducialArray &msg, PoseOutputs *
             fid_map_pose_out mp;
             fid_map_pose_cov mcov;
             fid_status mrc;
-            if (ignoreIds.empty()) {
+            if (mapOutlierPx > 0.) {
+                // the consensus pose: the markers that agree, and the ids of those that do not (the used markers recounted as the
+                // kernel counts them: list order, ids the map does not name skipped, an id seen twice left out, the first 256)
+                std::vector<fid_marker> list;
+                for (int i = 0; i < n; i++)
+                    if (std::count(ignoreIds.begin(), ignoreIds.end(), ids[i]) == 0) list.push_back(markers[(size_t)i]);
+                const fid_map_robust_opts opts = {mapOutlierPx, mapMinMarkers, 0};
+                fid_map_robust_out rob;
+                mrc = ignoreIds.empty() ? fid_map_pose_robust_last_cam(ctx, &camera, &opts, &mp, &rob, 1)
+                                        : fid_map_pose_robust_cam(ctx, &camera, list.data(), (int32_t)list.size(), &opts, &mp, &rob);
+                if (mrc == FID_OK) {
+                    std::vector<fid_marker> inliers;
+                    int k = 0;
+                    for (size_t i = 0; i < list.size() && k < FID_MAP_MAX_USED; i++) {
+                        const int id = list[i].id;
+                        if (!std::binary_search(mapIds.begin(), mapIds.end(), id)) continue;
+                        if (std::count_if(list.begin(), list.end(), [id](const fid_marker &m) { return m.id == id; }) != 1) continue;
+                        if ((rob.outlier_mask[k >> 6] >> (k & 63)) & 1u)
+                            po.map_outliers.push_back(id);
+                        else
+                            inliers.push_back(list[i]);
+                        k++;
+                    }
+                    if (poseCovariance && mp.n_markers > 0) {  // (the same pose bytes again, and the covariance over the inliers)
+                        fid_map_pose_out again;
+                        mrc = fid_map_pose_cov_cam(ctx, &camera, inliers.data(), (int32_t)inliers.size(), &again, poseCovarianceSigmaPx, &mcov);
+                    }
+                }
+            } else if (ignoreIds.empty()) {
                 mrc = poseCovariance ? fid_map_pose_last_cov_cam(ctx, &camera, &mp, 1, poseCovarianceSigmaPx, &mcov) : fid_map_pose_last_cam(ctx, &camera, &mp, 1);
             } else {
                 std::vector<fid_marker> kept;

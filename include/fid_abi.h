@@ -385,6 +385,77 @@ fid_status fid_map_pose_last_cov_cam(fid_ctx *ctx, const fid_camera *cam, fid_ma
 fid_status fid_map_pose_cov_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, int32_t n, fid_map_pose_out *out,
                                 double sigma_px, fid_map_pose_cov *cov);
 
+/* ---- map pose that survives wrong markers: consensus, outliers reported (additions to ABI 7: entry points and structs only).
+ * fid_map_pose* trusts every mapped marker equally; one marker that is wrong -- an id read wrongly, a fiducial moved after the map
+ * was written, a map line with a wrong yaw, a reflection -- drags the pose and nothing in the record says so.  The calls below find
+ * the largest-agreeing set of markers deterministically (no random samples), pose the camera from that set with fid_map_pose_cam's
+ * own arithmetic, and say which markers were left out.  No OpenCV call does this; ITS MEANING IS FIXED HERE (restated in NumPy in
+ * tests/map_robust_restatement.py).  Per frame:
+ *
+ * - Used markers: exactly fid_map_pose's selection -- list order, ids the map does not name skipped, an id seen twice in the frame
+ *   left out altogether, the first FID_MAP_MAX_USED kept and the rest counted in n_over.  They are indexed k = 0 .. n_used - 1.
+ * - Eligible: a used marker all four of whose corners the camera model can undistort.  An ineligible marker (FID_CAM_EQUIDISTANT
+ *   only: a corner at or beyond 89 degrees) is an outlier from the start, never a hypothesis and never admitted -- for these calls
+ *   it does NOT void the frame.
+ * - err(p, j): the largest pixel distance, over the four corners of marker j, between the image corner (the float widened to
+ *   double) and the projection of its map object point under pose p by the camera model, in double, unrounded.
+ * - Hypotheses: at most FID_MAP_ROBUST_HYPOTHESES (64) eligible markers, those of largest image area (shoelace; on a tie the lower
+ *   k).  h_k is the closed-form pose of marker k alone (undistorted corners, the quad's homography, the pose from it) composed with
+ *   its place in the map.  score(k) is the LOWER MEDIAN of err(h_k, j) over all m eligible j: element (m - 1) / 2 of the ascending
+ *   list.  The winner k* has the smallest score (on a tie the lower k).
+ * - First set: I_0 = { j eligible : err(h_k*, j) <= max(inlier_px, 3 score(k*)) }.
+ * - Rounds r = 0, 1, ..., at most FID_MAP_ROBUST_SOLVES (4) solves: p_r = fid_map_pose_cam's solve (planarity test, start,
+ *   CvLevMarq) over the markers of I_r in list order; I_{r+1} = { j eligible : err(p_r, j) <= inlier_px } over ALL eligible markers
+ *   (a marker that the lever arm of a one-marker hypothesis kept out of I_0 comes back).  I_{r+1} == I_r: stop, stable = 1.
+ *   |I_{r+1}| < min_markers (or |I_0| < min_markers): stop, status FID_MAP_ROBUST_NO_CONSENSUS.  After the fourth solve: stop,
+ *   stable = 0.
+ * - Result: the fid_map_pose_out is p_r of the last set solved, byte for byte what fid_map_pose_cam returns for that subset of the
+ *   list; n_markers is the set's size, n_over as in the plain call.  On NO_CONSENSUS and with no used marker it is the all-zero
+ *   record.  The consensus follows the LARGEST coherent group as the median sees it: if more than half of the markers were moved
+ *   together rigidly, the pose is relative to them.
+ *
+ * inlier_px must be finite and > 0, min_markers >= 1 (else FID_E_INVALID_ARG); there is no default.  RECOMMENDED inlier_px: 4.0.
+ * Basis: over the rendered scenes of tests/aruco_map_cases.py with truthful maps, detected by the reference detector's restatement,
+ * the largest err of any marker under the all-marker cv::solvePnP pose was measured as 0.371 px (the six coplanar scenes, which
+ * that solvePnP restatement takes; on the three two-wall scenes, which it refuses, 1.69 px under the exact minimiser of the same
+ * error).  The recommendation is ten times 0.371, rounded up to half a pixel, so that a merely noisy marker is never dropped while a
+ * wrong marker is tens of pixels off.
+ *
+ * There is no _cov form: the covariance of the robust pose is fid_map_pose_cov_cam on the inlier markers.
+ * fid_map_pose_robust_last_cam works as fid_map_pose_last_cam does, on the markers where they lie: once called, the next
+ * fid_detect* / fid_submit* runs the kernel for the same camera and options in its own stream, and the call after it is a copy
+ * (FID_NO_POSE_AHEAD as for the others).  Refusals are the plain calls' own: no map, a batch in flight, capacity.  The results of
+ * fid_map_pose_last* and fid_pose_last* on the same batch are untouched; a context that never asks allocates and launches nothing. */
+#define FID_MAP_ROBUST_HYPOTHESES 64
+#define FID_MAP_ROBUST_SOLVES 4
+#define FID_MAP_ROBUST_OK 0
+#define FID_MAP_ROBUST_NO_CONSENSUS 1
+#define FID_MAP_ROBUST_NO_MARKERS 2 /* the map names none of the frame's markers */
+typedef struct fid_map_robust_opts {
+    double inlier_px;
+    int32_t min_markers;
+    int32_t reserved0; /* ignored */
+} fid_map_robust_opts;
+typedef struct fid_map_robust_out {
+    int32_t status;        /* FID_MAP_ROBUST_* */
+    int32_t n_used;        /* used markers (eligible or not) */
+    int32_t n_inliers;     /* the set the returned pose was solved over; 0 without a pose */
+    int32_t n_outliers;    /* n_used - n_inliers */
+    int32_t hypothesis;    /* LIST index of the winning marker k*, or -1 (no eligible marker) */
+    int32_t rounds;        /* solves run, 0 .. FID_MAP_ROBUST_SOLVES */
+    int32_t stable;        /* 1: the set the last solve's pose admits is the set it was solved over */
+    int32_t reserved0;     /* 0 */
+    double score;          /* score(k*), px; -1 without a hypothesis */
+    double worst_inlier_px;  /* largest err under the returned pose over the inliers; -1 where there is none */
+    double best_outlier_px;  /* smallest err under the returned pose over the ELIGIBLE outliers; -1 where there is none */
+    uint64_t outlier_mask[4];  /* bit (k % 64) of word k / 64: used marker k is an outlier (complete, however many) */
+    int32_t outlier_index[16]; /* LIST indices of the first 16 outliers in list order, -1 after them */
+} fid_map_robust_out;
+fid_status fid_map_pose_robust_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, int32_t n, const fid_map_robust_opts *opts,
+                                   fid_map_pose_out *pose_out, fid_map_robust_out *robust_out);
+fid_status fid_map_pose_robust_last_cam(fid_ctx *ctx, const fid_camera *cam, const fid_map_robust_opts *opts, fid_map_pose_out *pose_out,
+                                        fid_map_robust_out *robust_out, int32_t cap_frames);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
