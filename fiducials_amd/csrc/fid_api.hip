@@ -74,6 +74,11 @@ struct fid_ctx {
                          // survivors over 4 waves instead of 12 -- 1.13 M -> 0.70 M VALU wave-instructions a frame, lane utilisation 0.24 -> 0.33, same frame rate)
     int probe_refill0 = 0;  // FID_PROBE_REFILL0: the same for the first pass (0: k_probe_lut<6, 0>)
     int probe_refill = 4;  // FID_PROBE_REFILL: workgroups per frame of the refilled second probe pass (0: k_probe_lut<32, 1>)
+    int probe_passes = 1;   // FID_PROBE_PASSES: 1: a batch sieves its starts in ONE refilled pass (k_probe_refill<32, 2>: starts -> surv, surv1 / nsurv1 unused);
+                            // 2: the two passes (k_probe_lut<6, 0> + k_probe_refill<32, 1>), as calls of fewer than 16 frames always do.  Values other
+                            // than 1 and 2 are ignored.  The single pass is a refilled one: FID_PROBE_REFILL=0 (no refilled kernels) takes the two
+                            // passes whatever this says
+    int probe_single = 16;  // FID_PROBE_SINGLE: workgroups per frame of that single pass, clamped to 1 ... 64 (8 ... 32 measured alike)
     hipEvent_t sub_ev[MAX_SUB][20] = {};   // per sub-batch stage boundaries (FID_PROFILE)
     int sub_frames = 0;                    // frames per sub-batch (0 = automatic)
     fid_params params;
@@ -791,18 +796,24 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
             if (si != sa) HIPCHK(c, hipStreamWaitEvent(si, c->aux_fork[sb], 0));
             hipLaunchKernelGGL(k_seed_index, dim3(8 * gm, Fs), dim3(256), 0, si, seedq, seedhash, counts, P);
             HIPCHK(c, hipEventRecord(c->aux_idx[sb], si));
-            if (c->probe_refill0 && gm == 1)
-                hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(c->probe_refill0, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
+            const bool single_pass = c->probe_passes == 1 && c->probe_refill && gm == 1;
+            if (single_pass) {  // (batches: one pass over every start)
+                hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 2>), dim3(c->probe_single, Fs), dim3(256), 0, sa, masks, starts, surv, counts, c->d_global, P,
                                    (const uint4 *)c->d_probe_tables);
-            else
-                hipLaunchKernelGGL((k_probe_lut<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
-                                   (const uint4 *)c->d_probe_tables);
-            if (c->probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
-                hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(c->probe_refill, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                   (const uint4 *)c->d_probe_tables);
-            else
-                hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                   (const uint4 *)c->d_probe_tables);
+            } else {
+                if (c->probe_refill0 && gm == 1)
+                    hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(c->probe_refill0, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
+                                       (const uint4 *)c->d_probe_tables);
+                else
+                    hipLaunchKernelGGL((k_probe_lut<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
+                                       (const uint4 *)c->d_probe_tables);
+                if (c->probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
+                    hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(c->probe_refill, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
+                                       (const uint4 *)c->d_probe_tables);
+                else
+                    hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
+                                       (const uint4 *)c->d_probe_tables);
+            }
             const int wb3 = c->walk2_div > 0 ? (wb / c->walk2_div > 0 ? wb / c->walk2_div : 1) : wb2;
             hipLaunchKernelGGL(k_walk_full<2>, dim3(wb3, Fs), dim3(64 * WALK_WAVES), 0, sa, masks, surv, wres, tab, pool, segs, pend, counts,
                                c->d_global, P);
@@ -1286,6 +1297,14 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     if (getenv("FID_WALK2_DIV")) c->walk2_div = atoi(getenv("FID_WALK2_DIV"));
     if (getenv("FID_PROBE_REFILL")) c->probe_refill = atoi(getenv("FID_PROBE_REFILL"));
     if (getenv("FID_PROBE_REFILL0")) c->probe_refill0 = atoi(getenv("FID_PROBE_REFILL0"));
+    if (getenv("FID_PROBE_PASSES")) {  // (1 or 2; anything else leaves the default)
+        const int v = atoi(getenv("FID_PROBE_PASSES"));
+        if (v == 1 || v == 2) c->probe_passes = v;
+    }
+    if (getenv("FID_PROBE_SINGLE")) {  // (1 ... 64 workgroups a frame, the range of the sweep; clamped)
+        const int v = atoi(getenv("FID_PROBE_SINGLE"));
+        c->probe_single = v < 1 ? 1 : (v > 64 ? 64 : v);
+    }
     if (getenv("FID_CHAIN_AT")) c->chain_at = atoi(getenv("FID_CHAIN_AT"));
     if (!c->whole_border_walk) {
         TRY(dalloc(c, &c->d_segs, F * L.max_contours_per_frame));
@@ -2036,7 +2055,8 @@ fid_status fid_tap_read(fid_ctx *c, fid_tap which, void *dst, int64_t dst_bytes)
             o[12 * f + 5] = c->h_counts[f].nmark;
             o[12 * f + 6] = c->h_counts[f].overflow | ((int32_t)c->h_global->overflow << 8);
             o[12 * f + 7] = c->h_counts[f].nsurv;
-            o[12 * f + 8] = c->h_counts[f].npool;
+            // (cycle tracing: per frame, from the walks' lengths; the whole-border walk has only the allocator's head, in whole arenas)
+            o[12 * f + 8] = c->whole_border_walk ? c->h_counts[f].npool : c->h_counts[f].nchunks;
             o[12 * f + 9] = c->h_counts[f].nsurv1;
             o[12 * f + 11] = c->h_counts[f].ndense;  // contour points handed to approxPolyDP (every contour's rounded up to 8)
         }

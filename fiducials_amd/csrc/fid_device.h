@@ -170,7 +170,8 @@ struct DevCounts {
     int nstarts;    // border-following start candidates found by k_find_starts
     int ncontours;  // contour slots handed out by the full walk pass (dropped walks leave count == 0)
     int nsurv;      // starts that survived the probe pass
-    int npool;      // point chunks handed out by the full walk pass
+    int npool;      // point chunks the walker waves have taken from the pool, in whole arenas (the allocator's head: the sub-batch's first
+                    //   frame holds the launch's; how many waves take one depends on the order they reach the work queues in)
     int nwalk;      // survivors handed to walker waves so far (work queue head of the full pass)
     int nsurv1;     // starts that survived the first (short) probe pass
     int ndense;     // contour points copied to the dense point array so far
@@ -179,7 +180,9 @@ struct DevCounts {
     int nrec;       // copy records written by k_seg_cycles (pieces of accepted contours)
     int ncontours2; // cycle tracing: contours of the borders WITHOUT a seed (second list: [maxContours / 2, maxContours) of the frame's
     int nrec2;      //   contour arrays, second half of its record array), traced on the auxiliary stream beside the seed cycles
-    int pad[15];
+    int nchunks;    // cycle tracing: point chunks that the codes of the frame's recorded walks fill -- every seed's segment, every survivor
+                    //   walk that stopped at a seed state or was accepted (k_seg_cycles); the same in every run, unlike npool
+    int pad[14];
 };
 
 // global counters

@@ -1550,6 +1550,7 @@ __device__ __forceinline__ long long chunk_tab_at(const DevParams &P, int f, uns
 // long as its longest lane, so the starts are sieved twice before the full walk:
 //   LEVEL 0   every start, at most PROBE0_STEPS steps in each direction -> surv1   (kills ~90 %)
 //   LEVEL 1   surv1, at most PROBE1_STEPS steps                         -> surv
+//   LEVEL 2   every start, at most PROBE1_STEPS steps                   -> surv    (k_probe_refill only: batches of cycle tracing)
 // What is still undecided (or closed with a length that passes the perimeter gate) is appended to the next
 // list with one atomic per wave.  Contours shorter than a probe are rejected here for good when they fail
 // minMarkerPerimeterRate.
@@ -2429,8 +2430,21 @@ __global__ __launch_bounds__(256) void k_probe_lut(const uint32_t *__restrict__ 
 // PROBE_REFILL_MIN lanes are idle (or nobody is stepping) the finished ones hand in their verdict -- survivors collect in an LDS
 // list that leaves with one atomic per 64 -- and take the next starts of the share.  Start-up and one step are the statements of
 // k_probe_lut's loop, one step per trip; the decisions per start are the same, the order of the survivor list was never defined.
+// LEVEL 2 (the single sieve of the batch form): starts -> surv in ONE pass of PROBE1_STEPS steps.  The 6-step pass is a prefix of the
+// 32-step pass statement for statement -- both run this loop from the start pixel, and the only statement that names STEPS is the
+// `count >= STEPS` exit, which comes behind the closing test and leaves `ok` and `closed` alone -- so a start that the short pass
+// dropped is dropped here at the same step for the same reason, one that it kept undecided (count == 6, not closed) goes on here
+// exactly as the second pass re-walked it, and one that it kept CLOSED (count <= 6) closes here at the same count and meets the
+// same rule `minPerim <= count <= maxPerim`.  What the second pass repeated (its first PROBE0_STEPS steps on every start of surv1,
+// 40 % of its lane-steps), surv1 and the launch between the two are gone.  Most of the 38 k starts a frame die within four steps:
+// the pass refills when half of its lanes are idle (PROBE_SINGLE_MIN).  Not a tuned value: one run a point, 16 and 32 idle lanes
+// (and 8 ... 32 workgroups a frame) lie within the parent's own run-to-run spread; only 48 lanes (and 4 or 64 workgroups) were
+// clearly slower (profiles/r11_seedless_ab.txt).
 #ifndef PROBE_REFILL_MIN
 #define PROBE_REFILL_MIN 16
+#endif
+#ifndef PROBE_SINGLE_MIN
+#define PROBE_SINGLE_MIN 32
 #endif
 template <int STEPS, int LEVEL>
 __global__ __launch_bounds__(256) void k_probe_refill(const uint32_t *__restrict__ masks, const uint2 *__restrict__ in_list,
@@ -2482,7 +2496,7 @@ __global__ __launch_bounds__(256) void k_probe_refill(const uint32_t *__restrict
     int sdir = 0, i1x = 0, i1y = 0, bx = 0, by = 0, bf = 0, pb = 0, cx = 0, cy = 0, pc = 0;
     for (;;) {
         const unsigned long long running = ballot64(phase == PH_RUN);
-        if (running == 0 || 64 - __popcll(running) >= PROBE_REFILL_MIN) {
+        if (running == 0 || 64 - __popcll(running) >= (LEVEL == 2 ? PROBE_SINGLE_MIN : PROBE_REFILL_MIN)) {
             // ---- verdicts of the finished lanes
             const int keep = phase == PH_DONE && ok && (!closed || (count >= P.minPerim && count <= P.maxPerim));
             const unsigned long long mk = ballot64(keep);
@@ -3066,6 +3080,12 @@ __global__ WALKER_WG_ATTR(64, 256) void k_seg_cycles(const uint2 *__restrict__ s
             acc += *reinterpret_cast<const volatile uint32_t *>(reinterpret_cast<const char *>(fsg) + (size_t)k * 128u);
         asm volatile("" ::"v"(acc));
     }
+    // FID_TAP_COUNTS' pool chunks: what the codes of the frame's recorded walks fill, a sum over the records this kernel reads anyway.
+    // (The allocator's own count, counts[0].npool, goes up by a whole arena whenever a walker wave first needs a chunk or runs out;
+    //  how many waves that is depends on which wave wins which batch of the work queue, so it differs between runs of one call.)
+    // A walk that the pool had no chunk for leaves no length (SEG_INVALID, or p = 0 and z = 0) and is not in the sum: that call has
+    // the pool's overflow flag set, and which walks went without is the allocator's race again.
+    unsigned nck = 0;
     for (unsigned i0 = ibeg + blockIdx.x * 64; i0 < iend; i0 += gridDim.x * 64) {
         const unsigned i = i0 + lane;
         int accept = 0, hole = 0;
@@ -3073,6 +3093,7 @@ __global__ WALKER_WG_ATTR(64, 256) void k_seg_cycles(const uint2 *__restrict__ s
         uint2 st = make_uint2(0u, 0u);
         if (i < ns) {
             const DevSegC s = fsg[i];
+            if (s.n != SEG_INVALID) nck += (s.n + CK - 1u) / CK;
             if (s.n != SEG_INVALID && s.n != 0u && s.linked && (s.ko & s.kh) != 0xffffffffu) {
                 bool co = s.ko != 0xffffffffu, ch = s.kh != 0xffffffffu, closed = false;
                 unsigned KO = s.ko, KH = s.kh, cur = s.next_idx;
@@ -3125,8 +3146,11 @@ __global__ WALKER_WG_ATTR(64, 256) void k_seg_cycles(const uint2 *__restrict__ s
             }
         } else if (i < iend) {
             const unsigned j = i - ns;
-            if (!fpd[j].p) {  // decided by the survivor walk itself (a border without seeds): accepted iff it left a length
+            const unsigned walked = fpd[j].p;
+            nck += (walked + CK - 1u) / CK;
+            if (!walked) {  // decided by the survivor walk itself (a border without seeds): accepted iff it left a length
                 const uint4 w = wres[(long long)f * P.maxContours + j];
+                nck += (w.z + CK - 1u) / CK;
                 if (w.z) {
                     st = make_uint2(w.x, w.y);
                     L = w.z;
@@ -3195,6 +3219,8 @@ __global__ WALKER_WG_ATTR(64, 256) void k_seg_cycles(const uint2 *__restrict__ s
             }
         }
     }
+    nck = (unsigned)wave_sum_i32((int)nck);
+    if (lane == 0 && nck) atomicAdd((unsigned *)&counts[f].nchunks, nck);
 }
 
 // points per contour the first (short-LDS) launch of k_approx accepts

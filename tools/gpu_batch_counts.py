@@ -14,6 +14,6 @@ dev = torch.from_numpy(frames).cuda()
 det = ArucoDetector("DICT_5X5_250", max_width=1920, max_height=1080, max_batch=B, max_markers=64, max_candidates=2048)
 det.detect_markers_device(dev.data_ptr(), B, 1920, 1080, unpack=False)
 c = det.tap_counts()[:B].astype(np.float64)
-names = {0: "starts", 10: "seeds", 9: "surv1", 7: "survivors", 1: "contours", 11: "contour points", 8: "chunks", 2: "cands", 3: "filtered", 5: "markers"}
+names = {0: "starts", 10: "seeds", 9: "surv1", 7: "survivors", 1: "contours", 11: "contour points", 8: "chunks filled by recorded walks (not the pool's consumption)", 2: "cands", 3: "filtered", 5: "markers"}
 print("per frame (mean over %d frames):" % B, ", ".join(f"{n} {c[:, k].mean():.0f}" for k, n in names.items()))
 det.close()
