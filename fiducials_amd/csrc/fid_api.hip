@@ -27,6 +27,49 @@ static_assert(THRW_NT * THRW_WT >= 8191, "k_threshold_wide: a row per workgroup"
 
 }  // namespace
 
+struct fid_ctx;
+
+// What a fid_*_last* call asks for beside the markers of the last detect call.  The fields a kind of request does not have stay zero.
+struct PoseAsk {
+    fid_camera cam;             // (normalised: D beyond n_dist zero; the model is part of "the same camera")
+    double len;                 // marker pose: fiducial_len
+    bool cov;                   // marker pose and map pose: with the covariance ...
+    double sigma;               // ... at this sigma_px
+    fid_map_robust_opts opts;   // map pose by consensus: inlier_px, min_markers
+};
+
+// A remembered request: a fid_*_last* call that had to run its kernel remembers what it was asked.  The next fid_detect_* /
+// fid_submit_* then runs the same kernel for it in its own stream (under the other sub-batch's tail instead of after everything, and
+// without a second host round trip), and the same question after that call only hands the records over.  Same kernel, same
+// arithmetic, same results.  The context holds one for the marker pose, one for the map pose, one for the map pose by consensus.
+struct PoseRequest {
+    enum Kind { MARKER, MAP, MAP_ROBUST };
+    Kind kind;
+    PoseAsk ask = {};
+    bool armed = false;    // the next detect call computes it
+    bool at_hand = false;  // the records in pinned host memory (the marker pose's covariances: on the device) answer it
+    explicit PoseRequest(Kind k) : kind(k) {}
+    // armed, and what the kernel needs is there: a map, the robust records.  enqueue_detect launches by it, finish_detect marks by it
+    inline bool ahead(const fid_ctx *c) const;
+    // a batch was enqueued, or the map has changed: nothing is at hand
+    void forget() { at_hand = false; }
+    // the batch has finished: what was computed ahead is at hand
+    void finished(const fid_ctx *c) { at_hand = ahead(c); }
+    // are the records at hand the answer to `a`?  (Asked without the covariance where it was remembered with one: yes, and the
+    // covariance stays armed.  Asked with it where it was remembered without, or at another sigma_px: no.)
+    bool answers(const PoseAsk &a) const
+    {
+        return at_hand && !memcmp(&ask.cam, &a.cam, sizeof a.cam) && ask.len == a.len && ask.opts.inlier_px == a.opts.inlier_px &&
+               ask.opts.min_markers == a.opts.min_markers && (!a.cov || (ask.cov && ask.sigma == a.sigma));
+    }
+    // `a` was just computed behind the detect call: remember it, unless looking ahead is switched off (read per call: tests set it)
+    void answered(const PoseAsk &a)
+    {
+        ask = a;
+        armed = at_hand = getenv("FID_NO_POSE_AHEAD") == nullptr;
+    }
+};
+
 struct fid_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -155,44 +198,29 @@ struct fid_ctx {
     DevCounts *h_counts = nullptr;
     DevGlobal *h_global = nullptr;
     fid_pose_out *h_poses = nullptr;
-    // the camera of the last fid_pose_last call: the next fid_detect_* runs k_pose for it at the end of every sub-batch's stream
-    // (under the other sub-batch's tail instead of after everything, and without a second host round trip); fid_pose_last with the
-    // same camera then only hands the results over.  Same kernel, same arithmetic, same results.
-    bool pose_cam_valid = false, pose_done = false;
-    fid_camera pose_cam = {};  // (normalised: D beyond n_dist zero; the model is part of "the same camera")
-    double pose_len = 0.;
-    // the pose covariance (fid_pose_last_cov_cam; nothing of it exists until the first _cov call): whether the remembered camera's
-    // pose was asked for with its covariance and at which sigma_px -- the next fid_detect_* then runs k_pose_cov behind k_pose --,
-    // a fid_pose_cov beside every fid_pose_out of the context's largest call, on the device only (a _cov call copies out what the
-    // frames' counts need), and whether the poses at hand came with it
-    bool pose_cov = false, pose_cov_done = false;
-    double pose_sigma = 0.;
+    // the remembered requests (PoseRequest): fid_pose_last*: k_pose (+ k_pose_cov) at the end of every sub-batch's stream;
+    // fid_map_pose_last*: k_map_pose (or its COV form) behind them; fid_map_pose_robust_last_cam: k_map_pose_robust behind the result copy
+    PoseRequest pose_req{PoseRequest::MARKER}, map_req{PoseRequest::MAP}, rob_req{PoseRequest::MAP_ROBUST};
+    // the pose covariance (nothing of it exists until the first _cov call): a fid_pose_cov beside every fid_pose_out of the context's
+    // largest call, on the device only (a _cov call copies out what the frames' counts need)
     fid_pose_cov *d_pcov = nullptr;
     size_t pcov_cap = 0;
     fid_pose_cov *d_pcov_in = nullptr;  // fid_pose_cov_cam's, beside d_pose_in
     int pcov_in_cap = 0;
     // the map of fiducials (fid_set_map; nothing of it exists until the first one is set): its ids ascending, per entry the four
     // object points in the map frame; a fid_map_pose_out per frame of a batch and one more for fid_map_pose, on the device and in
-    // pinned host memory; room for markers handed in from the host.  map_cam_* / map_done: as pose_cam_* / pose_done, for k_map_pose
+    // pinned host memory; room for markers handed in from the host (stage_map_markers)
     int *d_map_ids = nullptr;
     double *d_map_obj = nullptr;
     int map_n = 0;
     fid_map_pose_out *d_mposes = nullptr, *h_mposes = nullptr;
     fid_marker *d_map_in = nullptr;
     int map_in_cap = 0;
-    bool map_cam_valid = false, map_done = false;
-    fid_camera map_cam = {};
-    // as pose_cov / pose_sigma / d_pcov, for k_map_pose_cov: max_batch + 1 records like d_mposes, allocated by the first _cov call
-    bool map_cov = false, map_cov_done = false;
-    double map_sigma = 0.;
+    // as d_pcov, for k_map_pose_cov: max_batch + 1 records like d_mposes, allocated by the first _cov call
     fid_map_pose_cov *d_mcov = nullptr, *h_mcov = nullptr;
-    // k_map_pose_robust (fid_map_pose_robust.hip): max_batch + 1 pose and robust records of its own, allocated by the first robust call;
-    // rob_cam_* / rob_opts / rob_done: as map_cam_* / map_done
+    // k_map_pose_robust (fid_map_pose_robust.hip): max_batch + 1 pose and robust records of its own, allocated by the first robust call
     fid_map_pose_out *d_rposes = nullptr, *h_rposes = nullptr;
     fid_map_robust_out *d_mrob = nullptr, *h_mrob = nullptr;
-    bool rob_cam_valid = false, rob_done = false;
-    fid_camera rob_cam = {};
-    fid_map_robust_opts rob_opts = {};
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -203,6 +231,8 @@ struct fid_ctx {
     float stage_ms[ST_COUNT] = {};
     std::string last_error;
 };
+
+inline bool PoseRequest::ahead(const fid_ctx *c) const { return armed && (kind == MARKER || c->map_n > 0) && (kind != MAP_ROBUST || c->d_mrob); }
 
 // k_map_pose for F frames on a stream (fid_map_pose.hip, at the end of this translation unit)
 static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
@@ -228,6 +258,24 @@ fid_status dalloc(fid_ctx *c, T **p, size_t count)
 {
     HIPCHK(c, hipMalloc((void **)p, count * sizeof(T)));
     return FID_OK;
+}
+
+// the refusals the entry points share: true, with the message set, when the call cannot go on
+bool refuse_in_flight(fid_ctx *c)
+{
+    if (c->in_flight) c->last_error = "a submitted batch is in flight: fid_collect first";
+    return c->in_flight;
+}
+bool refuse_no_map(fid_ctx *c)
+{
+    if (c->map_n == 0) c->last_error = "no map: fid_set_map first";
+    return c->map_n == 0;
+}
+bool refuse_room(fid_ctx *c, int cap_frames)
+{
+    if (cap_frames < c->last_frames)
+        c->last_error = "caller room for " + std::to_string(cap_frames) + " frames, the last call had " + std::to_string(c->last_frames);
+    return cap_frames < c->last_frames;
 }
 
 int roundup(int v, int m) { return (v + m - 1) / m * m; }
@@ -547,6 +595,11 @@ fid_status check_call(fid_ctx *c, int F, int W, int H, int stride, fid_encoding 
     return FID_OK;
 }
 
+// k_pose (+ k_pose_cov) on a stream.  Defined BEHIND enqueue_detect: the device code is emitted in the order in which the host code
+// first names the kernels, and the counter files under profiles/ are keyed to its bytes
+void pose_launch(fid_ctx *c, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const fid_marker *d_markers, const int *d_n, int n_stride_ints,
+                 const double *d_lens, int F, int per_frame, const PoseAsk &a, fid_pose_out *d_out, fid_pose_cov *d_cov);
+
 fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H, int stride, long long fstride, fid_encoding enc)
 {
     {
@@ -554,7 +607,6 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         if (rcv != FID_OK) return rcv;
     }
     hipStream_t st0 = c->stream;
-    c->pose_done = false;
     // ---- K0 geometry: mono8 device input is used in place (any stride); colour goes through k_to_gray
     const bool to_gray = enc != FID_ENC_MONO8;
     const int gstride = to_gray ? W : stride;
@@ -911,21 +963,9 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
                 hipLaunchKernelGGL(k_subpix<SP_MAXWIN_MAX>, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
         }
         mark(ST_SUBPIX + 1);
-        if (c->pose_cam_valid) {
-            const PoseCam cam = pose_cam_from(c->pose_cam, c->pose_len);
-            int blocks = (Fs * P.maxMarkers + 7) / 8;  // eight lanes per marker, eight markers per wave
-            blocks = blocks < 1 ? 1 : (blocks > 256 * 16 ? 256 * 16 : blocks);
-            if (c->profile) (void)hipEventRecord(ev[18], st);
-            POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers,
-                                                            (const int *)&counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)),
-                                                            (const double *)nullptr, Fs, P.maxMarkers, cam, c->d_poses + f0 * MM));
-            if (c->pose_cov)  // (fid_pose_last_cov_cam was the last to ask: the covariance of these poses, behind them)
-                POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose_cov<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, (const fid_marker *)markers,
-                                                                (const int *)&counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)),
-                                                                (const double *)nullptr, Fs, P.maxMarkers, cam,
-                                                                (const fid_pose_out *)(c->d_poses + f0 * MM), c->pose_sigma, c->d_pcov + f0 * MM));
-            if (c->profile) (void)hipEventRecord(ev[19], st);
-        }
+        if (c->pose_req.ahead(c))  // (the remembered marker pose; where fid_pose_last_cov_cam was the last to ask, its covariance behind it)
+            pose_launch(c, st, ev[18], ev[19], markers, &counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, Fs, P.maxMarkers,
+                        c->pose_req.ask, c->d_poses + f0 * MM, c->d_pcov ? c->d_pcov + f0 * MM : nullptr);
         chain_point(99);
         if (nsub > 1) {
             HIPCHK(c, hipEventRecord(c->sub_done[sb], st));
@@ -954,26 +994,24 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     const DevParams &P = c->P;
     HIPCHK(c, hipGetLastError());
     // ---- results
-    c->pose_done = false;
-    c->map_done = false;
-    c->pose_cov_done = false;
-    c->map_cov_done = false;
-    c->rob_done = false;
-    const bool map_ahead = c->map_n > 0 && c->map_cam_valid;
-    const bool rob_ahead = c->map_n > 0 && c->rob_cam_valid && c->d_mrob;
+    c->pose_req.forget();
+    c->map_req.forget();
+    c->rob_req.forget();
+    const bool map_ahead = c->map_req.ahead(c);
+    const PoseAsk &ma = c->map_req.ask;
     if (map_ahead) {
         // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
-        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->map_cam, c->d_mposes,
-                        c->map_cov, c->map_sigma, c->d_mcov);
+        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, ma.cam, c->d_mposes, ma.cov,
+                        ma.sigma, c->d_mcov);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_cam_valid ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
+    HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_req.ahead(c) ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
     if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
-    if (map_ahead && c->map_cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st));
-    if (rob_ahead) {
+    if (map_ahead && ma.cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st));
+    if (c->rob_req.ahead(c)) {
         // fid_map_pose_robust_last_cam asked before: the consensus pose of these frames, for the same camera and options
-        map_pose_robust_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->rob_cam,
-                               c->rob_opts, c->d_rposes, c->d_mrob);
+        map_pose_robust_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->rob_req.ask.cam,
+                               c->rob_req.ask.opts, c->d_rposes, c->d_mrob);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_rposes, c->d_rposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(c->h_mrob, c->d_mrob, sizeof(fid_map_robust_out) * (size_t)F, hipMemcpyDeviceToHost, st));
@@ -992,6 +1030,22 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     return FID_OK;
 }
 
+// k_pose for F frames of per_frame markers on a stream, for a.cov with k_pose_cov behind it; under FID_PROFILE between two events
+void pose_launch(fid_ctx *c, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const fid_marker *d_markers, const int *d_n, int n_stride_ints,
+                 const double *d_lens, int F, int per_frame, const PoseAsk &a, fid_pose_out *d_out, fid_pose_cov *d_cov)
+{
+    const PoseCam cam = pose_cam_from(a.cam, a.len);
+    int blocks = (F * per_frame + 7) / 8;  // eight lanes per marker, eight markers per wave
+    blocks = blocks < 1 ? 1 : (blocks > 256 * 16 ? 256 * 16 : blocks);
+    if (c->profile) (void)hipEventRecord(ev0, st);
+    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, d_markers, d_n, n_stride_ints, d_lens, F,
+                                                    per_frame, cam, d_out));
+    if (a.cov)
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose_cov<CAM_MODEL>, dim3(blocks), dim3(64), 0, st, d_markers, d_n, n_stride_ints, d_lens, F,
+                                                        per_frame, cam, (const fid_pose_out *)d_out, a.sigma, d_cov));
+    if (c->profile) (void)hipEventRecord(ev1, st);
+}
+
 fid_status run_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H, int stride, long long fstride, fid_encoding enc,
                       fid_marker *out, int cap_per_frame, int *n_per_frame);
 
@@ -1001,11 +1055,9 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
     const int F = c->pend.F;
     c->in_flight = false;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->pose_done = c->pose_cam_valid;
-    c->map_done = c->map_n > 0 && c->map_cam_valid;
-    c->pose_cov_done = c->pose_done && c->pose_cov;
-    c->map_cov_done = c->map_done && c->map_cov;
-    c->rob_done = c->map_n > 0 && c->rob_cam_valid && c->d_mrob;
+    c->pose_req.finished(c);
+    c->map_req.finished(c);
+    c->rob_req.finished(c);
     if (c->profile) {
         // a stage's time = its event-bracketed time on its own stream, summed over the sub-batches (with more than
         // one sub-batch the brackets of different streams overlap in wall time)
@@ -1020,7 +1072,7 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
                 float ms = 0.f;
                 if (hipEventElapsedTime(&ms, c->sub_ev[sb][14], c->sub_ev[sb][15]) == hipSuccess) c->stage_ms[ST_SEEDWALK] += ms;
                 if (hipEventElapsedTime(&ms, c->sub_ev[sb][16], c->sub_ev[sb][17]) == hipSuccess) c->stage_ms[ST_SEEDLESS] += ms;
-                if (c->pose_cam_valid && hipEventElapsedTime(&ms, c->sub_ev[sb][18], c->sub_ev[sb][19]) == hipSuccess) c->stage_ms[ST_POSE] += ms;
+                if (c->pose_req.at_hand && hipEventElapsedTime(&ms, c->sub_ev[sb][18], c->sub_ev[sb][19]) == hipSuccess) c->stage_ms[ST_POSE] += ms;
             }
     }
 #ifdef FID_DEBUG_STATS
@@ -1097,8 +1149,7 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
 fid_status run_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H, int stride, long long fstride, fid_encoding enc,
                       fid_marker *out, int cap_per_frame, int *n_per_frame)
 {
-    if (!out || !n_per_frame || cap_per_frame < 0 || c->in_flight) {
-        if (c->in_flight) c->last_error = "a submitted batch is in flight: fid_collect first";
+    if (refuse_in_flight(c) || !out || !n_per_frame || cap_per_frame < 0) {
         c->wait_ev = c->wait_copy_ev = nullptr;  // (fid_order_after holds for one call, refused or not)
         c->chained = false;
         return FID_E_INVALID_ARG;
@@ -1482,9 +1533,8 @@ fid_status fid_submit_device(fid_ctx *c, const void *d_imgs, int32_t nframes, in
 {
     if (!c) return FID_E_INVALID_ARG;
     fid_status rc = FID_E_INVALID_ARG;
-    const bool was_in_flight = c->in_flight;
-    if (was_in_flight) c->last_error = "a submitted batch is in flight: fid_collect first";
-    else if (d_imgs) {
+    const bool was_in_flight = refuse_in_flight(c);
+    if (!was_in_flight && d_imgs) {
         const hipError_t dev_rc = hipSetDevice(c->device);
         if (dev_rc == hipSuccess) rc = enqueue_detect(c, (const uint8_t *)d_imgs, nframes, width, height, stride, frame_stride, enc);
         else {
@@ -1549,11 +1599,7 @@ static fid_status feed_and_enqueue_impl(fid_ctx *c, const uint8_t *imgs, int32_t
                                         int64_t frame_stride, fid_encoding enc)
 {
     if (!c || !imgs || nframes < 1 || height < 1 || stride < 1) return FID_E_INVALID_ARG;
-    if (nframes > c->lim.max_batch) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
+    if (nframes > c->lim.max_batch || refuse_in_flight(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     if (frame_stride < (int64_t)stride * height) return FID_E_INVALID_ARG;
     {
@@ -1652,22 +1698,11 @@ fid_status fid_detect(fid_ctx *c, const uint8_t *img, int32_t width, int32_t hei
     return fid_detect_batch(c, img, 1, width, height, stride, (int64_t)stride * height, enc, out, cap, n);
 }
 
-static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d_n, int n_stride_ints, const double *d_lens,
-                           int F, int per_frame, const fid_camera &camera, double fiducial_len, fid_pose_out *d_out, bool with_cov = false,
-                           double sigma_px = 0., fid_pose_cov *d_cov = nullptr)
+// k_pose (+ k_pose_cov) on the context's stream, timed as the pose stage
+static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d_n, int n_stride_ints, const double *d_lens, int F, int per_frame,
+                           const PoseAsk &a, fid_pose_out *d_out, fid_pose_cov *d_cov)
 {
-    const PoseCam cam = pose_cam_from(camera, fiducial_len);
-    int total = F * per_frame;
-    int blocks = (total + 7) / 8;  // eight lanes per marker, eight markers per wave
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    if (c->profile) (void)hipEventRecord(c->ev[ST_POSE], c->stream);
-    POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose<CAM_MODEL>, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens, F,
-                                                    per_frame, cam, d_out));
-    if (with_cov)
-        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_pose_cov<CAM_MODEL>, dim3(blocks), dim3(64), 0, c->stream, d_markers, d_n, n_stride_ints, d_lens,
-                                                        F, per_frame, cam, (const fid_pose_out *)d_out, sigma_px, d_cov));
-    if (c->profile) (void)hipEventRecord(c->ev[ST_POSE + 1], c->stream);
+    pose_launch(c, c->stream, c->ev[ST_POSE], c->ev[ST_POSE + 1], d_markers, d_n, n_stride_ints, d_lens, F, per_frame, a, d_out, d_cov);
     HIPCHK(c, hipGetLastError());
     return FID_OK;
 }
@@ -1699,33 +1734,19 @@ static fid_status pose_last_run(fid_ctx *c, const fid_camera *camera, double fid
 {
     if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
     if (with_cov && (!cov || !fid_sigma_usable(sigma_px))) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const int F = c->last_frames, MM = c->P.maxMarkers;
-    const fid_camera cam = fid_camera_normalised(*camera);
-    const bool same_cam = c->pose_cam_valid && !memcmp(&c->pose_cam, &cam, sizeof cam) && c->pose_len == fiducial_len;
-    // (done: the detect call already ran k_pose -- and, asked for with this sigma_px, k_pose_cov -- for this camera on these markers)
-    const bool done = same_cam && c->pose_done && (!with_cov || (c->pose_cov && c->pose_sigma == sigma_px && c->pose_cov_done));
+    const PoseAsk ask = {fid_camera_normalised(*camera), fiducial_len, with_cov, sigma_px, {}};
     fid_status rc = with_cov ? ensure_pose_cov(c) : FID_OK;
     if (rc != FID_OK) return rc;
-    if (!done) {
-        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, cam, fiducial_len, c->d_poses, with_cov,
-                      sigma_px, c->d_pcov);
+    if (!c->pose_req.answers(ask)) {  // (else the detect call already ran k_pose -- and k_pose_cov -- for this camera on these markers)
+        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, ask, c->d_poses, c->d_pcov);
         if (rc != FID_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_poses, c->d_poses, sizeof(fid_pose_out) * (size_t)F * MM, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->profile) (void)hipEventElapsedTime(&c->stage_ms[ST_POSE], c->ev[ST_POSE], c->ev[ST_POSE + 1]);
-        c->pose_cam = cam;
-        c->pose_len = fiducial_len;
-        c->pose_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
-        c->pose_done = c->pose_cam_valid;
-        // (asked for without its covariance: the next call runs k_pose alone)
-        c->pose_cov = with_cov && c->pose_cam_valid;
-        c->pose_sigma = sigma_px;
-        c->pose_cov_done = c->pose_cov;
+        c->pose_req.answered(ask);  // (asked for without its covariance: the next call runs k_pose alone)
     }
     int nmax = 0;
     for (int f = 0; f < F; f++) {
@@ -1767,22 +1788,6 @@ fid_status fid_pose(fid_ctx *c, const double K[9], const double D[5], const fid_
 }
 
 static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
-                               double fiducial_len, fid_pose_out *out, bool with_cov, double sigma_px, fid_pose_cov *cov);
-
-fid_status fid_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
-                        double fiducial_len, fid_pose_out *out)
-{
-    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, false, 0., nullptr);
-}
-
-fid_status fid_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
-                            double fiducial_len, fid_pose_out *out, double sigma_px, fid_pose_cov *cov)
-{
-    if (!fid_sigma_usable(sigma_px) || (n > 0 && !cov)) return FID_E_INVALID_ARG;
-    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, true, sigma_px, cov);
-}
-
-static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
                                double fiducial_len, fid_pose_out *out, bool with_cov, double sigma_px, fid_pose_cov *cov)
 {
     if (!c || !fid_camera_usable(camera) || (n > 0 && (!markers || !out)) || n < 0 || !(fiducial_len > 0)) return FID_E_INVALID_ARG;
@@ -1790,7 +1795,7 @@ static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_m
     if (len_per_marker)
         for (int i = 0; i < n; i++)
             if (!(len_per_marker[i] > 0)) return FID_E_INVALID_ARG;  // CV_Assert(markerLength > 0), aruco_detect.cpp:229
-    if (c->in_flight) return FID_E_INVALID_ARG;  // (shares the context's stream and buffers with the batch in flight)
+    if (refuse_in_flight(c)) return FID_E_INVALID_ARG;  // (shares the context's stream and buffers with the batch in flight)
     HIPCHK(c, hipSetDevice(c->device));
     if (n > c->pose_cap) {
         if (c->d_pose_in) (void)hipFree(c->d_pose_in);
@@ -1818,7 +1823,7 @@ static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_m
         HIPCHK(c, hipMalloc((void **)&c->d_pcov_in, sizeof(fid_pose_cov) * (size_t)c->pose_cap));
         c->pcov_in_cap = c->pose_cap;
     }
-    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, *camera, fiducial_len, d_out, with_cov, sigma_px, c->d_pcov_in);
+    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, {*camera, fiducial_len, with_cov, sigma_px, {}}, d_out, c->d_pcov_in);
     if (rc != FID_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_pose_out) * n, hipMemcpyDeviceToHost, c->stream));
     if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, c->d_pcov_in, sizeof(fid_pose_cov) * n, hipMemcpyDeviceToHost, c->stream));
@@ -1826,15 +1831,25 @@ static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_m
     return FID_OK;
 }
 
+fid_status fid_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                        double fiducial_len, fid_pose_out *out)
+{
+    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, false, 0., nullptr);
+}
+
+fid_status fid_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, const double *len_per_marker, int32_t n,
+                            double fiducial_len, fid_pose_out *out, double sigma_px, fid_pose_cov *cov)
+{
+    if (!fid_sigma_usable(sigma_px) || (n > 0 && !cov)) return FID_E_INVALID_ARG;
+    return pose_cam_run(c, camera, markers, len_per_marker, n, fiducial_len, out, true, sigma_px, cov);
+}
+
 fid_status fid_project_points_cam(fid_ctx *c, const fid_camera *camera, const double rvec[3], const double tvec[3], const double *obj_xyz,
                                   int32_t n, double *uv, double *jac)
 {
     if (!c || !fid_camera_usable(camera) || !rvec || !tvec || n < 0 || (n > 0 && (!obj_xyz || !uv))) return FID_E_INVALID_ARG;
     if (n == 0) return FID_OK;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     // one block of device memory for the call: the points, the projections, the Jacobian rows (a utility, not a hot path)
     const size_t nn = (size_t)n;
@@ -1918,10 +1933,7 @@ fid_status fid_refine_contour_corners(fid_ctx *c, const int32_t *pts_xy, const i
                                       int32_t *status_per_marker)
 {
     if (!c || !pts_xy || !offsets || !corners || !status_per_marker || n < 0) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c)) return FID_E_INVALID_ARG;
     if (n == 0) return FID_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (offsets[0] != 0) return FID_E_INVALID_ARG;

@@ -364,11 +364,7 @@ static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_mark
 
 fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
 {
-    if (!c || n < 0 || (n > 0 && !entries)) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
+    if (!c || n < 0 || (n > 0 && !entries) || refuse_in_flight(c)) return FID_E_INVALID_ARG;
     if (n > FID_MAP_MAX_ENTRIES) {
         c->last_error = "a map holds at most " + std::to_string(FID_MAP_MAX_ENTRIES) + " entries (FID_MAP_MAX_ENTRIES), not " + std::to_string(n);
         return FID_E_UNSUPPORTED;
@@ -393,8 +389,8 @@ fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
         }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->map_done = false;
-    c->rob_done = false;
+    c->map_req.forget();  // (the poses at hand are the old map's)
+    c->rob_req.forget();
     if (n == 0) {
         c->map_n = 0;
         return FID_OK;
@@ -444,42 +440,23 @@ static fid_status map_pose_last_run(fid_ctx *c, const fid_camera *camera, fid_ma
 {
     if (!c || !fid_camera_usable(camera) || !out || c->last_frames <= 0) return FID_E_INVALID_ARG;
     if (with_cov && (!cov || !fid_sigma_usable(sigma_px))) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
-    if (c->map_n == 0) {
-        c->last_error = "no map: fid_set_map first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
+    if (refuse_room(c, cap_frames)) return FID_E_CAPACITY;
     const int F = c->last_frames;
-    if (cap_frames < F) {
-        c->last_error = "caller room for " + std::to_string(cap_frames) + " frames, the last call had " + std::to_string(F);
-        return FID_E_CAPACITY;
-    }
     HIPCHK(c, hipSetDevice(c->device));
     if (with_cov) {
         const fid_status rca = ensure_map_cov(c);
         if (rca != FID_OK) return rca;
     }
-    const fid_camera cam = fid_camera_normalised(*camera);
-    const bool same_cam = c->map_cam_valid && !memcmp(&c->map_cam, &cam, sizeof cam);
-    // (done: the detect call already ran k_map_pose -- asked for with this sigma_px, its COV form -- for this camera on these markers)
-    const bool done = same_cam && c->map_done && (!with_cov || (c->map_cov && c->map_sigma == sigma_px && c->map_cov_done));
-    if (!done) {
-        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, cam, c->d_mposes,
+    const PoseAsk ask = {fid_camera_normalised(*camera), 0., with_cov, sigma_px, {}};
+    if (!c->map_req.answers(ask)) {  // (else the detect call already ran k_map_pose, or its COV form, for this camera on these markers)
+        map_pose_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, ask.cam, c->d_mposes,
                         with_cov, sigma_px, c->d_mcov);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         if (with_cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->map_cam = cam;
-        c->map_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
-        c->map_done = c->map_cam_valid;
-        // (asked for without its covariance: the next call runs k_map_pose's COV = false form)
-        c->map_cov = with_cov && c->map_cam_valid;
-        c->map_sigma = sigma_px;
-        c->map_cov_done = c->map_cov;
+        c->map_req.answered(ask);  // (asked for without its covariance: the next call runs k_map_pose's COV = false form)
     }
     memcpy(out, c->h_mposes, sizeof(fid_map_pose_out) * (size_t)F);
     if (with_cov) memcpy(cov, c->h_mcov, sizeof(fid_map_pose_cov) * (size_t)F);
@@ -504,34 +481,9 @@ fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const 
     return fid_map_pose_cam(c, &cam, markers, n, out);
 }
 
-static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
-                                   double sigma_px, fid_map_pose_cov *cov);
-
-fid_status fid_map_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out)
+// a marker list from the host in d_map_in, which grows in steps of 256 markers, its count behind it at *d_n (both map _cam entry points)
+static fid_status stage_map_markers(fid_ctx *c, const fid_marker *markers, int32_t n, int **d_n)
 {
-    return map_pose_cam_run(c, camera, markers, n, out, false, 0., nullptr);
-}
-
-fid_status fid_map_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, double sigma_px,
-                                fid_map_pose_cov *cov)
-{
-    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
-    return map_pose_cam_run(c, camera, markers, n, out, true, sigma_px, cov);
-}
-
-static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
-                                   double sigma_px, fid_map_pose_cov *cov)
-{
-    if (!c || !fid_camera_usable(camera) || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
-    if (c->map_n == 0) {
-        c->last_error = "no map: fid_set_map first";
-        return FID_E_INVALID_ARG;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
     if (n > c->map_in_cap || !c->d_map_in) {
         if (c->d_map_in) (void)hipFree(c->d_map_in);
         c->d_map_in = nullptr;
@@ -540,12 +492,23 @@ static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const f
         HIPCHK(c, hipMalloc((void **)&c->d_map_in, sizeof(fid_marker) * (size_t)cap + sizeof(int)));
         c->map_in_cap = cap;
     }
-    int *d_n = (int *)((char *)c->d_map_in + sizeof(fid_marker) * (size_t)c->map_in_cap);
-    fid_map_pose_out *d_out = c->d_mposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
-    const int nn = n;
+    *d_n = (int *)((char *)c->d_map_in + sizeof(fid_marker) * (size_t)c->map_in_cap);
     if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (nn is a stack temporary)
+    HIPCHK(c, hipMemcpyAsync(*d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (n is a stack temporary)
+    return FID_OK;
+}
+
+static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
+                                   double sigma_px, fid_map_pose_cov *cov)
+{
+    if (!c || !fid_camera_usable(camera) || !out || n < 0 || (n > 0 && !markers)) return FID_E_INVALID_ARG;
+    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
+    HIPCHK(c, hipSetDevice(c->device));
+    int *d_n = nullptr;
+    const fid_status rcs = stage_map_markers(c, markers, n, &d_n);
+    if (rcs != FID_OK) return rcs;
+    fid_map_pose_out *d_out = c->d_mposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
     if (with_cov) {
         const fid_status rca = ensure_map_cov(c);
         if (rca != FID_OK) return rca;
@@ -557,4 +520,16 @@ static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const f
     if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, d_cov, sizeof(fid_map_pose_cov), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FID_OK;
+}
+
+fid_status fid_map_pose_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out)
+{
+    return map_pose_cam_run(c, camera, markers, n, out, false, 0., nullptr);
+}
+
+fid_status fid_map_pose_cov_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, double sigma_px,
+                                fid_map_pose_cov *cov)
+{
+    if (!cov || !fid_sigma_usable(sigma_px)) return FID_E_INVALID_ARG;
+    return map_pose_cam_run(c, camera, markers, n, out, true, sigma_px, cov);
 }

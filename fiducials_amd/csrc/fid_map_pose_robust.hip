@@ -552,36 +552,21 @@ fid_status fid_map_pose_robust_last_cam(fid_ctx *c, const fid_camera *camera, co
                                         fid_map_robust_out *robust_out, int32_t cap_frames)
 {
     if (!c || !fid_camera_usable(camera) || !pose_out || !robust_out || !fid_robust_opts_usable(opts) || c->last_frames <= 0) return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
-    if (c->map_n == 0) {
-        c->last_error = "no map: fid_set_map first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
+    if (refuse_room(c, cap_frames)) return FID_E_CAPACITY;
     const int F = c->last_frames;
-    if (cap_frames < F) {
-        c->last_error = "caller room for " + std::to_string(cap_frames) + " frames, the last call had " + std::to_string(F);
-        return FID_E_CAPACITY;
-    }
     HIPCHK(c, hipSetDevice(c->device));
     const fid_status rca = ensure_map_robust(c);
     if (rca != FID_OK) return rca;
-    const fid_camera cam = fid_camera_normalised(*camera);
-    const bool same = c->rob_cam_valid && !memcmp(&c->rob_cam, &cam, sizeof cam) && c->rob_opts.inlier_px == opts->inlier_px &&
-                      c->rob_opts.min_markers == opts->min_markers;
-    if (!(same && c->rob_done)) {
-        map_pose_robust_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, cam, *opts,
-                               c->d_rposes, c->d_mrob);
+    const PoseAsk ask = {fid_camera_normalised(*camera), 0., false, 0., {opts->inlier_px, opts->min_markers, 0}};
+    if (!c->rob_req.answers(ask)) {
+        map_pose_robust_launch(c, c->stream, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), c->P.maxMarkers, F, ask.cam,
+                               ask.opts, c->d_rposes, c->d_mrob);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(c->h_rposes, c->d_rposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->h_mrob, c->d_mrob, sizeof(fid_map_robust_out) * (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->rob_cam = cam;
-        c->rob_opts = {opts->inlier_px, opts->min_markers, 0};
-        c->rob_cam_valid = getenv("FID_NO_POSE_AHEAD") == nullptr;
-        c->rob_done = c->rob_cam_valid;
+        c->rob_req.answered(ask);
     }
     memcpy(pose_out, c->h_rposes, sizeof(fid_map_pose_out) * (size_t)F);
     memcpy(robust_out, c->h_mrob, sizeof(fid_map_robust_out) * (size_t)F);
@@ -593,32 +578,14 @@ fid_status fid_map_pose_robust_cam(fid_ctx *c, const fid_camera *camera, const f
 {
     if (!c || !fid_camera_usable(camera) || !pose_out || !robust_out || !fid_robust_opts_usable(opts) || n < 0 || (n > 0 && !markers))
         return FID_E_INVALID_ARG;
-    if (c->in_flight) {
-        c->last_error = "a submitted batch is in flight: fid_collect first";
-        return FID_E_INVALID_ARG;
-    }
-    if (c->map_n == 0) {
-        c->last_error = "no map: fid_set_map first";
-        return FID_E_INVALID_ARG;
-    }
+    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
-    if (n > c->map_in_cap || !c->d_map_in) {
-        if (c->d_map_in) (void)hipFree(c->d_map_in);
-        c->d_map_in = nullptr;
-        c->map_in_cap = 0;
-        const int cap = (n + 256) / 256 * 256;
-        HIPCHK(c, hipMalloc((void **)&c->d_map_in, sizeof(fid_marker) * (size_t)cap + sizeof(int)));
-        c->map_in_cap = cap;
-    }
-    const fid_status rca = ensure_map_robust(c);
+    int *d_n = nullptr;
+    fid_status rca = stage_map_markers(c, markers, n, &d_n);
+    if (rca == FID_OK) rca = ensure_map_robust(c);
     if (rca != FID_OK) return rca;
-    int *d_n = (int *)((char *)c->d_map_in + sizeof(fid_marker) * (size_t)c->map_in_cap);
     fid_map_pose_out *d_out = c->d_rposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
     fid_map_robust_out *d_rout = c->d_mrob + c->lim.max_batch;
-    const int nn = n;
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (nn is a stack temporary)
     map_pose_robust_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, *opts, d_out, d_rout);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(pose_out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
