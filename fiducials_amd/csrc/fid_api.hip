@@ -20,6 +20,11 @@ enum { ST_GRAY = 0, ST_THRESH, ST_STARTS, ST_PROBE, ST_WALK, ST_APPROX, ST_SORT,
 //  cycles; seedless_chain is the auxiliary stream's probes + survivor walk + cycles + copy + approx beside them)
 const char *const kStageNames[ST_COUNT] = {"to_gray", "threshold", "find_starts", "walk_probe", "walk_full", "approx", "sort_cands",
                                            "near", "resolve", "identify", "filter_markers", "subpix", "pose", "seed_walk", "seedless_chain"};
+// A sub-batch's event row (fid_ctx::sub_ev, FID_PROFILE): events 0 .. ST_SUBPIX + 1 are the stage boundaries on its main stream (stage i
+// runs from event i to event i + 1); beside them the brackets of the seed walk (main stream), of the seedless chain (auxiliary
+// stream) and of the remembered marker pose
+enum { EV_SEEDWALK0 = 14, EV_SEEDWALK1, EV_SEEDLESS0, EV_SEEDLESS1, EV_POSE0, EV_POSE1, EV_COUNT };
+static_assert(EV_SEEDWALK0 > ST_SUBPIX + 1, "the brackets lie behind the stage boundaries");
 
 constexpr int TX = 128, TY = 32, NT = 256;
 constexpr int THRW_NT = 512, THRW_WT = 16;  // k_threshold_wide: 512 threads x 16 columns cover the 8191-px frame limit
@@ -74,6 +79,60 @@ struct fid_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     enum { MAX_SUB = 8 };
+    // ---- launch tunables: read from the environment once, by read_tuning() in fid_create
+    struct Tuning {
+        // -- how a call is cut into sub-batches and how they are ordered
+        int sub_frames = 0;                    // FID_SUB_FRAMES: frames per sub-batch (0 = automatic)
+        // FID_SUB_SHARES: the pieces of a resident call of 32 frames or more, per cent ("64,36" unless set; set, it also cuts a batch
+        // of a chain, see plan_sub_batches).  What the text holds of positive numbers, at most MAX_SUB of them
+        bool sub_shares_set = false;
+        int sub_share[MAX_SUB] = {64, 36}, n_sub_share = 2;
+        int feed_share[4] = {20, 30, 30, 20};  // FID_FEED_SHARES: the four copy pieces of a host-fed call (measured 15.7 k frames/s; 25-25-25-25: 15.3 k,
+                                               // 34-28-22-16: 15.4 k, 10-22-34-34: 15.0 k)
+        // ONE blocking call laid out like the batches in turn of two contexts (round 5): `pieces` pieces, piece k's front (threshold ..
+        // approxPolyDP) on main stream k & 1, its seedless chain AND its candidate tail (sort .. pose) on auxiliary stream k & 1; piece
+        // k + 1's threshold starts when piece k's find_starts is through -- four streams in all (the runtime's four hardware queues),
+        // the latency-bound tail of a piece under the fronts of the pieces behind it.  0 / 1: the two sub-batches side by side.
+        int pieces = 0;                        // FID_PIECES
+        int stagger = 0;                       // FID_STAGGER: sub-batch k starts when sub-batch k - stagger has left its contour stage (0: all at once)
+        int fs_barrier = 0;                    // FID_FS_BARRIER=1: the walks of every sub-batch wait for all find_starts (measured: find_starts
+                                               // 3.6 -> 2.2 ms, the seed walks 3.3 -> 4.9 ms now side by side: the step is the same)
+        // batches in turn on several contexts (fid_order_after): tail_ev is recorded where the LAST sub-batch of a batch has its
+        // chip-filling kernels behind it (chain_at: 0 after find_starts, 1 seed walk, 2 copy, 3 approxPolyDP, 4 in front of the
+        // candidate sort, 5 after the too-close filter)
+        int chain_at = 0;                      // FID_CHAIN_AT
+        bool idx_stream = true;                // FID_NO_IDX_STREAM unset: calls laid out as one piece of up to 16 frames run k_seed_index on a stream of its own
+        bool prio = false;                     // FID_PRIO=1: earlier sub-batches more urgent.  Measured slower (18.1k vs 18.8k frames/s) than equal priorities.
+        // -- the front
+        int thr_xcd = 1;  // strips dealt out so that an XCD works through neighbouring strips (FID_THR_XCD=0: plain grid order)
+        int thr_nw = 3, thr_split = 0, thr_rows = 0;  // stream kernel: consumer waves per workgroup, un-fused LDS reads, rows per workgroup (0 = automatic)
+        int seed_shift = 0;        // FID_SEED_SHIFT: force the seed grid spacing 8 << shift (0 = by call size)
+        int seed_kernel = 0;       // FID_SEED_KERNEL=split|fused: k_find_starts<false> + k_find_seeds, or k_find_starts<true> (0 = by the seed grid)
+        // -- the contour stages
+        bool trace_legacy = false;  // FID_TRACE=legacy: every call of the context is traced by the whole-border walk (fid_ctx::whole_border_walk)
+        int walk_blocks = 0;  // FID_WALK_BLOCKS: one-wave workgroups per frame in the full walk pass (0 = automatic)
+        int walk_blocks_cap = 0;   // FID_WALK_CAP: most walker workgroups per frame (0: 64, 256 for calls of one or two frames)
+        int walk2_div = 6;   // FID_WALK2_DIV: the survivor walk gets walk_blocks / this workgroups a frame (round 6: 2 -> 6, one workgroup a frame at 128 frames: 1.5 k
+                             // survivors over 4 waves instead of 12 -- 1.13 M -> 0.70 M VALU wave-instructions a frame, lane utilisation 0.24 -> 0.33, same frame rate)
+        int sw_blocks = 0;   // FID_SW_BLOCKS: seed-walker workgroups per frame (0 = automatic)
+        int copy_blocks = 0;  // FID_COPY_BLOCKS: workgroups per frame of k_seg_copy (0: 256; a quarter of it for the seedless chain's)
+        int probe_refill = 4;  // FID_PROBE_REFILL: workgroups per frame of the refilled second probe pass (0: k_probe_lut<32, 1>)
+        int probe_refill0 = 0;  // FID_PROBE_REFILL0: the same for the first pass (0: k_probe_lut<6, 0>)
+        int probe_passes = 1;   // FID_PROBE_PASSES: 1: a batch sieves its starts in ONE refilled pass (k_probe_refill<32, 2>: starts -> surv, surv1 / nsurv1 unused);
+                                // 2: the two passes (k_probe_lut<6, 0> + k_probe_refill<32, 1>), as calls of fewer than 16 frames always do.  Values other
+                                // than 1 and 2 are ignored.  The single pass is a refilled one: FID_PROBE_REFILL=0 (no refilled kernels) takes the two
+                                // passes whatever this says
+        int probe_single = 16;  // FID_PROBE_SINGLE: workgroups per frame of that single pass, clamped to 1 ... 64 (8 ... 32 measured alike)
+        int segc_warm = 1;      // FID_NO_SEGC_WARM unset: k_seg_cycles<48> of a call of one or two frames first reads the frame's segment table (its `warm`)
+        // -- the candidate tail
+        int light_x = 1;     // FID_LIGHT_X: grid multiplier of k_near / k_seg_cycles, 1024 threads for k_sort_cands
+        int resolve_lds_kb = 64;   // FID_RESOLVE_LDS: KB of LDS a k_resolve workgroup asks for (see launch_grids)
+        int resolve_serial = 0;    // FID_RESOLVE_SERIAL=1: k_resolve's single-wave path even when the near triangle fits LDS (tests)
+        int resolve_reg_max = 64;  // FID_RESOLVE_REG_MAX: components of up to so many candidates are resolved in registers (0: none; tests)
+        int tail_grid = 4096;  // FID_TAIL_GRID: workgroups of k_identify (x 4: k_subpix) -- 1024 left 5 k candidates five rounds of an 80 us chain: +5 %
+        int filter_lds = 256;  // markers k_filter_markers keeps in LDS (FID_FILTER_LDS; more go through the global scratch)
+    } tune;
+    // ---- streams and the events between them
     hipStream_t sub_stream[MAX_SUB] = {};  // sub-batches of one call run on these, overlapping each other's tails
     int sub_prio[MAX_SUB] = {};
     hipStream_t aux_stream[MAX_SUB] = {};  // per sub-batch: the seed walk runs here, beside the probe passes and the survivor walk
@@ -82,7 +141,26 @@ struct fid_ctx {
     hipEvent_t sub_done[MAX_SUB] = {}, fork_ev = nullptr;
     hipStream_t copy_stream = nullptr;     // fid_detect_batch: the frames go up sub-batch by sub-batch on this stream ...
     hipEvent_t in_ready[MAX_SUB] = {};     // ... and a sub-batch starts when its frames have landed (H2D of k + 1 under the compute of k)
-    bool host_feed = false;                // this run_detect call is fed that way
+    // batches in turn on several contexts (fid_order_after): tail_ev is recorded where the LAST sub-batch of a batch has its
+    // chip-filling kernels behind it (Tuning::chain_at); the next batch's first kernel, on another context, waits for wait_ev
+    hipEvent_t tail_ev = nullptr, wait_ev = nullptr;
+    // host-fed batches in turn: the copy of this context's next batch starts when the copy of the batch in flight on the other
+    // context has landed (wait_copy_ev = that context's in_ready event).  Two copies side by side share the link, both take
+    // twice as long, and the two contexts then run in lockstep: 13.8 k frames/s from pinned memory instead of 21 k.
+    hipEvent_t wait_copy_ev = nullptr;
+    hipEvent_t fs_done[MAX_SUB] = {};      // a sub-batch's start / seed search is through (the piece chain, FID_FS_BARRIER)
+    hipEvent_t walk_done[MAX_SUB] = {};    // a sub-batch has left its contour stage (staggered starts, FID_STAGGER)
+    hipEvent_t front_done[MAX_SUB] = {};   // the piece chain: a piece's main stream is through approxPolyDP, its tail goes on on the auxiliary stream
+    hipEvent_t sub_ev[MAX_SUB][EV_COUNT] = {};  // per sub-batch stage boundaries (FID_PROFILE)
+    // ---- the call in progress and the batch in flight (state, not tunables: the entry points set it around enqueue_detect)
+    bool blocking = false;        // the call in progress is fid_detect*: nobody can chain behind it (no tail_ev on its stream)
+    bool chained = false;         // the next submit is one of a chain of batches (fid_order_after): one sub-batch, see plan_sub_batches
+    bool host_feed = false;       // this call's frames go up sub-batch by sub-batch on the copy stream (feed_and_enqueue)
+    bool from_host_call = false;  // enqueue_detect is running under feed_and_enqueue: the sub-batches are the copy's pieces, never a piece chain
+    bool piece_chain = false;     // this call is laid out as a chain of pieces (Tuning::pieces)
+    bool tail_recorded = false;   // this call has recorded tail_ev (chain_point)
+    bool whole_border_walk = false;  // probe passes + whole-border walk only (FID_TRACE=legacy, and a call whose seed tables overflowed);
+                                     // else cycle tracing: borders read off the seed cycles, starts only for borders without a seed
     struct Pending {                       // the batch fid_submit_device enqueued and fid_collect has not yet fetched
         const uint8_t *d_src;
         int F, W, H, stride;
@@ -90,40 +168,7 @@ struct fid_ctx {
         fid_encoding enc;
     } pend = {};
     bool in_flight = false;
-    // batches in turn on several contexts (fid_order_after): tail_ev is recorded where the LAST sub-batch of a batch has its
-    // chip-filling kernels behind it (chain_at: 0 after find_starts, 1 seed walk, 2 copy, 3 approxPolyDP, 4 in front of the
-    // candidate sort, 5 after the too-close filter); the next batch's first kernel, on another context, waits for wait_ev
-    hipEvent_t tail_ev = nullptr, wait_ev = nullptr;
-    // host-fed batches in turn: the copy of this context's next batch starts when the copy of the batch in flight on the other
-    // context has landed (wait_copy_ev = that context's in_ready event).  Two copies side by side share the link, both take
-    // twice as long, and the two contexts then run in lockstep: 13.8 k frames/s from pinned memory instead of 21 k.
-    hipEvent_t wait_copy_ev = nullptr;
     bool fed_from_host = false;  // the batch in flight came through feed_and_enqueue
-    int chain_at = 0;
-    bool chained = false;  // the next submit is one of a chain of batches (fid_order_after): one sub-batch, see plan_sub_batches
-    hipEvent_t walk_done[MAX_SUB] = {}, fs_done[MAX_SUB] = {}, front_done[MAX_SUB] = {};
-    // ONE blocking call laid out like the batches in turn of two contexts (round 5): `pieces` pieces, piece k's front (threshold ..
-    // approxPolyDP) on main stream k & 1, its seedless chain AND its candidate tail (sort .. pose) on auxiliary stream k & 1; piece
-    // k + 1's threshold starts when piece k's find_starts is through -- four streams in all (the runtime's four hardware queues),
-    // the latency-bound tail of a piece under the fronts of the pieces behind it.  0 / 1: the two sub-batches side by side.
-    int pieces = 0;
-    bool piece_chain = false;  // (this call is laid out that way)
-    bool from_host_call = false;  // enqueue_detect is running under feed_and_enqueue: the sub-batches are the copy's pieces, never a piece chain
-    int fs_barrier = 0;                    // FID_FS_BARRIER=1: the walks of every sub-batch wait for all find_starts (measured: find_starts
-                                           // 3.6 -> 2.2 ms, the seed walks 3.3 -> 4.9 ms now side by side: the step is the same)     // a sub-batch has left its contour stage (staggered starts, FID_STAGGER)
-    int stagger = 0;                        // sub-batch k starts when sub-batch k - stagger has left its contour stage (0: all at once)
-    int resolve_lds_kb = 64;
-    int walk2_div = 6;   // FID_WALK2_DIV: the survivor walk gets walk_blocks / this workgroups a frame (round 6: 2 -> 6, one workgroup a frame at 128 frames: 1.5 k
-                         // survivors over 4 waves instead of 12 -- 1.13 M -> 0.70 M VALU wave-instructions a frame, lane utilisation 0.24 -> 0.33, same frame rate)
-    int probe_refill0 = 0;  // FID_PROBE_REFILL0: the same for the first pass (0: k_probe_lut<6, 0>)
-    int probe_refill = 4;  // FID_PROBE_REFILL: workgroups per frame of the refilled second probe pass (0: k_probe_lut<32, 1>)
-    int probe_passes = 1;   // FID_PROBE_PASSES: 1: a batch sieves its starts in ONE refilled pass (k_probe_refill<32, 2>: starts -> surv, surv1 / nsurv1 unused);
-                            // 2: the two passes (k_probe_lut<6, 0> + k_probe_refill<32, 1>), as calls of fewer than 16 frames always do.  Values other
-                            // than 1 and 2 are ignored.  The single pass is a refilled one: FID_PROBE_REFILL=0 (no refilled kernels) takes the two
-                            // passes whatever this says
-    int probe_single = 16;  // FID_PROBE_SINGLE: workgroups per frame of that single pass, clamped to 1 ... 64 (8 ... 32 measured alike)
-    hipEvent_t sub_ev[MAX_SUB][20] = {};   // per sub-batch stage boundaries (FID_PROFILE)
-    int sub_frames = 0;                    // frames per sub-batch (0 = automatic)
     fid_params params;
     fid_limits lim;
     DevParams P;
@@ -147,23 +192,8 @@ struct fid_ctx {
     uint4 *d_wres = nullptr, *d_cinfo = nullptr;
     uint32_t *d_cbase = nullptr, *d_dense = nullptr;
     uint4 *d_recs = nullptr;  // copy records: pieces of the accepted contours
-    int thr_xcd = 1;  // strips dealt out so that an XCD works through neighbouring strips (FID_THR_XCD=0: plain grid order)
-    int thr_nw = 3, thr_split = 0, thr_rows = 0;  // stream kernel: consumer waves per workgroup, un-fused LDS reads, rows per workgroup (0 = automatic)
-    bool whole_border_walk = false;  // probe passes + whole-border walk only (FID_TRACE=legacy, and a call whose seed tables overflowed);
-                                     // else cycle tracing: borders read off the seed cycles, starts only for borders without a seed
-    int sw_blocks = 0;   // FID_SW_BLOCKS: seed-walker workgroups per frame (0 = automatic)
-    int tail_grid = 4096;  // FID_TAIL_GRID: workgroups of k_identify (x 4: k_subpix) -- 1024 left 5 k candidates five rounds of an 80 us chain: +5 %
-    int filter_lds = 256;  // markers k_filter_markers keeps in LDS (FID_FILTER_LDS; more go through the global scratch)
-    int light_x = 1;     // FID_LIGHT_X: grid multiplier of k_near / k_seg_cycles, 1024 threads for k_sort_cands
     long long fallbacks = 0;  // calls that fell back to the whole-border walk because the seed table was too small
     int max_chunks = 0;
-    int walk_blocks = 0;  // one-wave workgroups per frame in the full walk pass (0 = automatic)
-    int walk_blocks_cap = 0;   // FID_WALK_CAP: most walker workgroups per frame (0: 64, 256 for calls of one or two frames)
-    int copy_blocks = 0;
-    int resolve_serial = 0;    // FID_RESOLVE_SERIAL=1: k_resolve's single-wave path even when the near triangle fits LDS (tests)
-    int resolve_reg_max = 64;  // FID_RESOLVE_REG_MAX: components of up to so many candidates are resolved in registers (0: none; tests)
-    int seed_shift = 0;        // FID_SEED_SHIFT: force the seed grid spacing 8 << shift (0 = by call size)
-    int seed_kernel = 0;       // FID_SEED_KERNEL=split|fused: k_find_starts<false> + k_find_seeds, or k_find_starts<true> (0 = by the seed grid)
     uint4 *d_contours = nullptr;
     uint32_t *d_ckpts = nullptr;
     size_t ckpts_elems = 0;
@@ -191,7 +221,6 @@ struct fid_ctx {
     // of three fills and three or four copies (each a ~5 us kernel on the stream of a 0.8 ms single-frame call)
     uint8_t *d_res = nullptr, *h_res = nullptr;
     size_t res_clear_bytes = 0, res_markers_end = 0, res_poses_end = 0, res_poses_off = 0;
-    bool blocking = false;        // the call in progress is fid_detect*: nobody can chain behind it (no tail_ev on its stream)
     bool res_precleared = false;  // feed_and_enqueue has put this call's clear of d_res in front of its host -> device copy
     // pinned host staging
     fid_marker *h_markers = nullptr;
@@ -226,8 +255,7 @@ struct fid_ctx {
     const uint8_t *last_gray = nullptr;
     long long last_gfstride = 0;
     bool profile = false;
-    hipEvent_t ev[ST_COUNT + 1] = {};
-    bool ev_valid[ST_COUNT + 1] = {};
+    hipEvent_t pose_ev[2] = {};  // FID_PROFILE: the bracket of a pose kernel on the context's stream (run_pose)
     float stage_ms[ST_COUNT] = {};
     std::string last_error;
 };
@@ -437,7 +465,7 @@ void set_geometry(fid_ctx *c, int W, int H, int gstride, int F)
         int sh = 4;  // 128 px: batches (measured on the 256-frame bench batch: 64 px and 256 px are both slower)
         if (F <= 16 && P.maxContours >= 32768 && c->max_chunks >= 2 * 65536) sh = 3;  // 64 px
         if (F <= 2 && P.maxContours >= 65536 && c->max_chunks >= 4 * 65536) sh = 2;    // 32 px (one frame: 0.98 ms against 1.00 at 64 px)
-        if (c->seed_shift > 0) sh = c->seed_shift;
+        if (c->tune.seed_shift > 0) sh = c->tune.seed_shift;
         P.seedShift = sh < SEED_SHIFT_MIN ? SEED_SHIFT_MIN : (sh > SEED_SHIFT_MAX ? SEED_SHIFT_MAX : sh);
         P.seedHashCap = c->seed_hash_cap;
     }
@@ -464,7 +492,7 @@ fid_status ensure_streams(fid_ctx *c, int nsub, int F)
     // one piece = two streams so far: a third one still fits the runtime's default of four hardware queues
     // (only for calls of a few frames -- the node's shape: a 256-frame batch of a chain is one piece too, but two contexts in turn
     //  would then hold six streams, and more than four live streams cost the batch 17 % in round 3)
-    if (nsub == 1 && F <= 16 && !c->whole_border_walk && !c->idx_stream && !getenv("FID_NO_IDX_STREAM")) HIPCHK(c, hipStreamCreateWithFlags(&c->idx_stream, hipStreamNonBlocking));
+    if (nsub == 1 && F <= 16 && !c->whole_border_walk && !c->idx_stream && c->tune.idx_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->idx_stream, hipStreamNonBlocking));
     return FID_OK;
 }
 
@@ -476,8 +504,9 @@ struct SubPlan {
 };
 SubPlan plan_sub_batches(const fid_ctx *c, int F)
 {
+    const fid_ctx::Tuning &t = c->tune;
     SubPlan pl;
-    if (c->chained && c->sub_frames <= 0 && !getenv("FID_SUB_SHARES")) {
+    if (c->chained && t.sub_frames <= 0 && !t.sub_shares_set) {
         // a batch in a chain of batches on two contexts (fid_order_after) IS the other half: the batch before it on the other
         // context plays the part of the first sub-batch, for ever, with no call boundary at which the last piece's latency-bound
         // end has the chip to itself.  Measured, 256 frames a batch, two contexts: whole batches 30.5 k frames/s, 64 % + 36 %
@@ -487,29 +516,27 @@ SubPlan plan_sub_batches(const fid_ctx *c, int F)
         pl.f0[1] = F;
         return pl;
     }
-    if (c->sub_frames <= 0 && c->host_feed && F >= 64) {
+    if (t.sub_frames <= 0 && c->host_feed && F >= 64) {
         // frames that come up from the host while the call runs (the link, ~45 GB/s under load, is slower than the kernels):
         // four pieces -- the first kernels start after a fifth of the copy, the copy engine never idles, and what is left to
         // compute when the last byte has landed is a small piece.  The rate is insensitive to the split: the step is the arrival
         // of the first piece plus the kernels' time at the lower efficiency of small sub-batches
-        int share[4] = {20, 30, 30, 20};  // (measured 15.7 k frames/s; 25-25-25-25: 15.3 k, 34-28-22-16: 15.4 k, 10-22-34-34: 15.0 k)
-        if (const char *e = getenv("FID_FEED_SHARES")) (void)sscanf(e, "%d,%d,%d,%d", &share[0], &share[1], &share[2], &share[3]);
         pl.nsub = 4;
         int acc = 0;
         for (int k = 0; k < 4; k++) {
             pl.f0[k] = acc;
-            acc += k == 3 ? F - acc : (F * share[k] + 50) / 100;
+            acc += k == 3 ? F - acc : (F * t.feed_share[k] + 50) / 100;
         }
         pl.f0[4] = F;
         return pl;
     }
     if (c->piece_chain) {
-        pl.nsub = c->pieces < fid_ctx::MAX_SUB ? c->pieces : fid_ctx::MAX_SUB;
+        pl.nsub = t.pieces < fid_ctx::MAX_SUB ? t.pieces : fid_ctx::MAX_SUB;
         for (int k = 0; k <= pl.nsub; k++) pl.f0[k] = (int)((long long)F * k / pl.nsub);
         return pl;
     }
     // resident frames: two halves measured best (more streams fight for CUs)
-    int per = c->sub_frames > 0 ? c->sub_frames : (F >= 32 ? (F + 1) / 2 : F);
+    int per = t.sub_frames > 0 ? t.sub_frames : (F >= 32 ? (F + 1) / 2 : F);
     int nsub = (F + per - 1) / per;
     if (nsub > fid_ctx::MAX_SUB) {
         nsub = fid_ctx::MAX_SUB;
@@ -518,22 +545,13 @@ SubPlan plan_sub_batches(const fid_ctx *c, int F)
     }
     pl.nsub = nsub;
     for (int k = 0; k <= nsub; k++) pl.f0[k] = k * per < F ? k * per : F;
-    if (c->sub_frames <= 0 && F >= 32) {
+    if (t.sub_frames <= 0 && F >= 32) {
         // the sub-batches do not run in step: the first one's kernels meet less of the others' (its find_starts runs beside a
         // threshold, the second one's beside a seed walk and the probes), so with equal pieces it is through ~2 ms earlier and
         // the last one's latency-bound tail has the chip to itself.  Decreasing pieces even that out (FID_SUB_SHARES, per cent).
-        int sh[fid_ctx::MAX_SUB], n = 0, sum = 0;
-        const char *e = getenv("FID_SUB_SHARES");
-        const char *txt = e ? e : "64,36";
-        for (const char *q = txt; *q && n < fid_ctx::MAX_SUB;) {
-            const int v = atoi(q);
-            if (v > 0) {
-                sh[n++] = v;
-                sum += v;
-            }
-            while (*q && *q != ',') q++;
-            if (*q == ',') q++;
-        }
+        const int n = t.n_sub_share, *sh = t.sub_share;
+        int sum = 0;
+        for (int k = 0; k < n; k++) sum += sh[k];
         if (n >= 1 && sum > 0) {
             pl.nsub = n;
             int acc = 0;
@@ -596,9 +614,464 @@ fid_status check_call(fid_ctx *c, int F, int W, int H, int stride, fid_encoding 
 }
 
 // k_pose (+ k_pose_cov) on a stream.  Defined BEHIND enqueue_detect: the device code is emitted in the order in which the host code
-// first names the kernels, and the counter files under profiles/ are keyed to its bytes
+// first names the kernels, and the counter files under profiles/ are keyed to its bytes.  For the same reason the stage functions
+// below stand in the order front, whole-border, cycle tracing, tail, and name their kernels in the order the launch sequence always had
 void pose_launch(fid_ctx *c, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const fid_marker *d_markers, const int *d_n, int n_stride_ints,
                  const double *d_lens, int F, int per_frame, const PoseAsk &a, fid_pose_out *d_out, fid_pose_cov *d_cov);
+
+// ---- Sub-batch `sb` of a call: frames [f0, f0 + Fs) of it, the streams they run on under the call's layout, and THEIR part of every
+// per-frame buffer.  The buffers are the arrays of the HBM layout at the top of fid_device.h, every one indexed [frame][...]: "frames
+// [f0, f0 + Fs) of buffer X" is X + f0 * (X's elements per frame), and that arithmetic stands here and nowhere else -- the kernels
+// get these pointers with DevParams::nframes = Fs and index them from frame 0.
+struct SubBatch {
+    int sb, nsub, f0, Fs;
+    DevParams P;  // the call's, with nframes = Fs
+    // main stream; auxiliary stream (cycle tracing: the seedless chain; the piece chain: the candidate tail as well); the stream of
+    // k_seed_index (a stream of its own for a call of ONE piece of up to 16 frames, else the auxiliary one); the stream of the tail
+    hipStream_t st, sa, si, tail;
+    hipEvent_t *ev;  // its row of fid_ctx::sub_ev
+    const uint8_t *src;  // the caller's frames: colour input, k_to_gray reads them and writes gray_dst
+    uint8_t *gray_dst;
+    const uint8_t *g;  // the gray frames the detector sees (mono8 input: the caller's, in place), gfstride bytes apart
+    long long gfstride;
+    uint32_t *masks, *tab, *pool;  // (chunk table: rows of the seeds, then of the survivors; chain codes: CKW words per chunk of CK points)
+    uint2 *starts, *surv1, *surv;
+    uint4 *contours;
+    DevCounts *counts;
+    // cycle tracing (nullptr in a context created for the whole-border walk)
+    uint2 *seedq;
+    DevSegC *segs;
+    DevPend *pend;
+    unsigned long long *seedhash;
+    uint4 *wres, *cinfo, *recs;
+    uint32_t *cbase, *dense;  // (dense: one code byte per point)
+    // the candidate tail
+    DevCand *cands, *sorted, *filtered;
+    float4 *cmeta;
+    uint32_t *nearb;
+    unsigned *worklist, *nwork;
+    DevIdent *ident;
+    uint8_t *bits;
+    fid_marker *pre, *markers, *filter_scratch;
+    int *accsrc, *mksrc;
+    fid_pose_out *poses;
+    fid_pose_cov *pcov;  // (nullptr until the first _cov call)
+};
+
+template <typename T>
+inline T *frames_from(T *base, int f0, size_t per_frame)
+{
+    return base ? base + (size_t)f0 * per_frame : nullptr;
+}
+
+SubBatch sub_batch_view(fid_ctx *c, const SubPlan &plan, int sb, const uint8_t *d_src, long long fstride, const uint8_t *gray, long long gfstride, int W,
+                        int H)
+{
+    SubBatch s;
+    s.sb = sb;
+    s.nsub = plan.nsub;
+    s.f0 = plan.f0[sb];
+    s.Fs = plan.f0[sb + 1] - s.f0;
+    s.P = c->P;
+    s.P.nframes = s.Fs;
+    const DevParams &P = s.P;
+    const int f0 = s.f0, lane = c->piece_chain ? (sb & 1) : sb;  // (piece k of a chain works on main stream k & 1 and auxiliary stream k & 1)
+    s.st = s.nsub > 1 ? c->sub_stream[lane] : c->stream;
+    s.sa = c->aux_stream[lane];
+    s.si = (s.nsub == 1 && s.Fs <= 16 && c->idx_stream) ? c->idx_stream : s.sa;
+    s.tail = c->piece_chain ? s.sa : s.st;
+    s.ev = c->sub_ev[sb];
+    const size_t MC = (size_t)P.maxCands, MM = (size_t)P.maxMarkers, MCn = (size_t)P.maxContours, msb = (size_t)(P.markerSize + 2 * P.borderBits);
+    s.src = d_src + (long long)f0 * fstride;
+    s.gray_dst = c->d_gray + (size_t)f0 * W * H;
+    s.g = gray + (long long)f0 * gfstride;
+    s.gfstride = gfstride;
+    const size_t MS = (size_t)P.maxStarts, chunks = (size_t)P.maxChunks;
+    s.masks = frames_from(c->d_masks, f0, (size_t)P.nscales * P.TR * P.TC * MT_ROWS);
+    s.starts = frames_from(c->d_starts, f0, MS), s.surv1 = frames_from(c->d_surv1, f0, MS), s.surv = frames_from(c->d_surv, f0, MS);
+    s.contours = frames_from(c->d_contours, f0, MCn);
+    s.tab = frames_from(c->d_ckpts, f0, 2 * MCn * chunk_tab_pitch(P)), s.pool = frames_from(c->d_pool, f0, chunks * CKW);
+    s.counts = c->d_counts + f0;
+    s.seedq = frames_from(c->d_seedq, f0, MCn), s.segs = frames_from(c->d_segs, f0, MCn), s.pend = frames_from(c->d_pend, f0, MCn);
+    s.seedhash = frames_from(c->d_seedhash, f0, (size_t)P.seedHashCap);
+    s.wres = frames_from(c->d_wres, f0, MCn), s.cinfo = frames_from(c->d_cinfo, f0, MCn), s.recs = frames_from(c->d_recs, f0, 2 * MCn);
+    s.cbase = frames_from(c->d_cbase, f0, MCn), s.dense = frames_from(c->d_dense, f0, chunks * (CK / 4));
+    s.cands = frames_from(c->d_cands, f0, MC), s.sorted = frames_from(c->d_sorted, f0, MC), s.filtered = frames_from(c->d_filtered, f0, MC);
+    s.cmeta = frames_from(c->d_cmeta, f0, MC), s.nearb = frames_from(c->d_near, f0, MC * (MC / 32));
+    s.worklist = frames_from(c->d_worklist, f0, MC), s.nwork = c->d_nwork + sb;  // (one work-list counter per sub-batch)
+    s.ident = frames_from(c->d_ident, f0, MC), s.bits = frames_from(c->d_bits, f0, MC * msb * msb);
+    s.pre = frames_from(c->d_pre, f0, MM), s.markers = frames_from(c->d_markers, f0, MM), s.filter_scratch = frames_from(c->d_filter_scratch, f0, MC);
+    s.accsrc = frames_from(c->d_accsrc, f0, MC), s.mksrc = frames_from(c->d_mksrc, f0, MM);
+    s.poses = frames_from(c->d_poses, f0, MM), s.pcov = frames_from(c->d_pcov, f0, MM);
+    return s;
+}
+
+// ---- Launch geometry of a sub-batch: every workgroup count and dynamic-LDS size of the chain, from the tunables, the parameters and
+// the sub-batch's frame count.  The kernels with a fixed number of workgroups per frame are sized for batches; what a smaller call
+// gets instead is decided by its regime, once:
+//   ONE_OR_TWO  Fs <= 2: every seed in flight at once (256-workgroup walker cap, a lane for every seed in k_seg_cycles<48>)
+//   FEW         Fs < 16: more workgroups per frame (gm = 16 / Fs of them for each one of a batch -- 1 again from 9 frames on)
+//   BATCH       Fs >= 16
+// (the index stream of a call of one piece is a matter of streams, not of grids: SubBatch::si, up to 16 frames)
+struct Grids {
+    enum Regime { ONE_OR_TWO, FEW, BATCH } regime;
+    int gm;
+    // the front
+    enum Threshold { THR_STREAM, THR_WIDE, THR_TILES } thr;  // the node's window table / windows above 81 px / any other table
+    dim3 thr_grid;
+    int thr_rows;  // rows per workgroup (k_threshold_stream: RS; k_threshold_wide: BH)
+    size_t thr_lds;
+    unsigned k2blocks;
+    bool split_seeds;
+    int seed_blocks;
+    // the contour stages
+    int wb, wb3, swb, cpb, scb;
+    bool single_pass;
+    int cap1;
+    size_t lds1, lds2;
+    // the candidate tail
+    int sort_y, light_blocks;
+    size_t resolve_lds;
+    int near_words;
+    int ident_blocks, subpix_blocks;
+    size_t ident_lds, filter_lds;
+};
+
+Grids launch_grids(const fid_ctx::Tuning &t, const DevParams &P, int Fs)
+{
+    Grids G;
+    const int W = P.W, H = P.H;
+    G.regime = Fs <= 2 ? Grids::ONE_OR_TWO : (Fs < 16 ? Grids::FEW : Grids::BATCH);
+    // kernels with a fixed number of workgroups per frame (sized for batches): a call of a few frames gets more of them
+    const int gm = G.gm = G.regime == Grids::BATCH ? 1 : 16 / Fs;
+    // ---- K1
+    bool node_table = P.nscales == 13;  // 3, 7, ..., 51: the node defaults (aruco_detect.cpp:690-693)
+    for (int i = 0; i < P.nscales && node_table; i++) node_table = P.win[i] == 3 + 4 * i;
+    G.thr_lds = 0;
+    if (node_table) {
+        // strips of 64 * NW columns, cut into row segments so that the grid fills the chip (a segment pays a warm-up
+        // of about ten steps, so they are kept as tall as the batch allows)
+        const int cols = 64 * t.thr_nw, strips = (W + cols - 1) / cols;
+        int RS = t.thr_rows;
+        if (RS <= 0) {
+            int segs = (1536 + strips * Fs - 1) / (strips * Fs);
+            const int maxsegs = (H + 63) / 64;
+            segs = segs < 1 ? 1 : (segs > maxsegs ? maxsegs : segs);
+            RS = (H + segs - 1) / segs;
+        }
+        RS = (RS + 3) & ~3;
+        G.thr = Grids::THR_STREAM;
+        G.thr_grid = dim3(strips, (H + RS - 1) / RS, Fs);
+        G.thr_rows = RS;
+    } else if (P.rmax > 40) {
+        // windows above 81 px: bands of whole rows, enough of them to fill the chip (a band pays a closed-form start of its
+        // running column sums, up to min(2 rmax + 1, H) rows per scale, so they are not cut below 16 rows)
+        int bands = (512 + Fs - 1) / Fs;
+        const int maxb = (H + 15) / 16;
+        bands = bands < 1 ? 1 : (bands > maxb ? maxb : bands);
+        const int BH = (H + bands - 1) / bands;
+        G.thr = Grids::THR_WIDE;
+        G.thr_grid = dim3((H + BH - 1) / BH, 1, Fs);
+        G.thr_rows = BH;
+        G.thr_lds = (size_t)(W + 1 + THRW_NT / 64) * sizeof(unsigned long long);
+    } else {
+        int R = P.rmax, RW = TX + 2 * R, RH = TY + 2 * R, PT = (RW + 1) | 1;
+        G.thr = Grids::THR_TILES;
+        G.thr_grid = dim3((W + TX - 1) / TX, (H + TY - 1) / TY, Fs);
+        G.thr_rows = 0;
+        G.thr_lds = (size_t)(RH + 1) * PT * sizeof(uint32_t);
+    }
+    // ---- K2
+    // the tracing seeds: on the 128 px grid of batches few word columns and rows hold any, and a kernel of their own finds them
+    // (split); on the denser grids of small calls every word column or every second one is a grid column: k_find_starts<true>
+    G.split_seeds = t.seed_kernel ? t.seed_kernel == 1 : P.seedShift >= 4;
+    {
+        long long groups = (long long)P.nscales * P.TR * ((P.WW + 15) / 16);  // two groups per wave and iteration
+        long long k2blocks = (groups + 7) / 8;
+        if (k2blocks > 256) k2blocks = 256;
+        G.k2blocks = (unsigned)k2blocks;
+    }
+    G.seed_blocks = 0;
+    if (G.split_seeds) {
+        const SeedUnits su = seed_units(P);
+        // (a wave per unit: a batch gives a frame 32 workgroups, a call of a few frames a workgroup for every four units)
+        const int smax = G.regime == Grids::BATCH ? 32 : 512;
+        G.seed_blocks = (su.n + 3) / 4 < smax ? (su.n + 3) / 4 : smax;
+    }
+    // ---- K3, K4
+    // persistent walker workgroups (WALK_WAVES waves each) per frame: about 16 waves per CU over the sub-batch
+    int wb = t.walk_blocks > 0 ? t.walk_blocks : (3072 / WALK_WAVES + Fs - 1) / Fs;  // (measured: 6 per frame at 128 frames beats 8 and 12)
+    // (the walks of one frame want every seed in flight at once: one frame, 32 px grid: seed walk 0.25 -> 0.115 ms)
+    const int wcap = t.walk_blocks_cap > 0 ? t.walk_blocks_cap : (G.regime == Grids::ONE_OR_TWO ? 256 : 64);
+    G.wb = wb = wb < 2 ? 2 : (wb > wcap ? wcap : wb);
+    const int wb2 = wb > 1 ? wb / 2 : 1;  // the two walks share the CUs' LDS
+    G.wb3 = t.walk2_div > 0 ? (wb / t.walk2_div > 0 ? wb / t.walk2_div : 1) : wb2;
+    // about 4 walker waves per CU over the sub-batch (34 KB LDS per 2-wave workgroup: two of them leave a CU room for
+    // the other sub-batch's kernels; 8 waves per CU measured 7 % slower end to end)
+    int swb = t.sw_blocks > 0 ? t.sw_blocks : (1024 / SW_WAVES + Fs - 1) / Fs;
+    G.swb = swb < 2 ? 2 : (swb > 4 * wcap ? 4 * wcap : swb);
+    G.cpb = t.copy_blocks > 0 ? t.copy_blocks : 256;
+    // (batches: one pass over every start; 16 waves a frame that keep their lanes filled -- a call of a few frames wants every start
+    //  in flight at once, in two passes)
+    G.single_pass = t.probe_passes == 1 && t.probe_refill && gm == 1;
+    // (a call of one or two frames: a lane for every seed at once -- a workgroup that came round to a second 64 seeds walked a
+    //  second longest cycle behind the first, 2 x 26 us of the single frame's 55 us)
+    G.scb = G.regime == Grids::ONE_OR_TWO ? (int)((P.maxContours + 63) / 64 < 4096 ? (P.maxContours + 63) / 64 : 4096) : 32 * gm * t.light_x;
+    // approxPolyDP: short contours with a small LDS footprint first, then the long / flagged ones
+    G.cap1 = pts_cap_first(P);
+    G.lds1 = k_approx_lds_bytes(G.cap1);
+    G.lds2 = k_approx_lds_bytes(P.maxPerim + 1);
+    // ---- K5 .. K7
+    const size_t MC = (size_t)P.maxCands;
+    // (a rank sort: every candidate is compared with all of them -- a call of a few frames gives the frame sixteen workgroups)
+    G.sort_y = (t.light_x > 1 || G.regime != Grids::BATCH) ? 16 : 1;
+    G.light_blocks = 32 * gm * t.light_x;
+    // k_resolve: sizes, labels, component sizes; the rest holds the near triangle (64 KB: fits beside two seed-walker workgroups of
+    // the other sub-batch on a CU; with 96 KB the kernel waited for whole CUs to drain)
+    G.resolve_lds = (size_t)t.resolve_lds_kb * 1024;
+    G.near_words = t.resolve_serial ? 0 : (int)((G.resolve_lds - 3 * MC * 4) / 4);
+    const int SZ = (P.markerSize + 2 * P.borderBits) * P.cellSize;
+    G.ident_blocks = t.tail_grid > 0 ? t.tail_grid : 256 * 4;
+    G.ident_lds = (size_t)SZ * SZ;
+    G.filter_lds = (size_t)t.filter_lds * sizeof(fid_marker);
+    {
+        long long items = (long long)Fs * P.maxMarkers * 4;
+        const long long bcap = t.tail_grid > 0 ? 4LL * t.tail_grid : 256 * 16;
+        G.subpix_blocks = (int)(items < bcap ? items : bcap);
+    }
+    return G;
+}
+
+// a stage boundary of the sub-batch (FID_PROFILE)
+inline void mark(const fid_ctx *c, const SubBatch &s, hipStream_t st, int idx)
+{
+    if (c->profile) (void)hipEventRecord(s.ev[idx], st);
+}
+// a point at which the next batch of a chain (fid_order_after, on another context) may start: tail_ev is recorded at the first one
+// the LAST sub-batch passes at or behind Tuning::chain_at (a point the mode in use does not pass falls through to the next one that it does)
+inline void chain_point(fid_ctx *c, const SubBatch &s, hipStream_t st, int pt)
+{
+    if (s.sb == s.nsub - 1 && !c->tail_recorded && !c->blocking && c->tune.chain_at <= pt) {  // (an event record costs the stream ~6 us)
+        (void)hipEventRecord(c->tail_ev, st);
+        c->tail_recorded = true;
+    }
+}
+
+// ---- The front, on the main stream: gray conversion, threshold, and under cycle tracing the start / seed search -- every
+// sub-batch's find_starts is then queued before any walk, and (fs_barrier) the walks of all sub-batches wait for the last find_starts:
+// beside another sub-batch's seed walk and probes a find_starts took 2.5 ms for 92 frames, beside another find_starts 1.1 ms for 164.
+// Records fs_done; chain point 0.
+fid_status stage_front(fid_ctx *c, const SubBatch &s, const Grids &G, const fid_ctx::Pending &in)
+{
+    const DevParams &P = s.P;
+    const fid_ctx::Tuning &t = c->tune;
+    hipStream_t st = s.st;
+    const int Fs = s.Fs;
+    mark(c, s, st, 0);
+    // ---- K0: mono8 device input is used in place (any stride); colour goes through k_to_gray
+    if (in.enc != FID_ENC_MONO8 && (int)in.enc <= FID_ENC_RGBA8)
+        hipLaunchKernelGGL(k_to_gray, dim3(2048), dim3(256), 0, st, s.src, in.stride, in.fstride, (int)in.enc, s.gray_dst, P.W, P.H, Fs);
+    else if (in.enc != FID_ENC_MONO8)  // (ABI 7: Bayer mosaics, 16-bit layouts, UYVY -- cv_bridge's conversion and BGR2GRAY in one pass)
+        hipLaunchKernelGGL(k_raw_to_gray, dim3((P.W + 255) / 256, (P.H + 3) / 4, Fs), dim3(64, 4), 0, st, s.src, in.stride, in.fstride, (int)in.enc,
+                           s.gray_dst, P.W, P.H);
+    mark(c, s, st, ST_GRAY + 1);
+    // ---- K1
+    if (G.thr == Grids::THR_STREAM) {
+        if (t.thr_nw == 5 && t.thr_split) launch_thr_stream<5, true>(G.thr_grid, st, s.g, s.gfstride, s.masks, P, G.thr_rows, t.thr_xcd);
+        else if (t.thr_nw == 5) launch_thr_stream<5, false>(G.thr_grid, st, s.g, s.gfstride, s.masks, P, G.thr_rows, t.thr_xcd);
+        else if (t.thr_split) launch_thr_stream<3, true>(G.thr_grid, st, s.g, s.gfstride, s.masks, P, G.thr_rows, t.thr_xcd);
+        else launch_thr_stream<3, false>(G.thr_grid, st, s.g, s.gfstride, s.masks, P, G.thr_rows, t.thr_xcd);
+    } else if (G.thr == Grids::THR_WIDE) {
+        fid_launch_log("k_threshold_wide", THRW_NT, G.thr_lds);
+        hipLaunchKernelGGL((k_threshold_wide<THRW_NT, THRW_WT>), G.thr_grid, dim3(THRW_NT), G.thr_lds, st, s.g, s.gfstride, s.masks, P, G.thr_rows);
+    } else {
+        hipLaunchKernelGGL((k_threshold<TX, TY, NT>), G.thr_grid, dim3(NT), G.thr_lds, st, s.g, s.gfstride, s.masks, P);
+    }
+    mark(c, s, st, ST_THRESH + 1);
+    if (c->whole_border_walk) return FID_OK;  // (its start search heads the whole-border stage)
+    // ---- K2
+    if (G.split_seeds) {
+        // the seeds come from a kernel of their own that only visits the grid lines (k_find_seeds), directly behind the
+        // start search on the same stream.  (On the sub-batch's auxiliary stream, beside k_find_starts<false> and joined
+        // in front of the seed walk by two events, it measured 0.2 - 0.5 % slower: profiles/r10_seed_split_ab.txt.)
+        hipLaunchKernelGGL(k_find_starts<false>, dim3(G.k2blocks, Fs), dim3(256), 0, st, s.masks, s.starts, s.counts, c->d_global, (uint2 *)nullptr, P);
+        mark(c, s, st, ST_STARTS + 1);
+        hipLaunchKernelGGL(k_find_seeds, dim3(G.seed_blocks, Fs), dim3(256), 0, st, s.masks, s.counts, c->d_global, s.seedq, P);
+    } else {
+        hipLaunchKernelGGL(k_find_starts<true>, dim3(G.k2blocks, Fs), dim3(256), 0, st, s.masks, s.starts, s.counts, c->d_global, s.seedq, P);
+        mark(c, s, st, ST_STARTS + 1);
+    }
+    if (s.nsub > 1) HIPCHK(c, hipEventRecord(c->fs_done[s.sb], st));
+    chain_point(c, s, st, 0);
+    return FID_OK;
+}
+
+// ---- The whole-border contour stage, all on the main stream: start search, two probe passes that sieve the starts, the walk of
+// the survivors to the end, approxPolyDP
+fid_status stage_whole_border(fid_ctx *c, const SubBatch &s, const Grids &G)
+{
+    const DevParams &P = s.P;
+    hipStream_t st = s.st;
+    const int Fs = s.Fs, gm = G.gm;
+    hipLaunchKernelGGL(k_find_starts<false>, dim3(G.k2blocks, Fs), dim3(256), 0, st, s.masks, s.starts, s.counts, c->d_global, (uint2 *)nullptr, P);
+    mark(c, s, st, ST_STARTS + 1);
+    // ---- K3: sieve the starts twice, then walk the survivors to the end
+    hipLaunchKernelGGL((k_probe<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, st, s.masks, s.starts, s.surv1, s.counts, c->d_global, P);
+    hipLaunchKernelGGL((k_probe<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, st, s.masks, s.surv1, s.surv, s.counts, c->d_global, P);
+    mark(c, s, st, ST_PROBE + 1);
+    hipLaunchKernelGGL(k_walk_full<0>, dim3(G.wb, Fs), dim3(64 * WALK_WAVES), 0, st, s.masks, s.surv, s.contours, s.tab, s.pool, (DevSegC *)nullptr,
+                       (DevPend *)nullptr, s.counts, c->d_global, P);
+    mark(c, s, st, ST_WALK + 1);
+    // ---- K4: short contours with a small LDS footprint first, then the long / flagged ones
+    fid_launch_log("k_approx", 64, G.lds1);
+    hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), G.lds1, st, s.contours, s.tab, s.pool, s.cands, s.counts, P, G.cap1, 0,
+                       (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    fid_launch_log("k_approx", 64, G.lds2);
+    hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), G.lds2, st, s.contours, s.tab, s.pool, s.cands, s.counts, P, P.maxPerim + 1, 1,
+                       (const uint32_t *)nullptr, (const uint32_t *)nullptr);
+    mark(c, s, st, ST_APPROX + 1);
+    return FID_OK;
+}
+
+// ---- The cycle-tracing contour stage (k_find_starts / k_find_seeds were queued by the front).  Main stream: the seeds walk their
+// segments, link, the cycles become contour list A, copy, approxPolyDP.  Auxiliary stream, beside it: seed index, then the chain that
+// only exists for borders WITHOUT a seed state (probe passes that drop a start at the first seed state, survivor walk, contour list B,
+// copy, approxPolyDP) -- off the critical path, it used to be 2.9 ms of a 9.6 ms sub-batch.  Both append candidates; the streams join
+// in front of the candidate tail (aux_join), or, in a chain of pieces, the tail goes on on the auxiliary stream (front_done).
+//   main:       aux_fork . k_seed_walk [chain point 1] ................ (aux_idx) k_seg_link2 k_seg_cycles k_seg_copy [2] k_approx x 2 [3]
+//   auxiliary:  (aux_fork) [k_seed_index aux_idx] probes k_walk_full<2> (aux_idx) k_seg_cycles k_seg_copy k_approx x 2 aux_join
+//   index:      (aux_fork) k_seed_index aux_idx          -- a call of one piece of up to 16 frames; else on the auxiliary stream
+fid_status stage_cycle_tracing(fid_ctx *c, const SubBatch &s, const Grids &G)
+{
+    const DevParams &P = s.P;
+    const fid_ctx::Tuning &t = c->tune;
+    hipStream_t st = s.st, sa = s.sa, si = s.si;
+    const int Fs = s.Fs, gm = G.gm, sb = s.sb;
+    const uint4 *probe_tables = (const uint4 *)c->d_probe_tables;
+    HIPCHK(c, hipEventRecord(c->aux_fork[sb], st));
+    HIPCHK(c, hipStreamWaitEvent(sa, c->aux_fork[sb], 0));
+    // -- the main stream's first kernel goes out BEFORE the auxiliary chain's eight launches: the host needs ~15 us to
+    //    enqueue those, and for a single frame the seed walk sat waiting behind them (round 4, cfg 2 timeline)
+    mark(c, s, st, EV_SEEDWALK0);
+    hipLaunchKernelGGL(k_seed_walk, dim3(G.swb, Fs), dim3(64 * SW_WAVES), 0, st, s.masks, s.seedq, s.tab, s.pool, s.segs, s.counts, c->d_global, P);
+    mark(c, s, st, EV_SEEDWALK1);
+    mark(c, s, st, ST_PROBE + 1);
+    chain_point(c, s, st, 1);
+    // -- auxiliary stream.  k_seed_index (the map seed state -> seed index, which only k_seg_link2 on the main stream and
+    //    the auxiliary k_seg_cycles need) is off the auxiliary chain's critical path when the call is one piece: a stream of
+    //    its own beside the probes (39 us of a single frame's 314 us contour stage)
+    mark(c, s, sa, EV_SEEDLESS0);
+    if (si != sa) HIPCHK(c, hipStreamWaitEvent(si, c->aux_fork[sb], 0));
+    hipLaunchKernelGGL(k_seed_index, dim3(8 * gm, Fs), dim3(256), 0, si, s.seedq, s.seedhash, s.counts, P);
+    HIPCHK(c, hipEventRecord(c->aux_idx[sb], si));
+    if (G.single_pass) {  // (batches: one pass over every start)
+        hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 2>), dim3(t.probe_single, Fs), dim3(256), 0, sa, s.masks, s.starts, s.surv, s.counts, c->d_global, P,
+                           probe_tables);
+    } else {
+        if (t.probe_refill0 && gm == 1)
+            hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(t.probe_refill0, Fs), dim3(256), 0, sa, s.masks, s.starts, s.surv1, s.counts,
+                               c->d_global, P, probe_tables);
+        else
+            hipLaunchKernelGGL((k_probe_lut<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, sa, s.masks, s.starts, s.surv1, s.counts, c->d_global, P,
+                               probe_tables);
+        if (t.probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
+            hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(t.probe_refill, Fs), dim3(256), 0, sa, s.masks, s.surv1, s.surv, s.counts,
+                               c->d_global, P, probe_tables);
+        else
+            hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, s.masks, s.surv1, s.surv, s.counts, c->d_global, P,
+                               probe_tables);
+    }
+    hipLaunchKernelGGL(k_walk_full<2>, dim3(G.wb3, Fs), dim3(64 * WALK_WAVES), 0, sa, s.masks, s.surv, s.wres, s.tab, s.pool, s.segs, s.pend, s.counts,
+                       c->d_global, P);
+    if (si != sa) HIPCHK(c, hipStreamWaitEvent(sa, c->aux_idx[sb], 0));  // (the survivors' seed look-ups need the map)
+    hipLaunchKernelGGL(k_seg_cycles<0>, dim3(8 * gm, Fs), dim3(64), 0, sa, s.seedq, s.segs, s.pend, s.wres, s.contours, s.cinfo, s.cbase, s.recs,
+                       s.counts, c->d_global, P, 1, 0);
+    hipLaunchKernelGGL(k_seg_copy, dim3(G.cpb / 4 > 0 ? G.cpb / 4 : 1, Fs), dim3(256), 0, sa, s.recs, s.tab, s.pool, s.dense, s.counts, P, 1);
+    fid_launch_log("k_approx", 64, G.lds1);
+    hipLaunchKernelGGL(k_approx, dim3(32 * gm, Fs), dim3(64), G.lds1, sa, s.contours, s.tab, s.pool, s.cands, s.counts, P, G.cap1, 0, s.dense, s.cbase, 2);
+    fid_launch_log("k_approx", 64, G.lds2);
+    hipLaunchKernelGGL(k_approx, dim3(8 * gm, Fs), dim3(64), G.lds2, sa, s.contours, s.tab, s.pool, s.cands, s.counts, P, P.maxPerim + 1, 1, s.dense,
+                       s.cbase, 2);
+    mark(c, s, sa, EV_SEEDLESS1);
+    HIPCHK(c, hipEventRecord(c->aux_join[sb], sa));
+    // -- main stream, continued
+    HIPCHK(c, hipStreamWaitEvent(st, c->aux_idx[sb], 0));
+    hipLaunchKernelGGL(k_seg_link2, dim3(16 * gm, Fs), dim3(256), 0, st, s.seedq, s.segs, s.seedhash, s.counts, P);
+    if (G.regime == Grids::ONE_OR_TWO)
+        hipLaunchKernelGGL(k_seg_cycles<48>, dim3(G.scb, Fs), dim3(64), 0, st, s.seedq, s.segs, s.pend, s.wres, s.contours, s.cinfo, s.cbase, s.recs,
+                           s.counts, c->d_global, P, 0, t.segc_warm);
+    else
+        hipLaunchKernelGGL(k_seg_cycles<0>, dim3(G.scb, Fs), dim3(64), 0, st, s.seedq, s.segs, s.pend, s.wres, s.contours, s.cinfo, s.cbase, s.recs,
+                           s.counts, c->d_global, P, 0, 0);
+    hipLaunchKernelGGL(k_seg_copy, dim3(G.cpb, Fs), dim3(256), 0, st, s.recs, s.tab, s.pool, s.dense, s.counts, P, 0);
+    mark(c, s, st, ST_WALK + 1);
+    chain_point(c, s, st, 2);
+    fid_launch_log("k_approx", 64, G.lds1);
+    hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), G.lds1, st, s.contours, s.tab, s.pool, s.cands, s.counts, P, G.cap1, 0, s.dense, s.cbase, 1);
+    fid_launch_log("k_approx", 64, G.lds2);
+    hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), G.lds2, st, s.contours, s.tab, s.pool, s.cands, s.counts, P, P.maxPerim + 1, 1, s.dense,
+                       s.cbase, 1);
+    mark(c, s, st, ST_APPROX + 1);
+    chain_point(c, s, st, 3);
+    if (c->piece_chain) {
+        // the candidate tail of this piece moves to its auxiliary stream (behind the seedless chain, which is there already):
+        // the main stream is free for the front of the piece after next
+        HIPCHK(c, hipEventRecord(c->front_done[sb], st));
+        HIPCHK(c, hipStreamWaitEvent(sa, c->front_done[sb], 0));
+    } else {
+        HIPCHK(c, hipStreamWaitEvent(st, c->aux_join[sb], 0));
+    }
+    return FID_OK;
+}
+
+// ---- The candidate tail, a chain of short latency-bound kernels on the sub-batch's tail stream: sort, near pairs, too-close
+// filter, identification, marker filter, corner refinement, the remembered marker pose.  Records walk_done in front of it (staggered
+// starts); chain points 4 (in front of the sort), 5 (behind the too-close filter) and the end
+fid_status stage_tail(fid_ctx *c, const SubBatch &s, const Grids &G)
+{
+    const DevParams &P = s.P;
+    const fid_ctx::Tuning &t = c->tune;
+    hipStream_t st = s.tail;
+    const int Fs = s.Fs;
+    const size_t MC = (size_t)P.maxCands;
+    if (s.nsub > 1 && t.stagger > 0) HIPCHK(c, hipEventRecord(c->walk_done[s.sb], st));
+    chain_point(c, s, st, 4);
+    // ---- K5
+    fid_launch_log("k_sort_cands", 256, (size_t)(MC * 8));
+    hipLaunchKernelGGL(k_sort_cands, dim3(Fs, G.sort_y), dim3(256), MC * 8, st, s.cands, s.sorted, s.cmeta, s.counts, P);
+    mark(c, s, st, ST_SORT + 1);
+    hipLaunchKernelGGL(k_near, dim3(G.light_blocks, Fs), dim3(256), 0, st, s.sorted, s.cmeta, s.nearb, s.counts, P);
+    mark(c, s, st, ST_NEAR + 1);
+    fid_launch_log("k_resolve", 1024, G.resolve_lds);
+    hipLaunchKernelGGL(k_resolve, dim3(Fs), dim3(1024), G.resolve_lds, st, s.sorted, s.nearb, s.filtered, s.counts, s.worklist, s.nwork, P, G.near_words,
+                       c->d_global, t.resolve_reg_max);
+    mark(c, s, st, ST_RESOLVE + 1);
+    chain_point(c, s, st, 5);
+    // ---- K6
+    fid_launch_log("k_identify", 64, G.ident_lds);
+    hipLaunchKernelGGL(k_identify, dim3(G.ident_blocks), dim3(64), G.ident_lds, st, s.g, s.gfstride, s.filtered, s.worklist, s.nwork, c->d_dict, s.ident,
+                       s.bits, P);
+    mark(c, s, st, ST_IDENT + 1);
+    // ---- K7
+    fid_launch_log("k_filter_markers", 64, G.filter_lds);
+    hipLaunchKernelGGL(k_filter_markers, dim3(Fs), dim3(64), G.filter_lds, st, s.filtered, s.ident, s.pre, s.counts, P, s.filter_scratch, t.filter_lds,
+                       s.accsrc, s.mksrc);
+    mark(c, s, st, ST_FILTER + 1);
+    if (P.refine == 2)  // CORNER_REFINE_CONTOUR: a wave per marker fits the four sides of its contour (writes ids and corners)
+        hipLaunchKernelGGL(k_refine_contour, dim3(P.maxMarkers < 64 ? P.maxMarkers : 64, Fs), dim3(64), 0, st, (const fid_marker *)s.pre, s.markers,
+                           (const int *)s.mksrc, (const DevCand *)s.filtered, (const uint32_t *)s.dense, (const uint32_t *)s.tab, (const uint32_t *)s.pool,
+                           s.counts, P);
+    else if (P.subpixWin <= 7)  // (the LDS and tap registers of k_subpix follow its window bound)
+        hipLaunchKernelGGL(k_subpix<7>, dim3(G.subpix_blocks), dim3(64), 0, st, s.g, s.gfstride, s.pre, s.markers, s.counts, c->d_subpix_mask, P);
+    else
+        hipLaunchKernelGGL(k_subpix<SP_MAXWIN_MAX>, dim3(G.subpix_blocks), dim3(64), 0, st, s.g, s.gfstride, s.pre, s.markers, s.counts, c->d_subpix_mask, P);
+    mark(c, s, st, ST_SUBPIX + 1);
+    if (c->pose_req.ahead(c))  // (the remembered marker pose; where fid_pose_last_cov_cam was the last to ask, its covariance behind it)
+        pose_launch(c, st, s.ev[EV_POSE0], s.ev[EV_POSE1], s.markers, &s.counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, Fs, P.maxMarkers,
+                    c->pose_req.ask, s.poses, s.pcov);
+    chain_point(c, s, st, 99);
+    return FID_OK;
+}
 
 fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H, int stride, long long fstride, fid_encoding enc)
 {
@@ -606,6 +1079,8 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
         const fid_status rcv = check_call(c, F, W, H, stride, enc);
         if (rcv != FID_OK) return rcv;
     }
+    const fid_ctx::Tuning &t = c->tune;
+    const fid_ctx::Pending in = {d_src, F, W, H, stride, fstride, enc};
     hipStream_t st0 = c->stream;
     // ---- K0 geometry: mono8 device input is used in place (any stride); colour goes through k_to_gray
     const bool to_gray = enc != FID_ENC_MONO8;
@@ -638,337 +1113,48 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     // ---- the batch is cut into sub-batches that run the whole pipeline on their own streams: the latency-bound
     //      tail of one sub-batch's kernels (the longest border, the last candidates) overlaps the next one's bulk
     // (decided HERE and nowhere else: frames that come up from the host are cut by the copy's pieces whether or not the copy overlaps)
-    c->piece_chain = c->pieces > 1 && !c->chained && !c->host_feed && !c->from_host_call && !c->whole_border_walk && c->sub_frames <= 0 &&
-                     F >= 32 * c->pieces && c->stagger == 0;
+    c->piece_chain = t.pieces > 1 && !c->chained && !c->host_feed && !c->from_host_call && !c->whole_border_walk && t.sub_frames <= 0 &&
+                     F >= 32 * t.pieces && t.stagger == 0;
     const SubPlan plan = plan_sub_batches(c, F);
     const int nsub = plan.nsub;
-    const bool chainp = c->piece_chain;
+    const bool chainp = c->piece_chain, cycles = !c->whole_border_walk;
     c->last_nsub = nsub;
+    c->tail_recorded = false;
     {
         const fid_status rcs = ensure_streams(c, nsub, F);
         if (rcs != FID_OK) return rcs;
     }
+    SubBatch subs[fid_ctx::MAX_SUB];
+    Grids grids[fid_ctx::MAX_SUB];
+    for (int sb = 0; sb < nsub; sb++) {
+        subs[sb] = sub_batch_view(c, plan, sb, d_src, fstride, gray, gfstride, W, H);
+        grids[sb] = launch_grids(t, subs[sb].P, subs[sb].Fs);
+    }
     if (nsub > 1) HIPCHK(c, hipEventRecord(c->fork_ev, st0));
-    // The host enqueues in two rounds: first every sub-batch's gray conversion + threshold, then every sub-batch's rest.  (One
-    // round -- a whole sub-batch, some thirty launches, before the next one's first kernel -- left the second sub-batch's stream
-    // empty for the first 0.35 - 0.6 ms of every step.)
-    bool tail_recorded = false;
-    auto sub_phase = [&](int sb, int phase) -> fid_status {
-        const int f0 = plan.f0[sb], Fs = plan.f0[sb + 1] - f0;
-        hipStream_t st = nsub > 1 ? c->sub_stream[chainp ? (sb & 1) : sb] : st0;
-        if (nsub > 1 && phase == 0) HIPCHK(c, hipStreamWaitEvent(st, c->fork_ev, 0));
+    // a sub-batch's front, behind what it has to wait for
+    auto front = [&](int sb) -> fid_status {
+        hipStream_t st = subs[sb].st;
+        if (nsub > 1) HIPCHK(c, hipStreamWaitEvent(st, c->fork_ev, 0));
         // (a chain of pieces: this one's threshold starts when the piece before it is through its find_starts)
-        if (chainp && phase == 0 && sb > 0) HIPCHK(c, hipStreamWaitEvent(st, c->fs_done[sb - 1], 0));
-        if (c->host_feed && phase == 0) HIPCHK(c, hipStreamWaitEvent(st, c->in_ready[sb], 0));
+        if (chainp && sb > 0) HIPCHK(c, hipStreamWaitEvent(st, c->fs_done[sb - 1], 0));
+        if (c->host_feed) HIPCHK(c, hipStreamWaitEvent(st, c->in_ready[sb], 0));
         // staggered starts: the contour stage of a sub-batch (threshold ... approx) keeps the whole chip busy, what follows
         // (candidates, identification, corners) is a chain of short latency-bound kernels -- let the next sub-batch's contour
         // stage run under that tail instead of beside another contour stage
-        if (nsub > 1 && phase == 0 && c->stagger > 0 && sb >= c->stagger) HIPCHK(c, hipStreamWaitEvent(st, c->walk_done[sb - c->stagger], 0));
-        DevParams P = c->P;
-        P.nframes = Fs;
-        const size_t MC = (size_t)P.maxCands, MM = (size_t)P.maxMarkers;
-        const uint8_t *g = gray + (long long)f0 * gfstride;
-        uint32_t *masks = c->d_masks + (size_t)f0 * P.nscales * P.TR * P.TC * MT_ROWS;
-        uint2 *starts = c->d_starts + (size_t)f0 * P.maxStarts, *surv1 = c->d_surv1 + (size_t)f0 * P.maxStarts,
-              *surv = c->d_surv + (size_t)f0 * P.maxStarts;
-        uint4 *contours = c->d_contours + (size_t)f0 * P.maxContours;
-        uint32_t *tab = c->d_ckpts + (size_t)f0 * 2 * P.maxContours * chunk_tab_pitch(P);
-        uint32_t *pool = c->d_pool + (size_t)f0 * P.maxChunks * CKW;  // (chain codes: CKW words per chunk of CK points)
-        DevCounts *counts = c->d_counts + f0;
-        DevCand *cands = c->d_cands + f0 * MC, *sorted = c->d_sorted + f0 * MC, *filtered = c->d_filtered + f0 * MC;
-        uint32_t *nearb = c->d_near + f0 * MC * (MC / 32);
-        DevIdent *ident = c->d_ident + f0 * MC;
-        fid_marker *pre = c->d_pre + f0 * MM, *markers = c->d_markers + f0 * MM;
-        unsigned *worklist = c->d_worklist + f0 * MC, *nwork = c->d_nwork + sb;
-        hipEvent_t *ev = c->sub_ev[sb];
-        auto mark = [&](int idx) {
-            if (c->profile) (void)hipEventRecord(ev[idx], st);
-        };
-        auto chain_point = [&](int pt) {  // (a point the mode in use does not pass falls through to the next one that it does)
-            if (sb == nsub - 1 && !tail_recorded && !c->blocking && c->chain_at <= pt) {  // (an event record costs the stream ~6 us)
-                (void)hipEventRecord(c->tail_ev, st);
-                tail_recorded = true;
-            }
-        };
-      if (phase == 0) {
-        mark(0);
-        if (to_gray && (int)enc <= FID_ENC_RGBA8)
-            hipLaunchKernelGGL(k_to_gray, dim3(2048), dim3(256), 0, st, d_src + (long long)f0 * fstride, stride, fstride, (int)enc,
-                               c->d_gray + (size_t)f0 * W * H, W, H, Fs);
-        else if (to_gray)  // (ABI 7: Bayer mosaics, 16-bit layouts, UYVY -- cv_bridge's conversion and BGR2GRAY in one pass)
-            hipLaunchKernelGGL(k_raw_to_gray, dim3((W + 255) / 256, (H + 3) / 4, Fs), dim3(64, 4), 0, st, d_src + (long long)f0 * fstride, stride,
-                               fstride, (int)enc, c->d_gray + (size_t)f0 * W * H, W, H);
-        mark(ST_GRAY + 1);
-        // ---- K1
-        {
-            bool node_table = P.nscales == 13;  // 3, 7, ..., 51: the node defaults (aruco_detect.cpp:690-693)
-            for (int i = 0; i < P.nscales && node_table; i++) node_table = P.win[i] == 3 + 4 * i;
-            if (node_table) {
-                // strips of 64 * NW columns, cut into row segments so that the grid fills the chip (a segment pays a warm-up
-                // of about ten steps, so they are kept as tall as the batch allows)
-                const int cols = 64 * c->thr_nw, strips = (W + cols - 1) / cols;
-                int RS = c->thr_rows;
-                if (RS <= 0) {
-                    int segs = (1536 + strips * Fs - 1) / (strips * Fs);
-                    const int maxsegs = (H + 63) / 64;
-                    segs = segs < 1 ? 1 : (segs > maxsegs ? maxsegs : segs);
-                    RS = (H + segs - 1) / segs;
-                }
-                RS = (RS + 3) & ~3;
-                dim3 grid(strips, (H + RS - 1) / RS, Fs);
-                if (c->thr_nw == 5 && c->thr_split) launch_thr_stream<5, true>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
-                else if (c->thr_nw == 5) launch_thr_stream<5, false>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
-                else if (c->thr_split) launch_thr_stream<3, true>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
-                else launch_thr_stream<3, false>(grid, st, g, gfstride, masks, P, RS, c->thr_xcd);
-            } else if (P.rmax > 40) {
-                // windows above 81 px: bands of whole rows, enough of them to fill the chip (a band pays a closed-form start of its
-                // running column sums, up to min(2 rmax + 1, H) rows per scale, so they are not cut below 16 rows)
-                int bands = (512 + Fs - 1) / Fs;
-                const int maxb = (H + 15) / 16;
-                bands = bands < 1 ? 1 : (bands > maxb ? maxb : bands);
-                const int BH = (H + bands - 1) / bands;
-                const size_t lds = (size_t)(W + 1 + THRW_NT / 64) * sizeof(unsigned long long);
-                fid_launch_log("k_threshold_wide", THRW_NT, lds);
-                hipLaunchKernelGGL((k_threshold_wide<THRW_NT, THRW_WT>), dim3((H + BH - 1) / BH, 1, Fs), dim3(THRW_NT), lds, st, g, gfstride,
-                                   masks, P, BH);
-            } else {
-                int R = P.rmax, RW = TX + 2 * R, RH = TY + 2 * R, PT = (RW + 1) | 1;
-                size_t lds = (size_t)(RH + 1) * PT * sizeof(uint32_t);
-                dim3 grid((W + TX - 1) / TX, (H + TY - 1) / TY, Fs);
-                hipLaunchKernelGGL((k_threshold<TX, TY, NT>), grid, dim3(NT), lds, st, g, gfstride, masks, P);
-            }
-        }
-        mark(ST_THRESH + 1);
-      }
-        // ---- K2
-        // the tracing seeds: on the 128 px grid of batches few word columns and rows hold any, and a kernel of their own finds them
-        // (split); on the denser grids of small calls every word column or every second one is a grid column: k_find_starts<true>
-        const bool split_seeds = c->seed_kernel ? c->seed_kernel == 1 : P.seedShift >= 4;
-        long long k2blocks;
-        {
-            long long groups = (long long)P.nscales * P.TR * ((P.WW + 15) / 16);  // two groups per wave and iteration
-            k2blocks = (groups + 7) / 8;
-            if (k2blocks > 256) k2blocks = 256;
-        }
-      if (phase == 0) {
-        // cycle tracing's start / seed enumeration belongs to the first round as well: every sub-batch's find_starts is then
-        // queued before any walk, and (fs_barrier) the walks of all sub-batches wait for the last find_starts -- beside another
-        // sub-batch's seed walk and probes a find_starts took 2.5 ms for 92 frames, beside another find_starts 1.1 ms for 164
-        if (!c->whole_border_walk) {
-            uint2 *seedq = c->d_seedq + f0 * (size_t)P.maxContours;
-            if (split_seeds) {
-                // the seeds come from a kernel of their own that only visits the grid lines (k_find_seeds), directly behind the
-                // start search on the same stream.  (On the sub-batch's auxiliary stream, beside k_find_starts<false> and joined
-                // in front of the seed walk by two events, it measured 0.2 - 0.5 % slower: profiles/r10_seed_split_ab.txt.)
-                const SeedUnits su = seed_units(P);
-                // (a wave per unit: a batch gives a frame 32 workgroups, a call of a few frames a workgroup for every four units)
-                const int smax = Fs >= 16 ? 32 : 512, sblocks = (su.n + 3) / 4 < smax ? (su.n + 3) / 4 : smax;
-                hipLaunchKernelGGL(k_find_starts<false>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
-                                   (uint2 *)nullptr, P);
-                mark(ST_STARTS + 1);
-                hipLaunchKernelGGL(k_find_seeds, dim3(sblocks, Fs), dim3(256), 0, st, masks, counts, c->d_global, seedq, P);
-            } else {
-                hipLaunchKernelGGL(k_find_starts<true>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global, seedq, P);
-                mark(ST_STARTS + 1);
-            }
-            if (nsub > 1) HIPCHK(c, hipEventRecord(c->fs_done[sb], st));
-            chain_point(0);
-        }
-        return FID_OK;
-      }
-        if (!c->whole_border_walk && nsub > 1 && c->fs_barrier && !chainp)
+        if (nsub > 1 && t.stagger > 0 && sb >= t.stagger) HIPCHK(c, hipStreamWaitEvent(st, c->walk_done[sb - t.stagger], 0));
+        return stage_front(c, subs[sb], grids[sb], in);
+    };
+    // its contour stage and candidate tail; the context's stream waits for its end
+    auto rest = [&](int sb) -> fid_status {
+        const SubBatch &s = subs[sb];
+        if (cycles && nsub > 1 && t.fs_barrier && !chainp)
             for (int o = 0; o < nsub; o++)
-                if (o != sb) HIPCHK(c, hipStreamWaitEvent(st, c->fs_done[o], 0));
-        // persistent walker workgroups (WALK_WAVES waves each) per frame: about 16 waves per CU over the sub-batch
-        int wb = c->walk_blocks > 0 ? c->walk_blocks : (3072 / WALK_WAVES + Fs - 1) / Fs;  // (measured: 6 per frame at 128 frames beats 8 and 12)
-        // (the walks of one frame want every seed in flight at once: one frame, 32 px grid: seed walk 0.25 -> 0.115 ms)
-        const int wcap = c->walk_blocks_cap > 0 ? c->walk_blocks_cap : (Fs <= 2 ? 256 : 64);
-        wb = wb < 2 ? 2 : (wb > wcap ? wcap : wb);
-        // kernels with a fixed number of workgroups per frame (sized for batches): a call of a few frames gets more of them
-        const int gm = Fs >= 16 ? 1 : 16 / Fs;
-        const int wb2 = wb > 1 ? wb / 2 : 1;  // the two walks share the CUs' LDS
-        const int cap1 = pts_cap_first(P);
-        const size_t lds1 = k_approx_lds_bytes(cap1);
-        const size_t lds2 = k_approx_lds_bytes(P.maxPerim + 1);
-        if (c->whole_border_walk) {
-            hipLaunchKernelGGL(k_find_starts<false>, dim3((unsigned)k2blocks, Fs), dim3(256), 0, st, masks, starts, counts, c->d_global,
-                               (uint2 *)nullptr, P);
-            mark(ST_STARTS + 1);
-            // ---- K3: sieve the starts twice, then walk the survivors to the end
-            hipLaunchKernelGGL((k_probe<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, st, masks, starts, surv1, counts, c->d_global, P);
-            hipLaunchKernelGGL((k_probe<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, st, masks, surv1, surv, counts, c->d_global, P);
-            mark(ST_PROBE + 1);
-            hipLaunchKernelGGL(k_walk_full<0>, dim3(wb, Fs), dim3(64 * WALK_WAVES), 0, st, masks, surv, contours, tab, pool, (DevSegC *)nullptr,
-                               (DevPend *)nullptr, counts, c->d_global, P);
-            mark(ST_WALK + 1);
-            // ---- K4: short contours with a small LDS footprint first, then the long / flagged ones
-            fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, P, cap1, 0,
-                               (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-            fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, P,
-                               P.maxPerim + 1, 1, (const uint32_t *)nullptr, (const uint32_t *)nullptr);
-            mark(ST_APPROX + 1);
-        } else {
-            const size_t MCn = (size_t)P.maxContours;
-            DevSegC *segs = c->d_segs + f0 * MCn;
-            DevPend *pend = c->d_pend + f0 * MCn;
-            uint2 *seedq = c->d_seedq + f0 * MCn;
-            unsigned long long *seedhash = c->d_seedhash + (size_t)f0 * P.seedHashCap;
-            uint4 *wres = c->d_wres + f0 * MCn, *cinfo = c->d_cinfo + f0 * MCn;
-            uint32_t *cbase = c->d_cbase + f0 * MCn;
-            uint32_t *dense = c->d_dense + (size_t)f0 * P.maxChunks * (CK / 4);  // (one code byte per point)
-            // (k_find_starts<true> was queued in the first round)
-            // ---- cycle tracing.  Main stream: the seeds walk their segments, link, the cycles become contour list A, copy,
-            //      approxPolyDP.  Auxiliary stream, beside it: seed index, then the chain that only exists for borders WITHOUT a
-            //      seed state (probe passes that drop a start at the first seed state, survivor walk, contour list B, copy,
-            //      approxPolyDP) -- off the critical path, it used to be 2.9 ms of a 9.6 ms sub-batch.  Both append candidates;
-            //      the streams join in front of k_sort_cands.
-            hipStream_t sa = c->aux_stream[chainp ? (sb & 1) : sb];
-            HIPCHK(c, hipEventRecord(c->aux_fork[sb], st));
-            HIPCHK(c, hipStreamWaitEvent(sa, c->aux_fork[sb], 0));
-            // about 4 walker waves per CU over the sub-batch (34 KB LDS per 2-wave workgroup: two of them leave a CU room for
-            // the other sub-batch's kernels; 8 waves per CU measured 7 % slower end to end)
-            int swb = c->sw_blocks > 0 ? c->sw_blocks : (1024 / SW_WAVES + Fs - 1) / Fs;
-            swb = swb < 2 ? 2 : (swb > 4 * wcap ? 4 * wcap : swb);
-            uint4 *recs = c->d_recs + 2 * f0 * MCn;
-            const int cpb = c->copy_blocks > 0 ? c->copy_blocks : 256;
-            // -- the main stream's first kernel goes out BEFORE the auxiliary chain's eight launches: the host needs ~15 us to
-            //    enqueue those, and for a single frame the seed walk sat waiting behind them (round 4, cfg 2 timeline)
-            if (c->profile) (void)hipEventRecord(ev[14], st);
-            hipLaunchKernelGGL(k_seed_walk, dim3(swb, Fs), dim3(64 * SW_WAVES), 0, st, masks, seedq, tab, pool, segs, counts, c->d_global, P);
-            if (c->profile) (void)hipEventRecord(ev[15], st);
-            mark(ST_PROBE + 1);
-            chain_point(1);
-            // -- auxiliary stream.  k_seed_index (the map seed state -> seed index, which only k_seg_link2 on the main stream and
-            //    the auxiliary k_seg_cycles need) is off the auxiliary chain's critical path when the call is one piece: a stream of
-            //    its own beside the probes (39 us of a single frame's 314 us contour stage)
-            if (c->profile) (void)hipEventRecord(ev[16], sa);
-            hipStream_t si = (nsub == 1 && Fs <= 16 && c->idx_stream) ? c->idx_stream : sa;
-            if (si != sa) HIPCHK(c, hipStreamWaitEvent(si, c->aux_fork[sb], 0));
-            hipLaunchKernelGGL(k_seed_index, dim3(8 * gm, Fs), dim3(256), 0, si, seedq, seedhash, counts, P);
-            HIPCHK(c, hipEventRecord(c->aux_idx[sb], si));
-            const bool single_pass = c->probe_passes == 1 && c->probe_refill && gm == 1;
-            if (single_pass) {  // (batches: one pass over every start)
-                hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 2>), dim3(c->probe_single, Fs), dim3(256), 0, sa, masks, starts, surv, counts, c->d_global, P,
-                                   (const uint4 *)c->d_probe_tables);
-            } else {
-                if (c->probe_refill0 && gm == 1)
-                    hipLaunchKernelGGL((k_probe_refill<PROBE0_STEPS, 0>), dim3(c->probe_refill0, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-                else
-                    hipLaunchKernelGGL((k_probe_lut<PROBE0_STEPS, 0>), dim3(64 * gm, Fs), dim3(256), 0, sa, masks, starts, surv1, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-                if (c->probe_refill && gm == 1)  // (batches: 16 waves a frame that keep their lanes filled; a call of a few frames wants every start in flight at once)
-                    hipLaunchKernelGGL((k_probe_refill<PROBE1_STEPS, 1>), dim3(c->probe_refill, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-                else
-                    hipLaunchKernelGGL((k_probe_lut<PROBE1_STEPS, 1>), dim3(16 * gm, Fs), dim3(256), 0, sa, masks, surv1, surv, counts, c->d_global, P,
-                                       (const uint4 *)c->d_probe_tables);
-            }
-            const int wb3 = c->walk2_div > 0 ? (wb / c->walk2_div > 0 ? wb / c->walk2_div : 1) : wb2;
-            hipLaunchKernelGGL(k_walk_full<2>, dim3(wb3, Fs), dim3(64 * WALK_WAVES), 0, sa, masks, surv, wres, tab, pool, segs, pend, counts,
-                               c->d_global, P);
-            if (si != sa) HIPCHK(c, hipStreamWaitEvent(sa, c->aux_idx[sb], 0));  // (the survivors' seed look-ups need the map)
-            hipLaunchKernelGGL(k_seg_cycles<0>, dim3(8 * gm, Fs), dim3(64), 0, sa, seedq, segs, pend, wres, contours, cinfo, cbase,
-                               recs, counts, c->d_global, P, 1, 0);
-            hipLaunchKernelGGL(k_seg_copy, dim3(cpb / 4 > 0 ? cpb / 4 : 1, Fs), dim3(256), 0, sa, recs, tab, pool, dense, counts, P, 1);
-            fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(32 * gm, Fs), dim3(64), lds1, sa, contours, tab, pool, cands, counts, P, cap1, 0,
-                               dense, cbase, 2);
-            fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(8 * gm, Fs), dim3(64), lds2, sa, contours, tab, pool, cands, counts, P,
-                               P.maxPerim + 1, 1, dense, cbase, 2);
-            if (c->profile) (void)hipEventRecord(ev[17], sa);
-            HIPCHK(c, hipEventRecord(c->aux_join[sb], sa));
-            // -- main stream, continued
-            HIPCHK(c, hipStreamWaitEvent(st, c->aux_idx[sb], 0));
-            hipLaunchKernelGGL(k_seg_link2, dim3(16 * gm, Fs), dim3(256), 0, st, seedq, segs, seedhash, counts, P);
-            // (a call of one or two frames: a lane for every seed at once -- a workgroup that came round to a second 64 seeds walked a
-            //  second longest cycle behind the first, 2 x 26 us of the single frame's 55 us)
-            const int scb = Fs <= 2 ? (int)((P.maxContours + 63) / 64 < 4096 ? (P.maxContours + 63) / 64 : 4096) : 32 * gm * c->light_x;
-            if (Fs <= 2)
-                hipLaunchKernelGGL(k_seg_cycles<48>, dim3(scb, Fs), dim3(64), 0, st, seedq, segs, pend, wres, contours, cinfo, cbase,
-                                   recs, counts, c->d_global, P, 0, getenv("FID_NO_SEGC_WARM") ? 0 : 1);
-            else
-                hipLaunchKernelGGL(k_seg_cycles<0>, dim3(scb, Fs), dim3(64), 0, st, seedq, segs, pend, wres, contours, cinfo, cbase,
-                                   recs, counts, c->d_global, P, 0, 0);
-            hipLaunchKernelGGL(k_seg_copy, dim3(cpb, Fs), dim3(256), 0, st, recs, tab, pool, dense, counts, P, 0);
-            mark(ST_WALK + 1);
-            chain_point(2);
-            fid_launch_log("k_approx", 64, (size_t)(lds1));
-            hipLaunchKernelGGL(k_approx, dim3(128 * gm, Fs), dim3(64), lds1, st, contours, tab, pool, cands, counts, P, cap1, 0,
-                               dense, cbase, 1);
-            fid_launch_log("k_approx", 64, (size_t)(lds2));
-            hipLaunchKernelGGL(k_approx, dim3(16 * gm, Fs), dim3(64), lds2, st, contours, tab, pool, cands, counts, P,
-                               P.maxPerim + 1, 1, dense, cbase, 1);
-            mark(ST_APPROX + 1);
-            chain_point(3);
-            if (chainp) {
-                // the candidate tail of this piece moves to its auxiliary stream (behind the seedless chain, which is there already):
-                // the main stream is free for the front of the piece after next
-                HIPCHK(c, hipEventRecord(c->front_done[sb], st));
-                HIPCHK(c, hipStreamWaitEvent(sa, c->front_done[sb], 0));
-                st = sa;
-            } else {
-                HIPCHK(c, hipStreamWaitEvent(st, c->aux_join[sb], 0));
-            }
-        }
-        if (nsub > 1 && c->stagger > 0) HIPCHK(c, hipEventRecord(c->walk_done[sb], st));
-        chain_point(4);
-        // ---- K5
-        float4 *cmeta = c->d_cmeta + f0 * MC;
-        // (a rank sort: every candidate is compared with all of them -- a call of a few frames gives the frame sixteen workgroups)
-        fid_launch_log("k_sort_cands", 256, (size_t)(MC * 8));
-        hipLaunchKernelGGL(k_sort_cands, dim3(Fs, (c->light_x > 1 || Fs < 16) ? 16 : 1), dim3(256), MC * 8, st, cands, sorted, cmeta, counts, P);
-        mark(ST_SORT + 1);
-        hipLaunchKernelGGL(k_near, dim3(32 * gm * c->light_x, Fs), dim3(256), 0, st, sorted, cmeta, nearb, counts, P);
-        mark(ST_NEAR + 1);
-        {
-            // sizes, labels, component sizes; the rest holds the near triangle (64 KB: fits beside two seed-walker workgroups of
-            // the other sub-batch on a CU; with 96 KB the kernel waited for whole CUs to drain)
-            const size_t lds = (size_t)c->resolve_lds_kb * 1024;
-            const int near_words = c->resolve_serial ? 0 : (int)((lds - 3 * MC * 4) / 4);
-            fid_launch_log("k_resolve", 1024, (size_t)(lds));
-            hipLaunchKernelGGL(k_resolve, dim3(Fs), dim3(1024), lds, st, sorted, nearb, filtered, counts, worklist, nwork, P, near_words, c->d_global,
-                               c->resolve_reg_max);
-        }
-        mark(ST_RESOLVE + 1);
-        chain_point(5);
-        // ---- K6
-        {
-            int SZ = (P.markerSize + 2 * P.borderBits) * P.cellSize;
-            fid_launch_log("k_identify", 64, (size_t)((size_t)SZ * SZ));
-            hipLaunchKernelGGL(k_identify, dim3(c->tail_grid > 0 ? c->tail_grid : 256 * 4), dim3(64), (size_t)SZ * SZ, st, g, gfstride, filtered, worklist, nwork,
-                               c->d_dict, ident, c->d_bits + f0 * MC * (size_t)(P.markerSize + 2 * P.borderBits) * (P.markerSize + 2 * P.borderBits), P);
-        }
-        mark(ST_IDENT + 1);
-        // ---- K7
-        fid_launch_log("k_filter_markers", 64, (size_t)((size_t)c->filter_lds * sizeof(fid_marker)));
-        hipLaunchKernelGGL(k_filter_markers, dim3(Fs), dim3(64), (size_t)c->filter_lds * sizeof(fid_marker), st, filtered, ident, pre, counts, P,
-                           c->d_filter_scratch + f0 * MC, c->filter_lds, c->d_accsrc + f0 * MC, c->d_mksrc + f0 * MM);
-        mark(ST_FILTER + 1);
-        {
-            long long items = (long long)Fs * P.maxMarkers * 4;
-            const long long bcap = c->tail_grid > 0 ? 4LL * c->tail_grid : 256 * 16;
-            int blocks = (int)(items < bcap ? items : bcap);
-            if (P.refine == 2)  // CORNER_REFINE_CONTOUR: a wave per marker fits the four sides of its contour (writes ids and corners)
-                hipLaunchKernelGGL(k_refine_contour, dim3(P.maxMarkers < 64 ? P.maxMarkers : 64, Fs), dim3(64), 0, st, (const fid_marker *)pre, markers,
-                                   (const int *)(c->d_mksrc + f0 * MM), (const DevCand *)filtered,
-                                   (const uint32_t *)(c->d_dense ? c->d_dense + (size_t)f0 * P.maxChunks * (CK / 4) : nullptr), (const uint32_t *)tab,
-                                   (const uint32_t *)pool, counts, P);
-            else if (P.subpixWin <= 7)  // (the LDS and tap registers of k_subpix follow its window bound)
-                hipLaunchKernelGGL(k_subpix<7>, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
-            else
-                hipLaunchKernelGGL(k_subpix<SP_MAXWIN_MAX>, dim3(blocks), dim3(64), 0, st, g, gfstride, pre, markers, counts, c->d_subpix_mask, P);
-        }
-        mark(ST_SUBPIX + 1);
-        if (c->pose_req.ahead(c))  // (the remembered marker pose; where fid_pose_last_cov_cam was the last to ask, its covariance behind it)
-            pose_launch(c, st, ev[18], ev[19], markers, &counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, Fs, P.maxMarkers,
-                        c->pose_req.ask, c->d_poses + f0 * MM, c->d_pcov ? c->d_pcov + f0 * MM : nullptr);
-        chain_point(99);
+                if (o != sb) HIPCHK(c, hipStreamWaitEvent(s.st, c->fs_done[o], 0));
+        fid_status rc = cycles ? stage_cycle_tracing(c, s, grids[sb]) : stage_whole_border(c, s, grids[sb]);
+        if (rc == FID_OK) rc = stage_tail(c, s, grids[sb]);
+        if (rc != FID_OK) return rc;
         if (nsub > 1) {
-            HIPCHK(c, hipEventRecord(c->sub_done[sb], st));
+            HIPCHK(c, hipEventRecord(c->sub_done[sb], s.tail));
             // (a chain of pieces: the context's stream carries the fronts of the even pieces -- it waits for the tails when all
             //  pieces are enqueued, below)
             if (!chainp) HIPCHK(c, hipStreamWaitEvent(st0, c->sub_done[sb], 0));
@@ -977,20 +1163,25 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     };
     if (chainp) {
         // piece by piece: piece k + 2 goes behind piece k on the same two streams
-        for (int sb = 0; sb < nsub; sb++)
-            for (int phase = 0; phase < 2; phase++) {
-                const fid_status rcs = sub_phase(sb, phase);
-                if (rcs != FID_OK) return rcs;
-            }
+        for (int sb = 0; sb < nsub; sb++) {
+            fid_status rcs = front(sb);
+            if (rcs == FID_OK) rcs = rest(sb);
+            if (rcs != FID_OK) return rcs;
+        }
         for (int sb = 0; sb < nsub; sb++) HIPCHK(c, hipStreamWaitEvent(st0, c->sub_done[sb], 0));
     } else {
-        for (int phase = 0; phase < 2; phase++)
-            for (int sb = 0; sb < nsub; sb++) {
-                const fid_status rcs = sub_phase(sb, phase);
-                if (rcs != FID_OK) return rcs;
-            }
+        // The host enqueues in two rounds: first every sub-batch's front, then every sub-batch's rest.  (One round -- a whole
+        // sub-batch, some thirty launches, before the next one's first kernel -- left the second sub-batch's stream empty for the
+        // first 0.35 - 0.6 ms of every step.)
+        for (int sb = 0; sb < nsub; sb++) {
+            const fid_status rcs = front(sb);
+            if (rcs != FID_OK) return rcs;
+        }
+        for (int sb = 0; sb < nsub; sb++) {
+            const fid_status rcs = rest(sb);
+            if (rcs != FID_OK) return rcs;
+        }
     }
-    hipStream_t st = st0;
     const DevParams &P = c->P;
     HIPCHK(c, hipGetLastError());
     // ---- results
@@ -1001,27 +1192,27 @@ fid_status enqueue_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H,
     const PoseAsk &ma = c->map_req.ask;
     if (map_ahead) {
         // the camera among the map's fiducials, a wave per frame, behind every sub-batch's k_pose
-        map_pose_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, ma.cam, c->d_mposes, ma.cov,
+        map_pose_launch(c, st0, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, ma.cam, c->d_mposes, ma.cov,
                         ma.sigma, c->d_mcov);
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_req.ahead(c) ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st));  // one copy
-    if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
-    if (map_ahead && ma.cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(c->h_res, c->d_res, c->pose_req.ahead(c) ? c->res_poses_end : c->res_markers_end, hipMemcpyDeviceToHost, st0));  // one copy
+    if (map_ahead) HIPCHK(c, hipMemcpyAsync(c->h_mposes, c->d_mposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st0));
+    if (map_ahead && ma.cov) HIPCHK(c, hipMemcpyAsync(c->h_mcov, c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)F, hipMemcpyDeviceToHost, st0));
     if (c->rob_req.ahead(c)) {
         // fid_map_pose_robust_last_cam asked before: the consensus pose of these frames, for the same camera and options
-        map_pose_robust_launch(c, st, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->rob_req.ask.cam,
+        map_pose_robust_launch(c, st0, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), P.maxMarkers, F, c->rob_req.ask.cam,
                                c->rob_req.ask.opts, c->d_rposes, c->d_mrob);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_rposes, c->d_rposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(c->h_mrob, c->d_mrob, sizeof(fid_map_robust_out) * (size_t)F, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(c->h_rposes, c->d_rposes, sizeof(fid_map_pose_out) * (size_t)F, hipMemcpyDeviceToHost, st0));
+        HIPCHK(c, hipMemcpyAsync(c->h_mrob, c->d_mrob, sizeof(fid_map_robust_out) * (size_t)F, hipMemcpyDeviceToHost, st0));
     }
     c->last_frames = F;
     c->last_W = W;
     c->last_H = H;
     c->last_gray = gray;
     c->last_gfstride = gfstride;
-    c->pend = {d_src, F, W, H, stride, fstride, enc};
+    c->pend = in;
     c->in_flight = true;
     c->chained = false;
     c->wait_ev = nullptr;       // fid_order_after holds for ONE submit: the other context's events are not kept beyond it (it may
@@ -1070,9 +1261,9 @@ fid_status finish_detect(fid_ctx *c, fid_marker *out, int cap_per_frame, int *n_
         if (!c->whole_border_walk)  // the seed walk, and the seedless chain beside it on the auxiliary streams
             for (int sb = 0; sb < c->last_nsub; sb++) {
                 float ms = 0.f;
-                if (hipEventElapsedTime(&ms, c->sub_ev[sb][14], c->sub_ev[sb][15]) == hipSuccess) c->stage_ms[ST_SEEDWALK] += ms;
-                if (hipEventElapsedTime(&ms, c->sub_ev[sb][16], c->sub_ev[sb][17]) == hipSuccess) c->stage_ms[ST_SEEDLESS] += ms;
-                if (c->pose_req.at_hand && hipEventElapsedTime(&ms, c->sub_ev[sb][18], c->sub_ev[sb][19]) == hipSuccess) c->stage_ms[ST_POSE] += ms;
+                if (hipEventElapsedTime(&ms, c->sub_ev[sb][EV_SEEDWALK0], c->sub_ev[sb][EV_SEEDWALK1]) == hipSuccess) c->stage_ms[ST_SEEDWALK] += ms;
+                if (hipEventElapsedTime(&ms, c->sub_ev[sb][EV_SEEDLESS0], c->sub_ev[sb][EV_SEEDLESS1]) == hipSuccess) c->stage_ms[ST_SEEDLESS] += ms;
+                if (c->pose_req.at_hand && hipEventElapsedTime(&ms, c->sub_ev[sb][EV_POSE0], c->sub_ev[sb][EV_POSE1]) == hipSuccess) c->stage_ms[ST_POSE] += ms;
             }
     }
 #ifdef FID_DEBUG_STATS
@@ -1166,6 +1357,59 @@ fid_status run_detect(fid_ctx *c, const uint8_t *d_src, int F, int W, int H, int
     return finish_detect(c, out, cap_per_frame, n_per_frame);
 }
 
+// The launch tunables of a context, from the environment: read once, here, when the context is created
+fid_ctx::Tuning read_tuning()
+{
+    fid_ctx::Tuning t;
+    auto num = [](const char *name, int *v) {  // (a variable that is not set leaves the default)
+        const char *e = getenv(name);
+        if (e) *v = atoi(e);
+        return e != nullptr;
+    };
+    int v = 0;
+    num("FID_SUB_FRAMES", &t.sub_frames);
+    if (const char *e = getenv("FID_SUB_SHARES")) {
+        t.sub_shares_set = true;
+        t.n_sub_share = 0;
+        for (const char *q = e; *q && t.n_sub_share < fid_ctx::MAX_SUB;) {
+            if (atoi(q) > 0) t.sub_share[t.n_sub_share++] = atoi(q);
+            while (*q && *q != ',') q++;
+            if (*q == ',') q++;
+        }
+    }
+    if (const char *e = getenv("FID_FEED_SHARES")) (void)sscanf(e, "%d,%d,%d,%d", &t.feed_share[0], &t.feed_share[1], &t.feed_share[2], &t.feed_share[3]);
+    num("FID_PIECES", &t.pieces);
+    num("FID_STAGGER", &t.stagger);
+    num("FID_FS_BARRIER", &t.fs_barrier);
+    num("FID_CHAIN_AT", &t.chain_at);
+    t.idx_stream = getenv("FID_NO_IDX_STREAM") == nullptr;
+    if (num("FID_PRIO", &v)) t.prio = v != 0;
+    if (num("FID_THR_NW", &v)) t.thr_nw = v == 3 ? 3 : 5;
+    if (num("FID_THR_SPLIT", &v)) t.thr_split = v != 0;
+    num("FID_THR_ROWS", &t.thr_rows);
+    if (num("FID_THR_XCD", &v)) t.thr_xcd = v != 0;
+    num("FID_SEED_SHIFT", &t.seed_shift);
+    if (const char *e = getenv("FID_SEED_KERNEL")) t.seed_kernel = !strcmp(e, "split") ? 1 : (!strcmp(e, "fused") ? 2 : 0);
+    t.trace_legacy = getenv("FID_TRACE") && !strcmp(getenv("FID_TRACE"), "legacy");
+    if (num("FID_WALK_BLOCKS", &v) && v > 0) t.walk_blocks = v;
+    num("FID_WALK_CAP", &t.walk_blocks_cap);
+    num("FID_WALK2_DIV", &t.walk2_div);
+    num("FID_SW_BLOCKS", &t.sw_blocks);
+    num("FID_COPY_BLOCKS", &t.copy_blocks);
+    num("FID_PROBE_REFILL", &t.probe_refill);
+    num("FID_PROBE_REFILL0", &t.probe_refill0);
+    if (num("FID_PROBE_PASSES", &v) && (v == 1 || v == 2)) t.probe_passes = v;  // (1 or 2; anything else leaves the default)
+    if (num("FID_PROBE_SINGLE", &v)) t.probe_single = v < 1 ? 1 : (v > 64 ? 64 : v);  // (1 ... 64 workgroups a frame, the range of the sweep; clamped)
+    t.segc_warm = getenv("FID_NO_SEGC_WARM") ? 0 : 1;
+    if (num("FID_LIGHT_X", &v)) t.light_x = v > 0 ? v : 1;
+    num("FID_RESOLVE_LDS", &t.resolve_lds_kb);
+    num("FID_RESOLVE_SERIAL", &t.resolve_serial);
+    if (num("FID_RESOLVE_REG_MAX", &v)) t.resolve_reg_max = v < 0 ? 0 : (v > 64 ? 64 : v);
+    num("FID_TAIL_GRID", &t.tail_grid);
+    if (num("FID_FILTER_LDS", &v)) t.filter_lds = v > 0 ? v : 1;
+    return t;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1255,21 +1499,8 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     size_t dbytes = (size_t)dict->n_markers * 4 * ((dict->marker_size * dict->marker_size + 7) / 8);
     c->dict_host.assign(dict->bytes, dict->bytes + dbytes);
     c->profile = getenv("FID_PROFILE") && atoi(getenv("FID_PROFILE")) != 0;
-    if (getenv("FID_SUB_FRAMES")) c->sub_frames = atoi(getenv("FID_SUB_FRAMES"));
-    if (getenv("FID_WALK_CAP")) c->walk_blocks_cap = atoi(getenv("FID_WALK_CAP"));
-    if (getenv("FID_SEED_SHIFT")) c->seed_shift = atoi(getenv("FID_SEED_SHIFT"));
-    if (const char *e = getenv("FID_SEED_KERNEL")) c->seed_kernel = !strcmp(e, "split") ? 1 : (!strcmp(e, "fused") ? 2 : 0);
-    if (getenv("FID_RESOLVE_SERIAL")) c->resolve_serial = atoi(getenv("FID_RESOLVE_SERIAL"));
-    if (getenv("FID_RESOLVE_REG_MAX")) {
-        const int v = atoi(getenv("FID_RESOLVE_REG_MAX"));
-        c->resolve_reg_max = v < 0 ? 0 : (v > 64 ? 64 : v);
-    }
-    if (getenv("FID_COPY_BLOCKS")) c->copy_blocks = atoi(getenv("FID_COPY_BLOCKS"));
-    if (getenv("FID_THR_NW")) c->thr_nw = atoi(getenv("FID_THR_NW")) == 3 ? 3 : 5;
-    if (getenv("FID_THR_SPLIT")) c->thr_split = atoi(getenv("FID_THR_SPLIT")) != 0;
-    if (getenv("FID_THR_ROWS")) c->thr_rows = atoi(getenv("FID_THR_ROWS"));
-    if (getenv("FID_THR_XCD")) c->thr_xcd = atoi(getenv("FID_THR_XCD")) != 0;
-    if (getenv("FID_WALK_BLOCKS")) c->walk_blocks = atoi(getenv("FID_WALK_BLOCKS")) > 0 ? atoi(getenv("FID_WALK_BLOCKS")) : c->walk_blocks;
+    c->tune = read_tuning();
+    c->whole_border_walk = c->tune.trace_legacy;
     memset(&c->P, 0, sizeof(c->P));
 
     fid_status rc = FID_OK;
@@ -1292,15 +1523,13 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     } while (0)
     TRYHIP(hipSetDevice(device));
     TRYHIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int i = 0; i <= ST_COUNT; i++) TRYHIP(hipEventCreate(&c->ev[i]));
+    for (hipEvent_t &e : c->pose_ev) TRYHIP(hipEventCreate(&e));
     TRYHIP(hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
     TRYHIP(hipEventCreateWithFlags(&c->tail_ev, hipEventDisableTiming));
     int prio_lo = 0, prio_hi = 0;  // (numerically lower = more urgent)
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    // FID_PRIO=1: earlier sub-batches more urgent.  Measured slower (18.1k vs 18.8k frames/s) than equal priorities.
-    const bool use_prio = getenv("FID_PRIO") && atoi(getenv("FID_PRIO"));
     for (int sb = 0; sb < fid_ctx::MAX_SUB; sb++) {
-        int prio = use_prio ? prio_hi + sb : prio_lo;
+        int prio = c->tune.prio ? prio_hi + sb : prio_lo;
         if (prio > prio_lo) prio = prio_lo;
         // (the sub-batch and auxiliary streams themselves are made when a call first needs them -- ensure_streams(): every live
         //  stream is a claim on the hardware queues; eighteen idle ones per context cost the STag path its rate in round 2, and
@@ -1314,7 +1543,7 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
         TRYHIP(hipEventCreateWithFlags(&c->fs_done[sb], hipEventDisableTiming));
         TRYHIP(hipEventCreateWithFlags(&c->front_done[sb], hipEventDisableTiming));
         TRYHIP(hipEventCreateWithFlags(&c->aux_idx[sb], hipEventDisableTiming));
-        for (int i = 0; i < 20; i++) TRYHIP(hipEventCreate(&c->sub_ev[sb][i]));
+        for (hipEvent_t &e : c->sub_ev[sb]) TRYHIP(hipEventCreate(&e));
     }
     const size_t F = L.max_batch, MC = L.max_candidates_per_frame, MM = L.max_markers_per_frame;
     TRY(dalloc(c, &c->d_subpix_mask, (size_t)(2 * SP_MAXWIN_MAX + 1) * (2 * SP_MAXWIN_MAX + 1)));
@@ -1336,27 +1565,6 @@ fid_status fid_create(const fid_params *params, const fid_dict *dict, const fid_
     TRY(dalloc(c, &c->d_surv, F * L.max_starts_per_frame));
     c->max_chunks = (L.max_points_per_frame + CK - 1) / CK;
     TRY(dalloc(c, &c->d_pool, F * (size_t)c->max_chunks * CKW));
-    c->whole_border_walk = getenv("FID_TRACE") && !strcmp(getenv("FID_TRACE"), "legacy");
-    if (getenv("FID_SW_BLOCKS")) c->sw_blocks = atoi(getenv("FID_SW_BLOCKS"));
-    if (getenv("FID_STAGGER")) c->stagger = atoi(getenv("FID_STAGGER"));
-    if (getenv("FID_PIECES")) c->pieces = atoi(getenv("FID_PIECES"));
-    if (getenv("FID_FS_BARRIER")) c->fs_barrier = atoi(getenv("FID_FS_BARRIER"));
-    if (getenv("FID_TAIL_GRID")) c->tail_grid = atoi(getenv("FID_TAIL_GRID"));
-    if (getenv("FID_FILTER_LDS")) c->filter_lds = atoi(getenv("FID_FILTER_LDS")) > 0 ? atoi(getenv("FID_FILTER_LDS")) : 1;
-    if (getenv("FID_LIGHT_X")) c->light_x = atoi(getenv("FID_LIGHT_X")) > 0 ? atoi(getenv("FID_LIGHT_X")) : 1;
-    if (getenv("FID_RESOLVE_LDS")) c->resolve_lds_kb = atoi(getenv("FID_RESOLVE_LDS"));
-    if (getenv("FID_WALK2_DIV")) c->walk2_div = atoi(getenv("FID_WALK2_DIV"));
-    if (getenv("FID_PROBE_REFILL")) c->probe_refill = atoi(getenv("FID_PROBE_REFILL"));
-    if (getenv("FID_PROBE_REFILL0")) c->probe_refill0 = atoi(getenv("FID_PROBE_REFILL0"));
-    if (getenv("FID_PROBE_PASSES")) {  // (1 or 2; anything else leaves the default)
-        const int v = atoi(getenv("FID_PROBE_PASSES"));
-        if (v == 1 || v == 2) c->probe_passes = v;
-    }
-    if (getenv("FID_PROBE_SINGLE")) {  // (1 ... 64 workgroups a frame, the range of the sweep; clamped)
-        const int v = atoi(getenv("FID_PROBE_SINGLE"));
-        c->probe_single = v < 1 ? 1 : (v > 64 ? 64 : v);
-    }
-    if (getenv("FID_CHAIN_AT")) c->chain_at = atoi(getenv("FID_CHAIN_AT"));
     if (!c->whole_border_walk) {
         TRY(dalloc(c, &c->d_segs, F * L.max_contours_per_frame));
         TRY(dalloc(c, &c->d_pend, F * L.max_contours_per_frame));
@@ -1430,8 +1638,8 @@ void fid_destroy(fid_ctx *c)
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
-    for (int i = 0; i <= ST_COUNT; i++)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+    for (hipEvent_t e : c->pose_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
     if (c->tail_ev) (void)hipEventDestroy(c->tail_ev);
     for (int sb = 0; sb < fid_ctx::MAX_SUB; sb++) {
@@ -1453,8 +1661,8 @@ void fid_destroy(fid_ctx *c)
         if (c->in_ready[sb]) (void)hipEventDestroy(c->in_ready[sb]);
         if (c->fs_done[sb]) (void)hipEventDestroy(c->fs_done[sb]);
         if (c->front_done[sb]) (void)hipEventDestroy(c->front_done[sb]);
-        for (int i = 0; i < 20; i++)
-            if (c->sub_ev[sb][i]) (void)hipEventDestroy(c->sub_ev[sb][i]);
+        for (hipEvent_t e : c->sub_ev[sb])
+            if (e) (void)hipEventDestroy(e);
         if (c->sub_stream[sb] && c->sub_stream[sb] != c->stream) (void)hipStreamDestroy(c->sub_stream[sb]);
     }
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -1702,7 +1910,7 @@ fid_status fid_detect(fid_ctx *c, const uint8_t *img, int32_t width, int32_t hei
 static fid_status run_pose(fid_ctx *c, const fid_marker *d_markers, const int *d_n, int n_stride_ints, const double *d_lens, int F, int per_frame,
                            const PoseAsk &a, fid_pose_out *d_out, fid_pose_cov *d_cov)
 {
-    pose_launch(c, c->stream, c->ev[ST_POSE], c->ev[ST_POSE + 1], d_markers, d_n, n_stride_ints, d_lens, F, per_frame, a, d_out, d_cov);
+    pose_launch(c, c->stream, c->pose_ev[0], c->pose_ev[1], d_markers, d_n, n_stride_ints, d_lens, F, per_frame, a, d_out, d_cov);
     HIPCHK(c, hipGetLastError());
     return FID_OK;
 }
@@ -1745,7 +1953,7 @@ static fid_status pose_last_run(fid_ctx *c, const fid_camera *camera, double fid
         if (rc != FID_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_poses, c->d_poses, sizeof(fid_pose_out) * (size_t)F * MM, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->profile) (void)hipEventElapsedTime(&c->stage_ms[ST_POSE], c->ev[ST_POSE], c->ev[ST_POSE + 1]);
+        if (c->profile) (void)hipEventElapsedTime(&c->stage_ms[ST_POSE], c->pose_ev[0], c->pose_ev[1]);
         c->pose_req.answered(ask);  // (asked for without its covariance: the next call runs k_pose alone)
     }
     int nmax = 0;
