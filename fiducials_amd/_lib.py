@@ -69,6 +69,12 @@ class FidMapRobustOpts(C.Structure):
     _fields_ = [("inlier_px", C.c_double), ("min_markers", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class FidCalibOpts(C.Structure):
+    """fid_calib_opts (fid_default_calib_opts fills the defaults)."""
+    _fields_ = [("free_mask", C.c_uint32), ("start", C.c_int32), ("fix_aspect", C.c_int32), ("min_markers", C.c_int32), ("max_iter", C.c_int32),
+                ("reserved0", C.c_int32), ("eps", C.c_double)]
+
+
 class FidLimits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_starts_per_frame", C.c_int32), ("max_contours_per_frame", C.c_int32),
@@ -121,6 +127,17 @@ MAP_ROBUST_INLIER_PX = 4.0  # the header's RECOMMENDED inlier_px (the ABI has no
 MAP_ROBUST_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_inliers", "<i4"), ("n_outliers", "<i4"), ("hypothesis", "<i4"),
                              ("rounds", "<i4"), ("stable", "<i4"), ("reserved0", "<i4"), ("score", "<f8"), ("worst_inlier_px", "<f8"),
                              ("best_outlier_px", "<f8"), ("outlier_mask", "<u8", (4,)), ("outlier_index", "<i4", (16,))])
+# fid_calibrate_map (fid_abi.h: "camera calibration from views of the map")
+CALIB_MAX_VIEWS = 1024
+CALIB_START_GIVEN, CALIB_START_AUTO = 0, 1
+CALIB_OK, CALIB_MAX_ITER, CALIB_STALLED = 0, 1, 2
+CALIB_VIEW_USED, CALIB_VIEW_FEW, CALIB_VIEW_NO_START = 0, 1, 2
+CALIB_FREE_FOCAL, CALIB_FREE_K, CALIB_FREE_PLUMB_BOB, CALIB_FREE_PLUMB_BOB_NO_K3 = 0x0003, 0x000F, 0x01FF, 0x00FF
+CALIB_FREE_EQUIDISTANT, CALIB_FREE_RATIONAL, CALIB_FREE_RATIONAL_PRISM = 0x00FF, 0x0FFF, 0xFFFF
+CALIB_OUT_DTYPE = np.dtype([("status", "<i4"), ("n_views_used", "<i4"), ("n_points", "<i4"), ("n_iter", "<i4"), ("n_free", "<i4"), ("reserved0", "<i4"),
+                            ("cost", "<f8"), ("rms", "<f8"), ("start_cost", "<f8"), ("std_dev", "<f8", (16,))])  # fid_calib_out
+CALIB_VIEW_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_over", "<i4"), ("reserved0", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
+                             ("rms", "<f8")])  # fid_calib_view
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -136,6 +153,7 @@ SYMBOLS = [
     "fid_stag_bundle_pose_cam", "fid_stag_detect_bundles_batch_cam", "fid_stag_detect_bundles_batch_device_cam",
     "fid_pose_cov_cam", "fid_pose_last_cov_cam", "fid_map_pose_last_cov_cam", "fid_map_pose_cov_cam",
     "fid_map_pose_robust_cam", "fid_map_pose_robust_last_cam",
+    "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -328,6 +346,12 @@ def load():
         cam = C.POINTER(FidCamera)
         L.fid_map_pose_robust_cam.argtypes = [vp, cam, vp, i32, C.POINTER(FidMapRobustOpts), vp, vp]
         L.fid_map_pose_robust_last_cam.argtypes = [vp, cam, C.POINTER(FidMapRobustOpts), vp, vp, i32]
+    if hasattr(L, "fid_calibrate_map"):  # (calibration from views of the map; FID_LIB may name a build from before it)
+        cam = C.POINTER(FidCamera)
+        L.fid_default_calib_opts.argtypes = [C.POINTER(FidCalibOpts)]
+        L.fid_default_calib_opts.restype = None
+        L.fid_calibrate_map.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(FidCalibOpts), cam, vp, vp]
+        L.fid_camera_to_info.argtypes = [cam, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

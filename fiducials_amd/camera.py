@@ -49,6 +49,19 @@ class Camera:
     def D(self) -> np.ndarray:
         return np.array(self.c.D[:self.n_dist], dtype=np.float64)
 
+    def to_info(self):
+        """Camera -> (distortion_model, K (3, 3), D) as sensor_msgs/CameraInfo carries them (fid_camera_to_info, the inverse of
+        from_info): "plumb_bob" with 5 coefficients, "rational_polynomial" with 8 or 12, "equidistant" with 4."""
+        L = _lib.load()
+        name = C.create_string_buffer(32)
+        K = (C.c_double * 9)()
+        D = (C.c_double * 12)()
+        n = C.c_int32(0)
+        rc = L.fid_camera_to_info(C.byref(self.c), name, K, D, C.byref(n))
+        if rc != _lib.FID_OK:
+            raise FidError(rc, "fid_camera_to_info: the camera's model or coefficient count is outside the ABI's")
+        return name.value.decode(), np.array(K[:], dtype=np.float64).reshape(3, 3), np.array(D[:n.value], dtype=np.float64)
+
     def __repr__(self) -> str:
         return f"Camera({MODEL_NAMES.get(self.model, self.model)}, K={self.K.tolist()}, D={self.D.tolist()})"
 

@@ -250,6 +250,8 @@ struct fid_ctx {
     // k_map_pose_robust (fid_map_pose_robust.hip): max_batch + 1 pose and robust records of its own, allocated by the first robust call
     fid_map_pose_out *d_rposes = nullptr, *h_rposes = nullptr;
     fid_map_robust_out *d_mrob = nullptr, *h_mrob = nullptr;
+    // fid_calibrate_map (fid_calib.hip): its buffers, sized by the views of the largest call; nothing until the first call
+    struct CalibBufs *calib = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -269,6 +271,9 @@ static void map_pose_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_mark
 // k_map_pose_robust for F frames on a stream (fid_map_pose_robust.hip, behind fid_map_pose.hip)
 static void map_pose_robust_launch(fid_ctx *c, hipStream_t st, const fid_marker *d_markers, const int *d_n, int n_stride_ints, int per_frame, int F,
                                    const fid_camera &camera, const fid_map_robust_opts &opts, fid_map_pose_out *d_out, fid_map_robust_out *d_rout);
+
+// fid_calibrate_map's buffers (fid_calib.hip, behind fid_map_pose_robust.hip)
+static void calib_free(fid_ctx *c);
 
 namespace {
 
@@ -1635,6 +1640,7 @@ void fid_destroy(fid_ctx *c)
                    c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in, c->d_pcov, c->d_pcov_in, c->d_mcov, c->d_rposes, c->d_mrob};
     for (void *p : dev)
         if (p) (void)hipFree(p);
+    calib_free(c);
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -2335,3 +2341,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_map.hip"
 #include "fid_map_pose.hip"
 #include "fid_map_pose_robust.hip"
+#include "fid_calib.hip"

@@ -511,6 +511,58 @@ class ArucoDetector:
         self._check(self._L.fid_map_pose_robust_last_cam(self._ctx, C.byref(cam.c), C.byref(opts), out.ctypes.data, rob.ctypes.data, len(out)))
         return out[:self._last_frames], rob[:self._last_frames]
 
+    # -- calibration ------------------------------------------------------------------------------
+    def calibrate_map(self, views, image_size, model: int = _lib.CAM_PLUMB_BOB, free: int | None = None, start=None, fix_aspect: bool = False,
+                      max_iter: int | None = None, eps: float | None = None, min_markers: int = 1):
+        """The camera from views of the context's map (fid_calibrate_map; set_map first).  views: a list of (corners (n, 4, 2), ids (n,))
+        as detect_markers_batch returns them, or of (ids, corners).  image_size: (width, height).  model: CAM_*.  free: a CALIB_FREE_*
+        mask (default: the model's usual one -- plumb-bob 9 slots, rational 12, equidistant 8).  start: None for the AUTO start (planar
+        maps), or the Camera to start from -- it also gives the values of the slots that are not free and, with fix_aspect, the ratio
+        fx / fy.  Returns (Camera, CALIB_OUT_DTYPE record, CALIB_VIEW_DTYPE array)."""
+        L = self._L
+        default_free = {_lib.CAM_PLUMB_BOB: (_lib.CALIB_FREE_PLUMB_BOB, 5), _lib.CAM_RATIONAL: (_lib.CALIB_FREE_RATIONAL, 8),
+                        _lib.CAM_EQUIDISTANT: (_lib.CALIB_FREE_EQUIDISTANT, 4)}
+        opts = _lib.FidCalibOpts()
+        L.fid_default_calib_opts(C.byref(opts))
+        if start is None:
+            if int(model) not in default_free:
+                raise FidError(_lib.FID_E_INVALID_ARG, f"calibrate_map: model {model} is not a CAM_* value")
+            mask, nd = default_free[int(model)]
+            if free is not None:
+                mask = int(free)
+                if int(model) == _lib.CAM_RATIONAL and mask >> 12:
+                    nd = 12
+            cam = _camera.Camera(int(model), np.eye(3), np.zeros(nd))
+            opts.start = _lib.CALIB_START_AUTO
+        else:
+            if not isinstance(start, _camera.Camera):
+                raise TypeError("start= takes a fiducials_amd.camera.Camera")
+            cam = _camera.Camera(start.model, start.K, start.D)
+            mask = default_free[cam.model][0] & ((1 << (4 + cam.n_dist)) - 1) if free is None else int(free)
+            opts.start = _lib.CALIB_START_GIVEN
+        opts.free_mask = mask
+        opts.fix_aspect = 1 if fix_aspect else 0
+        opts.min_markers = int(min_markers)
+        if max_iter is not None:
+            opts.max_iter = int(max_iter)
+        if eps is not None:
+            opts.eps = float(eps)
+        # a view: (corners, ids) as detect_markers_batch returns it, or (ids, corners) -- the ids are the flat one of the pair
+        views = [(a, b) if np.asarray(b).ndim <= 1 and np.asarray(a).ndim > 1 else (b, a) for a, b in views]
+        cap = max([len(np.asarray(v[1]).reshape(-1)) for v in views] + [1])
+        mk = np.zeros((max(len(views), 1), cap), _MARKER_DT)
+        n = np.zeros(max(len(views), 1), np.int32)
+        for i, (corners, ids) in enumerate(views):
+            ids = np.asarray(ids, np.int32).reshape(-1)
+            n[i] = len(ids)
+            mk["id"][i, :len(ids)] = ids
+            mk["corners"][i, :len(ids)] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        out = np.zeros(1, _lib.CALIB_OUT_DTYPE)
+        vout = np.zeros(max(len(views), 1), _lib.CALIB_VIEW_DTYPE)
+        self._check(L.fid_calibrate_map(self._ctx, mk.ctypes.data, n.ctypes.data, len(views), cap, int(image_size[0]), int(image_size[1]), C.byref(opts),
+                                        C.byref(cam.c), out.ctypes.data, vout.ctypes.data))
+        return cam, out[0], vout[:len(views)]
+
     # -- stage taps for parity tests ------------------------------------------------------------
     def tap(self, which: int) -> np.ndarray:
         nbytes = self._L.fid_tap_bytes(self._ctx, which)

@@ -456,6 +456,116 @@ fid_status fid_map_pose_robust_cam(fid_ctx *ctx, const fid_camera *cam, const fi
 fid_status fid_map_pose_robust_last_cam(fid_ctx *ctx, const fid_camera *cam, const fid_map_robust_opts *opts, fid_map_pose_out *pose_out,
                                         fid_map_robust_out *robust_out, int32_t cap_frames);
 
+/* ---- camera calibration from views of the map (additions to ABI 7: entry points and structs only).  cv::aruco::
+ * calibrateCameraAruco -- the board points of every view into cv::calibrateCamera -- as ONE joint least-squares solve over the
+ * intrinsics and one pose per view, on the device.  No OpenCV is at hand to compare with, so ITS MEANING IS FIXED HERE (restated in
+ * NumPy in tests/calib_restatement.py).
+ *
+ * Views.  n_views <= FID_CALIB_MAX_VIEWS marker lists; view v is markers[v * cap_per_view .. + n_per_view[v]) -- fid_detect_batch's
+ * output layout (a negative n_per_view counts as 0).  The markers used from a view are exactly fid_map_pose_cam's selection: list
+ * order, ids the map does not name skipped, an id seen twice in the view left out altogether, the first FID_MAP_MAX_USED kept and the
+ * rest counted in n_over.  A view with fewer than opts.min_markers used markers is skipped (FID_CALIB_VIEW_FEW); a view whose start
+ * pose cannot be computed -- fid_map_pose_cam's record under the start camera is the "cannot be posed" one or is not finite, or, with
+ * START_AUTO, the view's homography does not exist -- is skipped (FID_CALIB_VIEW_NO_START).  A skipped view does not fail the call.
+ * A corner that is not finite in any listed marker: FID_E_INVALID_ARG.
+ *
+ * Parameters.  Sixteen slots fx fy cx cy D[0..11], D in fid_camera's order for cam_io->model.  Bit i of opts.free_mask set: slot i
+ * is estimated; cleared: the slot keeps its value in *cam_io, byte for byte.  Slots 4 + n_dist and beyond (n_dist = cam_io->n_dist)
+ * are never free: a set bit there is FID_E_INVALID_ARG.  With opts.fix_aspect != 0 (CALIB_FIX_ASPECT_RATIO) bit 0 is ignored: fy
+ * is the parameter where bit 1 is set, and fx = a fy with a = cam_io->K[0] / cam_io->K[4] (std_dev[0] = a std_dev[1]); with bit 1
+ * cleared both stay.  n_free = the free intrinsics + 6 per used view.  Fewer residuals (2 per used corner) than n_free, or no used
+ * view: FID_E_INVALID_ARG.
+ *
+ * Start.  FID_CALIB_START_GIVEN: *cam_io is the start, any map.  FID_CALIB_START_AUTO: only where the used entries of every view
+ * with at least min_markers used markers are coplanar by k_map_pose's test (else FID_E_INVALID_ARG: give a start, as OpenCV asks
+ * for non-planar rigs).  AUTO's values (cvInitIntrinsicParams2D): the principal point ((w - 1) / 2, (h - 1) / 2) where its slot
+ * is free, the given value where it is fixed; per view H = findHomography's DLT (as k_map_pose runs it) from the view's points in
+ * their plane frame to the float pixels, the principal point subtracted from its first two rows (H[0][j] -= H[2][j] cx, H[1][j] -=
+ * H[2][j] cy); with h1, h2 its first two columns, d1 = (h1 + h2) / 2, d2 = (h1 - h2) / 2, each of the four scaled to unit length,
+ * the two constraints  h1x h2x X + h1y h2y Y = -h1z h2z  and  d1x d2x X + d1y d2y Y = -d1z d2z  in X = 1 / fx^2, Y = 1 / fy^2; the
+ * least-squares solution over all views by the 2 x 2 normal equations, rows added in view order; fx = sqrt(|1 / X|), fy = sqrt(|1 /
+ * Y|) for the slots that are free (with fix_aspect: fy from Y, fx = a fy); free distortion slots start at 0.  A solution that is not
+ * finite: FID_E_INVALID_ARG.  In both modes every view's pose starts from fid_map_pose_cam's own solve under the start camera.
+ *
+ * Solve.  Minimise cost = the sum of squared pixel residuals (projection by the model in double, unrounded, minus the float corner
+ * widened) over all used corners of all used views, by Levenberg-Marquardt with CvLevMarq's machine (fid_pnp.h's LevMarq): lambda =
+ * 10^l, l from -3 inside [-16, 16]; a trial step solves (J^T J with its diagonal times 1 + lambda) x = J^T e through the Schur
+ * complement of the per-view 6 x 6 blocks and moves to p - x; a trial whose cost is not above the current cost is accepted (l <- max(l
+ * - 1, -16)), otherwise rejected (l <- l + 1 and the step is solved again from the same J^T J).  The stop, tested in this order:
+ *   before a trial, max_iter trials (accepted or rejected) have been made     FID_CALIB_MAX_ITER   (max_iter = 0: the start is returned)
+ *   after an accepted trial, |x| / (|p| + DBL_EPSILON) < eps over all free parameters, p the parameters before the step
+ *                                                                                FID_CALIB_OK
+ *   after a rejected trial, l > 16, or a trial whose reduced matrix has no Cholesky factor or whose cost is not finite at l = 16
+ *                                                                                FID_CALIB_STALLED
+ * Defaults (fid_default_calib_opts): free_mask FID_CALIB_FREE_PLUMB_BOB, start AUTO, fix_aspect 0, min_markers 1, max_iter 100, eps
+ * 1e-12.  The returned parameters are those of the last accepted trial (or the start); the returned cost is evaluated at them and is
+ * never above the start's.  The result is to be judged at the minimum, not by the path.
+ *
+ * Reproducible: every sum runs in a fixed order (per-lane partial sums and a butterfly inside a view, views added in index order, no
+ * floating-point atomics); the same inputs give the same bytes.
+ *
+ * Refusals: FID_E_INVALID_ARG as named above and for a NULL pointer, n_views outside 1 .. FID_CALIB_MAX_VIEWS, cap_per_view < 1,
+ * image_w or image_h < 1, a camera that is not usable, eps negative or not finite, max_iter < 0, min_markers < 1, a start outside
+ * the two, no map, a batch in flight; fid_last_error says which.  Nothing of it exists on a context until its first call (buffers
+ * sized by n_views, kept and grown by the context); the results of the detect and pose calls are untouched by it. */
+#define FID_CALIB_MAX_VIEWS 1024
+#define FID_CALIB_START_GIVEN 0
+#define FID_CALIB_START_AUTO 1
+#define FID_CALIB_OK 0
+#define FID_CALIB_MAX_ITER 1
+#define FID_CALIB_STALLED 2
+#define FID_CALIB_VIEW_USED 0
+#define FID_CALIB_VIEW_FEW 1      /* fewer than min_markers used markers */
+#define FID_CALIB_VIEW_NO_START 2 /* no start pose */
+#define FID_CALIB_FREE_FOCAL 0x0003u
+#define FID_CALIB_FREE_K 0x000fu                /* fx fy cx cy */
+#define FID_CALIB_FREE_PLUMB_BOB 0x01ffu        /* + k1 k2 p1 p2 k3: 9 slots */
+#define FID_CALIB_FREE_PLUMB_BOB_NO_K3 0x00ffu  /* + k1 k2 p1 p2 */
+#define FID_CALIB_FREE_EQUIDISTANT 0x00ffu      /* + k1 k2 k3 k4 of the fisheye model: 8 slots */
+#define FID_CALIB_FREE_RATIONAL 0x0fffu         /* + k1 k2 p1 p2 k3 k4 k5 k6: 12 slots */
+#define FID_CALIB_FREE_RATIONAL_PRISM 0xffffu   /* + s1 s2 s3 s4: 16 slots */
+typedef struct fid_calib_opts {
+    uint32_t free_mask;
+    int32_t start;       /* FID_CALIB_START_* */
+    int32_t fix_aspect;
+    int32_t min_markers;
+    int32_t max_iter;
+    int32_t reserved0;   /* ignored */
+    double eps;
+} fid_calib_opts;
+typedef struct fid_calib_out {
+    int32_t status;      /* FID_CALIB_OK / MAX_ITER / STALLED */
+    int32_t n_views_used;
+    int32_t n_points;    /* corners of the used views */
+    int32_t n_iter;      /* trials made */
+    int32_t n_free;      /* free intrinsics + 6 n_views_used */
+    int32_t reserved0;   /* 0 */
+    double cost;         /* at the returned parameters */
+    double rms;          /* sqrt(cost / n_points): calibrateCamera's return value */
+    double start_cost;
+    double std_dev[16];  /* stdDeviationsIntrinsics: sqrt(diag((J^T J)^-1)_i cost / (2 n_points - n_free)) over the WHOLE parameter vector
+                            -- the intrinsics block of the inverse is the inverse of the Schur complement --, J at the returned
+                            parameters; 0 for a fixed slot, and all 0 where 2 n_points = n_free or the complement has no Cholesky factor */
+} fid_calib_out;
+typedef struct fid_calib_view {
+    int32_t status;      /* FID_CALIB_VIEW_* */
+    int32_t n_used;      /* markers used (counted for a skipped view too) */
+    int32_t n_over;
+    int32_t reserved0;   /* 0 */
+    double rvec[3], tvec[3];  /* the map in the camera; 0 for a skipped view */
+    double rms;          /* sqrt(the view's cost / its corners); 0 for a skipped view */
+} fid_calib_view;
+void fid_default_calib_opts(fid_calib_opts *opts);
+/* views: n_views records, may be NULL.  *cam_io: model, n_dist and the start / fixed values in; the calibrated camera out (unchanged
+ * on a refusal). */
+fid_status fid_calibrate_map(fid_ctx *ctx, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views, int32_t cap_per_view,
+                             int32_t image_w, int32_t image_h, const fid_calib_opts *opts, fid_camera *cam_io, fid_calib_out *out,
+                             fid_calib_view *views);
+/* fid_camera -> sensor_msgs/CameraInfo, the inverse of fid_camera_from_info.  Host code, no device.  model_string: room for 32 bytes;
+ * D: room for 12.  "plumb_bob" with 5 coefficients (n_dist 4: k3 = 0), "rational_polynomial" with 8 (n_dist <= 8) or 12,
+ * "equidistant" with 4.  FID_E_INVALID_ARG: a NULL pointer or a camera that is not usable. */
+fid_status fid_camera_to_info(const fid_camera *cam, char *model_string, double K[9], double *D, int32_t *n_D);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
