@@ -69,6 +69,12 @@ class FidMapRobustOpts(C.Structure):
     _fields_ = [("inlier_px", C.c_double), ("min_markers", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class FidBuildOpts(C.Structure):
+    """fid_build_opts (fid_default_build_opts fills the defaults)."""
+    _fields_ = [("fiducial_len", C.c_double), ("len_ids", C.c_void_p), ("len_values", C.c_void_p), ("n_len", C.c_int32), ("min_views", C.c_int32),
+                ("max_iter", C.c_int32), ("reserved0", C.c_int32), ("eps", C.c_double), ("sigma_px", C.c_double)]
+
+
 class FidCalibOpts(C.Structure):
     """fid_calib_opts (fid_default_calib_opts fills the defaults)."""
     _fields_ = [("free_mask", C.c_uint32), ("start", C.c_int32), ("fix_aspect", C.c_int32), ("min_markers", C.c_int32), ("max_iter", C.c_int32),
@@ -138,6 +144,18 @@ CALIB_OUT_DTYPE = np.dtype([("status", "<i4"), ("n_views_used", "<i4"), ("n_poin
                             ("cost", "<f8"), ("rms", "<f8"), ("start_cost", "<f8"), ("std_dev", "<f8", (16,))])  # fid_calib_out
 CALIB_VIEW_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_over", "<i4"), ("reserved0", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
                              ("rms", "<f8")])  # fid_calib_view
+# fid_build_map_cam (fid_abi.h: "building the map"); status: BUILD_*, a marker's: BUILD_MARKER_*, a view's: BUILD_VIEW_*
+BUILD_MAX_VIEWS, BUILD_MAX_MARKERS, BUILD_MAX_PER_VIEW = 4096, 128, 64
+BUILD_OK, BUILD_MAX_ITER, BUILD_STALLED = 0, 1, 2
+BUILD_MARKER_FIXED, BUILD_MARKER_SOLVED, BUILD_MARKER_FEW_VIEWS, BUILD_MARKER_UNREACHED, BUILD_MARKER_NO_START = 0, 1, 2, 3, 4
+BUILD_VIEW_USED, BUILD_VIEW_FEW, BUILD_VIEW_UNREACHED, BUILD_VIEW_NO_START = 0, 1, 2, 3
+BUILD_OUT_DTYPE = np.dtype([("status", "<i4"), ("n_views_used", "<i4"), ("n_markers", "<i4"), ("n_fixed", "<i4"), ("n_points", "<i4"), ("n_iter", "<i4"),
+                            ("n_free", "<i4"), ("reserved0", "<i4"), ("cost", "<f8"), ("start_cost", "<f8"), ("rms", "<f8")])  # fid_build_out
+_MAP_ENTRY_DT = np.dtype([("id", "<i4"), ("reserved0", "<i4"), ("len", "<f8"), ("R", "<f8", (3, 3)), ("t", "<f8", (3,))])  # fid_map_entry
+BUILD_MARKER_DTYPE = np.dtype([("id", "<i4"), ("status", "<i4"), ("n_views", "<i4"), ("slot", "<i4"), ("links", "<u4", (4,)), ("rms", "<f8"),
+                               ("entry", _MAP_ENTRY_DT), ("cov", "<f8", (6, 6))])  # fid_build_marker
+BUILD_VIEW_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_over", "<i4"), ("reserved0", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
+                             ("rms", "<f8")])  # fid_build_view
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -153,7 +171,7 @@ SYMBOLS = [
     "fid_stag_bundle_pose_cam", "fid_stag_detect_bundles_batch_cam", "fid_stag_detect_bundles_batch_device_cam",
     "fid_pose_cov_cam", "fid_pose_last_cov_cam", "fid_map_pose_last_cov_cam", "fid_map_pose_cov_cam",
     "fid_map_pose_robust_cam", "fid_map_pose_robust_last_cam",
-    "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info",
+    "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info", "fid_default_build_opts", "fid_build_map_cam", "fid_map_save_file",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -352,6 +370,11 @@ def load():
         L.fid_default_calib_opts.restype = None
         L.fid_calibrate_map.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(FidCalibOpts), cam, vp, vp]
         L.fid_camera_to_info.argtypes = [cam, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]
+    if hasattr(L, "fid_build_map_cam"):  # (building the map; FID_LIB may name a build from before it)
+        L.fid_default_build_opts.argtypes = [C.POINTER(FidBuildOpts)]
+        L.fid_default_build_opts.restype = None
+        L.fid_build_map_cam.argtypes = [vp, C.POINTER(FidCamera), vp, vp, i32, i32, vp, i32, C.POINTER(FidBuildOpts), vp, vp, i32, C.POINTER(i32), vp]
+        L.fid_map_save_file.argtypes = [C.c_char_p, vp, i32]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

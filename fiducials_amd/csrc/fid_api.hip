@@ -252,6 +252,8 @@ struct fid_ctx {
     fid_map_robust_out *d_mrob = nullptr, *h_mrob = nullptr;
     // fid_calibrate_map (fid_calib.hip): its buffers, sized by the views of the largest call; nothing until the first call
     struct CalibBufs *calib = nullptr;
+    // fid_build_map_cam (fid_map_build.hip): one buffer sized by the largest call; nothing until the first call
+    struct BuildBufs *build = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -274,6 +276,8 @@ static void map_pose_robust_launch(fid_ctx *c, hipStream_t st, const fid_marker 
 
 // fid_calibrate_map's buffers (fid_calib.hip, behind fid_map_pose_robust.hip)
 static void calib_free(fid_ctx *c);
+// fid_build_map_cam's buffer (fid_map_build.hip, behind fid_calib.hip)
+static void build_free(fid_ctx *c);
 
 namespace {
 
@@ -1641,6 +1645,7 @@ void fid_destroy(fid_ctx *c)
     for (void *p : dev)
         if (p) (void)hipFree(p);
     calib_free(c);
+    build_free(c);
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -2342,3 +2347,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_map_pose.hip"
 #include "fid_map_pose_robust.hip"
 #include "fid_calib.hip"
+#include "fid_map_build.hip"

@@ -108,6 +108,15 @@ def map_entries(ids, lengths, Rs, ts) -> np.ndarray:
     return e
 
 
+def save_map(path: str, markers) -> None:
+    """The file fiducial_slam reads as its map_file (fid_map_save_file): the FIXED and SOLVED records of build_map's markers."""
+    L = _lib.load()
+    m = np.ascontiguousarray(markers, dtype=_lib.BUILD_MARKER_DTYPE).reshape(-1)
+    rc = L.fid_map_save_file(str(path).encode(), m.ctypes.data if len(m) else None, len(m))
+    if rc != 0:
+        raise FidError(rc, L.fid_map_last_error().decode())
+
+
 def load_map(path: str, fiducial_len: float, fiducial_len_override: dict | None = None):
     """A fiducial_slam map file (fiducial_slam/src/map.cpp:541-625; fid_map_load_file): returns (entries, n_skipped) -- the
     entries as MAP_ENTRY_DTYPE with len = fiducial_len, or its per-id override (the node's fiducial_len_override list), and the
@@ -562,6 +571,55 @@ class ArucoDetector:
         self._check(L.fid_calibrate_map(self._ctx, mk.ctypes.data, n.ctypes.data, len(views), cap, int(image_size[0]), int(image_size[1]), C.byref(opts),
                                         C.byref(cam.c), out.ctypes.data, vout.ctypes.data))
         return cam, out[0], vout[:len(views)]
+
+    # -- building the map -------------------------------------------------------------------------
+    def build_map(self, views, camera, fiducial_len: float, fixed, len_override: dict | None = None, min_views: int = 2, max_iter: int | None = None,
+                  eps: float | None = None, sigma_px: float = 0.0):
+        """The map from a set of views by bundle adjustment on the device (fid_build_map_cam).  views: a list of (corners (n, 4, 2), ids
+        (n,)) as detect_markers_batch returns them, or of (ids, corners).  camera: a Camera (or (K, D) for plumb-bob), the same for every
+        view.  fixed: MAP_ENTRY_DTYPE records that define the map frame (at least one).  len_override: {id: length}.  Returns (entries,
+        out, markers, views): entries (MAP_ENTRY_DTYPE, the FIXED and SOLVED markers) goes straight into set_map; out a BUILD_OUT_DTYPE
+        record, markers a BUILD_MARKER_DTYPE array of every id seen, views a BUILD_VIEW_DTYPE array."""
+        L = self._L
+        cam = camera if isinstance(camera, _camera.Camera) else _camera.resolve(camera[0], camera[1], None)
+        opts = _lib.FidBuildOpts()
+        L.fid_default_build_opts(C.byref(opts))
+        opts.fiducial_len = float(fiducial_len)
+        opts.min_views = int(min_views)
+        opts.sigma_px = float(sigma_px)
+        if max_iter is not None:
+            opts.max_iter = int(max_iter)
+        if eps is not None:
+            opts.eps = float(eps)
+        lids = np.ascontiguousarray(list((len_override or {}).keys()), dtype=np.int32)
+        lvals = np.ascontiguousarray(list((len_override or {}).values()), dtype=np.float64)
+        if len(lids):
+            opts.len_ids, opts.len_values, opts.n_len = lids.ctypes.data, lvals.ctypes.data, len(lids)
+        fx = np.zeros(0, MAP_ENTRY_DTYPE) if fixed is None else np.ascontiguousarray(fixed, dtype=MAP_ENTRY_DTYPE).reshape(-1)
+        views = [(a, b) if np.asarray(b).ndim <= 1 and np.asarray(a).ndim > 1 else (b, a) for a, b in views]
+        cap = max([len(np.asarray(v[1]).reshape(-1)) for v in views] + [1])
+        mk = np.zeros((max(len(views), 1), cap), _MARKER_DT)
+        n = np.zeros(max(len(views), 1), np.int32)
+        for i, (corners, ids) in enumerate(views):
+            ids = np.asarray(ids, np.int32).reshape(-1)
+            n[i] = len(ids)
+            mk["id"][i, :len(ids)] = ids
+            mk["corners"][i, :len(ids)] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        out = np.zeros(1, _lib.BUILD_OUT_DTYPE)
+        vout = np.zeros(max(len(views), 1), _lib.BUILD_VIEW_DTYPE)
+        cap_m = max(int(n.sum()), 1)
+        mout = np.zeros(cap_m, _lib.BUILD_MARKER_DTYPE)
+        n_m = C.c_int32(0)
+        self._check(L.fid_build_map_cam(self._ctx, C.byref(cam.c), mk.ctypes.data, n.ctypes.data, len(views), cap, fx.ctypes.data if len(fx) else None,
+                                        len(fx), C.byref(opts), out.ctypes.data, mout.ctypes.data, cap_m, C.byref(n_m), vout.ctypes.data))
+        mout = mout[:n_m.value]
+        ok = (mout["status"] == _lib.BUILD_MARKER_FIXED) | (mout["status"] == _lib.BUILD_MARKER_SOLVED)
+        return np.ascontiguousarray(mout["entry"][ok]).astype(MAP_ENTRY_DTYPE), out[0], mout, vout[:len(views)]
+
+    @staticmethod
+    def save_map(path: str, markers) -> None:
+        """build_map's markers as the file fiducial_slam reads as its map_file (the module's save_map)."""
+        save_map(path, markers)
 
     # -- stage taps for parity tests ------------------------------------------------------------
     def tap(self, which: int) -> np.ndarray:

@@ -566,6 +566,140 @@ fid_status fid_calibrate_map(fid_ctx *ctx, const fid_marker *markers, const int3
  * "equidistant" with 4.  FID_E_INVALID_ARG: a NULL pointer or a camera that is not usable. */
 fid_status fid_camera_to_info(const fid_camera *cam, char *model_string, double K[9], double *D, int32_t *n_D);
 
+/* ---- building the map (additions to ABI 7: entry points and structs only).  The map that fid_set_map takes, made from a set of
+ * views by bundle adjustment: ONE joint least-squares solve over the pose of every fiducial and the pose of every view, on the
+ * device.  fiducial_slam builds its map sequentially (Map::autoInit, Map::updateMap: single-marker poses chained and fused with a
+ * scalar variance); this is the joint solve instead, no OpenCV function does it, so ITS MEANING IS FIXED HERE (restated in NumPy in
+ * tests/map_build_restatement.py).
+ *
+ * Views and selection.  n_views <= FID_BUILD_MAX_VIEWS marker lists; view v is markers[v * cap_per_view .. + n_per_view[v]) --
+ * fid_detect_batch's output layout (a negative n_per_view counts as 0, one above cap_per_view as cap_per_view).  Markers are taken
+ * in list order; an id seen twice in a view is left out of that view altogether; of the rest the first FID_BUILD_MAX_PER_VIEW are
+ * KEPT and the others counted in n_over.  A corner that is not finite in any listed marker: FID_E_INVALID_ARG.  The camera is *cam
+ * for every view (any of the three models) and is not estimated.
+ *
+ * Gauge.  fixed holds n_fixed >= 1 entries, each id once (none, or an id twice: FID_E_INVALID_ARG; an entry must pass fid_set_map's
+ * test).  They are not moved and define the map frame: one entry at identity is autoInit's "origin on a fiducial"; a surveyed map
+ * passed as fixed is extended by the fiducials it does not name.  The side length of a fiducial that is not fixed is
+ * opts.len_values[k] where opts.len_ids[k] is its id (the first such k), otherwise opts.fiducial_len; every length must be > 0.
+ * Object points as in fid_map_entry: (-h, h, 0), (h, h, 0), (h, -h, 0), (-h, -h, 0), h = (double)(float)(len / 2).
+ *
+ * Which markers and views enter.  n_views of a marker = the views that keep it.  A marker that is not fixed and is kept by fewer
+ * than opts.min_views views is FID_BUILD_MARKER_FEW_VIEWS and is not looked at again.  Reachability is a fixed point over the rest:
+ * a view is reached when it keeps a placed marker (a fixed one, or one reached earlier), a marker is reached when a reached view
+ * keeps it.  Markers and views outside the component of the fixed entries are UNREACHED; a view that keeps no marker other than
+ * FEW_VIEWS ones is FID_BUILD_VIEW_FEW.  The reached markers and the fixed markers that some view keeps are "in the solve": more
+ * than FID_BUILD_MAX_MARKERS of them is FID_E_UNSUPPORTED with the count in fid_last_error.  A marker or view in one of these states
+ * is left out; none of them fails the call.  No reached view at all, or fewer residuals than free parameters: FID_E_INVALID_ARG.
+ *
+ * Start, in rounds until nothing changes: (a) every view without a pose that keeps a placed marker gets fid_map_pose_cam's own
+ * solve (k_map_pose) over its placed markers in the solve; (b) every marker in the solve that is not placed and is kept by a posed
+ * view is placed from the posed view in which its image area (fid_pose_out.fiducial_area) is largest, a tie going to the lowest view
+ * index: T_map_fid = T_cam_map^-1 T_cam_fid with T_cam_fid = fid_pose_cam's pose of that marker under its own length (k_pose, run
+ * once over all kept markers).  A reached view whose solve gives the "cannot be posed" record or a value that is not finite is
+ * FID_BUILD_VIEW_NO_START and is skipped; a marker that no posed view keeps is FID_BUILD_MARKER_NO_START and is left out.
+ *
+ * Solve.  Minimise cost = the sum of squared pixel residuals (projection by the model in double of T_cam_map T_map_fid applied to the
+ * object point, minus the float corner widened) over the four corners of every USED observation: a marker in the solve kept by a used
+ * view.  Free parameters: (rvec, t) of T_map_fid of every marker in the solve that is not fixed, (rvec, tvec) of every used view (the
+ * map in the camera); n_free = 6 (these markers) + 6 (used views).  The residual function is the calibration's, the point first taken
+ * through the marker's pose (a fixed marker's through its entry's R and t as given).  Levenberg-Marquardt with the calibration's
+ * machine, word for word: lambda = 10^l, l from -3 inside [-16, 16]; a trial step solves (J^T J with its diagonal times 1 + lambda)
+ * x = J^T e -- the views eliminated first, the reduced system over the markers assembled and factored (Cholesky) on the device -- and
+ * moves to p - x; accept where the cost does not rise (l <- max(l - 1, -16)), else reject (l <- l + 1, the same J^T J); the stops in
+ * the calibration's order: max_iter trials made (FID_BUILD_MAX_ITER; max_iter = 0 returns the start), after an accepted trial |x| /
+ * (|p| + DBL_EPSILON) < eps over all free parameters (FID_BUILD_OK), l > 16 after a rejected trial or a trial without a Cholesky
+ * factor or a finite cost at l = 16 (FID_BUILD_STALLED).  Defaults (fid_default_build_opts): fiducial_len 0 (the caller sets it), no
+ * overrides, min_views 2, max_iter 100, eps 1e-12, sigma_px 0.  The result is to be judged at the minimum, not by the path.
+ *
+ * Reproducible: every sum runs in a fixed order (a matrix entry is one serial sum in row order, the views of a marker pair are
+ * added in index order, the factorisation's order is fixed by the code, costs are per-lane partial sums and a fixed tree; no
+ * floating-point atomics); the same inputs give the same bytes.
+ *
+ * Output.  markers_out: every id that some view keeps, ascending (more than cap_markers: FID_E_CAPACITY, *n_markers_out = the count).
+ * cov of a SOLVED marker: the marker's 6 x 6 block of (J^T J)^-1, the inverse taken over the WHOLE parameter vector, J at the returned
+ * parameters, row-major over (rvec, t) of T_map_fid, times cost / (2 n_points - n_free) -- with opts.sigma_px > 0 times sigma_px^2
+ * instead; zero for every other marker, and all zero where 2 n_points <= n_free (and sigma_px = 0) or the reduced matrix has no
+ * Cholesky factor.  entry of a FIXED marker is the given one, of a SOLVED marker (R = Rodrigues(rvec), t, its length) what fid_set_map
+ * takes as it is; of any other marker id and len only.  slot: the marker's index among the FIXED and SOLVED ones in id order (-1
+ * otherwise); links: bit k (word k / 32, bit k % 32) set where the marker of slot k shares a used view with this one.
+ *
+ * Refusals: FID_E_INVALID_ARG as named above and for a NULL pointer (views may be NULL), n_views outside 1 .. FID_BUILD_MAX_VIEWS,
+ * cap_per_view < 1, a camera that is not usable or not finite, a length <= 0, min_views < 1, max_iter < 0, eps or sigma_px negative
+ * or not finite, n_len < 0, a batch in flight; fid_last_error says which.  Nothing of it exists on a context until its first call
+ * (one buffer sized by the call, kept and grown by the context); the context's map and the results of the detect, pose and
+ * calibration calls are untouched by it. */
+#define FID_BUILD_MAX_VIEWS 4096
+#define FID_BUILD_MAX_MARKERS 128 /* distinct ids that enter the solve, fixed ones included */
+#define FID_BUILD_MAX_PER_VIEW 64 /* kept markers of one view; the rest counted in n_over */
+#define FID_BUILD_OK 0
+#define FID_BUILD_MAX_ITER 1
+#define FID_BUILD_STALLED 2
+#define FID_BUILD_MARKER_FIXED 0
+#define FID_BUILD_MARKER_SOLVED 1
+#define FID_BUILD_MARKER_FEW_VIEWS 2
+#define FID_BUILD_MARKER_UNREACHED 3
+#define FID_BUILD_MARKER_NO_START 4
+#define FID_BUILD_VIEW_USED 0
+#define FID_BUILD_VIEW_FEW 1
+#define FID_BUILD_VIEW_UNREACHED 2
+#define FID_BUILD_VIEW_NO_START 3
+typedef struct fid_build_opts {
+    double fiducial_len;
+    const int32_t *len_ids;   /* fiducial_len_override: n_len ids ... */
+    const double *len_values; /* ... and their lengths; both may be NULL where n_len is 0 */
+    int32_t n_len;
+    int32_t min_views;
+    int32_t max_iter;
+    int32_t reserved0;        /* ignored */
+    double eps;
+    double sigma_px;
+} fid_build_opts;
+typedef struct fid_build_out {
+    int32_t status;       /* FID_BUILD_OK / MAX_ITER / STALLED */
+    int32_t n_views_used;
+    int32_t n_markers;    /* in the solve, fixed ones included */
+    int32_t n_fixed;      /* of them fixed */
+    int32_t n_points;     /* corners of the used observations */
+    int32_t n_iter;       /* trials made */
+    int32_t n_free;       /* 6 (n_markers - n_fixed) + 6 n_views_used */
+    int32_t reserved0;    /* 0 */
+    double cost;          /* at the returned parameters */
+    double start_cost;
+    double rms;           /* sqrt(cost / n_points) */
+} fid_build_out;
+typedef struct fid_build_marker {
+    int32_t id;
+    int32_t status;       /* FID_BUILD_MARKER_* */
+    int32_t n_views;      /* views that keep it */
+    int32_t slot;
+    uint32_t links[4];
+    double rms;           /* sqrt(the cost of its used observations / their corners); 0 for a marker left out */
+    fid_map_entry entry;
+    double cov[36];
+} fid_build_marker;
+typedef struct fid_build_view {
+    int32_t status;       /* FID_BUILD_VIEW_* */
+    int32_t n_used;       /* markers in the solve that it keeps; 0 for a skipped view */
+    int32_t n_over;
+    int32_t reserved0;    /* 0 */
+    double rvec[3], tvec[3]; /* the map in the camera; 0 for a skipped view */
+    double rms;           /* sqrt(the view's cost / its corners); 0 for a skipped view */
+} fid_build_view;
+void fid_default_build_opts(fid_build_opts *opts);
+fid_status fid_build_map_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views,
+                             int32_t cap_per_view, const fid_map_entry *fixed, int32_t n_fixed, const fid_build_opts *opts, fid_build_out *out,
+                             fid_build_marker *markers_out, int32_t cap_markers, int32_t *n_markers_out, fid_build_view *views /* may be NULL */);
+/* the file fiducial_slam reads as its map_file (map.cpp:541-565): for every FIXED and SOLVED marker of the n, in the order given, the
+ * line `id x y z roll pitch yaw variance numObs links...` by "%d %lf %lf %lf %lf %lf %lf %lf %d" and " %d" per link.  x y z = entry.t;
+ * roll pitch yaw = tf2's getRPY of entry.R (pitch = asin(-R[2][0]); roll = atan2(R[2][1], R[2][2]), yaw = atan2(R[1][0], R[0][0]); at
+ * |R[2][0]| >= 1 yaw = 0 and roll = atan2(+-R[0][1], +-R[0][2])), in degrees; variance = (cov[21] + cov[28] + cov[35]) / 3, the mean of
+ * the three translational variances (0 for a fixed marker, as the reference's origin has); numObs = n_views; links = the ids of the
+ * markers named by `links`, ascending, the marker itself left out.  fid_map_load_file reads it back to the six printed decimals.
+ * n = 0 writes an empty file.  Host code, no device.  FID_E_INVALID_ARG: a NULL path, n < 0, n > 0 without markers, a file that
+ * cannot be written; fid_map_last_error() says what. */
+fid_status fid_map_save_file(const char *path, const fid_build_marker *markers, int32_t n);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
