@@ -75,6 +75,11 @@ class FidBuildOpts(C.Structure):
                 ("max_iter", C.c_int32), ("reserved0", C.c_int32), ("eps", C.c_double), ("sigma_px", C.c_double)]
 
 
+class FidBuildRobustOpts(C.Structure):
+    """fid_build_robust_opts: inlier_px (finite, > 0, no default), min_views_place (>= 1)."""
+    _fields_ = [("inlier_px", C.c_double), ("min_views_place", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class FidCalibOpts(C.Structure):
     """fid_calib_opts (fid_default_calib_opts fills the defaults)."""
     _fields_ = [("free_mask", C.c_uint32), ("start", C.c_int32), ("fix_aspect", C.c_int32), ("min_markers", C.c_int32), ("max_iter", C.c_int32),
@@ -156,6 +161,12 @@ BUILD_MARKER_DTYPE = np.dtype([("id", "<i4"), ("status", "<i4"), ("n_views", "<i
                                ("entry", _MAP_ENTRY_DT), ("cov", "<f8", (6, 6))])  # fid_build_marker
 BUILD_VIEW_DTYPE = np.dtype([("status", "<i4"), ("n_used", "<i4"), ("n_over", "<i4"), ("reserved0", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)),
                              ("rms", "<f8")])  # fid_build_view
+# fid_build_map_robust_cam (fid_abi.h: "building the map from views that hold wrong detections"); an observation's state: OBS_*
+BUILD_ROBUST_SOLVES, BUILD_ROBUST_HYPOTHESES = 4, 64
+OBS_NOT_KEPT, OBS_INLIER, OBS_OUTLIER, OBS_LEFT_OUT = 0, 1, 2, 3
+BUILD_ROBUST_MEASURED_PX, BUILD_ROBUST_INLIER_PX = 1.3215, 13.5  # the header's measured err and RECOMMENDED inlier_px (the ABI has no default)
+BUILD_ROBUST_OUT_DTYPE = np.dtype([("rounds", "<i4"), ("stable", "<i4"), ("n_obs", "<i4"), ("n_inliers", "<i4"), ("n_outliers", "<i4"), ("reserved0", "<i4"),
+                                   ("worst_inlier_px", "<f8"), ("best_outlier_px", "<f8")])  # fid_build_robust_out
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -172,6 +183,7 @@ SYMBOLS = [
     "fid_pose_cov_cam", "fid_pose_last_cov_cam", "fid_map_pose_last_cov_cam", "fid_map_pose_cov_cam",
     "fid_map_pose_robust_cam", "fid_map_pose_robust_last_cam",
     "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info", "fid_default_build_opts", "fid_build_map_cam", "fid_map_save_file",
+    "fid_build_map_robust_cam",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -375,6 +387,9 @@ def load():
         L.fid_default_build_opts.restype = None
         L.fid_build_map_cam.argtypes = [vp, C.POINTER(FidCamera), vp, vp, i32, i32, vp, i32, C.POINTER(FidBuildOpts), vp, vp, i32, C.POINTER(i32), vp]
         L.fid_map_save_file.argtypes = [C.c_char_p, vp, i32]
+    if hasattr(L, "fid_build_map_robust_cam"):  # (the trimmed build; FID_LIB may name a build from before it)
+        L.fid_build_map_robust_cam.argtypes = [vp, C.POINTER(FidCamera), vp, vp, i32, i32, vp, i32, C.POINTER(FidBuildOpts), C.POINTER(FidBuildRobustOpts), vp, vp,
+                                               vp, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

@@ -580,6 +580,18 @@ class ArucoDetector:
         view.  fixed: MAP_ENTRY_DTYPE records that define the map frame (at least one).  len_override: {id: length}.  Returns (entries,
         out, markers, views): entries (MAP_ENTRY_DTYPE, the FIXED and SOLVED markers) goes straight into set_map; out a BUILD_OUT_DTYPE
         record, markers a BUILD_MARKER_DTYPE array of every id seen, views a BUILD_VIEW_DTYPE array."""
+        return self._build_map(None, views, camera, fiducial_len, fixed, len_override, min_views, max_iter, eps, sigma_px)
+
+    def build_map_robust(self, views, camera, fiducial_len: float, fixed, inlier_px: float, min_views_place: int = 1, len_override: dict | None = None,
+                         min_views: int = 2, max_iter: int | None = None, eps: float | None = None, sigma_px: float = 0.0):
+        """build_map over views that hold wrong detections (fid_build_map_robust_cam): the solve is run in at most four rounds, each over
+        the observations within inlier_px of the round before, from a start made by consensus.  inlier_px has no default; the header
+        recommends _lib.BUILD_ROBUST_INLIER_PX.  Returns build_map's tuple plus (robust_out, obs_state, obs_err_px, marker_outliers,
+        view_outliers): a BUILD_ROBUST_OUT_DTYPE record; per view a uint8 array of _lib.OBS_* and a float64 array of the errors (-1 where
+        there is none), both parallel to the view's list; the outlier observations per entry of `markers` and per view (int32)."""
+        return self._build_map((float(inlier_px), int(min_views_place)), views, camera, fiducial_len, fixed, len_override, min_views, max_iter, eps, sigma_px)
+
+    def _build_map(self, robust, views, camera, fiducial_len, fixed, len_override, min_views, max_iter, eps, sigma_px):
         L = self._L
         cam = camera if isinstance(camera, _camera.Camera) else _camera.resolve(camera[0], camera[1], None)
         opts = _lib.FidBuildOpts()
@@ -610,11 +622,26 @@ class ArucoDetector:
         cap_m = max(int(n.sum()), 1)
         mout = np.zeros(cap_m, _lib.BUILD_MARKER_DTYPE)
         n_m = C.c_int32(0)
-        self._check(L.fid_build_map_cam(self._ctx, C.byref(cam.c), mk.ctypes.data, n.ctypes.data, len(views), cap, fx.ctypes.data if len(fx) else None,
-                                        len(fx), C.byref(opts), out.ctypes.data, mout.ctypes.data, cap_m, C.byref(n_m), vout.ctypes.data))
+        if robust is None:
+            self._check(L.fid_build_map_cam(self._ctx, C.byref(cam.c), mk.ctypes.data, n.ctypes.data, len(views), cap, fx.ctypes.data if len(fx) else None,
+                                            len(fx), C.byref(opts), out.ctypes.data, mout.ctypes.data, cap_m, C.byref(n_m), vout.ctypes.data))
+        else:
+            ropts = _lib.FidBuildRobustOpts(robust[0], robust[1], 0)
+            rout = np.zeros(1, _lib.BUILD_ROBUST_OUT_DTYPE)
+            state = np.zeros((len(n), cap), np.uint8)
+            err = np.zeros((len(n), cap), np.float64)
+            m_outl = np.zeros(cap_m, np.int32)
+            v_outl = np.zeros(len(n), np.int32)
+            self._check(L.fid_build_map_robust_cam(self._ctx, C.byref(cam.c), mk.ctypes.data, n.ctypes.data, len(views), cap, fx.ctypes.data if len(fx) else None,
+                                                   len(fx), C.byref(opts), C.byref(ropts), out.ctypes.data, rout.ctypes.data, mout.ctypes.data, cap_m, C.byref(n_m),
+                                                   vout.ctypes.data, state.ctypes.data, err.ctypes.data, m_outl.ctypes.data, v_outl.ctypes.data))
         mout = mout[:n_m.value]
         ok = (mout["status"] == _lib.BUILD_MARKER_FIXED) | (mout["status"] == _lib.BUILD_MARKER_SOLVED)
-        return np.ascontiguousarray(mout["entry"][ok]).astype(MAP_ENTRY_DTYPE), out[0], mout, vout[:len(views)]
+        plain = (np.ascontiguousarray(mout["entry"][ok]).astype(MAP_ENTRY_DTYPE), out[0], mout, vout[:len(views)])
+        if robust is None:
+            return plain
+        return plain + (rout[0], [state[v, :n[v]].copy() for v in range(len(views))], [err[v, :n[v]].copy() for v in range(len(views))], m_outl[:n_m.value],
+                        v_outl[:len(views)])
 
     @staticmethod
     def save_map(path: str, markers) -> None:

@@ -690,6 +690,108 @@ void fid_default_build_opts(fid_build_opts *opts);
 fid_status fid_build_map_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views,
                              int32_t cap_per_view, const fid_map_entry *fixed, int32_t n_fixed, const fid_build_opts *opts, fid_build_out *out,
                              fid_build_marker *markers_out, int32_t cap_markers, int32_t *n_markers_out, fid_build_view *views /* may be NULL */);
+
+/* ---- building the map from views that hold wrong detections (additions to ABI 7: entry points and structs only).
+ * fid_build_map_cam with a trimmed solve: at most FID_BUILD_ROBUST_SOLVES rounds of the same bundle adjustment, each over the
+ * observations within inlier_px of the round before, the start made by consensus, the observations left out named.  The design is
+ * fid_map_pose_robust_cam's (deterministic, hypotheses scored by a median, at most four solves with re-admission, outliers named).
+ * No OpenCV function does it, so ITS MEANING IS FIXED HERE (restated in NumPy in tests/map_build_robust_restatement.py).
+ *
+ * Error.  err(v, m) of a kept observation (view v keeps marker m) whose view and marker both have a pose: the largest pixel
+ * distance, over the four corners, between the float corner widened to double and the projection of the object point through
+ * T_cam_map(v) T_map_fid(m) by the camera model, in double, unrounded -- fid_map_pose_robust_cam's err.  A fixed marker's pose is its
+ * entry; a solved marker's is (Rodrigues(rvec), t) as returned in entry.
+ *
+ * Candidates.  Validation, the kept observations of a view, the per-view cap, FEW_VIEWS, reachability, FID_BUILD_MAX_MARKERS and the
+ * refusals are fid_build_map_cam's, evaluated over the ACTIVE observations: all kept ones at the beginning.  (A marker's n_views
+ * in markers_out stays the views that KEEP it.)
+ *
+ * Robust start, in fid_build_map_cam's rounds (a) and (b) until nothing changes:
+ *  (a) every reached view without a pose that keeps a placed marker gets fid_map_pose_robust_cam's own solve (k_map_pose_robust)
+ *      over its placed markers, with ropts.inlier_px and min_markers 1.  A record whose status is not FID_MAP_ROBUST_OK or that holds
+ *      a value that is not finite: the view is FID_BUILD_VIEW_NO_START.
+ *  (b) a marker in the solve that is not placed and is kept by at least ropts.min_views_place posed views gets one hypothesis per
+ *      posed view that keeps it and in which fid_pose_cam's pose of it under its own length (k_pose) exists and is finite:
+ *      T_map_fid = T_cam_map^-1 T_cam_fid.  At most FID_BUILD_ROBUST_HYPOTHESES are taken, those of largest fiducial_area, a tie going
+ *      to the lower view.  score(h) = the LOWER MEDIAN (element (n - 1) / 2 of the n sorted values) of err of the marker under h over
+ *      ALL posed views that keep it.  The hypothesis of smallest score places the marker, a tie going to the lower view; a marker
+ *      without a hypothesis, or whose smallest score is not finite, is not placed.  A marker with fewer posed views waits for a later
+ *      round; it is FID_BUILD_MARKER_NO_START if none comes.
+ * The start runs once, before the first solve; no later round starts a view or a marker again.
+ *
+ * First set.  A least-squares solve over every kept observation spreads each gross error over the truthful observations of the
+ * same marker and view (a pose moves by about 1 / n of the error, n its observations), and their err then stands AT inlier_px: on
+ * the reference's cases with swapped ids and with a moved fiducial the largest admitted and the smallest refused err of such a first
+ * solve lie within 3 % of the recommended inlier_px on both sides, and with a wrong id in a marker's largest observation five
+ * truthful observations end as outliers (tests/test_map_build_robust_restatement.py shows it).  So, as fid_map_pose_robust_cam
+ * admits its first set under the winning hypothesis before its first solve, err is computed under the START's poses and the first
+ * active set is { err <= inlier_px }; an observation without an err stays active, and a truthful observation that the start (a
+ * chain of single-marker poses, not a minimum) does not admit returns after the first solve.  FEW_VIEWS, reachability and the used
+ * views are recomputed over the first set; no reached view then: FID_E_INVALID_ARG.
+ *
+ * A limit of the start: a marker is placed in the first start round in which min_views_place posed views keep it, from those views
+ * alone, and is not started again.  Where the first posed views that keep an id do so mostly through wrong labels (a marker far
+ * from the fixed ones, wrong ids in many views), it is placed wrongly, the first set refuses its truthful observations, and it ends
+ * FEW_VIEWS with them named as outliers: the marker is missing from the map, not misplaced in it.  A larger min_views_place, or
+ * fixed entries near every part of the walk, is the remedy.
+ *
+ * Rounds r = 0 .. FID_BUILD_ROBUST_SOLVES - 1.  Solve with fid_build_map_cam's Levenberg-Marquardt machine (its kernels, its stops,
+ * opts.max_iter trials per round, l from -3 in every round) over the active observations whose marker is in the solve and has a
+ * pose and whose view is reached and has a pose, from the start in round 0 and from the parameters of round r - 1 afterwards.  Then
+ * err is computed for EVERY kept observation whose view and marker have a pose; a pose that is not in the current solve keeps its
+ * last value.  The new active set: an observation with an err is active where err <= inlier_px (a NaN is not), an observation
+ * without one stays as it was.  The same set as the one just solved over: stop, stable = 1.  After the fourth solve: stop, stable =
+ * 0.  Otherwise FEW_VIEWS, reachability and the used views are recomputed over the new set (a reached view or marker that has no
+ * pose is NO_START) and the next round solves.  No reached view, no used view, or fewer residuals than free parameters after
+ * trimming: the call returns the previous round's result with stable = 0; in round 0 that is FID_E_INVALID_ARG, as the plain call.
+ *
+ * Result.  out, markers_out (with cov) and views describe the LAST solve over ITS active set and are to be judged at the minimum, as
+ * the plain call's.  obs_state of a kept observation: FID_BUILD_OBS_OUTLIER where it is not in that active set; otherwise
+ * FID_BUILD_OBS_INLIER where it entered that solve and FID_BUILD_OBS_LEFT_OUT where its marker or view did not (FEW_VIEWS, UNREACHED,
+ * NO_START, FEW).  obs_err_px: err under the returned parameters, -1 where the observation has none.  robust_out.n_obs: the kept
+ * observations that have an err (the candidates); n_inliers / n_outliers: the INLIER / OUTLIER observations; worst_inlier_px / best_outlier_px: the
+ * largest err over the first and the smallest over the second, -1 where there is none.  marker_outliers[i]: the OUTLIER observations
+ * of markers_out[i]; view_outliers[v]: those of view v.
+ *
+ * Reproducible: the same inputs give the same bytes; no random samples, no floating-point atomics, the median is exact.
+ *
+ * inlier_px has no default.  Over the truthful cases of tests/map_build_cases.py and ten rendered views the NumPy restatement's
+ * largest err at the plain minimum is FID_BUILD_ROBUST_MEASURED_PX; ten times that, rounded up to half a pixel, is the recommended
+ * value FID_BUILD_ROBUST_RECOMMENDED_PX (the rule that gave fid_map_pose_robust_cam its 4.0).
+ *
+ * Refusals: fid_build_map_cam's, and FID_E_INVALID_ARG for ropts or robust_out NULL, inlier_px not finite or <= 0, min_views_place <
+ * 1.  The four arrays may be NULL.  The context's buffer is the plain call's, larger; a context that never makes this call allocates
+ * and launches nothing of it. */
+#define FID_BUILD_ROBUST_SOLVES 4
+#define FID_BUILD_ROBUST_HYPOTHESES 64
+#define FID_BUILD_OBS_NOT_KEPT 0 /* beyond n_per_view, an id seen twice in the view, or over the per-view cap */
+#define FID_BUILD_OBS_INLIER 1
+#define FID_BUILD_OBS_OUTLIER 2
+#define FID_BUILD_OBS_LEFT_OUT 3
+#define FID_BUILD_ROBUST_MEASURED_PX 1.3215   /* 0.46 on the generated views (corner noise +-0.3 px), 1.32 on the rendered ones (detected corners) */
+#define FID_BUILD_ROBUST_RECOMMENDED_PX 13.5
+typedef struct fid_build_robust_opts {
+    double inlier_px;        /* finite and > 0; no default */
+    int32_t min_views_place; /* >= 1 */
+    int32_t reserved0;       /* ignored */
+} fid_build_robust_opts;
+typedef struct fid_build_robust_out {
+    int32_t rounds;     /* solves run, 1 .. FID_BUILD_ROBUST_SOLVES */
+    int32_t stable;     /* 1: the set the last solve's parameters admit is the set it was solved over */
+    int32_t n_obs;      /* kept observations whose view and marker have a pose */
+    int32_t n_inliers;
+    int32_t n_outliers;
+    int32_t reserved0;  /* 0 */
+    double worst_inlier_px;
+    double best_outlier_px;
+} fid_build_robust_out;
+/* obs_state (uint8_t) and obs_err_px (double): n_views * cap_per_view entries, parallel to markers; marker_outliers (int32_t):
+ * cap_markers entries, parallel to markers_out; view_outliers (int32_t): n_views entries.  Each may be NULL. */
+fid_status fid_build_map_robust_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views,
+                                    int32_t cap_per_view, const fid_map_entry *fixed, int32_t n_fixed, const fid_build_opts *opts,
+                                    const fid_build_robust_opts *ropts, fid_build_out *out, fid_build_robust_out *robust_out,
+                                    fid_build_marker *markers_out, int32_t cap_markers, int32_t *n_markers_out, fid_build_view *views,
+                                    uint8_t *obs_state, double *obs_err_px, int32_t *marker_outliers, int32_t *view_outliers);
 /* the file fiducial_slam reads as its map_file (map.cpp:541-565): for every FIXED and SOLVED marker of the n, in the order given, the
  * line `id x y z roll pitch yaw variance numObs links...` by "%d %lf %lf %lf %lf %lf %lf %lf %d" and " %d" per link.  x y z = entry.t;
  * roll pitch yaw = tf2's getRPY of entry.R (pitch = asin(-R[2][0]); roll = atan2(R[2][1], R[2][2]), yaw = atan2(R[1][0], R[0][0]); at
