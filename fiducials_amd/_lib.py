@@ -86,6 +86,12 @@ class FidCalibOpts(C.Structure):
                 ("reserved0", C.c_int32), ("eps", C.c_double)]
 
 
+class FidCharucoBoard(C.Structure):
+    """fid_charuco_board: squares a side, square and marker length, the id of the first marker."""
+    _fields_ = [("squares_x", C.c_int32), ("squares_y", C.c_int32), ("square_len", C.c_double), ("marker_len", C.c_double), ("first_id", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 class FidLimits(C.Structure):
     _fields_ = [("max_width", C.c_int32), ("max_height", C.c_int32), ("max_batch", C.c_int32),
                 ("max_starts_per_frame", C.c_int32), ("max_contours_per_frame", C.c_int32),
@@ -167,6 +173,12 @@ OBS_NOT_KEPT, OBS_INLIER, OBS_OUTLIER, OBS_LEFT_OUT = 0, 1, 2, 3
 BUILD_ROBUST_MEASURED_PX, BUILD_ROBUST_INLIER_PX = 1.3215, 13.5  # the header's measured err and RECOMMENDED inlier_px (the ABI has no default)
 BUILD_ROBUST_OUT_DTYPE = np.dtype([("rounds", "<i4"), ("stable", "<i4"), ("n_obs", "<i4"), ("n_inliers", "<i4"), ("n_outliers", "<i4"), ("reserved0", "<i4"),
                                    ("worst_inlier_px", "<f8"), ("best_outlier_px", "<f8")])  # fid_build_robust_out
+# ChArUco boards (fid_abi.h: "ChArUco boards"); a pose record's status: CHARUCO_POSE_*
+CHARUCO_MAX_SQUARES = 512  # FID_CHARUCO_MAX_SQUARES
+CHARUCO_POSE_OK, CHARUCO_POSE_FEW, CHARUCO_POSE_COLLINEAR, CHARUCO_POSE_VOID = 0, 1, 2, 3
+CHARUCO_CORNER_DTYPE = np.dtype([("id", "<i4"), ("win", "<i4"), ("x", "<f4"), ("y", "<f4"), ("x0", "<f4"), ("y0", "<f4")])  # fid_charuco_corner
+CHARUCO_POSE_DTYPE = np.dtype([("n_corners", "<i4"), ("status", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("R", "<f8", (3, 3)),
+                               ("cam_R", "<f8", (3, 3)), ("cam_t", "<f8", (3,)), ("image_error", "<f8")])  # fid_charuco_pose_out
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -184,6 +196,7 @@ SYMBOLS = [
     "fid_map_pose_robust_cam", "fid_map_pose_robust_last_cam",
     "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info", "fid_default_build_opts", "fid_build_map_cam", "fid_map_save_file",
     "fid_build_map_robust_cam",
+    "fid_set_charuco_board", "fid_charuco_last_cam", "fid_charuco_interpolate_cam", "fid_charuco_pose_last_cam", "fid_charuco_pose_cam",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -390,6 +403,13 @@ def load():
     if hasattr(L, "fid_build_map_robust_cam"):  # (the trimmed build; FID_LIB may name a build from before it)
         L.fid_build_map_robust_cam.argtypes = [vp, C.POINTER(FidCamera), vp, vp, i32, i32, vp, i32, C.POINTER(FidBuildOpts), C.POINTER(FidBuildRobustOpts), vp, vp,
                                                vp, i32, C.POINTER(i32), vp, vp, vp, vp, vp]
+    if hasattr(L, "fid_set_charuco_board"):  # (ChArUco boards; FID_LIB may name a build from before them)
+        cam = C.POINTER(FidCamera)
+        L.fid_set_charuco_board.argtypes = [vp, C.POINTER(FidCharucoBoard)]
+        L.fid_charuco_last_cam.argtypes = [vp, cam, i32, vp, i32, vp]
+        L.fid_charuco_interpolate_cam.argtypes = [vp, cam, vp, i32, vp, i32, i32, i32, i32, vp, i32, C.POINTER(i32)]
+        L.fid_charuco_pose_last_cam.argtypes = [vp, cam, i32, vp, i32]
+        L.fid_charuco_pose_cam.argtypes = [vp, cam, vp, vp, i32, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

@@ -254,6 +254,8 @@ struct fid_ctx {
     struct CalibBufs *calib = nullptr;
     // fid_build_map_cam (fid_map_build.hip): one buffer sized by the largest call; nothing until the first call
     struct BuildBufs *build = nullptr;
+    // the ChArUco board (fid_charuco.hip): its tables and result slots; nothing until the first fid_set_charuco_board
+    struct CharucoBufs *charuco = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -278,6 +280,8 @@ static void map_pose_robust_launch(fid_ctx *c, hipStream_t st, const fid_marker 
 static void calib_free(fid_ctx *c);
 // fid_build_map_cam's buffer (fid_map_build.hip, behind fid_calib.hip)
 static void build_free(fid_ctx *c);
+// the ChArUco board's buffers (fid_charuco.hip, behind fid_map_build.hip)
+static void charuco_free(fid_ctx *c);
 
 namespace {
 
@@ -1646,6 +1650,7 @@ void fid_destroy(fid_ctx *c)
         if (p) (void)hipFree(p);
     calib_free(c);
     build_free(c);
+    charuco_free(c);
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -2348,3 +2353,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_map_pose_robust.hip"
 #include "fid_calib.hip"
 #include "fid_map_build.hip"
+#include "fid_charuco.hip"

@@ -44,6 +44,8 @@ MAP_POSE_DTYPE = np.dtype([("n_markers", "<i4"), ("n_over", "<i4"), ("rvec", "<f
 POSE_COV_DTYPE = np.dtype(_lib.POSE_COV_FIELDS)  # fid_pose_cov
 MAP_POSE_COV_DTYPE = np.dtype([("pose", POSE_COV_DTYPE), ("cov_cam_pose", "<f8", (6, 6))])  # fid_map_pose_cov
 MAP_ROBUST_DTYPE = _lib.MAP_ROBUST_DTYPE  # fid_map_robust_out
+CHARUCO_CORNER_DTYPE = _lib.CHARUCO_CORNER_DTYPE  # fid_charuco_corner
+CHARUCO_POSE_DTYPE = _lib.CHARUCO_POSE_DTYPE  # fid_charuco_pose_out
 
 
 def map_robust_outlier_positions(rec) -> np.ndarray:
@@ -519,6 +521,82 @@ class ArucoDetector:
         rob = np.zeros(len(out), MAP_ROBUST_DTYPE)
         self._check(self._L.fid_map_pose_robust_last_cam(self._ctx, C.byref(cam.c), C.byref(opts), out.ctypes.data, rob.ctypes.data, len(out)))
         return out[:self._last_frames], rob[:self._last_frames]
+
+    # -- ChArUco boards ---------------------------------------------------------------------------
+    def set_charuco_board(self, board) -> None:
+        """The ChArUco board whose chessboard corners charuco_* interpolate (fid_set_charuco_board): a fiducials_amd.charuco.CharucoBoard;
+        None clears it.  Independent of set_map."""
+        if board is None:
+            self._check(self._L.fid_set_charuco_board(self._ctx, None))
+            self._charuco = None
+            return
+        b = board.c_struct()
+        self._check(self._L.fid_set_charuco_board(self._ctx, C.byref(b)))
+        self._charuco = board
+
+    def _charuco_cap(self, cap):
+        board = getattr(self, "_charuco", None)
+        return int(cap) if cap is not None else (board.n_corners if board is not None else 1)
+
+    def charuco_last(self, min_markers: int = 2, K=None, D=None, camera=None, cap: int | None = None) -> list:
+        """The chessboard corners of every frame of the last detect_* / collect call, interpolated from its markers and refined on its
+        gray frames without either leaving the device (fid_charuco_last_cam): a list of CHARUCO_CORNER_DTYPE arrays, one per frame, in
+        ascending corner id.  Without a camera the positions come from the per-marker homographies; with K, D or camera= from the
+        board pose and the camera's projection.  cap: the caller's room per frame (default: the board's corner count)."""
+        cam = _camera.resolve(K, D, camera)
+        cap = self._charuco_cap(cap)
+        F = max(self._last_frames, 1)
+        out = np.zeros(F * max(cap, 1), CHARUCO_CORNER_DTYPE)
+        n = np.zeros(F, np.int32)
+        self.last_charuco_counts = n
+        self._check(self._L.fid_charuco_last_cam(self._ctx, C.byref(cam.c) if cam is not None else None, int(min_markers), out.ctypes.data, cap,
+                                                 n.ctypes.data))
+        return [out[f * cap:f * cap + int(n[f])].copy() for f in range(self._last_frames)]
+
+    def charuco_interpolate(self, corners, ids, image, min_markers: int = 2, K=None, D=None, camera=None, cap: int | None = None) -> np.ndarray:
+        """charuco_last's kernels on markers (corners (n, 4, 2), ids (n,), in list order) and a mono8 image from host memory
+        (fid_charuco_interpolate_cam): one CHARUCO_CORNER_DTYPE array."""
+        cam = _camera.resolve(K, D, camera)
+        cap = self._charuco_cap(cap)
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        mk = np.zeros(len(ids), _MARKER_DT)
+        mk["id"] = ids
+        mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise FidError(_lib.FID_E_INVALID_ARG, "charuco_interpolate takes a mono8 image (H, W) uint8")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        out = np.zeros(max(cap, 1), CHARUCO_CORNER_DTYPE)
+        n = C.c_int32(0)
+        self.last_charuco_counts = n
+        self._check(self._L.fid_charuco_interpolate_cam(self._ctx, C.byref(cam.c) if cam is not None else None, mk.ctypes.data if len(mk) else None,
+                                                        len(mk), img.ctypes.data, img.shape[1], img.shape[0], img.strides[0], int(min_markers),
+                                                        out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def charuco_pose(self, xy, ids, K=None, D=None, camera=None) -> np.ndarray:
+        """estimatePoseCharucoBoard on corners handed in from the host (fid_charuco_pose_cam): xy (n, 2), ids (n,) chessboard corner
+        indices.  Returns one CHARUCO_POSE_DTYPE record; status CHARUCO_POSE_* says why there is no pose."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        pts = np.ascontiguousarray(xy, dtype=np.float32).reshape(len(ids), 2)
+        out = np.zeros(1, CHARUCO_POSE_DTYPE)
+        self._check(self._L.fid_charuco_pose_cam(self._ctx, C.byref(cam.c), pts.ctypes.data if len(ids) else None, ids.ctypes.data if len(ids) else None,
+                                                 len(ids), out.ctypes.data))
+        return out[0]
+
+    def charuco_pose_last(self, K=None, D=None, camera=None, min_markers: int = 2) -> np.ndarray:
+        """The board pose of every frame of the last detect_* / collect call from its refined chessboard corners
+        (fid_charuco_pose_last_cam: interpolation by the camera route, refinement, one solvePnP): CHARUCO_POSE_DTYPE records."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        out = np.zeros(max(self._last_frames, 1), CHARUCO_POSE_DTYPE)
+        self._check(self._L.fid_charuco_pose_last_cam(self._ctx, C.byref(cam.c), int(min_markers), out.ctypes.data, len(out)))
+        return out[:self._last_frames]
 
     # -- calibration ------------------------------------------------------------------------------
     def calibrate_map(self, views, image_size, model: int = _lib.CAM_PLUMB_BOB, free: int | None = None, start=None, fix_aspect: bool = False,

@@ -9,6 +9,7 @@ white), as a self-contained SVG (`gen_svg`) or as one page of a multi-page vecto
 
     python -m fiducials_amd.marker_gen 100 112 markers.pdf [dictionary=7] [--paper-size letter|a4]
     python -m fiducials_amd.marker_gen 100 112 outdir/ --svg
+    python -m fiducials_amd.marker_gen 0 0 board.pdf --charuco 5x4:40:24     (a ChArUco board, markers 0 .. 9)
 """
 from __future__ import annotations
 
@@ -173,6 +174,56 @@ def pdf_text(x: float, y: float, size: float, s: str, page_height: float) -> str
     return "BT /F1 %g Tf %.3f %.3f Td (%s) Tj ET" % (size, x * k - width / 2, (page_height - y) * k, s.replace("(", "\\(").replace(")", "\\)"))
 
 
+def charuco_sheet_layout(board, d: Dictionary, paper_size, allow_fillers: bool = False):
+    """A ChArUco board (fiducials_amd.charuco.CharucoBoard, lengths in metres) as one page, printed at its true size and centred:
+    (black rects, white rects, texts) in millimetres, origin top left.  The rectangles are board.layout()'s -- the board's own object
+    points -- so the sheet and the pose tables agree by construction."""
+    for i in board.ids:
+        _check_printable(d, int(i), allow_fillers)
+    pw, ph = paper_size
+    bw, bh = board.squares_x * board.square_len * 1000.0, board.squares_y * board.square_len * 1000.0
+    if bw > pw - 10 or bh > ph - 20:
+        raise ValueError(f"a board of {bw:.1f} x {bh:.1f} mm does not fit a page of {pw} x {ph} mm with its margins")
+    x0, y0 = (pw - bw) / 2, (ph - bh) / 2
+    black, white = board.layout(d)
+
+    def page(r):  # board metres, y up -> page mm, y down
+        x, y, w, h = r
+        return (x0 + x * 1000.0, y0 + bh - (y + h) * 1000.0, w * 1000.0, h * 1000.0)
+
+    texts = [(pw / 2, y0 + bh + 8, 8, "ChArUco %d x %d, square %.2f mm, marker %.2f mm, ids %d - %d D%d: check the square size after printing."
+              % (board.squares_x, board.squares_y, board.square_len * 1000.0, board.marker_len * 1000.0, board.ids[0], board.ids[-1], _dicno_of(d)))]
+    return [page(r) for r in black], [page(r) for r in white], texts
+
+
+def gen_charuco_svg(board, dicno: int = 7, paper_size=PAPER["letter"], allow_fillers: bool = False) -> str:
+    d = get_predefined_dictionary(dicno, allow_fillers=allow_fillers)
+    black, white, texts = charuco_sheet_layout(board, d, paper_size, allow_fillers)
+    pw, ph = paper_size
+    out = ['<svg width="%gmm" height="%gmm" viewBox="0 0 %g %g" version="1.1" xmlns="http://www.w3.org/2000/svg">' % (pw, ph, pw, ph)]
+    for x, y, w, h in black:
+        out.append('  <rect x="%.4f" y="%.4f" width="%.4f" height="%.4f" style="stroke:none; fill:black"/>' % (x, y, w, h))
+    for x, y, w, h in white:
+        out.append('  <rect class="cell" x="%.4f" y="%.4f" width="%.4f" height="%.4f" style="stroke:none; fill:white"/>' % (x, y, w, h))
+    for x, y, size, s in texts:
+        out.append('  <text x="%.4f" y="%.4f" text-anchor="middle" style="font-family:arial; font-size:%gpt;">%s</text>' % (x, y, size * 25.4 / 72 * 0.75, s))
+    out.append("</svg>")
+    return "\n".join(out) + "\n"
+
+
+def write_charuco_pdf(path: str, board, dicno: int = 7, paper_size=PAPER["letter"], allow_fillers: bool = False) -> None:
+    """The sheet as a one-page vector PDF."""
+    d = get_predefined_dictionary(dicno, allow_fillers=allow_fillers)
+    black, white, texts = charuco_sheet_layout(board, d, paper_size, allow_fillers)
+    k = 72 / 25.4
+    ph = paper_size[1]
+    c = ["0 g"] + ["%.3f %.3f %.3f %.3f re f" % (x * k, (ph - y - h) * k, w * k, h * k) for x, y, w, h in black]
+    c += ["1 g"] + ["%.3f %.3f %.3f %.3f re f" % (x * k, (ph - y - h) * k, w * k, h * k) for x, y, w, h in white]
+    c += ["0 g"] + [pdf_text(x, y, size, s, ph) for x, y, size, s in texts]
+    with open(path, "wb") as fh:
+        fh.write(pdf_file(["\n".join(c).encode("ascii")], paper_size))
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description="Generate Aruco Markers.")
     ap.add_argument("startId", type=int, help="start of marker range to generate")
@@ -184,7 +235,23 @@ def main(argv=None) -> int:
     ap.add_argument("--allow-fillers", action="store_true",
                     help="also print ids whose codeword in the shipped table is a locally generated filler (NOT OpenCV's: such a print "
                          "is only read back by this repository's own tables)")
+    ap.add_argument("--charuco", metavar="SXxSY:SQUARE_MM:MARKER_MM",
+                    help="one ChArUco board instead of single markers, e.g. 5x4:40:24; its markers are startId, startId + 1, ... (endId is not read)")
     a = ap.parse_args(argv)
+    if a.charuco:
+        from .charuco import CharucoBoard
+
+        size, square, marker = a.charuco.split(":")
+        sx, sy = size.lower().split("x")
+        board = CharucoBoard(int(sx), int(sy), float(square) / 1000.0, float(marker) / 1000.0, a.startId)
+        if a.svg:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "charuco%d.svg" % a.startId), "w") as fh:
+                fh.write(gen_charuco_svg(board, a.dictionary, PAPER[a.paper_size], a.allow_fillers))
+        else:
+            write_charuco_pdf(a.out, board, a.dictionary, PAPER[a.paper_size], a.allow_fillers)
+        print("After printing, please make sure that a square is EXACTLY %.1f mm wide." % (board.square_len * 1000.0))
+        return 0
     ids = list(range(a.startId, a.endId + 1))
     if a.svg:
         os.makedirs(a.out, exist_ok=True)

@@ -428,3 +428,88 @@ def make_aruco_board_frame(d: Dictionary, ids, placements, K, R, t, seed: int, w
     if noise_sigma > 0:
         img = img + rng.normal(0.0, noise_sigma, size=img.shape).astype(np.float32)
     return ArucoBoardFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), ids, R, _rot_to_rvec(R), t, cm, ci)
+
+
+@dataclass
+class CharucoFrame:
+    image: np.ndarray          # (H, W) uint8
+    R: np.ndarray              # (3, 3) board -> camera
+    rvec: np.ndarray           # (3,)
+    tvec: np.ndarray           # (3,)
+    corners_image: np.ndarray  # (n_corners, 2) the chessboard corners' true projections
+    markers_image: np.ndarray  # (n_markers, 4, 2) the marker corners' true projections
+
+
+def _distort_plumb_bob(x, y, D):
+    k1, k2, p1, p2, k3 = D
+    r2 = x * x + y * y
+    cd = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    return x * cd + 2 * p1 * x * y + p2 * (r2 + 2 * x * x), y * cd + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+
+
+def make_charuco_frame(d: Dictionary, board, K, R, t, seed: int, width: int = 640, height: int = 480, noise_sigma: float = 2.0,
+                       border_bits: int = 1, D=None, hidden=(), margin: float = 0.5) -> CharucoFrame:
+    """A ChArUco board (fiducials_amd.charuco.CharucoBoard) seen through ONE camera pose.  R, t: the board frame in the camera frame
+    (solvePnP's convention); K with D = None: pinhole, or D = (k1, k2, p1, p2, k3).  Every sample is classified from the board's own
+    object points -- the square it falls in, the marker's rectangle, the marker's cell -- so picture, pose tables and printed sheet
+    agree by construction.  Sampling, grey levels, background, blur and noise are make_aruco_board_frame's: 3 x 3 samples a pixel, 25 /
+    230 on a 128 background with a low-frequency gradient, blur sigma 0.8, seeded noise.  A white margin of `margin` squares surrounds
+    the board; the markers listed in `hidden` (marker indices) are left out of the picture (their squares stay white)."""
+    rng = np.random.default_rng(seed)
+    K = np.asarray(K, float).reshape(3, 3)
+    R = np.asarray(R, float).reshape(3, 3)
+    t = np.asarray(t, float).reshape(3)
+    Dv = np.zeros(5) if D is None else np.concatenate([np.asarray(D, float).reshape(-1)[:5], np.zeros(5)])[:5]
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float32)
+    gdir, gamp, phase = rng.uniform(0, 2 * np.pi), rng.uniform(10, 30), rng.uniform(0, 2 * np.pi)
+    bg = (128.0 + gamp * np.sin((np.cos(gdir) * xx / width + np.sin(gdir) * yy / height) * np.pi + phase)).astype(np.float32)
+    ss = 3
+    sub = (np.arange(ss) + 0.5) / ss - 0.5
+    PX, PY = np.meshgrid((np.arange(width)[:, None] + sub[None, :]).reshape(-1), (np.arange(height)[:, None] + sub[None, :]).reshape(-1))
+    # pixel -> normalised image point (the distortion undone by fixed-point iteration) -> board plane
+    xd, yd = (PX - K[0, 2]) / K[0, 0], (PY - K[1, 2]) / K[1, 1]
+    xn, yn = xd.copy(), yd.copy()
+    if np.any(Dv != 0):
+        for _ in range(12):
+            ex, ey = _distort_plumb_bob(xn, yn, Dv)
+            xn, yn = xn - (ex - xd), yn - (ey - yd)
+    Hi = np.linalg.inv(np.stack([R[:, 0], R[:, 1], t], axis=1))  # normalised image -> board plane (X, Y, 1)
+    den = Hi[2, 0] * xn + Hi[2, 1] * yn + Hi[2, 2]
+    U = (Hi[0, 0] * xn + Hi[0, 1] * yn + Hi[0, 2]) / den
+    V = (Hi[1, 0] * xn + Hi[1, 1] * yn + Hi[1, 2]) / den
+    s = board.square_len
+    mg = margin * s
+    sheet = (U >= -mg) & (U < board.squares_x * s + mg) & (V >= -mg) & (V < board.squares_y * s + mg) & (den * np.sign(Hi[2, 2]) > 0)
+    qx, qy = np.floor(U / s).astype(np.int64), np.floor(V / s).astype(np.int64)
+    on_board = sheet & (qx >= 0) & (qx < board.squares_x) & (qy >= 0) & (qy < board.squares_y)
+    qxc, qyc = np.clip(qx, 0, board.squares_x - 1), np.clip(qy, 0, board.squares_y - 1)
+    white = ~on_board | ((qxc + qyc) % 2 == 1)
+    ncell = d.marker_size + 2 * border_bits
+    cells = np.stack([draw_marker(d, int(i), ncell, border_bits) > 0 for i in board.ids])
+    mk = np.where(on_board, board.marker_at[qyc, qxc], -1)
+    shown = np.ones(board.n_markers, bool)
+    shown[list(hidden)] = False
+    has = (mk >= 0) & shown[np.clip(mk, 0, None)]
+    mkc = np.clip(mk, 0, None)
+    c0, c2 = board.marker_object_points[:, 0], board.marker_object_points[:, 2]
+    mu = (U - c0[mkc, 0]) / (c2[mkc, 0] - c0[mkc, 0]) * ncell
+    mv = (c0[mkc, 1] - V) / (c0[mkc, 1] - c2[mkc, 1]) * ncell
+    in_marker = has & (mu >= 0) & (mu < ncell) & (mv >= 0) & (mv < ncell)
+    cell_white = cells[mkc, np.clip(np.floor(mv).astype(np.int64), 0, ncell - 1), np.clip(np.floor(mu).astype(np.int64), 0, ncell - 1)]
+    white = np.where(in_marker, cell_white, white)
+    val = np.where(white, 230.0, 25.0).astype(np.float32)
+    cnt = sheet.reshape(height, ss, width, ss).sum(axis=(1, 3)).astype(np.float32)
+    col = (val * sheet).reshape(height, ss, width, ss).sum(axis=(1, 3)).astype(np.float32)
+    cov = cnt / (ss * ss)
+    img = bg * (1 - cov) + np.where(cnt > 0, col / np.maximum(cnt, 1), 0) * cov
+    img = _blur(img.astype(np.float32), 0.8)
+    if noise_sigma > 0:
+        img = img + rng.normal(0.0, noise_sigma, size=img.shape).astype(np.float32)
+
+    def proj(P):
+        Pc = P @ R.T + t
+        x, y = _distort_plumb_bob(Pc[:, 0] / Pc[:, 2], Pc[:, 1] / Pc[:, 2], Dv)
+        return np.stack([K[0, 0] * x + K[0, 2], K[1, 1] * y + K[1, 2]], axis=1)
+
+    return CharucoFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), R, _rot_to_rvec(R), t, proj(board.corner_object_points),
+                        proj(board.marker_object_points.reshape(-1, 3)).reshape(-1, 4, 2))

@@ -802,6 +802,92 @@ fid_status fid_build_map_robust_cam(fid_ctx *ctx, const fid_camera *cam, const f
  * cannot be written; fid_map_last_error() says what. */
 fid_status fid_map_save_file(const char *path, const fid_build_marker *markers, int32_t n);
 
+/* ---- ChArUco boards (additions to ABI 7: entry points and structs only).  A chessboard with an aruco marker in every white square:
+ * the markers say which chessboard corner is which, and the chessboard corners are saddle points that cornerSubPix locates far better
+ * than a marker's outer corner.  cv::aruco::interpolateCornersCharuco and estimatePoseCharucoBoard (OpenCV 4.2 charuco.cpp) on what a
+ * detect call leaves on the device: the gray frames, the marker lists, the counts.  A context without a board behaves exactly as
+ * before: no allocation, no launch.
+ *
+ * The board.  Board frame: x right, y up, z out of the face.  Square (x, y) covers [x s, (x + 1) s] x [y s, (y + 1) s], s = square_len.
+ * Squares with x + y even are black; squares with x + y odd are white and carry a marker.  The markers are numbered k = 0, 1, ... over
+ * the white squares, y outermost and x innermost; marker k has the id first_id + k.  With m = marker_len and d = (s - m) / 2 the
+ * corners of the marker in square (x, y) are, in double and then each coordinate rounded through float (Point3f):
+ *   corner 0 = (x s + d, y s + d + m, 0), corner 1 = corner 0 + (m, 0, 0), corner 2 = corner 0 + (m, -m, 0), corner 3 = corner 0 + (0, -m, 0)
+ * Chessboard corner i = cy (squares_x - 1) + cx, cx in 0 .. squares_x - 2, cy in 0 .. squares_y - 2, sits at ((cx + 1) s, (cy + 1) s, 0),
+ * rounded through float.  Its two NEAREST MARKERS are those of the two white squares that meet at it, in ascending marker index:
+ * squares (cx + 1, cy) and (cx, cy + 1) when cx + cy is even, else (cx, cy) and (cx + 1, cy + 1); of each, the corner nearest the
+ * chessboard corner is the one used below.
+ * Refused, the board unchanged (the last-error text names the bound): FID_E_INVALID_ARG for a side below 2 squares, marker_len not inside
+ * (0, square_len) or not finite, an id outside the context's dictionary (first_id < 0 or first_id + markers > its size), a batch in
+ * flight; FID_E_UNSUPPORTED for squares_x * squares_y > FID_CHARUCO_MAX_SQUARES (at most FID_MAP_MAX_USED markers: what one board
+ * pose can use).  board == NULL clears it.  The board has device tables of its own and is independent of fid_set_map. */
+#define FID_CHARUCO_MAX_SQUARES 512
+typedef struct fid_charuco_board {
+    int32_t squares_x, squares_y;
+    double square_len, marker_len;
+    int32_t first_id;
+    int32_t reserved0;
+} fid_charuco_board;
+fid_status fid_set_charuco_board(fid_ctx *ctx, const fid_charuco_board *board);
+/* Interpolation and refinement, per frame:
+ *  1. Gather: the markers in list order that the board names; an id that occurs more than once in the frame is left out altogether
+ *     (k_map_pose's rule.  DEPARTURE: OpenCV takes the first occurrence).
+ *  2. Positions.  cam == NULL: per used marker the homography from its four board-plane corners (x, y) to its image corners -- what
+ *     findHomography gives for exactly four points, here by the closed form of the pose kernels' start (DEPARTURE: OpenCV runs its DLT
+ *     on the four points; the two agree far below a float ulp of a pixel coordinate); a marker whose four image corners admit no
+ *     homography counts as not detected.  Each chessboard corner is mapped through the homographies of its detected nearest markers,
+ *     each result rounded to float; the position is (p0 + p1) / 2 in float when both are detected, else the one result.
+ *     cam != NULL: the board pose from the used markers exactly as fid_map_pose_cam gives it with the board's markers as the map
+ *     (k_map_pose on the board's tables); the position is every chessboard corner projected with cam (any model) and rounded to float.
+ *     No pose, or the void fisheye record: 0 corners for the frame.
+ *  3. Window: minDist = the smallest, over the detected nearest markers, of the distance between the position and that marker's nearest
+ *     image corner (the difference in float, the norm in double); win = clamp((int)(minDist - 2), 1, 10).
+ *  4. Selection: a corner is kept when at least min_markers (1 or 2; OpenCV: 2) of its nearest markers are detected and
+ *     2 <= x < W - 2 and 2 <= y < H - 2.
+ *  5. Refinement: cornerSubPix on the gray frame from the position, window win, 30 iterations, eps 0.1 (OpenCV's DetectorParameters
+ *     defaults -- not the context's fid_params): the sequential cornerSubPix bit for bit.
+ * One fid_charuco_corner per kept corner in ascending id; x0, y0 is the position before refinement. */
+typedef struct fid_charuco_corner {
+    int32_t id;  /* chessboard corner index */
+    int32_t win; /* the cornerSubPix half-window used */
+    float x, y;  /* refined */
+    float x0, y0;
+} fid_charuco_corner;
+/* every frame of the last fid_detect* / fid_collect (for device frames handed to fid_detect_device as mono8 the caller's memory must
+ * still hold them).  Frame f's corners start at out[f * cap_per_frame], n_per_frame[f] is its count; a frame with more corners than
+ * cap_per_frame: FID_E_CAPACITY, the count still reported.  FID_E_INVALID_ARG: no board, a batch in flight, min_markers outside 1..2,
+ * a NULL out or n_per_frame, no last call. */
+fid_status fid_charuco_last_cam(fid_ctx *ctx, const fid_camera *cam, int32_t min_markers, fid_charuco_corner *out, int32_t cap_per_frame,
+                                int32_t *n_per_frame);
+/* the same kernels on n markers and a mono8 image from host memory (stride_bytes >= width; within the context's frame limits); the
+ * last detect call's results stay as they are */
+fid_status fid_charuco_interpolate_cam(fid_ctx *ctx, const fid_camera *cam, const fid_marker *markers, int32_t n, const uint8_t *img,
+                                       int32_t width, int32_t height, int32_t stride_bytes, int32_t min_markers, fid_charuco_corner *out,
+                                       int32_t cap, int32_t *n_out);
+/* estimatePoseCharucoBoard: ONE cv::solvePnP (ITERATIVE) over the refined corners -- fid_map_pose's planarity test, homography start
+ * (the points are coplanar, so it is always the one taken) and CvLevMarq, on single points.  No pose -- status says why, everything
+ * else but n_corners zero -- with fewer than 4 corners, with all corners on one line of the grid (tested exactly on the integer cx, cy),
+ * or, in the equidistant model, with a corner the model cannot undistort. */
+#define FID_CHARUCO_POSE_OK 0
+#define FID_CHARUCO_POSE_FEW 1
+#define FID_CHARUCO_POSE_COLLINEAR 2
+#define FID_CHARUCO_POSE_VOID 3
+typedef struct fid_charuco_pose_out {
+    int32_t n_corners;
+    int32_t status; /* FID_CHARUCO_POSE_* */
+    double rvec[3], tvec[3];
+    double R[9];        /* cv::Rodrigues(rvec), row-major: the board frame in the camera frame */
+    double cam_R[9];    /* the camera in the board frame: R^T ... */
+    double cam_t[3];    /* ... and -R^T tvec */
+    double image_error; /* mean squared reprojection error over the corners, projections rounded to float, px^2 */
+} fid_charuco_pose_out;
+/* interpolation by the camera route and refinement as fid_charuco_last_cam does them, then the pose: one record per frame of the last
+ * call (cap_frames >= the frame count, else FID_E_CAPACITY).  cam is required. */
+fid_status fid_charuco_pose_last_cam(fid_ctx *ctx, const fid_camera *cam, int32_t min_markers, fid_charuco_pose_out *out, int32_t cap_frames);
+/* the pose kernel on n corners from host memory: xy = n x 2 floats, ids = their chessboard corner indices (each inside the board, else
+ * FID_E_INVALID_ARG; n at most FID_CHARUCO_MAX_SQUARES) */
+fid_status fid_charuco_pose_cam(fid_ctx *ctx, const fid_camera *cam, const float *xy, const int32_t *ids, int32_t n, fid_charuco_pose_out *out);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
