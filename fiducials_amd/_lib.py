@@ -197,6 +197,7 @@ SYMBOLS = [
     "fid_default_calib_opts", "fid_calibrate_map", "fid_camera_to_info", "fid_default_build_opts", "fid_build_map_cam", "fid_map_save_file",
     "fid_build_map_robust_cam",
     "fid_set_charuco_board", "fid_charuco_last_cam", "fid_charuco_interpolate_cam", "fid_charuco_pose_last_cam", "fid_charuco_pose_cam",
+    "fid_calibrate_charuco",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -410,6 +411,8 @@ def load():
         L.fid_charuco_interpolate_cam.argtypes = [vp, cam, vp, i32, vp, i32, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.fid_charuco_pose_last_cam.argtypes = [vp, cam, i32, vp, i32]
         L.fid_charuco_pose_cam.argtypes = [vp, cam, vp, vp, i32, vp]
+    if hasattr(L, "fid_calibrate_charuco"):  # (calibration from ChArUco corners; FID_LIB may name a build from before it)
+        L.fid_calibrate_charuco.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(FidCalibOpts), C.POINTER(FidCamera), vp, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

@@ -256,6 +256,8 @@ struct fid_ctx {
     struct BuildBufs *build = nullptr;
     // the ChArUco board (fid_charuco.hip): its tables and result slots; nothing until the first fid_set_charuco_board
     struct CharucoBufs *charuco = nullptr;
+    // fid_calibrate_charuco (fid_calib_points.hip): the point tables beside `calib`; nothing until the first call
+    struct CalibPtsBufs *calib_pts = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -282,6 +284,8 @@ static void calib_free(fid_ctx *c);
 static void build_free(fid_ctx *c);
 // the ChArUco board's buffers (fid_charuco.hip, behind fid_map_build.hip)
 static void charuco_free(fid_ctx *c);
+// fid_calibrate_charuco's buffers (fid_calib_points.hip, behind fid_charuco.hip)
+static void calib_pts_free(fid_ctx *c);
 
 namespace {
 
@@ -1651,6 +1655,7 @@ void fid_destroy(fid_ctx *c)
     calib_free(c);
     build_free(c);
     charuco_free(c);
+    calib_pts_free(c);
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -2354,3 +2359,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_calib.hip"
 #include "fid_map_build.hip"
 #include "fid_charuco.hip"
+#include "fid_calib_points.hip"

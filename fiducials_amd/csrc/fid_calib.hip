@@ -29,6 +29,9 @@
 //       k_calib_init     one wave, once: which views are used, their start poses from k_map_pose's records, the counts.
 // No kernel keeps an array that is indexed at run time in registers: rows, triangles and factors live in LDS.  No scratch, no spills
 // (tests/test_calib_kernel_allocations.py).
+// K22 and K24 are thin: their bodies are the device functions cal_view_blocks and cal_view_eval over a row source (CalMarkers here),
+// and k_calib_init's is cal_init_views over the start-pose record.  fid_calib_points.hip instantiates the same bodies over a per-view
+// point table for fid_calibrate_charuco, and both entry points share the host steps at the end of this file.
 
 #define CAL_COLS 23   // a Jacobian row in LDS: 16 intrinsics slots, 6 pose parameters, the residual
 #define CAL_TRI 276   // the upper triangle of 23 x 23
@@ -42,6 +45,7 @@ struct CalCfg {
     int col[16];       // the slot of free intrinsic j, ascending
     int fix_aspect;    // fx = aspect * fy, fy's slot is free
     int start_auto, min_markers, max_iter, n_views, per_view;
+    int per_item;      // image points an item of a view's list brings: 4 (a marker), 1 (a point of fid_calib_points.hip)
     double aspect, eps;
 };
 struct CalState {
@@ -52,6 +56,34 @@ struct CalState {
 };
 
 #include "fid_cal_model.h"
+
+// cvInitIntrinsicParams2D's two rows for a view from its homography h (changed in place): c6 = {a, b, c} of a X + b Y = c, twice.
+// -> whether all six are finite
+__device__ __forceinline__ bool cal_focal_rows(double h[9], double cx0, double cy0, double c6[6])
+{
+    for (int j = 0; j < 3; j++) {
+        h[j] -= h[6 + j] * cx0;
+        h[3 + j] -= h[6 + j] * cy0;
+    }
+    double h1[3], h2[3], d1[3], d2[3], n4[4] = {0, 0, 0, 0};
+    for (int j = 0; j < 3; j++) {
+        const double t0 = h[3 * j], t1 = h[3 * j + 1];
+        h1[j] = t0;
+        h2[j] = t1;
+        d1[j] = (t0 + t1) * 0.5;
+        d2[j] = (t0 - t1) * 0.5;
+        n4[0] += t0 * t0; n4[1] += t1 * t1; n4[2] += d1[j] * d1[j]; n4[3] += d2[j] * d2[j];
+    }
+    for (int j = 0; j < 4; j++) n4[j] = 1. / sqrt(n4[j]);
+    for (int j = 0; j < 3; j++) {
+        h1[j] *= n4[0]; h2[j] *= n4[1]; d1[j] *= n4[2]; d2[j] *= n4[3];
+    }
+    c6[0] = h1[0] * h2[0]; c6[1] = h1[1] * h2[1]; c6[2] = -h1[2] * h2[2];
+    c6[3] = d1[0] * d2[0]; c6[4] = d1[1] * d2[1]; c6[5] = -d1[2] * d2[2];
+    bool fin = true;
+    for (int j = 0; j < 6; j++) fin = fin && c6[j] - c6[j] == 0.;
+    return fin;
+}
 
 // ------------------------------------------------------------------------------------------------ K21: the views' used markers
 // vinfo[4 v + ..]: 0 n_used, 1 n_over, 2 the view's status (k_calib_init), 3 bit 0: coplanar, bit 1: the homography exists.
@@ -136,31 +168,7 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_start(const fid_marker *__restr
                 s.Mxy[p][1] = (float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
             }
             SR_LDS_SYNC();
-            if (mp_homography_dlt(&s, npts, lane, h)) {
-                // cvInitIntrinsicParams2D's two rows for this view
-                for (int j = 0; j < 3; j++) {
-                    h[j] -= h[6 + j] * cx0;
-                    h[3 + j] -= h[6 + j] * cy0;
-                }
-                double h1[3], h2[3], d1[3], d2[3], n4[4] = {0, 0, 0, 0};
-                for (int j = 0; j < 3; j++) {
-                    const double t0 = h[3 * j], t1 = h[3 * j + 1];
-                    h1[j] = t0;
-                    h2[j] = t1;
-                    d1[j] = (t0 + t1) * 0.5;
-                    d2[j] = (t0 - t1) * 0.5;
-                    n4[0] += t0 * t0; n4[1] += t1 * t1; n4[2] += d1[j] * d1[j]; n4[3] += d2[j] * d2[j];
-                }
-                for (int j = 0; j < 4; j++) n4[j] = 1. / sqrt(n4[j]);
-                for (int j = 0; j < 3; j++) {
-                    h1[j] *= n4[0]; h2[j] *= n4[1]; d1[j] *= n4[2]; d2[j] *= n4[3];
-                }
-                c6[0] = h1[0] * h2[0]; c6[1] = h1[1] * h2[1]; c6[2] = -h1[2] * h2[2];
-                c6[3] = d1[0] * d2[0]; c6[4] = d1[1] * d2[1]; c6[5] = -d1[2] * d2[2];
-                bool fin = true;
-                for (int j = 0; j < 6; j++) fin = fin && c6[j] - c6[j] == 0.;
-                if (fin) flags |= 2;
-            }
+            if (mp_homography_dlt(&s, npts, lane, h) && cal_focal_rows(h, cx0, cy0, c6)) flags |= 2;
         }
     }
     if (lane == 0) {
@@ -172,9 +180,11 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_start(const fid_marker *__restr
     }
 }
 
-// which views are used, their start poses, the counts (one wave)
-__global__ __launch_bounds__(64) void k_calib_init(const CalCfg *__restrict__ cfg, CalState *__restrict__ st, int *__restrict__ vinfo,
-                                                    const fid_map_pose_out *__restrict__ vpose, double *__restrict__ pose)
+// which views are used, their start poses, the counts (one wave).  REC: fid_map_pose_out or fid_charuco_pose_out, the record of the
+// view's start pose; posed(record) says whether it holds one.
+template <class REC, class POSED>
+__device__ __forceinline__ void cal_init_views(const CalCfg *__restrict__ cfg, CalState *__restrict__ st, int *__restrict__ vinfo,
+                                               const REC *__restrict__ vpose, double *__restrict__ pose, POSED posed)
 {
     const int lane = threadIdx.x;
     int nv = 0, np = 0;
@@ -184,8 +194,8 @@ __global__ __launch_bounds__(64) void k_calib_init(const CalCfg *__restrict__ cf
         if (n_used < cfg->min_markers || n_used < 1) {
             status = FID_CALIB_VIEW_FEW;
         } else {
-            const fid_map_pose_out *o = vpose + v;
-            bool ok = o->n_markers > 0 && o->image_error >= 0.;
+            const REC *o = vpose + v;
+            bool ok = posed(o);
             for (int i = 0; i < 3; i++) ok = ok && o->rvec[i] - o->rvec[i] == 0. && o->tvec[i] - o->tvec[i] == 0.;
             if (cfg->start_auto && !(vinfo[4 * v + 3] & 2)) ok = false;
             if (!ok) status = FID_CALIB_VIEW_NO_START;
@@ -197,7 +207,7 @@ __global__ __launch_bounds__(64) void k_calib_init(const CalCfg *__restrict__ cf
         vinfo[4 * v + 2] = status;
         if (status == FID_CALIB_VIEW_USED) {
             nv++;
-            np += 4 * n_used;
+            np += cfg->per_item * n_used;
         }
     }
     for (int m = 1; m < 64; m <<= 1) {
@@ -210,16 +220,51 @@ __global__ __launch_bounds__(64) void k_calib_init(const CalCfg *__restrict__ cf
     }
 }
 
+__global__ __launch_bounds__(64) void k_calib_init(const CalCfg *__restrict__ cfg, CalState *__restrict__ st, int *__restrict__ vinfo,
+                                                    const fid_map_pose_out *__restrict__ vpose, double *__restrict__ pose)
+{
+    cal_init_views(cfg, st, vinfo, vpose, pose, [](const fid_map_pose_out *o) { return o->n_markers > 0 && o->image_error >= 0.; });
+}
+
+// ------------------------------------------------------------------------------------------------ where a view's residuals come from
+// The bodies of the per-view kernels K22 and K24 are written over a source SRC: bind(v, cfg) turns to view v, residual r of
+// the view (r < PER_ITEM * 2 * n_used) has the object point object(r, M) and the image coordinate image(r).
+// CalMarkers: the used markers' list positions and map entries (k_calib_start) -- residual r is coordinate r & 1 of corner (r >> 1) & 3
+// of used marker r >> 3.  The point route's source is CalPoints (fid_calib_points.hip).
+struct CalMarkers {
+    static constexpr int PER_ITEM = 4;
+    const fid_marker *__restrict__ markers;
+    const int2 *__restrict__ sel;
+    const double *__restrict__ map_obj;
+    const fid_marker *mlist;
+    const int2 *vs;
+    __device__ __forceinline__ void bind(int v, const CalCfg *__restrict__ cfg)
+    {
+        mlist = markers + (long long)v * cfg->per_view;
+        vs = sel + (size_t)v * MP_MAX_USED;
+    }
+    __device__ __forceinline__ void object(int r, double M[3]) const
+    {
+        const int p = r >> 1, k = p >> 2, q = p & 3;
+        const double *src = map_obj + (size_t)vs[k].y * 12 + q * 3;
+        M[0] = src[0];
+        M[1] = src[1];
+        M[2] = src[2];
+    }
+    __device__ __forceinline__ double image(int r) const
+    {
+        const int p = r >> 1, su = r & 1, k = p >> 2, q = p & 3;
+        return (double)mlist[vs[k].x].corners[2 * q + su];
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ K22: a view's blocks
 // blk[CAL_TRI v + ..]: the packed upper triangle of [J e]^T [J e] over the view's residuals, J's columns the free intrinsics (cfg->col's
 // order) and then the view's pose, N = nI + 7 columns with the residual.  sch[CAL_SCH v + ..]: W B^T (16 j + k) and W g_pose (256 + j).
-// (launched with 64 threads; the never-launched upper bound makes the compiler aim for the occupancy four-wave workgroups would have
-// under this LDS, i.e. schedule for few registers instead of settling at the 170 the one-wave workgroup's LDS would allow)
-template <int MODEL>
-__global__ WALKER_WG_ATTR(64, 1024) void k_calib_blocks(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, const fid_marker *__restrict__ markers,
-                                                      const int2 *__restrict__ sel, const int *__restrict__ vinfo, const double *__restrict__ map_obj,
-                                                      const double *__restrict__ pose, double *__restrict__ blk, double *__restrict__ sch,
-                                                      double *__restrict__ cost, int final)
+template <int MODEL, class SRC>
+__device__ __forceinline__ void cal_view_blocks(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, SRC src, const int *__restrict__ vinfo,
+                                                const double *__restrict__ pose, double *__restrict__ blk, double *__restrict__ sch,
+                                                double *__restrict__ cost, int final)
 {
     __shared__ double rows[64][CAL_COLS];
     __shared__ double tri[CAL_TRI];
@@ -249,25 +294,22 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_blocks(const CalCfg *__restrict
         for (int i = 0; i < 12; i++) kd[i] = st->k[4 + i];
 #pragma unroll
         for (int i = 0; i < 3; i++) tv[i] = pose[6 * v + 3 + i];
-        const fid_marker *mlist = markers + (long long)v * cfg->per_view;
-        const int2 *vs = sel + (size_t)v * MP_MAX_USED;
-        const int nres = 8 * vinfo[4 * v];
+        src.bind(v, cfg);
+        const int nres = 2 * SRC::PER_ITEM * vinfo[4 * v];
         const bool fixa = cfg->fix_aspect != 0;
         const double aspect = cfg->aspect;
         double acc[5] = {0., 0., 0., 0., 0.}, e2 = 0.;
         for (int r0 = 0; r0 < nres; r0 += 64) {
             const int r = r0 + lane;
             if (r < nres) {
-                const int p = r >> 1, su = r & 1, k = p >> 2, q = p & 3;
-                const int2 se = vs[k];
-                const double *src = map_obj + (size_t)se.y * 12 + q * 3;
-                const double M[3] = {src[0], src[1], src[2]};
+                double M[3];
+                src.object(r, M);
                 double *row = rows[lane];  // (cal_row stores the row's entries as it has them: no lane holds the 22 at once)
                 // (the 36 doubles of the rotation are read where they are used: an offset the compiler cannot see through keeps it from
                 // hoisting the loads out of the loop into 72 registers of every lane)
                 int roff = 0;
                 asm volatile("" : "+v"(roff));
-                const double err = cal_row<MODEL>(M, rot + roff, rot + roff + 9, tv, K, kd, su, row + 16, row) - (double)mlist[se.x].corners[2 * q + su];
+                const double err = cal_row<MODEL>(M, rot + roff, rot + roff + 9, tv, K, kd, r & 1, row + 16, row) - src.image(r);
                 row[22] = err;
                 e2 += err * err;
                 if (fixa) row[1] += aspect * row[0];
@@ -322,6 +364,17 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_blocks(const CalCfg *__restrict
             sch[(size_t)v * CAL_SCH + 16 * lane + k] = sjk;
         }
     }
+}
+
+// (launched with 64 threads; the never-launched upper bound makes the compiler aim for the occupancy four-wave workgroups would have
+// under this LDS, i.e. schedule for few registers instead of settling at the 170 the one-wave workgroup's LDS would allow)
+template <int MODEL>
+__global__ WALKER_WG_ATTR(64, 1024) void k_calib_blocks(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, const fid_marker *__restrict__ markers,
+                                                      const int2 *__restrict__ sel, const int *__restrict__ vinfo, const double *__restrict__ map_obj,
+                                                      const double *__restrict__ pose, double *__restrict__ blk, double *__restrict__ sch,
+                                                      double *__restrict__ cost, int final)
+{
+    cal_view_blocks<MODEL>(cfg, st, CalMarkers{markers, sel, map_obj, nullptr, nullptr}, vinfo, pose, blk, sch, cost, final);
 }
 
 // ------------------------------------------------------------------------------------------------ K23: the reduced system
@@ -479,18 +532,17 @@ __global__ __launch_bounds__(320) void k_calib_solve(const CalCfg *__restrict__ 
             o.rvec[i] = used ? pose[6 * v + i] : 0.;
             o.tvec[i] = used ? pose[6 * v + 3 + i] : 0.;
         }
-        o.rms = used ? sqrt(cost[v] / (double)(4 * o.n_used)) : 0.;
+        o.rms = used ? sqrt(cost[v] / (double)(cfg->per_item * o.n_used)) : 0.;
         vout[v] = o;
     }
 }
 
 // ------------------------------------------------------------------------------------------------ K24: a view's candidate
 // dnpn[2 v + ..]: |step|^2 and |pose|^2 of the view's six
-template <int MODEL>
-__global__ __launch_bounds__(64) void k_calib_eval(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, const fid_marker *__restrict__ markers,
-                                                    const int2 *__restrict__ sel, const int *__restrict__ vinfo, const double *__restrict__ map_obj,
-                                                    const double *__restrict__ pose, const double *__restrict__ blk, double *__restrict__ cand_pose,
-                                                    double *__restrict__ cand_cost, double *__restrict__ dnpn)
+template <int MODEL, class SRC>
+__device__ __forceinline__ void cal_view_eval(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, SRC src, const int *__restrict__ vinfo,
+                                              const double *__restrict__ pose, const double *__restrict__ blk, double *__restrict__ cand_pose,
+                                              double *__restrict__ cand_cost, double *__restrict__ dnpn)
 {
     const int v = blockIdx.x, lane = threadIdx.x;
     if (st->done || st->bad) return;
@@ -525,17 +577,14 @@ __global__ __launch_bounds__(64) void k_calib_eval(const CalCfg *__restrict__ cf
     double kd[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) kd[i] = st->cand[4 + i];
-    const fid_marker *mlist = markers + (long long)v * cfg->per_view;
-    const int2 *vs = sel + (size_t)v * MP_MAX_USED;
-    const int nres = 8 * vinfo[4 * v];
+    src.bind(v, cfg);
+    const int nres = 2 * SRC::PER_ITEM * vinfo[4 * v];
     double e2 = 0., R[9];
     cal_rotation_value(param, R);
     for (int r = lane; r < nres; r += 64) {
-        const int p = r >> 1, su = r & 1, k = p >> 2, q = p & 3;
-        const int2 se = vs[k];
-        const double *src = map_obj + (size_t)se.y * 12 + q * 3;
-        const double M[3] = {src[0], src[1], src[2]};
-        const double err = cal_project<MODEL>(M, R, param + 3, K, kd, su) - (double)mlist[se.x].corners[2 * q + su];
+        double M[3];
+        src.object(r, M);
+        const double err = cal_project<MODEL>(M, R, param + 3, K, kd, r & 1) - src.image(r);
         e2 += err * err;
     }
     e2 = wave_sum_f64(e2);
@@ -546,6 +595,15 @@ __global__ __launch_bounds__(64) void k_calib_eval(const CalCfg *__restrict__ cf
         dnpn[2 * v] = dn;
         dnpn[2 * v + 1] = pn;
     }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_calib_eval(const CalCfg *__restrict__ cfg, const CalState *__restrict__ st, const fid_marker *__restrict__ markers,
+                                                    const int2 *__restrict__ sel, const int *__restrict__ vinfo, const double *__restrict__ map_obj,
+                                                    const double *__restrict__ pose, const double *__restrict__ blk, double *__restrict__ cand_pose,
+                                                    double *__restrict__ cand_cost, double *__restrict__ dnpn)
+{
+    cal_view_eval<MODEL>(cfg, st, CalMarkers{markers, sel, map_obj, nullptr, nullptr}, vinfo, pose, blk, cand_pose, cand_cost, dnpn);
 }
 
 // ------------------------------------------------------------------------------------------------ K25: accept or reject, the stop
@@ -704,43 +762,46 @@ fid_status fid_camera_to_info(const fid_camera *cam, char *model_string, double 
     return FID_OK;
 }
 
-static bool calib_refuse(fid_ctx *c, const std::string &why)
+static bool calib_refuse(fid_ctx *c, const char *who, const std::string &why)
 {
-    c->last_error = "fid_calibrate_map: " + why;
+    c->last_error = std::string(who) + ": " + why;
     return true;
 }
 
-fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views, int32_t cap_per_view, int32_t image_w,
-                             int32_t image_h, const fid_calib_opts *opts, fid_camera *cam_io, fid_calib_out *out, fid_calib_view *views)
+// ---- the steps fid_calibrate_map and fid_calibrate_charuco (fid_calib_points.hip) share; `who` names the entry point in the last error
+// the arguments that do not depend on what a view holds -> whether the call is refused
+static bool calib_refuse_args(fid_ctx *c, const char *who, const void *items, const int32_t *n_per_view, int32_t n_views, int32_t cap_per_view,
+                              int32_t image_w, int32_t image_h, const fid_calib_opts *opts, const fid_camera *cam_io, const fid_calib_out *out)
 {
-    if (!c) return FID_E_INVALID_ARG;
-    if (!markers || !n_per_view || !opts || !cam_io || !out) return calib_refuse(c, "a NULL pointer"), FID_E_INVALID_ARG;
+    if (!items || !n_per_view || !opts || !cam_io || !out) return calib_refuse(c, who, "a NULL pointer");
     if (n_views < 1 || n_views > FID_CALIB_MAX_VIEWS)
-        return calib_refuse(c, std::to_string(n_views) + " views: 1 .. " + std::to_string(FID_CALIB_MAX_VIEWS) + " (FID_CALIB_MAX_VIEWS)"), FID_E_INVALID_ARG;
-    if (cap_per_view < 1 || image_w < 1 || image_h < 1) return calib_refuse(c, "cap_per_view, image_w and image_h must be positive"), FID_E_INVALID_ARG;
-    if (!fid_camera_usable(cam_io)) return calib_refuse(c, "the camera's model or n_dist is outside the ABI's"), FID_E_INVALID_ARG;
-    if (opts->start != FID_CALIB_START_GIVEN && opts->start != FID_CALIB_START_AUTO) return calib_refuse(c, "start is neither GIVEN nor AUTO"), FID_E_INVALID_ARG;
+        return calib_refuse(c, who, std::to_string(n_views) + " views: 1 .. " + std::to_string(FID_CALIB_MAX_VIEWS) + " (FID_CALIB_MAX_VIEWS)");
+    if (cap_per_view < 1 || image_w < 1 || image_h < 1) return calib_refuse(c, who, "cap_per_view, image_w and image_h must be positive");
+    if (!fid_camera_usable(cam_io)) return calib_refuse(c, who, "the camera's model or n_dist is outside the ABI's");
+    if (opts->start != FID_CALIB_START_GIVEN && opts->start != FID_CALIB_START_AUTO) return calib_refuse(c, who, "start is neither GIVEN nor AUTO");
     if (!(opts->eps >= 0.) || opts->eps - opts->eps != 0. || opts->max_iter < 0 || opts->min_markers < 1)
-        return calib_refuse(c, "eps must be finite and >= 0, max_iter >= 0, min_markers >= 1"), FID_E_INVALID_ARG;
+        return calib_refuse(c, who, "eps must be finite and >= 0, max_iter >= 0, min_markers >= 1");
     const int n_slots = 4 + cam_io->n_dist;
     if (opts->free_mask >> n_slots)
-        return calib_refuse(c, "free_mask names a slot beyond the camera's " + std::to_string(cam_io->n_dist) + " coefficients"), FID_E_INVALID_ARG;
-    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
-    const bool start_auto = opts->start == FID_CALIB_START_AUTO, fixa = opts->fix_aspect != 0;
-    fid_camera start = fid_camera_normalised(*cam_io);
+        return calib_refuse(c, who, "free_mask names a slot beyond the camera's " + std::to_string(cam_io->n_dist) + " coefficients");
+    return false;
+}
+
+// the start camera's values -> whether the call is refused
+static bool calib_refuse_start(fid_ctx *c, const char *who, const fid_calib_opts *opts, const fid_camera &start)
+{
     for (int i = 0; i < 9; i++)
-        if (start.K[i] - start.K[i] != 0.) return calib_refuse(c, "the camera holds a value that is not finite"), FID_E_INVALID_ARG;
+        if (start.K[i] - start.K[i] != 0.) return calib_refuse(c, who, "the camera holds a value that is not finite");
     for (int i = 0; i < 12; i++)
-        if (start.D[i] - start.D[i] != 0.) return calib_refuse(c, "the camera holds a value that is not finite"), FID_E_INVALID_ARG;
-    if (fixa && !(start.K[4] != 0.)) return calib_refuse(c, "fix_aspect needs fy != 0 in the camera"), FID_E_INVALID_ARG;
-    for (int v = 0; v < n_views; v++) {
-        const int n = n_per_view[v] < 0 ? 0 : (n_per_view[v] > cap_per_view ? cap_per_view : n_per_view[v]);
-        const fid_marker *m = markers + (size_t)v * cap_per_view;
-        for (int i = 0; i < n; i++)
-            for (int q = 0; q < 8; q++)
-                if (m[i].corners[q] - m[i].corners[q] != 0.f)
-                    return calib_refuse(c, "view " + std::to_string(v) + ", marker " + std::to_string(i) + ": a corner is not finite"), FID_E_INVALID_ARG;
-    }
+        if (start.D[i] - start.D[i] != 0.) return calib_refuse(c, who, "the camera holds a value that is not finite");
+    if (opts->fix_aspect != 0 && !(start.K[4] != 0.)) return calib_refuse(c, who, "fix_aspect needs fy != 0 in the camera");
+    return false;
+}
+
+// the free slots and the rest of the device's configuration; *mask_out: the free slots as the solve takes them
+static CalCfg calib_config(const fid_calib_opts *opts, const fid_camera &start, int n_views, int cap_per_view, int per_item, int min_items, unsigned *mask_out)
+{
+    const bool fixa = opts->fix_aspect != 0;
     CalCfg cfg = {};
     unsigned mask = opts->free_mask;
     if (fixa) mask &= ~1u;
@@ -748,105 +809,105 @@ fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_
         if (mask >> i & 1u) cfg.col[cfg.nI++] = i;
     cfg.fix_aspect = fixa && (mask >> 1 & 1u);
     cfg.aspect = fixa ? start.K[0] / start.K[4] : 1.;
-    cfg.start_auto = start_auto;
-    cfg.min_markers = opts->min_markers;
+    cfg.start_auto = opts->start == FID_CALIB_START_AUTO;
+    cfg.min_markers = min_items;
     cfg.max_iter = opts->max_iter;
     cfg.n_views = n_views;
     cfg.per_view = cap_per_view;
+    cfg.per_item = per_item;
     cfg.eps = opts->eps;
+    *mask_out = mask;
+    return cfg;
+}
 
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t n_markers = (size_t)n_views * cap_per_view;
-    const fid_status rce = calib_ensure(c, n_views, n_markers);
-    if (rce != FID_OK) return rce;
+// START_AUTO's values into `start` from the views' flags and focal constraints (vinfo and con as the start kernel of the route left
+// them): the rows of the views with at least cfg.min_markers used items and a homography (flag bit 1, and not bit 2: the point route's
+// "on one line"), added in view order.  planar_or_refuse: a counted view without flag bit 0 refuses the call (the marker route).
+static fid_status calib_auto_start(fid_ctx *c, const char *who, const CalCfg &cfg, unsigned mask, double cx0, double cy0, bool planar_or_refuse,
+                                   fid_camera *start)
+{
     CalibBufs *b = c->calib;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(b->d_markers, markers, sizeof(fid_marker) * n_markers, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(b->d_n, n_per_view, sizeof(int) * (size_t)n_views, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(b->d_mem + b->zero_from, 0, b->zero_bytes, st));
-    // ---- the views' used markers; with AUTO the focal constraints
-    const double cx0 = (mask >> 2 & 1u) ? 0.5 * (image_w - 1) : start.K[2], cy0 = (mask >> 3 & 1u) ? 0.5 * (image_h - 1) : start.K[5];
-    hipLaunchKernelGGL(k_calib_start, dim3(n_views), dim3(64), 0, st, (const fid_marker *)b->d_markers, (const int *)b->d_n, cap_per_view,
-                       (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, start_auto ? 1 : 0, cx0, cy0, b->d_sel, b->d_vinfo, b->d_con);
-    HIPCHK(c, hipGetLastError());
-    if (start_auto) {
-        std::vector<int> vinfo((size_t)n_views * 4);
-        std::vector<double> con((size_t)n_views * 6);
-        HIPCHK(c, hipMemcpyAsync(vinfo.data(), b->d_vinfo, sizeof(int) * vinfo.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(con.data(), b->d_con, sizeof(double) * con.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        double aa = 0, ab = 0, bb = 0, ac = 0, bc = 0;
-        for (int v = 0; v < n_views; v++) {
-            if (vinfo[4 * (size_t)v] < opts->min_markers) continue;
-            if (!(vinfo[4 * (size_t)v + 3] & 1))
-                return calib_refuse(c, "view " + std::to_string(v) + ": its mapped markers are not coplanar; START_AUTO needs planar views, give a start"),
-                       FID_E_INVALID_ARG;
-            if (!(vinfo[4 * (size_t)v + 3] & 2)) continue;
-            for (int r = 0; r < 2; r++) {  // the view's two rows, in order
-                const double *q = &con[6 * (size_t)v + 3 * r];
-                aa += q[0] * q[0]; ab += q[0] * q[1]; bb += q[1] * q[1]; ac += q[0] * q[2]; bc += q[1] * q[2];
-            }
+    const int n_views = cfg.n_views;
+    std::vector<int> vinfo((size_t)n_views * 4);
+    std::vector<double> con((size_t)n_views * 6);
+    HIPCHK(c, hipMemcpyAsync(vinfo.data(), b->d_vinfo, sizeof(int) * vinfo.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(con.data(), b->d_con, sizeof(double) * con.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    double aa = 0, ab = 0, bb = 0, ac = 0, bc = 0;
+    for (int v = 0; v < n_views; v++) {
+        if (vinfo[4 * (size_t)v] < cfg.min_markers) continue;
+        const int flags = vinfo[4 * (size_t)v + 3];
+        if (planar_or_refuse && !(flags & 1))
+            return calib_refuse(c, who, "view " + std::to_string(v) + ": its mapped markers are not coplanar; START_AUTO needs planar views, give a start"),
+                   FID_E_INVALID_ARG;
+        if ((flags & 6) != 2) continue;
+        for (int r = 0; r < 2; r++) {  // the view's two rows, in order
+            const double *q = &con[6 * (size_t)v + 3 * r];
+            aa += q[0] * q[0]; ab += q[0] * q[1]; bb += q[1] * q[1]; ac += q[0] * q[2]; bc += q[1] * q[2];
         }
-        const double det = aa * bb - ab * ab;
-        const double X = (ac * bb - bc * ab) / det, Y = (aa * bc - ab * ac) / det;
-        const double fx = sqrt(fabs(1. / X)), fy = sqrt(fabs(1. / Y));
-        if (!(fx - fx == 0.) || !(fy - fy == 0.) || !(fx > 0.) || !(fy > 0.))
-            return calib_refuse(c, "START_AUTO: the views do not determine the focal lengths; give a start"), FID_E_INVALID_ARG;
-        if (mask >> 1 & 1u) start.K[4] = fy;
-        if (mask & 1u) start.K[0] = fx;
-        start.K[2] = cx0;
-        start.K[5] = cy0;
-        for (int i = 0; i < 12; i++)
-            if (mask >> (4 + i) & 1u) start.D[i] = 0.;
     }
-    if (cfg.fix_aspect) start.K[0] = cfg.aspect * start.K[4];
-    // ---- the start poses: k_map_pose over the views under the start camera
-    map_pose_launch(c, st, b->d_markers, b->d_n, 1, cap_per_view, n_views, start, b->d_vpose);
-    HIPCHK(c, hipGetLastError());
+    const double det = aa * bb - ab * ab;
+    const double X = (ac * bb - bc * ab) / det, Y = (aa * bc - ab * ac) / det;
+    const double fx = sqrt(fabs(1. / X)), fy = sqrt(fabs(1. / Y));
+    if (!(fx - fx == 0.) || !(fy - fy == 0.) || !(fx > 0.) || !(fy > 0.))
+        return calib_refuse(c, who, "START_AUTO: the views do not determine the focal lengths; give a start"), FID_E_INVALID_ARG;
+    if (mask >> 1 & 1u) start->K[4] = fy;
+    if (mask & 1u) start->K[0] = fx;
+    start->K[2] = cx0;
+    start->K[5] = cy0;
+    for (int i = 0; i < 12; i++)
+        if (mask >> (4 + i) & 1u) start->D[i] = 0.;
+    return FID_OK;
+}
+
+// From the start camera and the views' start-pose records to the caller's results: the state, the route's init kernel, the counts and
+// their refusals, Levenberg-Marquardt in chunks of CAL_CHUNK trials, FINAL, the copies back.  init(), blocks(final) and eval() launch the
+// route's K22 / K24 (and its form of k_calib_init) on the context's stream; k_calib_solve and k_calib_accept are launched here.
+template <class INIT, class BLOCKS, class EVAL>
+static fid_status calib_solve_views(fid_ctx *c, const char *who, const char *none_why, const CalCfg &cfg, unsigned mask, const fid_camera &start,
+                                    INIT init, BLOCKS view_blocks, EVAL view_eval, fid_camera *cam_io, fid_calib_out *out, fid_calib_view *views)
+{
+    CalibBufs *b = c->calib;
+    hipStream_t st = c->stream;
+    const int n_views = cfg.n_views, max_iter = cfg.max_iter;
     CalState hs = {};
     hs.k[0] = start.K[0]; hs.k[1] = start.K[4]; hs.k[2] = start.K[2]; hs.k[3] = start.K[5];
     for (int i = 0; i < 12; i++) hs.k[4 + i] = start.D[i];
     for (int i = 0; i < 16; i++) hs.cand[i] = hs.k[i];
     hs.lambdaLg10 = -3;
     hs.needJ = 1;
-    hs.done = opts->max_iter == 0 ? 1 : 0;
-    hs.status = opts->max_iter == 0 ? FID_CALIB_MAX_ITER : FID_CALIB_OK;
+    hs.done = max_iter == 0 ? 1 : 0;
+    hs.status = max_iter == 0 ? FID_CALIB_MAX_ITER : FID_CALIB_OK;
     HIPCHK(c, hipMemcpyAsync(b->d_cfg, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(b->d_state, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_calib_init, dim3(1), dim3(64), 0, st, (const CalCfg *)b->d_cfg, b->d_state, b->d_vinfo, (const fid_map_pose_out *)b->d_vpose, b->d_pose);
+    init();
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(&hs, b->d_state, sizeof(hs), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     const int n_free = cfg.nI + 6 * hs.n_views_used;
-    if (hs.n_views_used == 0) return calib_refuse(c, "no view can be used (too few mapped markers, or no start pose)"), FID_E_INVALID_ARG;
+    if (hs.n_views_used == 0) return calib_refuse(c, who, none_why), FID_E_INVALID_ARG;
     if (2 * hs.n_points < n_free)
-        return calib_refuse(c, std::to_string(2 * hs.n_points) + " residuals for " + std::to_string(n_free) + " free parameters"), FID_E_INVALID_ARG;
+        return calib_refuse(c, who, std::to_string(2 * hs.n_points) + " residuals for " + std::to_string(n_free) + " free parameters"), FID_E_INVALID_ARG;
     // ---- Levenberg-Marquardt: CAL_CHUNK trials, then the status
-    const int model = start.model;
     auto blocks = [&](int final) {
-        POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_blocks<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
-                                                    (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
-                                                    (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose, b->d_blk, b->d_sch,
-                                                    b->d_cost, final));
+        view_blocks(final);
         hipLaunchKernelGGL(k_calib_solve, dim3(1), dim3(320), 0, st, (const CalCfg *)b->d_cfg, b->d_state, (const int *)b->d_vinfo, (const double *)b->d_blk,
                            (const double *)b->d_sch, (const double *)b->d_cost, (const double *)b->d_pose, final, b->d_out, b->d_vout);
     };
     int queued = 0;
     while (!hs.done) {
-        for (int i = 0; i < CAL_CHUNK && queued < opts->max_iter; i++, queued++) {
+        for (int i = 0; i < CAL_CHUNK && queued < max_iter; i++, queued++) {
             blocks(0);
-            POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_eval<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
-                                                        (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
-                                                        (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose,
-                                                        (const double *)b->d_blk, b->d_cand, b->d_ccost, b->d_dnpn));
+            view_eval();
             hipLaunchKernelGGL(k_calib_accept, dim3(1), dim3(64), 0, st, (const CalCfg *)b->d_cfg, b->d_state, (const int *)b->d_vinfo, b->d_pose,
                                (const double *)b->d_cand, (const double *)b->d_ccost, (const double *)b->d_dnpn);
         }
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(&hs.lambdaLg10, &b->d_state->lambdaLg10, sizeof(int) * 4, hipMemcpyDeviceToHost, st));  // lambdaLg10 trials status done
         HIPCHK(c, hipStreamSynchronize(st));
-        if (!hs.done && queued >= opts->max_iter) {
-            c->last_error = "fid_calibrate_map: the device did not report the stop after max_iter trials";
+        if (!hs.done && queued >= max_iter) {
+            c->last_error = std::string(who) + ": the device did not report the stop after max_iter trials";
             return FID_E_HIP;
         }
     }
@@ -868,4 +929,68 @@ fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_
     *out = ho;
     if (views) memcpy(views, hv.data(), sizeof(fid_calib_view) * (size_t)n_views);
     return FID_OK;
+}
+
+fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_t *n_per_view, int32_t n_views, int32_t cap_per_view, int32_t image_w,
+                             int32_t image_h, const fid_calib_opts *opts, fid_camera *cam_io, fid_calib_out *out, fid_calib_view *views)
+{
+    static const char who[] = "fid_calibrate_map";
+    if (!c) return FID_E_INVALID_ARG;
+    if (calib_refuse_args(c, who, markers, n_per_view, n_views, cap_per_view, image_w, image_h, opts, cam_io, out)) return FID_E_INVALID_ARG;
+    if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
+    fid_camera start = fid_camera_normalised(*cam_io);
+    if (calib_refuse_start(c, who, opts, start)) return FID_E_INVALID_ARG;
+    for (int v = 0; v < n_views; v++) {
+        const int n = n_per_view[v] < 0 ? 0 : (n_per_view[v] > cap_per_view ? cap_per_view : n_per_view[v]);
+        const fid_marker *m = markers + (size_t)v * cap_per_view;
+        for (int i = 0; i < n; i++)
+            for (int q = 0; q < 8; q++)
+                if (m[i].corners[q] - m[i].corners[q] != 0.f)
+                    return calib_refuse(c, who, "view " + std::to_string(v) + ", marker " + std::to_string(i) + ": a corner is not finite"), FID_E_INVALID_ARG;
+    }
+    unsigned mask = 0;
+    const CalCfg cfg = calib_config(opts, start, n_views, cap_per_view, 4, opts->min_markers, &mask);
+
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n_markers = (size_t)n_views * cap_per_view;
+    const fid_status rce = calib_ensure(c, n_views, n_markers);
+    if (rce != FID_OK) return rce;
+    CalibBufs *b = c->calib;
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(b->d_markers, markers, sizeof(fid_marker) * n_markers, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(b->d_n, n_per_view, sizeof(int) * (size_t)n_views, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(b->d_mem + b->zero_from, 0, b->zero_bytes, st));
+    // ---- the views' used markers; with AUTO the focal constraints
+    const double cx0 = (mask >> 2 & 1u) ? 0.5 * (image_w - 1) : start.K[2], cy0 = (mask >> 3 & 1u) ? 0.5 * (image_h - 1) : start.K[5];
+    hipLaunchKernelGGL(k_calib_start, dim3(n_views), dim3(64), 0, st, (const fid_marker *)b->d_markers, (const int *)b->d_n, cap_per_view,
+                       (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, cfg.start_auto, cx0, cy0, b->d_sel, b->d_vinfo, b->d_con);
+    HIPCHK(c, hipGetLastError());
+    if (cfg.start_auto) {
+        const fid_status rca = calib_auto_start(c, who, cfg, mask, cx0, cy0, true, &start);
+        if (rca != FID_OK) return rca;
+    }
+    if (cfg.fix_aspect) start.K[0] = cfg.aspect * start.K[4];
+    // ---- the start poses: k_map_pose over the views under the start camera
+    map_pose_launch(c, st, b->d_markers, b->d_n, 1, cap_per_view, n_views, start, b->d_vpose);
+    HIPCHK(c, hipGetLastError());
+    const int model = start.model;
+    return calib_solve_views(
+        c, who, "no view can be used (too few mapped markers, or no start pose)", cfg, mask, start,
+        [&] {
+            hipLaunchKernelGGL(k_calib_init, dim3(1), dim3(64), 0, st, (const CalCfg *)b->d_cfg, b->d_state, b->d_vinfo, (const fid_map_pose_out *)b->d_vpose,
+                               b->d_pose);
+        },
+        [&](int final) {
+            POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_blocks<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
+                                                        (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
+                                                        (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose, b->d_blk, b->d_sch,
+                                                        b->d_cost, final));
+        },
+        [&] {
+            POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_eval<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
+                                                        (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
+                                                        (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose,
+                                                        (const double *)b->d_blk, b->d_cand, b->d_ccost, b->d_dnpn));
+        },
+        cam_io, out, views);
 }

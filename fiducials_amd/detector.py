@@ -599,21 +599,15 @@ class ArucoDetector:
         return out[:self._last_frames]
 
     # -- calibration ------------------------------------------------------------------------------
-    def calibrate_map(self, views, image_size, model: int = _lib.CAM_PLUMB_BOB, free: int | None = None, start=None, fix_aspect: bool = False,
-                      max_iter: int | None = None, eps: float | None = None, min_markers: int = 1):
-        """The camera from views of the context's map (fid_calibrate_map; set_map first).  views: a list of (corners (n, 4, 2), ids (n,))
-        as detect_markers_batch returns them, or of (ids, corners).  image_size: (width, height).  model: CAM_*.  free: a CALIB_FREE_*
-        mask (default: the model's usual one -- plumb-bob 9 slots, rational 12, equidistant 8).  start: None for the AUTO start (planar
-        maps), or the Camera to start from -- it also gives the values of the slots that are not free and, with fix_aspect, the ratio
-        fx / fy.  Returns (Camera, CALIB_OUT_DTYPE record, CALIB_VIEW_DTYPE array)."""
-        L = self._L
+    def _calib_setup(self, who, model, free, start, fix_aspect, max_iter, eps, min_items):
+        """fid_calib_opts and the camera that goes in, as calibrate_map and calibrate_charuco both read their arguments."""
         default_free = {_lib.CAM_PLUMB_BOB: (_lib.CALIB_FREE_PLUMB_BOB, 5), _lib.CAM_RATIONAL: (_lib.CALIB_FREE_RATIONAL, 8),
                         _lib.CAM_EQUIDISTANT: (_lib.CALIB_FREE_EQUIDISTANT, 4)}
         opts = _lib.FidCalibOpts()
-        L.fid_default_calib_opts(C.byref(opts))
+        self._L.fid_default_calib_opts(C.byref(opts))
         if start is None:
             if int(model) not in default_free:
-                raise FidError(_lib.FID_E_INVALID_ARG, f"calibrate_map: model {model} is not a CAM_* value")
+                raise FidError(_lib.FID_E_INVALID_ARG, f"{who}: model {model} is not a CAM_* value")
             mask, nd = default_free[int(model)]
             if free is not None:
                 mask = int(free)
@@ -629,11 +623,22 @@ class ArucoDetector:
             opts.start = _lib.CALIB_START_GIVEN
         opts.free_mask = mask
         opts.fix_aspect = 1 if fix_aspect else 0
-        opts.min_markers = int(min_markers)
+        opts.min_markers = int(min_items)
         if max_iter is not None:
             opts.max_iter = int(max_iter)
         if eps is not None:
             opts.eps = float(eps)
+        return opts, cam
+
+    def calibrate_map(self, views, image_size, model: int = _lib.CAM_PLUMB_BOB, free: int | None = None, start=None, fix_aspect: bool = False,
+                      max_iter: int | None = None, eps: float | None = None, min_markers: int = 1):
+        """The camera from views of the context's map (fid_calibrate_map; set_map first).  views: a list of (corners (n, 4, 2), ids (n,))
+        as detect_markers_batch returns them, or of (ids, corners).  image_size: (width, height).  model: CAM_*.  free: a CALIB_FREE_*
+        mask (default: the model's usual one -- plumb-bob 9 slots, rational 12, equidistant 8).  start: None for the AUTO start (planar
+        maps), or the Camera to start from -- it also gives the values of the slots that are not free and, with fix_aspect, the ratio
+        fx / fy.  Returns (Camera, CALIB_OUT_DTYPE record, CALIB_VIEW_DTYPE array)."""
+        L = self._L
+        opts, cam = self._calib_setup("calibrate_map", model, free, start, fix_aspect, max_iter, eps, min_markers)
         # a view: (corners, ids) as detect_markers_batch returns it, or (ids, corners) -- the ids are the flat one of the pair
         views = [(a, b) if np.asarray(b).ndim <= 1 and np.asarray(a).ndim > 1 else (b, a) for a, b in views]
         cap = max([len(np.asarray(v[1]).reshape(-1)) for v in views] + [1])
@@ -649,6 +654,37 @@ class ArucoDetector:
         self._check(L.fid_calibrate_map(self._ctx, mk.ctypes.data, n.ctypes.data, len(views), cap, int(image_size[0]), int(image_size[1]), C.byref(opts),
                                         C.byref(cam.c), out.ctypes.data, vout.ctypes.data))
         return cam, out[0], vout[:len(views)]
+
+    def calibrate_charuco(self, views, image_size, model: int = _lib.CAM_PLUMB_BOB, free: int | None = None, start=None, fix_aspect: bool = False,
+                          max_iter: int | None = None, eps: float | None = None, min_points: int = 4):
+        """The camera from views of the context's ChArUco board (fid_calibrate_charuco; set_charuco_board first).  views: the list
+        charuco_last returns (one CHARUCO_CORNER_DTYPE array per frame), or a list of (ids (n,), xy (n, 2)) pairs.  Everything else is
+        calibrate_map's; start=None is the AUTO start, which a board always allows.  min_points: a view with fewer used points (never
+        fewer than four) is skipped.  Returns (Camera, CALIB_OUT_DTYPE record, CALIB_VIEW_DTYPE array)."""
+        opts, cam = self._calib_setup("calibrate_charuco", model, free, start, fix_aspect, max_iter, eps, min_points)
+        recs = []
+        for view in views:
+            if isinstance(view, np.ndarray) and view.dtype == CHARUCO_CORNER_DTYPE:
+                recs.append(view.reshape(-1))
+                continue
+            ids, xy = view
+            ids = np.asarray(ids, np.int32).reshape(-1)
+            r = np.zeros(len(ids), CHARUCO_CORNER_DTYPE)
+            r["id"] = ids
+            r["x"], r["y"] = np.asarray(xy, np.float32).reshape(len(ids), 2).T
+            r["x0"], r["y0"] = r["x"], r["y"]
+            recs.append(r)
+        cap = max([len(r) for r in recs] + [1])
+        packed = np.zeros((max(len(recs), 1), cap), CHARUCO_CORNER_DTYPE)
+        n = np.zeros(max(len(recs), 1), np.int32)
+        for i, r in enumerate(recs):
+            n[i] = len(r)
+            packed[i, :len(r)] = r
+        out = np.zeros(1, _lib.CALIB_OUT_DTYPE)
+        vout = np.zeros(max(len(recs), 1), _lib.CALIB_VIEW_DTYPE)
+        self._check(self._L.fid_calibrate_charuco(self._ctx, packed.ctypes.data, n.ctypes.data, len(recs), cap, int(image_size[0]), int(image_size[1]),
+                                                  C.byref(opts), C.byref(cam.c), out.ctypes.data, vout.ctypes.data))
+        return cam, out[0], vout[:len(recs)]
 
     # -- building the map -------------------------------------------------------------------------
     def build_map(self, views, camera, fiducial_len: float, fixed, len_override: dict | None = None, min_views: int = 2, max_iter: int | None = None,

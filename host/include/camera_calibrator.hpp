@@ -1,7 +1,8 @@
 // camera_calibrator.hpp -- the host side of fid_calibrate_map (include/fid_abi.h: "camera calibration from views of the map"):
 // collect the markers of frames that show the context's map, calibrate, and hand the result on as sensor_msgs/CameraInfo's fields
-// or as the YAML file camera drivers load through `camera_info_url` (camera_calibration_parsers' layout).  Header only; needs
-// nothing but the C-ABI.
+// or as the YAML file camera drivers load through `camera_info_url` (camera_calibration_parsers' layout).  CharucoCalibrator is the
+// same over fid_calibrate_charuco: the views are the chessboard corner records of frames that show the context's ChArUco board.
+// Header only; needs nothing but the C-ABI.
 #pragma once
 
 #include <array>
@@ -101,6 +102,46 @@ private:
     fid_ctx *ctx_;
     int w_, h_;
     std::vector<std::vector<fid_marker>> views_;
+};
+
+// fid_calibrate_charuco (include/fid_abi.h: "camera calibration from ChArUco corners") over views collected one by one; the result goes
+// on through CameraCalibrator::toCameraInfo / writeYaml
+class CharucoCalibrator {
+public:
+    // ctx: a context with its board set (fid_set_charuco_board); it is borrowed, not owned
+    CharucoCalibrator(fid_ctx *ctx, int image_width, int image_height) : ctx_(ctx), w_(image_width), h_(image_height) {}
+
+    // the corner records of one frame (fid_charuco_last_cam's or fid_charuco_interpolate_cam's output); a frame without corners may be
+    // added, it is skipped by the solve
+    void addView(const fid_charuco_corner *corners, int n)
+    {
+        views_.emplace_back(corners, corners + (n > 0 ? n : 0));
+    }
+    size_t size() const { return views_.size(); }
+    void clear() { views_.clear(); }
+
+    // fid_calibrate_charuco over the views added so far.  *cam_io: model, n_dist, start / fixed values in, the calibrated camera out.
+    fid_status calibrate(const fid_calib_opts &opts, fid_camera *cam_io, fid_calib_out *out, std::vector<fid_calib_view> *views = nullptr) const
+    {
+        size_t cap = 1;
+        for (const auto &v : views_) cap = v.size() > cap ? v.size() : cap;
+        std::vector<fid_charuco_corner> packed(views_.size() * cap);
+        std::vector<int32_t> n(views_.size());
+        for (size_t i = 0; i < views_.size(); i++) {
+            n[i] = (int32_t)views_[i].size();
+            for (size_t k = 0; k < views_[i].size(); k++) packed[i * cap + k] = views_[i][k];
+        }
+        std::vector<fid_calib_view> vout(views_.size());
+        const fid_status rc = fid_calibrate_charuco(ctx_, packed.data(), n.data(), (int32_t)views_.size(), (int32_t)cap, w_, h_, &opts, cam_io, out,
+                                                    vout.empty() ? nullptr : vout.data());
+        if (rc == FID_OK && views) *views = vout;
+        return rc;
+    }
+
+private:
+    fid_ctx *ctx_;
+    int w_, h_;
+    std::vector<std::vector<fid_charuco_corner>> views_;
 };
 
 }  // namespace fiducials_amd

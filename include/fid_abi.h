@@ -888,6 +888,39 @@ fid_status fid_charuco_pose_last_cam(fid_ctx *ctx, const fid_camera *cam, int32_
  * FID_E_INVALID_ARG; n at most FID_CHARUCO_MAX_SQUARES) */
 fid_status fid_charuco_pose_cam(fid_ctx *ctx, const fid_camera *cam, const float *xy, const int32_t *ids, int32_t n, fid_charuco_pose_out *out);
 
+/* ---- camera calibration from ChArUco corners (an addition to ABI 7: one entry point).  cv::aruco::calibrateCameraCharuco -- the
+ * chessboard corners of every view into cv::calibrateCamera -- as fid_calibrate_map's joint solve over points instead of markers
+ * (restated in NumPy in tests/charuco_calib_restatement.py).  The board is the context's (fid_set_charuco_board); a map is not needed.
+ * EVERYTHING NOT NAMED BELOW IS fid_calibrate_map's, word for word: the sixteen slots, free_mask, fix_aspect, AUTO's arithmetic, the
+ * solve and its stop, the defaults, std_dev, reproducibility, and "nothing of it exists on a context until its first call".
+ *
+ * Views.  n_views <= FID_CALIB_MAX_VIEWS lists of corner records; view v is corners[v * cap_per_view .. + n_per_view[v]) --
+ * fid_charuco_last_cam's output layout, so a batch of frames goes detect -> fid_charuco_last_cam -> here as it is.  n_per_view[v] is
+ * clamped to [0, cap_per_view].
+ *
+ * Points of a view.  The records in list order.  The image point is (x, y), the refined position, widened to double; x0, y0 and win
+ * are ignored.  The object point of id i is the board's chessboard corner i as defined above, ((cx + 1) s, (cy + 1) s, 0) with each
+ * coordinate rounded through float.  An id outside the board, or an x or y that is not finite, in any listed record:
+ * FID_E_INVALID_ARG.  An id that occurs more than once in a view is left out altogether (k_map_pose's rule).
+ * fid_calib_view.n_used is the number of points used, n_over is 0; fid_calib_view.rms is sqrt(the view's cost / its points) and
+ * fid_calib_out.n_points counts points.
+ *
+ * Which views are used.  With m = max(opts.min_markers, 4) -- the field is read as a count of points here; OpenCV also asks for
+ * four -- a view with fewer than m used points is FID_CALIB_VIEW_FEW.  A view is FID_CALIB_VIEW_NO_START when its used points lie on
+ * one line of the grid (tested exactly on the integer cx, cy, as fid_charuco_pose_cam does), when fid_charuco_pose_cam's record for
+ * the used points under the start camera is not FID_CHARUCO_POSE_OK or is not finite, or, with START_AUTO, when the view's
+ * homography does not exist.  A skipped view does not fail the call.
+ *
+ * Start.  A board is planar, so START_AUTO is always allowed.  Its per-view homography is fid_calibrate_map's: the plane frame of
+ * the view's own used points, then the DLT to the float pixels (x, y); the views counted are those with at least m used points that
+ * are not on one line.  In both modes every view's pose starts from fid_charuco_pose_cam's solve on the view's used points under the
+ * start camera.
+ *
+ * Refusals: fid_calibrate_map's, with "no board" in place of "no map". */
+fid_status fid_calibrate_charuco(fid_ctx *ctx, const fid_charuco_corner *corners, const int32_t *n_per_view, int32_t n_views,
+                                 int32_t cap_per_view, int32_t image_w, int32_t image_h, const fid_calib_opts *opts, fid_camera *cam_io,
+                                 fid_calib_out *out, fid_calib_view *views);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
