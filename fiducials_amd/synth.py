@@ -74,9 +74,18 @@ def _blur(img, sigma):
 
 def make_frame(d: Dictionary, seed: int, width: int = 1920, height: int = 1080, n_markers: int = 20,
                ids: np.ndarray | None = None, K: np.ndarray | None = None, noise_sigma: float = 2.0,
-               side_range=(96.0, 160.0), max_tilt_deg: float = 35.0, pinned_only: bool = False, border_bits: int = 1) -> SynthFrame:
+               side_range=(96.0, 160.0), max_tilt_deg: float = 35.0, pinned_only: bool = False, border_bits: int = 1,
+               cells=None) -> SynthFrame:
     """border_bits: cells of black border the markers are drawn with (aruco::drawMarker's borderBits; the detector side is
-    DetectorParameters::markerBorderBits, aruco_detect.cpp:718)."""
+    DetectorParameters::markerBorderBits, aruco_detect.cpp:718).
+    cells: optional mapping marker index (0 ... n_markers - 1) -> a full (n + 2 border_bits)^2 cell grid, 0 = black, non-zero =
+    white, drawn instead of draw_marker(d, ids[index], ...) -- markers with a damaged border.  None: every marker is draw_marker's."""
+    cell_grids = {}
+    for mi, grid in (cells or {}).items():
+        grid = np.asarray(grid)
+        if grid.shape != (d.marker_size + 2 * border_bits,) * 2:
+            raise ValueError(f"cells[{mi}]: a {d.marker_size + 2 * border_bits} x {d.marker_size + 2 * border_bits} grid is drawn, got {grid.shape}")
+        cell_grids[int(mi)] = grid
     rng = np.random.default_rng(seed)
     if K is None:
         K = K_DEFAULT.copy()
@@ -162,8 +171,8 @@ def make_frame(d: Dictionary, seed: int, width: int = 1920, height: int = 1080, 
         V = (H[1, 0] * PX + H[1, 1] * PY + H[1, 2]) / den
         inside = (U >= -q) & (U < ncell + q) & (V >= -q) & (V < ncell + q)
         tiny = np.full((ncell + 2, ncell + 2), 230.0, dtype=np.float32)  # quiet zone white
-        m = draw_marker(d, int(ids[mi]), ncell, border_bits).astype(np.float32)
-        tiny[1:-1, 1:-1] = np.where(m > 0, 230.0, 25.0)
+        m = cell_grids[mi] if mi in cell_grids else draw_marker(d, int(ids[mi]), ncell, border_bits)
+        tiny[1:-1, 1:-1] = np.where(m.astype(np.float32) > 0, 230.0, 25.0)
         ui = np.clip(np.floor(U + q).astype(np.int64), 0, ncell + 1)
         vi = np.clip(np.floor(V + q).astype(np.int64), 0, ncell + 1)
         val = tiny[vi, ui]
