@@ -86,6 +86,11 @@ class FidCalibOpts(C.Structure):
                 ("reserved0", C.c_int32), ("eps", C.c_double)]
 
 
+class FidDiamondOpts(C.Structure):
+    """fid_diamond_opts: square_len / marker_len, the matching tolerance in marker sides, whether to refine."""
+    _fields_ = [("square_marker_rate", C.c_double), ("max_rep_rate", C.c_double), ("refine", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class FidCharucoBoard(C.Structure):
     """fid_charuco_board: squares a side, square and marker length, the id of the first marker."""
     _fields_ = [("squares_x", C.c_int32), ("squares_y", C.c_int32), ("square_len", C.c_double), ("marker_len", C.c_double), ("first_id", C.c_int32),
@@ -179,6 +184,10 @@ CHARUCO_POSE_OK, CHARUCO_POSE_FEW, CHARUCO_POSE_COLLINEAR, CHARUCO_POSE_VOID = 0
 CHARUCO_CORNER_DTYPE = np.dtype([("id", "<i4"), ("win", "<i4"), ("x", "<f4"), ("y", "<f4"), ("x0", "<f4"), ("y0", "<f4")])  # fid_charuco_corner
 CHARUCO_POSE_DTYPE = np.dtype([("n_corners", "<i4"), ("status", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("R", "<f8", (3, 3)),
                                ("cam_R", "<f8", (3, 3)), ("cam_t", "<f8", (3,)), ("image_error", "<f8")])  # fid_charuco_pose_out
+# ChArUco diamonds (fid_abi.h: "ChArUco diamonds")
+DIAMOND_MAX_PER_FRAME, DIAMOND_MAX_MARKERS = 64, 256  # FID_DIAMOND_MAX_PER_FRAME, FID_DIAMOND_MAX_MARKERS
+DIAMOND_DTYPE = np.dtype([("ids", "<i4", (4,)), ("index", "<i4", (4,)), ("corners", "<f4", (4, 2)), ("corners0", "<f4", (4, 2)),
+                          ("win", "<i4", (4,))])  # fid_diamond
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -198,6 +207,7 @@ SYMBOLS = [
     "fid_build_map_robust_cam",
     "fid_set_charuco_board", "fid_charuco_last_cam", "fid_charuco_interpolate_cam", "fid_charuco_pose_last_cam", "fid_charuco_pose_cam",
     "fid_calibrate_charuco",
+    "fid_default_diamond_opts", "fid_diamonds_last", "fid_diamonds_detect", "fid_diamond_pose_cam",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -413,6 +423,12 @@ def load():
         L.fid_charuco_pose_cam.argtypes = [vp, cam, vp, vp, i32, vp]
     if hasattr(L, "fid_calibrate_charuco"):  # (calibration from ChArUco corners; FID_LIB may name a build from before it)
         L.fid_calibrate_charuco.argtypes = [vp, vp, vp, i32, i32, i32, i32, C.POINTER(FidCalibOpts), C.POINTER(FidCamera), vp, vp]
+    if hasattr(L, "fid_diamonds_last"):  # (ChArUco diamonds; FID_LIB may name a build from before them)
+        L.fid_default_diamond_opts.argtypes = [C.POINTER(FidDiamondOpts)]
+        L.fid_default_diamond_opts.restype = None
+        L.fid_diamonds_last.argtypes = [vp, C.POINTER(FidDiamondOpts), vp, i32, vp]
+        L.fid_diamonds_detect.argtypes = [vp, C.POINTER(FidDiamondOpts), vp, i32, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
+        L.fid_diamond_pose_cam.argtypes = [vp, C.POINTER(FidCamera), vp, i32, C.c_double, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

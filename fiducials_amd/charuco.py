@@ -108,3 +108,36 @@ class CharucoBoard:
             y0, y1 = Hpx - int(round(c0[1] * k)), Hpx - int(round(c2[1] * k))
             img[y0:y1, x0:x1] = draw_marker(d, int(self.ids[m]), x1 - x0, border_bits)[:y1 - y0]
         return img
+
+
+class CharucoDiamond(CharucoBoard):
+    """A ChArUco diamond (include/fid_abi.h, "ChArUco diamonds"): the 3 x 3 board whose four markers, in the squares (1,0), (0,1), (2,1),
+    (1,2), carry the ids given -- any four, repeats allowed -- around the black middle square.  Object points, layout() and draw() are
+    the board's, so the printed sheet (marker_gen --diamond), the synthetic frame (synth.make_diamond_frame) and the pose agree by
+    construction.  ArucoDetector.diamonds_last reports the chessboard corners in the order RECORD_CORNERS."""
+
+    RECORD_CORNERS = (2, 3, 1, 0)  # fid_diamond.corners: the order of a marker's corners (top left, top right, bottom right, bottom left)
+
+    def __init__(self, ids, square_len: float, marker_len: float):
+        super().__init__(3, 3, square_len, marker_len, 0)
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        if len(ids) != 4 or np.any(ids < 0):
+            raise ValueError("a diamond has four marker ids, none negative")
+        self.ids = ids.astype(np.int32)
+
+    @property
+    def square_marker_rate(self) -> float:
+        return self.square_len / self.marker_len
+
+    @property
+    def record_object_points(self) -> np.ndarray:
+        """(4, 3): the chessboard corners in the order of fid_diamond.corners"""
+        return self.corner_object_points[list(self.RECORD_CORNERS)]
+
+    @property
+    def centre(self) -> np.ndarray:
+        """the middle of the middle square: the origin of the fiducial that diamond_pose poses"""
+        return np.array([1.5 * self.square_len, 1.5 * self.square_len, 0.0])
+
+    def c_struct(self):
+        raise TypeError("a diamond is not a context's board: diamonds_last / diamonds_detect take its square_marker_rate")

@@ -258,6 +258,8 @@ struct fid_ctx {
     struct CharucoBufs *charuco = nullptr;
     // fid_calibrate_charuco (fid_calib_points.hip): the point tables beside `calib`; nothing until the first call
     struct CalibPtsBufs *calib_pts = nullptr;
+    // ChArUco diamonds (fid_diamond.hip): proposals, result slots, staging; nothing until the first fid_diamonds_* call
+    struct DiamondBufs *diamond = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -286,6 +288,8 @@ static void build_free(fid_ctx *c);
 static void charuco_free(fid_ctx *c);
 // fid_calibrate_charuco's buffers (fid_calib_points.hip, behind fid_charuco.hip)
 static void calib_pts_free(fid_ctx *c);
+// the diamonds' buffers (fid_diamond.hip, behind fid_calib_points.hip)
+static void diamond_free(fid_ctx *c);
 
 namespace {
 
@@ -1656,6 +1660,7 @@ void fid_destroy(fid_ctx *c)
     build_free(c);
     charuco_free(c);
     calib_pts_free(c);
+    diamond_free(c);
     void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
@@ -2360,3 +2365,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_map_build.hip"
 #include "fid_charuco.hip"
 #include "fid_calib_points.hip"
+#include "fid_diamond.hip"

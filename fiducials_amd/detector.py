@@ -46,6 +46,7 @@ MAP_POSE_COV_DTYPE = np.dtype([("pose", POSE_COV_DTYPE), ("cov_cam_pose", "<f8",
 MAP_ROBUST_DTYPE = _lib.MAP_ROBUST_DTYPE  # fid_map_robust_out
 CHARUCO_CORNER_DTYPE = _lib.CHARUCO_CORNER_DTYPE  # fid_charuco_corner
 CHARUCO_POSE_DTYPE = _lib.CHARUCO_POSE_DTYPE  # fid_charuco_pose_out
+DIAMOND_DTYPE = _lib.DIAMOND_DTYPE  # fid_diamond
 
 
 def map_robust_outlier_positions(rec) -> np.ndarray:
@@ -597,6 +598,66 @@ class ArucoDetector:
         out = np.zeros(max(self._last_frames, 1), CHARUCO_POSE_DTYPE)
         self._check(self._L.fid_charuco_pose_last_cam(self._ctx, C.byref(cam.c), int(min_markers), out.ctypes.data, len(out)))
         return out[:self._last_frames]
+
+    # -- ChArUco diamonds -------------------------------------------------------------------------
+    def _diamond_opts(self, square_marker_rate, max_rep_rate, refine):
+        o = _lib.FidDiamondOpts()
+        self._L.fid_default_diamond_opts(C.byref(o))
+        if square_marker_rate is not None:
+            o.square_marker_rate = float(square_marker_rate)
+        if max_rep_rate is not None:
+            o.max_rep_rate = float(max_rep_rate)
+        o.refine = int(bool(refine))
+        return o
+
+    def diamonds_last(self, square_marker_rate: float | None = None, max_rep_rate: float | None = None, refine: bool = True,
+                      cap: int = _lib.DIAMOND_MAX_PER_FRAME) -> list:
+        """The diamonds (four markers around one chessboard square) among the markers of every frame of the last detect_* / collect
+        call, their chessboard corners refined on its gray frames, nothing leaving the device in between (fid_diamonds_last): a list
+        of DIAMOND_DTYPE arrays, one per frame, in the order of the diamonds' first markers.  square_marker_rate: square_len /
+        marker_len of the print (default: marker_gen's sheet); max_rep_rate: the matching tolerance in marker sides (default 1.0:
+        markers of about 30 px and more); cap: the caller's room per frame."""
+        o = self._diamond_opts(square_marker_rate, max_rep_rate, refine)
+        cap = int(cap)
+        F = max(self._last_frames, 1)
+        out = np.zeros(F * max(cap, 1), DIAMOND_DTYPE)
+        n = np.zeros(F, np.int32)
+        self.last_diamond_counts = n
+        self._check(self._L.fid_diamonds_last(self._ctx, C.byref(o), out.ctypes.data, cap, n.ctypes.data))
+        return [out[f * cap:f * cap + int(n[f])].copy() for f in range(self._last_frames)]
+
+    def diamonds_detect(self, corners, ids, image, square_marker_rate: float | None = None, max_rep_rate: float | None = None,
+                        refine: bool = True, cap: int = _lib.DIAMOND_MAX_PER_FRAME) -> np.ndarray:
+        """diamonds_last's kernels on markers (corners (n, 4, 2), ids (n,), in list order) and a mono8 image from host memory
+        (fid_diamonds_detect): one DIAMOND_DTYPE array."""
+        o = self._diamond_opts(square_marker_rate, max_rep_rate, refine)
+        cap = int(cap)
+        ids = np.asarray(ids, np.int32).reshape(-1)
+        mk = np.zeros(len(ids), _MARKER_DT)
+        mk["id"] = ids
+        mk["corners"] = np.asarray(corners, np.float32).reshape(len(ids), 8)
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise FidError(_lib.FID_E_INVALID_ARG, "diamonds_detect takes a mono8 image (H, W) uint8")
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        out = np.zeros(max(cap, 1), DIAMOND_DTYPE)
+        n = C.c_int32(0)
+        self.last_diamond_counts = n
+        self._check(self._L.fid_diamonds_detect(self._ctx, C.byref(o), mk.ctypes.data if len(mk) else None, len(mk), img.ctypes.data, img.shape[1],
+                                                img.shape[0], img.strides[0], out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def diamond_pose(self, diamonds, square_len: float, K=None, D=None, camera=None) -> PoseResult:
+        """The diamonds as fiducials of side square_len centred on their middle squares (fid_diamond_pose_cam: fid_pose_cam on
+        {ids[0], corners}): DIAMOND_DTYPE records in, a PoseResult out."""
+        cam = _camera.resolve(K, D, camera)
+        if cam is None:
+            raise ValueError("a pose needs K, D or camera=")
+        d = np.ascontiguousarray(diamonds, dtype=DIAMOND_DTYPE).reshape(-1)
+        out = (FidPoseOut * max(len(d), 1))()
+        self._check(self._L.fid_diamond_pose_cam(self._ctx, C.byref(cam.c), d.ctypes.data if len(d) else None, len(d), float(square_len), out))
+        return _poses_to_result(out, len(d))
 
     # -- calibration ------------------------------------------------------------------------------
     def _calib_setup(self, who, model, free, start, fix_aspect, max_iter, eps, min_items):

@@ -10,6 +10,7 @@ white), as a self-contained SVG (`gen_svg`) or as one page of a multi-page vecto
     python -m fiducials_amd.marker_gen 100 112 markers.pdf [dictionary=7] [--paper-size letter|a4]
     python -m fiducials_amd.marker_gen 100 112 outdir/ --svg
     python -m fiducials_amd.marker_gen 0 0 board.pdf --charuco 5x4:40:24     (a ChArUco board, markers 0 .. 9)
+    python -m fiducials_amd.marker_gen 0 0 diamond.pdf --diamond 0,1,1,2  (a ChArUco diamond of those four markers)
 """
 from __future__ import annotations
 
@@ -196,9 +197,25 @@ def charuco_sheet_layout(board, d: Dictionary, paper_size, allow_fillers: bool =
     return [page(r) for r in black], [page(r) for r in white], texts
 
 
+def diamond_sheet_layout(diamond, d: Dictionary, paper_size, allow_fillers: bool = False):
+    """A ChArUco diamond (fiducials_amd.charuco.CharucoDiamond) as one page -- the reference's drawCharucoDiamond: the sheet of its 3 x 3
+    board, drawn from the diamond's own object points, under a label of its own."""
+    black, white, texts = charuco_sheet_layout(diamond, d, paper_size, allow_fillers)
+    x, y, size, _ = texts[0]
+    label = "ChArUco diamond %s, square %.2f mm, marker %.2f mm D%d: check the square size after printing." % (
+        ",".join(str(int(i)) for i in diamond.ids), diamond.square_len * 1000.0, diamond.marker_len * 1000.0, _dicno_of(d))
+    return black, white, [(x, y, size, label)]
+
+
+def _sheet_layout(board, d, paper_size, allow_fillers):
+    from .charuco import CharucoDiamond
+
+    return (diamond_sheet_layout if isinstance(board, CharucoDiamond) else charuco_sheet_layout)(board, d, paper_size, allow_fillers)
+
+
 def gen_charuco_svg(board, dicno: int = 7, paper_size=PAPER["letter"], allow_fillers: bool = False) -> str:
     d = get_predefined_dictionary(dicno, allow_fillers=allow_fillers)
-    black, white, texts = charuco_sheet_layout(board, d, paper_size, allow_fillers)
+    black, white, texts = _sheet_layout(board, d, paper_size, allow_fillers)
     pw, ph = paper_size
     out = ['<svg width="%gmm" height="%gmm" viewBox="0 0 %g %g" version="1.1" xmlns="http://www.w3.org/2000/svg">' % (pw, ph, pw, ph)]
     for x, y, w, h in black:
@@ -214,7 +231,7 @@ def gen_charuco_svg(board, dicno: int = 7, paper_size=PAPER["letter"], allow_fil
 def write_charuco_pdf(path: str, board, dicno: int = 7, paper_size=PAPER["letter"], allow_fillers: bool = False) -> None:
     """The sheet as a one-page vector PDF."""
     d = get_predefined_dictionary(dicno, allow_fillers=allow_fillers)
-    black, white, texts = charuco_sheet_layout(board, d, paper_size, allow_fillers)
+    black, white, texts = _sheet_layout(board, d, paper_size, allow_fillers)
     k = 72 / 25.4
     ph = paper_size[1]
     c = ["0 g"] + ["%.3f %.3f %.3f %.3f re f" % (x * k, (ph - y - h) * k, w * k, h * k) for x, y, w, h in black]
@@ -237,16 +254,28 @@ def main(argv=None) -> int:
                          "is only read back by this repository's own tables)")
     ap.add_argument("--charuco", metavar="SXxSY:SQUARE_MM:MARKER_MM",
                     help="one ChArUco board instead of single markers, e.g. 5x4:40:24; its markers are startId, startId + 1, ... (endId is not read)")
+    ap.add_argument("--diamond", metavar="ID0,ID1,ID2,ID3[:SQUARE_MM:MARKER_MM]",
+                    help="one ChArUco diamond instead of single markers, e.g. 0,1,1,2 (squares of 40 mm, markers of 24 mm) or "
+                         "0,1,1,2:50:30; startId and endId are not read")
     a = ap.parse_args(argv)
-    if a.charuco:
-        from .charuco import CharucoBoard
+    if a.charuco or a.diamond:
+        from .charuco import CharucoBoard, CharucoDiamond
 
-        size, square, marker = a.charuco.split(":")
-        sx, sy = size.lower().split("x")
-        board = CharucoBoard(int(sx), int(sy), float(square) / 1000.0, float(marker) / 1000.0, a.startId)
+        if a.diamond:
+            parts = a.diamond.split(":")
+            if len(parts) not in (1, 3):
+                ap.error("--diamond takes ID0,ID1,ID2,ID3 or ID0,ID1,ID2,ID3:SQUARE_MM:MARKER_MM")
+            square, marker = parts[1:] if len(parts) == 3 else ("40", "24")
+            board = CharucoDiamond([int(i) for i in parts[0].split(",")], float(square) / 1000.0, float(marker) / 1000.0)
+            name = "diamond%s.svg" % "_".join(str(int(i)) for i in board.ids)
+        else:
+            size, square, marker = a.charuco.split(":")
+            sx, sy = size.lower().split("x")
+            board = CharucoBoard(int(sx), int(sy), float(square) / 1000.0, float(marker) / 1000.0, a.startId)
+            name = "charuco%d.svg" % a.startId
         if a.svg:
             os.makedirs(a.out, exist_ok=True)
-            with open(os.path.join(a.out, "charuco%d.svg" % a.startId), "w") as fh:
+            with open(os.path.join(a.out, name), "w") as fh:
                 fh.write(gen_charuco_svg(board, a.dictionary, PAPER[a.paper_size], a.allow_fillers))
         else:
             write_charuco_pdf(a.out, board, a.dictionary, PAPER[a.paper_size], a.allow_fillers)

@@ -522,3 +522,89 @@ def make_charuco_frame(d: Dictionary, board, K, R, t, seed: int, width: int = 64
 
     return CharucoFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), R, _rot_to_rvec(R), t, proj(board.corner_object_points),
                         proj(board.marker_object_points.reshape(-1, 3)).reshape(-1, 4, 2))
+
+
+@dataclass
+class DiamondFrame:
+    image: np.ndarray          # (H, W) uint8
+    diamonds: list             # per diamond: (CharucoDiamond, R, t)
+    corners_image: np.ndarray  # (n_diamonds, 4, 2) the chessboard corners' true projections, in the order of fid_diamond.corners
+    markers_image: np.ndarray  # (n_diamonds, 4, 4, 2) the diamonds' marker corners' true projections
+    loose_ids: np.ndarray      # (n_loose,)
+    loose_image: np.ndarray    # (n_loose, 4, 2) the loose markers' corners' true projections
+
+
+class _LooseMarker:
+    """One marker on a white sheet of its own, in the terms a sheet is rendered from (a board of one white square)."""
+
+    def __init__(self, marker_id: int, marker_len: float):
+        self.squares_x = self.squares_y = 1
+        self.square_len, self.marker_len = 1.5 * marker_len, float(marker_len)
+        self.ids = np.array([marker_id], np.int32)
+        self.n_markers = 1
+        self.marker_at = np.zeros((1, 1), np.int64)
+        lo, hi = 0.25 * marker_len, 1.25 * marker_len
+        self.marker_object_points = np.array([[[lo, hi, 0.0], [hi, hi, 0.0], [hi, lo, 0.0], [lo, lo, 0.0]]])
+
+
+def make_diamond_frame(d: Dictionary, diamonds, K, seed: int, loose=(), width: int = 640, height: int = 480, noise_sigma: float = 2.0,
+                       border_bits: int = 1, margin: float = 0.25) -> DiamondFrame:
+    """Several ChArUco diamonds and loose markers seen by one pinhole camera.  diamonds: (CharucoDiamond, R, t) triples, the
+    diamond's frame in the camera frame; loose: (id, marker_len, R, t), the frame of a marker_len sheet corner in the camera frame.
+    Every sample is classified from the sheet's own object points, as make_charuco_frame does it, and grey levels, background, blur and
+    noise are that function's; where sheets overlap the later one lies on top."""
+    rng = np.random.default_rng(seed)
+    K = np.asarray(K, float).reshape(3, 3)
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float32)
+    gdir, gamp, phase = rng.uniform(0, 2 * np.pi), rng.uniform(10, 30), rng.uniform(0, 2 * np.pi)
+    bg = (128.0 + gamp * np.sin((np.cos(gdir) * xx / width + np.sin(gdir) * yy / height) * np.pi + phase)).astype(np.float32)
+    ss = 3
+    sub = (np.arange(ss) + 0.5) / ss - 0.5
+    PX, PY = np.meshgrid((np.arange(width)[:, None] + sub[None, :]).reshape(-1), (np.arange(height)[:, None] + sub[None, :]).reshape(-1))
+    xn, yn = (PX - K[0, 2]) / K[0, 0], (PY - K[1, 2]) / K[1, 1]
+    ncell = d.marker_size + 2 * border_bits
+    covered = np.zeros(PX.shape, bool)
+    val = np.zeros(PX.shape, np.float32)
+    sheets = [(b, np.asarray(R, float).reshape(3, 3), np.asarray(t, float).reshape(3)) for b, R, t in diamonds]
+    sheets += [(_LooseMarker(int(i), float(m)), np.asarray(R, float).reshape(3, 3), np.asarray(t, float).reshape(3)) for i, m, R, t in loose]
+    for board, R, t in sheets:
+        Hi = np.linalg.inv(np.stack([R[:, 0], R[:, 1], t], axis=1))  # normalised image -> sheet plane (X, Y, 1)
+        den = Hi[2, 0] * xn + Hi[2, 1] * yn + Hi[2, 2]
+        U = (Hi[0, 0] * xn + Hi[0, 1] * yn + Hi[0, 2]) / den
+        V = (Hi[1, 0] * xn + Hi[1, 1] * yn + Hi[1, 2]) / den
+        s = board.square_len
+        mg = margin * s
+        sheet = (U >= -mg) & (U < board.squares_x * s + mg) & (V >= -mg) & (V < board.squares_y * s + mg) & (den * np.sign(Hi[2, 2]) > 0)
+        qx, qy = np.floor(U / s).astype(np.int64), np.floor(V / s).astype(np.int64)
+        on_board = sheet & (qx >= 0) & (qx < board.squares_x) & (qy >= 0) & (qy < board.squares_y)
+        qxc, qyc = np.clip(qx, 0, board.squares_x - 1), np.clip(qy, 0, board.squares_y - 1)
+        mk = np.where(on_board, board.marker_at[qyc, qxc], -1)
+        white = ~on_board | (mk >= 0)  # (the squares that carry a marker are the white ones)
+        cells = np.stack([draw_marker(d, int(i), ncell, border_bits) > 0 for i in board.ids])
+        mkc = np.clip(mk, 0, None)
+        c0, c2 = board.marker_object_points[:, 0], board.marker_object_points[:, 2]
+        mu = (U - c0[mkc, 0]) / (c2[mkc, 0] - c0[mkc, 0]) * ncell
+        mv = (c0[mkc, 1] - V) / (c0[mkc, 1] - c2[mkc, 1]) * ncell
+        in_marker = (mk >= 0) & (mu >= 0) & (mu < ncell) & (mv >= 0) & (mv < ncell)
+        cell_white = cells[mkc, np.clip(np.floor(mv).astype(np.int64), 0, ncell - 1), np.clip(np.floor(mu).astype(np.int64), 0, ncell - 1)]
+        white = np.where(in_marker, cell_white, white)
+        val = np.where(sheet, np.where(white, 230.0, 25.0), val).astype(np.float32)
+        covered |= sheet
+    cnt = covered.reshape(height, ss, width, ss).sum(axis=(1, 3)).astype(np.float32)
+    col = (val * covered).reshape(height, ss, width, ss).sum(axis=(1, 3)).astype(np.float32)
+    cov = cnt / (ss * ss)
+    img = bg * (1 - cov) + np.where(cnt > 0, col / np.maximum(cnt, 1), 0) * cov
+    img = _blur(img.astype(np.float32), 0.8)
+    if noise_sigma > 0:
+        img = img + rng.normal(0.0, noise_sigma, size=img.shape).astype(np.float32)
+
+    def proj(P, R, t):
+        Pc = np.asarray(P, float).reshape(-1, 3) @ R.T + t
+        return np.stack([K[0, 0] * Pc[:, 0] / Pc[:, 2] + K[0, 2], K[1, 1] * Pc[:, 1] / Pc[:, 2] + K[1, 2]], axis=1)
+
+    nd = len(diamonds)
+    return DiamondFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), [(b, R, t) for b, R, t in sheets[:nd]],
+                        np.array([proj(b.record_object_points, R, t) for b, R, t in sheets[:nd]]).reshape(-1, 4, 2),
+                        np.array([proj(b.marker_object_points, R, t) for b, R, t in sheets[:nd]]).reshape(-1, 4, 4, 2),
+                        np.array([b.ids[0] for b, _, _ in sheets[nd:]], np.int32),
+                        np.array([proj(b.marker_object_points, R, t) for b, R, t in sheets[nd:]]).reshape(-1, 4, 2))

@@ -921,6 +921,82 @@ fid_status fid_calibrate_charuco(fid_ctx *ctx, const fid_charuco_corner *corners
                                  int32_t cap_per_view, int32_t image_w, int32_t image_h, const fid_calib_opts *opts, fid_camera *cam_io,
                                  fid_calib_out *out, fid_calib_view *views);
 
+/* ---- ChArUco diamonds (additions to ABI 7: entry points and structs only).  A diamond is four markers around one chessboard square:
+ * the footprint of one large fiducial, the identity of four ids, and four corners that are saddle points.  cv::aruco::
+ * detectCharucoDiamond (OpenCV 4.2 charuco.cpp) on the markers of a frame: the search for the diamonds among them, their chessboard
+ * corners, the refinement, and the pose of a diamond as a fiducial.  A context needs no board and no map; one that never asks
+ * allocates and launches nothing of it.
+ *
+ * The layout L(rate), rate = opts.square_marker_rate, is the 3 x 3 fid_charuco_board above with marker_len = 1, square_len = rate:
+ * its markers k = 0 .. 3 lie in the squares (1,0), (0,1), (2,1), (1,2), its chessboard corners are i = 0 .. 3, its object points and
+ * nearest-marker tables are that board's (every coordinate rounded through float).  Ids play no part in the matching: the dictionary
+ * is not consulted and a diamond may repeat an id.
+ *
+ * Per frame, on the marker list in list order (n markers; a list of more than FID_DIAMOND_MAX_MARKERS is FID_E_UNSUPPORTED):
+ *  1. Proposals, every marker a on its own.  H_a = the homography from layout marker 0's four plane corners to a's image corners, by
+ *     the closed form of rule 2 above; none (or not finite): a proposes nothing.  side_a = the mean of a's four side lengths (the
+ *     difference in float, the norm in double, the four summed in corner order and divided by 4 in double);
+ *     tol_a = max_rep_rate * side_a.  For k = 1, 2, 3: q_k = layout marker k's four corners through H_a, each coordinate rounded to
+ *     float.  For every j != a: d2(k, j) = max over c = 0 .. 3 of dx^2 + dy^2, (dx, dy) = q_k[c] - corners_j[c] taken in float and
+ *     squared and summed in double -- the same corner order only (OpenCV's checkAllOrders = false).  m_k = the j of smallest d2(k, j),
+ *     the lower j on a tie.  The proposal (a, m_1, m_2, m_3) is VALID when every d2(k, m_k) < tol_a^2 (both sides in double: the test
+ *     d < tol_a made on the squares) and m_1, m_2, m_3 are three different markers.
+ *  2. Resolution, serial in list order: a founds a diamond when a is unassigned, its proposal is valid, and m_1, m_2, m_3 are
+ *     unassigned; the four then become assigned.  At most FID_DIAMOND_MAX_PER_FRAME diamonds are founded in a frame (four markers
+ *     each: the list's bound admits no more).
+ *     DEPARTURE: OpenCV (refineDetectedMarkers, greedy and serial) offers each anchor only the still-unassigned markers and so falls
+ *     back to a second-closest candidate where the closest is taken.  Here the proposals do not depend on the order, which is what
+ *     lets them run in parallel; only this pass is serial.
+ *  3. Positions: each of the four markers gets the rule-2 homography from its OWN layout corners; chessboard corner i goes through
+ *     those of its two nearest markers, each result rounded to float; both belong to the diamond, so the position is (p0 + p1) / 2
+ *     in float.  Window: rule 3.  Selection: rule 4 with both markers required, which leaves 2 <= x < W - 2, 2 <= y < H - 2.  A
+ *     diamond with any corner not selected is not reported; its markers stay assigned.
+ *  4. Refinement, opts.refine != 0: rule 5 on the gray frame from every position with its own window -- the sequential cornerSubPix
+ *     bit for bit.  opts.refine == 0: corners = corners0.
+ *  5. Record, one fid_diamond per reported diamond, in the order of the anchors: corners = chessboard corners 2, 3, 1, 0 -- the order
+ *     of a marker's corners, so the diamond poses as a fiducial of side square_len centred on the middle square; ids = (id_a, id_m1,
+ *     id_m2, id_m3); index = the four list positions; corners0 = the positions before refinement; win = the four windows, in the
+ *     order of corners.
+ *
+ * max_rep_rate, default 1.0: measured on the CPU with an exact homography (6 000 random poses, tilt up to 0.6 rad, any roll, marker
+ * sides of 12 to 50 px, corner noise +-0.3 px, rate = 0.04 / 0.024; tests/test_diamond_restatement.py repeats it with a fixed seed):
+ * the right partner's d / side_a reaches 0.58 for markers of 30 - 50 px side, 0.91 at 20 - 30 px and 2.17 below 20 px, while the
+ * closest WRONG partner inside the diamond never came below 1.72.  (An earlier run of the same design, with other samples, gave
+ * 0.57, 1.16, 1.83 and 1.67.)  So 1.0 separates the two for markers of about 30 px and more; SMALLER MARKERS NEED A LARGER VALUE,
+ * at the price of that separation.  OpenCV's own constant (minRepDistanceRate = 1.302455 on the root of the four squared sides'
+ * sum: about 2.6 sides) is looser still. */
+#define FID_DIAMOND_MAX_PER_FRAME 64
+#define FID_DIAMOND_MAX_MARKERS 256
+typedef struct fid_diamond_opts {
+    double square_marker_rate; /* square_len / marker_len, > 1 [no default: the print decides] */
+    double max_rep_rate;       /* [1.0] */
+    int32_t refine;            /* [1] */
+    int32_t reserved0;
+} fid_diamond_opts;
+/* square_marker_rate = 0.04 / 0.024 (marker_gen's sheet), max_rep_rate = 1.0, refine = 1 */
+void fid_default_diamond_opts(fid_diamond_opts *opts);
+typedef struct fid_diamond {
+    int32_t ids[4];
+    int32_t index[4];
+    float corners[8];  /* x0,y0 .. x3,y3: refined (opts.refine) chessboard corners 2, 3, 1, 0 */
+    float corners0[8]; /* before refinement */
+    int32_t win[4];
+} fid_diamond;
+/* every frame of the last fid_detect* / fid_collect, on the markers and gray frames where they lie: fid_charuco_last_cam's contract
+ * (frame f's diamonds start at out[f * cap_per_frame]; FID_E_CAPACITY with the count still reported).  FID_E_INVALID_ARG, the
+ * last-error text naming the bound: a rate that is not finite or <= 1, max_rep_rate not finite or <= 0, a NULL opts, out (with
+ * cap_per_frame > 0) or n_per_frame, a batch in flight, no last call.  FID_E_UNSUPPORTED: a context whose max_markers_per_frame
+ * exceeds FID_DIAMOND_MAX_MARKERS. */
+fid_status fid_diamonds_last(fid_ctx *ctx, const fid_diamond_opts *opts, fid_diamond *out, int32_t cap_per_frame, int32_t *n_per_frame);
+/* the same kernels on n markers and a mono8 image from host memory (stride_bytes >= width; within the context's frame limits); the
+ * last detect call's results stay as they are */
+fid_status fid_diamonds_detect(fid_ctx *ctx, const fid_diamond_opts *opts, const fid_marker *markers, int32_t n, const uint8_t *img,
+                               int32_t width, int32_t height, int32_t stride_bytes, fid_diamond *out, int32_t cap, int32_t *n_out);
+/* the diamonds as fiducials of side square_len: the bytes fid_pose_cam gives for the markers {ids[0], corners} with
+ * len_per_marker = square_len -- a thin entry over that road, no kernel of its own */
+fid_status fid_diamond_pose_cam(fid_ctx *ctx, const fid_camera *cam, const fid_diamond *diamonds, int32_t n, double square_len,
+                                fid_pose_out *out);
+
 /* aruco.cpp _refineCandidateLines on its own (what CORNER_REFINE_CONTOUR does to every marker inside fid_detect*): n markers,
  * contour i = points [offsets[i], offsets[i + 1]) of pts_xy (int32 x, y pairs in cv::findContours order, CHAIN_APPROX_NONE;
  * offsets[0] = 0), corners = 8 floats per marker, in: the quad (its corners are contour points), out: the crossings of the
