@@ -168,7 +168,7 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_start(const fid_marker *__restr
                 s.Mxy[p][1] = (float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
             }
             SR_LDS_SYNC();
-            if (mp_homography_dlt(&s, npts, lane, h) && cal_focal_rows(h, cx0, cy0, c6)) flags |= 2;
+            if (pnp_homography_dlt(MpView{&s, found}, npts, lane, h) && cal_focal_rows(h, cx0, cy0, c6)) flags |= 2;
         }
     }
     if (lane == 0) {

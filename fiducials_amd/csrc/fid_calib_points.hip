@@ -150,7 +150,7 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_calib_start_pts(const fid_charuco_cor
                 s.p.Mxy[p][1] = (float)(Rt[3] * s.p.obj[p][0] + Rt[4] * s.p.obj[p][1] + tt[1]);
             }
             SR_LDS_SYNC();
-            if (ch_homography_dlt(&s.p, n, lane, h) && cal_focal_rows(h, cx0, cy0, c6)) flags |= 2;
+            if (pnp_homography_dlt(ChPoseView{&s.p}, n, lane, h) && cal_focal_rows(h, cx0, cy0, c6)) flags |= 2;
         }
     }
     if (lane == 0) {

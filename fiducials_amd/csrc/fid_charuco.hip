@@ -14,8 +14,9 @@
 //       prefix count.
 // k_charuco_subpix, one wave per (frame, kept corner): k_subpix's arithmetic with the item's own window (at most 10) -- the same tap
 // order, the same five accumulators summed each by its own lane -- so the float corner is the sequential cornerSubPix bit for bit.
-// k_charuco_pose, one wave per frame: k_map_pose's stages (2)-(4) on single points: residuals strided over the lanes, per-lane partial
-// sums in residual order, one xor butterfly.
+// k_charuco_pose, one wave per frame: its own exits (few corners, one line, a corner beyond the model) and point load, then fid_pnp.h's
+// pnp_wave_solve -- the solve of k_map_pose -- over ChPoseView, single points with z = 0: a planar-only view, so the planarity test and
+// the start of a set that is not coplanar are not compiled.
 #include <algorithm>
 
 #define CH_MAX_MARKERS FID_MAP_MAX_USED
@@ -383,55 +384,29 @@ struct ChPoseLds {
     double A[81], V[81];
 };
 
-// HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS, summed as k_map_pose sums them
-// (strided per-lane partial sums, one butterfly per entry); every lane returns the same H
-__device__ bool ch_homography_dlt(ChPoseLds *s, int n, int lane, double H[9])
-{
-    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
-    for (int i = lane; i < n; i += 64) {
-        cmx += s->mn[i][0];
-        cmy += s->mn[i][1];
-        cMx += s->Mxy[i][0];
-        cMy += s->Mxy[i][1];
+// fid_pnp.h's view of the corners: the tables as they stand, z = 0 on the board (a planar-only view: no markers, no areas)
+struct ChPoseView {
+    ChPoseLds *s;
+    static constexpr bool PLANAR_ONLY = true;
+    __device__ __forceinline__ void obj(int i, double M[3]) const
+    {
+        M[0] = s->obj[i][0];
+        M[1] = s->obj[i][1];
+        M[2] = 0.;
     }
-    cmx = wave_sum_f64(cmx) / n; cmy = wave_sum_f64(cmy) / n; cMx = wave_sum_f64(cMx) / n; cMy = wave_sum_f64(cMy) / n;
-    for (int i = lane; i < n; i += 64) {
-        smx += fabs(s->mn[i][0] - cmx);
-        smy += fabs(s->mn[i][1] - cmy);
-        sMx += fabs(s->Mxy[i][0] - cMx);
-        sMy += fabs(s->Mxy[i][1] - cMy);
-    }
-    smx = wave_sum_f64(smx); smy = wave_sum_f64(smy); sMx = wave_sum_f64(sMx); sMy = wave_sum_f64(sMy);
-    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
-    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
-    for (int j = 0; j < 9; j++)
-        for (int k = j; k < 9; k++) {
-            double acc = 0;
-            for (int i = lane; i < n; i += 64) {
-                const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
-                const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
-                double lxj, lyj, lxk, lyk;
-                pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
-                pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
-                acc += lxj * lxk + lyj * lyk;
-            }
-            acc = wave_sum_f64(acc);
-            if (lane == 0) {
-                s->A[j * 9 + k] = acc;
-                s->A[k * 9 + j] = acc;
-            }
-        }
-    return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
-}
+    __device__ __forceinline__ double img(int i, int c) const { return s->img[i][c]; }
+    __device__ __forceinline__ float mn(int i, int c) const { return s->mn[i][c]; }
+    __device__ __forceinline__ float *Mxy(int i) const { return s->Mxy[i]; }
+    __device__ __forceinline__ double *A() const { return s->A; }
+    __device__ __forceinline__ double *V() const { return s->V; }
+};
 
 __device__ __forceinline__ void ch_pose_none(fid_charuco_pose_out *o, int n, int status)
 {
     fid_charuco_pose_out r;
     r.n_corners = n;
     r.status = status;
-    for (int i = 0; i < 3; i++) r.rvec[i] = r.tvec[i] = r.cam_t[i] = 0.;
-    for (int i = 0; i < 9; i++) r.R[i] = r.cam_R[i] = 0.;
-    r.image_error = 0.;
+    pnp_pose_record_zero(r, 0.);
     *o = r;
 }
 
@@ -505,103 +480,14 @@ __global__ __launch_bounds__(64) void k_charuco_pose(const fid_charuco_corner *_
             return;
         }
     }
-    // ---- (2) the centred scatter matrix of the object points and its eigenvectors: the plane's frame (every lane the same)
-    double Mc[3] = {0, 0, 0}, Wv[3], Vt[3][3];
-    {
-        for (int p = lane; p < n; p += 64) {
-            Mc[0] += s.obj[p][0];
-            Mc[1] += s.obj[p][1];
-        }
-        for (int a = 0; a < 2; a++) Mc[a] = wave_sum_f64(Mc[a]) / n;
-        double m3[3] = {0, 0, 0};
-        for (int p = lane; p < n; p += 64) {
-            const double d0 = s.obj[p][0] - Mc[0], d1 = s.obj[p][1] - Mc[1];
-            m3[0] += d0 * d0; m3[1] += d0 * d1; m3[2] += d1 * d1;
-        }
-        for (int i = 0; i < 3; i++) m3[i] = wave_sum_f64(m3[i]);
-        double MM[3][3] = {{m3[0], m3[1], 0.}, {m3[1], m3[2], 0.}, {0., 0., 0.}};
-        pnp_scatter_eig(MM, Wv, Vt);
-    }
-    // ---- (3) the start: the points turned into their plane, the DLT homography over all of them
-    double param[6] = {0, 0, 0, 0, 0, 0};
-    {
-        double Rt[9], tt[3];
-        pnp_plane_frame(Vt, Mc, Rt, tt);
-        for (int p = lane; p < n; p += 64) {
-            s.Mxy[p][0] = (float)(Rt[0] * s.obj[p][0] + Rt[1] * s.obj[p][1] + tt[0]);
-            s.Mxy[p][1] = (float)(Rt[3] * s.obj[p][0] + Rt[4] * s.obj[p][1] + tt[1]);
-        }
-        SR_LDS_SYNC();
-        double h[9], R[9];
-        if (ch_homography_dlt(&s, n, lane, h)) {
-            double t3[3];
-            pnp_pose_from_h(h, t3);
-            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
-            pnp_mul3(h, Rt, R);
-        } else {
-            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
-        }
-        rodrigues_m2v(R, param);
-    }
-    // ---- (4) CvLevMarq over the 2 n residuals: lane l owns residuals l, l + 64, ... (residual r: point r / 2, coordinate r % 2)
-    const int nres = 2 * n;
-    double S[21], gJ[6], e2 = 0;
-    bool needJ = true;
-    LevMarq lm;
-    do {
-        double Sp[21], gp[6];
-        e2 = 0;
-        for (int i = 0; i < 21; i++) Sp[i] = 0.;
-        for (int i = 0; i < 6; i++) gp[i] = 0.;
-        for (int r = lane; r < nres; r += 64) {
-            const int p = r >> 1, sel = r & 1;
-            const double M[3] = {s.obj[p][0], s.obj[p][1], 0.};
-            double Jrow[6];
-            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
-            e2 += err * err;
-            if (needJ) {
-                int idx = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
-                    gp[a] += Jrow[a] * err;
-                }
-            }
-        }
-        if (needJ) {
-#pragma unroll
-            for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
-#pragma unroll
-            for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
-        }
-    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(e2); }, needJ));
-    // ---- the reprojection error over the corners: projections rounded to float, sum |d|^2 / n
-    double tot = 0;
-    for (int p = lane; p < n; p += 64) {
-        const double M[3] = {s.obj[p][0], s.obj[p][1], 0.};
-        double Jrow[6];
-        const double dx = s.img[p][0] - (double)(float)project_one<MODEL>(M, param, K, kd, 0, Jrow, false);
-        const double dy = s.img[p][1] - (double)(float)project_one<MODEL>(M, param, K, kd, 1, Jrow, false);
-        const double e = sqrt(dx * dx + dy * dy);
-        tot += e * e;
-    }
-    tot = wave_sum_f64(tot);
+    // ---- the plane's frame, the DLT start, CvLevMarq and the reprojection error over the corners
+    double param[6], image_error;
+    pnp_wave_solve<MODEL>(ChPoseView{&s}, n, lane, K, kd, param, &image_error);
     if (lane == 0) {
         fid_charuco_pose_out o;
         o.n_corners = n;
         o.status = FID_CHARUCO_POSE_OK;
-        for (int i = 0; i < 3; i++) {
-            o.rvec[i] = param[i];
-            o.tvec[i] = param[3 + i];
-        }
-        double dummy[27];
-        rodrigues_v2m(param, o.R, dummy, false);
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) o.cam_R[3 * i + j] = o.R[3 * j + i];
-            o.cam_t[i] = -(o.R[i] * param[3] + o.R[3 + i] * param[4] + o.R[6 + i] * param[5]);
-        }
-        o.image_error = tot / n;
+        pnp_pose_record(o, param, image_error);
         out[f] = o;
     }
 }

@@ -1,24 +1,21 @@
 // fid_map_pose.hip -- one camera pose per frame from a map of fiducials (fid_abi.h).  Part of the fid_api.hip translation unit,
-// behind fid_stag.hip.  solvePnP's pieces -- the starts, the projection, CvLevMarq -- come from fid_pnp.h.
+// behind fid_stag.hip.  The solve itself -- planarity, the start, CvLevMarq, the reprojection error -- is fid_pnp.h's wave-strided
+// pnp_wave_solve, which k_map_pose_robust and k_charuco_pose run as well; this file gathers the points it runs on.
 //
 // ------------------------------------------------------------------------------------------------ K19: map pose
 // cv::aruco::estimatePoseBoard: cv::solvePnP (ITERATIVE) over the four corners of every marker of a frame that the map names.
 // One wave per frame (blockIdx.x: a batch is one launch):
-//   (1) gather.  Lanes take the markers of the frame's list 64 at a time and binary-search the id in the map's sorted id table.
-//       A first pass marks every map entry that is hit (a bit per entry in LDS, set with an atomic or; a second hit sets the entry's
-//       bit in a second table): an id that occurs more than once in the frame is left out altogether.  The second pass compacts the
-//       survivors in list order (ballot + prefix count) and stops filling at MP_MAX_USED; the rest are counted.  Object points (the
-//       map's, double) and image points (the float corners widened) go to LDS, with the undistorted image point rounded to float
-//       (findHomography's input) and the marker's image area.
-//   (2) planarity: cvFindExtrinsicCameraParams2's test, the eigenvalues of the centred scatter matrix -- per-lane partial sums over
-//       the lane's points (p = lane, lane + 64, ...), then one xor butterfly per entry.
-//   (3) the start.  Coplanar: the points turned into their plane, the DLT homography over all of them with the float-input
-//       normalisation of HomographyEstimatorCallback::runKernel; each of the 45 entries of the 9 x 9 is a strided partial sum per
-//       lane and a butterfly.  Not coplanar: the closed-form pose of the used marker with the largest image area (the first of equals)
-//       composed with that marker's place in the map (OpenCV runs a 12 x 12 DLT there; the start is unpinned).
-//   (4) CvLevMarq (fid_pnp.h's LevMarq, as in k_pose), the camera model's distortion (the template parameter) in the projection and its Jacobian.  The 2 P residuals are strided over the 64 lanes; J^T J (21), J^T e (6) and |e|^2 are
-//       per-lane partial sums in residual order followed by one xor butterfly: a fixed order, reproducible from run to run, the same
-//       value in every lane.
+//   (1) gather (mp_gather, shared with k_map_pose_robust).  Lanes take the markers of the frame's list 64 at a time and binary-search
+//       the id in the map's sorted id table.  A first pass marks every map entry that is hit (a bit per entry in LDS, set with an
+//       atomic or; a second hit sets the entry's bit in a second table): an id that occurs more than once in the frame is left out
+//       altogether.  The second pass compacts the survivors in list order (ballot + prefix count) and stops filling at MP_MAX_USED;
+//       the rest are counted.  Then the points (mp_load_points): object points (the map's, double) and image points (the float
+//       corners widened) go to LDS, with the undistorted image point rounded to float (findHomography's input) and the marker's
+//       image area.
+//   (2)-(4) pnp_wave_solve over MpView, the tables as they stand: planarity, the DLT start of a coplanar set or the largest marker's
+//       closed-form pose, CvLevMarq with the camera model's distortion (the template parameter), the reprojection error.  Point p is
+//       on lane p % 64; every sum is per-lane partial sums in point order followed by one xor butterfly: a fixed order, reproducible
+//       from run to run, the same value in every lane.
 // LDS: 24 KB object points + 16 KB image points (the 40 KB of 1 024 points) + 16 KB of float pairs for the DLT + 7 KB of tables.
 #include <algorithm>
 
@@ -48,70 +45,13 @@ __device__ __forceinline__ int mp_find(const int *__restrict__ ids, int n, int i
     return (lo < n && ids[lo] == id) ? lo : -1;
 }
 
-// HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn in LDS; every lane returns the same H
-__device__ bool mp_homography_dlt(MpLds *s, int n, int lane, double H[9])
+// stage (1) of k_map_pose and k_map_pose_robust: the frame's markers that the map names, in list order, without the ids seen twice,
+// as s.mk (index in the list) and s.ent (entry of the map).  Returns how many are used (at most MP_MAX_USED), *n_over: those beyond.
+__device__ __forceinline__ int mp_gather(MpLds &s, const fid_marker *__restrict__ mlist, int nm, int per_frame, const int *__restrict__ map_ids, int map_n,
+                                         int lane, int *n_over)
 {
-    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
-    for (int i = lane; i < n; i += 64) {
-        cmx += s->mn[i][0];
-        cmy += s->mn[i][1];
-        cMx += s->Mxy[i][0];
-        cMy += s->Mxy[i][1];
-    }
-    cmx = wave_sum_f64(cmx) / n; cmy = wave_sum_f64(cmy) / n; cMx = wave_sum_f64(cMx) / n; cMy = wave_sum_f64(cMy) / n;
-    for (int i = lane; i < n; i += 64) {
-        smx += fabs(s->mn[i][0] - cmx);
-        smy += fabs(s->mn[i][1] - cmy);
-        sMx += fabs(s->Mxy[i][0] - cMx);
-        sMy += fabs(s->Mxy[i][1] - cMy);
-    }
-    smx = wave_sum_f64(smx); smy = wave_sum_f64(smy); sMx = wave_sum_f64(sMx); sMy = wave_sum_f64(sMy);
-    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
-    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
-    // LtL, entry (j, k), j <= k: the lane's points in their order, then the butterfly
-    for (int j = 0; j < 9; j++)
-        for (int k = j; k < 9; k++) {
-            double acc = 0;
-            for (int i = lane; i < n; i += 64) {
-                const double x = (s->mn[i][0] - cmx) * smx, y = (s->mn[i][1] - cmy) * smy;
-                const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
-                double lxj, lyj, lxk, lyk;
-                pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
-                pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
-                acc += lxj * lxk + lyj * lyk;
-            }
-            acc = wave_sum_f64(acc);
-            if (lane == 0) {
-                s->A[j * 9 + k] = acc;
-                s->A[k * 9 + j] = acc;
-            }
-        }
-    return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
-}
-
-// COV: the covariance tail (fid_abi.h: "pose covariance") over the same points -- the selection above it is this one body's --, summed
-// as the Levenberg-Marquardt sums are; it also writes cov_cam_pose.  The COV = true form takes (double sigma_px, fid_map_pose_cov *cov)
-// as the pack CovArgs, so that the COV = false form has the parameter list it always had AND stays the kernel's own body: moved into
-// an _impl function behind two __global__ wrappers (the STag kernels' form, which they had before) the COV = false kernel came out
-// scheduled and allocated differently from the parent's.  k_map_pose_cov<MODEL> names the COV = true instantiation.
-struct MapPoseCovArgs {
-    double sigma_px;
-    fid_map_pose_cov *cov;
-};
-template <int MODEL, bool COV = false, class... CovArgs>
-__global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
-                                                  int per_frame, const int *__restrict__ map_ids, const double *__restrict__ map_obj, int map_n,
-                                                  PoseCam cam, fid_map_pose_out *__restrict__ out, CovArgs... cov_args)
-{
-    static_assert(sizeof...(CovArgs) == (COV ? 2 : 0), "k_map_pose: (sigma_px, cov) with COV, nothing without");
-    __shared__ MpLds s;
-    const int f = blockIdx.x, lane = threadIdx.x;
-    const double *K = cam.K, *kd = cam.D;
-    const fid_marker *mlist = markers + (long long)f * per_frame;
-    int nm = nmark_per_frame[(long long)f * nmark_stride_ints];
     nm = nm < 0 ? 0 : (nm > per_frame ? per_frame : nm);
     map_n = map_n > FID_MAP_MAX_ENTRIES ? FID_MAP_MAX_ENTRIES : map_n;
-    // ---- (1) the frame's markers that the map names, in list order, without the ids seen twice
     for (int e = lane; e < MP_BIT_WORDS; e += 64) s.seen[e] = s.dup[e] = 0u;
     SR_LDS_SYNC();
     for (int m0 = 0; m0 < nm; m0 += 64) {
@@ -138,28 +78,31 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         }
         found += __builtin_popcountll(hit);
     }
-    const int n_over = found > MP_MAX_USED ? found - MP_MAX_USED : 0;
-    found -= n_over;
-    if (found == 0) {
-        if (lane == 0) {
-            fid_map_pose_out o;
-            o.n_markers = 0;
-            o.n_over = 0;
-            for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = o.cam_t[i] = 0.;
-            for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
-            o.image_error = 0.;
-            out[f] = o;
-            if constexpr (COV) {
-                fid_map_pose_cov *cov = MapPoseCovArgs{cov_args...}.cov;
-                pnp_cov_zero(&cov[f].pose, 1, 0, cov[f].cov_cam_pose);
-            }
-        }
-        return;
-    }
-    SR_LDS_SYNC();
-    const int npts = 4 * found;
+    *n_over = found > MP_MAX_USED ? found - MP_MAX_USED : 0;
+    return found - *n_over;
+}
+
+// the undistorted image point of point p rounded to float (the DLT's input: findHomography converts to float); false: (u, v) lies
+// beyond the (equidistant) model
+template <int MODEL>
+__device__ __forceinline__ bool mp_store_mn(MpLds &s, int p, double u, double v, const double K[9], const double kd[12])
+{
+    double x, y;
+    const bool ok = pnp_undistort<MODEL>(K, kd, u, v, &x, &y);
+    s.mn[p][0] = (float)x;
+    s.mn[p][1] = (float)y;
+    return ok;
+}
+
+// the points of the found markers: object points (the map's, double), image points (the float corners widened), the marker's image
+// area and, with MN, mn in the same pass (k_map_pose_robust writes mn later, its counters lie there until scoring is done; a
+// pass of its own behind this one measured slower for k_map_pose).  False in a lane that met a corner beyond the model.
+template <int MODEL, bool MN>
+__device__ __forceinline__ bool mp_load_points(MpLds &s, const fid_marker *__restrict__ mlist, const double *__restrict__ map_obj, int found, int lane,
+                                               const double K[9], const double kd[12])
+{
     bool posable = true;
-    for (int p = lane; p < npts; p += 64) {
+    for (int p = lane; p < 4 * found; p += 64) {
         const int k = p >> 2, q = p & 3;
         const fid_marker *mk = mlist + s.mk[k];
         const double *src = map_obj + (size_t)s.ent[k] * 12 + q * 3;
@@ -167,11 +110,10 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
         const double u = (double)mk->corners[2 * q], v = (double)mk->corners[2 * q + 1];
         s.img[p][0] = u;
         s.img[p][1] = v;
-        double x, y;
-        const bool ok = pnp_undistort<MODEL>(K, kd, u, v, &x, &y);
-        if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = posable && ok;
-        s.mn[p][0] = (float)x;  // (the DLT's input: findHomography converts to float)
-        s.mn[p][1] = (float)y;
+        if constexpr (MN) {
+            const bool ok = mp_store_mn<MODEL>(s, p, u, v, K, kd);
+            if constexpr (MODEL == FID_CAM_EQUIDISTANT) posable = posable && ok;
+        }
         if (q == 0) {  // the marker's area in the image (shoelace over its four corners)
             double a2 = 0;
             for (int i = 0; i < 4; i++) {
@@ -181,17 +123,81 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
             s.area[k] = fabs(a2);
         }
     }
+    return posable;
+}
+
+// fid_pnp.h's view of all found markers' points: the tables as they stand
+struct MpView {
+    MpLds *s;
+    int found;
+    static constexpr bool PLANAR_ONLY = false;
+    __device__ __forceinline__ void obj(int i, double M[3]) const
+    {
+        for (int a = 0; a < 3; a++) M[a] = s->obj[i][a];
+    }
+    __device__ __forceinline__ double img(int i, int c) const { return s->img[i][c]; }
+    __device__ __forceinline__ float mn(int i, int c) const { return s->mn[i][c]; }
+    __device__ __forceinline__ float *Mxy(int i) const { return s->Mxy[i]; }
+    __device__ __forceinline__ double *A() const { return s->A; }
+    __device__ __forceinline__ double *V() const { return s->V; }
+    __device__ __forceinline__ int markers() const { return found; }
+    __device__ __forceinline__ double area(int k) const { return s->area[k]; }
+    static constexpr bool MARKER_IN_PLACE = false;
+    __device__ __forceinline__ int first(int k) const { return 4 * k; }
+};
+
+// a frame's record without a pose (no marker of the map; a corner beyond the model)
+__device__ __forceinline__ void mp_pose_none(fid_map_pose_out *dst, int n_markers, int n_over, double image_error)
+{
+    fid_map_pose_out o;
+    o.n_markers = n_markers;
+    o.n_over = n_over;
+    pnp_pose_record_zero(o, image_error);
+    *dst = o;
+}
+
+// COV: the covariance tail (fid_abi.h: "pose covariance") over the same points -- the selection above it is this one body's --: J^T J
+// from pnp_wave_residuals, the sums of the Levenberg-Marquardt loop without J^T e; it also writes cov_cam_pose.  The COV = true form
+// takes (double sigma_px, fid_map_pose_cov *cov) as the pack CovArgs, so that the COV = false form has the parameter list it always
+// had AND stays the kernel's own body: moved into an _impl function behind two __global__ wrappers (the STag kernels' form, which
+// they had before) the COV = false kernel came out scheduled and allocated differently.  What the body shares is below it, not
+// around it: the gather, the point load, the solve and the record are calls into inlined functions.  k_map_pose_cov<MODEL> names the
+// COV = true instantiation.
+struct MapPoseCovArgs {
+    double sigma_px;
+    fid_map_pose_cov *cov;
+};
+template <int MODEL, bool COV = false, class... CovArgs>
+__global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ markers, const int *__restrict__ nmark_per_frame, int nmark_stride_ints,
+                                                  int per_frame, const int *__restrict__ map_ids, const double *__restrict__ map_obj, int map_n,
+                                                  PoseCam cam, fid_map_pose_out *__restrict__ out, CovArgs... cov_args)
+{
+    static_assert(sizeof...(CovArgs) == (COV ? 2 : 0), "k_map_pose: (sigma_px, cov) with COV, nothing without");
+    __shared__ MpLds s;
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const double *K = cam.K, *kd = cam.D;
+    const fid_marker *mlist = markers + (long long)f * per_frame;
+    // ---- (1) the frame's markers that the map names
+    int n_over;
+    const int found = mp_gather(s, mlist, nmark_per_frame[(long long)f * nmark_stride_ints], per_frame, map_ids, map_n, lane, &n_over);
+    if (found == 0) {
+        if (lane == 0) {
+            mp_pose_none(out + f, 0, 0, 0.);
+            if constexpr (COV) {
+                fid_map_pose_cov *cov = MapPoseCovArgs{cov_args...}.cov;
+                pnp_cov_zero(&cov[f].pose, 1, 0, cov[f].cov_cam_pose);
+            }
+        }
+        return;
+    }
+    SR_LDS_SYNC();
+    const int npts = 4 * found;
+    const bool posable = mp_load_points<MODEL, true>(s, mlist, map_obj, found, lane, K, kd);
     SR_LDS_SYNC();
     if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
         if (__ballot(!posable) != 0ull) {  // a corner beyond the model (fid_abi.h: "a marker that cannot be posed") voids the frame's record
             if (lane == 0) {
-                fid_map_pose_out o;
-                o.n_markers = found;
-                o.n_over = n_over;
-                for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = o.cam_t[i] = 0.;
-                for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
-                o.image_error = -1.;
-                out[f] = o;
+                mp_pose_none(out + f, found, n_over, -1.);
                 if constexpr (COV) {
                     fid_map_pose_cov *cov = MapPoseCovArgs{cov_args...}.cov;
                     pnp_cov_zero(&cov[f].pose, 1, npts, cov[f].cov_cam_pose);
@@ -200,147 +206,21 @@ __global__ __launch_bounds__(64) void k_map_pose(const fid_marker *__restrict__ 
             return;
         }
     }
-    // ---- (2) planarity: the centred scatter matrix of the object points and its eigenvalues (every lane the same)
-    double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
-    {
-        for (int p = lane; p < npts; p += 64)
-            for (int a = 0; a < 3; a++) Mc[a] += s.obj[p][a];
-        for (int a = 0; a < 3; a++) Mc[a] = wave_sum_f64(Mc[a]) / npts;
-        double m6[6] = {0, 0, 0, 0, 0, 0};
-        for (int p = lane; p < npts; p += 64) {
-            const double d[3] = {s.obj[p][0] - Mc[0], s.obj[p][1] - Mc[1], s.obj[p][2] - Mc[2]};
-            m6[0] += d[0] * d[0]; m6[1] += d[0] * d[1]; m6[2] += d[0] * d[2];
-            m6[3] += d[1] * d[1]; m6[4] += d[1] * d[2]; m6[5] += d[2] * d[2];
-        }
-        for (int i = 0; i < 6; i++) m6[i] = wave_sum_f64(m6[i]);
-        double MM[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
-        pnp_scatter_eig(MM, W, Vt);
-    }
-    const bool planar = W[2] / W[1] < 1e-3;
-    // ---- (3) the start
-    double param[6] = {0, 0, 0, 0, 0, 0};
-    if (planar) {
-        double Rt[9], tt[3];
-        pnp_plane_frame(Vt, Mc, Rt, tt);
-        for (int p = lane; p < npts; p += 64) {
-            const double *src = s.obj[p];
-            s.Mxy[p][0] = (float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
-            s.Mxy[p][1] = (float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
-        }
-        SR_LDS_SYNC();
-        double h[9], R[9];
-        if (mp_homography_dlt(&s, npts, lane, h)) {
-            double t3[3];
-            pnp_pose_from_h(h, t3);
-            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
-            pnp_mul3(h, Rt, R);
-        } else {
-            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
-        }
-        rodrigues_m2v(R, param);
-    } else {
-        // the used marker with the largest image area, the first of equals: per lane over its markers, then a butterfly on (area, index)
-        int big = lane < found ? lane : 0;
-        double abig = s.area[big];
-        for (int k = lane + 64; k < found; k += 64)
-            if (s.area[k] > abig) {
-                abig = s.area[k];
-                big = k;
-            }
-        for (int mask = 1; mask < 64; mask <<= 1) {
-            const double ao = shfl_xor_f64(abig, mask);
-            const int bo = __shfl_xor(big, mask, WAVE);
-            if (ao > abig || (ao == abig && bo < big)) {
-                abig = ao;
-                big = bo;
-            }
-        }
-        const double *c0 = s.obj[4 * big], *c2 = s.obj[4 * big + 2];
-        const double cc[3] = {0.5 * (c0[0] + c2[0]), 0.5 * (c0[1] + c2[1]), 0.5 * (c0[2] + c2[2])};
-        pnp_start_largest<MODEL>(c0, s.obj[4 * big + 1], s.obj[4 * big + 3], cc, s.img + 4 * big, K, kd, param);
-    }
-    // ---- (4) CvLevMarq over the 2 * npts residuals: lane l owns residuals l, l + 64, ... (residual r: point r / 2, coordinate r % 2)
-    const int nres = 2 * npts;
-    double S[21], gJ[6], e2 = 0;
-    bool needJ = true;
-    LevMarq lm;
-    do {
-        // the residuals (and, with needJ, the normal equations) at param
-        double Sp[21], gp[6];
-        e2 = 0;
-        for (int i = 0; i < 21; i++) Sp[i] = 0.;
-        for (int i = 0; i < 6; i++) gp[i] = 0.;
-        for (int r = lane; r < nres; r += 64) {
-            const int p = r >> 1, sel = r & 1;
-            const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
-            double Jrow[6];
-            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
-            e2 += err * err;
-            if (needJ) {
-                int idx = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
-                    gp[a] += Jrow[a] * err;
-                }
-            }
-        }
-        if (needJ) {
-#pragma unroll
-            for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
-#pragma unroll
-            for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
-        }
-    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(e2); }, needJ));
-    // ---- getReprojectionError over the used points: projections rounded to float (vector<Point2f>), sum |d|^2 / P
-    double tot = 0;
-    for (int p = lane; p < npts; p += 64) {
-        const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
-        double Jrow[6];
-        const double dx = s.img[p][0] - (double)(float)project_one<MODEL>(M, param, K, kd, 0, Jrow, false);
-        const double dy = s.img[p][1] - (double)(float)project_one<MODEL>(M, param, K, kd, 1, Jrow, false);
-        const double e = sqrt(dx * dx + dy * dy);
-        tot += e * e;
-    }
-    tot = wave_sum_f64(tot);
+    // ---- (2)-(4) and the reprojection error over all of them
+    const MpView view = {&s, found};
+    double param[6], image_error;
+    pnp_wave_solve<MODEL>(view, npts, lane, K, kd, param, &image_error);
     if (lane == 0) {
         fid_map_pose_out o;
         o.n_markers = found;
         o.n_over = n_over;
-        for (int i = 0; i < 3; i++) {
-            o.rvec[i] = param[i];
-            o.tvec[i] = param[3 + i];
-        }
-        double dummy[27];
-        rodrigues_v2m(param, o.R, dummy, false);
-        for (int i = 0; i < 3; i++) {
-            for (int j = 0; j < 3; j++) o.cam_R[3 * i + j] = o.R[3 * j + i];
-            o.cam_t[i] = -(o.R[i] * param[3] + o.R[3 + i] * param[4] + o.R[6 + i] * param[5]);
-        }
-        o.image_error = tot / npts;
+        pnp_pose_record(o, param, image_error);
         out[f] = o;
     }
     if constexpr (COV) {
-        // ---- the covariance: J and e at the returned param, strided partial sums and the butterfly as above
-        double Sp[21];
-        e2 = 0;
-        for (int i = 0; i < 21; i++) Sp[i] = 0.;
-        for (int r = lane; r < nres; r += 64) {
-            const int p = r >> 1, sel = r & 1;
-            const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
-            double Jrow[6];
-            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, true) - s.img[p][sel];
-            e2 += err * err;
-            int idx = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++)
-#pragma unroll
-                for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
-        }
-#pragma unroll
-        for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
-        e2 = wave_sum_f64(e2);
+        // ---- the covariance: J and e at the returned param, summed as the Levenberg-Marquardt sums are
+        double S[21];
+        const double e2 = wave_sum_f64(pnp_wave_residuals<MODEL, false>(view, npts, lane, K, kd, param, true, S, nullptr));
         const MapPoseCovArgs ca = {cov_args...};
         if (lane == 0) pnp_covariance<true>(S, e2, npts, param, ca.sigma_px, &ca.cov[f].pose, ca.cov[f].cov_cam_pose);
     }

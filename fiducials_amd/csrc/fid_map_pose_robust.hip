@@ -3,7 +3,8 @@
 //
 // ------------------------------------------------------------------------------------------------ K20: robust map pose
 // One wave per frame (blockIdx.x: a batch is one launch):
-//   (1) gather: k_map_pose's own, into the same LDS tables -- ALL used markers stay there; a solve reads a subset through sub[].
+//   (1) gather: k_map_pose's (mp_gather, mp_load_points), into the same LDS tables -- ALL used markers stay there; a solve reads a
+//       subset through sub[].  mn is written after scoring (mp_store_mn): until then the counters of (3) lie there.
 //   (2) eligibility (a ballot per 64 markers; uniform 4 x 64 bit masks in registers from here on) and the hypotheses: the rank of
 //       every eligible marker by (area descending, k ascending), counted against the whole list; rank < 64 is a hypothesis and the
 //       rank is its lane.
@@ -13,10 +14,10 @@
 //       Mxy tables, which nothing needs yet); the bucket that holds rank (m - 1) / 2 extends the prefix.  A bucket with one member
 //       ends the search one pass later (that pass remembers the member); otherwise nine passes spell all 63 bits.  Nothing is
 //       rounded and nothing is stored per (lane, marker).
-//   (4) the winner (smallest score bits, then lowest k: a butterfly), I_0 with lanes = markers, then up to four solves.  rb_solve is
-//       stages (2)-(4) of k_map_pose and its reprojection error, statement for statement, over the subset's points in list order
-//       (point p of the subset is point 4 sub[p / 4] + p % 4 of the tables): the same operands in the same order of sums, so the
-//       record equals fid_map_pose_cam's on that subset.  k_map_pose keeps its own body (see its comment on scheduling).
+//   (4) the winner (smallest score bits, then lowest k: a butterfly), I_0 with lanes = markers, then up to four solves.  A solve is
+//       fid_pnp.h's pnp_wave_solve, the one k_map_pose runs, over RbView: the subset's points in list order (point p of the subset
+//       is point 4 sub[p / 4] + p % 4 of the tables, the largest marker is sought among the subset's): the same operands in the same
+//       order of sums, so the record equals fid_map_pose_cam's on that subset.
 // LDS: MpLds (63 760 B) + sub (256 B) + hyp (128 B).
 struct RbLds {
     MpLds m;
@@ -46,178 +47,29 @@ __device__ __forceinline__ double rb_err(const MpLds *s, int j, const double par
 
 __device__ __forceinline__ bool rb_bit(const unsigned long long m[4], int k) { return (m[k >> 6] >> (k & 63)) & 1ull; }
 
-// mp_homography_dlt over the subset: correspondence i is Mxy[i] (written in subset order) -> mn[4 sub[i / 4] + i % 4]
-__device__ bool rb_homography_dlt(RbLds *rs, int n, int lane, double H[9])
-{
-    MpLds *s = &rs->m;
-#define RB_Q(i) (4 * (int)rs->sub[(i) >> 2] + ((i) & 3))
-    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
-    for (int i = lane; i < n; i += 64) {
-        const int q = RB_Q(i);
-        cmx += s->mn[q][0];
-        cmy += s->mn[q][1];
-        cMx += s->Mxy[i][0];
-        cMy += s->Mxy[i][1];
-    }
-    cmx = wave_sum_f64(cmx) / n; cmy = wave_sum_f64(cmy) / n; cMx = wave_sum_f64(cMx) / n; cMy = wave_sum_f64(cMy) / n;
-    for (int i = lane; i < n; i += 64) {
-        const int q = RB_Q(i);
-        smx += fabs(s->mn[q][0] - cmx);
-        smy += fabs(s->mn[q][1] - cmy);
-        sMx += fabs(s->Mxy[i][0] - cMx);
-        sMy += fabs(s->Mxy[i][1] - cMy);
-    }
-    smx = wave_sum_f64(smx); smy = wave_sum_f64(smy); sMx = wave_sum_f64(sMx); sMy = wave_sum_f64(sMy);
-    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
-    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
-    for (int j = 0; j < 9; j++)
-        for (int k = j; k < 9; k++) {
-            double acc = 0;
-            for (int i = lane; i < n; i += 64) {
-                const int q = RB_Q(i);
-                const double x = (s->mn[q][0] - cmx) * smx, y = (s->mn[q][1] - cmy) * smy;
-                const double X = (s->Mxy[i][0] - cMx) * sMx, Y = (s->Mxy[i][1] - cMy) * sMy;
-                double lxj, lyj, lxk, lyk;
-                pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
-                pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
-                acc += lxj * lxk + lyj * lyk;
-            }
-            acc = wave_sum_f64(acc);
-            if (lane == 0) {
-                s->A[j * 9 + k] = acc;
-                s->A[k * 9 + j] = acc;
-            }
-        }
-    return pnp_dlt_finish(s->A, s->V, lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
-}
-
-// stages (2)-(4) of k_map_pose over the nsub markers sub[0..nsub) and getReprojectionError over them; every lane returns the same
-template <int MODEL>
-__device__ void rb_solve(RbLds *rs, int nsub, int lane, const double K[9], const double kd[12], double param[6], double *image_error)
-{
-    MpLds &s = rs->m;
-    const int npts = 4 * nsub;
-    // ---- (2) planarity
-    double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
+// fid_pnp.h's view of the subset sub[0..nsub): point i is point 4 sub[i / 4] + i % 4 of the tables, marker k is marker sub[k]; Mxy is
+// written and read in subset order
+struct RbView {
+    RbLds *rs;
+    int nsub;
+    static constexpr bool PLANAR_ONLY = false;
+    __device__ __forceinline__ int at(int i) const { return 4 * (int)rs->sub[i >> 2] + (i & 3); }
+    __device__ __forceinline__ void obj(int i, double M[3]) const
     {
-        for (int p = lane; p < npts; p += 64) {
-            const int q = RB_Q(p);
-            for (int a = 0; a < 3; a++) Mc[a] += s.obj[q][a];
-        }
-        for (int a = 0; a < 3; a++) Mc[a] = wave_sum_f64(Mc[a]) / npts;
-        double m6[6] = {0, 0, 0, 0, 0, 0};
-        for (int p = lane; p < npts; p += 64) {
-            const int q = RB_Q(p);
-            const double d[3] = {s.obj[q][0] - Mc[0], s.obj[q][1] - Mc[1], s.obj[q][2] - Mc[2]};
-            m6[0] += d[0] * d[0]; m6[1] += d[0] * d[1]; m6[2] += d[0] * d[2];
-            m6[3] += d[1] * d[1]; m6[4] += d[1] * d[2]; m6[5] += d[2] * d[2];
-        }
-        for (int i = 0; i < 6; i++) m6[i] = wave_sum_f64(m6[i]);
-        double MM[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
-        pnp_scatter_eig(MM, W, Vt);
+        const int q = at(i);
+        for (int a = 0; a < 3; a++) M[a] = rs->m.obj[q][a];
     }
-    const bool planar = W[2] / W[1] < 1e-3;
-    // ---- (3) the start
-    for (int i = 0; i < 6; i++) param[i] = 0.;
-    if (planar) {
-        double Rt[9], tt[3];
-        pnp_plane_frame(Vt, Mc, Rt, tt);
-        SR_LDS_SYNC();  // (the Mxy of the solve before this one has been read)
-        for (int p = lane; p < npts; p += 64) {
-            const double *src = s.obj[RB_Q(p)];
-            s.Mxy[p][0] = (float)(Rt[0] * src[0] + Rt[1] * src[1] + Rt[2] * src[2] + tt[0]);
-            s.Mxy[p][1] = (float)(Rt[3] * src[0] + Rt[4] * src[1] + Rt[5] * src[2] + tt[1]);
-        }
-        SR_LDS_SYNC();
-        double h[9], R[9];
-        if (rb_homography_dlt(rs, npts, lane, h)) {
-            double t3[3];
-            pnp_pose_from_h(h, t3);
-            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
-            pnp_mul3(h, Rt, R);
-        } else {
-            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
-        }
-        rodrigues_m2v(R, param);
-    } else {
-        // the subset's marker with the largest image area, the first of equals (positions in the subset, as k_map_pose's are in its list)
-        int big = lane < nsub ? lane : 0;
-        double abig = s.area[rs->sub[big]];
-        for (int k = lane + 64; k < nsub; k += 64)
-            if (s.area[rs->sub[k]] > abig) {
-                abig = s.area[rs->sub[k]];
-                big = k;
-            }
-        for (int mask = 1; mask < 64; mask <<= 1) {
-            const double ao = shfl_xor_f64(abig, mask);
-            const int bo = __shfl_xor(big, mask, WAVE);
-            if (ao > abig || (ao == abig && bo < big)) {
-                abig = ao;
-                big = bo;
-            }
-        }
-        const int b4 = 4 * (int)rs->sub[big];
-        const double *c0 = s.obj[b4], *c2 = s.obj[b4 + 2];
-        const double cc[3] = {0.5 * (c0[0] + c2[0]), 0.5 * (c0[1] + c2[1]), 0.5 * (c0[2] + c2[2])};
-        pnp_start_largest<MODEL>(c0, s.obj[b4 + 1], s.obj[b4 + 3], cc, s.img + b4, K, kd, param);
-    }
-    // ---- (4) CvLevMarq over the 2 * npts residuals, lane l owns residuals l, l + 64, ...
-    const int nres = 2 * npts;
-    double S[21], gJ[6], e2 = 0;
-    bool needJ = true;
-    LevMarq lm;
-    do {
-        double Sp[21], gp[6];
-        e2 = 0;
-        for (int i = 0; i < 21; i++) Sp[i] = 0.;
-        for (int i = 0; i < 6; i++) gp[i] = 0.;
-        for (int r = lane; r < nres; r += 64) {
-            const int p = RB_Q(r >> 1), sel = r & 1;
-            const double M[3] = {s.obj[p][0], s.obj[p][1], s.obj[p][2]};
-            double Jrow[6];
-            const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - s.img[p][sel];
-            e2 += err * err;
-            if (needJ) {
-                int idx = 0;
-#pragma unroll
-                for (int a = 0; a < 6; a++) {
-#pragma unroll
-                    for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
-                    gp[a] += Jrow[a] * err;
-                }
-            }
-        }
-        if (needJ) {
-#pragma unroll
-            for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
-#pragma unroll
-            for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
-        }
-    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(e2); }, needJ));
-    // ---- getReprojectionError over the subset's points
-    double tot = 0;
-    for (int p = lane; p < npts; p += 64) {
-        const int q = RB_Q(p);
-        const double M[3] = {s.obj[q][0], s.obj[q][1], s.obj[q][2]};
-        double Jrow[6];
-        const double dx = s.img[q][0] - (double)(float)project_one<MODEL>(M, param, K, kd, 0, Jrow, false);
-        const double dy = s.img[q][1] - (double)(float)project_one<MODEL>(M, param, K, kd, 1, Jrow, false);
-        const double e = sqrt(dx * dx + dy * dy);
-        tot += e * e;
-    }
-    tot = wave_sum_f64(tot);
-    *image_error = tot / npts;
-}
-#undef RB_Q
-
-__device__ __forceinline__ void rb_zero_pose(fid_map_pose_out *o)
-{
-    o->n_markers = 0;
-    o->n_over = 0;
-    for (int i = 0; i < 3; i++) o->rvec[i] = o->tvec[i] = o->cam_t[i] = 0.;
-    for (int i = 0; i < 9; i++) o->R[i] = o->cam_R[i] = 0.;
-    o->image_error = 0.;
-}
+    __device__ __forceinline__ double img(int i, int c) const { return rs->m.img[at(i)][c]; }
+    __device__ __forceinline__ float mn(int i, int c) const { return rs->m.mn[at(i)][c]; }
+    __device__ __forceinline__ float *Mxy(int i) const { return rs->m.Mxy[i]; }
+    __device__ __forceinline__ double *A() const { return rs->m.A; }
+    __device__ __forceinline__ double *V() const { return rs->m.V; }
+    __device__ __forceinline__ int markers() const { return nsub; }
+    __device__ __forceinline__ double area(int k) const { return rs->m.area[rs->sub[k]]; }
+    static constexpr bool MARKER_IN_PLACE = true;
+    __device__ __forceinline__ PnpObj4 marker_obj(int k) const { return rs->m.obj + 4 * (int)rs->sub[k]; }
+    __device__ __forceinline__ PnpImg4 marker_img(int k) const { return rs->m.img + 4 * (int)rs->sub[k]; }
+};
 
 // { j eligible : err(param, j) <= thr }, lanes = markers; every lane returns the same masks.  With stats: the largest err inside
 // `in` and the smallest over the eligible markers outside it (-1 where there is none).
@@ -265,38 +117,9 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
     const int f = blockIdx.x, lane = threadIdx.x;
     const double *K = cam.K, *kd = cam.D;
     const fid_marker *mlist = markers + (long long)f * per_frame;
-    int nm = nmark_per_frame[(long long)f * nmark_stride_ints];
-    nm = nm < 0 ? 0 : (nm > per_frame ? per_frame : nm);
-    map_n = map_n > FID_MAP_MAX_ENTRIES ? FID_MAP_MAX_ENTRIES : map_n;
-    // ---- (1) the frame's markers that the map names, in list order, without the ids seen twice (k_map_pose's gather)
-    for (int e = lane; e < MP_BIT_WORDS; e += 64) s.seen[e] = s.dup[e] = 0u;
-    SR_LDS_SYNC();
-    for (int m0 = 0; m0 < nm; m0 += 64) {
-        const int m = m0 + lane;
-        const int idx = m < nm ? mp_find(map_ids, map_n, mlist[m].id) : -1;
-        if (idx >= 0) {
-            const unsigned bit = 1u << (idx & 31);
-            if (atomicOr(&s.seen[idx >> 5], bit) & bit) atomicOr(&s.dup[idx >> 5], bit);
-        }
-    }
-    SR_LDS_SYNC();
-    int found = 0;
-    for (int m0 = 0; m0 < nm; m0 += 64) {
-        const int m = m0 + lane;
-        int idx = m < nm ? mp_find(map_ids, map_n, mlist[m].id) : -1;
-        if (idx >= 0 && (s.dup[idx >> 5] >> (idx & 31) & 1u)) idx = -1;
-        const unsigned long long hit = __ballot(idx >= 0);
-        if (idx >= 0) {
-            const int pos = found + __builtin_popcountll(hit & ((1ull << lane) - 1ull));
-            if (pos < MP_MAX_USED) {
-                s.mk[pos] = m;
-                s.ent[pos] = idx;
-            }
-        }
-        found += __builtin_popcountll(hit);
-    }
-    const int n_over = found > MP_MAX_USED ? found - MP_MAX_USED : 0;
-    found -= n_over;
+    // ---- (1) the frame's markers that the map names (k_map_pose's gather)
+    int n_over;
+    const int found = mp_gather(s, mlist, nmark_per_frame[(long long)f * nmark_stride_ints], per_frame, map_ids, map_n, lane, &n_over);
     // the record beside the pose: what every exit below starts from
     fid_map_robust_out ro;
     ro.status = FID_MAP_ROBUST_NO_MARKERS;
@@ -312,31 +135,14 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
     for (int i = 0; i < 16; i++) ro.outlier_index[i] = -1;
     if (found == 0) {
         if (lane == 0) {
-            fid_map_pose_out o;
-            rb_zero_pose(&o);
-            out[f] = o;
+            mp_pose_none(out + f, 0, 0, 0.);
             rout[f] = ro;
         }
         return;
     }
     SR_LDS_SYNC();
     const int npts = 4 * found;
-    for (int p = lane; p < npts; p += 64) {
-        const int k = p >> 2, q = p & 3;
-        const fid_marker *mk = mlist + s.mk[k];
-        const double *src = map_obj + (size_t)s.ent[k] * 12 + q * 3;
-        for (int a = 0; a < 3; a++) s.obj[p][a] = src[a];
-        s.img[p][0] = (double)mk->corners[2 * q];
-        s.img[p][1] = (double)mk->corners[2 * q + 1];
-        if (q == 0) {  // the marker's area in the image (shoelace over its four corners)
-            double a2 = 0;
-            for (int i = 0; i < 4; i++) {
-                const int i1 = (i + 1) & 3;
-                a2 += (double)mk->corners[2 * i] * (double)mk->corners[2 * i1 + 1] - (double)mk->corners[2 * i1] * (double)mk->corners[2 * i + 1];
-            }
-            s.area[k] = fabs(a2);
-        }
-    }
+    (void)mp_load_points<MODEL, false>(s, mlist, map_obj, found, lane, K, kd);
     SR_LDS_SYNC();
     // ---- (2) eligible markers (all four corners undistort) ...
     unsigned long long elig[4], I[4], Inext[4];
@@ -408,12 +214,7 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
     }
     SR_LDS_SYNC();  // (the counters lay over mn and Mxy)
     // the undistorted image points as floats (the DLT's input), for every used point: a solve reads its subset's
-    for (int p = lane; p < npts; p += 64) {
-        double x, y;
-        (void)pnp_undistort<MODEL>(K, kd, s.img[p][0], s.img[p][1], &x, &y);
-        s.mn[p][0] = (float)x;
-        s.mn[p][1] = (float)y;
-    }
+    for (int p = lane; p < npts; p += 64) (void)mp_store_mn<MODEL>(s, p, s.img[p][0], s.img[p][1], K, kd);
     // ---- (4) the winner: the smallest score, then the lowest k
     int win_k = hk >= 0 ? hk : 0x7fffffff, win_lane = lane;
     unsigned long long win_bits = score_bits;
@@ -452,7 +253,7 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
                 before += __builtin_popcountll(I[w]);
             }
             SR_LDS_SYNC();
-            rb_solve<MODEL>(&rs, nI, lane, K, kd, param, &image_error);
+            pnp_wave_solve<MODEL>(RbView{&rs, nI}, 4 * nI, lane, K, kd, param, &image_error);
             rounds++;
             double wi, bo;
             rb_admit<MODEL, true>(&s, found, lane, elig, param, K, kd, inlier_px, Inext, I, &wi, &bo);
@@ -486,17 +287,7 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
         if (status == FID_MAP_ROBUST_OK) {
             o.n_markers = nI;
             o.n_over = n_over;
-            for (int i = 0; i < 3; i++) {
-                o.rvec[i] = param[i];
-                o.tvec[i] = param[3 + i];
-            }
-            double dummy[27];
-            rodrigues_v2m(param, o.R, dummy, false);
-            for (int i = 0; i < 3; i++) {
-                for (int j = 0; j < 3; j++) o.cam_R[3 * i + j] = o.R[3 * j + i];
-                o.cam_t[i] = -(o.R[i] * param[3] + o.R[3 + i] * param[4] + o.R[6 + i] * param[5]);
-            }
-            o.image_error = image_error;
+            pnp_pose_record(o, param, image_error);
             ro.n_inliers = nI;
             ro.n_outliers = found - nI;
             int no = 0;
@@ -507,7 +298,9 @@ __global__ __launch_bounds__(64) void k_map_pose_robust(const fid_marker *__rest
                     no++;
                 }
         } else {
-            rb_zero_pose(&o);
+            o.n_markers = 0;
+            o.n_over = 0;
+            pnp_pose_record_zero(o, 0.);
             ro.worst_inlier_px = ro.best_outlier_px = -1.;
             int no = 0;
             for (int k = 0; k < found; k++) {

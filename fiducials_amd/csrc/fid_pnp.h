@@ -1,6 +1,7 @@
 // fid_pnp.h -- cv::solvePnP (SOLVEPNP_ITERATIVE) as a device library: what k_pose (fid_kernels.hip K8), k_stag_pose and
-// k_stag_bundle_pose (fid_stag_pose.hip K17, K18) and k_map_pose (fid_map_pose.hip K19) have in common.  Included once, ahead
-// of K8, in the fid_api.hip translation unit (needs WAVE and <float.h> from fid_kernels.hip's head).
+// k_stag_bundle_pose (fid_stag_pose.hip K17, K18), k_map_pose (fid_map_pose.hip K19), k_map_pose_robust (fid_map_pose_robust.hip
+// K20) and k_charuco_pose (fid_charuco.hip) have in common.  Included once, ahead of K8, in the fid_api.hip translation unit
+// (needs WAVE and <float.h> from fid_kernels.hip's head).
 //
 //   lane-group sums      shfl_xor_f64, dpp_f64, grp_sum8, grp_sum16, wave_sum_f64
 //   the camera           PoseCam, pose_cam_from (fid_camera -> PoseCam), POSE_CAM_DISPATCH (the host picks the instantiation)
@@ -13,16 +14,22 @@
 //                        pnp_start_largest (sets that are not coplanar)
 //   CvLevMarq            lm_lambda, solve6_spd, LevMarq
 //   the covariance       pnp_covariance, pnp_cov_zero (sigma^2 (J^T J)^-1 at the returned pose, in the ROS pose convention)
+//   the wave-strided     pnp_wave_solve over a view of a kernel's points (planarity, either start, CvLevMarq, the reprojection
+//   solve                error), with pnp_homography_dlt and pnp_wave_residuals (also the covariance's J^T J); the record's
+//                        pose part: pnp_pose_record, pnp_pose_record_zero
 //
 // A kernel gathers its points, makes the start, and runs
 //     LevMarq lm;
 //     bool needJ = true;
 //     do { residuals at param; with needJ: reduce S, gJ } while (lm.step(param, S, gJ, errSq, needJ));  (errSq: a callable, see LevMarq)
-// with its OWN reduction over its lanes -- the order of a floating-point sum is part of a kernel's result, so the reductions
-// are not shared: eight lanes (DPP), sixteen lanes, a wave with two residuals per lane, a wave with strided partial sums.
+// with a reduction over its lanes.  The order of a floating-point sum is part of a kernel's result, so a reduction is shared only
+// where the order is the same.  ONE form is: a wave per point set with strided per-lane partial sums and a butterfly, the order of
+// k_map_pose, k_map_pose_robust and k_charuco_pose, which run pnp_wave_solve (at the end of this file) on their views.  The other
+// three are each one kernel's own: eight lanes by DPP (k_pose), sixteen lanes (k_stag_pose), a wave with two residuals per lane
+// and sequential sums (k_stag_bundle_pose).
 //
-// The camera model (fid_camera_model, fid_abi.h) is a TEMPLATE parameter of project_one, pnp_undistort, pnp_start_largest and of the
-// four kernels: nothing inside the Levenberg-Marquardt loop asks for it at run time.  The FID_CAM_PLUMB_BOB instantiation is the code
+// The camera model (fid_camera_model, fid_abi.h) is a TEMPLATE parameter of project_one, pnp_undistort, pnp_start_largest,
+// pnp_wave_solve and of the kernels: nothing inside the Levenberg-Marquardt loop asks for it at run time.  The FID_CAM_PLUMB_BOB instantiation is the code
 // as it was before the models came (the same expressions in the same order); FID_CAM_RATIONAL adds OpenCV 4.2's terms so that with
 // k4..k6 and s1..s4 zero every intermediate value equals the plumb-bob one (x * 1.0, + 0.0).
 #pragma once
@@ -910,9 +917,9 @@ __device__ int pnp_smallest_eigvec9(double *A, double *V, int lane)
 
 // the tail of HomographyEstimatorCallback::runKernel (fundam.cpp): LtL is in A (LDS, both triangles); the eigenvector of its
 // smallest eigenvalue, de-normalised by the two point sets' centroids (c..) and scales (s..; m: image, M: plane), scaled to
-// H[8] = 1.  The ACCUMULATION of LtL stays with the kernels on purpose: k_stag_bundle_pose sums every entry serially over the
-// points on lanes < 45, k_map_pose sums strided per-lane partials and butterflies them -- the float sums land on different bits,
-// and each kernel's bits are its result.
+// H[8] = 1.  The ACCUMULATION of LtL is not part of it on purpose: k_stag_bundle_pose sums every entry serially over the points
+// on lanes < 45 (sb_homography_dlt), the wave-strided kernels sum strided per-lane partials and butterfly them
+// (pnp_homography_dlt below) -- the float sums land on different bits, and each kernel's bits are its result.
 __device__ __forceinline__ bool pnp_dlt_finish(double *A, double *V, int lane, double cmx, double cmy, double smx, double smy, double cMx, double cMy,
                                                double sMx, double sMy, double H[9])
 {
@@ -978,3 +985,270 @@ struct LevMarq {
         return true;
     }
 };
+
+// ------------------------------------------------------------------------------------------------ the wave-strided solve
+// solvePnP over ONE point set by ONE wave: point p on lane p % 64, per-lane partial sums in point order, one xor butterfly per
+// entry -- a fixed order, reproducible from run to run, the same value in every lane.  k_map_pose, k_map_pose_robust and
+// k_charuco_pose all sum in this order, so they share the body; each hands its points over as a VIEW of its LDS tables, a small
+// struct that is inlined away:
+//     PLANAR_ONLY                  (static constexpr bool) the object points are (x, y, 0): no planarity test, no other start
+//     obj(i, M)                    object point i as three doubles (a PLANAR_ONLY view: the literal 0. as the third)
+//     img(i, c)                    coordinate c of image point i
+//     mn(i, c)                     the undistorted image point rounded to float (findHomography's input)
+//     Mxy(i)                       the float in-plane point, two floats of LDS written and read in view order
+//     A(), V()                     81 doubles of LDS each: the DLT's 9 x 9 and its eigenvectors
+//     markers(), area(k)           for the start of a set that is not coplanar: the markers in view order, the image area of
+//                                  marker k (a PLANAR_ONLY view has neither, nor what follows)
+//     MARKER_IN_PLACE              (static constexpr bool) how the start reads the largest marker: false -- first(k), the index
+//                                  of its first point (of four in a row), the points copied into registers through obj / img;
+//                                  true -- marker_obj(k), marker_img(k), its four object and image points where they lie in
+//                                  LDS.  Same values either way; each kernel has the form it measured faster with (HISTORY)
+typedef const double (*PnpObj4)[3];  // four object points in a row
+typedef const double (*PnpImg4)[2];  // four image points in a row
+
+// HomographyEstimatorCallback::runKernel (fundam.cpp) over the n correspondences Mxy -> mn of a view, with the float-input
+// normalisation; each of the 45 entries of LtL is a strided partial sum per lane and a butterfly.  Every lane returns the same H.
+template <class View>
+__device__ bool pnp_homography_dlt(const View &v, int n, int lane, double H[9])
+{
+    double cMx = 0, cMy = 0, cmx = 0, cmy = 0, sMx = 0, sMy = 0, smx = 0, smy = 0;
+    for (int i = lane; i < n; i += 64) {
+        cmx += v.mn(i, 0);
+        cmy += v.mn(i, 1);
+        cMx += v.Mxy(i)[0];
+        cMy += v.Mxy(i)[1];
+    }
+    cmx = wave_sum_f64(cmx) / n; cmy = wave_sum_f64(cmy) / n; cMx = wave_sum_f64(cMx) / n; cMy = wave_sum_f64(cMy) / n;
+    for (int i = lane; i < n; i += 64) {
+        smx += fabs(v.mn(i, 0) - cmx);
+        smy += fabs(v.mn(i, 1) - cmy);
+        sMx += fabs(v.Mxy(i)[0] - cMx);
+        sMy += fabs(v.Mxy(i)[1] - cMy);
+    }
+    smx = wave_sum_f64(smx); smy = wave_sum_f64(smy); sMx = wave_sum_f64(sMx); sMy = wave_sum_f64(sMy);
+    if (!(fabs(smx) >= DBL_EPSILON) || !(fabs(smy) >= DBL_EPSILON) || !(fabs(sMx) >= DBL_EPSILON) || !(fabs(sMy) >= DBL_EPSILON)) return false;
+    smx = n / smx; smy = n / smy; sMx = n / sMx; sMy = n / sMy;
+    // LtL, entry (j, k), j <= k: the lane's points in their order, then the butterfly
+    double *A = v.A();
+    for (int j = 0; j < 9; j++)
+        for (int k = j; k < 9; k++) {
+            double acc = 0;
+            for (int i = lane; i < n; i += 64) {
+                const double x = (v.mn(i, 0) - cmx) * smx, y = (v.mn(i, 1) - cmy) * smy;
+                const double X = (v.Mxy(i)[0] - cMx) * sMx, Y = (v.Mxy(i)[1] - cMy) * sMy;
+                double lxj, lyj, lxk, lyk;
+                pnp_dlt_entry(j, X, Y, x, y, &lxj, &lyj);
+                pnp_dlt_entry(k, X, Y, x, y, &lxk, &lyk);
+                acc += lxj * lxk + lyj * lyk;
+            }
+            acc = wave_sum_f64(acc);
+            if (lane == 0) {
+                A[j * 9 + k] = acc;
+                A[k * 9 + j] = acc;
+            }
+        }
+    return pnp_dlt_finish(A, v.V(), lane, cmx, cmy, smx, smy, cMx, cMy, sMx, sMy, H);
+}
+
+// the 2 n residuals of a view at param, residual r (point r / 2, coordinate r % 2) on lane r % 64: returns the lane's share of
+// |e|^2, which the caller butterflies when it reads it.  With needJ the normal equations as well, every lane the same: S = J^T J
+// (packed upper triangle, solve6_spd's order) and, with GRAD, gJ = J^T e (without: gJ is not touched; the covariance needs S alone).
+template <int MODEL, bool GRAD, class View>
+__device__ __forceinline__ double pnp_wave_residuals(const View &v, int n, int lane, const double K[9], const double kd[12], const double param[6],
+                                                     bool needJ, double S[21], double gJ[6])
+{
+    const int nres = 2 * n;
+    double Sp[21], gp[6], e2 = 0;
+    for (int i = 0; i < 21; i++) Sp[i] = 0.;
+    for (int i = 0; i < 6; i++) gp[i] = 0.;
+    for (int r = lane; r < nres; r += 64) {
+        const int p = r >> 1, sel = r & 1;
+        double M[3], Jrow[6];
+        v.obj(p, M);
+        const double err = project_one<MODEL>(M, param, K, kd, sel, Jrow, needJ) - v.img(p, sel);
+        e2 += err * err;
+        if (needJ) {
+            int idx = 0;
+#pragma unroll
+            for (int a = 0; a < 6; a++) {
+#pragma unroll
+                for (int c = a; c < 6; c++) Sp[idx++] += Jrow[a] * Jrow[c];
+                if constexpr (GRAD) gp[a] += Jrow[a] * err;
+            }
+        }
+    }
+    if (needJ) {
+#pragma unroll
+        for (int i = 0; i < 21; i++) S[i] = wave_sum_f64(Sp[i]);
+        if constexpr (GRAD) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) gJ[i] = wave_sum_f64(gp[i]);
+        }
+    }
+    return e2;
+}
+
+// cv::solvePnP (ITERATIVE) over the n points of a view and getReprojectionError over them; every lane returns the same param and
+// image_error.  The caller has made its LDS tables visible to the wave (SR_LDS_SYNC) and may call again with another view of them.
+//   (a) planarity: cvFindExtrinsicCameraParams2's test, the eigenvalues of the centred scatter matrix.
+//   (b) the start.  Coplanar: the points turned into their plane, the DLT homography over all of them.  Not coplanar: the closed-form
+//       pose of the marker with the largest image area (the first of equals in view order) composed with that marker's place in the
+//       set (OpenCV runs a 12 x 12 DLT there; the start is unpinned).
+//   (c) CvLevMarq with the camera model's distortion in the projection and its Jacobian.
+//   (d) the reprojection error: projections rounded to float (vector<Point2f>), sum |d|^2 / n.
+// A PLANAR_ONLY view sums the scatter matrix over x and y and turns the points with two terms: the three-term forms with z = 0. give
+// another sign to a zero in corner cases (-0. + 0.) and cost instructions that nothing folds without fast-math.
+template <int MODEL, class View>
+__device__ __forceinline__ void pnp_wave_solve(const View &v, int n, int lane, const double K[9], const double kd[12], double param[6],
+                                               double *image_error)
+{
+    // ---- (a) the centred scatter matrix of the object points and its eigenvalues and eigenvectors
+    double Mc[3] = {0, 0, 0}, W[3], Vt[3][3];
+    bool planar = true;
+    if constexpr (View::PLANAR_ONLY) {
+        for (int p = lane; p < n; p += 64) {
+            double M[3];
+            v.obj(p, M);
+            Mc[0] += M[0];
+            Mc[1] += M[1];
+        }
+        for (int a = 0; a < 2; a++) Mc[a] = wave_sum_f64(Mc[a]) / n;
+        double m3[3] = {0, 0, 0};
+        for (int p = lane; p < n; p += 64) {
+            double M[3];
+            v.obj(p, M);
+            const double d0 = M[0] - Mc[0], d1 = M[1] - Mc[1];
+            m3[0] += d0 * d0; m3[1] += d0 * d1; m3[2] += d1 * d1;
+        }
+        for (int i = 0; i < 3; i++) m3[i] = wave_sum_f64(m3[i]);
+        double MM[3][3] = {{m3[0], m3[1], 0.}, {m3[1], m3[2], 0.}, {0., 0., 0.}};
+        pnp_scatter_eig(MM, W, Vt);
+    } else {
+        for (int p = lane; p < n; p += 64) {
+            double M[3];
+            v.obj(p, M);
+            for (int a = 0; a < 3; a++) Mc[a] += M[a];
+        }
+        for (int a = 0; a < 3; a++) Mc[a] = wave_sum_f64(Mc[a]) / n;
+        double m6[6] = {0, 0, 0, 0, 0, 0};
+        for (int p = lane; p < n; p += 64) {
+            double M[3];
+            v.obj(p, M);
+            const double d[3] = {M[0] - Mc[0], M[1] - Mc[1], M[2] - Mc[2]};
+            m6[0] += d[0] * d[0]; m6[1] += d[0] * d[1]; m6[2] += d[0] * d[2];
+            m6[3] += d[1] * d[1]; m6[4] += d[1] * d[2]; m6[5] += d[2] * d[2];
+        }
+        for (int i = 0; i < 6; i++) m6[i] = wave_sum_f64(m6[i]);
+        double MM[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
+        pnp_scatter_eig(MM, W, Vt);
+        planar = W[2] / W[1] < 1e-3;
+    }
+    // ---- (b) the start
+    for (int i = 0; i < 6; i++) param[i] = 0.;
+    if (planar) {
+        double Rt[9], tt[3];
+        pnp_plane_frame(Vt, Mc, Rt, tt);
+        SR_LDS_SYNC();  // (a solve before this one has read its Mxy)
+        for (int p = lane; p < n; p += 64) {
+            double M[3];
+            v.obj(p, M);
+            if constexpr (View::PLANAR_ONLY) {
+                v.Mxy(p)[0] = (float)(Rt[0] * M[0] + Rt[1] * M[1] + tt[0]);
+                v.Mxy(p)[1] = (float)(Rt[3] * M[0] + Rt[4] * M[1] + tt[1]);
+            } else {
+                v.Mxy(p)[0] = (float)(Rt[0] * M[0] + Rt[1] * M[1] + Rt[2] * M[2] + tt[0]);
+                v.Mxy(p)[1] = (float)(Rt[3] * M[0] + Rt[4] * M[1] + Rt[5] * M[2] + tt[1]);
+            }
+        }
+        SR_LDS_SYNC();
+        double h[9], R[9];
+        if (pnp_homography_dlt(v, n, lane, h)) {
+            double t3[3];
+            pnp_pose_from_h(h, t3);
+            for (int i = 0; i < 3; i++) param[3 + i] = h[i * 3] * tt[0] + h[i * 3 + 1] * tt[1] + h[i * 3 + 2] * tt[2] + t3[i];
+            pnp_mul3(h, Rt, R);
+        } else {
+            for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1. : 0.;
+        }
+        rodrigues_m2v(R, param);
+    } else if constexpr (!View::PLANAR_ONLY) {
+        // the marker with the largest image area, the first of equals: per lane over its markers, then a butterfly on (area, index)
+        const int nmk = v.markers();
+        int big = lane < nmk ? lane : 0;
+        double abig = v.area(big);
+        for (int k = lane + 64; k < nmk; k += 64)
+            if (v.area(k) > abig) {
+                abig = v.area(k);
+                big = k;
+            }
+        for (int mask = 1; mask < 64; mask <<= 1) {
+            const double ao = shfl_xor_f64(abig, mask);
+            const int bo = __shfl_xor(big, mask, WAVE);
+            if (ao > abig || (ao == abig && bo < big)) {
+                abig = ao;
+                big = bo;
+            }
+        }
+        // its four object and image points: where they lie in LDS, or copied into registers through the view's accessors
+        double cq[4][3], uvq[4][2];
+        PnpObj4 c = cq;
+        PnpImg4 uv = uvq;
+        if constexpr (View::MARKER_IN_PLACE) {
+            c = v.marker_obj(big);
+            uv = v.marker_img(big);
+        } else {
+            const int p0 = v.first(big);
+            for (int q = 0; q < 4; q++) {
+                v.obj(p0 + q, cq[q]);
+                uvq[q][0] = v.img(p0 + q, 0);
+                uvq[q][1] = v.img(p0 + q, 1);
+            }
+        }
+        const double cc[3] = {0.5 * (c[0][0] + c[2][0]), 0.5 * (c[0][1] + c[2][1]), 0.5 * (c[0][2] + c[2][2])};
+        pnp_start_largest<MODEL>(c[0], c[1], c[3], cc, uv, K, kd, param);
+    }
+    // ---- (c) CvLevMarq over the 2 n residuals
+    double S[21], gJ[6], e2 = 0;
+    bool needJ = true;
+    LevMarq lm;
+    do {
+        e2 = pnp_wave_residuals<MODEL, true>(v, n, lane, K, kd, param, needJ, S, gJ);
+    } while (lm.step(param, S, gJ, [&] { return wave_sum_f64(e2); }, needJ));
+    // ---- (d) getReprojectionError
+    double tot = 0;
+    for (int p = lane; p < n; p += 64) {
+        double M[3], Jrow[6];
+        v.obj(p, M);
+        const double dx = v.img(p, 0) - (double)(float)project_one<MODEL>(M, param, K, kd, 0, Jrow, false);
+        const double dy = v.img(p, 1) - (double)(float)project_one<MODEL>(M, param, K, kd, 1, Jrow, false);
+        const double e = sqrt(dx * dx + dy * dy);
+        tot += e * e;
+    }
+    *image_error = wave_sum_f64(tot) / n;
+}
+
+// the pose part of a record (fid_map_pose_out, fid_charuco_pose_out: rvec, tvec, R, cam_R, cam_t, image_error; the counts in front
+// of them are the kernel's): param as the board's pose in the camera frame and, inverted, the camera's in the board's ...
+template <class Rec>
+__device__ __forceinline__ void pnp_pose_record(Rec &o, const double param[6], double image_error)
+{
+    for (int i = 0; i < 3; i++) {
+        o.rvec[i] = param[i];
+        o.tvec[i] = param[3 + i];
+    }
+    double dummy[27];
+    rodrigues_v2m(param, o.R, dummy, false);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) o.cam_R[3 * i + j] = o.R[3 * j + i];
+        o.cam_t[i] = -(o.R[i] * param[3] + o.R[3 + i] * param[4] + o.R[6 + i] * param[5]);
+    }
+    o.image_error = image_error;
+}
+// ... and the record of a set that has no pose: all zero, image_error as the caller's exit defines it
+template <class Rec>
+__device__ __forceinline__ void pnp_pose_record_zero(Rec &o, double image_error)
+{
+    for (int i = 0; i < 3; i++) o.rvec[i] = o.tvec[i] = o.cam_t[i] = 0.;
+    for (int i = 0; i < 9; i++) o.R[i] = o.cam_R[i] = 0.;
+    o.image_error = image_error;
+}
