@@ -47,63 +47,56 @@ __device__ __forceinline__ int stag_reflect101(int p, int n)
 // Every source byte is read once, every gray byte written once.  The frame lies at base + off: in a group every frame's arguments
 // are frame 0's but for off (the recorder's one per-frame scalar, fid_stag_batch.h) and dst (its context's slab delta), so a
 // group's ingest is one launch.
-__device__ __forceinline__ void k_stag_ingest_impl(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
-                                                   long long stride, int enc)
-{
-    const long long cpr = (W + 15) >> 4;  // 16-pixel chunks per row
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= cpr * H) return;
-    const int y = (int)(i / cpr), x0 = (int)(i - (long long)y * cpr) * 16;
-    const int n = W - x0 < 16 ? W - x0 : 16;
-    const int bpp = enc == FID_ENC_MONO8 ? 1 : 3;
-    const uint8_t *s = base + off + (unsigned long long)y * (unsigned long long)stride + (unsigned long long)x0 * bpp;
-    uint8_t *d = dst + (size_t)y * W + x0;
-    const bool swide = n == 16 && ((uintptr_t)s & 15) == 0, dwide = n == 16 && ((uintptr_t)d & 15) == 0;
-    unsigned o[4] = {0u, 0u, 0u, 0u};
-    if (enc == FID_ENC_MONO8) {
-        if (swide) {
-            const uint4 a = *reinterpret_cast<const uint4 *>(s);
-            o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-        } else {
-            for (int k = 0; k < n; k++) o[k >> 2] |= (unsigned)s[k] << ((k & 3) * 8);
-        }
-    } else {
-        const bool bfirst = enc == FID_ENC_BGR8;
-        if (swide) {
-            const uint4 *q = reinterpret_cast<const uint4 *>(s);
-            const uint4 a = q[0], b = q[1], c = q[2];
-            const unsigned w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
-#pragma unroll
-            for (int p = 0; p < 16; p++) {
-                const int c0 = (int)((w[(3 * p) >> 2] >> (((3 * p) & 3) * 8)) & 0xffu);
-                const int c1 = (int)((w[(3 * p + 1) >> 2] >> (((3 * p + 1) & 3) * 8)) & 0xffu);
-                const int c2 = (int)((w[(3 * p + 2) >> 2] >> (((3 * p + 2) & 3) * 8)) & 0xffu);
-                const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
-                o[p >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((p & 3) * 8);
-            }
-        } else {
-            for (int k = 0; k < n; k++) {
-                const int c0 = s[3 * k], c1 = s[3 * k + 1], c2 = s[3 * k + 2];
-                const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
-                o[k >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((k & 3) * 8);
-            }
-        }
-    }
-    if (dwide) {
-        *reinterpret_cast<uint4 *>(d) = make_uint4(o[0], o[1], o[2], o[3]);
-    } else {
-        for (int k = 0; k < n; k++) d[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_ingest(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
-                                                     long long stride, int enc)
-{
-    k_stag_ingest_impl(dst, base, off, W, H, stride, enc);
-}
 struct k_stag_ingest_fn {
     static constexpr int kBounds = 256;
     __device__ __forceinline__ void operator()(uint8_t *__restrict__ dst, const uint8_t *__restrict__ base, unsigned long long off, int W, int H,
-                                               long long stride, int enc) const { k_stag_ingest_impl(dst, base, off, W, H, stride, enc); }
+                                               long long stride, int enc) const
+    {
+        const long long cpr = (W + 15) >> 4;  // 16-pixel chunks per row
+        const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (i >= cpr * H) return;
+        const int y = (int)(i / cpr), x0 = (int)(i - (long long)y * cpr) * 16;
+        const int n = W - x0 < 16 ? W - x0 : 16;
+        const int bpp = enc == FID_ENC_MONO8 ? 1 : 3;
+        const uint8_t *s = base + off + (unsigned long long)y * (unsigned long long)stride + (unsigned long long)x0 * bpp;
+        uint8_t *d = dst + (size_t)y * W + x0;
+        const bool swide = n == 16 && ((uintptr_t)s & 15) == 0, dwide = n == 16 && ((uintptr_t)d & 15) == 0;
+        unsigned o[4] = {0u, 0u, 0u, 0u};
+        if (enc == FID_ENC_MONO8) {
+            if (swide) {
+                const uint4 a = *reinterpret_cast<const uint4 *>(s);
+                o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+            } else {
+                for (int k = 0; k < n; k++) o[k >> 2] |= (unsigned)s[k] << ((k & 3) * 8);
+            }
+        } else {
+            const bool bfirst = enc == FID_ENC_BGR8;
+            if (swide) {
+                const uint4 *q = reinterpret_cast<const uint4 *>(s);
+                const uint4 a = q[0], b = q[1], c = q[2];
+                const unsigned w[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+                for (int p = 0; p < 16; p++) {
+                    const int c0 = (int)((w[(3 * p) >> 2] >> (((3 * p) & 3) * 8)) & 0xffu);
+                    const int c1 = (int)((w[(3 * p + 1) >> 2] >> (((3 * p + 1) & 3) * 8)) & 0xffu);
+                    const int c2 = (int)((w[(3 * p + 2) >> 2] >> (((3 * p + 2) & 3) * 8)) & 0xffu);
+                    const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
+                    o[p >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((p & 3) * 8);
+                }
+            } else {
+                for (int k = 0; k < n; k++) {
+                    const int c0 = s[3 * k], c1 = s[3 * k + 1], c2 = s[3 * k + 2];
+                    const int bb = bfirst ? c0 : c2, rr = bfirst ? c2 : c0;
+                    o[k >> 2] |= (unsigned)((bb * 3735 + c1 * 19235 + rr * 9798 + (1 << 14)) >> 15) << ((k & 3) * 8);
+                }
+            }
+        }
+        if (dwide) {
+            *reinterpret_cast<uint4 *>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+        } else {
+            for (int k = 0; k < n; k++) d[k] = (uint8_t)(o[k >> 2] >> ((k & 3) * 8));
+        }
+    }
 };
 
 // One workgroup = one SX x SY output tile.  src tile + 3 px halo (BORDER_REFLECT_101) -> LDS; horizontal [1 4 6 4 1] pass
@@ -111,144 +104,139 @@ struct k_stag_ingest_fn {
 // from LDS.  HBM traffic per pixel: 1 byte in (+ halo), 4 bytes out (smooth u8, grad i16, dir u8).
 #define SX 64
 #define SY 16
-__device__ __forceinline__ void k_stag_smooth_grad_impl(const uint8_t *__restrict__ src, int stride, int W, int H, int grad_thresh,
-                                                           uint8_t *__restrict__ smooth, int16_t *__restrict__ grad,
-                                                           uint8_t *__restrict__ dir)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t s_src[SY + 6][SX + 6 + 2];
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[SY + 6][SX + 4];  // (68 columns: the four-pixel path keeps x0 - 2 .. x0 + 65)
-    __shared__ __attribute__((aligned(16))) uint8_t s_sm[SY + 2][SX + 2 + 2];
-    const int x0 = blockIdx.x * SX, y0 = blockIdx.y * SY;
-    const int tid = threadIdx.x;
-    // (round 6) INTERIOR tiles -- no reflected coordinate, no image-border pixel, rows that can be read and written as 32-bit words:
-    // 90 % of a 1080p frame -- take four pixels a thread.  The byte-a-thread form below issued ~115 VALU instructions per 64 pixels
-    // (five LDS bytes + four multiply-adds per tap pass, eight bytes per Prewitt, divisions by 70 and 66 for the tile indices) and
-    // was bound by that, alone on the chip, not by HBM.  Here a tap pass is one v_dot4_u32_u8 per output on bytes shifted into place
-    // by v_alignbyte (horizontal) or packed 16-bit arithmetic on two columns at once (vertical: the sums stay below 65 536), and
-    // Prewitt works on the column sums of three rows.  The same integers as below, pixel for pixel.
-    if (x0 >= 4 && x0 + SX + 4 <= W && y0 >= 3 && y0 + SY + 3 <= H && ((stride | W) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
-        // bytes x0 - 4 .. x0 + 67 of rows y0 - 3 .. y0 + 18, as words
-        uint32_t(*w_src)[18] = reinterpret_cast<uint32_t(*)[18]>(&s_src[0][0]);  // 22 x 18 words = 1 584 bytes of the 1 584 there
-        uint32_t(*w_h)[34] = reinterpret_cast<uint32_t(*)[34]>(&s_h[0][0]);       // 22 x 34 words: two smoothed columns a word
-        uint32_t(*w_sm)[17] = reinterpret_cast<uint32_t(*)[17]>(&s_sm[0][0]);     // 18 x 17 words: four smoothed pixels a word
-        for (int i = tid; i < 22 * 18; i += 256) {
-            const int r = i / 18, c = i - r * 18;
-            w_src[r][c] = *reinterpret_cast<const uint32_t *>(src + (long long)(y0 - 3 + r) * stride + (x0 - 4 + 4 * c));
-        }
-        __syncthreads();
-        // horizontal [1 4 6 4 1]: item (row r, group j) = smoothed columns x0 - 2 + 4 j + k, k = 0 .. 3, from bytes k .. k + 4 of words j, j + 1
-        for (int i = tid; i < 22 * 17; i += 256) {
-            const int r = i / 17, j = i - r * 17;
-            const uint32_t d0 = w_src[r][j], d1 = w_src[r][j + 1];
-            const uint32_t h0 = __builtin_amdgcn_udot4(d0, 0x04060401u, d1 & 0xffu, false);
-            const uint32_t h1 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 1), 0x04060401u, (d1 >> 8) & 0xffu, false);
-            const uint32_t h2 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 2), 0x04060401u, (d1 >> 16) & 0xffu, false);
-            const uint32_t h3 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 3), 0x04060401u, d1 >> 24, false);
-            w_h[r][2 * j] = h0 | (h1 << 16);
-            w_h[r][2 * j + 1] = h2 | (h3 << 16);
-        }
-        __syncthreads();
-        // vertical pass, two columns a word: smoothed row y0 - 1 + r from rows r .. r + 4; (acc + 128) >> 8 per 16-bit half
-        for (int i = tid; i < 18 * 17; i += 256) {
-            const int r = i / 17, j = i - r * 17;
-            uint32_t o[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const uint32_t a = w_h[r][2 * j + q], b = w_h[r + 1][2 * j + q], c = w_h[r + 2][2 * j + q], d = w_h[r + 3][2 * j + q],
-                               e = w_h[r + 4][2 * j + q];
-                // a + e + 4 (b + d) + 6 c <= 16 * 4 080 = 65 280 in each half: no carry crosses the halves
-                const uint32_t acc = (a + e) + 4u * (b + d) + 6u * c + 0x00800080u;
-                o[q] = (acc >> 8) & 0x00ff00ffu;
-            }
-            w_sm[r][j] = (o[0] & 0xffu) | ((o[0] >> 8) & 0xff00u) | ((o[1] & 0xffu) << 16) | ((o[1] << 8) & 0xff000000u);
-        }
-        __syncthreads();
-        // Prewitt: thread = four pixels x0 + 4 j + k of row y0 + r; their 3 x 3 neighbourhoods are bytes 1 + k .. 3 + k of words j, j + 1
-        // (smoothed columns x0 - 2 + 4 j ...) of rows r .. r + 2.  gx = S(x + 1) - S(x - 1) with S = the column's sum over the three
-        // rows, gy = (bottom - top) summed over the three columns: ComputeGradient's com1 / com2 form, regrouped (integers: exact)
-        {
-            const int r = tid >> 4, j = tid & 15;
-            const uint32_t t0 = w_sm[r][j], t1 = w_sm[r][j + 1], m0 = w_sm[r + 1][j], m1 = w_sm[r + 1][j + 1], b0 = w_sm[r + 2][j],
-                           b1 = w_sm[r + 2][j + 1];
-            int S[8], D[8];
-#pragma unroll
-            for (int p = 1; p <= 6; p++) {
-                const int tp = (int)(((p < 4 ? t0 : t1) >> (8 * (p & 3))) & 0xffu), mp = (int)(((p < 4 ? m0 : m1) >> (8 * (p & 3))) & 0xffu),
-                          bp = (int)(((p < 4 ? b0 : b1) >> (8 * (p & 3))) & 0xffu);
-                S[p] = tp + mp + bp;
-                D[p] = bp - tp;
-            }
-            uint32_t gw[2] = {0u, 0u}, dw = 0u;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                int gxv = S[3 + k] - S[1 + k], gyv = D[1 + k] + D[2 + k] + D[3 + k];
-                gxv = gxv < 0 ? -gxv : gxv;
-                gyv = gyv < 0 ? -gyv : gyv;
-                const int sum = gxv + gyv;
-                gw[k >> 1] |= (uint32_t)sum << (16 * (k & 1));
-                dw |= (uint32_t)(sum >= grad_thresh ? (gxv >= gyv ? STAG_EDGE_VERTICAL : STAG_EDGE_HORIZONTAL) : 0) << (8 * k);
-            }
-            const long long idx = (long long)(y0 + r) * W + (x0 + 4 * j);
-            *reinterpret_cast<uint32_t *>(smooth + idx) = __builtin_amdgcn_alignbyte(m1, m0, 2);  // bytes 2 .. 5: the four centres
-            *reinterpret_cast<uint2 *>(grad + idx) = make_uint2(gw[0], gw[1]);
-            *reinterpret_cast<uint32_t *>(dir + idx) = dw;
-        }
-        return;
-    }
-    // source tile with halo 3
-    for (int i = tid; i < (SY + 6) * (SX + 6); i += 256) {
-        const int r = i / (SX + 6), c = i - r * (SX + 6);
-        const int gy = stag_reflect101(y0 - 3 + r, H), gx = stag_reflect101(x0 - 3 + c, W);
-        s_src[r][c] = src[(long long)gy * stride + gx];
-    }
-    __syncthreads();
-    // horizontal pass for the smoothed region with halo 1: columns x0-1 .. x0+SX, all SY+6 rows
-    for (int i = tid; i < (SY + 6) * (SX + 2); i += 256) {
-        const int r = i / (SX + 2), c = i - r * (SX + 2);  // smoothed column x0 - 1 + c  <->  source column index c + 2
-        const uint8_t *p = &s_src[r][c];
-        s_h[r][c] = (uint16_t)(p[0] + 4 * p[1] + 6 * p[2] + 4 * p[3] + p[4]);
-    }
-    __syncthreads();
-    // vertical pass: rows y0-1 .. y0+SY
-    for (int i = tid; i < (SY + 2) * (SX + 2); i += 256) {
-        const int r = i / (SX + 2), c = i - r * (SX + 2);  // smoothed row y0 - 1 + r  <->  s_h rows r .. r + 4
-        const int acc = s_h[r][c] + 4 * s_h[r + 1][c] + 6 * s_h[r + 2][c] + 4 * s_h[r + 3][c] + s_h[r + 4][c];
-        s_sm[r][c] = (uint8_t)((acc + 128) >> 8);
-    }
-    __syncthreads();
-    // Prewitt on the smoothed image
-    for (int i = tid; i < SY * SX; i += 256) {
-        const int r = i / SX, c = i - r * SX;
-        const int gy = y0 + r, gx = x0 + c;
-        if (gy >= H || gx >= W) continue;
-        const long long idx = (long long)gy * W + gx;
-        // NOTE: at image borders the halo of s_sm holds smoothed values of REFLECTED coordinates, which the reference never
-        // reads: border pixels get the constant below
-        smooth[idx] = s_sm[r + 1][c + 1];
-        if (gy == 0 || gy == H - 1 || gx == 0 || gx == W - 1) {
-            grad[idx] = (int16_t)(grad_thresh - 1);
-            dir[idx] = 0;  // (the reference leaves these unwritten)
-            continue;
-        }
-        const int A = s_sm[r][c], B = s_sm[r][c + 1], C = s_sm[r][c + 2];
-        const int D = s_sm[r + 1][c], E = s_sm[r + 1][c + 2];
-        const int F = s_sm[r + 2][c], G = s_sm[r + 2][c + 1], Hh = s_sm[r + 2][c + 2];
-        const int com1 = Hh - A, com2 = C - F;
-        int gxv = com1 + com2 + (E - D), gyv = com1 - com2 + (G - B);
-        gxv = gxv < 0 ? -gxv : gxv;
-        gyv = gyv < 0 ? -gyv : gyv;
-        const int sum = gxv + gyv;
-        grad[idx] = (int16_t)sum;
-        dir[idx] = sum >= grad_thresh ? (gxv >= gyv ? STAG_EDGE_VERTICAL : STAG_EDGE_HORIZONTAL) : 0;
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_smooth_grad(const uint8_t *__restrict__ src, int stride, int W, int H, int grad_thresh, uint8_t *__restrict__ smooth, int16_t *__restrict__ grad, uint8_t *__restrict__ dir)
-{
-    k_stag_smooth_grad_impl(src, stride, W, H, grad_thresh, smooth, grad, dir);
-}
 struct k_stag_smooth_grad_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const uint8_t *__restrict__ src, int stride, int W, int H, int grad_thresh, uint8_t *__restrict__ smooth, int16_t *__restrict__ grad, uint8_t *__restrict__ dir) const { k_stag_smooth_grad_impl(src, stride, W, H, grad_thresh, smooth, grad, dir); }
+    __device__ __forceinline__ void operator()(const uint8_t *__restrict__ src, int stride, int W, int H, int grad_thresh,
+                                               uint8_t *__restrict__ smooth, int16_t *__restrict__ grad,
+                                               uint8_t *__restrict__ dir) const
+    {
+        __shared__ __attribute__((aligned(16))) uint8_t s_src[SY + 6][SX + 6 + 2];
+        __shared__ __attribute__((aligned(16))) uint16_t s_h[SY + 6][SX + 4];  // (68 columns: the four-pixel path keeps x0 - 2 .. x0 + 65)
+        __shared__ __attribute__((aligned(16))) uint8_t s_sm[SY + 2][SX + 2 + 2];
+        const int x0 = blockIdx.x * SX, y0 = blockIdx.y * SY;
+        const int tid = threadIdx.x;
+        // (round 6) INTERIOR tiles -- no reflected coordinate, no image-border pixel, rows that can be read and written as 32-bit words:
+        // 90 % of a 1080p frame -- take four pixels a thread.  The byte-a-thread form below issued ~115 VALU instructions per 64 pixels
+        // (five LDS bytes + four multiply-adds per tap pass, eight bytes per Prewitt, divisions by 70 and 66 for the tile indices) and
+        // was bound by that, alone on the chip, not by HBM.  Here a tap pass is one v_dot4_u32_u8 per output on bytes shifted into place
+        // by v_alignbyte (horizontal) or packed 16-bit arithmetic on two columns at once (vertical: the sums stay below 65 536), and
+        // Prewitt works on the column sums of three rows.  The same integers as below, pixel for pixel.
+        if (x0 >= 4 && x0 + SX + 4 <= W && y0 >= 3 && y0 + SY + 3 <= H && ((stride | W) & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 3) == 0) {
+            // bytes x0 - 4 .. x0 + 67 of rows y0 - 3 .. y0 + 18, as words
+            uint32_t(*w_src)[18] = reinterpret_cast<uint32_t(*)[18]>(&s_src[0][0]);  // 22 x 18 words = 1 584 bytes of the 1 584 there
+            uint32_t(*w_h)[34] = reinterpret_cast<uint32_t(*)[34]>(&s_h[0][0]);       // 22 x 34 words: two smoothed columns a word
+            uint32_t(*w_sm)[17] = reinterpret_cast<uint32_t(*)[17]>(&s_sm[0][0]);     // 18 x 17 words: four smoothed pixels a word
+            for (int i = tid; i < 22 * 18; i += 256) {
+                const int r = i / 18, c = i - r * 18;
+                w_src[r][c] = *reinterpret_cast<const uint32_t *>(src + (long long)(y0 - 3 + r) * stride + (x0 - 4 + 4 * c));
+            }
+            __syncthreads();
+            // horizontal [1 4 6 4 1]: item (row r, group j) = smoothed columns x0 - 2 + 4 j + k, k = 0 .. 3, from bytes k .. k + 4 of words j, j + 1
+            for (int i = tid; i < 22 * 17; i += 256) {
+                const int r = i / 17, j = i - r * 17;
+                const uint32_t d0 = w_src[r][j], d1 = w_src[r][j + 1];
+                const uint32_t h0 = __builtin_amdgcn_udot4(d0, 0x04060401u, d1 & 0xffu, false);
+                const uint32_t h1 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 1), 0x04060401u, (d1 >> 8) & 0xffu, false);
+                const uint32_t h2 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 2), 0x04060401u, (d1 >> 16) & 0xffu, false);
+                const uint32_t h3 = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 3), 0x04060401u, d1 >> 24, false);
+                w_h[r][2 * j] = h0 | (h1 << 16);
+                w_h[r][2 * j + 1] = h2 | (h3 << 16);
+            }
+            __syncthreads();
+            // vertical pass, two columns a word: smoothed row y0 - 1 + r from rows r .. r + 4; (acc + 128) >> 8 per 16-bit half
+            for (int i = tid; i < 18 * 17; i += 256) {
+                const int r = i / 17, j = i - r * 17;
+                uint32_t o[2];
+#pragma unroll
+                for (int q = 0; q < 2; q++) {
+                    const uint32_t a = w_h[r][2 * j + q], b = w_h[r + 1][2 * j + q], c = w_h[r + 2][2 * j + q], d = w_h[r + 3][2 * j + q],
+                                   e = w_h[r + 4][2 * j + q];
+                    // a + e + 4 (b + d) + 6 c <= 16 * 4 080 = 65 280 in each half: no carry crosses the halves
+                    const uint32_t acc = (a + e) + 4u * (b + d) + 6u * c + 0x00800080u;
+                    o[q] = (acc >> 8) & 0x00ff00ffu;
+                }
+                w_sm[r][j] = (o[0] & 0xffu) | ((o[0] >> 8) & 0xff00u) | ((o[1] & 0xffu) << 16) | ((o[1] << 8) & 0xff000000u);
+            }
+            __syncthreads();
+            // Prewitt: thread = four pixels x0 + 4 j + k of row y0 + r; their 3 x 3 neighbourhoods are bytes 1 + k .. 3 + k of words j, j + 1
+            // (smoothed columns x0 - 2 + 4 j ...) of rows r .. r + 2.  gx = S(x + 1) - S(x - 1) with S = the column's sum over the three
+            // rows, gy = (bottom - top) summed over the three columns: ComputeGradient's com1 / com2 form, regrouped (integers: exact)
+            {
+                const int r = tid >> 4, j = tid & 15;
+                const uint32_t t0 = w_sm[r][j], t1 = w_sm[r][j + 1], m0 = w_sm[r + 1][j], m1 = w_sm[r + 1][j + 1], b0 = w_sm[r + 2][j],
+                               b1 = w_sm[r + 2][j + 1];
+                int S[8], D[8];
+#pragma unroll
+                for (int p = 1; p <= 6; p++) {
+                    const int tp = (int)(((p < 4 ? t0 : t1) >> (8 * (p & 3))) & 0xffu), mp = (int)(((p < 4 ? m0 : m1) >> (8 * (p & 3))) & 0xffu),
+                              bp = (int)(((p < 4 ? b0 : b1) >> (8 * (p & 3))) & 0xffu);
+                    S[p] = tp + mp + bp;
+                    D[p] = bp - tp;
+                }
+                uint32_t gw[2] = {0u, 0u}, dw = 0u;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    int gxv = S[3 + k] - S[1 + k], gyv = D[1 + k] + D[2 + k] + D[3 + k];
+                    gxv = gxv < 0 ? -gxv : gxv;
+                    gyv = gyv < 0 ? -gyv : gyv;
+                    const int sum = gxv + gyv;
+                    gw[k >> 1] |= (uint32_t)sum << (16 * (k & 1));
+                    dw |= (uint32_t)(sum >= grad_thresh ? (gxv >= gyv ? STAG_EDGE_VERTICAL : STAG_EDGE_HORIZONTAL) : 0) << (8 * k);
+                }
+                const long long idx = (long long)(y0 + r) * W + (x0 + 4 * j);
+                *reinterpret_cast<uint32_t *>(smooth + idx) = __builtin_amdgcn_alignbyte(m1, m0, 2);  // bytes 2 .. 5: the four centres
+                *reinterpret_cast<uint2 *>(grad + idx) = make_uint2(gw[0], gw[1]);
+                *reinterpret_cast<uint32_t *>(dir + idx) = dw;
+            }
+            return;
+        }
+        // source tile with halo 3
+        for (int i = tid; i < (SY + 6) * (SX + 6); i += 256) {
+            const int r = i / (SX + 6), c = i - r * (SX + 6);
+            const int gy = stag_reflect101(y0 - 3 + r, H), gx = stag_reflect101(x0 - 3 + c, W);
+            s_src[r][c] = src[(long long)gy * stride + gx];
+        }
+        __syncthreads();
+        // horizontal pass for the smoothed region with halo 1: columns x0-1 .. x0+SX, all SY+6 rows
+        for (int i = tid; i < (SY + 6) * (SX + 2); i += 256) {
+            const int r = i / (SX + 2), c = i - r * (SX + 2);  // smoothed column x0 - 1 + c  <->  source column index c + 2
+            const uint8_t *p = &s_src[r][c];
+            s_h[r][c] = (uint16_t)(p[0] + 4 * p[1] + 6 * p[2] + 4 * p[3] + p[4]);
+        }
+        __syncthreads();
+        // vertical pass: rows y0-1 .. y0+SY
+        for (int i = tid; i < (SY + 2) * (SX + 2); i += 256) {
+            const int r = i / (SX + 2), c = i - r * (SX + 2);  // smoothed row y0 - 1 + r  <->  s_h rows r .. r + 4
+            const int acc = s_h[r][c] + 4 * s_h[r + 1][c] + 6 * s_h[r + 2][c] + 4 * s_h[r + 3][c] + s_h[r + 4][c];
+            s_sm[r][c] = (uint8_t)((acc + 128) >> 8);
+        }
+        __syncthreads();
+        // Prewitt on the smoothed image
+        for (int i = tid; i < SY * SX; i += 256) {
+            const int r = i / SX, c = i - r * SX;
+            const int gy = y0 + r, gx = x0 + c;
+            if (gy >= H || gx >= W) continue;
+            const long long idx = (long long)gy * W + gx;
+            // NOTE: at image borders the halo of s_sm holds smoothed values of REFLECTED coordinates, which the reference never
+            // reads: border pixels get the constant below
+            smooth[idx] = s_sm[r + 1][c + 1];
+            if (gy == 0 || gy == H - 1 || gx == 0 || gx == W - 1) {
+                grad[idx] = (int16_t)(grad_thresh - 1);
+                dir[idx] = 0;  // (the reference leaves these unwritten)
+                continue;
+            }
+            const int A = s_sm[r][c], B = s_sm[r][c + 1], C = s_sm[r][c + 2];
+            const int D = s_sm[r + 1][c], E = s_sm[r + 1][c + 2];
+            const int F = s_sm[r + 2][c], G = s_sm[r + 2][c + 1], Hh = s_sm[r + 2][c + 2];
+            const int com1 = Hh - A, com2 = C - F;
+            int gxv = com1 + com2 + (E - D), gyv = com1 - com2 + (G - B);
+            gxv = gxv < 0 ? -gxv : gxv;
+            gyv = gyv < 0 ? -gyv : gyv;
+            const int sum = gxv + gyv;
+            grad[idx] = (int16_t)sum;
+            dir[idx] = sum >= grad_thresh ? (gxv >= gyv ? STAG_EDGE_VERTICAL : STAG_EDGE_HORIZONTAL) : 0;
+        }
+    }
 };
 
 // The smoothed image is 8-bit, so |gx|, |gy| <= 3 * 255 and the gradient value never exceeds 1530: the reference's
@@ -260,205 +248,180 @@ struct k_stag_smooth_grad_fn {
 
 // Anchor points: local gradient maxima across the edge normal (ANCHOR_THRESH, SCAN_INTERVAL as in the reference), counted
 // per (row, gradient value) for the counting sort (global atomics: the anchors are sparse; 16-bit counts, two a word).
-__device__ __forceinline__ void k_stag_anchors_impl(const int16_t *__restrict__ grad, const uint8_t *__restrict__ dir, int W, int H,
-                                                       int grad_thresh, int anchor_thresh, int scan_interval,
-                                                       uint8_t *__restrict__ edge, unsigned *__restrict__ rowhist)
-{
-    // (row and column are carried along the grid-stride loop: one 32-bit division per thread instead of a 64-bit one per pixel --
-    //  the images are < 2^31 pixels, fid_stag_create caps both sides at 8 191)
-    const unsigned total = (unsigned)W * (unsigned)H, stride = gridDim.x * 256u;
-    const unsigned first = blockIdx.x * 256u + threadIdx.x;
-    const int si = (int)(stride / (unsigned)W), sj = (int)(stride - (unsigned)si * (unsigned)W);
-    int i = (int)(first / (unsigned)W), j = (int)(first - (unsigned)i * (unsigned)W);
-    for (unsigned idx = first; idx < total; idx += stride, i += si, j += sj) {
-        if (j >= W) {
-            j -= W;
-            i++;
-        }
-        uint8_t e = 0;
-        if (i >= 2 && i < H - 2 && j >= 2 && j < W - 2) {
-            // rows that are not a multiple of SCAN_INTERVAL are scanned at columns SCAN_INTERVAL, 2 SCAN_INTERVAL, ...
-            const bool scanned = scan_interval == 1 || (i % scan_interval == 0) || (j >= scan_interval && j % scan_interval == 0);
-            const int g = grad[idx];
-            if (scanned && g >= grad_thresh) {
-                int d1, d2;
-                if (dir[idx] == STAG_EDGE_VERTICAL) {
-                    d1 = g - grad[idx - 1];
-                    d2 = g - grad[idx + 1];
-                } else {
-                    d1 = g - grad[idx - W];
-                    d2 = g - grad[idx + W];
-                }
-                if (d1 >= anchor_thresh && d2 >= anchor_thresh) {
-                    e = STAG_ANCHOR_PIXEL;
-                    // SortAnchorsByGradValue only counts anchors with 1 <= i < H-1, 1 <= j < W-1: all of these qualify
-                    // (two 16-bit counts a word -- a row holds < 2^16 anchors: half the clearing, summing and placing traffic)
-                    atomicAdd(&rowhist[(size_t)i * (STAG_BINS / 2) + (g >> 1)], 1u << ((g & 1) * 16));
-                }
-            }
-        }
-        edge[idx] = e;
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_anchors(const int16_t *__restrict__ grad, const uint8_t *__restrict__ dir, int W, int H, int grad_thresh, int anchor_thresh, int scan_interval, uint8_t *__restrict__ edge, unsigned *__restrict__ rowhist)
-{
-    k_stag_anchors_impl(grad, dir, W, H, grad_thresh, anchor_thresh, scan_interval, edge, rowhist);
-}
 struct k_stag_anchors_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, const uint8_t *__restrict__ dir, int W, int H, int grad_thresh, int anchor_thresh, int scan_interval, uint8_t *__restrict__ edge, unsigned *__restrict__ rowhist) const { k_stag_anchors_impl(grad, dir, W, H, grad_thresh, anchor_thresh, scan_interval, edge, rowhist); }
+    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, const uint8_t *__restrict__ dir, int W, int H,
+                                               int grad_thresh, int anchor_thresh, int scan_interval,
+                                               uint8_t *__restrict__ edge, unsigned *__restrict__ rowhist) const
+    {
+        // (row and column are carried along the grid-stride loop: one 32-bit division per thread instead of a 64-bit one per pixel --
+        //  the images are < 2^31 pixels, fid_stag_create caps both sides at 8 191)
+        const unsigned total = (unsigned)W * (unsigned)H, stride = gridDim.x * 256u;
+        const unsigned first = blockIdx.x * 256u + threadIdx.x;
+        const int si = (int)(stride / (unsigned)W), sj = (int)(stride - (unsigned)si * (unsigned)W);
+        int i = (int)(first / (unsigned)W), j = (int)(first - (unsigned)i * (unsigned)W);
+        for (unsigned idx = first; idx < total; idx += stride, i += si, j += sj) {
+            if (j >= W) {
+                j -= W;
+                i++;
+            }
+            uint8_t e = 0;
+            if (i >= 2 && i < H - 2 && j >= 2 && j < W - 2) {
+                // rows that are not a multiple of SCAN_INTERVAL are scanned at columns SCAN_INTERVAL, 2 SCAN_INTERVAL, ...
+                const bool scanned = scan_interval == 1 || (i % scan_interval == 0) || (j >= scan_interval && j % scan_interval == 0);
+                const int g = grad[idx];
+                if (scanned && g >= grad_thresh) {
+                    int d1, d2;
+                    if (dir[idx] == STAG_EDGE_VERTICAL) {
+                        d1 = g - grad[idx - 1];
+                        d2 = g - grad[idx + 1];
+                    } else {
+                        d1 = g - grad[idx - W];
+                        d2 = g - grad[idx + W];
+                    }
+                    if (d1 >= anchor_thresh && d2 >= anchor_thresh) {
+                        e = STAG_ANCHOR_PIXEL;
+                        // SortAnchorsByGradValue only counts anchors with 1 <= i < H-1, 1 <= j < W-1: all of these qualify
+                        // (two 16-bit counts a word -- a row holds < 2^16 anchors: half the clearing, summing and placing traffic)
+                        atomicAdd(&rowhist[(size_t)i * (STAG_BINS / 2) + (g >> 1)], 1u << ((g & 1) * 16));
+                    }
+                }
+            }
+            edge[idx] = e;
+        }
+    }
 };
 
 // anchors per (band of STAG_BAND_ROWS rows, gradient value)
-__device__ __forceinline__ void k_stag_bandsum_impl(const unsigned *__restrict__ rowhist, int H, unsigned *__restrict__ bandhist)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x, band = blockIdx.y;
-    unsigned acc = 0;
-#pragma unroll
-    for (int r = 0; r < STAG_BAND_ROWS; r++) {
-        const int row = band * STAG_BAND_ROWS + r;
-        if (row < H) acc += (rowhist[(size_t)row * (STAG_BINS / 2) + (g >> 1)] >> ((g & 1) * 16)) & 0xffffu;
-    }
-    bandhist[(size_t)band * STAG_BINS + g] = acc;
-}
-__global__ __launch_bounds__(256) void k_stag_bandsum(const unsigned *__restrict__ rowhist, int H, unsigned *__restrict__ bandhist)
-{
-    k_stag_bandsum_impl(rowhist, H, bandhist);
-}
 struct k_stag_bandsum_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const unsigned *__restrict__ rowhist, int H, unsigned *__restrict__ bandhist) const { k_stag_bandsum_impl(rowhist, H, bandhist); }
+    __device__ __forceinline__ void operator()(const unsigned *__restrict__ rowhist, int H, unsigned *__restrict__ bandhist) const
+    {
+        const int g = blockIdx.x * 256 + threadIdx.x, band = blockIdx.y;
+        unsigned acc = 0;
+#pragma unroll
+        for (int r = 0; r < STAG_BAND_ROWS; r++) {
+            const int row = band * STAG_BAND_ROWS + r;
+            if (row < H) acc += (rowhist[(size_t)row * (STAG_BINS / 2) + (g >> 1)] >> ((g & 1) * 16)) & 0xffffu;
+        }
+        bandhist[(size_t)band * STAG_BINS + g] = acc;
+    }
 };
 
 // per gradient value: bands from the LAST to the first (the reference's --C[grad] placement leaves the offsets of one
 // gradient value in descending order) -> start of each band inside the value's bucket; tot[g] = size of the bucket
-__device__ __forceinline__ void k_stag_bandscan_impl(unsigned *__restrict__ bandhist, int nbands, unsigned *__restrict__ tot)
-{
-    const int g = blockIdx.x * 256 + threadIdx.x;
-    unsigned acc = 0;
-    int b = nbands - 1;
-    for (; b >= 15; b -= 16) {  // sixteen independent loads in flight (four until round 6: with 4-row bands a 1080p frame has 270 of them)
-        unsigned n[16];
-#pragma unroll
-        for (int k = 0; k < 16; k++) n[k] = bandhist[(size_t)(b - k) * STAG_BINS + g];
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            bandhist[(size_t)(b - k) * STAG_BINS + g] = acc;
-            acc += n[k];
-        }
-    }
-    for (; b >= 0; b--) {
-        const unsigned n = bandhist[(size_t)b * STAG_BINS + g];
-        bandhist[(size_t)b * STAG_BINS + g] = acc;
-        acc += n;
-    }
-    tot[g] = acc;
-}
-__global__ __launch_bounds__(256) void k_stag_bandscan(unsigned *__restrict__ bandhist, int nbands, unsigned *__restrict__ tot)
-{
-    k_stag_bandscan_impl(bandhist, nbands, tot);
-}
 struct k_stag_bandscan_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(unsigned *__restrict__ bandhist, int nbands, unsigned *__restrict__ tot) const { k_stag_bandscan_impl(bandhist, nbands, tot); }
+    __device__ __forceinline__ void operator()(unsigned *__restrict__ bandhist, int nbands, unsigned *__restrict__ tot) const
+    {
+        const int g = blockIdx.x * 256 + threadIdx.x;
+        unsigned acc = 0;
+        int b = nbands - 1;
+        for (; b >= 15; b -= 16) {  // sixteen independent loads in flight (four until round 6: with 4-row bands a 1080p frame has 270 of them)
+            unsigned n[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) n[k] = bandhist[(size_t)(b - k) * STAG_BINS + g];
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                bandhist[(size_t)(b - k) * STAG_BINS + g] = acc;
+                acc += n[k];
+            }
+        }
+        for (; b >= 0; b--) {
+            const unsigned n = bandhist[(size_t)b * STAG_BINS + g];
+            bandhist[(size_t)b * STAG_BINS + g] = acc;
+            acc += n;
+        }
+        tot[g] = acc;
+    }
 };
 
 // exclusive prefix sums over the gradient values (one workgroup): bstart[g] = number of anchors with a smaller gradient
-__device__ __forceinline__ void k_stag_scan_impl(const unsigned *__restrict__ tot, unsigned *__restrict__ bstart, unsigned *__restrict__ n_anchors)
-{
-    __shared__ unsigned s_part[512];
-    const int tid = threadIdx.x;
-    constexpr int PER = STAG_BINS / 512;
-    unsigned loc[PER];
-    unsigned acc = 0;
-    for (int k = 0; k < PER; k++) {
-        loc[k] = acc;
-        acc += tot[tid * PER + k];
-    }
-    s_part[tid] = acc;
-    __syncthreads();
-    for (int d = 1; d < 512; d <<= 1) {
-        unsigned v = tid >= d ? s_part[tid - d] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    const unsigned base = tid ? s_part[tid - 1] : 0u;
-    for (int k = 0; k < PER; k++) bstart[tid * PER + k] = base + loc[k];
-    if (tid == 511) *n_anchors = s_part[511];
-}
-__global__ __launch_bounds__(512) void k_stag_scan(const unsigned *__restrict__ tot, unsigned *__restrict__ bstart, unsigned *__restrict__ n_anchors)
-{
-    k_stag_scan_impl(tot, bstart, n_anchors);
-}
 struct k_stag_scan_fn {
     static constexpr int kBounds = 512;
-    __device__ __forceinline__ void operator()(const unsigned *__restrict__ tot, unsigned *__restrict__ bstart, unsigned *__restrict__ n_anchors) const { k_stag_scan_impl(tot, bstart, n_anchors); }
+    __device__ __forceinline__ void operator()(const unsigned *__restrict__ tot, unsigned *__restrict__ bstart, unsigned *__restrict__ n_anchors) const
+    {
+        __shared__ unsigned s_part[512];
+        const int tid = threadIdx.x;
+        constexpr int PER = STAG_BINS / 512;
+        unsigned loc[PER];
+        unsigned acc = 0;
+        for (int k = 0; k < PER; k++) {
+            loc[k] = acc;
+            acc += tot[tid * PER + k];
+        }
+        s_part[tid] = acc;
+        __syncthreads();
+        for (int d = 1; d < 512; d <<= 1) {
+            unsigned v = tid >= d ? s_part[tid - d] : 0u;
+            __syncthreads();
+            s_part[tid] += v;
+            __syncthreads();
+        }
+        const unsigned base = tid ? s_part[tid - 1] : 0u;
+        for (int k = 0; k < PER; k++) bstart[tid * PER + k] = base + loc[k];
+        if (tid == 511) *n_anchors = s_part[511];
+    }
 };
 
 // Placement: one workgroup per band, one wave per row.  LDS holds, per (row of the band, gradient value), the next free
 // slot: bucket start + band start + anchors of that value in the LATER rows of the band.  Every wave then goes through
 // its row from the last column to the first, 64 columns at a time; lanes with the same gradient value take consecutive
 // slots in descending column order.  No sort, no atomics: the order is exactly the reference's.
-__device__ __forceinline__ void k_stag_place_impl(const int16_t *__restrict__ grad, const uint8_t *__restrict__ edge, int W, int H,
-                                                                    const unsigned *__restrict__ rowhist, const unsigned *__restrict__ bandstart,
-                                                                    const unsigned *__restrict__ bstart, int32_t *__restrict__ sorted)
-{
-    __shared__ unsigned s_slot[STAG_BAND_ROWS][STAG_BINS];
-    const int band = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    for (int g = tid; g < STAG_BINS; g += 64 * STAG_BAND_ROWS) {
-        unsigned n[STAG_BAND_ROWS];
+struct k_stag_place_fn {
+    static constexpr int kBounds = 64 * STAG_BAND_ROWS;
+    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, const uint8_t *__restrict__ edge, int W, int H,
+                                               const unsigned *__restrict__ rowhist, const unsigned *__restrict__ bandstart,
+                                               const unsigned *__restrict__ bstart, int32_t *__restrict__ sorted) const
+    {
+        __shared__ unsigned s_slot[STAG_BAND_ROWS][STAG_BINS];
+        const int band = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+        for (int g = tid; g < STAG_BINS; g += 64 * STAG_BAND_ROWS) {
+            unsigned n[STAG_BAND_ROWS];
 #pragma unroll
-        for (int r = 0; r < STAG_BAND_ROWS; r++) {
-            const int row = band * STAG_BAND_ROWS + r;
-            n[r] = row < H ? (rowhist[(size_t)row * (STAG_BINS / 2) + (g >> 1)] >> ((g & 1) * 16)) & 0xffffu : 0u;
+            for (int r = 0; r < STAG_BAND_ROWS; r++) {
+                const int row = band * STAG_BAND_ROWS + r;
+                n[r] = row < H ? (rowhist[(size_t)row * (STAG_BINS / 2) + (g >> 1)] >> ((g & 1) * 16)) & 0xffffu : 0u;
+            }
+            unsigned acc = bstart[g] + bandstart[(size_t)band * STAG_BINS + g];
+#pragma unroll
+            for (int r = STAG_BAND_ROWS - 1; r >= 0; r--) {
+                s_slot[r][g] = acc;
+                acc += n[r];
+            }
         }
-        unsigned acc = bstart[g] + bandstart[(size_t)band * STAG_BINS + g];
+        __syncthreads();
+        const int row = band * STAG_BAND_ROWS + w;
+        if (row >= H) return;
+        const long long rbase = (long long)row * W;
+        const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
+        unsigned *slot = s_slot[w];
+        for (int c4 = ((W - 1) >> 8) << 8; c4 >= 0; c4 -= 256) {
+            uint8_t e[4];
 #pragma unroll
-        for (int r = STAG_BAND_ROWS - 1; r >= 0; r--) {
-            s_slot[r][g] = acc;
-            acc += n[r];
-        }
-    }
-    __syncthreads();
-    const int row = band * STAG_BAND_ROWS + w;
-    if (row >= H) return;
-    const long long rbase = (long long)row * W;
-    const unsigned long long above = lane == 63 ? 0ull : ~0ull << (lane + 1);
-    unsigned *slot = s_slot[w];
-    for (int c4 = ((W - 1) >> 8) << 8; c4 >= 0; c4 -= 256) {
-        uint8_t e[4];
+            for (int k = 0; k < 4; k++) {
+                const int col = c4 + k * 64 + lane;
+                e[k] = col < W ? edge[rbase + col] : (uint8_t)0;
+            }
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int col = c4 + k * 64 + lane;
-            e[k] = col < W ? edge[rbase + col] : (uint8_t)0;
-        }
-#pragma unroll
-        for (int k = 3; k >= 0; k--) {
-            const int col = c4 + k * 64 + lane;
-            const bool is_anchor = e[k] == STAG_ANCHOR_PIXEL;
-            unsigned long long pending = __ballot(is_anchor);
-            if (!pending) continue;
-            const int gv = is_anchor ? (int)grad[rbase + col] : -1;
-            while (pending) {
-                const int src = __builtin_ctzll(pending);
-                const int g0 = __builtin_amdgcn_readlane(gv, src);
-                const unsigned long long m = __ballot(gv == g0);
-                const unsigned base = slot[g0];
-                if (gv == g0) sorted[base + __builtin_popcountll(m & above)] = (int32_t)(rbase + col);
-                if (lane == src) slot[g0] = base + (unsigned)__builtin_popcountll(m);
-                pending &= ~m;
+            for (int k = 3; k >= 0; k--) {
+                const int col = c4 + k * 64 + lane;
+                const bool is_anchor = e[k] == STAG_ANCHOR_PIXEL;
+                unsigned long long pending = __ballot(is_anchor);
+                if (!pending) continue;
+                const int gv = is_anchor ? (int)grad[rbase + col] : -1;
+                while (pending) {
+                    const int src = __builtin_ctzll(pending);
+                    const int g0 = __builtin_amdgcn_readlane(gv, src);
+                    const unsigned long long m = __ballot(gv == g0);
+                    const unsigned base = slot[g0];
+                    if (gv == g0) sorted[base + __builtin_popcountll(m & above)] = (int32_t)(rbase + col);
+                    if (lane == src) slot[g0] = base + (unsigned)__builtin_popcountll(m);
+                    pending &= ~m;
+                }
             }
         }
     }
-}
-__global__ __launch_bounds__(64 * STAG_BAND_ROWS) void k_stag_place(const int16_t *__restrict__ grad, const uint8_t *__restrict__ edge, int W, int H, const unsigned *__restrict__ rowhist, const unsigned *__restrict__ bandstart, const unsigned *__restrict__ bstart, int32_t *__restrict__ sorted)
-{
-    k_stag_place_impl(grad, edge, W, H, rowhist, bandstart, bstart, sorted);
-}
-struct k_stag_place_fn {
-    static constexpr int kBounds = 64 * STAG_BAND_ROWS;
-    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, const uint8_t *__restrict__ edge, int W, int H, const unsigned *__restrict__ rowhist, const unsigned *__restrict__ bandstart, const unsigned *__restrict__ bstart, int32_t *__restrict__ sorted) const { k_stag_place_impl(grad, edge, W, H, rowhist, bandstart, bstart, sorted); }
 };
 
 #include "fid_stag_route.hip"
@@ -795,16 +758,16 @@ fid_status fid_stag_create(int libraryHD, int errorCorrection, int max_width, in
         c->no_sparse = sp && atoi(sp) == 0 ? 1 : 0;
         const char *sl = getenv("FID_STAG_SPLIT_LDS");
         c->split_lds_env = sl ? atoi(sl) : -1;
-        ok = ok && hipFuncSetAttribute((const void *)k_stag_route_walk, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
-             hipFuncSetAttribute((const void *)k_stag_comp_sort_big, hipFuncAttributeMaxDynamicSharedMemorySize, STAG_SORT_BIG * 4) == hipSuccess &&
+        ok = ok && hipFuncSetAttribute((const void *)stag_frame_entry<k_stag_route_walk_fn<false>>(), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
+             hipFuncSetAttribute((const void *)stag_frame_entry<k_stag_comp_sort_big_fn>(), hipFuncAttributeMaxDynamicSharedMemorySize, STAG_SORT_BIG * 4) == hipSuccess &&
              // (and their group-mode trampolines, fid_stag_batch.h)
-             hipFuncSetAttribute((const void *)k_stag_batch<k_stag_route_walk_fn>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
+             hipFuncSetAttribute((const void *)k_stag_batch<k_stag_route_walk_fn<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess &&
              hipFuncSetAttribute((const void *)k_stag_batch<k_stag_comp_sort_big_fn>, hipFuncAttributeMaxDynamicSharedMemorySize, STAG_SORT_BIG * 4) == hipSuccess &&
-             hipFuncSetAttribute((const void *)k_stag_split_lines, hipFuncAttributeMaxDynamicSharedMemorySize, SL_LDS_BYTES(1024)) == hipSuccess &&
-             hipFuncSetAttribute((const void *)k_stag_batch<k_stag_split_lines_fn>, hipFuncAttributeMaxDynamicSharedMemorySize, SL_LDS_BYTES(1024)) == hipSuccess;
+             hipFuncSetAttribute((const void *)stag_frame_entry<k_stag_split_lines_fn<false>>(), hipFuncAttributeMaxDynamicSharedMemorySize, SL_LDS_BYTES(1024)) == hipSuccess &&
+             hipFuncSetAttribute((const void *)k_stag_batch<k_stag_split_lines_fn<true>>, hipFuncAttributeMaxDynamicSharedMemorySize, SL_LDS_BYTES(1024)) == hipSuccess;
         if (getenv("FID_VERBOSE"))
             fprintf(stderr, "fid stag: frames per merged launch: route_walk %d, route_extract %d, quads %d, decode %d, smooth_grad %d\n",
-                    StagTab<k_stag_route_walk_fn>::kMax, StagTab<k_stag_route_extract_fn>::kMax, StagTab<k_stag_quads_fn>::kMax,
+                    StagTab<k_stag_route_walk_fn<true>>::kMax, StagTab<k_stag_route_extract_fn<true>>::kMax, StagTab<k_stag_quads_fn<true>>::kMax,
                     StagTab<k_stag_decode_fn>::kMax, StagTab<k_stag_smooth_grad_fn>::kMax);
     }
     ok = ok && slab.take((void **)&c->d_smooth2, n) && slab.take((void **)&c->d_vgrad, n * 2) &&
@@ -1281,24 +1244,24 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
                 //  and at 99 VGPRs the kernel holds four workgroups per CU whether they own 8 or 37 KB)
                 const int lds = !c->route_tile ? 0 : (grouped ? j.lds_cap : ((cur[10] + 1023) / 1024) * 1024);
                 if (grouped && c->route_tile && lds > STAG_SMALL_TILE) {
-                    // (two launches by class: see k_stag_route_walk_impl; both grids cover every rank, a workgroup beyond its class returns)
-                    STAG_LAUNCH(k_stag_route_walk, dim3(nc), dim3(256), (size_t)lds, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_sorted,
+                    // (two launches by class: see k_stag_route_walk_fn; both grids cover every rank, a workgroup beyond its class returns)
+                    STAG_LAUNCH_FM(k_stag_route_walk, dim3(nc), dim3(256), (size_t)lds, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_sorted,
                                        c->d_aslots, c->d_label, 16, lds | no_sparse, c->d_prodflag, ovf, 1);
-                    STAG_LAUNCH(k_stag_route_walk, dim3(nc), dim3(256), (size_t)STAG_SMALL_TILE, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder,
+                    STAG_LAUNCH_FM(k_stag_route_walk, dim3(nc), dim3(256), (size_t)STAG_SMALL_TILE, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder,
                                        c->d_sorted, c->d_aslots, c->d_label, 16, STAG_SMALL_TILE | no_sparse, c->d_prodflag, ovf, 2);
                 } else {
-                    STAG_LAUNCH(k_stag_route_walk, dim3(nc), dim3(256), (size_t)lds, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_sorted,
+                    STAG_LAUNCH_FM(k_stag_route_walk, dim3(nc), dim3(256), (size_t)lds, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_sorted,
                                        c->d_aslots, c->d_label, 16, lds | no_sparse, c->d_prodflag, ovf, 0);
                 }
             }
             STAG_LAUNCH(k_stag_next_above, dim3(1), dim3(scan_threads), 0, st, c->d_prodflag, c->d_n, c->d_next);
             if (nc > 0 && grouped) {  // (two launches by class, like the walk: the big components, then the small ones four workgroups to a CU)
-                STAG_LAUNCH(k_stag_route_extract_big, dim3(nc), dim3(64), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_next,
+                STAG_LAUNCH_FM(k_stag_route_extract_big, dim3(nc), dim3(64), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_next,
                                    c->d_n, c->d_blkpix, c->d_blksegs, c->d_blkwhere, ovf, 1);
-                STAG_LAUNCH(k_stag_route_extract_small, dim3((nc + 3) / 4), dim3(256), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder,
+                STAG_LAUNCH_FM(k_stag_route_extract_small, dim3((nc + 3) / 4), dim3(256), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder,
                                    c->d_next, c->d_n, c->d_blkpix, c->d_blksegs, c->d_blkwhere, ovf, 2);
             } else if (nc > 0) {
-                STAG_LAUNCH(k_stag_route_extract, dim3((nc + 3) / 4), dim3(256), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_next,
+                STAG_LAUNCH_FM(k_stag_route_extract, dim3((nc + 3) / 4), dim3(256), 0, st, j.R, A, c->d_comps, c->d_cursors, c->d_corder, c->d_next,
                                    c->d_n, c->d_blkpix, c->d_blksegs, c->d_blkwhere, ovf, 0);
             }
             {
@@ -1392,13 +1355,13 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
             int lds_pix = c->split_lds_env >= 0 ? c->split_lds_env : (grouped ? 256 : 1024);
             lds_pix = lds_pix > 1024 ? 1024 : lds_pix;
             if (grouped && c->split_lds_env < 0) {
-                // (two launches of one-wave workgroups by segment length: see k_stag_split_lines_impl)
-                STAG_LAUNCH(k_stag_split_lines, dim3(ns), dim3(64), (size_t)sl_lds_wave_bytes(1024), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
+                // (two launches of one-wave workgroups by segment length: see k_stag_split_lines_fn)
+                STAG_LAUNCH_FM(k_stag_split_lines, dim3(ns), dim3(64), (size_t)sl_lds_wave_bytes(1024), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
                                    c->min_line_len, 1.0, c->d_lslots, c->d_lcounts, 1024, 256, 0x7fffffff);
-                STAG_LAUNCH(k_stag_split_lines, dim3(ns), dim3(64), (size_t)sl_lds_wave_bytes(256), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
+                STAG_LAUNCH_FM(k_stag_split_lines, dim3(ns), dim3(64), (size_t)sl_lds_wave_bytes(256), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
                                    c->min_line_len, 1.0, c->d_lslots, c->d_lcounts, 256, -1, 256);
             } else {
-                STAG_LAUNCH(k_stag_split_lines, dim3((ns + 3) / 4), dim3(256), (size_t)SL_LDS_BYTES(lds_pix), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
+                STAG_LAUNCH_FM(k_stag_split_lines, dim3((ns + 3) / 4), dim3(256), (size_t)SL_LDS_BYTES(lds_pix), st, c->d_vsegs, c->d_vtotal, c->d_outpix, PF,
                                    c->min_line_len, 1.0, c->d_lslots, c->d_lcounts, lds_pix, -1, 0x7fffffff);
             }
         }
@@ -1460,7 +1423,7 @@ static fid_status stag_advance_impl(fid_stag_ctx *c, StagJob &j)
         if (STAG_MEMSET(c->d_lrange, 0, (size_t)(ns + 1) * sizeof(int2), st) != hipSuccess) return stag_finish(j, FID_E_HIP);
         if (nl > 0) STAG_LAUNCH(k_stag_line_ranges, dim3((nl + 255) / 256), dim3(256), 0, st, c->d_vlines, c->d_vltotal, c->d_lrange);
         if (ns > 0)
-            STAG_LAUNCH(k_stag_quads, dim3((ns + 3) / 4), dim3(256), 0, st, c->d_vlines, c->d_lrange, c->d_vtotal, c->d_vsegs, c->d_outpix, c->d_src,
+            STAG_LAUNCH_FM(k_stag_quads, dim3((ns + 3) / 4), dim3(256), 0, st, c->d_vlines, c->d_lrange, c->d_vtotal, c->d_vsegs, c->d_outpix, c->d_src,
                                W, H, c->d_corners, c->d_order, c->d_qslots, c->d_qcounts);
         STAG_LAUNCH(k_stag_scan_counts, dim3(1), dim3(scan_threads), 0, st, c->d_qcounts, c->d_vtotal, c->d_qtotal);
         if (ns > 0)
@@ -1771,7 +1734,7 @@ static fid_status stag_pose_last_run(fid_stag_ctx *c, const fid_camera *camera, 
         POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose_cov<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers,
                                                         c->d_nmarkers, cam, marker_size, c->d_poses, sigma_px, c->d_cov));
     } else {
-        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_pose<CAM_MODEL>, dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers,
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(stag_frame_entry<k_stag_pose_fn<CAM_MODEL>>(), dim3((c->n_markers + 3) / 4), dim3(64), 0, st, c->d_markers,
                                                         c->d_nmarkers, cam, marker_size, c->d_poses));
     }
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
@@ -1839,7 +1802,7 @@ static fid_status stag_bundle_pose_run(fid_stag_ctx *c, const fid_camera &camera
         POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose_cov<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags,
                                                         c->d_lstart, cam, c->d_bposes, sigma_px, c->d_cov));
     } else {
-        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(k_stag_bundle_pose<CAM_MODEL>, dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags,
+        POSE_CAM_DISPATCH(cam.model, hipLaunchKernelGGL(stag_frame_entry<k_stag_bundle_pose_fn<CAM_MODEL>>(), dim3(c->n_bundles), dim3(64), 0, st, d_markers, d_n, c->d_ltags,
                                                         c->d_lstart, cam, c->d_bposes));
     }
     if (hipGetLastError() != hipSuccess) return FID_E_HIP;
@@ -1945,9 +1908,9 @@ static fid_status stag_batch_groups(fid_stag_ctx *const *ctxs, int32_t nctx, con
 {
     // a group is at most as large as the smallest argument table (the routing kernels carry ~250 bytes of arguments per frame and
     // kernel-argument memory is 4 KB: a group one frame larger would launch them twice)
-    constexpr int kGroupMax = std::min({StagTab<k_stag_route_walk_fn>::kMax, StagTab<k_stag_route_extract_fn>::kMax, StagTab<k_stag_route_extract_small_fn>::kMax, StagTab<k_stag_route_extract_big_fn>::kMax, StagTab<k_stag_route_gather_fn>::kMax,
-                                        StagTab<k_stag_quads_fn>::kMax, StagTab<k_stag_decode_fn>::kMax, StagTab<k_stag_validate_lines_fn>::kMax,
-                                        StagTab<k_stag_split_lines_fn>::kMax, StagTab<k_stag_refine_fn>::kMax, (int)STAG_MAXF});
+    constexpr int kGroupMax = std::min({StagTab<k_stag_route_walk_fn<true>>::kMax, StagTab<k_stag_route_extract_fn<true>>::kMax, StagTab<k_stag_route_extract_small_fn<true>>::kMax, StagTab<k_stag_route_extract_big_fn<true>>::kMax, StagTab<k_stag_route_gather_fn>::kMax,
+                                        StagTab<k_stag_quads_fn<true>>::kMax, StagTab<k_stag_decode_fn>::kMax, StagTab<k_stag_validate_lines_fn>::kMax,
+                                        StagTab<k_stag_split_lines_fn<true>>::kMax, StagTab<k_stag_refine_fn>::kMax, (int)STAG_MAXF});
     // (the pose kernels carry a PoseCam by value -- 23 words since it holds twelve coefficients and the model -- and still take a
     //  full group in one launch)
     static_assert(StagTab<k_stag_pose_fn<FID_CAM_RATIONAL>>::kMax >= STAG_MAXF && StagTab<k_stag_bundle_pose_fn<FID_CAM_RATIONAL>>::kMax >= STAG_MAXF,

@@ -5,10 +5,11 @@
 // frames goes through the same state machine in lockstep on ONE stream: while a segment's host code runs for every frame of the
 // group, its launches are RECORDED instead of issued -- launch site by launch site, the arguments of every frame into a table --
 // and then each site is launched ONCE for the whole group: grid (largest per-frame grid, frames in blockIdx.z), a trampoline
-// kernel that picks its frame's argument tuple out of the table (kernel-argument memory: scalar loads) and runs the unchanged
-// kernel body (k_stag_X_impl, produced from the frame-at-a-time kernels by tools/stag_kernels_to_impl.py).  A workgroup beyond
-// its own frame's grid returns at once.  Host waits, launches and small copies per frame drop by the group size; the whole-image
-// passes of a group fill the chip together instead of one 2-Mpixel frame at a time.
+// kernel that picks its frame's argument tuple out of the table (kernel-argument memory: scalar loads) and runs the kernel's
+// functor.  A workgroup beyond its own frame's grid returns at once.  Host waits, launches and small copies per frame drop by the
+// group size; the whole-image passes of a group fill the chip together instead of one 2-Mpixel frame at a time.
+// A STag kernel IS its functor: struct k_stag_X_fn holds the launch bound (kBounds) and, in operator(), the parameter list and the
+// body -- once.  k_stag_frame<k_stag_X_fn, ...> is its frame-at-a-time entry, k_stag_batch<k_stag_X_fn> the group's.
 // Frames that take another road (sequential routing fallback, empty frame) simply record other sites: sites are merged by
 // their id (source order), so a frame's launches keep their order and frames never depend on one another.
 #pragma once
@@ -177,6 +178,23 @@ struct stag_frame_minor : std::false_type {
 template <typename F>
 struct stag_frame_minor<F, std::void_t<decltype(F::kFrameMinor)>> : std::integral_constant<bool, F::kFrameMinor> {
 };
+// the frame-at-a-time entry of a functor: the parameters of its operator() are the kernel's, by value and in order
+template <class Fn, class... A>
+__global__ __launch_bounds__(Fn::kBounds) void k_stag_frame(A... a)
+{
+    Fn{}(a...);
+}
+template <typename Fn, typename C, typename... A>
+static inline auto stag_frame_entry_of(void (C::*)(A...) const)
+{
+    return &k_stag_frame<Fn, A...>;
+}
+template <typename Fn>
+static inline auto stag_frame_entry()  // what a launch site launches: k_stag_frame<Fn, A...> with A... read off Fn::operator(), as StagSig reads it
+{
+    return stag_frame_entry_of<Fn>(decltype(&Fn::operator())());  // (only the type: host code may not name a __device__ function outside decltype)
+}
+// the group's entry: frame f's arguments rebuilt from the table, then the same functor
 template <typename Fn>
 __global__ __launch_bounds__(Fn::kBounds) void k_stag_batch(const StagTab<Fn> tab)
 {
@@ -242,12 +260,17 @@ struct StagSite {
     static void launch(StagRecorder &R)
     {
         if (n == 0) return;
-        if (lds > 0 && name) fid_launch_log(name, block.x * block.y * block.z, lds);
-        const bool fm = stag_frame_minor<Fn>::value && mx <= 65535u;  // (blockIdx.z is 16 bits; larger grids keep the frames in z)
-        if (stag_frame_minor<Fn>::value && !fm) R.failed = true;  // (cannot happen for the functors that ask for it: their grids are components / segments of a frame)
-        hipLaunchKernelGGL(k_stag_batch<Fn>, fm ? dim3((unsigned)n, my, mx) : dim3(mx, my, (unsigned)n), block, lds, R.stream, tab);
-        if (hipGetLastError() != hipSuccess) R.failed = true;
-        R.merged_launches++;
+        constexpr bool fm = stag_frame_minor<Fn>::value;
+        if (fm && mx > 65535u) {
+            // blockIdx.z is 16 bits, and the body's x index is blockIdx.z at compile time: such a grid is refused, not launched with the
+            // frames back in z (cannot happen for the functors that ask for it: their grids are components / segments of a frame)
+            R.failed = true;
+        } else {
+            if (lds > 0 && name) fid_launch_log(name, block.x * block.y * block.z, lds);
+            hipLaunchKernelGGL(k_stag_batch<Fn>, fm ? dim3((unsigned)n, my, mx) : dim3(mx, my, (unsigned)n), block, lds, R.stream, tab);
+            if (hipGetLastError() != hipSuccess) R.failed = true;
+            R.merged_launches++;
+        }
         n = 0;
         mx = my = 0;
         lds = 0;
@@ -348,31 +371,24 @@ thread_local unsigned StagSite<Fn, SITE>::my = 0;
 template <typename Fn, int SITE>
 thread_local const char *StagSite<Fn, SITE>::name = nullptr;
 
-// a launch site of the state machine: issued at once (frame-at-a-time entry points) or recorded (group mode)
-#define STAG_LAUNCH(K, grid, block, lds, st, ...)                                                          \
+// a launch site of the state machine: issued at once (the frame entry of FRAME_FN) or recorded (group mode, GROUP_FN's site)
+#define STAG_LAUNCH_AS(FRAME_FN, GROUP_FN, NAME, GROUP_NAME, grid, block, lds, st, ...)                    \
     do {                                                                                                   \
         if (g_stag_rec && g_stag_rec->on) {                                                                \
-            using Site_ = StagSite<K##_fn, __COUNTER__>;                                                   \
-            Site_::name = #K "[g]";                                                                        \
+            using Site_ = StagSite<GROUP_FN, __COUNTER__>;                                                 \
+            Site_::name = GROUP_NAME;                                                                      \
             Site_::record(*g_stag_rec, grid, block, lds, __VA_ARGS__);                                     \
         } else {                                                                                           \
-            if ((size_t)(lds) > 0) fid_launch_log(#K, dim3(block).x * dim3(block).y * dim3(block).z, (size_t)(lds)); \
-            hipLaunchKernelGGL(K, grid, block, lds, st, __VA_ARGS__);                                      \
+            if ((size_t)(lds) > 0) fid_launch_log(NAME, dim3(block).x * dim3(block).y * dim3(block).z, (size_t)(lds)); \
+            hipLaunchKernelGGL(stag_frame_entry<FRAME_FN>(), grid, block, lds, st, __VA_ARGS__);           \
         }                                                                                                  \
     } while (0)
-
-// the same for a kernel and functor that are templates on ONE constant (the pose kernels' camera model): K<T> and K_fn<T>
-#define STAG_LAUNCH_T(K, T, grid, block, lds, st, ...)                                                     \
-    do {                                                                                                   \
-        if (g_stag_rec && g_stag_rec->on) {                                                                \
-            using Site_ = StagSite<K##_fn<T>, __COUNTER__>;                                                \
-            Site_::name = #K "<" #T ">[g]";                                                                \
-            Site_::record(*g_stag_rec, grid, block, lds, __VA_ARGS__);                                     \
-        } else {                                                                                           \
-            if ((size_t)(lds) > 0) fid_launch_log(#K, dim3(block).x * dim3(block).y * dim3(block).z, (size_t)(lds)); \
-            hipLaunchKernelGGL(K<T>, grid, block, lds, st, __VA_ARGS__);                                   \
-        }                                                                                                  \
-    } while (0)
+#define STAG_LAUNCH(K, ...) STAG_LAUNCH_AS(K##_fn, K##_fn, #K, #K "[g]", __VA_ARGS__)
+// a functor that is a template on ONE constant (the pose kernels' camera model): K_fn<T>
+#define STAG_LAUNCH_T(K, T, ...) STAG_LAUNCH_AS(K##_fn<T>, K##_fn<T>, #K, #K "<" #T ">[g]", __VA_ARGS__)
+// a functor that declares kFrameMinor (template <bool FM>: its body reads its x index through STAG_BX<FM>()): K_fn<false> under the
+// frame entry, K_fn<true> under the group's
+#define STAG_LAUNCH_FM(K, ...) STAG_LAUNCH_AS(K##_fn<false>, K##_fn<true>, #K, #K "[g]", __VA_ARGS__)
 // ... with the constant picked from a fid_camera_model at run time.  Three sites in a row in source order; one call's frames all
 // carry the same camera, so a group uses one of them.
 #define STAG_LAUNCH_CAM(K, model, grid, block, lds, st, ...)                                               \
@@ -385,38 +401,34 @@ thread_local const char *StagSite<Fn, SITE>::name = nullptr;
 // ---- the small device operations of the state machine as kernels, so that a group issues each of them ONCE: fills, device
 // copies, and the few bytes of counters that go back to the host after every segment (written straight into the context's
 // pinned host block through its device alias: no copy engine round per frame)
-__device__ __forceinline__ void k_stag_memset_impl(uint8_t *dst, int val, unsigned long long bytes)
-{
-    const unsigned long long head = ((16ull - ((unsigned long long)dst & 15ull)) & 15ull) < bytes ? ((16ull - ((unsigned long long)dst & 15ull)) & 15ull) : bytes;
-    const unsigned long long n16 = (bytes - head) >> 4, tail = bytes - head - (n16 << 4);
-    const unsigned v = (unsigned)(val & 0xff) * 0x01010101u;
-    uint4 *mid = reinterpret_cast<uint4 *>(dst + head);
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (unsigned long long)gridDim.x * 256) mid[i] = make_uint4(v, v, v, v);
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < head) dst[threadIdx.x] = (uint8_t)val;
-        if (threadIdx.x < tail) dst[head + (n16 << 4) + threadIdx.x] = (uint8_t)val;
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_memset(uint8_t *dst, int val, unsigned long long bytes) { k_stag_memset_impl(dst, val, bytes); }
 struct k_stag_memset_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(uint8_t *dst, int val, unsigned long long bytes) const { k_stag_memset_impl(dst, val, bytes); }
-};
-__device__ __forceinline__ void k_stag_memcpy_impl(uint8_t *dst, const uint8_t *src, unsigned long long bytes)
-{
-    if ((((unsigned long long)dst | (unsigned long long)src) & 15ull) == 0) {
-        const unsigned long long n16 = bytes >> 4;
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (unsigned long long)gridDim.x * 256)
-            reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
-        if (blockIdx.x == 0 && threadIdx.x < (bytes & 15ull)) dst[(n16 << 4) + threadIdx.x] = src[(n16 << 4) + threadIdx.x];
-    } else {
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < bytes; i += (unsigned long long)gridDim.x * 256) dst[i] = src[i];
+    __device__ __forceinline__ void operator()(uint8_t *dst, int val, unsigned long long bytes) const
+    {
+        const unsigned long long head = ((16ull - ((unsigned long long)dst & 15ull)) & 15ull) < bytes ? ((16ull - ((unsigned long long)dst & 15ull)) & 15ull) : bytes;
+        const unsigned long long n16 = (bytes - head) >> 4, tail = bytes - head - (n16 << 4);
+        const unsigned v = (unsigned)(val & 0xff) * 0x01010101u;
+        uint4 *mid = reinterpret_cast<uint4 *>(dst + head);
+        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (unsigned long long)gridDim.x * 256) mid[i] = make_uint4(v, v, v, v);
+        if (blockIdx.x == 0) {
+            if (threadIdx.x < head) dst[threadIdx.x] = (uint8_t)val;
+            if (threadIdx.x < tail) dst[head + (n16 << 4) + threadIdx.x] = (uint8_t)val;
+        }
     }
-}
-__global__ __launch_bounds__(256) void k_stag_memcpy(uint8_t *dst, const uint8_t *src, unsigned long long bytes) { k_stag_memcpy_impl(dst, src, bytes); }
+};
 struct k_stag_memcpy_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(uint8_t *dst, const uint8_t *src, unsigned long long bytes) const { k_stag_memcpy_impl(dst, src, bytes); }
+    __device__ __forceinline__ void operator()(uint8_t *dst, const uint8_t *src, unsigned long long bytes) const
+    {
+        if ((((unsigned long long)dst | (unsigned long long)src) & 15ull) == 0) {
+            const unsigned long long n16 = bytes >> 4;
+            for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16; i += (unsigned long long)gridDim.x * 256)
+                reinterpret_cast<uint4 *>(dst)[i] = reinterpret_cast<const uint4 *>(src)[i];
+            if (blockIdx.x == 0 && threadIdx.x < (bytes & 15ull)) dst[(n16 << 4) + threadIdx.x] = src[(n16 << 4) + threadIdx.x];
+        } else {
+            for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < bytes; i += (unsigned long long)gridDim.x * 256) dst[i] = src[i];
+        }
+    }
 };
 
 // pinned host blocks the kernels may write into: host address range -> device alias (registered by fid_stag_create)

@@ -586,211 +586,206 @@ __device__ bool sr_in_quad(const double c[8], double px, double py)
     return true;
 }
 
-__device__ __forceinline__ void k_stag_refine_impl(fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
-                                                    const int2 *__restrict__ vsegs, const int *__restrict__ nsegs, const int2 *__restrict__ pix,
-                                                    int *__restrict__ chosen_out)
-{
-    const int m = blockIdx.x, lane = threadIdx.x;
-    if (m >= *nmarkers) return;
-    fid_stag_marker M = markers[m];
-    const double sinVals[36] = {0.000000,  0.173648,  0.342020,  0.500000,  0.642788,  0.766044,  0.866025,  0.939693,  0.984808,
-                                1.000000,  0.984808,  0.939693,  0.866025,  0.766044,  0.642788,  0.500000,  0.342020,  0.173648,
-                                0.000000,  -0.173648, -0.342020, -0.500000, -0.642788, -0.766044, -0.866025, -0.939693, -0.984808,
-                                -1.000000, -0.984808, -0.939693, -0.866025, -0.766044, -0.642788, -0.500000, -0.342020, -0.173648};
-    double Hinv[9];
-    sr_inv3(M.H, Hinv);
-#ifdef SR_TIMING
-    const unsigned long long t_0 = __builtin_readcyclecounter();
-    int d_cands = 0;
-#endif
-    // ---- (1) the edge segment of the circular border
-    int chosen = -1;
-    double minAcc = INFINITY;
-    const int ns = *nsegs;
-    for (int sg0 = 0; sg0 < ns; sg0 += 64) {
-      // the cheap tests (length, closed loop, sampled pixels inside the quad) for 64 segments at once, one per lane; the
-      // survivors are then examined one after the other, in segment order, by the whole wave
-      unsigned long long cand;
-      {
-        const int sgl = sg0 + lane;
-        bool ok = false;
-        if (sgl < ns) {
-            const int first = vsegs[sgl].x, n = vsegs[sgl].y;
-            if (n >= 20) {
-                const int2 *p = pix + first;
-                if (!(sq_dist2((double)p[0].y, (double)p[0].x, (double)p[n - 1].y, (double)p[n - 1].x) > 7.0 * 7.0)) {
-                    ok = true;
-                    for (int k = 0; k < n && ok; k += 20)
-                        if (!sr_in_quad(M.corners, (double)p[k].y, (double)p[k].x)) ok = false;
-                }
-            }
-        }
-        cand = __ballot(ok);
-      }
-      while (cand) {
-        const int sg = sg0 + __builtin_ctzll(cand);
-        cand &= cand - 1;
-#ifdef SR_TIMING
-        d_cands++;
-#endif
-        const int first = vsegs[sg].x, n = vsegs[sg].y;
-        const int2 *p = pix + first;
-        // back-projection; per sample point the minimum over the pixels, per pixel the minimum over the sample points
-        bool bad = false;
-        // (round 3) first only the per-pixel test that rejects: 22 of the 23 closed loops inside a marker are code dots whose
-        // pixels lie nowhere near the circle -- they end here, after the first 64 pixels, without the 36 wave-wide minima per
-        // chunk that only the accepted segment's error sum needs (same distances, same comparisons, same decision)
-        for (int k0 = 0; k0 < n && !bad; k0 += 64) {
-            const int k = k0 + lane;
-            const bool act = k < n;
-            double pixErr = INFINITY;
-            if (act) {
-                const double ex = p[k].y, ey = p[k].x;
-                const double a0 = Hinv[0] * ex + Hinv[1] * ey + Hinv[2] * 1, a1 = Hinv[3] * ex + Hinv[4] * ey + Hinv[5] * 1;
-                const double a2 = Hinv[6] * ex + Hinv[7] * ey + Hinv[8] * 1;
-                const double qx = a0 / a2, qy = a1 / a2;
-                // (round 4) min_s sqrt(x_s) == sqrt(min_s x_s) bit for bit -- the correctly rounded square root is monotone -- so the
-                // rejecting pass takes ONE square root per pixel instead of 36 (23 code-dot loops per marker end in this pass)
-                double m2 = INFINITY;
-                for (int s = 0; s < 36; s++) {
-                    const double sx = 0.5 + 0.4 * sinVals[(s + 9) % 36], sy = 0.5 + 0.4 * sinVals[s];
-                    const double d2 = (qx - sx) * (qx - sx) + (qy - sy) * (qy - sy);
-                    if (d2 < m2) m2 = d2;
-                }
-                pixErr = sqrt(m2);
-            }
-            if (__ballot(act && pixErr > 0.1)) bad = true;
-        }
-        if (bad) continue;
-        double sampleErr[36];
-        for (int s = 0; s < 36; s++) sampleErr[s] = INFINITY;
-        for (int k0 = 0; k0 < n; k0 += 64) {
-            const int k = k0 + lane;
-            double qx = 0, qy = 0;
-            const bool act = k < n;
-            if (act) {
-                const double ex = p[k].y, ey = p[k].x;
-                const double a0 = Hinv[0] * ex + Hinv[1] * ey + Hinv[2] * 1, a1 = Hinv[3] * ex + Hinv[4] * ey + Hinv[5] * 1;
-                const double a2 = Hinv[6] * ex + Hinv[7] * ey + Hinv[8] * 1;
-                qx = a0 / a2;
-                qy = a1 / a2;
-            }
-            double pixErr = INFINITY;
-            for (int s = 0; s < 36; s++) {
-                const double sx = 0.5 + 0.4 * sinVals[(s + 9) % 36], sy = 0.5 + 0.4 * sinVals[s];
-                const double d = act ? sqrt((qx - sx) * (qx - sx) + (qy - sy) * (qy - sy)) : INFINITY;
-                if (d < pixErr) pixErr = d;
-                const double mn = sr_wave_min_f64(d);
-                if (mn < sampleErr[s]) sampleErr[s] = mn;
-            }
-            if (__ballot(act && pixErr > 0.1)) bad = true;
-        }
-        if (bad) continue;
-        double errSum = 0;
-        for (int s = 0; s < 36; s++) errSum += sampleErr[s];
-        if (errSum < minAcc && errSum < 36 * 0.05) {
-            minAcc = errSum;
-            chosen = sg;
-        }
-      }
-    }
-    if (lane == 0) chosen_out[m] = chosen;
-    if (chosen < 0) return;
-#ifdef SR_TIMING
-    const unsigned long long t_1 = __builtin_readcyclecounter();
-#endif
-    // ---- (2) ellipse through the chosen segment: scatter matrix, one lane per entry (p <= q), summed in pixel order
-    __shared__ double s_S[7][7];
-    {
-        const int first = vsegs[chosen].x, n = vsegs[chosen].y;
-        const int2 *p = pix + first;
-        if (lane < 49) s_S[lane / 7][lane % 7] = 0.0;
-        __builtin_amdgcn_wave_barrier();
-        // (round 3) the pixels across the lanes, every lane the 21 running sums of its pixels, then 21 wave sums: the terms are
-        // integers (pixel coordinates), so up to ~600 pixels every partial sum is exact in a double whatever the order; beyond
-        // that the order changes the last bit of a sum that the ellipse fit and the simplex search, a tolerance row anyway
-        // (1e-3 px against the reference), do not resolve.  (One lane per matrix entry walked all n pixels: 0.15 ms per marker.)
-        double acc[21];
-#pragma unroll
-        for (int e = 0; e < 21; e++) acc[e] = 0.0;
-        for (int l = lane; l < n; l += 64) {
-            const double tx = (double)p[l].y, ty = (double)(-p[l].x);
-            const double Dl[6] = {tx * tx, tx * ty, ty * ty, tx, ty, 1.0};
-            int e = 0;
-#pragma unroll
-            for (int a = 0; a < 6; a++)
-#pragma unroll
-                for (int b = a; b < 6; b++) acc[e++] += Dl[a] * Dl[b];
-        }
-        {
-            int e = 0;
-#pragma unroll
-            for (int a = 1; a <= 6; a++)
-#pragma unroll
-                for (int b = a; b <= 6; b++) {
-                    double v = acc[e++];
-                    v += shfl_xor_f64(v, 1);
-                    v += shfl_xor_f64(v, 2);
-                    v += shfl_xor_f64(v, 4);
-                    v += shfl_xor_f64(v, 8);
-                    v += shfl_xor_f64(v, 16);
-                    v += shfl_xor_f64(v, 32);
-                    if (lane == 0) {
-                        s_S[a][b] = v;
-                        s_S[b][a] = v;
-                    }
-                }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (n < 6) return;
-    }
-    // from here on every lane carries the same values (the fit is small scalar work; the simplex search spreads its function
-    // evaluations over the lanes)
-    __shared__ SrSimplex s_simplex;
-    SrM S;
-    for (int i = 0; i < 7; i++)
-        for (int j = 0; j < 7; j++) S[i][j] = s_S[i][j];
-    SrEllipse E;
-    if (!sr_fit_from_scatter(S, &E)) return;
-    double Cm[9];
-    Cm[0] = E.A1; Cm[1] = Cm[3] = -E.B1 / 2; Cm[4] = E.C1; Cm[2] = Cm[6] = E.D1 / 2; Cm[5] = Cm[7] = -E.E1 / 2; Cm[8] = E.F1;
-    // ---- (3) Nelder-Mead over the entries of H
-    double x[9], step[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) x[i + j * 3] = M.H[3 * i + j];
-    for (int k = 0; k < 9; k++) step[k] = fabs(0.001 * x[k]);
-#ifdef SR_TIMING
-    const unsigned long long t_2 = __builtin_readcyclecounter();
-    int d_evals = 0;
-    sr_downhill(x, step, Cm, lane, &s_simplex, &d_evals);
-    if (lane == 0)
-        printf("refine marker %d: segments %d, candidates examined %d, chosen length %d; ticks: search %llu, scatter + fit %llu, simplex %llu (%d evaluations)\n", m, ns,
-               d_cands, vsegs[chosen].y, t_1 - t_0, t_2 - t_1, (unsigned long long)__builtin_readcyclecounter() - t_2, d_evals);
-#else
-    sr_downhill(x, step, Cm, lane, &s_simplex);
-#endif
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) M.H[3 * i + j] = x[i + j * 3];
-    // ---- (4) points from the refined H
-    auto project = [&](double px, double py, double *ox, double *oy) {
-        const double a0 = M.H[0] * px + M.H[1] * py + M.H[2] * 1, a1 = M.H[3] * px + M.H[4] * py + M.H[5] * 1, a2 = M.H[6] * px + M.H[7] * py + M.H[8] * 1;
-        *ox = a0 / a2;
-        *oy = a1 / a2;
-    };
-    project(0.5, 0.5, &M.center[0], &M.center[1]);
-    project(0, 0, &M.corners[0], &M.corners[1]);
-    project(1, 0, &M.corners[2], &M.corners[3]);
-    project(1, 1, &M.corners[4], &M.corners[5]);
-    project(0, 1, &M.corners[6], &M.corners[7]);
-    if (lane == 0) markers[m] = M;
-}
-__global__ __launch_bounds__(64) void k_stag_refine(fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const int2 *__restrict__ vsegs, const int *__restrict__ nsegs, const int2 *__restrict__ pix, int *__restrict__ chosen_out)
-{
-    k_stag_refine_impl(markers, nmarkers, vsegs, nsegs, pix, chosen_out);
-}
 struct k_stag_refine_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const int2 *__restrict__ vsegs, const int *__restrict__ nsegs, const int2 *__restrict__ pix, int *__restrict__ chosen_out) const { k_stag_refine_impl(markers, nmarkers, vsegs, nsegs, pix, chosen_out); }
+    __device__ __forceinline__ void operator()(fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers,
+                                               const int2 *__restrict__ vsegs, const int *__restrict__ nsegs, const int2 *__restrict__ pix,
+                                               int *__restrict__ chosen_out) const
+    {
+        const int m = blockIdx.x, lane = threadIdx.x;
+        if (m >= *nmarkers) return;
+        fid_stag_marker M = markers[m];
+        const double sinVals[36] = {0.000000,  0.173648,  0.342020,  0.500000,  0.642788,  0.766044,  0.866025,  0.939693,  0.984808,
+                                    1.000000,  0.984808,  0.939693,  0.866025,  0.766044,  0.642788,  0.500000,  0.342020,  0.173648,
+                                    0.000000,  -0.173648, -0.342020, -0.500000, -0.642788, -0.766044, -0.866025, -0.939693, -0.984808,
+                                    -1.000000, -0.984808, -0.939693, -0.866025, -0.766044, -0.642788, -0.500000, -0.342020, -0.173648};
+        double Hinv[9];
+        sr_inv3(M.H, Hinv);
+#ifdef SR_TIMING
+        const unsigned long long t_0 = __builtin_readcyclecounter();
+        int d_cands = 0;
+#endif
+        // ---- (1) the edge segment of the circular border
+        int chosen = -1;
+        double minAcc = INFINITY;
+        const int ns = *nsegs;
+        for (int sg0 = 0; sg0 < ns; sg0 += 64) {
+          // the cheap tests (length, closed loop, sampled pixels inside the quad) for 64 segments at once, one per lane; the
+          // survivors are then examined one after the other, in segment order, by the whole wave
+          unsigned long long cand;
+          {
+            const int sgl = sg0 + lane;
+            bool ok = false;
+            if (sgl < ns) {
+                const int first = vsegs[sgl].x, n = vsegs[sgl].y;
+                if (n >= 20) {
+                    const int2 *p = pix + first;
+                    if (!(sq_dist2((double)p[0].y, (double)p[0].x, (double)p[n - 1].y, (double)p[n - 1].x) > 7.0 * 7.0)) {
+                        ok = true;
+                        for (int k = 0; k < n && ok; k += 20)
+                            if (!sr_in_quad(M.corners, (double)p[k].y, (double)p[k].x)) ok = false;
+                    }
+                }
+            }
+            cand = __ballot(ok);
+          }
+          while (cand) {
+            const int sg = sg0 + __builtin_ctzll(cand);
+            cand &= cand - 1;
+#ifdef SR_TIMING
+            d_cands++;
+#endif
+            const int first = vsegs[sg].x, n = vsegs[sg].y;
+            const int2 *p = pix + first;
+            // back-projection; per sample point the minimum over the pixels, per pixel the minimum over the sample points
+            bool bad = false;
+            // (round 3) first only the per-pixel test that rejects: 22 of the 23 closed loops inside a marker are code dots whose
+            // pixels lie nowhere near the circle -- they end here, after the first 64 pixels, without the 36 wave-wide minima per
+            // chunk that only the accepted segment's error sum needs (same distances, same comparisons, same decision)
+            for (int k0 = 0; k0 < n && !bad; k0 += 64) {
+                const int k = k0 + lane;
+                const bool act = k < n;
+                double pixErr = INFINITY;
+                if (act) {
+                    const double ex = p[k].y, ey = p[k].x;
+                    const double a0 = Hinv[0] * ex + Hinv[1] * ey + Hinv[2] * 1, a1 = Hinv[3] * ex + Hinv[4] * ey + Hinv[5] * 1;
+                    const double a2 = Hinv[6] * ex + Hinv[7] * ey + Hinv[8] * 1;
+                    const double qx = a0 / a2, qy = a1 / a2;
+                    // (round 4) min_s sqrt(x_s) == sqrt(min_s x_s) bit for bit -- the correctly rounded square root is monotone -- so the
+                    // rejecting pass takes ONE square root per pixel instead of 36 (23 code-dot loops per marker end in this pass)
+                    double m2 = INFINITY;
+                    for (int s = 0; s < 36; s++) {
+                        const double sx = 0.5 + 0.4 * sinVals[(s + 9) % 36], sy = 0.5 + 0.4 * sinVals[s];
+                        const double d2 = (qx - sx) * (qx - sx) + (qy - sy) * (qy - sy);
+                        if (d2 < m2) m2 = d2;
+                    }
+                    pixErr = sqrt(m2);
+                }
+                if (__ballot(act && pixErr > 0.1)) bad = true;
+            }
+            if (bad) continue;
+            double sampleErr[36];
+            for (int s = 0; s < 36; s++) sampleErr[s] = INFINITY;
+            for (int k0 = 0; k0 < n; k0 += 64) {
+                const int k = k0 + lane;
+                double qx = 0, qy = 0;
+                const bool act = k < n;
+                if (act) {
+                    const double ex = p[k].y, ey = p[k].x;
+                    const double a0 = Hinv[0] * ex + Hinv[1] * ey + Hinv[2] * 1, a1 = Hinv[3] * ex + Hinv[4] * ey + Hinv[5] * 1;
+                    const double a2 = Hinv[6] * ex + Hinv[7] * ey + Hinv[8] * 1;
+                    qx = a0 / a2;
+                    qy = a1 / a2;
+                }
+                double pixErr = INFINITY;
+                for (int s = 0; s < 36; s++) {
+                    const double sx = 0.5 + 0.4 * sinVals[(s + 9) % 36], sy = 0.5 + 0.4 * sinVals[s];
+                    const double d = act ? sqrt((qx - sx) * (qx - sx) + (qy - sy) * (qy - sy)) : INFINITY;
+                    if (d < pixErr) pixErr = d;
+                    const double mn = sr_wave_min_f64(d);
+                    if (mn < sampleErr[s]) sampleErr[s] = mn;
+                }
+                if (__ballot(act && pixErr > 0.1)) bad = true;
+            }
+            if (bad) continue;
+            double errSum = 0;
+            for (int s = 0; s < 36; s++) errSum += sampleErr[s];
+            if (errSum < minAcc && errSum < 36 * 0.05) {
+                minAcc = errSum;
+                chosen = sg;
+            }
+          }
+        }
+        if (lane == 0) chosen_out[m] = chosen;
+        if (chosen < 0) return;
+#ifdef SR_TIMING
+        const unsigned long long t_1 = __builtin_readcyclecounter();
+#endif
+        // ---- (2) ellipse through the chosen segment: scatter matrix, one lane per entry (p <= q), summed in pixel order
+        __shared__ double s_S[7][7];
+        {
+            const int first = vsegs[chosen].x, n = vsegs[chosen].y;
+            const int2 *p = pix + first;
+            if (lane < 49) s_S[lane / 7][lane % 7] = 0.0;
+            __builtin_amdgcn_wave_barrier();
+            // (round 3) the pixels across the lanes, every lane the 21 running sums of its pixels, then 21 wave sums: the terms are
+            // integers (pixel coordinates), so up to ~600 pixels every partial sum is exact in a double whatever the order; beyond
+            // that the order changes the last bit of a sum that the ellipse fit and the simplex search, a tolerance row anyway
+            // (1e-3 px against the reference), do not resolve.  (One lane per matrix entry walked all n pixels: 0.15 ms per marker.)
+            double acc[21];
+#pragma unroll
+            for (int e = 0; e < 21; e++) acc[e] = 0.0;
+            for (int l = lane; l < n; l += 64) {
+                const double tx = (double)p[l].y, ty = (double)(-p[l].x);
+                const double Dl[6] = {tx * tx, tx * ty, ty * ty, tx, ty, 1.0};
+                int e = 0;
+#pragma unroll
+                for (int a = 0; a < 6; a++)
+#pragma unroll
+                    for (int b = a; b < 6; b++) acc[e++] += Dl[a] * Dl[b];
+            }
+            {
+                int e = 0;
+#pragma unroll
+                for (int a = 1; a <= 6; a++)
+#pragma unroll
+                    for (int b = a; b <= 6; b++) {
+                        double v = acc[e++];
+                        v += shfl_xor_f64(v, 1);
+                        v += shfl_xor_f64(v, 2);
+                        v += shfl_xor_f64(v, 4);
+                        v += shfl_xor_f64(v, 8);
+                        v += shfl_xor_f64(v, 16);
+                        v += shfl_xor_f64(v, 32);
+                        if (lane == 0) {
+                            s_S[a][b] = v;
+                            s_S[b][a] = v;
+                        }
+                    }
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (n < 6) return;
+        }
+        // from here on every lane carries the same values (the fit is small scalar work; the simplex search spreads its function
+        // evaluations over the lanes)
+        __shared__ SrSimplex s_simplex;
+        SrM S;
+        for (int i = 0; i < 7; i++)
+            for (int j = 0; j < 7; j++) S[i][j] = s_S[i][j];
+        SrEllipse E;
+        if (!sr_fit_from_scatter(S, &E)) return;
+        double Cm[9];
+        Cm[0] = E.A1; Cm[1] = Cm[3] = -E.B1 / 2; Cm[4] = E.C1; Cm[2] = Cm[6] = E.D1 / 2; Cm[5] = Cm[7] = -E.E1 / 2; Cm[8] = E.F1;
+        // ---- (3) Nelder-Mead over the entries of H
+        double x[9], step[9];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) x[i + j * 3] = M.H[3 * i + j];
+        for (int k = 0; k < 9; k++) step[k] = fabs(0.001 * x[k]);
+#ifdef SR_TIMING
+        const unsigned long long t_2 = __builtin_readcyclecounter();
+        int d_evals = 0;
+        sr_downhill(x, step, Cm, lane, &s_simplex, &d_evals);
+        if (lane == 0)
+            printf("refine marker %d: segments %d, candidates examined %d, chosen length %d; ticks: search %llu, scatter + fit %llu, simplex %llu (%d evaluations)\n", m, ns,
+                   d_cands, vsegs[chosen].y, t_1 - t_0, t_2 - t_1, (unsigned long long)__builtin_readcyclecounter() - t_2, d_evals);
+#else
+        sr_downhill(x, step, Cm, lane, &s_simplex);
+#endif
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) M.H[3 * i + j] = x[i + j * 3];
+        // ---- (4) points from the refined H
+        auto project = [&](double px, double py, double *ox, double *oy) {
+            const double a0 = M.H[0] * px + M.H[1] * py + M.H[2] * 1, a1 = M.H[3] * px + M.H[4] * py + M.H[5] * 1, a2 = M.H[6] * px + M.H[7] * py + M.H[8] * 1;
+            *ox = a0 / a2;
+            *oy = a1 / a2;
+        };
+        project(0.5, 0.5, &M.center[0], &M.center[1]);
+        project(0, 0, &M.corners[0], &M.corners[1]);
+        project(1, 0, &M.corners[2], &M.corners[3]);
+        project(1, 1, &M.corners[4], &M.corners[5]);
+        project(0, 1, &M.corners[6], &M.corners[7]);
+        if (lane == 0) markers[m] = M;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------ K17: marker pose
@@ -899,11 +894,6 @@ template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_pose_cov(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out, double sigma_px, fid_pose_cov *__restrict__ cov)
 {
     k_stag_pose_impl<MODEL, true>(markers, nmarkers, cam, marker_size, out, sigma_px, cov);
-}
-template <int MODEL>
-__global__ __launch_bounds__(64) void k_stag_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, PoseCam cam, double marker_size, fid_stag_pose_out *__restrict__ out)
-{
-    k_stag_pose_impl<MODEL>(markers, nmarkers, cam, marker_size, out);
 }
 template <int MODEL>
 struct k_stag_pose_fn {
@@ -1179,11 +1169,6 @@ template <int MODEL>
 __global__ __launch_bounds__(64) void k_stag_bundle_pose_cov(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out, double sigma_px, fid_pose_cov *__restrict__ cov)
 {
     k_stag_bundle_pose_impl<MODEL, true>(markers, nmarkers, ltags, lstart, cam, out, sigma_px, cov);
-}
-template <int MODEL>
-__global__ __launch_bounds__(64) void k_stag_bundle_pose(const fid_stag_marker *__restrict__ markers, const int *__restrict__ nmarkers, const fid_stag_tag *__restrict__ ltags, const int *__restrict__ lstart, PoseCam cam, fid_stag_bundle_pose_out *__restrict__ out)
-{
-    k_stag_bundle_pose_impl<MODEL>(markers, nmarkers, ltags, lstart, cam, out);
 }
 template <int MODEL>
 struct k_stag_bundle_pose_fn {

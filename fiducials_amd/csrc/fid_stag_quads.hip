@@ -249,147 +249,132 @@ __device__ void sq_make_quad(const StagCorner c[4], fid_stag_quad *q)
 }
 
 // first line and number of lines of every validated segment (lines are stored segment by segment)
-__device__ __forceinline__ void k_stag_line_ranges_impl(const fid_stag_line *__restrict__ lines, const int *__restrict__ nlines, int2 *__restrict__ range)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = *nlines;
-    if (i >= n) return;
-    const int sg = lines[i].segmentNo;
-    if (i == 0 || lines[i - 1].segmentNo != sg) range[sg].x = i;
-    if (i == n - 1 || lines[i + 1].segmentNo != sg) range[sg].y = i + 1;
-}
-__global__ __launch_bounds__(256) void k_stag_line_ranges(const fid_stag_line *__restrict__ lines, const int *__restrict__ nlines, int2 *__restrict__ range)
-{
-    k_stag_line_ranges_impl(lines, nlines, range);
-}
 struct k_stag_line_ranges_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const fid_stag_line *__restrict__ lines, const int *__restrict__ nlines, int2 *__restrict__ range) const { k_stag_line_ranges_impl(lines, nlines, range); }
+    __device__ __forceinline__ void operator()(const fid_stag_line *__restrict__ lines, const int *__restrict__ nlines, int2 *__restrict__ range) const
+    {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        const int n = *nlines;
+        if (i >= n) return;
+        const int sg = lines[i].segmentNo;
+        if (i == 0 || lines[i - 1].segmentNo != sg) range[sg].x = i;
+        if (i == n - 1 || lines[i + 1].segmentNo != sg) range[sg].y = i + 1;
+    }
 };
 
-template <bool FM = false>
-__device__ __forceinline__ void k_stag_quads_impl(fid_stag_line *__restrict__ lines, const int2 *__restrict__ range, const int *__restrict__ nsegs,
-                                                    const int2 *__restrict__ vsegs, const int2 *__restrict__ pix, const uint8_t *__restrict__ img, int W,
-                                                    int H, StagCorner *__restrict__ corner_slots, int *__restrict__ order_slots,
-                                                    fid_stag_quad *__restrict__ quad_slots, int *__restrict__ counts)
-{
-    const int seg = (int)STAG_BX<FM>() * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (seg >= *nsegs) return;
-    const int lo = range[seg].x, n = range[seg].y - lo;
-    if (lane == 0) counts[seg] = 0;
-    if (range[seg].y == 0 || n < 4) return;  // groups need >= 4 lines of one edge segment
-    // ---- groupLines: fix the direction of every line of the group (each lane one line), then the order of the group
-    // (short lines a lane each; the long ones -- more samples than a wave has lanes -- one after the other by the whole wave)
-    unsigned long long longm[2] = {0ull, 0ull};  // (groups of up to 128 lines keep their long ones as bits; beyond: a lane each)
-    for (int k0 = 0; k0 < n; k0 += 64) {
-        const int k = k0 + lane;
-        bool is_long = false;
-        if (k < n) {
-            fid_stag_line l = lines[lo + k];
-            is_long = k < 128 && sq_direction_samples(l) > 64;
-            if (!is_long) {
-                sq_correct_direction(img, W, H, l);
-                lines[lo + k] = l;
-            }
-        }
-        const unsigned long long m = __ballot(is_long);
-        if (k0 < 128) longm[k0 >> 6] = m;
-    }
-    for (int w = 0; w < 2; w++)
-        while (longm[w]) {
-            const int k = 64 * w + __builtin_ctzll(longm[w]);
-            longm[w] &= longm[w] - 1;
-            fid_stag_line l = lines[lo + k];
-            sq_correct_direction<64>(img, W, H, l, lane);
-            if (lane == 0) lines[lo + k] = l;
-        }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const fid_stag_line *L = lines;
-    bool rev;
-    {
-        double ix, iy;
-        sq_intersect(L[lo], L[lo + 1], &ix, &iy);
-        rev = fabs(L[lo].sx - ix) + fabs(L[lo].sy - iy) < fabs(L[lo].ex - ix) + fabs(L[lo].ey - iy);
-    }
-    int *order = order_slots + lo;
-    for (int k = lane; k < n; k += 64) order[k] = rev ? lo + n - 1 - k : lo + k;
-    // ---- detectCorners: consecutive lines that turn the right way and meet on the edge segment
-    StagCorner *corners = corner_slots + lo;
-    int nc = 0;
-    const int2 *sp = pix + vsegs[seg].x;
-    const int spn = vsegs[seg].y;
-    for (int k = 0; k < n; k++) {
-        const int a = rev ? lo + n - 1 - k : lo + k, kn = (k + 1) % n, b = rev ? lo + n - 1 - kn : lo + kn;
-        const fid_stag_line &l1 = L[a], &l2 = L[b];
-        if (sq_cross(l1.ex - l1.sx, l1.ey - l1.sy, l2.ex - l1.sx, l2.ey - l1.sy) <= 0) continue;
-        double ix, iy;
-        sq_intersect(l1, l2, &ix, &iy);
-        const double thresManh = 7 * 1.41;
-        bool on = false;
-        for (int e0 = 0; e0 < spn && !on; e0 += 64) {
-            const int e = e0 + lane;
-            bool hit = false;
-            if (e < spn) hit = fabs(sp[e].y - ix) + fabs(sp[e].x - iy) < thresManh;
-            on = __ballot(hit) != 0ull;
-        }
-        if (!on) continue;
-        if (lane == 0) {
-            corners[nc].x = ix; corners[nc].y = iy; corners[nc].l1 = a; corners[nc].l2 = b;
-        }
-        nc++;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (nc < 3 || lane != 0) return;
-    // ---- quads from the corner group (lane 0)
-    fid_stag_quad *out = quad_slots + lo;
-    int nq = 0;
-    for (int ci = 0; ci < nc; ci++) {
-        const int i1 = ci, i2 = (i1 + 1) % nc, i3 = (i1 + 2) % nc, i4 = (i1 + 3) % nc;
-        StagCorner c[4] = {corners[i1], corners[i2], corners[i3], corners[i4]};
-        if (i1 == i4) {
-            c[3].x = INFINITY; c[3].y = INFINITY; c[3].l1 = c[3].l2 = -1;
-        }
-        if (!sq_form_quad(L, c)) continue;
-        fid_stag_quad q;
-        sq_make_quad(c, &q);
-        if (q.projectiveDistortion > 1.5) continue;  // thresProjectiveDistortion
-        out[nq++] = q;
-        if (nc <= 4) break;
-    }
-    counts[seg] = nq;
-}
-__global__ __launch_bounds__(256) void k_stag_quads(fid_stag_line *__restrict__ lines, const int2 *__restrict__ range, const int *__restrict__ nsegs, const int2 *__restrict__ vsegs, const int2 *__restrict__ pix, const uint8_t *__restrict__ img, int W, int H, StagCorner *__restrict__ corner_slots, int *__restrict__ order_slots, fid_stag_quad *__restrict__ quad_slots, int *__restrict__ counts)
-{
-    k_stag_quads_impl(lines, range, nsegs, vsegs, pix, img, W, H, corner_slots, order_slots, quad_slots, counts);
-}
+template <bool FM>
 struct k_stag_quads_fn {
     static constexpr int kBounds = 256;
-    static constexpr bool kFrameMinor = true;
-    __device__ __forceinline__ void operator()(fid_stag_line *__restrict__ lines, const int2 *__restrict__ range, const int *__restrict__ nsegs, const int2 *__restrict__ vsegs, const int2 *__restrict__ pix, const uint8_t *__restrict__ img, int W, int H, StagCorner *__restrict__ corner_slots, int *__restrict__ order_slots, fid_stag_quad *__restrict__ quad_slots, int *__restrict__ counts) const { k_stag_quads_impl<true>(lines, range, nsegs, vsegs, pix, img, W, H, corner_slots, order_slots, quad_slots, counts); }
+    static constexpr bool kFrameMinor = FM;
+    __device__ __forceinline__ void operator()(fid_stag_line *__restrict__ lines, const int2 *__restrict__ range, const int *__restrict__ nsegs,
+                                               const int2 *__restrict__ vsegs, const int2 *__restrict__ pix, const uint8_t *__restrict__ img, int W,
+                                               int H, StagCorner *__restrict__ corner_slots, int *__restrict__ order_slots,
+                                               fid_stag_quad *__restrict__ quad_slots, int *__restrict__ counts) const
+    {
+        const int seg = (int)STAG_BX<FM>() * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+        if (seg >= *nsegs) return;
+        const int lo = range[seg].x, n = range[seg].y - lo;
+        if (lane == 0) counts[seg] = 0;
+        if (range[seg].y == 0 || n < 4) return;  // groups need >= 4 lines of one edge segment
+        // ---- groupLines: fix the direction of every line of the group (each lane one line), then the order of the group
+        // (short lines a lane each; the long ones -- more samples than a wave has lanes -- one after the other by the whole wave)
+        unsigned long long longm[2] = {0ull, 0ull};  // (groups of up to 128 lines keep their long ones as bits; beyond: a lane each)
+        for (int k0 = 0; k0 < n; k0 += 64) {
+            const int k = k0 + lane;
+            bool is_long = false;
+            if (k < n) {
+                fid_stag_line l = lines[lo + k];
+                is_long = k < 128 && sq_direction_samples(l) > 64;
+                if (!is_long) {
+                    sq_correct_direction(img, W, H, l);
+                    lines[lo + k] = l;
+                }
+            }
+            const unsigned long long m = __ballot(is_long);
+            if (k0 < 128) longm[k0 >> 6] = m;
+        }
+        for (int w = 0; w < 2; w++)
+            while (longm[w]) {
+                const int k = 64 * w + __builtin_ctzll(longm[w]);
+                longm[w] &= longm[w] - 1;
+                fid_stag_line l = lines[lo + k];
+                sq_correct_direction<64>(img, W, H, l, lane);
+                if (lane == 0) lines[lo + k] = l;
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const fid_stag_line *L = lines;
+        bool rev;
+        {
+            double ix, iy;
+            sq_intersect(L[lo], L[lo + 1], &ix, &iy);
+            rev = fabs(L[lo].sx - ix) + fabs(L[lo].sy - iy) < fabs(L[lo].ex - ix) + fabs(L[lo].ey - iy);
+        }
+        int *order = order_slots + lo;
+        for (int k = lane; k < n; k += 64) order[k] = rev ? lo + n - 1 - k : lo + k;
+        // ---- detectCorners: consecutive lines that turn the right way and meet on the edge segment
+        StagCorner *corners = corner_slots + lo;
+        int nc = 0;
+        const int2 *sp = pix + vsegs[seg].x;
+        const int spn = vsegs[seg].y;
+        for (int k = 0; k < n; k++) {
+            const int a = rev ? lo + n - 1 - k : lo + k, kn = (k + 1) % n, b = rev ? lo + n - 1 - kn : lo + kn;
+            const fid_stag_line &l1 = L[a], &l2 = L[b];
+            if (sq_cross(l1.ex - l1.sx, l1.ey - l1.sy, l2.ex - l1.sx, l2.ey - l1.sy) <= 0) continue;
+            double ix, iy;
+            sq_intersect(l1, l2, &ix, &iy);
+            const double thresManh = 7 * 1.41;
+            bool on = false;
+            for (int e0 = 0; e0 < spn && !on; e0 += 64) {
+                const int e = e0 + lane;
+                bool hit = false;
+                if (e < spn) hit = fabs(sp[e].y - ix) + fabs(sp[e].x - iy) < thresManh;
+                on = __ballot(hit) != 0ull;
+            }
+            if (!on) continue;
+            if (lane == 0) {
+                corners[nc].x = ix; corners[nc].y = iy; corners[nc].l1 = a; corners[nc].l2 = b;
+            }
+            nc++;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (nc < 3 || lane != 0) return;
+        // ---- quads from the corner group (lane 0)
+        fid_stag_quad *out = quad_slots + lo;
+        int nq = 0;
+        for (int ci = 0; ci < nc; ci++) {
+            const int i1 = ci, i2 = (i1 + 1) % nc, i3 = (i1 + 2) % nc, i4 = (i1 + 3) % nc;
+            StagCorner c[4] = {corners[i1], corners[i2], corners[i3], corners[i4]};
+            if (i1 == i4) {
+                c[3].x = INFINITY; c[3].y = INFINITY; c[3].l1 = c[3].l2 = -1;
+            }
+            if (!sq_form_quad(L, c)) continue;
+            fid_stag_quad q;
+            sq_make_quad(c, &q);
+            if (q.projectiveDistortion > 1.5) continue;  // thresProjectiveDistortion
+            out[nq++] = q;
+            if (nc <= 4) break;
+        }
+        counts[seg] = nq;
+    }
 };
 
-__device__ __forceinline__ void k_stag_gather_quads_impl(const int2 *__restrict__ range, const int *__restrict__ nsegs, const int *__restrict__ counts,
-                                                          const int *__restrict__ total, const fid_stag_quad *__restrict__ slots,
-                                                          fid_stag_quad *__restrict__ out)
-{
-    const int seg = blockIdx.x * 64 + threadIdx.x;
-    const int ns = *nsegs;
-    if (seg >= ns) return;
-    const int o = counts[seg], n = (seg + 1 < ns ? counts[seg + 1] : *total) - o;
-    const fid_stag_quad *Q = slots + range[seg].x;
-    for (int j = 0; j < n; j++) out[o + j] = Q[j];
-}
-__global__ __launch_bounds__(64) void k_stag_gather_quads(const int2 *__restrict__ range, const int *__restrict__ nsegs, const int *__restrict__ counts, const int *__restrict__ total, const fid_stag_quad *__restrict__ slots, fid_stag_quad *__restrict__ out)
-{
-    k_stag_gather_quads_impl(range, nsegs, counts, total, slots, out);
-}
 struct k_stag_gather_quads_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(const int2 *__restrict__ range, const int *__restrict__ nsegs, const int *__restrict__ counts, const int *__restrict__ total, const fid_stag_quad *__restrict__ slots, fid_stag_quad *__restrict__ out) const { k_stag_gather_quads_impl(range, nsegs, counts, total, slots, out); }
+    __device__ __forceinline__ void operator()(const int2 *__restrict__ range, const int *__restrict__ nsegs, const int *__restrict__ counts,
+                                               const int *__restrict__ total, const fid_stag_quad *__restrict__ slots,
+                                               fid_stag_quad *__restrict__ out) const
+    {
+        const int seg = blockIdx.x * 64 + threadIdx.x;
+        const int ns = *nsegs;
+        if (seg >= ns) return;
+        const int o = counts[seg], n = (seg + 1 < ns ? counts[seg + 1] : *total) - o;
+        const fid_stag_quad *Q = slots + range[seg].x;
+        for (int j = 0; j < n; j++) out[o + j] = Q[j];
+    }
 };
 
 // ------------------------------------------------------------------------------------------------ K15: decoding
@@ -436,191 +421,181 @@ __device__ int sd_read_bilinear(const uint8_t *__restrict__ img, int W, int H, d
     return (int)(acc / tot);
 }
 
-__device__ __forceinline__ void k_stag_decode_impl(const fid_stag_quad *__restrict__ quads, const int *__restrict__ nquads,
-                                                     const uint8_t *__restrict__ img, int W, int H, const double *__restrict__ locs /* [72][3] */,
-                                                     const unsigned long long *__restrict__ words, int nwords, int err_corr,
-                                                     fid_stag_marker *__restrict__ cand, int *__restrict__ found)
-{
-    __shared__ int s_hist[4][256];
-    const int wq = threadIdx.x >> 6, q = blockIdx.x * 4 + wq, lane = threadIdx.x & 63;
-    if (q >= *nquads) return;
-    const fid_stag_quad Q = quads[q];
-    double Hm[9], cen[2];
-    sd_homography(Q.corners, Q.lineInf, Hm, cen);
-    int *hist = s_hist[wq];
-    for (int i = lane; i < 256; i += 64) hist[i] = 0;
-    __builtin_amdgcn_wave_barrier();
-    int smp[2] = {0, 0};
-    for (int k = 0; k < 2; k++) {
-        const int i = lane + 64 * k;
-        if (i < 72) {
-            const double *L = locs + 3 * i;
-            const double p0 = Hm[0] * L[0] + Hm[1] * L[1] + Hm[2] * L[2], p1 = Hm[3] * L[0] + Hm[4] * L[1] + Hm[5] * L[2];
-            const double p2 = Hm[6] * L[0] + Hm[7] * L[1] + Hm[8] * L[2];
-            smp[k] = sd_read_bilinear(img, W, H, p0 / p2, p1 / p2) & 255;
-            atomicAdd(&hist[smp[k]], 1);
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // Otsu threshold of the 72 readings (cv::threshold THRESH_OTSU: getThreshVal_Otsu_8u, the histogram form)
-    int thr;
-    {
-        const double scale = 1. / 72;
-        double mu = 0;
-        for (int i = 0; i < 256; i++) mu += i * (double)hist[i];
-        mu *= scale;
-        double mu1 = 0, q1 = 0, max_sigma = 0;
-        int max_val = 0;
-        // (round 6) 72 readings leave most of the 256 bins empty, and an empty bin only passes mu1 through (mu1 * q1) / q1.  Once that
-        // returns the mu1 it was given, this bin and every empty bin behind it change nothing: same q1, same mu1, the same sigma again,
-        // which is not above the maximum it already had its chance to set.  The walk jumps to the next non-empty bin there; where the
-        // round trip still moves mu1 by a rounding it goes on bin by bin, as the reference does.  (Two divisions a bin, 256 bins, by
-        // every lane alike: 30 of this kernel's 46 us.)
-        unsigned long long nz[4];
-#pragma unroll
-        for (int w = 0; w < 4; w++) nz[w] = __ballot(hist[64 * w + lane] != 0);
-        int i = 0;
-        while (i < 256) {
-            const int h = hist[i];
-            const double p_i = h * scale;
-            const double mu1_in = mu1;
-            mu1 *= q1;
-            q1 += p_i;
-            const double q2 = 1. - q1;
-            if (!(fmin(q1, q2) < 1.1920928955078125e-07 || fmax(q1, q2) > 1. - 1.1920928955078125e-07)) {
-                mu1 = (mu1 + i * p_i) / q1;
-                const double mu2 = (mu - q1 * mu1) / q2;
-                const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
-                if (sigma > max_sigma) {
-                    max_sigma = sigma;
-                    max_val = i;
-                }
-            }
-            if (h == 0 && mu1 == mu1_in) {
-                int j = 256;
-#pragma unroll
-                for (int w = 3; w >= 0; w--) {
-                    unsigned long long mm = nz[w];
-                    if (w == ((i + 1) >> 6)) mm &= ~0ull << ((i + 1) & 63);
-                    if (w >= ((i + 1) >> 6) && mm) j = 64 * w + (int)__builtin_ctzll(mm);
-                }
-                i = j;
-            } else {
-                i++;
-            }
-        }
-        thr = max_val;
-    }
-    // THRESH_BINARY_INV: readings above the threshold -> 0, the others -> 255 -> bit 1
-    const unsigned long long code = __ballot(lane < 48 && smp[0] <= thr);
-    // Decoder::decode: the first codeword within err_corr bits
-    int hit = -1;
-    for (int base = 0; base < nwords && hit < 0; base += 64) {
-        const int i = base + lane;
-        const bool ok = i < nwords && __builtin_popcountll(code ^ words[i]) <= err_corr;
-        const unsigned long long m = __ballot(ok);
-        if (m) hit = base + __builtin_ctzll(m);
-    }
-    if (lane != 0) return;
-    found[q] = hit >= 0 ? 1 : 0;
-    if (hit < 0) return;
-    const int n = nwords / 4, id = hit % n, shift = hit / n;
-    fid_stag_marker M;
-    M.id = id;
-    M.shift = shift;
-    for (int k = 0; k < 4; k++) {  // shiftCorners2: corner k <- corner (k + shift) % 4
-        M.corners[2 * k] = Q.corners[2 * ((k + shift) & 3)];
-        M.corners[2 * k + 1] = Q.corners[2 * ((k + shift) & 3) + 1];
-    }
-    for (int k = 0; k < 3; k++) M.lineInf[k] = Q.lineInf[k];
-    M.projectiveDistortion = Q.projectiveDistortion;
-    if (shift >= 1 && shift <= 3) sd_homography(M.corners, M.lineInf, M.H, M.center);
-    else {
-        for (int k = 0; k < 9; k++) M.H[k] = Hm[k];
-        M.center[0] = cen[0];
-        M.center[1] = cen[1];
-    }
-    M.code = code;
-    cand[q] = M;
-}
-__global__ __launch_bounds__(256) void k_stag_decode(const fid_stag_quad *__restrict__ quads, const int *__restrict__ nquads, const uint8_t *__restrict__ img, int W, int H, const double *__restrict__ locs , const unsigned long long *__restrict__ words, int nwords, int err_corr, fid_stag_marker *__restrict__ cand, int *__restrict__ found)
-{
-    k_stag_decode_impl(quads, nquads, img, W, H, locs, words, nwords, err_corr, cand, found);
-}
 struct k_stag_decode_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const fid_stag_quad *__restrict__ quads, const int *__restrict__ nquads, const uint8_t *__restrict__ img, int W, int H, const double *__restrict__ locs , const unsigned long long *__restrict__ words, int nwords, int err_corr, fid_stag_marker *__restrict__ cand, int *__restrict__ found) const { k_stag_decode_impl(quads, nquads, img, W, H, locs, words, nwords, err_corr, cand, found); }
+    __device__ __forceinline__ void operator()(const fid_stag_quad *__restrict__ quads, const int *__restrict__ nquads,
+                                               const uint8_t *__restrict__ img, int W, int H, const double *__restrict__ locs /* [72][3] */,
+                                               const unsigned long long *__restrict__ words, int nwords, int err_corr,
+                                               fid_stag_marker *__restrict__ cand, int *__restrict__ found) const
+    {
+        __shared__ int s_hist[4][256];
+        const int wq = threadIdx.x >> 6, q = blockIdx.x * 4 + wq, lane = threadIdx.x & 63;
+        if (q >= *nquads) return;
+        const fid_stag_quad Q = quads[q];
+        double Hm[9], cen[2];
+        sd_homography(Q.corners, Q.lineInf, Hm, cen);
+        int *hist = s_hist[wq];
+        for (int i = lane; i < 256; i += 64) hist[i] = 0;
+        __builtin_amdgcn_wave_barrier();
+        int smp[2] = {0, 0};
+        for (int k = 0; k < 2; k++) {
+            const int i = lane + 64 * k;
+            if (i < 72) {
+                const double *L = locs + 3 * i;
+                const double p0 = Hm[0] * L[0] + Hm[1] * L[1] + Hm[2] * L[2], p1 = Hm[3] * L[0] + Hm[4] * L[1] + Hm[5] * L[2];
+                const double p2 = Hm[6] * L[0] + Hm[7] * L[1] + Hm[8] * L[2];
+                smp[k] = sd_read_bilinear(img, W, H, p0 / p2, p1 / p2) & 255;
+                atomicAdd(&hist[smp[k]], 1);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        // Otsu threshold of the 72 readings (cv::threshold THRESH_OTSU: getThreshVal_Otsu_8u, the histogram form)
+        int thr;
+        {
+            const double scale = 1. / 72;
+            double mu = 0;
+            for (int i = 0; i < 256; i++) mu += i * (double)hist[i];
+            mu *= scale;
+            double mu1 = 0, q1 = 0, max_sigma = 0;
+            int max_val = 0;
+            // (round 6) 72 readings leave most of the 256 bins empty, and an empty bin only passes mu1 through (mu1 * q1) / q1.  Once that
+            // returns the mu1 it was given, this bin and every empty bin behind it change nothing: same q1, same mu1, the same sigma again,
+            // which is not above the maximum it already had its chance to set.  The walk jumps to the next non-empty bin there; where the
+            // round trip still moves mu1 by a rounding it goes on bin by bin, as the reference does.  (Two divisions a bin, 256 bins, by
+            // every lane alike: 30 of this kernel's 46 us.)
+            unsigned long long nz[4];
+#pragma unroll
+            for (int w = 0; w < 4; w++) nz[w] = __ballot(hist[64 * w + lane] != 0);
+            int i = 0;
+            while (i < 256) {
+                const int h = hist[i];
+                const double p_i = h * scale;
+                const double mu1_in = mu1;
+                mu1 *= q1;
+                q1 += p_i;
+                const double q2 = 1. - q1;
+                if (!(fmin(q1, q2) < 1.1920928955078125e-07 || fmax(q1, q2) > 1. - 1.1920928955078125e-07)) {
+                    mu1 = (mu1 + i * p_i) / q1;
+                    const double mu2 = (mu - q1 * mu1) / q2;
+                    const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
+                    if (sigma > max_sigma) {
+                        max_sigma = sigma;
+                        max_val = i;
+                    }
+                }
+                if (h == 0 && mu1 == mu1_in) {
+                    int j = 256;
+#pragma unroll
+                    for (int w = 3; w >= 0; w--) {
+                        unsigned long long mm = nz[w];
+                        if (w == ((i + 1) >> 6)) mm &= ~0ull << ((i + 1) & 63);
+                        if (w >= ((i + 1) >> 6) && mm) j = 64 * w + (int)__builtin_ctzll(mm);
+                    }
+                    i = j;
+                } else {
+                    i++;
+                }
+            }
+            thr = max_val;
+        }
+        // THRESH_BINARY_INV: readings above the threshold -> 0, the others -> 255 -> bit 1
+        const unsigned long long code = __ballot(lane < 48 && smp[0] <= thr);
+        // Decoder::decode: the first codeword within err_corr bits
+        int hit = -1;
+        for (int base = 0; base < nwords && hit < 0; base += 64) {
+            const int i = base + lane;
+            const bool ok = i < nwords && __builtin_popcountll(code ^ words[i]) <= err_corr;
+            const unsigned long long m = __ballot(ok);
+            if (m) hit = base + __builtin_ctzll(m);
+        }
+        if (lane != 0) return;
+        found[q] = hit >= 0 ? 1 : 0;
+        if (hit < 0) return;
+        const int n = nwords / 4, id = hit % n, shift = hit / n;
+        fid_stag_marker M;
+        M.id = id;
+        M.shift = shift;
+        for (int k = 0; k < 4; k++) {  // shiftCorners2: corner k <- corner (k + shift) % 4
+            M.corners[2 * k] = Q.corners[2 * ((k + shift) & 3)];
+            M.corners[2 * k + 1] = Q.corners[2 * ((k + shift) & 3) + 1];
+        }
+        for (int k = 0; k < 3; k++) M.lineInf[k] = Q.lineInf[k];
+        M.projectiveDistortion = Q.projectiveDistortion;
+        if (shift >= 1 && shift <= 3) sd_homography(M.corners, M.lineInf, M.H, M.center);
+        else {
+            for (int k = 0; k < 9; k++) M.H[k] = Hm[k];
+            M.center[0] = cen[0];
+            M.center[1] = cen[1];
+        }
+        M.code = code;
+        cand[q] = M;
+    }
 };
 
 // Stag::checkDuplicate over the decoded quads in quad order: one marker per id, the least distorted one, at the position of
 // the first quad that showed the id
-__device__ __forceinline__ void k_stag_dedup_impl(const fid_stag_marker *__restrict__ cand, const int *__restrict__ found, const int *__restrict__ nquads,
-                                                   fid_stag_marker *__restrict__ out, int *__restrict__ nout)
-{
-    if (blockIdx.x != 0) return;
-    const int n = *nquads;
-    const int lane = (int)threadIdx.x;
-    // (round 6) by a wave: the flags and ids of 64 quads arrive with one load each, lane k keeps (id, distortion, source quad) of
-    // output slot k, the decoded quads are taken in quad order as before -- one thread walked `found` one dependent load after the
-    // other: 24 us for a frame's ~100 quads.  More than 64 distinct ids (never seen; the library has 12 .. 157): the loop below.
-    {
-        int nfound = 0;
-        for (int q0 = 0; q0 < n; q0 += 64) nfound += (int)__builtin_popcountll(__ballot(q0 + lane < n && found[q0 + lane] != 0));
-        if (nfound <= 64) {
-            int m = 0, oid = -1, osrc = -1;
-            double opd = 0;
-            for (int q0 = 0; q0 < n; q0 += 64) {
-                const int q = q0 + lane;
-                const bool f = q < n && found[q] != 0;
-                const int id = f ? cand[q].id : -1;
-                const double pd = f ? cand[q].projectiveDistortion : 0.0;
-                unsigned long long mask = __ballot(f);
-                while (mask) {
-                    const int l = __builtin_ctzll(mask);
-                    mask &= mask - 1;
-                    const int idq = __builtin_amdgcn_readlane(id, l);
-                    const double pdq = shfl_f64(pd, l);
-                    const unsigned long long hit = __ballot(lane < m && oid == idq);
-                    if (hit) {
-                        if (lane < m && oid == idq && pdq < opd) {
-                            opd = pdq;
-                            osrc = q0 + l;
-                        }
-                    } else {
-                        if (lane == m) {
-                            oid = idq;
-                            opd = pdq;
-                            osrc = q0 + l;
-                        }
-                        m++;
-                    }
-                }
-            }
-            if (lane < m) out[lane] = cand[osrc];
-            if (lane == 0) *nout = m;
-            return;
-        }
-    }
-    if (lane != 0) return;
-    int m = 0;
-    for (int q = 0; q < n; q++) {
-        if (!found[q]) continue;
-        bool notFound = true;
-        for (int k = 0; k < m; k++) {
-            if (out[k].id == cand[q].id) {
-                notFound = false;
-                if (cand[q].projectiveDistortion < out[k].projectiveDistortion) out[k] = cand[q];
-            }
-        }
-        if (notFound) out[m++] = cand[q];
-    }
-    *nout = m;
-}
-__global__ __launch_bounds__(64) void k_stag_dedup(const fid_stag_marker *__restrict__ cand, const int *__restrict__ found, const int *__restrict__ nquads, fid_stag_marker *__restrict__ out, int *__restrict__ nout)
-{
-    k_stag_dedup_impl(cand, found, nquads, out, nout);
-}
 struct k_stag_dedup_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ cand, const int *__restrict__ found, const int *__restrict__ nquads, fid_stag_marker *__restrict__ out, int *__restrict__ nout) const { k_stag_dedup_impl(cand, found, nquads, out, nout); }
+    __device__ __forceinline__ void operator()(const fid_stag_marker *__restrict__ cand, const int *__restrict__ found, const int *__restrict__ nquads,
+                                               fid_stag_marker *__restrict__ out, int *__restrict__ nout) const
+    {
+        if (blockIdx.x != 0) return;
+        const int n = *nquads;
+        const int lane = (int)threadIdx.x;
+        // (round 6) by a wave: the flags and ids of 64 quads arrive with one load each, lane k keeps (id, distortion, source quad) of
+        // output slot k, the decoded quads are taken in quad order as before -- one thread walked `found` one dependent load after the
+        // other: 24 us for a frame's ~100 quads.  More than 64 distinct ids (never seen; the library has 12 .. 157): the loop below.
+        {
+            int nfound = 0;
+            for (int q0 = 0; q0 < n; q0 += 64) nfound += (int)__builtin_popcountll(__ballot(q0 + lane < n && found[q0 + lane] != 0));
+            if (nfound <= 64) {
+                int m = 0, oid = -1, osrc = -1;
+                double opd = 0;
+                for (int q0 = 0; q0 < n; q0 += 64) {
+                    const int q = q0 + lane;
+                    const bool f = q < n && found[q] != 0;
+                    const int id = f ? cand[q].id : -1;
+                    const double pd = f ? cand[q].projectiveDistortion : 0.0;
+                    unsigned long long mask = __ballot(f);
+                    while (mask) {
+                        const int l = __builtin_ctzll(mask);
+                        mask &= mask - 1;
+                        const int idq = __builtin_amdgcn_readlane(id, l);
+                        const double pdq = shfl_f64(pd, l);
+                        const unsigned long long hit = __ballot(lane < m && oid == idq);
+                        if (hit) {
+                            if (lane < m && oid == idq && pdq < opd) {
+                                opd = pdq;
+                                osrc = q0 + l;
+                            }
+                        } else {
+                            if (lane == m) {
+                                oid = idq;
+                                opd = pdq;
+                                osrc = q0 + l;
+                            }
+                            m++;
+                        }
+                    }
+                }
+                if (lane < m) out[lane] = cand[osrc];
+                if (lane == 0) *nout = m;
+                return;
+            }
+        }
+        if (lane != 0) return;
+        int m = 0;
+        for (int q = 0; q < n; q++) {
+            if (!found[q]) continue;
+            bool notFound = true;
+            for (int k = 0; k < m; k++) {
+                if (out[k].id == cand[q].id) {
+                    notFound = false;
+                    if (cand[q].projectiveDistortion < out[k].projectiveDistortion) out[k] = cand[q];
+                }
+            }
+            if (notFound) out[m++] = cand[q];
+        }
+        *nout = m;
+    }
 };

@@ -676,32 +676,27 @@ struct StagRouter {
     }
 };
 
-__device__ __forceinline__ void k_stag_route_seq_impl(StagRoute R, const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors,
-                                                       int grad_thresh)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    StagRouter S;
-    S.R = R;
-    S.noSegments = S.totalPixels = S.overflow = 0;
-    S.segbase = S.nsp = 0;
-    const int n = (int)*n_anchors;
-    for (int k = n - 1; k >= 0; k--) {
-        const int off = sorted[k];
-        if (R.edge[off] != STAG_ANCHOR_PIXEL) continue;
-        S.route_anchor(off / R.W, off % R.W, grad_thresh);
-        if (S.overflow) break;
-    }
-    R.counters[0] = S.noSegments;
-    R.counters[1] = S.totalPixels;
-    R.counters[2] = S.overflow;
-}
-__global__ __launch_bounds__(64) void k_stag_route_seq(StagRoute R, const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors, int grad_thresh)
-{
-    k_stag_route_seq_impl(R, sorted, n_anchors, grad_thresh);
-}
 struct k_stag_route_seq_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(StagRoute R, const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors, int grad_thresh) const { k_stag_route_seq_impl(R, sorted, n_anchors, grad_thresh); }
+    __device__ __forceinline__ void operator()(StagRoute R, const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors,
+                                               int grad_thresh) const
+    {
+        if (threadIdx.x != 0 || blockIdx.x != 0) return;
+        StagRouter S;
+        S.R = R;
+        S.noSegments = S.totalPixels = S.overflow = 0;
+        S.segbase = S.nsp = 0;
+        const int n = (int)*n_anchors;
+        for (int k = n - 1; k >= 0; k--) {
+            const int off = sorted[k];
+            if (R.edge[off] != STAG_ANCHOR_PIXEL) continue;
+            S.route_anchor(off / R.W, off % R.W, grad_thresh);
+            if (S.overflow) break;
+        }
+        R.counters[0] = S.noSegments;
+        R.counters[1] = S.totalPixels;
+        R.counters[2] = S.overflow;
+    }
 };
 
 // ---- component-parallel routing ---------------------------------------------------------------------------------
@@ -753,20 +748,15 @@ struct StagFills {
         vis(p); vis(n16); vis(na16); vis(v);
     }
 };
-__device__ __forceinline__ void k_stag_fills_impl(StagFills F)
-{
-    const unsigned i = blockIdx.x * 256 + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 6; k++)
-        if (i < (k < 3 ? F.n16[k] : F.na16)) F.p[k][i] = make_uint4(F.v[k], F.v[k], F.v[k], F.v[k]);
-}
-__global__ __launch_bounds__(256) void k_stag_fills(StagFills F)
-{
-    k_stag_fills_impl(F);
-}
 struct k_stag_fills_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(StagFills F) const { k_stag_fills_impl(F); }
+    __device__ __forceinline__ void operator()(StagFills F) const
+    {
+        const unsigned i = blockIdx.x * 256 + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < 6; k++)
+            if (i < (k < 3 ? F.n16[k] : F.na16)) F.p[k][i] = make_uint4(F.v[k], F.v[k], F.v[k], F.v[k]);
+    }
 };
 
 // A frame QUEUED AHEAD of its own counts (fid_stag.hip, stag_advance_impl): the host sizes every launch by what the context's last
@@ -793,27 +783,22 @@ struct StagGuard {
         v(cnt); v(cap); v(kill); v(ncnt); v(nkill); v(reset); v(bad); v(mdst); v(msrc); v(mn); v(bad_host);
     }
 };
-__device__ __forceinline__ void k_stag_spec_guard_impl(StagGuard g)
-{
-    if (blockIdx.x != 0) return;
-    for (int k = 0; k < 3; k++)
-        if (g.mdst[k] && (int)threadIdx.x < g.mn[k]) g.mdst[k][threadIdx.x] = g.msrc[k][threadIdx.x];
-    __syncthreads();  // (the counts are read above before thread 0 may zero them below)
-    if (threadIdx.x != 0) return;
-    bool b = !g.reset && *g.bad != 0;
-    for (int i = 0; i < g.ncnt; i++) b = b || (unsigned)*g.cnt[i] > (unsigned)g.cap[i];
-    if (g.reset || b) *g.bad = b ? 1 : 0;
-    if (g.bad_host) *g.bad_host = b ? 1 : 0;
-    if (b)
-        for (int i = 0; i < g.nkill; i++) *g.kill[i] = 0;
-}
-__global__ __launch_bounds__(64) void k_stag_spec_guard(StagGuard g)
-{
-    k_stag_spec_guard_impl(g);
-}
 struct k_stag_spec_guard_fn {
     static constexpr int kBounds = 64;
-    __device__ __forceinline__ void operator()(StagGuard g) const { k_stag_spec_guard_impl(g); }
+    __device__ __forceinline__ void operator()(StagGuard g) const
+    {
+        if (blockIdx.x != 0) return;
+        for (int k = 0; k < 3; k++)
+            if (g.mdst[k] && (int)threadIdx.x < g.mn[k]) g.mdst[k][threadIdx.x] = g.msrc[k][threadIdx.x];
+        __syncthreads();  // (the counts are read above before thread 0 may zero them below)
+        if (threadIdx.x != 0) return;
+        bool b = !g.reset && *g.bad != 0;
+        for (int i = 0; i < g.ncnt; i++) b = b || (unsigned)*g.cnt[i] > (unsigned)g.cap[i];
+        if (g.reset || b) *g.bad = b ? 1 : 0;
+        if (g.bad_host) *g.bad_host = b ? 1 : 0;
+        if (b)
+            for (int i = 0; i < g.nkill; i++) *g.kill[i] = 0;
+    }
 };
 
 __device__ __forceinline__ int ccl_find(const int *L, int a)
@@ -849,100 +834,90 @@ __device__ __forceinline__ void ccl_union(int *L, int a, int b)
     }
 }
 
-__device__ __forceinline__ void k_stag_ccl_tile_impl(const int16_t *__restrict__ grad, int W, int H, int thresh, int *__restrict__ label,
-                                                       int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, uint8_t *__restrict__ tilefg)
-{
-    __shared__ int L[CCL_TW * CCL_TH];
-    const int x0 = blockIdx.x * CCL_TW, y0 = blockIdx.y * CCL_TH;
-    int any = 0;
-    for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
-        const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
-        const bool fg = x < W && y < H && grad[y * W + x] >= thresh;
-        L[k] = fg ? k : -1;
-        any |= fg;
-    }
-    // (round 6) a tile without a foreground pixel -- 60 % of the tiles of the bench frames -- has nothing to merge: its labels are
-    // -1, and k_stag_ccl_flatten does not come back to it (tilefg)
-    if (!__syncthreads_or(any)) {
-        if (threadIdx.x == 0) tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x] = 0;
-        for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
-            const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
-            if (x < W && y < H) label[y * W + x] = -1;
-        }
-        return;
-    }
-    if (threadIdx.x == 0) tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x] = 1;
-    for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
-        if (L[k] < 0) continue;
-        const int lx = k % CCL_TW, ly = k / CCL_TW;
-        if (ly > 0) {
-            if (L[k - CCL_TW] >= 0) {
-                ccl_union(L, k, k - CCL_TW);
-            } else {
-                if (lx > 0 && L[k - CCL_TW - 1] >= 0) ccl_union(L, k, k - CCL_TW - 1);
-                if (lx < CCL_TW - 1 && L[k - CCL_TW + 1] >= 0) ccl_union(L, k, k - CCL_TW + 1);
-            }
-        }
-        if (lx > 0 && L[k - 1] >= 0) ccl_union(L, k, k - 1);
-    }
-    __syncthreads();
-    for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
-        const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
-        if (x >= W || y >= H) continue;
-        int v = -1;
-        if (L[k] >= 0) {
-            const int r = ccl_find(L, k);
-            v = (y0 + r / CCL_TW) * W + x0 + (r % CCL_TW);
-            if (r == k) {
-                // a component's final root is the smallest index in it, hence the root of its piece in ITS tile: the per-root counters
-                // only have to be clean at the tiles' local roots (until round 6: at every foreground pixel, 24 bytes each)
-                csize[y * W + x] = 0;
-                canch[y * W + x] = 0;
-                cbox[y * W + x] = make_int4(0x7fffffff, 0x7fffffff, -1, -1);  // min row, min column, max row, max column
-            }
-        }
-        label[y * W + x] = v;
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_ccl_tile(const int16_t *__restrict__ grad, int W, int H, int thresh, int *__restrict__ label, int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, uint8_t *__restrict__ tilefg)
-{
-    k_stag_ccl_tile_impl(grad, W, H, thresh, label, csize, canch, cbox, tilefg);
-}
 struct k_stag_ccl_tile_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, int W, int H, int thresh, int *__restrict__ label, int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, uint8_t *__restrict__ tilefg) const { k_stag_ccl_tile_impl(grad, W, H, thresh, label, csize, canch, cbox, tilefg); }
+    __device__ __forceinline__ void operator()(const int16_t *__restrict__ grad, int W, int H, int thresh, int *__restrict__ label,
+                                               int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, uint8_t *__restrict__ tilefg) const
+    {
+        __shared__ int L[CCL_TW * CCL_TH];
+        const int x0 = blockIdx.x * CCL_TW, y0 = blockIdx.y * CCL_TH;
+        int any = 0;
+        for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
+            const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
+            const bool fg = x < W && y < H && grad[y * W + x] >= thresh;
+            L[k] = fg ? k : -1;
+            any |= fg;
+        }
+        // (round 6) a tile without a foreground pixel -- 60 % of the tiles of the bench frames -- has nothing to merge: its labels are
+        // -1, and k_stag_ccl_flatten does not come back to it (tilefg)
+        if (!__syncthreads_or(any)) {
+            if (threadIdx.x == 0) tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x] = 0;
+            for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
+                const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
+                if (x < W && y < H) label[y * W + x] = -1;
+            }
+            return;
+        }
+        if (threadIdx.x == 0) tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x] = 1;
+        for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
+            if (L[k] < 0) continue;
+            const int lx = k % CCL_TW, ly = k / CCL_TW;
+            if (ly > 0) {
+                if (L[k - CCL_TW] >= 0) {
+                    ccl_union(L, k, k - CCL_TW);
+                } else {
+                    if (lx > 0 && L[k - CCL_TW - 1] >= 0) ccl_union(L, k, k - CCL_TW - 1);
+                    if (lx < CCL_TW - 1 && L[k - CCL_TW + 1] >= 0) ccl_union(L, k, k - CCL_TW + 1);
+                }
+            }
+            if (lx > 0 && L[k - 1] >= 0) ccl_union(L, k, k - 1);
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < CCL_TW * CCL_TH; k += 256) {
+            const int x = x0 + (k % CCL_TW), y = y0 + (k / CCL_TW);
+            if (x >= W || y >= H) continue;
+            int v = -1;
+            if (L[k] >= 0) {
+                const int r = ccl_find(L, k);
+                v = (y0 + r / CCL_TW) * W + x0 + (r % CCL_TW);
+                if (r == k) {
+                    // a component's final root is the smallest index in it, hence the root of its piece in ITS tile: the per-root counters
+                    // only have to be clean at the tiles' local roots (until round 6: at every foreground pixel, 24 bytes each)
+                    csize[y * W + x] = 0;
+                    canch[y * W + x] = 0;
+                    cbox[y * W + x] = make_int4(0x7fffffff, 0x7fffffff, -1, -1);  // min row, min column, max row, max column
+                }
+            }
+            label[y * W + x] = v;
+        }
+    }
 };
 
 // the pixels of a tile's first row, first column and last column against their neighbours in the adjacent tiles
-__device__ __forceinline__ void k_stag_ccl_border_impl(int W, int H, int *label)
-{
-    const int t = threadIdx.x;
-    int lx, ly;
-    if (t < CCL_TW) { lx = t; ly = 0; }
-    else if (t < CCL_TW + CCL_TH) { lx = 0; ly = t - CCL_TW; }
-    else if (t < CCL_TW + 2 * CCL_TH) { lx = CCL_TW - 1; ly = t - CCL_TW - CCL_TH; }
-    else return;
-    if (t >= CCL_TW && ly == 0) return;  // (the corners belong to the row)
-    const int c = blockIdx.x * CCL_TW + lx, r = blockIdx.y * CCL_TH + ly;
-    if (c >= W || r >= H) return;
-    const int i = r * W + c;
-    if (label[i] < 0) return;
-    const bool up = r > 0, left = c > 0, right = c < W - 1;
-    if (up && label[i - W] >= 0) {
-        if (ly == 0) ccl_union(label, i, i - W);
-    } else if (up) {
-        if (left && (lx == 0 || ly == 0) && label[i - W - 1] >= 0) ccl_union(label, i, i - W - 1);
-        if (right && (lx == CCL_TW - 1 || ly == 0) && label[i - W + 1] >= 0) ccl_union(label, i, i - W + 1);
-    }
-    if (left && lx == 0 && label[i - 1] >= 0) ccl_union(label, i, i - 1);
-}
-__global__ __launch_bounds__(128) void k_stag_ccl_border(int W, int H, int *label)
-{
-    k_stag_ccl_border_impl(W, H, label);
-}
 struct k_stag_ccl_border_fn {
     static constexpr int kBounds = 128;
-    __device__ __forceinline__ void operator()(int W, int H, int *label) const { k_stag_ccl_border_impl(W, H, label); }
+    __device__ __forceinline__ void operator()(int W, int H, int *label) const
+    {
+        const int t = threadIdx.x;
+        int lx, ly;
+        if (t < CCL_TW) { lx = t; ly = 0; }
+        else if (t < CCL_TW + CCL_TH) { lx = 0; ly = t - CCL_TW; }
+        else if (t < CCL_TW + 2 * CCL_TH) { lx = CCL_TW - 1; ly = t - CCL_TW - CCL_TH; }
+        else return;
+        if (t >= CCL_TW && ly == 0) return;  // (the corners belong to the row)
+        const int c = blockIdx.x * CCL_TW + lx, r = blockIdx.y * CCL_TH + ly;
+        if (c >= W || r >= H) return;
+        const int i = r * W + c;
+        if (label[i] < 0) return;
+        const bool up = r > 0, left = c > 0, right = c < W - 1;
+        if (up && label[i - W] >= 0) {
+            if (ly == 0) ccl_union(label, i, i - W);
+        } else if (up) {
+            if (left && (lx == 0 || ly == 0) && label[i - W - 1] >= 0) ccl_union(label, i, i - W - 1);
+            if (right && (lx == CCL_TW - 1 || ly == 0) && label[i - W + 1] >= 0) ccl_union(label, i, i - W + 1);
+        }
+        if (left && lx == 0 && label[i - 1] >= 0) ccl_union(label, i, i - 1);
+    }
 };
 
 // Every foreground pixel to its final root, and per root: pixels, anchors, bounding box.  A workgroup = one 64 x 16 tile (the tiles
@@ -950,223 +925,208 @@ struct k_stag_ccl_border_fn {
 // root that occurs in the tile -- and leave as ONE set of global atomics per (tile, root).  (Until round 6 a wave of 64 consecutive
 // pixels sent its own set per root: a marker's outline of 3 000 pixels meant ~2 000 sets of six atomics on the same six words, and
 // that traffic jam was 10 of this kernel's 16 us per frame; timed with the statistics compiled out, -DFLATTEN_NO_STATS.)
-__device__ __forceinline__ void k_stag_ccl_flatten_impl(int W, int H, int *label, const uint8_t *__restrict__ anchors, int *__restrict__ csize,
-                                                          int *__restrict__ canch, int4 *__restrict__ cbox, int *__restrict__ roots, int *__restrict__ cursors, const uint8_t *__restrict__ tilefg)
-{
-    constexpr int SLOTS = 32;
-    __shared__ int s_root[SLOTS], s_cnt[SLOTS], s_anch[SLOTS], s_minr[SLOTS], s_minc[SLOTS], s_maxr[SLOTS], s_maxc[SLOTS];
-    if (!tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x]) return;  // (no foreground pixel in this tile: k_stag_ccl_tile said so)
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int x0 = blockIdx.x * CCL_TW, y0 = blockIdx.y * CCL_TH;
-    if (tid < SLOTS) {
-        s_root[tid] = -1;
-        s_cnt[tid] = s_anch[tid] = 0;
-        s_minr[tid] = s_minc[tid] = 0x7fffffff;
-        s_maxr[tid] = s_maxc[tid] = -1;
-    }
-    __syncthreads();
-    const int c = x0 + lane;
-#pragma unroll
-    for (int j = 0; j < CCL_TH / 4; j++) {
-        const int r = y0 + (tid >> 6) + 4 * j;  // (wave-uniform: a wave takes one tile row per round)
-        const int i = r * W + c;
-        int root = -1;
-        bool anch = false;
-        if (c < W && r < H && label[i] >= 0) {
-            root = ccl_find(label, i);
-            label[i] = root;
-            anch = anchors[i] == STAG_ANCHOR_PIXEL;
-            // the frame's ROOTS as a list (cursors[13] counts them): k_stag_comp_alloc goes by it instead of asking every pixel of the
-            // image whether it is one (a few hundred roots among two million pixels).  8-connected components are at most
-            // ceil(W / 2) * ceil(H / 2), which is what `roots` holds.
-            if (root == i) roots[atomicAdd(&cursors[13], 1)] = i;
-        }
-        unsigned long long pending = __ballot(root >= 0);
-#ifdef FLATTEN_NO_STATS
-        pending = 0;
-#endif
-        while (pending) {
-            const int lead = __builtin_ctzll(pending);
-            const int r0 = __builtin_amdgcn_readlane(root, lead);
-            const bool mine = root == r0;
-            const unsigned long long m = __ballot(mine), ma = __ballot(mine && anch);
-            if (lane == lead) {
-                const int cnt = (int)__builtin_popcountll(m), na = (int)__builtin_popcountll(ma);
-                const int mnc = x0 + (int)__builtin_ctzll(m), mxc = x0 + 63 - (int)__builtin_clzll(m);
-                // the root's slot: open addressing on the root's index, SLOTS tries (a tile that holds more roots than slots -- noise --
-                // sends the surplus straight to global memory)
-                int slot = -1;
-                unsigned h = ((unsigned)r0 * 2654435761u) >> 27;
-                for (int t = 0; t < SLOTS; t++, h = (h + 1) & (SLOTS - 1)) {
-                    const int old = atomicCAS(&s_root[h], -1, r0);
-                    if (old == -1 || old == r0) {
-                        slot = (int)h;
-                        break;
-                    }
-                }
-                if (slot >= 0) {
-                    atomicAdd(&s_cnt[slot], cnt);
-                    if (na) atomicAdd(&s_anch[slot], na);
-                    atomicMin(&s_minr[slot], r);
-                    atomicMin(&s_minc[slot], mnc);
-                    atomicMax(&s_maxr[slot], r);
-                    atomicMax(&s_maxc[slot], mxc);
-                } else {
-                    atomicAdd(&csize[r0], cnt);
-                    if (na) atomicAdd(&canch[r0], na);
-                    int *bx = reinterpret_cast<int *>(cbox + r0);
-                    atomicMin(bx + 0, r);
-                    atomicMin(bx + 1, mnc);
-                    atomicMax(bx + 2, r);
-                    atomicMax(bx + 3, mxc);
-                }
-            }
-            pending &= ~m;
-        }
-    }
-    __syncthreads();
-    if (tid < SLOTS && s_root[tid] >= 0) {
-        const int r0 = s_root[tid];
-        atomicAdd(&csize[r0], s_cnt[tid]);
-        if (s_anch[tid]) atomicAdd(&canch[r0], s_anch[tid]);
-        int *bx = reinterpret_cast<int *>(cbox + r0);
-        atomicMin(bx + 0, s_minr[tid]);
-        atomicMin(bx + 1, s_minc[tid]);
-        atomicMax(bx + 2, s_maxr[tid]);
-        atomicMax(bx + 3, s_maxc[tid]);
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_ccl_flatten(int W, int H, int *label, const uint8_t *__restrict__ anchors, int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, int *__restrict__ roots, int *__restrict__ cursors, const uint8_t *__restrict__ tilefg)
-{
-    k_stag_ccl_flatten_impl(W, H, label, anchors, csize, canch, cbox, roots, cursors, tilefg);
-}
 struct k_stag_ccl_flatten_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(int W, int H, int *label, const uint8_t *__restrict__ anchors, int *__restrict__ csize, int *__restrict__ canch, int4 *__restrict__ cbox, int *__restrict__ roots, int *__restrict__ cursors, const uint8_t *__restrict__ tilefg) const { k_stag_ccl_flatten_impl(W, H, label, anchors, csize, canch, cbox, roots, cursors, tilefg); }
+    __device__ __forceinline__ void operator()(int W, int H, int *label, const uint8_t *__restrict__ anchors, int *__restrict__ csize,
+                                               int *__restrict__ canch, int4 *__restrict__ cbox, int *__restrict__ roots, int *__restrict__ cursors, const uint8_t *__restrict__ tilefg) const
+    {
+        constexpr int SLOTS = 32;
+        __shared__ int s_root[SLOTS], s_cnt[SLOTS], s_anch[SLOTS], s_minr[SLOTS], s_minc[SLOTS], s_maxr[SLOTS], s_maxc[SLOTS];
+        if (!tilefg[blockIdx.y * ((W + CCL_TW - 1) / CCL_TW) + blockIdx.x]) return;  // (no foreground pixel in this tile: k_stag_ccl_tile said so)
+        const int tid = threadIdx.x, lane = tid & 63;
+        const int x0 = blockIdx.x * CCL_TW, y0 = blockIdx.y * CCL_TH;
+        if (tid < SLOTS) {
+            s_root[tid] = -1;
+            s_cnt[tid] = s_anch[tid] = 0;
+            s_minr[tid] = s_minc[tid] = 0x7fffffff;
+            s_maxr[tid] = s_maxc[tid] = -1;
+        }
+        __syncthreads();
+        const int c = x0 + lane;
+#pragma unroll
+        for (int j = 0; j < CCL_TH / 4; j++) {
+            const int r = y0 + (tid >> 6) + 4 * j;  // (wave-uniform: a wave takes one tile row per round)
+            const int i = r * W + c;
+            int root = -1;
+            bool anch = false;
+            if (c < W && r < H && label[i] >= 0) {
+                root = ccl_find(label, i);
+                label[i] = root;
+                anch = anchors[i] == STAG_ANCHOR_PIXEL;
+                // the frame's ROOTS as a list (cursors[13] counts them): k_stag_comp_alloc goes by it instead of asking every pixel of the
+                // image whether it is one (a few hundred roots among two million pixels).  8-connected components are at most
+                // ceil(W / 2) * ceil(H / 2), which is what `roots` holds.
+                if (root == i) roots[atomicAdd(&cursors[13], 1)] = i;
+            }
+            unsigned long long pending = __ballot(root >= 0);
+#ifdef FLATTEN_NO_STATS
+            pending = 0;
+#endif
+            while (pending) {
+                const int lead = __builtin_ctzll(pending);
+                const int r0 = __builtin_amdgcn_readlane(root, lead);
+                const bool mine = root == r0;
+                const unsigned long long m = __ballot(mine), ma = __ballot(mine && anch);
+                if (lane == lead) {
+                    const int cnt = (int)__builtin_popcountll(m), na = (int)__builtin_popcountll(ma);
+                    const int mnc = x0 + (int)__builtin_ctzll(m), mxc = x0 + 63 - (int)__builtin_clzll(m);
+                    // the root's slot: open addressing on the root's index, SLOTS tries (a tile that holds more roots than slots -- noise --
+                    // sends the surplus straight to global memory)
+                    int slot = -1;
+                    unsigned h = ((unsigned)r0 * 2654435761u) >> 27;
+                    for (int t = 0; t < SLOTS; t++, h = (h + 1) & (SLOTS - 1)) {
+                        const int old = atomicCAS(&s_root[h], -1, r0);
+                        if (old == -1 || old == r0) {
+                            slot = (int)h;
+                            break;
+                        }
+                    }
+                    if (slot >= 0) {
+                        atomicAdd(&s_cnt[slot], cnt);
+                        if (na) atomicAdd(&s_anch[slot], na);
+                        atomicMin(&s_minr[slot], r);
+                        atomicMin(&s_minc[slot], mnc);
+                        atomicMax(&s_maxr[slot], r);
+                        atomicMax(&s_maxc[slot], mxc);
+                    } else {
+                        atomicAdd(&csize[r0], cnt);
+                        if (na) atomicAdd(&canch[r0], na);
+                        int *bx = reinterpret_cast<int *>(cbox + r0);
+                        atomicMin(bx + 0, r);
+                        atomicMin(bx + 1, mnc);
+                        atomicMax(bx + 2, r);
+                        atomicMax(bx + 3, mxc);
+                    }
+                }
+                pending &= ~m;
+            }
+        }
+        __syncthreads();
+        if (tid < SLOTS && s_root[tid] >= 0) {
+            const int r0 = s_root[tid];
+            atomicAdd(&csize[r0], s_cnt[tid]);
+            if (s_anch[tid]) atomicAdd(&canch[r0], s_anch[tid]);
+            int *bx = reinterpret_cast<int *>(cbox + r0);
+            atomicMin(bx + 0, s_minr[tid]);
+            atomicMin(bx + 1, s_minc[tid]);
+            atomicMax(bx + 2, s_maxr[tid]);
+            atomicMax(bx + 3, s_maxc[tid]);
+        }
+    }
 };
 
 // cursors: [0] components [1] anchor slots [2] scratch pixels [3] stack [4] chains [5] output pixels [6] segments [7] overflow
 //          [8] overflow flags of the routing kernels [9] most anchors in one component [10] largest tile [11] big / [12] small
 //          components in the walk's order list [13] roots (k_stag_ccl_flatten's list)
-__device__ __forceinline__ void k_stag_comp_alloc_impl(const int *__restrict__ roots, const int *__restrict__ csize,
-                                                         const int *__restrict__ canch, const int4 *__restrict__ cbox, int *__restrict__ cursors, int max_comps,
-                                                         const int *caps, StagComp *__restrict__ comps, int *__restrict__ cidmap)
-{
-    const int nroots = cursors[13];
-    const int lane = threadIdx.x & 63;
-    // (round 6) a WAVE asks for the places of its 64 roots at once: one atomic per cursor and wave, the lanes' shares by prefix sums.
-    // A thread per root sent eight returning atomics of its own to the same seven words -- a frame's ~8 k roots queued up there:
-    // 19 us.  Which component gets which place was never defined (the atomics' order); every component still gets its own.
-    for (int k0 = blockIdx.x * 256 + (int)(threadIdx.x & ~63u); k0 < nroots; k0 += gridDim.x * 256) {
-        const int k = k0 + lane;
-        const bool in = k < nroots;
-        const int i = in ? roots[k] : 0;  // (one thread per ROOT; until round 6: one per pixel, asking label[i] == i)
-        if (in) cidmap[i] = -1;
-        const int na = in ? canch[i] : 0, sz = in ? csize[i] : 0;
-        const bool has = na > 0;
-        const unsigned long long hm = __ballot(has);
-        if (!hm) continue;
-        StagComp C;
-        C.root = i; C.size = sz; C.nanch = na; C.nrec = 0;
-        if (has) {
-            const int4 bx = cbox[i];
-            C.minr = bx.x; C.minc = bx.y; C.maxr = bx.z; C.maxc = bx.w;
-        }
-        int p2 = 1;
-        while (p2 < na) p2 <<= 1;
-        C.anch_cap = has ? p2 : 0;
-        C.pix_cap = has ? 2 * sz + 12 * na + 64 : 0;
-        C.stack_cap = has ? (sz + 2 * na + 64) + (sz / 4 + 64) : 0;  // pending branches + (in its tail) the chain lists of the extraction
-        C.chain_cap = has ? sz + 2 * na + 64 : 0;
-        C.out_cap = C.pix_cap;
-        C.seg_cap = has ? C.pix_cap / 8 + na + 8 : 0;
-        const int wmax = wave_max_i32(na);
-        const int s1 = wave_iscan(C.anch_cap), s2 = wave_iscan(C.pix_cap), s3 = wave_iscan(C.stack_cap), s4 = wave_iscan(C.chain_cap),
-                  s6 = wave_iscan(C.seg_cap);
-        int b0 = 0, b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0, b6 = 0;
-        if (lane == 63) {  // (the lane that holds the totals)
-            atomicMax(&cursors[9], wmax);
-            b0 = atomicAdd(&cursors[0], (int)__builtin_popcountll(hm));
-            b1 = atomicAdd(&cursors[1], s1);
-            b2 = atomicAdd(&cursors[2], s2);
-            b3 = atomicAdd(&cursors[3], s3);
-            b4 = atomicAdd(&cursors[4], s4);
-            b5 = atomicAdd(&cursors[5], s2);  // (out_cap = pix_cap)
-            b6 = atomicAdd(&cursors[6], s6);
-        }
-        b0 = __builtin_amdgcn_readlane(b0, 63); b1 = __builtin_amdgcn_readlane(b1, 63); b2 = __builtin_amdgcn_readlane(b2, 63);
-        b3 = __builtin_amdgcn_readlane(b3, 63); b4 = __builtin_amdgcn_readlane(b4, 63); b5 = __builtin_amdgcn_readlane(b5, 63);
-        b6 = __builtin_amdgcn_readlane(b6, 63);
-        if (!has) continue;
-        const int cid = b0 + (int)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
-        if (cid >= max_comps) {
-            atomicOr(&cursors[7], 1);
-            continue;
-        }
-        C.anch_base = b1 + s1 - C.anch_cap;
-        C.pix_base = b2 + s2 - C.pix_cap;
-        C.stack_base = b3 + s3 - C.stack_cap;
-        C.chain_base = b4 + s4 - C.chain_cap;
-        C.out_base = b5 + s2 - C.out_cap;
-        C.seg_base = b6 + s6 - C.seg_cap;
-        if (C.anch_base + C.anch_cap > caps[1] || C.pix_base + C.pix_cap > caps[2] || C.stack_base + C.stack_cap > caps[3] ||
-            C.chain_base + C.chain_cap > caps[4] || C.out_base + C.out_cap > caps[5] || C.seg_base + C.seg_cap > caps[6]) {
-            atomicOr(&cursors[7], 2);
-            C.nanch = 0;  // not processed; the call reports FID_E_CAPACITY
-        }
-        comps[cid] = C;
-        cidmap[i] = cid;
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_comp_alloc(const int *__restrict__ roots, const int *__restrict__ csize, const int *__restrict__ canch, const int4 *__restrict__ cbox, int *__restrict__ cursors, int max_comps, const int *caps, StagComp *__restrict__ comps, int *__restrict__ cidmap)
-{
-    k_stag_comp_alloc_impl(roots, csize, canch, cbox, cursors, max_comps, caps, comps, cidmap);
-}
 struct k_stag_comp_alloc_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const int *__restrict__ roots, const int *__restrict__ csize, const int *__restrict__ canch, const int4 *__restrict__ cbox, int *__restrict__ cursors, int max_comps, const int *caps, StagComp *__restrict__ comps, int *__restrict__ cidmap) const { k_stag_comp_alloc_impl(roots, csize, canch, cbox, cursors, max_comps, caps, comps, cidmap); }
+    __device__ __forceinline__ void operator()(const int *__restrict__ roots, const int *__restrict__ csize,
+                                               const int *__restrict__ canch, const int4 *__restrict__ cbox, int *__restrict__ cursors, int max_comps,
+                                               const int *caps, StagComp *__restrict__ comps, int *__restrict__ cidmap) const
+    {
+        const int nroots = cursors[13];
+        const int lane = threadIdx.x & 63;
+        // (round 6) a WAVE asks for the places of its 64 roots at once: one atomic per cursor and wave, the lanes' shares by prefix sums.
+        // A thread per root sent eight returning atomics of its own to the same seven words -- a frame's ~8 k roots queued up there:
+        // 19 us.  Which component gets which place was never defined (the atomics' order); every component still gets its own.
+        for (int k0 = blockIdx.x * 256 + (int)(threadIdx.x & ~63u); k0 < nroots; k0 += gridDim.x * 256) {
+            const int k = k0 + lane;
+            const bool in = k < nroots;
+            const int i = in ? roots[k] : 0;  // (one thread per ROOT; until round 6: one per pixel, asking label[i] == i)
+            if (in) cidmap[i] = -1;
+            const int na = in ? canch[i] : 0, sz = in ? csize[i] : 0;
+            const bool has = na > 0;
+            const unsigned long long hm = __ballot(has);
+            if (!hm) continue;
+            StagComp C;
+            C.root = i; C.size = sz; C.nanch = na; C.nrec = 0;
+            if (has) {
+                const int4 bx = cbox[i];
+                C.minr = bx.x; C.minc = bx.y; C.maxr = bx.z; C.maxc = bx.w;
+            }
+            int p2 = 1;
+            while (p2 < na) p2 <<= 1;
+            C.anch_cap = has ? p2 : 0;
+            C.pix_cap = has ? 2 * sz + 12 * na + 64 : 0;
+            C.stack_cap = has ? (sz + 2 * na + 64) + (sz / 4 + 64) : 0;  // pending branches + (in its tail) the chain lists of the extraction
+            C.chain_cap = has ? sz + 2 * na + 64 : 0;
+            C.out_cap = C.pix_cap;
+            C.seg_cap = has ? C.pix_cap / 8 + na + 8 : 0;
+            const int wmax = wave_max_i32(na);
+            const int s1 = wave_iscan(C.anch_cap), s2 = wave_iscan(C.pix_cap), s3 = wave_iscan(C.stack_cap), s4 = wave_iscan(C.chain_cap),
+                      s6 = wave_iscan(C.seg_cap);
+            int b0 = 0, b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0, b6 = 0;
+            if (lane == 63) {  // (the lane that holds the totals)
+                atomicMax(&cursors[9], wmax);
+                b0 = atomicAdd(&cursors[0], (int)__builtin_popcountll(hm));
+                b1 = atomicAdd(&cursors[1], s1);
+                b2 = atomicAdd(&cursors[2], s2);
+                b3 = atomicAdd(&cursors[3], s3);
+                b4 = atomicAdd(&cursors[4], s4);
+                b5 = atomicAdd(&cursors[5], s2);  // (out_cap = pix_cap)
+                b6 = atomicAdd(&cursors[6], s6);
+            }
+            b0 = __builtin_amdgcn_readlane(b0, 63); b1 = __builtin_amdgcn_readlane(b1, 63); b2 = __builtin_amdgcn_readlane(b2, 63);
+            b3 = __builtin_amdgcn_readlane(b3, 63); b4 = __builtin_amdgcn_readlane(b4, 63); b5 = __builtin_amdgcn_readlane(b5, 63);
+            b6 = __builtin_amdgcn_readlane(b6, 63);
+            if (!has) continue;
+            const int cid = b0 + (int)__builtin_popcountll(hm & ((1ull << lane) - 1ull));
+            if (cid >= max_comps) {
+                atomicOr(&cursors[7], 1);
+                continue;
+            }
+            C.anch_base = b1 + s1 - C.anch_cap;
+            C.pix_base = b2 + s2 - C.pix_cap;
+            C.stack_base = b3 + s3 - C.stack_cap;
+            C.chain_base = b4 + s4 - C.chain_cap;
+            C.out_base = b5 + s2 - C.out_cap;
+            C.seg_base = b6 + s6 - C.seg_cap;
+            if (C.anch_base + C.anch_cap > caps[1] || C.pix_base + C.pix_cap > caps[2] || C.stack_base + C.stack_cap > caps[3] ||
+                C.chain_base + C.chain_cap > caps[4] || C.out_base + C.out_cap > caps[5] || C.seg_base + C.seg_cap > caps[6]) {
+                atomicOr(&cursors[7], 2);
+                C.nanch = 0;  // not processed; the call reports FID_E_CAPACITY
+            }
+            comps[cid] = C;
+            cidmap[i] = cid;
+        }
+    }
 };
 
 // (64 consecutive ranks hold many anchors of the frame's big components: one atomic per (wave, component), the anchors of
 //  a group placed in rank order)
-__device__ __forceinline__ void k_stag_comp_fill_impl(const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors,
-                                                        const int *__restrict__ label, const int *__restrict__ cidmap, const StagComp *__restrict__ comps,
-                                                        int *__restrict__ fill, int *__restrict__ aslots)
-{
-    const int r = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
-    int cid = -1;
-    if (r < (int)*n_anchors) {
-        cid = cidmap[label[sorted[r]]];
-        if (cid >= 0 && comps[cid].nanch == 0) cid = -1;
-    }
-    // (round 6) first every lane learns its group -- the lane that leads it, its place in it, its size: ballots only -- then the
-    // leaders ask for their groups' places with ONE wave instruction.  Before, the atomic sat inside the loop and the wave waited
-    // for it once per component: 64 consecutive ranks of the gradient order belong to 30 - 60 components, 35 us for a single frame.
-    unsigned long long pending = __ballot(cid >= 0);
-    int lead = 0, rank = 0, cnt = 0;
-    while (pending) {
-        const int l0 = __builtin_ctzll(pending);
-        const int c0 = __builtin_amdgcn_readlane(cid, l0);
-        const unsigned long long m = __ballot(cid == c0);
-        if (cid == c0) {
-            lead = l0;
-            rank = (int)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-            cnt = (int)__builtin_popcountll(m);
-        }
-        pending &= ~m;
-    }
-    int base = 0;
-    if (cid >= 0 && lane == lead) base = atomicAdd(&fill[cid], cnt);
-    base = __shfl(base, lead, 64);
-    if (cid >= 0) aslots[comps[cid].anch_base + base + rank] = r;
-}
-__global__ __launch_bounds__(256) void k_stag_comp_fill(const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors, const int *__restrict__ label, const int *__restrict__ cidmap, const StagComp *__restrict__ comps, int *__restrict__ fill, int *__restrict__ aslots)
-{
-    k_stag_comp_fill_impl(sorted, n_anchors, label, cidmap, comps, fill, aslots);
-}
 struct k_stag_comp_fill_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors, const int *__restrict__ label, const int *__restrict__ cidmap, const StagComp *__restrict__ comps, int *__restrict__ fill, int *__restrict__ aslots) const { k_stag_comp_fill_impl(sorted, n_anchors, label, cidmap, comps, fill, aslots); }
+    __device__ __forceinline__ void operator()(const int32_t *__restrict__ sorted, const unsigned *__restrict__ n_anchors,
+                                               const int *__restrict__ label, const int *__restrict__ cidmap, const StagComp *__restrict__ comps,
+                                               int *__restrict__ fill, int *__restrict__ aslots) const
+    {
+        const int r = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+        int cid = -1;
+        if (r < (int)*n_anchors) {
+            cid = cidmap[label[sorted[r]]];
+            if (cid >= 0 && comps[cid].nanch == 0) cid = -1;
+        }
+        // (round 6) first every lane learns its group -- the lane that leads it, its place in it, its size: ballots only -- then the
+        // leaders ask for their groups' places with ONE wave instruction.  Before, the atomic sat inside the loop and the wave waited
+        // for it once per component: 64 consecutive ranks of the gradient order belong to 30 - 60 components, 35 us for a single frame.
+        unsigned long long pending = __ballot(cid >= 0);
+        int lead = 0, rank = 0, cnt = 0;
+        while (pending) {
+            const int l0 = __builtin_ctzll(pending);
+            const int c0 = __builtin_amdgcn_readlane(cid, l0);
+            const unsigned long long m = __ballot(cid == c0);
+            if (cid == c0) {
+                lead = l0;
+                rank = (int)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+                cnt = (int)__builtin_popcountll(m);
+            }
+            pending &= ~m;
+        }
+        int base = 0;
+        if (cid >= 0 && lane == lead) base = atomicAdd(&fill[cid], cnt);
+        base = __shfl(base, lead, 64);
+        if (cid >= 0) aslots[comps[cid].anch_base + base + rank] = r;
+    }
 };
 
 // cursors[10] = the largest LDS tile (bytes) a component would need (the boxes come from k_stag_ccl_flatten)
@@ -1181,28 +1141,23 @@ __device__ __forceinline__ int stag_comp_by_rank(const int *__restrict__ order, 
     const int nbig = cursors[11], ncomp = cursors[0];
     return rank < nbig ? order[rank] : order[ncomp - 1 - (rank - nbig)];  // (small ones: slot s of the back = order[ncomp - 1 - s])
 }
-__device__ __forceinline__ void k_stag_comp_tilemax_impl(const StagComp *__restrict__ comps, int *cursors, int lds_cap, int *__restrict__ order, int max_comps)
-{
-    const int cid = blockIdx.x * 256 + threadIdx.x;
-    // (k_stag_comp_alloc counts past max_comps when the table is full -- the overflow flag is up and the frame takes the sequential
-    //  road -- but `order` and `comps` end at max_comps)
-    const int ncomp = cursors[0] < max_comps ? cursors[0] : max_comps;
-    if (cid >= ncomp) return;
-    const StagComp C = comps[cid];
-    // (every component gets a place, the empty ones among the small: nbig + nsmall = ncomp, front and back never meet)
-    const int bytes = (C.maxr - C.minr + 3) * (C.maxc - C.minc + 3) * 2;
-    if (C.nanch > 0 && (C.size >= STAG_BIG_COMP || bytes > STAG_SMALL_TILE)) order[atomicAdd(&cursors[11], 1)] = cid;
-    else order[ncomp - 1 - atomicAdd(&cursors[12], 1)] = cid;
-    if (C.nanch == 0) return;
-    atomicMax(&cursors[10], bytes <= lds_cap ? bytes : lds_cap);  // (beyond the cap: the whole of it, for the component's blocks)
-}
-__global__ __launch_bounds__(256) void k_stag_comp_tilemax(const StagComp *__restrict__ comps, int *cursors, int lds_cap, int *__restrict__ order, int max_comps)
-{
-    k_stag_comp_tilemax_impl(comps, cursors, lds_cap, order, max_comps);
-}
 struct k_stag_comp_tilemax_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, int *cursors, int lds_cap, int *__restrict__ order, int max_comps) const { k_stag_comp_tilemax_impl(comps, cursors, lds_cap, order, max_comps); }
+    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, int *cursors, int lds_cap, int *__restrict__ order, int max_comps) const
+    {
+        const int cid = blockIdx.x * 256 + threadIdx.x;
+        // (k_stag_comp_alloc counts past max_comps when the table is full -- the overflow flag is up and the frame takes the sequential
+        //  road -- but `order` and `comps` end at max_comps)
+        const int ncomp = cursors[0] < max_comps ? cursors[0] : max_comps;
+        if (cid >= ncomp) return;
+        const StagComp C = comps[cid];
+        // (every component gets a place, the empty ones among the small: nbig + nsmall = ncomp, front and back never meet)
+        const int bytes = (C.maxr - C.minr + 3) * (C.maxc - C.minc + 3) * 2;
+        if (C.nanch > 0 && (C.size >= STAG_BIG_COMP || bytes > STAG_SMALL_TILE)) order[atomicAdd(&cursors[11], 1)] = cid;
+        else order[ncomp - 1 - atomicAdd(&cursors[12], 1)] = cid;
+        if (C.nanch == 0) return;
+        atomicMax(&cursors[10], bytes <= lds_cap ? bytes : lds_cap);  // (beyond the cap: the whole of it, for the component's blocks)
+    }
 };
 
 // ranks of one component, descending: bitonic sort of the (padded, -1 filled) slice, one wave per component; slices of up to
@@ -1210,100 +1165,90 @@ struct k_stag_comp_tilemax_fn {
 #define STAG_SORT_LDS 2048
 #define STAG_SORT_WAVE 256   // slices up to here: a wave each (k_stag_comp_sort); up to STAG_SORT_BIG: a workgroup of 1024 each
 #define STAG_SORT_BIG 16384
-__device__ __forceinline__ void k_stag_comp_sort_impl(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots)
-{
-    __shared__ int s_buf[4][STAG_SORT_LDS];
-    const int wv = threadIdx.x >> 6, cid = blockIdx.x * 4 + wv, lane = threadIdx.x & 63;
-    if (cid >= cursors[0]) return;
-    const StagComp C = comps[cid];
-    if (C.nanch < 2) return;
-    int *g = aslots + C.anch_base;
-    const int P = C.anch_cap;
-    if (P > STAG_SORT_WAVE && P <= STAG_SORT_BIG) return;  // k_stag_comp_sort_big's
-    const bool in_lds = P <= STAG_SORT_LDS;
-    int *a = in_lds ? s_buf[wv] : g;
-    if (in_lds) {
-        for (int i = lane; i < P; i += 64) a[i] = g[i];
-        __builtin_amdgcn_wave_barrier();
-    }
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = lane; i < P; i += 64) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const int x = a[i], y = a[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? x < y : x > y) {
-                        a[i] = y;
-                        a[l] = x;
-                    }
-                }
-            }
-            if (in_lds) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            } else {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            }
-        }
-    }
-    if (in_lds)
-        for (int i = lane; i < P; i += 64) g[i] = a[i];
-}
-__global__ __launch_bounds__(256) void k_stag_comp_sort(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots)
-{
-    k_stag_comp_sort_impl(comps, cursors, aslots);
-}
 struct k_stag_comp_sort_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots) const { k_stag_comp_sort_impl(comps, cursors, aslots); }
+    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots) const
+    {
+        __shared__ int s_buf[4][STAG_SORT_LDS];
+        const int wv = threadIdx.x >> 6, cid = blockIdx.x * 4 + wv, lane = threadIdx.x & 63;
+        if (cid >= cursors[0]) return;
+        const StagComp C = comps[cid];
+        if (C.nanch < 2) return;
+        int *g = aslots + C.anch_base;
+        const int P = C.anch_cap;
+        if (P > STAG_SORT_WAVE && P <= STAG_SORT_BIG) return;  // k_stag_comp_sort_big's
+        const bool in_lds = P <= STAG_SORT_LDS;
+        int *a = in_lds ? s_buf[wv] : g;
+        if (in_lds) {
+            for (int i = lane; i < P; i += 64) a[i] = g[i];
+            __builtin_amdgcn_wave_barrier();
+        }
+        for (int k = 2; k <= P; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = lane; i < P; i += 64) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const int x = a[i], y = a[l];
+                        const bool desc = (i & k) == 0;
+                        if (desc ? x < y : x > y) {
+                            a[i] = y;
+                            a[l] = x;
+                        }
+                    }
+                }
+                if (in_lds) {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                } else {
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                }
+            }
+        }
+        if (in_lds)
+            for (int i = lane; i < P; i += 64) g[i] = a[i];
+    }
 };
 
 // the same for the slices of 257 .. 16384 entries (a frame's larger components): one workgroup of 1024 per component, the
 // slice in up to 64 KB of LDS (one wave took 118 us for a slice of 2048: 66 passes of 32 rounds each)
-__device__ __forceinline__ void k_stag_comp_sort_big_impl(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots)
-{
-    extern __shared__ int s_big[];
-    // (a workgroup goes through the components blockIdx.x, + gridDim.x, ...: a frame has a few dozen slices of this size among
-    //  its components, and a 1 024-thread workgroup with 64 KB of LDS per COMPONENT -- most of them returning at once -- waited for
-    //  16 free wave slots on one CU each: 112 us alone, 680 us beside the other groups' kernels)
-    const int ncomp = cursors[0];
-    for (int cid = blockIdx.x; cid < ncomp; cid += gridDim.x) {
-    const StagComp C = comps[cid];
-    const int P = C.anch_cap;
-    if (C.nanch < 2 || P <= STAG_SORT_WAVE || P > STAG_SORT_BIG) continue;
-    __syncthreads();  // (the slice of the component before this one has left the LDS)
-    int *g = aslots + C.anch_base;
-    for (int i = threadIdx.x; i < P; i += (int)blockDim.x) s_big[i] = g[i];
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += (int)blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const int x = s_big[i], y = s_big[l];
-                    const bool desc = (i & k) == 0;
-                    if (desc ? x < y : x > y) {
-                        s_big[i] = y;
-                        s_big[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = threadIdx.x; i < P; i += (int)blockDim.x) g[i] = s_big[i];
-    }
-}
-__global__ __launch_bounds__(1024) void k_stag_comp_sort_big(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots)
-{
-    k_stag_comp_sort_big_impl(comps, cursors, aslots);
-}
 struct k_stag_comp_sort_big_fn {
     static constexpr int kBounds = 1024;
-    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots) const { k_stag_comp_sort_big_impl(comps, cursors, aslots); }
+    __device__ __forceinline__ void operator()(const StagComp *__restrict__ comps, const int *__restrict__ cursors, int *aslots) const
+    {
+        extern __shared__ int s_big[];
+        // (a workgroup goes through the components blockIdx.x, + gridDim.x, ...: a frame has a few dozen slices of this size among
+        //  its components, and a 1 024-thread workgroup with 64 KB of LDS per COMPONENT -- most of them returning at once -- waited for
+        //  16 free wave slots on one CU each: 112 us alone, 680 us beside the other groups' kernels)
+        const int ncomp = cursors[0];
+        for (int cid = blockIdx.x; cid < ncomp; cid += gridDim.x) {
+        const StagComp C = comps[cid];
+        const int P = C.anch_cap;
+        if (C.nanch < 2 || P <= STAG_SORT_WAVE || P > STAG_SORT_BIG) continue;
+        __syncthreads();  // (the slice of the component before this one has left the LDS)
+        int *g = aslots + C.anch_base;
+        for (int i = threadIdx.x; i < P; i += (int)blockDim.x) s_big[i] = g[i];
+        __syncthreads();
+        for (int k = 2; k <= P; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = threadIdx.x; i < P; i += (int)blockDim.x) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const int x = s_big[i], y = s_big[l];
+                        const bool desc = (i & k) == 0;
+                        if (desc ? x < y : x > y) {
+                            s_big[i] = y;
+                            s_big[l] = x;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        for (int i = threadIdx.x; i < P; i += (int)blockDim.x) g[i] = s_big[i];
+        }
+    }
 };
 
 struct StagArenas {
@@ -1339,342 +1284,332 @@ __device__ void stag_bind(StagRouter &S, const StagRoute &G, const StagArenas &A
     S.par = true;
 }
 
-template <bool FM = false>
-__device__ __forceinline__ void k_stag_route_walk_impl(StagRoute G, StagArenas A, StagComp *__restrict__ comps, const int *__restrict__ cursors,
-                                                        const int *__restrict__ order, const int32_t *__restrict__ sorted, const int *__restrict__ aslots,
-                                                        const int *__restrict__ label,
-                                                        int grad_thresh, int lds_bytes, int *__restrict__ prodflag, int *__restrict__ ovf, int cls)
-{
-    extern __shared__ uint16_t s_tile[];
-    constexpr int WSTACK = 128;  // (deeper than that: the arena in global memory)
-    __shared__ int4 s_wstack[WSTACK];  // the first entries of the walk's stack (StagRouter::MemWave)
-    // one workgroup per component: four waves move the tile in and out, wave 0 walks
-    // (longest first: k_stag_comp_tilemax's order list -- big components from the front, small ones from the back of `order`)
-    // cls 0: every component; 1: the big ones only (ranks below cursors[11]); 2: the small ones only -- a group of frames launches the
-    // two classes one after the other: the big ones with the large tile, all of them resident at once, the small ones with
-    // STAG_SMALL_TILE of LDS, so that the hundreds of short walks are not queueing for the one slot per CU the long walks leave free
-    const int lane = threadIdx.x & 63, tid = threadIdx.x;
-    const int rank = (int)STAG_BX<FM>() + (cls == 2 ? cursors[11] : 0);
-    if (rank >= (cls == 1 ? cursors[11] : cursors[0])) return;
-    const int cid = stag_comp_by_rank(order, cursors, rank);
-    const StagComp C = sr_uni_struct(comps[cid]);
-    if (C.nanch == 0) return;
-    StagRouter S;
-    stag_bind(S, G, A, C);
-    S.noSegments = S.totalPixels = S.overflow = 0;
-    S.segbase = S.nsp = 0;
-    StagRec *recs = A.recs + C.anch_base;
-    int nrec = 0, pix_used = 0, chain_used = 0;
-    int2 *pix0 = S.R.pix;
-    StagChain *chain0 = S.R.chains;
-    const int capPix0 = S.R.capPix, capChain0 = C.chain_cap;
-    const int W = G.W;
-    // the component's bounding box (+1 all around) as an LDS tile, if it fits
-    StagRouter::Tile T;
-    T.t = s_tile;
-    T.r0 = C.minr - 1;
-    T.c0 = C.minc - 1;
-    T.tw = C.maxc - C.minc + 3;
-    T.gstk = S.R.stack; T.lstk.p = (SrLdsInt)(int *)s_wstack; T.lcap = WSTACK;
-    const int th = C.maxr - C.minr + 3;
-    const int lds_real = lds_bytes & ~3;  // (bit 0: an experiment switch)
-    const bool tiled = T.tw * th * 2 <= lds_real;
-#ifdef RW_TIMING
-    const unsigned long long rw_tl = __builtin_readcyclecounter();
-#endif
-    // ... or as 4 x 4 blocks (StagRouter::SparseTile), if those fit
-    __shared__ int s_nblk;
-    StagRouter::SparseTile P;
-    bool sparse = false;
-    if (!tiled && !(lds_bytes & 1)) {  // (bit 0 of lds_bytes: no blocks -- FID_STAG_SPARSE=0, an experiment switch)
-        constexpr int SH = StagRouter::SparseTile::SH, BM = StagRouter::SparseTile::BM, BW = 1 << (2 * SH);  // (words per block)
-        const int bw = (T.tw + BM) >> SH, bh = (th + BM) >> SH, ntab = (bw * bh + 63) & ~63;
-        const int maxblk = (lds_real / 2 - ntab) / BW - 1;  // (block 0 is the empty one)
-        P.tab = s_tile; P.blk = s_tile + ntab; P.r0 = T.r0; P.c0 = T.c0; P.bw = bw;
-        P.gstk = S.R.stack; P.lstk.p = (SrLdsInt)(int *)s_wstack; P.lcap = WSTACK;
-        if (maxblk >= 16 && maxblk < 65535) {  // (uniform over the workgroup: the barriers below are safe)
-            for (int i = tid; i < ntab; i += 256) s_tile[i] = 0;
-            if (tid < BW) P.blk[tid] = 0;
-            if (tid == 0) s_nblk = 0;
-            __syncthreads();
-            // the blocks within one pixel of a pixel of the component (a wave per row, its lanes along the row; the box's own
-            // border ring holds no pixel of the component)
-            for (int r4 = 1 + (tid >> 6) * 16; r4 < th - 1; r4 += 64)
-                for (int cc = 1 + lane; cc < T.tw - 1; cc += 64) {
-                    int lb[16];
-#pragma unroll
-                    for (int u = 0; u < 16; u++)  // (sixteen rows in flight per thread: the pass is a chain of memory round trips)
-                        if (r4 + u < th - 1) lb[u] = label[(T.r0 + r4 + u) * W + T.c0 + cc];
-#pragma unroll
-                    for (int u = 0; u < 16; u++)
-                        if (r4 + u < th - 1 && lb[u] == C.root) {
-                            const int rr = r4 + u;
-                            const int b0 = ((rr - 1) >> SH) * bw, b1 = ((rr + 1) >> SH) * bw, q0 = (cc - 1) >> SH, q1 = (cc + 1) >> SH;
-                            s_tile[b0 + q0] = 0xffff; s_tile[b0 + q1] = 0xffff; s_tile[b1 + q0] = 0xffff; s_tile[b1 + q1] = 0xffff;
-                        }
-                }
-            __syncthreads();
-            for (int i = tid; i < bw * bh; i += 256)
-                if (s_tile[i] == 0xffff) {
-                    const int slot = atomicAdd(&s_nblk, 1) + 1;
-                    s_tile[i] = (uint16_t)(slot <= maxblk ? slot : 0);
-                }
-            __syncthreads();
-            sparse = s_nblk <= maxblk;
-            if (sparse) {
-                for (int r4 = (tid >> 6) * 8; r4 < th; r4 += 32)
-                    for (int cc = lane; cc < T.tw; cc += 64) {
-                        int slot[8], e[8], gr[8], dr[8];
-#pragma unroll
-                        for (int u = 0; u < 8; u++) {
-                            slot[u] = r4 + u < th ? s_tile[((r4 + u) >> SH) * bw + (cc >> SH)] : 0;
-                            if (slot[u]) {
-                                const int g = (T.r0 + r4 + u) * W + T.c0 + cc;
-                                e[u] = G.edge[g]; gr[u] = G.grad[g]; dr[u] = G.dir[g];
-                            }
-                        }
-#pragma unroll
-                        for (int u = 0; u < 8; u++)
-                            if (slot[u]) {
-                                const int st = e[u] == STAG_EDGE_PIXEL ? 2 : e[u] == STAG_ANCHOR_PIXEL ? 1 : 0;
-                                P.blk[(slot[u] << (2 * SH)) | (((r4 + u) & BM) << SH) | (cc & BM)] =
-                                    (uint16_t)((gr[u] & 0x7ff) | (dr[u] == STAG_EDGE_VERTICAL ? 0x800 : 0) | (st << 12));
-                            }
-                    }
-            }
-            __syncthreads();
-        }
-    }
-    if (tiled) {
-        // a wave per row, its lanes along the row (no division per pixel), four rows in flight per thread
-        for (int r4 = (tid >> 6) * 4; r4 < th; r4 += 16)
-            for (int cc = lane; cc < T.tw; cc += 64) {
-                int e[4], gr[4], dr[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (r4 + u < th) {
-                        const int g = (T.r0 + r4 + u) * W + T.c0 + cc;
-                        e[u] = G.edge[g]; gr[u] = G.grad[g]; dr[u] = G.dir[g];
-                    }
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (r4 + u < th) {
-                        const int st = e[u] == STAG_EDGE_PIXEL ? 2 : e[u] == STAG_ANCHOR_PIXEL ? 1 : 0;
-                        s_tile[(r4 + u) * T.tw + cc] = (uint16_t)((gr[u] & 0x7ff) | (dr[u] == STAG_EDGE_VERTICAL ? 0x800 : 0) | (st << 12));
-                    }
-            }
-        __syncthreads();
-    }
-#ifdef RW_TIMING
-    const unsigned long long rw_t0 = __builtin_readcyclecounter();
-    const unsigned long long rw_load = rw_t0 - rw_tl;
-    unsigned long long rw_walk = 0;
-    int rw_walks = 0, rw_live = 0, rw_pix = 0, rw_chains = 0;
-#endif
-    // (which wave of the workgroup walks makes no difference: rotating it over the four, so that the walkers of the workgroups that
-    //  share a CU in a group of frames sit on different SIMDs, left the group's kernel where it was -- measured, round 5)
-    if (tid < 64) {
-    for (int k0 = 0; k0 < C.nanch; k0 += 64) {
-        // which of the next 64 anchors are still anchors?  (a walk can only turn anchors OFF, so a stale "on" is re-checked)
-        const int kk = k0 + lane;
-        int my_off = -1, my_rank = -1;
-        if (kk < C.nanch) {
-            my_rank = aslots[C.anch_base + kk];
-            my_off = sorted[my_rank];
-        }
-        bool on = false;
-        if (my_off >= 0) {
-            const int orr = my_off / W, occ = my_off - orr * W;
-            on = tiled    ? StagRouter::Tile::edge_of(s_tile[T.idx(orr, occ)]) == STAG_ANCHOR_PIXEL
-                 : sparse ? (P.blk[P.off(orr - P.r0, occ - P.c0)] >> 12) == 1
-                          : G.edge[my_off] == STAG_ANCHOR_PIXEL;
-        }
-        unsigned long long live = __ballot(on);
-        while (live) {
-            const int j = __builtin_ctzll(live);
-            live &= live - 1;
-            const int rank = __builtin_amdgcn_readlane(my_rank, j), off = __builtin_amdgcn_readlane(my_off, j);  // (no second trip to memory)
-            const int ar = off / W, ac = off - ar * W;
-            const bool still = tiled    ? StagRouter::Tile::edge_of((uint16_t)sr_uni(s_tile[T.idx(ar, ac)])) == STAG_ANCHOR_PIXEL
-                               : sparse ? (P.word_at(ar, ac) >> 12) == 1
-                                        : sr_uni(G.edge[off]) == STAG_ANCHOR_PIXEL;
-#ifdef RW_TIMING
-            rw_live++;
-#endif
-            if (!still) continue;
-            S.R.pix = pix0 + pix_used;
-            S.R.capPix = capPix0 - pix_used;
-            S.R.chains = chain0 + chain_used;
-            const int left = capChain0 - chain_used;
-            S.R.capChains = left < 32767 ? left : 32767;
-            if (S.R.capPix < 16 || S.R.capChains < 4) {
-                S.overflow |= 32;
-                break;
-            }
-#ifdef RW_TIMING
-            const unsigned long long rw_a = __builtin_readcyclecounter();
-#endif
-            const bool keep = tiled    ? S.walk_anchor_tile6(ar, ac, grad_thresh, lane, T)
-                              : sparse ? S.walk_anchor_tile6(ar, ac, grad_thresh, lane, P)
-                                       : S.walk_anchor_wave(ar, ac, grad_thresh, lane, SrLdsInt4{(SrLdsInt)(int *)s_wstack}, WSTACK);
-#ifdef RW_TIMING
-            rw_walk += __builtin_readcyclecounter() - rw_a;
-            rw_walks++;
-            rw_pix += S.wl_len;
-            rw_chains += S.wl_chains;
-#endif
-            if (S.overflow) break;
-            if (keep) {
-                if (lane == 0) {
-                    StagRec r;
-                    r.rank = rank; r.pix_off = pix_used; r.len = S.wl_len; r.chain_off = chain_used; r.nchains = S.wl_chains;
-                    r.out_off = r.out_len = r.seg_off = r.nsegs = 0;
-                    recs[nrec] = r;
-                    prodflag[rank] = 1;
-                }
-                nrec++;
-                pix_used += S.wl_len + 1;
-                chain_used += S.wl_chains;
-            }
-        }
-        if (S.overflow) break;
-    }
-    if (lane == 0) {
-        comps[cid].nrec = nrec;
-        if (S.overflow) atomicOr(ovf, S.overflow);
-    }
-#ifdef RW_TIMING
-    if (lane == 0 && C.nanch > 200)
-        printf("walk comp %d: size %d anchors %d tile %dx%d tiled %d | load %llu cycles, anchor loop %llu (walks %llu in %d walks of %d live, %d pixels, %d chains, %d kept)\n", cid, C.size, C.nanch,
-               T.tw, th, (int)tiled + 2 * (int)sparse, rw_load, (unsigned long long)(__builtin_readcyclecounter() - rw_t0), rw_walk, rw_walks, rw_live, rw_pix, rw_chains, nrec);
-#endif
-    }  // wave 0
-    if (tiled) {  // the component's own pixels back into the edge image
-        __syncthreads();
-        for (int r4 = 1 + (tid >> 6) * 4; r4 < th - 1; r4 += 16)
-            for (int cc = 1 + lane; cc < T.tw - 1; cc += 64) {
-                int lb[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (r4 + u < th - 1) lb[u] = label[(T.r0 + r4 + u) * W + T.c0 + cc];
-#pragma unroll
-                for (int u = 0; u < 4; u++)
-                    if (r4 + u < th - 1 && lb[u] == C.root)
-                        G.edge[(T.r0 + r4 + u) * W + T.c0 + cc] = (uint8_t)StagRouter::Tile::edge_of(s_tile[(r4 + u) * T.tw + cc]);
-            }
-    } else if (sparse) {
-        __syncthreads();
-        // block by block (not the box again: its label image is 4 bytes a pixel): a wave per block, sixteen lanes its pixels
-        constexpr int SH = StagRouter::SparseTile::SH, BW = 1 << (2 * SH);
-        const int nb = P.bw * ((th + StagRouter::SparseTile::BM) >> SH);
-        for (int b0 = (tid >> 6) * 64; b0 < nb; b0 += 256) {  // 64 table entries per wave and round, the blocks among them one by one
-            const int myslot = b0 + lane < nb ? P.tab[b0 + lane] : 0;
-            unsigned long long have = __ballot(myslot != 0);
-            while (have) {
-                const int j = __builtin_ctzll(have);
-                have &= have - 1;
-                const int slot = __builtin_amdgcn_readlane(myslot, j), b = b0 + j;
-                const int brow = b / P.bw, bcol = b - brow * P.bw;
-                const int rr = (brow << SH) + (lane >> SH), cc = (bcol << SH) + (lane & ((1 << SH) - 1));
-                if (lane < BW && rr >= 1 && rr < th - 1 && cc >= 1 && cc < T.tw - 1) {
-                    const int g = (T.r0 + rr) * W + T.c0 + cc;
-                    if (label[g] == C.root) G.edge[g] = (uint8_t)StagRouter::Tile::edge_of(P.blk[(slot << (2 * SH)) + lane]);
-                }
-            }
-        }
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_route_walk(StagRoute G, StagArenas A, StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int32_t *__restrict__ sorted, const int *__restrict__ aslots, const int *__restrict__ label, int grad_thresh, int lds_bytes, int *__restrict__ prodflag, int *__restrict__ ovf, int cls)
-{
-    k_stag_route_walk_impl(G, A, comps, cursors, order, sorted, aslots, label, grad_thresh, lds_bytes, prodflag, ovf, cls);
-}
+template <bool FM>
 struct k_stag_route_walk_fn {
     static constexpr int kBounds = 256;
-    static constexpr bool kFrameMinor = true;
-    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int32_t *__restrict__ sorted, const int *__restrict__ aslots, const int *__restrict__ label, int grad_thresh, int lds_bytes, int *__restrict__ prodflag, int *__restrict__ ovf, int cls) const { k_stag_route_walk_impl<true>(G, A, comps, cursors, order, sorted, aslots, label, grad_thresh, lds_bytes, prodflag, ovf, cls); }
+    static constexpr bool kFrameMinor = FM;
+    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, StagComp *__restrict__ comps, const int *__restrict__ cursors,
+                                               const int *__restrict__ order, const int32_t *__restrict__ sorted, const int *__restrict__ aslots,
+                                               const int *__restrict__ label,
+                                               int grad_thresh, int lds_bytes, int *__restrict__ prodflag, int *__restrict__ ovf, int cls) const
+    {
+        extern __shared__ uint16_t s_tile[];
+        constexpr int WSTACK = 128;  // (deeper than that: the arena in global memory)
+        __shared__ int4 s_wstack[WSTACK];  // the first entries of the walk's stack (StagRouter::MemWave)
+        // one workgroup per component: four waves move the tile in and out, wave 0 walks
+        // (longest first: k_stag_comp_tilemax's order list -- big components from the front, small ones from the back of `order`)
+        // cls 0: every component; 1: the big ones only (ranks below cursors[11]); 2: the small ones only -- a group of frames launches the
+        // two classes one after the other: the big ones with the large tile, all of them resident at once, the small ones with
+        // STAG_SMALL_TILE of LDS, so that the hundreds of short walks are not queueing for the one slot per CU the long walks leave free
+        const int lane = threadIdx.x & 63, tid = threadIdx.x;
+        const int rank = (int)STAG_BX<FM>() + (cls == 2 ? cursors[11] : 0);
+        if (rank >= (cls == 1 ? cursors[11] : cursors[0])) return;
+        const int cid = stag_comp_by_rank(order, cursors, rank);
+        const StagComp C = sr_uni_struct(comps[cid]);
+        if (C.nanch == 0) return;
+        StagRouter S;
+        stag_bind(S, G, A, C);
+        S.noSegments = S.totalPixels = S.overflow = 0;
+        S.segbase = S.nsp = 0;
+        StagRec *recs = A.recs + C.anch_base;
+        int nrec = 0, pix_used = 0, chain_used = 0;
+        int2 *pix0 = S.R.pix;
+        StagChain *chain0 = S.R.chains;
+        const int capPix0 = S.R.capPix, capChain0 = C.chain_cap;
+        const int W = G.W;
+        // the component's bounding box (+1 all around) as an LDS tile, if it fits
+        StagRouter::Tile T;
+        T.t = s_tile;
+        T.r0 = C.minr - 1;
+        T.c0 = C.minc - 1;
+        T.tw = C.maxc - C.minc + 3;
+        T.gstk = S.R.stack; T.lstk.p = (SrLdsInt)(int *)s_wstack; T.lcap = WSTACK;
+        const int th = C.maxr - C.minr + 3;
+        const int lds_real = lds_bytes & ~3;  // (bit 0: an experiment switch)
+        const bool tiled = T.tw * th * 2 <= lds_real;
+#ifdef RW_TIMING
+        const unsigned long long rw_tl = __builtin_readcyclecounter();
+#endif
+        // ... or as 4 x 4 blocks (StagRouter::SparseTile), if those fit
+        __shared__ int s_nblk;
+        StagRouter::SparseTile P;
+        bool sparse = false;
+        if (!tiled && !(lds_bytes & 1)) {  // (bit 0 of lds_bytes: no blocks -- FID_STAG_SPARSE=0, an experiment switch)
+            constexpr int SH = StagRouter::SparseTile::SH, BM = StagRouter::SparseTile::BM, BW = 1 << (2 * SH);  // (words per block)
+            const int bw = (T.tw + BM) >> SH, bh = (th + BM) >> SH, ntab = (bw * bh + 63) & ~63;
+            const int maxblk = (lds_real / 2 - ntab) / BW - 1;  // (block 0 is the empty one)
+            P.tab = s_tile; P.blk = s_tile + ntab; P.r0 = T.r0; P.c0 = T.c0; P.bw = bw;
+            P.gstk = S.R.stack; P.lstk.p = (SrLdsInt)(int *)s_wstack; P.lcap = WSTACK;
+            if (maxblk >= 16 && maxblk < 65535) {  // (uniform over the workgroup: the barriers below are safe)
+                for (int i = tid; i < ntab; i += 256) s_tile[i] = 0;
+                if (tid < BW) P.blk[tid] = 0;
+                if (tid == 0) s_nblk = 0;
+                __syncthreads();
+                // the blocks within one pixel of a pixel of the component (a wave per row, its lanes along the row; the box's own
+                // border ring holds no pixel of the component)
+                for (int r4 = 1 + (tid >> 6) * 16; r4 < th - 1; r4 += 64)
+                    for (int cc = 1 + lane; cc < T.tw - 1; cc += 64) {
+                        int lb[16];
+#pragma unroll
+                        for (int u = 0; u < 16; u++)  // (sixteen rows in flight per thread: the pass is a chain of memory round trips)
+                            if (r4 + u < th - 1) lb[u] = label[(T.r0 + r4 + u) * W + T.c0 + cc];
+#pragma unroll
+                        for (int u = 0; u < 16; u++)
+                            if (r4 + u < th - 1 && lb[u] == C.root) {
+                                const int rr = r4 + u;
+                                const int b0 = ((rr - 1) >> SH) * bw, b1 = ((rr + 1) >> SH) * bw, q0 = (cc - 1) >> SH, q1 = (cc + 1) >> SH;
+                                s_tile[b0 + q0] = 0xffff; s_tile[b0 + q1] = 0xffff; s_tile[b1 + q0] = 0xffff; s_tile[b1 + q1] = 0xffff;
+                            }
+                    }
+                __syncthreads();
+                for (int i = tid; i < bw * bh; i += 256)
+                    if (s_tile[i] == 0xffff) {
+                        const int slot = atomicAdd(&s_nblk, 1) + 1;
+                        s_tile[i] = (uint16_t)(slot <= maxblk ? slot : 0);
+                    }
+                __syncthreads();
+                sparse = s_nblk <= maxblk;
+                if (sparse) {
+                    for (int r4 = (tid >> 6) * 8; r4 < th; r4 += 32)
+                        for (int cc = lane; cc < T.tw; cc += 64) {
+                            int slot[8], e[8], gr[8], dr[8];
+#pragma unroll
+                            for (int u = 0; u < 8; u++) {
+                                slot[u] = r4 + u < th ? s_tile[((r4 + u) >> SH) * bw + (cc >> SH)] : 0;
+                                if (slot[u]) {
+                                    const int g = (T.r0 + r4 + u) * W + T.c0 + cc;
+                                    e[u] = G.edge[g]; gr[u] = G.grad[g]; dr[u] = G.dir[g];
+                                }
+                            }
+#pragma unroll
+                            for (int u = 0; u < 8; u++)
+                                if (slot[u]) {
+                                    const int st = e[u] == STAG_EDGE_PIXEL ? 2 : e[u] == STAG_ANCHOR_PIXEL ? 1 : 0;
+                                    P.blk[(slot[u] << (2 * SH)) | (((r4 + u) & BM) << SH) | (cc & BM)] =
+                                        (uint16_t)((gr[u] & 0x7ff) | (dr[u] == STAG_EDGE_VERTICAL ? 0x800 : 0) | (st << 12));
+                                }
+                        }
+                }
+                __syncthreads();
+            }
+        }
+        if (tiled) {
+            // a wave per row, its lanes along the row (no division per pixel), four rows in flight per thread
+            for (int r4 = (tid >> 6) * 4; r4 < th; r4 += 16)
+                for (int cc = lane; cc < T.tw; cc += 64) {
+                    int e[4], gr[4], dr[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (r4 + u < th) {
+                            const int g = (T.r0 + r4 + u) * W + T.c0 + cc;
+                            e[u] = G.edge[g]; gr[u] = G.grad[g]; dr[u] = G.dir[g];
+                        }
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (r4 + u < th) {
+                            const int st = e[u] == STAG_EDGE_PIXEL ? 2 : e[u] == STAG_ANCHOR_PIXEL ? 1 : 0;
+                            s_tile[(r4 + u) * T.tw + cc] = (uint16_t)((gr[u] & 0x7ff) | (dr[u] == STAG_EDGE_VERTICAL ? 0x800 : 0) | (st << 12));
+                        }
+                }
+            __syncthreads();
+        }
+#ifdef RW_TIMING
+        const unsigned long long rw_t0 = __builtin_readcyclecounter();
+        const unsigned long long rw_load = rw_t0 - rw_tl;
+        unsigned long long rw_walk = 0;
+        int rw_walks = 0, rw_live = 0, rw_pix = 0, rw_chains = 0;
+#endif
+        // (which wave of the workgroup walks makes no difference: rotating it over the four, so that the walkers of the workgroups that
+        //  share a CU in a group of frames sit on different SIMDs, left the group's kernel where it was -- measured, round 5)
+        if (tid < 64) {
+        for (int k0 = 0; k0 < C.nanch; k0 += 64) {
+            // which of the next 64 anchors are still anchors?  (a walk can only turn anchors OFF, so a stale "on" is re-checked)
+            const int kk = k0 + lane;
+            int my_off = -1, my_rank = -1;
+            if (kk < C.nanch) {
+                my_rank = aslots[C.anch_base + kk];
+                my_off = sorted[my_rank];
+            }
+            bool on = false;
+            if (my_off >= 0) {
+                const int orr = my_off / W, occ = my_off - orr * W;
+                on = tiled    ? StagRouter::Tile::edge_of(s_tile[T.idx(orr, occ)]) == STAG_ANCHOR_PIXEL
+                     : sparse ? (P.blk[P.off(orr - P.r0, occ - P.c0)] >> 12) == 1
+                              : G.edge[my_off] == STAG_ANCHOR_PIXEL;
+            }
+            unsigned long long live = __ballot(on);
+            while (live) {
+                const int j = __builtin_ctzll(live);
+                live &= live - 1;
+                const int rank = __builtin_amdgcn_readlane(my_rank, j), off = __builtin_amdgcn_readlane(my_off, j);  // (no second trip to memory)
+                const int ar = off / W, ac = off - ar * W;
+                const bool still = tiled    ? StagRouter::Tile::edge_of((uint16_t)sr_uni(s_tile[T.idx(ar, ac)])) == STAG_ANCHOR_PIXEL
+                                   : sparse ? (P.word_at(ar, ac) >> 12) == 1
+                                            : sr_uni(G.edge[off]) == STAG_ANCHOR_PIXEL;
+#ifdef RW_TIMING
+                rw_live++;
+#endif
+                if (!still) continue;
+                S.R.pix = pix0 + pix_used;
+                S.R.capPix = capPix0 - pix_used;
+                S.R.chains = chain0 + chain_used;
+                const int left = capChain0 - chain_used;
+                S.R.capChains = left < 32767 ? left : 32767;
+                if (S.R.capPix < 16 || S.R.capChains < 4) {
+                    S.overflow |= 32;
+                    break;
+                }
+#ifdef RW_TIMING
+                const unsigned long long rw_a = __builtin_readcyclecounter();
+#endif
+                const bool keep = tiled    ? S.walk_anchor_tile6(ar, ac, grad_thresh, lane, T)
+                                  : sparse ? S.walk_anchor_tile6(ar, ac, grad_thresh, lane, P)
+                                           : S.walk_anchor_wave(ar, ac, grad_thresh, lane, SrLdsInt4{(SrLdsInt)(int *)s_wstack}, WSTACK);
+#ifdef RW_TIMING
+                rw_walk += __builtin_readcyclecounter() - rw_a;
+                rw_walks++;
+                rw_pix += S.wl_len;
+                rw_chains += S.wl_chains;
+#endif
+                if (S.overflow) break;
+                if (keep) {
+                    if (lane == 0) {
+                        StagRec r;
+                        r.rank = rank; r.pix_off = pix_used; r.len = S.wl_len; r.chain_off = chain_used; r.nchains = S.wl_chains;
+                        r.out_off = r.out_len = r.seg_off = r.nsegs = 0;
+                        recs[nrec] = r;
+                        prodflag[rank] = 1;
+                    }
+                    nrec++;
+                    pix_used += S.wl_len + 1;
+                    chain_used += S.wl_chains;
+                }
+            }
+            if (S.overflow) break;
+        }
+        if (lane == 0) {
+            comps[cid].nrec = nrec;
+            if (S.overflow) atomicOr(ovf, S.overflow);
+        }
+#ifdef RW_TIMING
+        if (lane == 0 && C.nanch > 200)
+            printf("walk comp %d: size %d anchors %d tile %dx%d tiled %d | load %llu cycles, anchor loop %llu (walks %llu in %d walks of %d live, %d pixels, %d chains, %d kept)\n", cid, C.size, C.nanch,
+                   T.tw, th, (int)tiled + 2 * (int)sparse, rw_load, (unsigned long long)(__builtin_readcyclecounter() - rw_t0), rw_walk, rw_walks, rw_live, rw_pix, rw_chains, nrec);
+#endif
+        }  // wave 0
+        if (tiled) {  // the component's own pixels back into the edge image
+            __syncthreads();
+            for (int r4 = 1 + (tid >> 6) * 4; r4 < th - 1; r4 += 16)
+                for (int cc = 1 + lane; cc < T.tw - 1; cc += 64) {
+                    int lb[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (r4 + u < th - 1) lb[u] = label[(T.r0 + r4 + u) * W + T.c0 + cc];
+#pragma unroll
+                    for (int u = 0; u < 4; u++)
+                        if (r4 + u < th - 1 && lb[u] == C.root)
+                            G.edge[(T.r0 + r4 + u) * W + T.c0 + cc] = (uint8_t)StagRouter::Tile::edge_of(s_tile[(r4 + u) * T.tw + cc]);
+                }
+        } else if (sparse) {
+            __syncthreads();
+            // block by block (not the box again: its label image is 4 bytes a pixel): a wave per block, sixteen lanes its pixels
+            constexpr int SH = StagRouter::SparseTile::SH, BW = 1 << (2 * SH);
+            const int nb = P.bw * ((th + StagRouter::SparseTile::BM) >> SH);
+            for (int b0 = (tid >> 6) * 64; b0 < nb; b0 += 256) {  // 64 table entries per wave and round, the blocks among them one by one
+                const int myslot = b0 + lane < nb ? P.tab[b0 + lane] : 0;
+                unsigned long long have = __ballot(myslot != 0);
+                while (have) {
+                    const int j = __builtin_ctzll(have);
+                    have &= have - 1;
+                    const int slot = __builtin_amdgcn_readlane(myslot, j), b = b0 + j;
+                    const int brow = b / P.bw, bcol = b - brow * P.bw;
+                    const int rr = (brow << SH) + (lane >> SH), cc = (bcol << SH) + (lane & ((1 << SH) - 1));
+                    if (lane < BW && rr >= 1 && rr < th - 1 && cc >= 1 && cc < T.tw - 1) {
+                        const int g = (T.r0 + rr) * W + T.c0 + cc;
+                        if (label[g] == C.root) G.edge[g] = (uint8_t)StagRouter::Tile::edge_of(P.blk[(slot << (2 * SH)) + lane]);
+                    }
+                }
+            }
+        }
+    }
 };
 
 // next[r] = the smallest producing rank > r, or -1 (one workgroup, chunks of 1024 from the top)
-__device__ __forceinline__ void k_stag_next_above_impl(const int *__restrict__ prodflag, const unsigned *__restrict__ n_anchors, int *__restrict__ next)
-{
-    // next[r] = the smallest producing rank above r (-1: none): a running minimum over the ranks taken from the top down,
-    // 32 consecutive ranks per thread, wave scans by shuffles, one barrier pair per 32 768 ranks (1 024 threads)
-    __shared__ int s_w[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = (int)*n_anchors;
-    constexpr int PER = 32;  // (round 6: 32 ranks a thread, whole aligned runs read and written as 16-byte vectors -- a trip costs its
-                             //  memory round trips and barriers whatever it carries: five trips for a frame's ~40 k anchors were 38 us)
-    int carry = INT_MAX;
-    const int NT = (int)blockDim.x, NWV = NT >> 6;  // (any block size up to 1 024; launched with 256 since round 6, see k_stag_scan_counts)
-    const int ntop = (n + PER - 1) / PER * PER;      // (the ranks n .. ntop - 1 do not exist: no flag, nothing written)
-    for (int top = ntop; top > 0; top -= NT * PER) {
-        const int lo = top - (tid + 1) * PER;        // this thread's ranks: lo + PER - 1 down to lo (lo is a multiple of PER)
-        const bool whole = lo >= 0 && lo + PER <= n;
-        int f[PER], loc = INT_MAX;                   // f[k]: rank lo + k if it produces, else INT_MAX
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < PER; k += 4) {
-                const int4 q = *reinterpret_cast<const int4 *>(prodflag + lo + k);
-                f[k] = q.x ? lo + k : INT_MAX;
-                f[k + 1] = q.y ? lo + k + 1 : INT_MAX;
-                f[k + 2] = q.z ? lo + k + 2 : INT_MAX;
-                f[k + 3] = q.w ? lo + k + 3 : INT_MAX;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PER; k++) {
-                const int r = lo + k;
-                f[k] = (r >= 0 && r < n && prodflag[r]) ? r : INT_MAX;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < PER; k++) loc = min(loc, f[k]);
-        int incl = loc;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int o = __shfl_up(incl, d, 64);
-            if (lane >= d) incl = min(incl, o);
-        }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        int wpre = INT_MAX, tot = INT_MAX;
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int t = k < NWV ? s_w[k] : INT_MAX;
-            if (k < wv) wpre = min(wpre, t);
-            tot = min(tot, t);
-        }
-        const int left = __shfl_up(incl, 1, 64);
-        int run = min(min(carry, wpre), lane > 0 ? left : INT_MAX);  // the smallest producing rank above this thread's ranks
-#pragma unroll
-        for (int k = PER - 1; k >= 0; k--) {  // from the top down: f[k] -> next[lo + k]
-            const int t = f[k];
-            f[k] = run == INT_MAX ? -1 : run;
-            run = min(run, t);
-        }
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < PER; k += 4) *reinterpret_cast<int4 *>(next + lo + k) = make_int4(f[k], f[k + 1], f[k + 2], f[k + 3]);
-        } else {
-#pragma unroll
-            for (int k = 0; k < PER; k++) {
-                const int r = lo + k;
-                if (r >= 0 && r < n) next[r] = f[k];
-            }
-        }
-        carry = min(carry, tot);
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(1024) void k_stag_next_above(const int *__restrict__ prodflag, const unsigned *__restrict__ n_anchors, int *__restrict__ next)
-{
-    k_stag_next_above_impl(prodflag, n_anchors, next);
-}
 struct k_stag_next_above_fn {
     static constexpr int kBounds = 1024;
-    __device__ __forceinline__ void operator()(const int *__restrict__ prodflag, const unsigned *__restrict__ n_anchors, int *__restrict__ next) const { k_stag_next_above_impl(prodflag, n_anchors, next); }
+    __device__ __forceinline__ void operator()(const int *__restrict__ prodflag, const unsigned *__restrict__ n_anchors, int *__restrict__ next) const
+    {
+        // next[r] = the smallest producing rank above r (-1: none): a running minimum over the ranks taken from the top down,
+        // 32 consecutive ranks per thread, wave scans by shuffles, one barrier pair per 32 768 ranks (1 024 threads)
+        __shared__ int s_w[16];
+        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = (int)*n_anchors;
+        constexpr int PER = 32;  // (round 6: 32 ranks a thread, whole aligned runs read and written as 16-byte vectors -- a trip costs its
+                                 //  memory round trips and barriers whatever it carries: five trips for a frame's ~40 k anchors were 38 us)
+        int carry = INT_MAX;
+        const int NT = (int)blockDim.x, NWV = NT >> 6;  // (any block size up to 1 024; launched with 256 since round 6, see k_stag_scan_counts)
+        const int ntop = (n + PER - 1) / PER * PER;      // (the ranks n .. ntop - 1 do not exist: no flag, nothing written)
+        for (int top = ntop; top > 0; top -= NT * PER) {
+            const int lo = top - (tid + 1) * PER;        // this thread's ranks: lo + PER - 1 down to lo (lo is a multiple of PER)
+            const bool whole = lo >= 0 && lo + PER <= n;
+            int f[PER], loc = INT_MAX;                   // f[k]: rank lo + k if it produces, else INT_MAX
+            if (whole) {
+#pragma unroll
+                for (int k = 0; k < PER; k += 4) {
+                    const int4 q = *reinterpret_cast<const int4 *>(prodflag + lo + k);
+                    f[k] = q.x ? lo + k : INT_MAX;
+                    f[k + 1] = q.y ? lo + k + 1 : INT_MAX;
+                    f[k + 2] = q.z ? lo + k + 2 : INT_MAX;
+                    f[k + 3] = q.w ? lo + k + 3 : INT_MAX;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < PER; k++) {
+                    const int r = lo + k;
+                    f[k] = (r >= 0 && r < n && prodflag[r]) ? r : INT_MAX;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < PER; k++) loc = min(loc, f[k]);
+            int incl = loc;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(incl, d, 64);
+                if (lane >= d) incl = min(incl, o);
+            }
+            if (lane == 63) s_w[wv] = incl;
+            __syncthreads();
+            int wpre = INT_MAX, tot = INT_MAX;
+#pragma unroll
+            for (int k = 0; k < 16; k++) {
+                const int t = k < NWV ? s_w[k] : INT_MAX;
+                if (k < wv) wpre = min(wpre, t);
+                tot = min(tot, t);
+            }
+            const int left = __shfl_up(incl, 1, 64);
+            int run = min(min(carry, wpre), lane > 0 ? left : INT_MAX);  // the smallest producing rank above this thread's ranks
+#pragma unroll
+            for (int k = PER - 1; k >= 0; k--) {  // from the top down: f[k] -> next[lo + k]
+                const int t = f[k];
+                f[k] = run == INT_MAX ? -1 : run;
+                run = min(run, t);
+            }
+            if (whole) {
+#pragma unroll
+                for (int k = 0; k < PER; k += 4) *reinterpret_cast<int4 *>(next + lo + k) = make_int4(f[k], f[k + 1], f[k + 2], f[k + 3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < PER; k++) {
+                    const int r = lo + k;
+                    if (r >= 0 && r < n) next[r] = f[k];
+                }
+            }
+            carry = min(carry, tot);
+            __syncthreads();
+        }
+    }
 };
 
-template <bool FM = false, int EX_CHAINS = 512, int EX_PIX = 1024, int NWV = 4>
+template <bool FM, int EX_CHAINS, int EX_PIX, int NWV>
 __device__ __forceinline__ void k_stag_route_extract_impl(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors,
                                                             const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors,
                                                             int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where,
@@ -1688,7 +1623,7 @@ __device__ __forceinline__ void k_stag_route_extract_impl(StagRoute G, StagArena
     // of them behind the stores just issued -- half of this kernel's time on a marker's component
     // (EX_CHAINS / EX_PIX are template arguments since round 6: 512 / 1 024 = 32 KB a wave, one workgroup per CU -- what a marker's
     //  component needs; a group of frames takes its SMALL components (< STAG_BIG_COMP pixels) through an instance of 128 / 256 = 8 KB a
-    //  wave, four workgroups per CU, in a launch of its own: cls as in k_stag_route_walk_impl.  Which instance a component meets
+    //  wave, four workgroups per CU, in a launch of its own: cls as in k_stag_route_walk_fn.  Which instance a component meets
     //  only decides where its chain tree lives while it is taken apart -- the arithmetic is the same.)
     // (NWV waves per workgroup, a component each: 4 for a frame on its own and for a group's small components; ONE for a group's big
     //  components -- a 4-wave workgroup of the 32 KB-a-wave instance needs a CU with 128 KB of LDS free, and beside the other groups'
@@ -1786,72 +1721,59 @@ __device__ __forceinline__ void k_stag_route_extract_impl(StagRoute G, StagArena
 #endif
     if (S.overflow && lane == 0) atomicOr(ovf, S.overflow);
 }
-__global__ __launch_bounds__(256) void k_stag_route_extract(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls)
-{
-    k_stag_route_extract_impl(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls);
-}
-struct k_stag_route_extract_fn {
-    static constexpr int kBounds = 256;
-    static constexpr bool kFrameMinor = true;
-    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls) const { k_stag_route_extract_impl<true>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls); }
+// one body, three footprints: the functors differ in the template constants (and the launch bound that follows from NWV) only
+template <bool FM, int EX_CHAINS, int EX_PIX, int NWV>
+struct stag_route_extract_any {
+    static constexpr int kBounds = 64 * NWV;
+    static constexpr bool kFrameMinor = FM;
+    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls) const
+    {
+        k_stag_route_extract_impl<FM, EX_CHAINS, EX_PIX, NWV>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls);
+    }
+};
+template <bool FM>
+struct k_stag_route_extract_fn : stag_route_extract_any<FM, 512, 1024, 4> {
 };
 // (a group's big components: one wave, 32 KB, per workgroup)
-__global__ __launch_bounds__(64) void k_stag_route_extract_big(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls)
-{
-    k_stag_route_extract_impl<false, 512, 1024, 1>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls);
-}
-struct k_stag_route_extract_big_fn {
-    static constexpr int kBounds = 64;
-    static constexpr bool kFrameMinor = true;
-    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls) const { k_stag_route_extract_impl<true, 512, 1024, 1>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls); }
+template <bool FM>
+struct k_stag_route_extract_big_fn : stag_route_extract_any<FM, 512, 1024, 1> {
 };
 // (the small-footprint instance: group mode only)
-__global__ __launch_bounds__(256) void k_stag_route_extract_small(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls)
-{
-    k_stag_route_extract_impl<false, 128, 256>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls);
-}
-struct k_stag_route_extract_small_fn {
-    static constexpr int kBounds = 256;
-    static constexpr bool kFrameMinor = true;
-    __device__ __forceinline__ void operator()(StagRoute G, StagArenas A, const StagComp *__restrict__ comps, const int *__restrict__ cursors, const int *__restrict__ order, const int *__restrict__ next, const unsigned *__restrict__ n_anchors, int *__restrict__ blk_pix, int *__restrict__ blk_segs, int2 *__restrict__ blk_where, int *__restrict__ ovf, int cls) const { k_stag_route_extract_impl<true, 128, 256>(G, A, comps, cursors, order, next, n_anchors, blk_pix, blk_segs, blk_where, ovf, cls); }
+template <bool FM>
+struct k_stag_route_extract_small_fn : stag_route_extract_any<FM, 128, 256, 4> {
 };
 
 // blk_pix / blk_segs hold exclusive prefix sums by now: copy every block to its place in the global order
-__device__ __forceinline__ void k_stag_route_gather_impl(int per_wave, StagArenas A, const StagComp *__restrict__ comps, const unsigned *__restrict__ n_anchors,
-                                                           const int *__restrict__ prodflag, const int *__restrict__ blk_pix,
-                                                           const int *__restrict__ blk_segs, const int2 *__restrict__ blk_where,
-                                                           int2 *__restrict__ outpix, int2 *__restrict__ segs, int capOut, int capSegs, int *__restrict__ ovf)
-{
-    // a LANE per anchor asks whether it produced (most did not: one wave per anchor was 7 500 workgroups a frame, nearly all of
-    // them one load and an exit), the wave then copies the blocks of the ones that did, one after the other
-    const int lane = threadIdx.x & 63;
-    const int n = (int)*n_anchors;
-    const int q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * per_wave;  // (per_wave: 64, or 1 = a wave per anchor)
-    if (q0 >= n) return;
-    const int qm = q0 + lane;
-    unsigned long long todo = __ballot(lane < per_wave && qm < n && prodflag[n - 1 - qm] != 0);
-    while (todo) {
-        const int q = q0 + __builtin_ctzll(todo);
-        todo &= todo - 1;
-        const int2 w = blk_where[q];
-        const StagComp C = comps[w.x];
-        const StagRec r = (A.recs + C.anch_base)[w.y];
-        const int po = blk_pix[q], so = blk_segs[q];
-        if (po + r.out_len > capOut || so + r.nsegs > capSegs) {
-            if (lane == 0) atomicOr(ovf, 64);
-            continue;
-        }
-        const int2 *src = A.out + C.out_base + r.out_off;
-        for (int i = lane; i < r.out_len; i += 64) outpix[po + i] = src[i];
-        const int2 *sg = A.segs + C.seg_base + r.seg_off;
-        for (int i = lane; i < r.nsegs; i += 64) segs[so + i] = make_int2(sg[i].x - r.out_off + po, sg[i].y);
-    }
-}
-__global__ __launch_bounds__(256) void k_stag_route_gather(int per_wave, StagArenas A, const StagComp *__restrict__ comps, const unsigned *__restrict__ n_anchors, const int *__restrict__ prodflag, const int *__restrict__ blk_pix, const int *__restrict__ blk_segs, const int2 *__restrict__ blk_where, int2 *__restrict__ outpix, int2 *__restrict__ segs, int capOut, int capSegs, int *__restrict__ ovf)
-{
-    k_stag_route_gather_impl(per_wave, A, comps, n_anchors, prodflag, blk_pix, blk_segs, blk_where, outpix, segs, capOut, capSegs, ovf);
-}
 struct k_stag_route_gather_fn {
     static constexpr int kBounds = 256;
-    __device__ __forceinline__ void operator()(int per_wave, StagArenas A, const StagComp *__restrict__ comps, const unsigned *__restrict__ n_anchors, const int *__restrict__ prodflag, const int *__restrict__ blk_pix, const int *__restrict__ blk_segs, const int2 *__restrict__ blk_where, int2 *__restrict__ outpix, int2 *__restrict__ segs, int capOut, int capSegs, int *__restrict__ ovf) const { k_stag_route_gather_impl(per_wave, A, comps, n_anchors, prodflag, blk_pix, blk_segs, blk_where, outpix, segs, capOut, capSegs, ovf); }
+    __device__ __forceinline__ void operator()(int per_wave, StagArenas A, const StagComp *__restrict__ comps, const unsigned *__restrict__ n_anchors,
+                                               const int *__restrict__ prodflag, const int *__restrict__ blk_pix,
+                                               const int *__restrict__ blk_segs, const int2 *__restrict__ blk_where,
+                                               int2 *__restrict__ outpix, int2 *__restrict__ segs, int capOut, int capSegs, int *__restrict__ ovf) const
+    {
+        // a LANE per anchor asks whether it produced (most did not: one wave per anchor was 7 500 workgroups a frame, nearly all of
+        // them one load and an exit), the wave then copies the blocks of the ones that did, one after the other
+        const int lane = threadIdx.x & 63;
+        const int n = (int)*n_anchors;
+        const int q0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * per_wave;  // (per_wave: 64, or 1 = a wave per anchor)
+        if (q0 >= n) return;
+        const int qm = q0 + lane;
+        unsigned long long todo = __ballot(lane < per_wave && qm < n && prodflag[n - 1 - qm] != 0);
+        while (todo) {
+            const int q = q0 + __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int2 w = blk_where[q];
+            const StagComp C = comps[w.x];
+            const StagRec r = (A.recs + C.anch_base)[w.y];
+            const int po = blk_pix[q], so = blk_segs[q];
+            if (po + r.out_len > capOut || so + r.nsegs > capSegs) {
+                if (lane == 0) atomicOr(ovf, 64);
+                continue;
+            }
+            const int2 *src = A.out + C.out_base + r.out_off;
+            for (int i = lane; i < r.out_len; i += 64) outpix[po + i] = src[i];
+            const int2 *sg = A.segs + C.seg_base + r.seg_off;
+            for (int i = lane; i < r.nsegs; i += 64) segs[so + i] = make_int2(sg[i].x - r.out_off + po, sg[i].y);
+        }
+    }
 };

@@ -23,7 +23,9 @@ def test_static_sheet_of_the_shipped_library():
     d = json.loads(out.stdout)
     k = d["kernels"]
     for name in ("k_threshold_stream<3,4,13,3,false>", "k_seed_walk", "k_walk_full<2>", "k_probe_lut<6,0>", "k_raw_to_gray", "k_probe_tables",
-                 "k_stag_route_walk[g]", "k_stag_route_extract_big[g]", "k_stag_ccl_flatten[g]", "k_stag_refine[g]"):
+                 "k_stag_route_walk[g]", "k_stag_route_extract_big[g]", "k_stag_ccl_flatten[g]", "k_stag_refine[g]",
+                 # the frame-at-a-time forms, k_stag_frame<k_stag_X_fn, ...> in the code object, under the names the kernels always had
+                 "k_stag_route_walk", "k_stag_ccl_flatten", "k_stag_pose<0>"):
         assert name in k, name
         assert 0 < k[name]["vgpr"] <= 512 and k[name]["launches"], name
     # the walkers' static LDS: 2 x 16 KB of windows + the 2 KB step table
@@ -37,6 +39,19 @@ def test_static_sheet_of_the_shipped_library():
                  "k_stag_route_walk[g]", "k_stag_ccl_flatten[g]", "k_stag_smooth_grad[g]"):
         assert k[name]["scratch"] == 0, name
     assert len(d["device_text_sha256"]) == 64
+
+
+def test_names_of_the_stag_entries():
+    short = _tool().short
+    # the group trampoline, as the committed profiles spell it and as it is spelled for a frame-minor functor (template <bool FM>)
+    assert short("void k_stag_batch<k_stag_ccl_flatten_fn>(StagTab<k_stag_ccl_flatten_fn>)") == "k_stag_ccl_flatten[g]"
+    assert short("void k_stag_batch<k_stag_route_walk_fn<true> >(StagTab<k_stag_route_walk_fn<true> >)") == "k_stag_route_walk[g]"
+    assert short("void k_stag_batch<k_stag_pose_fn<0> >(StagTab<k_stag_pose_fn<0> >)") == "k_stag_batch<k_stag_pose_fn<0>>"
+    # the generic frame-at-a-time entry: the kernel's old name, the functor's own template arguments kept
+    assert short("void k_stag_frame<k_stag_ccl_flatten_fn, int, int, int*, unsigned char const*>(int, int, int*, unsigned char const*)") == "k_stag_ccl_flatten"
+    assert short("void k_stag_frame<k_stag_route_walk_fn<false>, StagRoute, StagArenas, int>(StagRoute, StagArenas, int)") == "k_stag_route_walk"
+    assert short("void k_stag_frame<k_stag_pose_fn<0>, fid_stag_marker const*, int const*>(fid_stag_marker const*, int const*)") == "k_stag_pose<0>"
+    assert short("void k_stag_pose_cov<2>(fid_stag_marker const*, int const*)") == "k_stag_pose_cov<2>"
 
 
 def test_residency_arithmetic():

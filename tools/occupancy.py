@@ -50,12 +50,18 @@ LAUNCH_BLOCK = {"k_seed_walk": 128, "k_walk_full": 256, "k_seg_cycles": 64}
 
 
 def short(name: str) -> str:
-    """k_stag_batch<k_stag_route_walk_fn>(...) -> k_stag_route_walk[g]; template arguments kept, parameter list dropped."""
+    """k_stag_batch<k_stag_route_walk_fn>(...) -> k_stag_route_walk[g]; template arguments kept, parameter list dropped.
+    Since the STag kernels are their functors alone: k_stag_frame<k_stag_X_fn, A...> -> k_stag_X (the name the frame-at-a-time kernel
+    had), with the functor's own template arguments kept (k_stag_pose<0>) except the frame-minor switch, which the [g] already says
+    (k_stag_batch<k_stag_route_walk_fn<true>> -> k_stag_route_walk[g], k_stag_frame<k_stag_route_walk_fn<false>, ...> -> k_stag_route_walk)."""
     n = name.replace("void ", "").strip()
     n = re.sub(r"\(.*$", "", n)
-    m = re.match(r"k_stag_batch<(k_stag_\w+)_fn>", n)
+    m = re.match(r"k_stag_batch<(k_stag_\w+)_fn(<true>\s*)?>", n)
     if m:
         return m.group(1) + "[g]"
+    m = re.match(r"k_stag_frame<(k_stag_\w+)_fn(<[^<>]*>)?\s*[,>]", n)
+    if m:
+        return m.group(1) + re.sub(r"\s+", "", m.group(2) or "").replace("<false>", "")
     return re.sub(r"\s+", "", n)
 
 
