@@ -130,6 +130,7 @@ struct fid_ctx {
         int resolve_serial = 0;    // FID_RESOLVE_SERIAL=1: k_resolve's single-wave path even when the near triangle fits LDS (tests)
         int resolve_reg_max = 64;  // FID_RESOLVE_REG_MAX: components of up to so many candidates are resolved in registers (0: none; tests)
         int tail_grid = 4096;  // FID_TAIL_GRID: workgroups of k_identify (x 4: k_subpix) -- 1024 left 5 k candidates five rounds of an 80 us chain: +5 %
+        bool subpix_win7 = false;  // FID_SUBPIX_WIN7=1: windows up to 5 run k_subpix<7>, the instantiation they had before k_subpix<5> (tests, A/B)
         int filter_lds = 256;  // markers k_filter_markers keeps in LDS (FID_FILTER_LDS; more go through the global scratch)
     } tune;
     // ---- streams and the events between them
@@ -1082,10 +1083,17 @@ fid_status stage_tail(fid_ctx *c, const SubBatch &s, const Grids &G)
         hipLaunchKernelGGL(k_refine_contour, dim3(P.maxMarkers < 64 ? P.maxMarkers : 64, Fs), dim3(64), 0, st, (const fid_marker *)s.pre, s.markers,
                            (const int *)s.mksrc, (const DevCand *)s.filtered, (const uint32_t *)s.dense, (const uint32_t *)s.tab, (const uint32_t *)s.pool,
                            s.counts, P);
-    else if (P.subpixWin <= 7)  // (the LDS and tap registers of k_subpix follow its window bound)
-        hipLaunchKernelGGL(k_subpix<7>, dim3(G.subpix_blocks), dim3(64), 0, st, s.g, s.gfstride, s.pre, s.markers, s.counts, c->d_subpix_mask, P);
-    else
-        hipLaunchKernelGGL(k_subpix<SP_MAXWIN_MAX>, dim3(G.subpix_blocks), dim3(64), 0, st, s.g, s.gfstride, s.pre, s.markers, s.counts, c->d_subpix_mask, P);
+    else {  // (the LDS and tap registers of k_subpix follow its window bound: an instantiation per bound, the smallest that holds the window)
+#define SUBPIX_LAUNCH(BOUND)                                                                                                                        \
+    {                                                                                                                                               \
+        fid_launch_log("k_subpix<" #BOUND ">", 64, 0);                                                                                              \
+        hipLaunchKernelGGL(k_subpix<BOUND>, dim3(G.subpix_blocks), dim3(64), 0, st, s.g, s.gfstride, s.pre, s.markers, s.counts, c->d_subpix_mask, P); \
+    }
+        if (P.subpixWin <= 5 && !t.subpix_win7) SUBPIX_LAUNCH(5)
+        else if (P.subpixWin <= 7) SUBPIX_LAUNCH(7)
+        else SUBPIX_LAUNCH(15)
+#undef SUBPIX_LAUNCH
+    }
     mark(c, s, st, ST_SUBPIX + 1);
     if (c->pose_req.ahead(c))  // (the remembered marker pose; where fid_pose_last_cov_cam was the last to ask, its covariance behind it)
         pose_launch(c, st, s.ev[EV_POSE0], s.ev[EV_POSE1], s.markers, &s.counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, Fs, P.maxMarkers,
@@ -1427,6 +1435,7 @@ fid_ctx::Tuning read_tuning()
     num("FID_RESOLVE_SERIAL", &t.resolve_serial);
     if (num("FID_RESOLVE_REG_MAX", &v)) t.resolve_reg_max = v < 0 ? 0 : (v > 64 ? 64 : v);
     num("FID_TAIL_GRID", &t.tail_grid);
+    if (num("FID_SUBPIX_WIN7", &v)) t.subpix_win7 = v != 0;
     if (num("FID_FILTER_LDS", &v)) t.filter_lds = v > 0 ? v : 1;
     return t;
 }

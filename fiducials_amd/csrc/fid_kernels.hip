@@ -4147,6 +4147,8 @@ __device__ __forceinline__ int sat_round_int(double v)
     return (int)rint(v);
 }
 
+// (allocated 144 registers for 137 used.  __attribute__((amdgpu_waves_per_eu(4))) brings the allocation to 128, what three
+//  k_threshold_stream workgroups leave beside them, but at the price of 4 spilled registers and 20 B of scratch: not taken)
 __global__ __launch_bounds__(64) void k_identify(const uint8_t *__restrict__ gray, long long gfstride,
                                                   const DevCand *__restrict__ filtered, const unsigned *__restrict__ worklist,
                                                   const unsigned *__restrict__ nwork, const uint8_t *__restrict__ dict,
@@ -4681,7 +4683,8 @@ __global__ __launch_bounds__(64) void k_filter_markers(const DevCand *__restrict
 // The (2w+3)^2 patch and the per-tap products are computed in parallel; each of the five accumulators is
 // summed by its own lane in the reference's (i, j) order so the float corner equals the sequential result
 // bit for bit.  SP_MAXWIN (a template argument: the window bound the LDS arrays and per-lane tap registers are sized for) is
-// instantiated for 7 (cornerRefinementWinSize <= 7, the node's 5 among them) and for 15 (8..15, the oracle's bound).
+// instantiated for 5 (cornerRefinementWinSize <= 5, the node's 5 among them: 6.5 KB of LDS a workgroup, where the registers and
+// not the LDS bound the waves a CU holds), for 7 (6, 7: 11.9 KB) and for 15 (8..15, the oracle's bound).
 #define SP_MAXWIN_MAX 15
 template <int SP_MAXWIN>
 __global__ __launch_bounds__(64) void k_subpix(const uint8_t *__restrict__ gray, long long gfstride,
@@ -4708,8 +4711,10 @@ __global__ __launch_bounds__(64) void k_subpix(const uint8_t *__restrict__ gray,
     for (int t = ww * ww + lane; t < SP_NTP; t += 64)
 #pragma unroll
         for (int q = 0; q < 5; q++) prod[q][t] = -0.0;
+    // (slot-major, as pose_item_live has it: work index v is corner slot v / nframes of frame v % nframes, so that a batch's live
+    //  corners are the front of the index space -- one corner each on the first blocks, not four in a row on the blocks b % 256 < 80)
     for (int item = blockIdx.x; item < total; item += gridDim.x) {
-        int f = item / (P.maxMarkers * 4), r = item % (P.maxMarkers * 4);
+        const int r = item / P.nframes, f = item - r * P.nframes;
         int mk = r >> 2, cn = r & 3;
         if (mk >= counts[f].nmark) continue;
         const fid_marker *src = pre + (long long)f * P.maxMarkers + mk;
@@ -5270,17 +5275,18 @@ __device__ double fiducial_area_d(const float *c)
 }
 
 // What k_pose and k_pose_cov share, so that the covariance is of the items and the object points the pose was solved on: whether
-// the item of a lane group is a marker of its frame, and a lane's object point
-__device__ __forceinline__ bool pose_item_live(int item, int total, int per_frame, const int *__restrict__ nmark_per_frame, int nmark_stride_ints)
+// the item of a lane group is a marker of its frame, and a lane's object point.
+// The work is enumerated slot-major: work index v is slot v / nframes of frame v % nframes.  The live markers (the slots below a
+// frame's count) of a batch then fill the front of the index space -- every frame's slot 0, then every frame's slot 1 ... -- so
+// consecutive live waves go to consecutive XCDs and the dead ones are the contiguous rest.  In frame-major order with 64 slots a
+// frame, twenty markers a frame were the workgroups b % 8 < 3: three of the eight XCDs, two rounds at one wave a SIMD.  A call
+// of one frame enumerates its slots as before.  Returns the item in the [frame][per_frame] arrays, or -1 where there is no marker.
+__device__ __forceinline__ int pose_item_live(int v, int nframes, int per_frame, const int *__restrict__ nmark_per_frame, int nmark_stride_ints)
 {
-    bool live = item < total;
-    int f = 0, kk = 0;
-    if (live) {
-        f = item / per_frame;
-        kk = item - f * per_frame;
-        live = kk < nmark_per_frame[(long long)f * nmark_stride_ints];
-    }
-    return live;
+    if (v >= nframes * per_frame) return -1;
+    const int kk = v / nframes, f = v - kk * nframes;
+    if (kk >= nmark_per_frame[(long long)f * nmark_stride_ints]) return -1;
+    return f * per_frame + kk;
 }
 // half the marker length as the node's float object points have it (aruco_detect.cpp:151-161)
 __device__ __forceinline__ float pose_half_len(double len)
@@ -5302,8 +5308,8 @@ __global__ __launch_bounds__(64) void k_pose(const fid_marker *__restrict__ mark
     const int pi = g >> 1, sel = g & 1;  // corner, coordinate
     const int groups_per_block = blockDim.x >> 3;
     for (int item0 = blockIdx.x * groups_per_block; item0 < total; item0 += gridDim.x * groups_per_block) {
-        const int item = item0 + (threadIdx.x >> 3);
-        if (!pose_item_live(item, total, per_frame, nmark_per_frame, nmark_stride_ints)) continue;  // group-uniform
+        const int item = pose_item_live(item0 + (threadIdx.x >> 3), nframes, per_frame, nmark_per_frame, nmark_stride_ints);
+        if (item < 0) continue;  // group-uniform
         const fid_marker mk = markers[item];
         const double len = lens ? lens[item] : cam.fiducial_len;
         const double *K = cam.K, *kd = cam.D;
@@ -5423,8 +5429,8 @@ __global__ __launch_bounds__(64) void k_pose_cov(const fid_marker *__restrict__ 
     const int pi = g >> 1, sel = g & 1;
     const int groups_per_block = blockDim.x >> 3;
     for (int item0 = blockIdx.x * groups_per_block; item0 < total; item0 += gridDim.x * groups_per_block) {
-        const int item = item0 + (threadIdx.x >> 3);
-        if (!pose_item_live(item, total, per_frame, nmark_per_frame, nmark_stride_ints)) continue;  // group-uniform
+        const int item = pose_item_live(item0 + (threadIdx.x >> 3), nframes, per_frame, nmark_per_frame, nmark_stride_ints);
+        if (item < 0) continue;  // group-uniform
         const fid_pose_out po = poses[item];
         if constexpr (MODEL == FID_CAM_EQUIDISTANT) {
             if (po.image_error == -1.) {  // k_pose's record of a marker that cannot be posed
