@@ -3,6 +3,8 @@
 // HIP device fid_create fails with FID_E_NO_DEVICE.
 #include "fid_kernels.hip"
 
+#include "fid_devmem.h"
+
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,6 +75,13 @@ struct PoseRequest {
         ask = a;
         armed = at_hand = getenv("FID_NO_POSE_AHEAD") == nullptr;
     }
+};
+
+// A marker list handed in from the host and, behind its `cap` markers, its count (stage_markers): grows in steps of 256 markers
+struct MarkerStage {
+    DevBlock mem;
+    int cap = 0;
+    fid_marker *markers() const { return (fid_marker *)mem.p; }
 };
 
 struct fid_ctx {
@@ -176,8 +185,7 @@ struct fid_ctx {
     std::vector<uint8_t> dict_host;
     int dict_ms = 0, dict_maxc = 0, dict_n = 0;
     // device buffers
-    uint8_t *d_in = nullptr;
-    size_t d_in_bytes = 0;
+    DevArray<uint8_t> in;  // the frames of a call that brings them from the host (feed_and_enqueue)
     uint8_t *d_gray = nullptr;
     uint32_t *d_masks = nullptr;
     size_t masks_bytes = 0;
@@ -213,8 +221,11 @@ struct fid_ctx {
     uint8_t *d_dict = nullptr;
     float *d_subpix_mask = nullptr;
     uint8_t *d_probe_tables = nullptr;  // k_probe_lut's forward and backward step tables (4 KB, built once: k_probe_tables)
+    // fid_pose_cam's markers, poses and lengths: one block laid out for pose_cap markers
+    DevBlock pose_mem;
     double *d_lens = nullptr;
     fid_marker *d_pose_in = nullptr;
+    fid_pose_out *d_pose_out = nullptr;
     int *d_pose_n = nullptr;
     int pose_cap = 0;
     // what a call hands back -- global flags, per-frame counters, markers, poses -- lies in ONE device block and ONE pinned host
@@ -233,20 +244,20 @@ struct fid_ctx {
     PoseRequest pose_req{PoseRequest::MARKER}, map_req{PoseRequest::MAP}, rob_req{PoseRequest::MAP_ROBUST};
     // the pose covariance (nothing of it exists until the first _cov call): a fid_pose_cov beside every fid_pose_out of the context's
     // largest call, on the device only (a _cov call copies out what the frames' counts need)
-    fid_pose_cov *d_pcov = nullptr;
-    size_t pcov_cap = 0;
-    fid_pose_cov *d_pcov_in = nullptr;  // fid_pose_cov_cam's, beside d_pose_in
-    int pcov_in_cap = 0;
+    DevArray<fid_pose_cov> pcov;
+    DevArray<fid_pose_cov> pcov_in;  // fid_pose_cov_cam's, beside d_pose_in
     // the map of fiducials (fid_set_map; nothing of it exists until the first one is set): its ids ascending, per entry the four
     // object points in the map frame; a fid_map_pose_out per frame of a batch and one more for fid_map_pose, on the device and in
-    // pinned host memory; room for markers handed in from the host (stage_map_markers)
+    // pinned host memory; room for markers handed in from the host (stage_markers).  Each of the three groups below is one device
+    // block and one pinned block that exist together or not at all (alloc_bound): its pointers are null until both do
+    DevBlock map_mem, mcov_mem, rob_mem;
+    PinnedBlock map_hmem, mcov_hmem, rob_hmem;
     int *d_map_ids = nullptr;
     double *d_map_obj = nullptr;
     int map_n = 0;
     fid_map_pose_out *d_mposes = nullptr, *h_mposes = nullptr;
-    fid_marker *d_map_in = nullptr;
-    int map_in_cap = 0;
-    // as d_pcov, for k_map_pose_cov: max_batch + 1 records like d_mposes, allocated by the first _cov call
+    MarkerStage map_in;
+    // as pcov, for k_map_pose_cov: max_batch + 1 records like d_mposes, allocated by the first _cov call
     fid_map_pose_cov *d_mcov = nullptr, *h_mcov = nullptr;
     // k_map_pose_robust (fid_map_pose_robust.hip): max_batch + 1 pose and robust records of its own, allocated by the first robust call
     fid_map_pose_out *d_rposes = nullptr, *h_rposes = nullptr;
@@ -310,6 +321,51 @@ fid_status dalloc(fid_ctx *c, T **p, size_t count)
     return FID_OK;
 }
 
+// A feature's device block and its pinned twin, both or neither: the layouts' pointers are written only when both blocks exist
+fid_status alloc_bound(fid_ctx *c, DevBlock &dev, const MemLayout &dl, PinnedBlock &host, const MemLayout &hl)
+{
+    hipError_t e = dev.reserve(dl.bytes());
+    if (e == hipSuccess) e = host.reserve(hl.bytes());
+    if (e != hipSuccess) {
+        dev.release();
+        host.release();
+    }
+    HIPCHK(c, e);
+    dl.bind(dev.p);
+    hl.bind(host.p);
+    return FID_OK;
+}
+
+// n markers and their count from the host to d_markers and d_n, on the context's stream
+fid_status upload_markers(fid_ctx *c, fid_marker *d_markers, int *d_n, const fid_marker *markers, int32_t n)
+{
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(d_markers, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // (n is a stack temporary)
+    return FID_OK;
+}
+
+// a marker list from the host in `s`, its count behind it at *d_n (the map _cam entry points, fid_charuco_interpolate_cam)
+fid_status stage_markers(fid_ctx *c, MarkerStage &s, const fid_marker *markers, int32_t n, int **d_n)
+{
+    if (n > s.cap || !s.mem.p) {
+        const int cap = (n + 256) / 256 * 256;
+        s.cap = 0;
+        HIPCHK(c, s.mem.reserve(sizeof(fid_marker) * (size_t)cap + sizeof(int)));
+        s.cap = cap;
+    }
+    *d_n = (int *)(s.markers() + s.cap);
+    return upload_markers(c, s.markers(), *d_n, markers, n);
+}
+
+// a gray image from the host's rows, packed (stride = width) into `img`, which grows with the largest image; on the context's stream
+fid_status stage_gray(fid_ctx *c, DevArray<uint8_t> &img, const uint8_t *src, int width, int height, int stride_bytes)
+{
+    HIPCHK(c, img.reserve((size_t)width * height));
+    HIPCHK(c, hipMemcpy2DAsync(img.data(), (size_t)width, src, (size_t)stride_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, c->stream));
+    return FID_OK;
+}
+
 // the refusals the entry points share: true, with the message set, when the call cannot go on
 bool refuse_in_flight(fid_ctx *c)
 {
@@ -330,36 +386,33 @@ bool refuse_room(fid_ctx *c, int cap_frames)
 
 int roundup(int v, int m) { return (v + m - 1) / m * m; }
 
+// [DevGlobal][nwork][DevCounts x F] (cleared at the start of a call) [fid_marker x F x MM][fid_pose_out x F x MM]: the block a call's
+// results lie in, on the device and in pinned host memory; *clear_end, *markers_end: where the cleared part and the markers end
+MemLayout results_layout(int F, int MM, DevGlobal **global, unsigned **nwork, DevCounts **counts, fid_marker **markers, fid_pose_out **poses,
+                         size_t *clear_end = nullptr, size_t *markers_end = nullptr)
+{
+    MemLayout l;
+    l.add(global, 1), l.add(nwork, fid_ctx::MAX_SUB), l.add(counts, (size_t)F);
+    if (clear_end) *clear_end = l.mark();
+    l.add(markers, (size_t)F * MM);
+    if (markers_end) *markers_end = l.mark();
+    l.add(poses, (size_t)F * MM);
+    return l;
+}
 size_t results_bytes(int F, int MM)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    return up(sizeof(DevGlobal)) + up(sizeof(unsigned) * fid_ctx::MAX_SUB) + up(sizeof(DevCounts) * (size_t)F) + up(sizeof(fid_marker) * (size_t)F * MM) +
-           up(sizeof(fid_pose_out) * (size_t)F * MM);
+    DevGlobal *g; unsigned *nw; DevCounts *cn; fid_marker *mk; fid_pose_out *po;
+    return results_layout(F, MM, &g, &nw, &cn, &mk, &po).bytes();
 }
-// [DevGlobal][nwork][DevCounts x F] (cleared at the start of a call) [fid_marker x F x MM][fid_pose_out x F x MM]
 void layout_results(fid_ctx *c, int F)
 {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const int MM = c->lim.max_markers_per_frame;
-    size_t off = 0;
-    c->d_global = (DevGlobal *)(c->d_res + off);
-    c->h_global = (DevGlobal *)(c->h_res + off);
-    off += up(sizeof(DevGlobal));
-    c->d_nwork = (unsigned *)(c->d_res + off);
-    off += up(sizeof(unsigned) * fid_ctx::MAX_SUB);
-    c->d_counts = (DevCounts *)(c->d_res + off);
-    c->h_counts = (DevCounts *)(c->h_res + off);
-    off += up(sizeof(DevCounts) * (size_t)F);
-    c->res_clear_bytes = off;
-    c->d_markers = (fid_marker *)(c->d_res + off);
-    c->h_markers = (fid_marker *)(c->h_res + off);
-    off += up(sizeof(fid_marker) * (size_t)F * MM);
-    c->res_markers_end = off;
-    c->res_poses_off = off;
-    c->d_poses = (fid_pose_out *)(c->d_res + off);
-    c->h_poses = (fid_pose_out *)(c->h_res + off);
-    off += up(sizeof(fid_pose_out) * (size_t)F * MM);
-    c->res_poses_end = off;
+    unsigned *h_nwork;  // (the work counters have no host twin)
+    const MemLayout d = results_layout(F, MM, &c->d_global, &c->d_nwork, &c->d_counts, &c->d_markers, &c->d_poses, &c->res_clear_bytes, &c->res_markers_end);
+    d.bind(c->d_res);
+    results_layout(F, MM, &c->h_global, &h_nwork, &c->h_counts, &c->h_markers, &c->h_poses).bind(c->h_res);
+    c->res_poses_off = c->res_markers_end;
+    c->res_poses_end = d.bytes();
 }
 
 template <int NW, bool SPLIT>
@@ -724,7 +777,7 @@ SubBatch sub_batch_view(fid_ctx *c, const SubPlan &plan, int sb, const uint8_t *
     s.ident = frames_from(c->d_ident, f0, MC), s.bits = frames_from(c->d_bits, f0, MC * msb * msb);
     s.pre = frames_from(c->d_pre, f0, MM), s.markers = frames_from(c->d_markers, f0, MM), s.filter_scratch = frames_from(c->d_filter_scratch, f0, MC);
     s.accsrc = frames_from(c->d_accsrc, f0, MC), s.mksrc = frames_from(c->d_mksrc, f0, MM);
-    s.poses = frames_from(c->d_poses, f0, MM), s.pcov = frames_from(c->d_pcov, f0, MM);
+    s.poses = frames_from(c->d_poses, f0, MM), s.pcov = frames_from(c->pcov.data(), f0, MM);
     return s;
 }
 
@@ -1659,10 +1712,9 @@ void fid_destroy(fid_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    void *dev[] = {c->d_in, c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
+    void *dev[] = {c->d_gray, c->d_masks, c->d_starts, c->d_surv1, c->d_surv, c->d_pool, c->d_segs, c->d_pend, c->d_seedq, c->d_seedhash, c->d_wres, c->d_cinfo, c->d_cbase, c->d_filter_scratch, c->d_accsrc, c->d_mksrc, c->d_dense, c->d_recs, c->d_contours, c->d_ckpts, c->d_cands, c->d_sorted, c->d_cmeta, c->d_filtered, c->d_near,
                    c->d_ident, c->d_bits, c->d_pre, c->d_res, c->d_worklist, c->d_dict,
-                   c->d_subpix_mask, c->d_probe_tables, c->d_lens, c->d_pose_in, c->d_pose_n,
-                   c->d_map_ids, c->d_map_obj, c->d_mposes, c->d_map_in, c->d_pcov, c->d_pcov_in, c->d_mcov, c->d_rposes, c->d_mrob};
+                   c->d_subpix_mask, c->d_probe_tables, c->d_pose_n};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     calib_free(c);
@@ -1670,9 +1722,7 @@ void fid_destroy(fid_ctx *c)
     charuco_free(c);
     calib_pts_free(c);
     diamond_free(c);
-    void *host[] = {c->h_res, c->h_mposes, c->h_mcov, c->h_rposes, c->h_mrob};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
+    if (c->h_res) (void)hipHostFree(c->h_res);
     for (hipEvent_t e : c->pose_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
@@ -1855,13 +1905,7 @@ static fid_status feed_and_enqueue_impl(fid_ctx *c, const uint8_t *imgs, int32_t
         }
     }
     size_t need = (size_t)frame_stride * (nframes - 1) + (size_t)stride * height;
-    if (need > c->d_in_bytes) {
-        if (c->d_in) (void)hipFree(c->d_in);
-        c->d_in = nullptr;
-        c->d_in_bytes = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_in, need));
-        c->d_in_bytes = need;
-    }
+    HIPCHK(c, c->in.reserve(need));
     // The frames go up in the pieces run_detect works in, one asynchronous copy per sub-batch on the copy stream with an event
     // behind it; a sub-batch's stream waits for its own event only, so the copy of sub-batch k + 1 runs under the kernels of
     // sub-batch k (pinned host memory -- a capture ring buffer -- copies at link speed; pageable memory is staged by the runtime
@@ -1884,20 +1928,20 @@ static fid_status feed_and_enqueue_impl(fid_ctx *c, const uint8_t *imgs, int32_t
     if (c->host_feed && c->wait_copy_ev) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->wait_copy_ev, 0));
     c->wait_copy_ev = nullptr;
     if (!c->host_feed) {
-        HIPCHK(c, hipMemcpyAsync(c->d_in, imgs, need, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->in.data(), imgs, need, hipMemcpyHostToDevice, c->stream));
     } else {
         // (the copy stream must not overtake the previous call's kernels that still read d_in: they were synchronised at its end)
         for (int sb = 0; sb < nsub; sb++) {
             const int f0 = plan.f0[sb], Fs = plan.f0[sb + 1] - f0;
             const size_t off = (size_t)frame_stride * f0;
             const size_t bytes = (size_t)frame_stride * (Fs - 1) + (size_t)stride * height;
-            HIPCHK(c, hipMemcpyAsync(c->d_in + off, imgs + off, bytes, hipMemcpyHostToDevice, c->copy_stream));
+            HIPCHK(c, hipMemcpyAsync(c->in.data() + off, imgs + off, bytes, hipMemcpyHostToDevice, c->copy_stream));
             HIPCHK(c, hipEventRecord(c->in_ready[sb], c->copy_stream));
         }
     }
     const bool fed = c->host_feed;
     c->from_host_call = true;  // (enqueue_detect plans the same sub-batches: no piece chain, FID_NO_FEED_OVERLAP or not)
-    const fid_status rc = enqueue_detect(c, c->d_in, nframes, width, height, stride, frame_stride, enc);
+    const fid_status rc = enqueue_detect(c, c->in.data(), nframes, width, height, stride, frame_stride, enc);
     c->host_feed = c->from_host_call = false;
     if (rc == FID_OK) {
         c->fed_from_host = fed;
@@ -1964,10 +2008,9 @@ fid_status fid_pose_last(fid_ctx *c, const double K[9], const double D[5], doubl
 static fid_status ensure_pose_cov(fid_ctx *c)
 {
     const size_t need = (size_t)c->lim.max_batch * (size_t)c->lim.max_markers_per_frame;
-    if (c->pcov_cap >= need) return FID_OK;
-    HIPCHK(c, hipMalloc((void **)&c->d_pcov, sizeof(fid_pose_cov) * need));
-    HIPCHK(c, hipMemsetAsync(c->d_pcov, 0, sizeof(fid_pose_cov) * need, c->stream));
-    c->pcov_cap = need;
+    if (c->pcov.cap() >= need) return FID_OK;
+    HIPCHK(c, c->pcov.reserve(need));
+    HIPCHK(c, hipMemsetAsync(c->pcov.data(), 0, sizeof(fid_pose_cov) * need, c->stream));
     return FID_OK;
 }
 
@@ -1984,7 +2027,7 @@ static fid_status pose_last_run(fid_ctx *c, const fid_camera *camera, double fid
     fid_status rc = with_cov ? ensure_pose_cov(c) : FID_OK;
     if (rc != FID_OK) return rc;
     if (!c->pose_req.answers(ask)) {  // (else the detect call already ran k_pose -- and k_pose_cov -- for this camera on these markers)
-        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, ask, c->d_poses, c->d_pcov);
+        rc = run_pose(c, c->d_markers, &c->d_counts[0].nmark, (int)(sizeof(DevCounts) / sizeof(int)), nullptr, F, MM, ask, c->d_poses, c->pcov.data());
         if (rc != FID_OK) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_poses, c->d_poses, sizeof(fid_pose_out) * (size_t)F * MM, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2004,7 +2047,7 @@ static fid_status pose_last_run(fid_ctx *c, const fid_camera *camera, double fid
     if (with_cov && nmax > 0) {
         // the first nmax records of every frame in one strided copy, straight into the caller's array (a frame with fewer markers
         // gets records beyond its count along: they are not part of the result)
-        HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(fid_pose_cov) * (size_t)cap_per_frame, c->d_pcov, sizeof(fid_pose_cov) * (size_t)MM,
+        HIPCHK(c, hipMemcpy2DAsync(cov, sizeof(fid_pose_cov) * (size_t)cap_per_frame, c->pcov.data(), sizeof(fid_pose_cov) * (size_t)MM,
                                    sizeof(fid_pose_cov) * (size_t)nmax, (size_t)F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -2041,17 +2084,15 @@ static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_m
     if (refuse_in_flight(c)) return FID_E_INVALID_ARG;  // (shares the context's stream and buffers with the batch in flight)
     HIPCHK(c, hipSetDevice(c->device));
     if (n > c->pose_cap) {
-        if (c->d_pose_in) (void)hipFree(c->d_pose_in);
-        if (c->d_lens) (void)hipFree(c->d_lens);
-        c->d_pose_in = nullptr;
-        c->d_lens = nullptr;
+        const int cap = roundup(n, 256);
+        MemLayout l;
+        l.add(&c->d_pose_in, cap), l.add(&c->d_pose_out, cap), l.add(&c->d_lens, cap);
         c->pose_cap = 0;
-        int cap = roundup(n, 256);
-        HIPCHK(c, hipMalloc((void **)&c->d_pose_in, sizeof(fid_marker) * cap + sizeof(fid_pose_out) * cap));
-        HIPCHK(c, hipMalloc((void **)&c->d_lens, sizeof(double) * cap));
+        HIPCHK(c, c->pose_mem.reserve(l.bytes()));
+        l.bind(c->pose_mem.p);
         c->pose_cap = cap;
     }
-    fid_pose_out *d_out = (fid_pose_out *)((char *)c->d_pose_in + sizeof(fid_marker) * c->pose_cap);
+    fid_pose_out *d_out = c->d_pose_out;
     HIPCHK(c, hipMemcpyAsync(c->d_pose_in, markers, sizeof(fid_marker) * n, hipMemcpyHostToDevice, c->stream));
     std::vector<double> lens(n);
     for (int i = 0; i < n; i++) lens[i] = len_per_marker ? len_per_marker[i] : fiducial_len;
@@ -2059,17 +2100,11 @@ static fid_status pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_m
     int nn = n;
     HIPCHK(c, hipMemcpyAsync(c->d_pose_n, &nn, sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // lens/nn are stack/heap temporaries
-    if (with_cov && n > c->pcov_in_cap) {
-        if (c->d_pcov_in) (void)hipFree(c->d_pcov_in);
-        c->d_pcov_in = nullptr;
-        c->pcov_in_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_pcov_in, sizeof(fid_pose_cov) * (size_t)c->pose_cap));
-        c->pcov_in_cap = c->pose_cap;
-    }
-    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, {*camera, fiducial_len, with_cov, sigma_px, {}}, d_out, c->d_pcov_in);
+    if (with_cov) HIPCHK(c, c->pcov_in.reserve((size_t)n, (size_t)c->pose_cap));
+    fid_status rc = run_pose(c, c->d_pose_in, c->d_pose_n, 0, c->d_lens, 1, n, {*camera, fiducial_len, with_cov, sigma_px, {}}, d_out, c->pcov_in.data());
     if (rc != FID_OK) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_pose_out) * n, hipMemcpyDeviceToHost, c->stream));
-    if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, c->d_pcov_in, sizeof(fid_pose_cov) * n, hipMemcpyDeviceToHost, c->stream));
+    if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, c->pcov_in.data(), sizeof(fid_pose_cov) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FID_OK;
 }

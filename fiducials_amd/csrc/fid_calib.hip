@@ -662,9 +662,8 @@ __global__ WALKER_WG_ATTR(64, 512) void k_calib_accept(const CalCfg *__restrict_
 // ------------------------------------------------------------------------------------------------ host
 struct CalibBufs {
     int cap_views = 0;
-    size_t cap_markers = 0;
-    fid_marker *d_markers = nullptr;
-    char *d_mem = nullptr;  // everything below, sized by cap_views
+    DevArray<fid_marker> markers;
+    DevBlock mem;  // everything below, sized by cap_views
     int *d_n = nullptr, *d_vinfo = nullptr;
     int2 *d_sel = nullptr;
     double *d_con = nullptr, *d_blk = nullptr, *d_sch = nullptr, *d_pose = nullptr, *d_cand = nullptr, *d_cost = nullptr, *d_ccost = nullptr, *d_dnpn = nullptr;
@@ -673,14 +672,11 @@ struct CalibBufs {
     CalState *d_state = nullptr;
     fid_calib_out *d_out = nullptr;
     fid_calib_view *d_vout = nullptr;
-    size_t zero_from = 0, zero_bytes = 0;  // blk .. dnpn: zeroed at every call (a view that is not used adds nothing)
+    size_t zero_from = 0, zero_bytes = 0;  // pose .. dnpn: zeroed at every call (a view that is not used adds nothing)
 };
 
 static void calib_free(fid_ctx *c)
 {
-    if (!c->calib) return;
-    if (c->calib->d_markers) (void)hipFree(c->calib->d_markers);
-    if (c->calib->d_mem) (void)hipFree(c->calib->d_mem);
     delete c->calib;
     c->calib = nullptr;
 }
@@ -690,49 +686,19 @@ static fid_status calib_ensure(fid_ctx *c, int n_views, size_t n_markers)
     if (!c->calib) c->calib = new (std::nothrow) CalibBufs();
     CalibBufs *b = c->calib;
     if (!b) return FID_E_OUT_OF_MEMORY;
-    if (n_markers > b->cap_markers) {
-        if (b->d_markers) (void)hipFree(b->d_markers);
-        b->d_markers = nullptr;
-        b->cap_markers = 0;
-        HIPCHK(c, hipMalloc((void **)&b->d_markers, sizeof(fid_marker) * n_markers));
-        b->cap_markers = n_markers;
-    }
+    HIPCHK(c, b->markers.reserve(n_markers));
     if (n_views > b->cap_views) {
-        if (b->d_mem) (void)hipFree(b->d_mem);
-        b->d_mem = nullptr;
         b->cap_views = 0;
         const size_t V = (size_t)n_views;
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += (bytes + 255) & ~(size_t)255;
-            return at;
-        };
-        const size_t o_cfg = take(sizeof(CalCfg)), o_state = take(sizeof(CalState)), o_out = take(sizeof(fid_calib_out)), o_n = take(sizeof(int) * V),
-                     o_vinfo = take(sizeof(int) * 4 * V), o_sel = take(sizeof(int2) * MP_MAX_USED * V), o_con = take(sizeof(double) * 6 * V),
-                     o_vpose = take(sizeof(fid_map_pose_out) * V), o_vout = take(sizeof(fid_calib_view) * V), o_pose = take(sizeof(double) * 6 * V),
-                     o_blk = take(sizeof(double) * CAL_TRI * V), o_sch = take(sizeof(double) * CAL_SCH * V), o_cand = take(sizeof(double) * 6 * V),
-                     o_cost = take(sizeof(double) * V), o_ccost = take(sizeof(double) * V), o_dnpn = take(sizeof(double) * 2 * V);
-        HIPCHK(c, hipMalloc((void **)&b->d_mem, off));
-        char *m = b->d_mem;
-        b->d_cfg = (CalCfg *)(m + o_cfg);
-        b->d_state = (CalState *)(m + o_state);
-        b->d_out = (fid_calib_out *)(m + o_out);
-        b->d_n = (int *)(m + o_n);
-        b->d_vinfo = (int *)(m + o_vinfo);
-        b->d_sel = (int2 *)(m + o_sel);
-        b->d_con = (double *)(m + o_con);
-        b->d_vpose = (fid_map_pose_out *)(m + o_vpose);
-        b->d_vout = (fid_calib_view *)(m + o_vout);
-        b->d_pose = (double *)(m + o_pose);
-        b->d_blk = (double *)(m + o_blk);
-        b->d_sch = (double *)(m + o_sch);
-        b->d_cand = (double *)(m + o_cand);
-        b->d_cost = (double *)(m + o_cost);
-        b->d_ccost = (double *)(m + o_ccost);
-        b->d_dnpn = (double *)(m + o_dnpn);
-        b->zero_from = o_pose;
-        b->zero_bytes = off - o_pose;
+        MemLayout l;
+        l.add(&b->d_cfg, 1), l.add(&b->d_state, 1), l.add(&b->d_out, 1), l.add(&b->d_n, V), l.add(&b->d_vinfo, 4 * V), l.add(&b->d_sel, MP_MAX_USED * V);
+        l.add(&b->d_con, 6 * V), l.add(&b->d_vpose, V), l.add(&b->d_vout, V);
+        b->zero_from = l.mark();
+        l.add(&b->d_pose, 6 * V), l.add(&b->d_blk, CAL_TRI * V), l.add(&b->d_sch, CAL_SCH * V), l.add(&b->d_cand, 6 * V), l.add(&b->d_cost, V);
+        l.add(&b->d_ccost, V), l.add(&b->d_dnpn, 2 * V);
+        b->zero_bytes = l.mark() - b->zero_from;
+        HIPCHK(c, b->mem.reserve(l.bytes()));
+        l.bind(b->mem.p);
         b->cap_views = n_views;
     }
     return FID_OK;
@@ -957,12 +923,12 @@ fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_
     if (rce != FID_OK) return rce;
     CalibBufs *b = c->calib;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(b->d_markers, markers, sizeof(fid_marker) * n_markers, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(b->markers.data(), markers, sizeof(fid_marker) * n_markers, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(b->d_n, n_per_view, sizeof(int) * (size_t)n_views, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(b->d_mem + b->zero_from, 0, b->zero_bytes, st));
+    HIPCHK(c, hipMemsetAsync(b->mem.p + b->zero_from, 0, b->zero_bytes, st));
     // ---- the views' used markers; with AUTO the focal constraints
     const double cx0 = (mask >> 2 & 1u) ? 0.5 * (image_w - 1) : start.K[2], cy0 = (mask >> 3 & 1u) ? 0.5 * (image_h - 1) : start.K[5];
-    hipLaunchKernelGGL(k_calib_start, dim3(n_views), dim3(64), 0, st, (const fid_marker *)b->d_markers, (const int *)b->d_n, cap_per_view,
+    hipLaunchKernelGGL(k_calib_start, dim3(n_views), dim3(64), 0, st, (const fid_marker *)b->markers.data(), (const int *)b->d_n, cap_per_view,
                        (const int *)c->d_map_ids, (const double *)c->d_map_obj, c->map_n, cfg.start_auto, cx0, cy0, b->d_sel, b->d_vinfo, b->d_con);
     HIPCHK(c, hipGetLastError());
     if (cfg.start_auto) {
@@ -971,7 +937,7 @@ fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_
     }
     if (cfg.fix_aspect) start.K[0] = cfg.aspect * start.K[4];
     // ---- the start poses: k_map_pose over the views under the start camera
-    map_pose_launch(c, st, b->d_markers, b->d_n, 1, cap_per_view, n_views, start, b->d_vpose);
+    map_pose_launch(c, st, b->markers.data(), b->d_n, 1, cap_per_view, n_views, start, b->d_vpose);
     HIPCHK(c, hipGetLastError());
     const int model = start.model;
     return calib_solve_views(
@@ -982,13 +948,13 @@ fid_status fid_calibrate_map(fid_ctx *c, const fid_marker *markers, const int32_
         },
         [&](int final) {
             POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_blocks<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
-                                                        (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
+                                                        (const CalState *)b->d_state, (const fid_marker *)b->markers.data(), (const int2 *)b->d_sel,
                                                         (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose, b->d_blk, b->d_sch,
                                                         b->d_cost, final));
         },
         [&] {
             POSE_CAM_DISPATCH(model, hipLaunchKernelGGL(k_calib_eval<CAM_MODEL>, dim3(n_views), dim3(64), 0, st, (const CalCfg *)b->d_cfg,
-                                                        (const CalState *)b->d_state, (const fid_marker *)b->d_markers, (const int2 *)b->d_sel,
+                                                        (const CalState *)b->d_state, (const fid_marker *)b->markers.data(), (const int2 *)b->d_sel,
                                                         (const int *)b->d_vinfo, (const double *)c->d_map_obj, (const double *)b->d_pose,
                                                         (const double *)b->d_blk, b->d_cand, b->d_ccost, b->d_dnpn));
         },

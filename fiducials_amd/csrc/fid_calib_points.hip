@@ -190,9 +190,8 @@ __global__ __launch_bounds__(64) void k_calib_eval_pts(const CalCfg *__restrict_
 // records, the count and the record of k_charuco_pose
 struct CalibPtsBufs {
     int cap_views = 0;
-    size_t cap_in = 0;
-    fid_charuco_corner *d_in = nullptr;
-    char *d_mem = nullptr;  // everything below, sized by cap_views
+    DevArray<fid_charuco_corner> in;
+    DevBlock mem;  // everything below, sized by cap_views
     CalPoint *d_pts = nullptr;
     fid_charuco_corner *d_used = nullptr;
     int *d_nposed = nullptr;
@@ -201,9 +200,6 @@ struct CalibPtsBufs {
 
 static void calib_pts_free(fid_ctx *c)
 {
-    if (!c->calib_pts) return;
-    if (c->calib_pts->d_in) (void)hipFree(c->calib_pts->d_in);
-    if (c->calib_pts->d_mem) (void)hipFree(c->calib_pts->d_mem);
     delete c->calib_pts;
     c->calib_pts = nullptr;
 }
@@ -213,31 +209,14 @@ static fid_status calib_pts_ensure(fid_ctx *c, int n_views, size_t n_in)
     if (!c->calib_pts) c->calib_pts = new (std::nothrow) CalibPtsBufs();
     CalibPtsBufs *p = c->calib_pts;
     if (!p) return FID_E_OUT_OF_MEMORY;
-    if (n_in > p->cap_in) {
-        if (p->d_in) (void)hipFree(p->d_in);
-        p->d_in = nullptr;
-        p->cap_in = 0;
-        HIPCHK(c, hipMalloc((void **)&p->d_in, sizeof(fid_charuco_corner) * n_in));
-        p->cap_in = n_in;
-    }
+    HIPCHK(c, p->in.reserve(n_in));
     if (n_views > p->cap_views) {
-        if (p->d_mem) (void)hipFree(p->d_mem);
-        p->d_mem = nullptr;
         p->cap_views = 0;
         const size_t V = (size_t)n_views;
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += (bytes + 255) & ~(size_t)255;
-            return at;
-        };
-        const size_t o_pts = take(sizeof(CalPoint) * CALP_STRIDE * V), o_used = take(sizeof(fid_charuco_corner) * CALP_STRIDE * V),
-                     o_nposed = take(sizeof(int) * V), o_vpose = take(sizeof(fid_charuco_pose_out) * V);
-        HIPCHK(c, hipMalloc((void **)&p->d_mem, off));
-        p->d_pts = (CalPoint *)(p->d_mem + o_pts);
-        p->d_used = (fid_charuco_corner *)(p->d_mem + o_used);
-        p->d_nposed = (int *)(p->d_mem + o_nposed);
-        p->d_vpose = (fid_charuco_pose_out *)(p->d_mem + o_vpose);
+        MemLayout l;
+        l.add(&p->d_pts, CALP_STRIDE * V), l.add(&p->d_used, CALP_STRIDE * V), l.add(&p->d_nposed, V), l.add(&p->d_vpose, V);
+        HIPCHK(c, p->mem.reserve(l.bytes()));
+        l.bind(p->mem.p);
         p->cap_views = n_views;
     }
     return FID_OK;
@@ -277,13 +256,13 @@ fid_status fid_calibrate_charuco(fid_ctx *c, const fid_charuco_corner *corners, 
     CalibBufs *b = c->calib;
     CalibPtsBufs *p = c->calib_pts;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(p->d_in, corners, sizeof(fid_charuco_corner) * n_in, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(p->in.data(), corners, sizeof(fid_charuco_corner) * n_in, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(b->d_n, n_per_view, sizeof(int) * (size_t)n_views, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(b->d_mem + b->zero_from, 0, b->zero_bytes, st));
+    HIPCHK(c, hipMemsetAsync(b->mem.p + b->zero_from, 0, b->zero_bytes, st));
     // ---- the views' used points; with AUTO the focal constraints
     const double cx0 = (mask >> 2 & 1u) ? 0.5 * (image_w - 1) : start.K[2], cy0 = (mask >> 3 & 1u) ? 0.5 * (image_h - 1) : start.K[5];
     const int row_len = B->board.squares_x - 1;
-    hipLaunchKernelGGL(k_calib_start_pts, dim3(n_views), dim3(64), 0, st, (const fid_charuco_corner *)p->d_in, (const int *)b->d_n, cap_per_view,
+    hipLaunchKernelGGL(k_calib_start_pts, dim3(n_views), dim3(64), 0, st, (const fid_charuco_corner *)p->in.data(), (const int *)b->d_n, cap_per_view,
                        (const double *)B->d_cobj, B->nc, row_len, min_points, cfg.start_auto, cx0, cy0, p->d_pts, p->d_used, p->d_nposed, b->d_vinfo, b->d_con);
     HIPCHK(c, hipGetLastError());
     if (cfg.start_auto) {

@@ -504,23 +504,36 @@ struct CharucoBufs {
     fid_charuco_corner *d_corners = nullptr;
     fid_map_pose_out *d_bposes = nullptr;
     fid_charuco_pose_out *d_cposes = nullptr;
-    uint8_t *d_img = nullptr;
-    size_t img_bytes = 0;
-    fid_marker *d_in = nullptr;  // n markers and, behind them, their count
-    int in_cap = 0;
+    DevBlock mem;  // everything above
+    DevArray<uint8_t> img;
+    MarkerStage in;
     std::vector<fid_charuco_corner> h_corners;
     std::vector<int> h_n;
 };
 
 static void charuco_free(fid_ctx *c)
 {
-    CharucoBufs *B = c->charuco;
-    if (!B) return;
-    void *dev[] = {B->d_ids, B->d_near, B->d_n, B->d_mobj, B->d_cobj, B->d_mask, B->d_corners, B->d_bposes, B->d_cposes, B->d_img, B->d_in};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    delete B;
+    delete c->charuco;
     c->charuco = nullptr;
+}
+
+// cornerSubPix's weight masks for the windows 1 .. CH_MAXWIN, as cornersubpix.cpp makes them (float expf): k_charuco_subpix's table
+static std::vector<float> charuco_subpix_masks()
+{
+    std::vector<float> mask((size_t)CH_MASK_STRIDE * CH_MAXWIN, 0.f);
+    for (int win = 1; win <= CH_MAXWIN; win++) {
+        const int ww = 2 * win + 1;
+        float *m = mask.data() + (size_t)(win - 1) * CH_MASK_STRIDE;
+        for (int i = 0; i < ww; i++) {
+            const float y = (float)(i - win) / win;
+            const float vy = expf(-y * y);
+            for (int j = 0; j < ww; j++) {
+                const float x = (float)(j - win) / win;
+                m[(size_t)i * ww + j] = (float)(vy * expf(-x * x));
+            }
+        }
+    }
+    return mask;
 }
 
 static bool refuse_no_board(fid_ctx *c)
@@ -617,34 +630,23 @@ fid_status fid_set_charuco_board(fid_ctx *c, const fid_charuco_board *board)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!c->charuco) {
+        // the first board of this context: the tables at their largest, the result slots, the masks -- published when all of it exists
         CharucoBufs *B = new (std::nothrow) CharucoBufs;
         if (!B) return FID_E_OUT_OF_MEMORY;
-        c->charuco = B;
         const size_t slots = (size_t)c->lim.max_batch + 1;
-        HIPCHK(c, hipMalloc((void **)&B->d_ids, sizeof(int) * CH_MAX_MARKERS));
-        HIPCHK(c, hipMalloc((void **)&B->d_mobj, sizeof(double) * 12 * CH_MAX_MARKERS));
-        HIPCHK(c, hipMalloc((void **)&B->d_near, sizeof(int) * 4 * CH_MAX_CORNERS));
-        HIPCHK(c, hipMalloc((void **)&B->d_cobj, sizeof(double) * 3 * CH_MAX_CORNERS));
-        HIPCHK(c, hipMalloc((void **)&B->d_mask, sizeof(float) * CH_MASK_STRIDE * CH_MAXWIN));
-        HIPCHK(c, hipMalloc((void **)&B->d_n, sizeof(int) * slots));
-        HIPCHK(c, hipMalloc((void **)&B->d_corners, sizeof(fid_charuco_corner) * CH_MAX_CORNERS * slots));
-        HIPCHK(c, hipMalloc((void **)&B->d_bposes, sizeof(fid_map_pose_out) * slots));
-        HIPCHK(c, hipMalloc((void **)&B->d_cposes, sizeof(fid_charuco_pose_out) * slots));
-        // cornerSubPix's weight masks for the windows 1 .. CH_MAXWIN, as cornersubpix.cpp makes them (float expf)
-        std::vector<float> mask((size_t)CH_MASK_STRIDE * CH_MAXWIN, 0.f);
-        for (int win = 1; win <= CH_MAXWIN; win++) {
-            const int ww = 2 * win + 1;
-            float *m = mask.data() + (size_t)(win - 1) * CH_MASK_STRIDE;
-            for (int i = 0; i < ww; i++) {
-                const float y = (float)(i - win) / win;
-                const float vy = expf(-y * y);
-                for (int j = 0; j < ww; j++) {
-                    const float x = (float)(j - win) / win;
-                    m[(size_t)i * ww + j] = (float)(vy * expf(-x * x));
-                }
-            }
+        MemLayout l;
+        l.add(&B->d_ids, CH_MAX_MARKERS), l.add(&B->d_mobj, 12 * CH_MAX_MARKERS), l.add(&B->d_near, 4 * CH_MAX_CORNERS), l.add(&B->d_cobj, 3 * CH_MAX_CORNERS);
+        l.add(&B->d_mask, CH_MASK_STRIDE * CH_MAXWIN), l.add(&B->d_n, slots), l.add(&B->d_corners, CH_MAX_CORNERS * slots), l.add(&B->d_bposes, slots);
+        l.add(&B->d_cposes, slots);
+        const std::vector<float> mask = charuco_subpix_masks();
+        hipError_t e = B->mem.reserve(l.bytes());
+        if (e == hipSuccess) {
+            l.bind(B->mem.p);
+            e = hipMemcpy(B->d_mask, mask.data(), mask.size() * sizeof(float), hipMemcpyHostToDevice);
         }
-        HIPCHK(c, hipMemcpy(B->d_mask, mask.data(), mask.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (e != hipSuccess) delete B;
+        HIPCHK(c, e);
+        c->charuco = B;
     }
     CharucoBufs *B = c->charuco;
     B->nm = B->nc = 0;
@@ -761,25 +763,6 @@ fid_status fid_charuco_last_cam(fid_ctx *c, const fid_camera *camera, int32_t mi
     return charuco_fetch(c, 0, c->last_frames, out, cap_per_frame, n_per_frame);
 }
 
-// n markers from the host in d_in, which grows in steps of 256 markers, their count behind them
-static fid_status charuco_stage_markers(fid_ctx *c, const fid_marker *markers, int32_t n, int **d_n)
-{
-    CharucoBufs *B = c->charuco;
-    if (n > B->in_cap || !B->d_in) {
-        if (B->d_in) (void)hipFree(B->d_in);
-        B->d_in = nullptr;
-        B->in_cap = 0;
-        const int cap = (n + 256) / 256 * 256;
-        HIPCHK(c, hipMalloc((void **)&B->d_in, sizeof(fid_marker) * (size_t)cap + sizeof(int)));
-        B->in_cap = cap;
-    }
-    *d_n = (int *)((char *)B->d_in + sizeof(fid_marker) * (size_t)B->in_cap);
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(B->d_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(*d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (n is a stack temporary)
-    return FID_OK;
-}
-
 fid_status fid_charuco_interpolate_cam(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, const uint8_t *img, int32_t width,
                                        int32_t height, int32_t stride_bytes, int32_t min_markers, fid_charuco_corner *out, int32_t cap, int32_t *n_out)
 {
@@ -792,20 +775,12 @@ fid_status fid_charuco_interpolate_cam(fid_ctx *c, const fid_camera *camera, con
     if (charuco_common_refusals(c, camera, false, min_markers)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     CharucoBufs *B = c->charuco;
-    const size_t need = (size_t)width * height;
-    if (need > B->img_bytes) {
-        if (B->d_img) (void)hipFree(B->d_img);
-        B->d_img = nullptr;
-        B->img_bytes = 0;
-        HIPCHK(c, hipMalloc((void **)&B->d_img, need));
-        B->img_bytes = need;
-    }
-    HIPCHK(c, hipMemcpy2DAsync(B->d_img, (size_t)width, img, (size_t)stride_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, c->stream));
     int *d_n = nullptr;
-    const fid_status rcs = charuco_stage_markers(c, markers, n, &d_n);
+    fid_status rcs = stage_gray(c, B->img, img, width, height, stride_bytes);
+    if (rcs == FID_OK) rcs = stage_markers(c, B->in, markers, n, &d_n);
     if (rcs != FID_OK) return rcs;
     const int slot = c->lim.max_batch;
-    const ChRun R = {B->d_in, d_n, 0, n > 0 ? n : 1, 1, B->d_img, 0, width, width, height, slot};
+    const ChRun R = {B->in.markers(), d_n, 0, n > 0 ? n : 1, 1, B->img.data(), 0, width, width, height, slot};
     const fid_status rc = charuco_enqueue(c, camera, min_markers, R);
     if (rc != FID_OK) return rc;
     return charuco_fetch(c, slot, 1, out, cap, n_out);

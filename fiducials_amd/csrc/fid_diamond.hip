@@ -262,9 +262,10 @@ struct DiamondBufs {
     DmHead *d_heads = nullptr;
     fid_charuco_corner *d_items = nullptr;
     float *d_mask = nullptr;
-    uint8_t *d_img = nullptr;
-    size_t img_bytes = 0;
-    fid_marker *d_in = nullptr;  // DM_MAX_MARKERS markers and, behind them, their count
+    fid_marker *d_in = nullptr;  // DM_MAX_MARKERS markers and their count
+    int *d_nin = nullptr;
+    DevBlock mem;  // everything above
+    DevArray<uint8_t> img;
     std::vector<DmHead> h_heads;
     std::vector<fid_charuco_corner> h_items;
     std::vector<int> h_n;
@@ -272,12 +273,7 @@ struct DiamondBufs {
 
 static void diamond_free(fid_ctx *c)
 {
-    DiamondBufs *B = c->diamond;
-    if (!B) return;
-    void *dev[] = {B->d_prop, B->d_n, B->d_heads, B->d_items, B->d_mask, B->d_img, B->d_in};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    delete B;
+    delete c->diamond;
     c->diamond = nullptr;
 }
 
@@ -312,29 +308,19 @@ static fid_status diamond_ensure(fid_ctx *c)
     if (c->diamond) return FID_OK;
     DiamondBufs *B = new (std::nothrow) DiamondBufs;
     if (!B) return FID_E_OUT_OF_MEMORY;
-    c->diamond = B;
     const size_t slots = (size_t)c->lim.max_batch + 1;
-    HIPCHK(c, hipMalloc((void **)&B->d_prop, sizeof(int) * DM_MAX_MARKERS * slots));
-    HIPCHK(c, hipMalloc((void **)&B->d_n, sizeof(int) * slots));
-    HIPCHK(c, hipMalloc((void **)&B->d_heads, sizeof(DmHead) * DM_MAX * slots));
-    HIPCHK(c, hipMalloc((void **)&B->d_items, sizeof(fid_charuco_corner) * DM_ITEMS * slots));
-    HIPCHK(c, hipMalloc((void **)&B->d_mask, sizeof(float) * CH_MASK_STRIDE * CH_MAXWIN));
-    HIPCHK(c, hipMalloc((void **)&B->d_in, sizeof(fid_marker) * DM_MAX_MARKERS + sizeof(int)));
-    // cornerSubPix's weight masks for the windows 1 .. CH_MAXWIN, as cornersubpix.cpp makes them (float expf): k_charuco_subpix's table
-    std::vector<float> mask((size_t)CH_MASK_STRIDE * CH_MAXWIN, 0.f);
-    for (int win = 1; win <= CH_MAXWIN; win++) {
-        const int ww = 2 * win + 1;
-        float *m = mask.data() + (size_t)(win - 1) * CH_MASK_STRIDE;
-        for (int i = 0; i < ww; i++) {
-            const float y = (float)(i - win) / win;
-            const float vy = expf(-y * y);
-            for (int j = 0; j < ww; j++) {
-                const float x = (float)(j - win) / win;
-                m[(size_t)i * ww + j] = (float)(vy * expf(-x * x));
-            }
-        }
+    MemLayout l;
+    l.add(&B->d_prop, DM_MAX_MARKERS * slots), l.add(&B->d_n, slots), l.add(&B->d_heads, DM_MAX * slots), l.add(&B->d_items, DM_ITEMS * slots);
+    l.add(&B->d_mask, CH_MASK_STRIDE * CH_MAXWIN), l.add(&B->d_in, DM_MAX_MARKERS), l.add(&B->d_nin, 1);
+    const std::vector<float> mask = charuco_subpix_masks();
+    hipError_t e = B->mem.reserve(l.bytes());
+    if (e == hipSuccess) {
+        l.bind(B->mem.p);
+        e = hipMemcpy(B->d_mask, mask.data(), mask.size() * sizeof(float), hipMemcpyHostToDevice);
     }
-    HIPCHK(c, hipMemcpy(B->d_mask, mask.data(), mask.size() * sizeof(float), hipMemcpyHostToDevice));
+    if (e != hipSuccess) delete B;
+    HIPCHK(c, e);
+    c->diamond = B;  // (published when all of it exists)
     return FID_OK;
 }
 
@@ -458,21 +444,11 @@ fid_status fid_diamonds_detect(fid_ctx *c, const fid_diamond_opts *opts, const f
     const fid_status rce = diamond_ensure(c);
     if (rce != FID_OK) return rce;
     DiamondBufs *B = c->diamond;
-    const size_t need = (size_t)width * height;
-    if (need > B->img_bytes) {
-        if (B->d_img) (void)hipFree(B->d_img);
-        B->d_img = nullptr;
-        B->img_bytes = 0;
-        HIPCHK(c, hipMalloc((void **)&B->d_img, need));
-        B->img_bytes = need;
-    }
-    HIPCHK(c, hipMemcpy2DAsync(B->d_img, (size_t)width, img, (size_t)stride_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, c->stream));
-    int *d_nin = (int *)((char *)B->d_in + sizeof(fid_marker) * DM_MAX_MARKERS);
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(B->d_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_nin, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (n is a stack temporary)
+    fid_status rcs = stage_gray(c, B->img, img, width, height, stride_bytes);
+    if (rcs == FID_OK) rcs = upload_markers(c, B->d_in, B->d_nin, markers, n);
+    if (rcs != FID_OK) return rcs;
     const int slot = c->lim.max_batch;
-    const ChRun R = {B->d_in, d_nin, 0, n > 0 ? n : 1, 1, B->d_img, 0, width, width, height, slot};
+    const ChRun R = {B->d_in, B->d_nin, 0, n > 0 ? n : 1, 1, B->img.data(), 0, width, width, height, slot};
     const fid_status rc = diamond_enqueue(c, *opts, R);
     if (rc != FID_OK) return rc;
     return diamond_fetch(c, slot, 1, out, cap, n_out);

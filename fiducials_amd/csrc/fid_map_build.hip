@@ -832,15 +832,10 @@ __global__ WALKER_WG_ATTR(64, 1024) void k_build_obs_err(PoseCam cam, const fid_
 }
 
 // ------------------------------------------------------------------------------------------------ host
-struct BuildBufs {
-    char *d_mem = nullptr;
-    size_t cap = 0;
-};
+struct BuildBufs : DevBlock {};
 
 static void build_free(fid_ctx *c)
 {
-    if (!c->build) return;
-    if (c->build->d_mem) (void)hipFree(c->build->d_mem);
     delete c->build;
     c->build = nullptr;
 }
@@ -1127,82 +1122,30 @@ struct BldRun {
         n_obs_max = 0;
         for (int v = 0; v < V; v++) n_obs_max += kept[(size_t)v].size();
         n_obs_max = std::max<size_t>(n_obs_max, 1);
-        const size_t nmax = 6 * (size_t)NS;
-        size_t off = 0;
-        auto take = [&](size_t bytes) {
-            const size_t at = off;
-            off += (bytes + 255) & ~(size_t)255;
-            return at;
-        };
+        const size_t nmax = 6 * (size_t)NS, S1 = (size_t)NS + 1, O = n_obs_max;
         VP = (size_t)V * pv;
-        const size_t o_cfg = take(sizeof(BldCfg)), o_state = take(sizeof(BldState)), o_out = take(sizeof(fid_build_out)), o_mk = take(sizeof(fid_marker) * VP),
-                     o_n = take(sizeof(int) * V), o_lens = take(sizeof(double) * VP), o_p1 = take(sizeof(fid_pose_out) * VP),
-                     o_mp = take(sizeof(fid_map_pose_out) * V), o_tid = take(sizeof(int) * (NS + 1)), o_tobj = take(sizeof(double) * 12 * (NS + 1)),
-                     o_voff = take(sizeof(int) * V), o_vcnt = take(sizeof(int) * V), o_omk = take(sizeof(int) * n_obs_max),
-                     o_oslot = take(sizeof(int) * n_obs_max), o_oview = take(sizeof(int) * n_obs_max), o_mobs = take(sizeof(int) * n_obs_max),
-                     o_moff = take(sizeof(int) * (NS + 1)), o_mfree = take(sizeof(int) * (NS + 1)), o_fslot = take(sizeof(int) * (NS + 1)),
-                     o_mpar = take(sizeof(double) * 6 * (NS + 1)), o_mcand = take(sizeof(double) * 6 * (NS + 1)), o_mrt = take(sizeof(double) * BLD_MR * (NS + 1)),
-                     o_crt = take(sizeof(double) * 12 * (NS + 1)), o_mout = take(sizeof(double) * 40 * (NS + 1)), o_vout = take(sizeof(fid_build_view) * V),
-                     o_vpose = take(sizeof(double) * 6 * V), o_vcand = take(sizeof(double) * 6 * V), o_vblk = take(sizeof(double) * BLD_VB * V),
-                     o_vcost = take(sizeof(double) * V), o_vccost = take(sizeof(double) * V), o_dnpn = take(sizeof(double) * 2 * V),
-                     o_oblk = take(sizeof(double) * BLD_OB * n_obs_max), o_ow = take(sizeof(double) * BLD_OW * n_obs_max),
-                     o_S = take(sizeof(double) * std::max<size_t>(nmax * nmax, 1)), o_g = take(sizeof(double) * (nmax + 1)), o_dx = take(sizeof(double) * (nmax + 1)),
-                     o_dg = take(sizeof(double) * BLD_NB * BLD_NB * (nmax / BLD_NB + 1));
-        off_solve0 = o_tid;
-        off_solve1 = off;
-        size_t o_rob = 0, o_pspan = 0, o_poidx = 0, o_phview = 0, o_evoff = 0, o_evcnt = 0, o_eomk = 0, o_eom = 0, o_vrt = 0, o_hyp = 0, o_phalf = 0, o_pres = 0,
-               o_emrt = 0, o_evpose = 0, o_err = 0;
+        MemLayout l;
+        l.add(&d_cfg, 1), l.add(&d_state, 1), l.add(&d_out, 1), l.add(&d_mk, VP), l.add(&d_n, V), l.add(&d_lens, VP), l.add(&d_p1, VP), l.add(&d_mp, V);
+        off_solve0 = l.mark();
+        l.add(&d_tid, S1), l.add(&d_tobj, 12 * S1), l.add(&d_voff, V), l.add(&d_vcnt, V), l.add(&d_omk, O), l.add(&d_oslot, O), l.add(&d_oview, O);
+        l.add(&d_mobs, O), l.add(&d_moff, S1), l.add(&d_mfree, S1), l.add(&d_fslot, S1), l.add(&d_mpar, 6 * S1), l.add(&d_mcand, 6 * S1);
+        l.add(&d_mrt, BLD_MR * S1), l.add(&d_crt, 12 * S1), l.add(&d_mout, 40 * S1), l.add(&d_vout, V), l.add(&d_vpose, 6 * (size_t)V);
+        l.add(&d_vcand, 6 * (size_t)V), l.add(&d_vblk, BLD_VB * (size_t)V), l.add(&d_vcost, V), l.add(&d_vccost, V), l.add(&d_dnpn, 2 * (size_t)V);
+        l.add(&d_oblk, BLD_OB * O), l.add(&d_ow, BLD_OW * O), l.add(&d_S, std::max<size_t>(nmax * nmax, 1)), l.add(&d_g, nmax + 1), l.add(&d_dx, nmax + 1);
+        l.add(&d_Dg, BLD_NB * BLD_NB * (nmax / BLD_NB + 1));
+        off_solve1 = l.mark();
         if (robust) {
-            o_rob = take(sizeof(fid_map_robust_out) * V);
-            o_pspan = take(sizeof(int) * 4 * (NS + 1));
-            o_poidx = take(sizeof(int) * 2 * n_obs_max);
-            o_phview = take(sizeof(int) * n_obs_max);
-            o_evoff = take(sizeof(int) * V);
-            o_evcnt = take(sizeof(int) * V);
-            o_eomk = take(sizeof(int) * n_obs_max);
-            o_eom = take(sizeof(int) * n_obs_max);
-            o_vrt = take(sizeof(double) * 12 * V);
-            o_hyp = take(sizeof(double) * 12 * n_obs_max);
-            o_phalf = take(sizeof(double) * (NS + 1));
-            o_pres = take(sizeof(double) * 2 * (NS + 1));
-            o_emrt = take(sizeof(double) * 16 * (NI + 1));
-            o_evpose = take(sizeof(double) * 6 * V);
-            o_err = take(sizeof(double) * n_obs_max);
+            l.add(&d_rob, V), l.add(&d_pspan, 4 * S1), l.add(&d_poidx, 2 * O), l.add(&d_phview, O), l.add(&d_evoff, V), l.add(&d_evcnt, V), l.add(&d_eomk, O);
+            l.add(&d_eom, O), l.add(&d_vrt, 12 * (size_t)V), l.add(&d_hyp, 12 * O), l.add(&d_phalf, S1), l.add(&d_pres, 2 * S1);
+            l.add(&d_emrt, 16 * ((size_t)NI + 1)), l.add(&d_evpose, 6 * (size_t)V), l.add(&d_err, O);
         }
+        const size_t off = l.bytes();
         HIPCHK(c, hipSetDevice(c->device));
         if (!c->build) c->build = new (std::nothrow) BuildBufs();
-        BuildBufs *bb = c->build;
-        if (!bb) return FID_E_OUT_OF_MEMORY;
-        if (off > bb->cap) {
-            if (bb->d_mem) (void)hipFree(bb->d_mem);
-            bb->d_mem = nullptr;
-            bb->cap = 0;
-            HIPCHK(c, hipMalloc((void **)&bb->d_mem, off));
-            bb->cap = off;
-        }
-        M = bb->d_mem;
-        d_cfg = (BldCfg *)(M + o_cfg);
-        d_state = (BldState *)(M + o_state);
-        d_out = (fid_build_out *)(M + o_out);
-        d_mk = (fid_marker *)(M + o_mk);
-        d_n = (int *)(M + o_n), d_tid = (int *)(M + o_tid), d_voff = (int *)(M + o_voff), d_vcnt = (int *)(M + o_vcnt), d_omk = (int *)(M + o_omk);
-        d_oslot = (int *)(M + o_oslot), d_oview = (int *)(M + o_oview), d_mobs = (int *)(M + o_mobs), d_moff = (int *)(M + o_moff);
-        d_mfree = (int *)(M + o_mfree), d_fslot = (int *)(M + o_fslot);
-        d_lens = (double *)(M + o_lens), d_tobj = (double *)(M + o_tobj), d_mpar = (double *)(M + o_mpar), d_mcand = (double *)(M + o_mcand);
-        d_mrt = (double *)(M + o_mrt), d_crt = (double *)(M + o_crt), d_mout = (double *)(M + o_mout), d_vpose = (double *)(M + o_vpose);
-        d_vcand = (double *)(M + o_vcand), d_vblk = (double *)(M + o_vblk), d_vcost = (double *)(M + o_vcost), d_vccost = (double *)(M + o_vccost);
-        d_dnpn = (double *)(M + o_dnpn), d_oblk = (double *)(M + o_oblk), d_ow = (double *)(M + o_ow), d_S = (double *)(M + o_S), d_Dg = (double *)(M + o_dg);
-        d_g = (double *)(M + o_g), d_dx = (double *)(M + o_dx);
-        d_p1 = (fid_pose_out *)(M + o_p1);
-        d_mp = (fid_map_pose_out *)(M + o_mp);
-        d_vout = (fid_build_view *)(M + o_vout);
-        if (robust) {
-            d_rob = (fid_map_robust_out *)(M + o_rob);
-            d_pspan = (int *)(M + o_pspan), d_poidx = (int *)(M + o_poidx), d_phview = (int *)(M + o_phview), d_evoff = (int *)(M + o_evoff), d_evcnt = (int *)(M + o_evcnt);
-            d_eomk = (int *)(M + o_eomk), d_eom = (int *)(M + o_eom);
-            d_vrt = (double *)(M + o_vrt), d_hyp = (double *)(M + o_hyp), d_phalf = (double *)(M + o_phalf), d_pres = (double *)(M + o_pres);
-            d_emrt = (double *)(M + o_emrt), d_evpose = (double *)(M + o_evpose), d_err = (double *)(M + o_err);
-        }
+        if (!c->build) return FID_E_OUT_OF_MEMORY;
+        HIPCHK(c, c->build->reserve(off));
+        M = c->build->p;
+        l.bind(M);
         HIPCHK(c, hipMemsetAsync(M, 0, off, c->stream));
         return FID_OK;
     }

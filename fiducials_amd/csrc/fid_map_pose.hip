@@ -277,10 +277,11 @@ fid_status fid_set_map(fid_ctx *c, const fid_map_entry *entries, int32_t n)
     }
     if (!c->d_map_ids) {
         // the first map of this context: the tables at their largest, a result slot per frame of a batch (device and pinned host)
-        HIPCHK(c, hipMalloc((void **)&c->d_map_ids, sizeof(int) * FID_MAP_MAX_ENTRIES));
-        HIPCHK(c, hipMalloc((void **)&c->d_map_obj, sizeof(double) * 12 * FID_MAP_MAX_ENTRIES));
-        HIPCHK(c, hipMalloc((void **)&c->d_mposes, sizeof(fid_map_pose_out) * (size_t)(c->lim.max_batch + 1)));
-        HIPCHK(c, hipHostMalloc((void **)&c->h_mposes, sizeof(fid_map_pose_out) * (size_t)(c->lim.max_batch + 1), hipHostMallocDefault));
+        MemLayout dl, hl;
+        dl.add(&c->d_map_ids, FID_MAP_MAX_ENTRIES), dl.add(&c->d_map_obj, 12 * FID_MAP_MAX_ENTRIES), dl.add(&c->d_mposes, (size_t)(c->lim.max_batch + 1));
+        hl.add(&c->h_mposes, (size_t)(c->lim.max_batch + 1));
+        const fid_status rca = alloc_bound(c, c->map_mem, dl, c->map_hmem, hl);
+        if (rca != FID_OK) return rca;
     }
     std::vector<int> ids((size_t)n);
     std::vector<double> obj((size_t)n * 12);
@@ -308,10 +309,11 @@ fid_status fid_map_pose_last(fid_ctx *c, const double K[9], const double D[5], f
 // max_batch + 1 fid_map_pose_cov beside d_mposes / h_mposes (the first _cov call allocates them)
 static fid_status ensure_map_cov(fid_ctx *c)
 {
-    if (c->d_mcov && c->h_mcov) return FID_OK;
-    if (!c->d_mcov) HIPCHK(c, hipMalloc((void **)&c->d_mcov, sizeof(fid_map_pose_cov) * (size_t)(c->lim.max_batch + 1)));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_mcov, sizeof(fid_map_pose_cov) * (size_t)(c->lim.max_batch + 1), hipHostMallocDefault));
-    return FID_OK;
+    if (c->d_mcov) return FID_OK;
+    MemLayout dl, hl;
+    dl.add(&c->d_mcov, (size_t)(c->lim.max_batch + 1));
+    hl.add(&c->h_mcov, (size_t)(c->lim.max_batch + 1));
+    return alloc_bound(c, c->mcov_mem, dl, c->mcov_hmem, hl);
 }
 
 // fid_map_pose_last_cam and fid_map_pose_last_cov_cam: the camera pose (with_cov: and its covariance) of every frame of the last call
@@ -361,24 +363,6 @@ fid_status fid_map_pose(fid_ctx *c, const double K[9], const double D[5], const 
     return fid_map_pose_cam(c, &cam, markers, n, out);
 }
 
-// a marker list from the host in d_map_in, which grows in steps of 256 markers, its count behind it at *d_n (both map _cam entry points)
-static fid_status stage_map_markers(fid_ctx *c, const fid_marker *markers, int32_t n, int **d_n)
-{
-    if (n > c->map_in_cap || !c->d_map_in) {
-        if (c->d_map_in) (void)hipFree(c->d_map_in);
-        c->d_map_in = nullptr;
-        c->map_in_cap = 0;
-        const int cap = (n + 256) / 256 * 256;
-        HIPCHK(c, hipMalloc((void **)&c->d_map_in, sizeof(fid_marker) * (size_t)cap + sizeof(int)));
-        c->map_in_cap = cap;
-    }
-    *d_n = (int *)((char *)c->d_map_in + sizeof(fid_marker) * (size_t)c->map_in_cap);
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d_map_in, markers, sizeof(fid_marker) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(*d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // (n is a stack temporary)
-    return FID_OK;
-}
-
 static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const fid_marker *markers, int32_t n, fid_map_pose_out *out, bool with_cov,
                                    double sigma_px, fid_map_pose_cov *cov)
 {
@@ -386,7 +370,7 @@ static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const f
     if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     int *d_n = nullptr;
-    const fid_status rcs = stage_map_markers(c, markers, n, &d_n);
+    const fid_status rcs = stage_markers(c, c->map_in, markers, n, &d_n);
     if (rcs != FID_OK) return rcs;
     fid_map_pose_out *d_out = c->d_mposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
     if (with_cov) {
@@ -394,7 +378,7 @@ static fid_status map_pose_cam_run(fid_ctx *c, const fid_camera *camera, const f
         if (rca != FID_OK) return rca;
     }
     fid_map_pose_cov *d_cov = with_cov ? c->d_mcov + c->lim.max_batch : nullptr;
-    map_pose_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, d_out, with_cov, sigma_px, d_cov);
+    map_pose_launch(c, c->stream, c->map_in.markers(), d_n, 0, n > 0 ? n : 1, 1, *camera, d_out, with_cov, sigma_px, d_cov);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
     if (with_cov) HIPCHK(c, hipMemcpyAsync(cov, d_cov, sizeof(fid_map_pose_cov), hipMemcpyDeviceToHost, c->stream));

@@ -333,12 +333,12 @@ static inline bool fid_robust_opts_usable(const fid_map_robust_opts *o)
 // what fid_map_pose_last* put there
 static fid_status ensure_map_robust(fid_ctx *c)
 {
+    if (c->d_mrob) return FID_OK;
     const size_t n = (size_t)(c->lim.max_batch + 1);
-    if (!c->d_rposes) HIPCHK(c, hipMalloc((void **)&c->d_rposes, sizeof(fid_map_pose_out) * n));
-    if (!c->d_mrob) HIPCHK(c, hipMalloc((void **)&c->d_mrob, sizeof(fid_map_robust_out) * n));
-    if (!c->h_rposes) HIPCHK(c, hipHostMalloc((void **)&c->h_rposes, sizeof(fid_map_pose_out) * n, hipHostMallocDefault));
-    if (!c->h_mrob) HIPCHK(c, hipHostMalloc((void **)&c->h_mrob, sizeof(fid_map_robust_out) * n, hipHostMallocDefault));
-    return FID_OK;
+    MemLayout dl, hl;
+    dl.add(&c->d_rposes, n), dl.add(&c->d_mrob, n);
+    hl.add(&c->h_rposes, n), hl.add(&c->h_mrob, n);
+    return alloc_bound(c, c->rob_mem, dl, c->rob_hmem, hl);
 }
 
 fid_status fid_map_pose_robust_last_cam(fid_ctx *c, const fid_camera *camera, const fid_map_robust_opts *opts, fid_map_pose_out *pose_out,
@@ -374,12 +374,12 @@ fid_status fid_map_pose_robust_cam(fid_ctx *c, const fid_camera *camera, const f
     if (refuse_in_flight(c) || refuse_no_map(c)) return FID_E_INVALID_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     int *d_n = nullptr;
-    fid_status rca = stage_map_markers(c, markers, n, &d_n);
+    fid_status rca = stage_markers(c, c->map_in, markers, n, &d_n);
     if (rca == FID_OK) rca = ensure_map_robust(c);
     if (rca != FID_OK) return rca;
     fid_map_pose_out *d_out = c->d_rposes + c->lim.max_batch;  // (the slot behind a batch's: the last call's results stay)
     fid_map_robust_out *d_rout = c->d_mrob + c->lim.max_batch;
-    map_pose_robust_launch(c, c->stream, c->d_map_in, d_n, 0, n > 0 ? n : 1, 1, *camera, *opts, d_out, d_rout);
+    map_pose_robust_launch(c, c->stream, c->map_in.markers(), d_n, 0, n > 0 ? n : 1, 1, *camera, *opts, d_out, d_rout);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(pose_out, d_out, sizeof(fid_map_pose_out), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(robust_out, d_rout, sizeof(fid_map_robust_out), hipMemcpyDeviceToHost, c->stream));

@@ -667,27 +667,13 @@ struct fid_stag_ctx {
 
 #define STAG_LAYOUT_TAGS (FID_STAG_MAX_BUNDLES * FID_STAG_MAX_TAGS_PER_BUNDLE)  // the most tags a layout can hold
 #define STAG_WORDS_RESERVE (1u << 20)  // bytes of the slab kept for the marker library (HD11, the largest: 22 309 words)
-struct StagSlab {
-    struct Item {
-        void **p;
-        size_t off;
-    };
-    std::vector<Item> items;
-    size_t bytes = 0;
-    bool take(void **p, size_t b)
-    {
-        items.push_back({p, bytes});
-        bytes += (b + 255) & ~(size_t)255;  // (hipMalloc's own alignment, which the kernels' 16-byte accesses rely on)
-        return true;
-    }
-    bool commit(char **base, size_t *total)
-    {
-        if (hipMalloc((void **)base, bytes) != hipSuccess) return false;
-        for (const Item &i : items) *i.p = *base + i.off;
-        *total = bytes;
-        return true;
-    }
-};
+// a buffer of `bytes` bytes in the slab's layout (the sizes below are in bytes, whatever the buffer's element type)
+template <class T>
+static bool slab_take(MemLayout &l, T **p, size_t bytes)
+{
+    l.add_bytes((void **)p, bytes);
+    return true;
+}
 
 extern "C" {
 
@@ -715,37 +701,37 @@ fid_status fid_stag_create(int libraryHD, int errorCorrection, int max_width, in
     // Every device buffer of the context is a piece of ONE slab, laid out in the order of the takes below: two contexts made for the
     // same image size have every buffer at the same OFFSET, so that frame f's pointer is frame 0's plus (slab_f - slab_0) -- which is
     // what lets a group's launch carry frame 0's arguments once and 32 bytes per further frame (fid_stag_batch.h).
-    StagSlab slab;
+    MemLayout slab;  // (every buffer on a multiple of 256 bytes: hipMalloc's own alignment, which the kernels' 16-byte accesses rely on)
     int caps_host[16] = {0};
-    ok = ok && slab.take((void **)&c->d_src, n) && slab.take((void **)&c->d_smooth, n) &&
-         slab.take((void **)&c->d_dir, n) && slab.take((void **)&c->d_edge, n) &&
-         slab.take((void **)&c->d_grad, n * 2) && slab.take((void **)&c->d_sorted, n * 4) &&
-         slab.take((void **)&c->d_rowhist, (size_t)max_height * STAG_BINS * 4) &&
-         slab.take((void **)&c->d_bandhist, (size_t)((max_height + STAG_BAND_ROWS - 1) / STAG_BAND_ROWS) * STAG_BINS * 4) &&
-         slab.take((void **)&c->d_tot, STAG_BINS * 4) && slab.take((void **)&c->d_bstart, STAG_BINS * 4) &&
-         slab.take((void **)&c->d_n, 4);
+    ok = ok && slab_take(slab, &c->d_src, n) && slab_take(slab, &c->d_smooth, n) &&
+         slab_take(slab, &c->d_dir, n) && slab_take(slab, &c->d_edge, n) &&
+         slab_take(slab, &c->d_grad, n * 2) && slab_take(slab, &c->d_sorted, n * 4) &&
+         slab_take(slab, &c->d_rowhist, (size_t)max_height * STAG_BINS * 4) &&
+         slab_take(slab, &c->d_bandhist, (size_t)((max_height + STAG_BAND_ROWS - 1) / STAG_BAND_ROWS) * STAG_BINS * 4) &&
+         slab_take(slab, &c->d_tot, STAG_BINS * 4) && slab_take(slab, &c->d_bstart, STAG_BINS * 4) &&
+         slab_take(slab, &c->d_n, 4);
     // routing: the reference sizes its scratch arrays for the worst case (width * height entries each, EDInternals.cpp:848-853)
-    ok = ok && slab.take((void **)&c->d_edgeimg, n) && slab.take((void **)&c->d_rpix, n * sizeof(int2)) &&
-         slab.take((void **)&c->d_outpix, n * sizeof(int2)) && slab.take((void **)&c->d_segs, (n / 8 + 16) * sizeof(int2)) &&
-         slab.take((void **)&c->d_rstack, n * sizeof(int4)) && slab.take((void **)&c->d_chains, 32767 * sizeof(StagChain)) &&
-         slab.take((void **)&c->d_chainnos, (size_t)(max_width + max_height) * 8 * sizeof(int)) &&
-         slab.take((void **)&c->d_rcount, 16);
+    ok = ok && slab_take(slab, &c->d_edgeimg, n) && slab_take(slab, &c->d_rpix, n * sizeof(int2)) &&
+         slab_take(slab, &c->d_outpix, n * sizeof(int2)) && slab_take(slab, &c->d_segs, (n / 8 + 16) * sizeof(int2)) &&
+         slab_take(slab, &c->d_rstack, n * sizeof(int4)) && slab_take(slab, &c->d_chains, 32767 * sizeof(StagChain)) &&
+         slab_take(slab, &c->d_chainnos, (size_t)(max_width + max_height) * 8 * sizeof(int)) &&
+         slab_take(slab, &c->d_rcount, 16);
     // component-parallel routing: labels, per-root counters, component table, arenas (sizes in entries; see k_stag_comp_alloc)
     c->max_comps = (int)(n / 8 + 64);
     c->cap_aslots = (int)(n / 2 + 64);
     c->max_roots = ((max_width + 1) / 2) * ((max_height + 1) / 2) + 64;  // (8-connected components of an image: no more than that)
-    ok = ok && slab.take((void **)&c->d_label, n * 4) && slab.take((void **)&c->d_csize, n * 4) &&
-         slab.take((void **)&c->d_canch, n * 4) && slab.take((void **)&c->d_cidmap, n * 4) && slab.take((void **)&c->d_cbox, n * sizeof(int4)) &&
-         slab.take((void **)&c->d_cursors, 64) && slab.take((void **)&c->d_caps, 64) &&
-         slab.take((void **)&c->d_corder, (size_t)c->max_comps * 4) && slab.take((void **)&c->d_roots, (size_t)c->max_roots * 4) &&
-         slab.take((void **)&c->d_tilefg, (size_t)((max_width + CCL_TW - 1) / CCL_TW) * ((max_height + CCL_TH - 1) / CCL_TH)) && slab.take((void **)&c->d_fill, (size_t)c->max_comps * 4) && slab.take((void **)&c->d_aslots, (size_t)c->cap_aslots * 4) &&
-         slab.take((void **)&c->d_prodflag, n * 4) && slab.take((void **)&c->d_next, n * 4) &&
-         slab.take((void **)&c->d_blkpix, n * 4) && slab.take((void **)&c->d_blksegs, n * 4) &&
-         slab.take((void **)&c->d_blkwhere, n * sizeof(int2)) && slab.take((void **)&c->d_apix, 3 * n * sizeof(int2)) &&
-         slab.take((void **)&c->d_aout, 3 * n * sizeof(int2)) && slab.take((void **)&c->d_asegs, (n / 2 + 64) * sizeof(int2)) &&
-         slab.take((void **)&c->d_astack, 2 * n * sizeof(int4)) && slab.take((void **)&c->d_achains, 2 * n * sizeof(StagChain)) &&
-         slab.take((void **)&c->d_comps, (size_t)c->max_comps * sizeof(StagComp)) &&
-         slab.take((void **)&c->d_recs, (size_t)c->cap_aslots * sizeof(StagRec));
+    ok = ok && slab_take(slab, &c->d_label, n * 4) && slab_take(slab, &c->d_csize, n * 4) &&
+         slab_take(slab, &c->d_canch, n * 4) && slab_take(slab, &c->d_cidmap, n * 4) && slab_take(slab, &c->d_cbox, n * sizeof(int4)) &&
+         slab_take(slab, &c->d_cursors, 64) && slab_take(slab, &c->d_caps, 64) &&
+         slab_take(slab, &c->d_corder, (size_t)c->max_comps * 4) && slab_take(slab, &c->d_roots, (size_t)c->max_roots * 4) &&
+         slab_take(slab, &c->d_tilefg, (size_t)((max_width + CCL_TW - 1) / CCL_TW) * ((max_height + CCL_TH - 1) / CCL_TH)) && slab_take(slab, &c->d_fill, (size_t)c->max_comps * 4) && slab_take(slab, &c->d_aslots, (size_t)c->cap_aslots * 4) &&
+         slab_take(slab, &c->d_prodflag, n * 4) && slab_take(slab, &c->d_next, n * 4) &&
+         slab_take(slab, &c->d_blkpix, n * 4) && slab_take(slab, &c->d_blksegs, n * 4) &&
+         slab_take(slab, &c->d_blkwhere, n * sizeof(int2)) && slab_take(slab, &c->d_apix, 3 * n * sizeof(int2)) &&
+         slab_take(slab, &c->d_aout, 3 * n * sizeof(int2)) && slab_take(slab, &c->d_asegs, (n / 2 + 64) * sizeof(int2)) &&
+         slab_take(slab, &c->d_astack, 2 * n * sizeof(int4)) && slab_take(slab, &c->d_achains, 2 * n * sizeof(StagChain)) &&
+         slab_take(slab, &c->d_comps, (size_t)c->max_comps * sizeof(StagComp)) &&
+         slab_take(slab, &c->d_recs, (size_t)c->cap_aslots * sizeof(StagRec));
     if (ok) {
         const int caps[16] = {c->max_comps, c->cap_aslots, (int)(3 * n), (int)(2 * n), (int)(2 * n), (int)(3 * n), (int)(n / 2 + 64), 0};
         memcpy(caps_host, caps, sizeof(caps));  // (uploaded below, when the slab exists)
@@ -770,35 +756,39 @@ fid_status fid_stag_create(int libraryHD, int errorCorrection, int max_width, in
                     StagTab<k_stag_route_walk_fn<true>>::kMax, StagTab<k_stag_route_extract_fn<true>>::kMax, StagTab<k_stag_quads_fn<true>>::kMax,
                     StagTab<k_stag_decode_fn>::kMax, StagTab<k_stag_smooth_grad_fn>::kMax);
     }
-    ok = ok && slab.take((void **)&c->d_smooth2, n) && slab.take((void **)&c->d_vgrad, n * 2) &&
-         slab.take((void **)&c->d_vhist, STAG_BINS * 4 * STAG_VHIST_SLICES) && slab.take((void **)&c->d_prob, STAG_BINS * 8) &&
-         slab.take((void **)&c->d_np, 4) && slab.take((void **)&c->d_vcounts, (n / 8 + 16) * 4) &&
-         slab.take((void **)&c->d_vtotal, 4) && slab.take((void **)&c->d_vstack, n * sizeof(int2)) &&
-         slab.take((void **)&c->d_vsegs, (n / 8 + 16) * sizeof(int2));
+    ok = ok && slab_take(slab, &c->d_smooth2, n) && slab_take(slab, &c->d_vgrad, n * 2) &&
+         slab_take(slab, &c->d_vhist, STAG_BINS * 4 * STAG_VHIST_SLICES) && slab_take(slab, &c->d_prob, STAG_BINS * 8) &&
+         slab_take(slab, &c->d_np, 4) && slab_take(slab, &c->d_vcounts, (n / 8 + 16) * 4) &&
+         slab_take(slab, &c->d_vtotal, 4) && slab_take(slab, &c->d_vstack, n * sizeof(int2)) &&
+         slab_take(slab, &c->d_vsegs, (n / 8 + 16) * sizeof(int2));
     c->prefcap = n + n / 8 + 64;
-    ok = ok && slab.take((void **)&c->d_prefix, c->prefcap * 5 * sizeof(long long)) &&
-         slab.take((void **)&c->d_lslots, (n / 9 + 16) * sizeof(fid_stag_line)) &&
-         slab.take((void **)&c->d_lines, (n / 9 + 16) * sizeof(fid_stag_line)) &&
-         slab.take((void **)&c->d_lcounts, (n / 8 + 16) * 4) && slab.take((void **)&c->d_ltotal, 4);
-    ok = ok && slab.take((void **)&c->d_atan_lut, 1025 * 8) &&
-         slab.take((void **)&c->d_kmin, (size_t)(4 * (max_width + max_height) + 16) * 4) &&
-         slab.take((void **)&c->d_lflags, (n / 9 + 16) * 4) && slab.take((void **)&c->d_vltotal, 4) &&
-         slab.take((void **)&c->d_vlines, (n / 9 + 16) * sizeof(fid_stag_line));
-    ok = ok && slab.take((void **)&c->d_lrange, (n / 8 + 16) * sizeof(int2)) &&
-         slab.take((void **)&c->d_corners, (n / 9 + 16) * sizeof(StagCorner)) &&
-         slab.take((void **)&c->d_order, (n / 9 + 16) * 4) && slab.take((void **)&c->d_qcounts, (n / 8 + 16) * 4) &&
-         slab.take((void **)&c->d_qtotal, 4) && slab.take((void **)&c->d_qslots, (n / 9 + 16) * sizeof(fid_stag_quad)) &&
-         slab.take((void **)&c->d_quads, (n / 9 + 16) * sizeof(fid_stag_quad));
-    ok = ok && slab.take((void **)&c->d_locs, 72 * 3 * 8) && slab.take((void **)&c->d_cand, (n / 9 + 16) * sizeof(fid_stag_marker)) &&
-         slab.take((void **)&c->d_markers, (n / 9 + 16) * sizeof(fid_stag_marker)) &&
-         slab.take((void **)&c->d_found, (n / 9 + 16) * 4) && slab.take((void **)&c->d_nmarkers, 4);
-    ok = ok && slab.take((void **)&c->d_specbad, 16) && slab.take((void **)&c->d_words_slab, STAG_WORDS_RESERVE);
-    ok = ok && slab.take((void **)&c->d_chosen, (n / 9 + 16) * 4) &&
-         slab.take((void **)&c->d_poses, (n / 9 + 16) * sizeof(fid_stag_pose_out));
-    ok = ok && slab.take((void **)&c->d_ltags, STAG_LAYOUT_TAGS * sizeof(fid_stag_tag)) && slab.take((void **)&c->d_lstart, (FID_STAG_MAX_BUNDLES + 1) * 4) &&
-         slab.take((void **)&c->d_bposes, FID_STAG_MAX_BUNDLES * sizeof(fid_stag_bundle_pose_out)) &&
-         slab.take((void **)&c->d_hmarkers, STAG_LAYOUT_TAGS * sizeof(fid_stag_marker)) && slab.take((void **)&c->d_hn, 4);
-    ok = ok && slab.commit(&c->d_slab, &c->slab_bytes);
+    ok = ok && slab_take(slab, &c->d_prefix, c->prefcap * 5 * sizeof(long long)) &&
+         slab_take(slab, &c->d_lslots, (n / 9 + 16) * sizeof(fid_stag_line)) &&
+         slab_take(slab, &c->d_lines, (n / 9 + 16) * sizeof(fid_stag_line)) &&
+         slab_take(slab, &c->d_lcounts, (n / 8 + 16) * 4) && slab_take(slab, &c->d_ltotal, 4);
+    ok = ok && slab_take(slab, &c->d_atan_lut, 1025 * 8) &&
+         slab_take(slab, &c->d_kmin, (size_t)(4 * (max_width + max_height) + 16) * 4) &&
+         slab_take(slab, &c->d_lflags, (n / 9 + 16) * 4) && slab_take(slab, &c->d_vltotal, 4) &&
+         slab_take(slab, &c->d_vlines, (n / 9 + 16) * sizeof(fid_stag_line));
+    ok = ok && slab_take(slab, &c->d_lrange, (n / 8 + 16) * sizeof(int2)) &&
+         slab_take(slab, &c->d_corners, (n / 9 + 16) * sizeof(StagCorner)) &&
+         slab_take(slab, &c->d_order, (n / 9 + 16) * 4) && slab_take(slab, &c->d_qcounts, (n / 8 + 16) * 4) &&
+         slab_take(slab, &c->d_qtotal, 4) && slab_take(slab, &c->d_qslots, (n / 9 + 16) * sizeof(fid_stag_quad)) &&
+         slab_take(slab, &c->d_quads, (n / 9 + 16) * sizeof(fid_stag_quad));
+    ok = ok && slab_take(slab, &c->d_locs, 72 * 3 * 8) && slab_take(slab, &c->d_cand, (n / 9 + 16) * sizeof(fid_stag_marker)) &&
+         slab_take(slab, &c->d_markers, (n / 9 + 16) * sizeof(fid_stag_marker)) &&
+         slab_take(slab, &c->d_found, (n / 9 + 16) * 4) && slab_take(slab, &c->d_nmarkers, 4);
+    ok = ok && slab_take(slab, &c->d_specbad, 16) && slab_take(slab, &c->d_words_slab, STAG_WORDS_RESERVE);
+    ok = ok && slab_take(slab, &c->d_chosen, (n / 9 + 16) * 4) &&
+         slab_take(slab, &c->d_poses, (n / 9 + 16) * sizeof(fid_stag_pose_out));
+    ok = ok && slab_take(slab, &c->d_ltags, STAG_LAYOUT_TAGS * sizeof(fid_stag_tag)) && slab_take(slab, &c->d_lstart, (FID_STAG_MAX_BUNDLES + 1) * 4) &&
+         slab_take(slab, &c->d_bposes, FID_STAG_MAX_BUNDLES * sizeof(fid_stag_bundle_pose_out)) &&
+         slab_take(slab, &c->d_hmarkers, STAG_LAYOUT_TAGS * sizeof(fid_stag_marker)) && slab_take(slab, &c->d_hn, 4);
+    ok = ok && hipMalloc((void **)&c->d_slab, slab.bytes()) == hipSuccess;
+    if (ok) {
+        slab.bind(c->d_slab);
+        c->slab_bytes = slab.bytes();
+    }
     ok = ok && hipMemcpy(c->d_caps, caps_host, sizeof(caps_host), hipMemcpyHostToDevice) == hipSuccess && hipMemset(c->d_specbad, 0, 16) == hipSuccess;
     ok = ok && hipHostMalloc((void **)&c->hp, sizeof(fid_stag_ctx::Pinned), hipHostMallocDefault) == hipSuccess &&
          hipHostMalloc((void **)&c->h_src, n, hipHostMallocDefault) == hipSuccess;
