@@ -64,6 +64,11 @@ class FidCamera(C.Structure):
     _fields_ = [("model", C.c_int32), ("n_dist", C.c_int32), ("K", C.c_double * 9), ("D", C.c_double * 12)]
 
 
+class FidRigCamera(C.Structure):
+    """fid_rig_camera: a camera of a rig -- the camera and the rig frame in the camera frame, X_cam = R X_rig + t."""
+    _fields_ = [("cam", FidCamera), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
 class FidMapRobustOpts(C.Structure):
     """fid_map_robust_opts: inlier_px (finite, > 0), min_markers (>= 1)."""
     _fields_ = [("inlier_px", C.c_double), ("min_markers", C.c_int32), ("reserved0", C.c_int32)]
@@ -188,6 +193,13 @@ CHARUCO_POSE_DTYPE = np.dtype([("n_corners", "<i4"), ("status", "<i4"), ("rvec",
 DIAMOND_MAX_PER_FRAME, DIAMOND_MAX_MARKERS = 64, 256  # FID_DIAMOND_MAX_PER_FRAME, FID_DIAMOND_MAX_MARKERS
 DIAMOND_DTYPE = np.dtype([("ids", "<i4", (4,)), ("index", "<i4", (4,)), ("corners", "<f4", (4, 2)), ("corners0", "<f4", (4, 2)),
                           ("win", "<i4", (4,))])  # fid_diamond
+# the camera rig (fid_abi.h: "one rig pose per time step")
+RIG_MAX_CAMERAS, RIG_MAX_USED = 16, 128  # FID_RIG_MAX_CAMERAS, FID_RIG_MAX_USED
+RIG_POSE_DTYPE = np.dtype([("n_markers", "<i4"), ("n_cameras", "<i4"), ("n_over", "<i4"), ("n_unposable", "<i4"), ("start_camera", "<i4"),
+                           ("n_per_camera", "<i4", (RIG_MAX_CAMERAS,)), ("reserved0", "<i4"), ("rvec", "<f8", (3,)), ("tvec", "<f8", (3,)), ("R", "<f8", (3, 3)),
+                           ("rig_R", "<f8", (3, 3)), ("rig_t", "<f8", (3,)), ("image_error", "<f8"), ("err_per_camera", "<f8", (RIG_MAX_CAMERAS,))],
+                          )  # fid_rig_pose_out: 22 int32, then doubles -- no padding
+assert RIG_POSE_DTYPE.itemsize == 440 and RIG_POSE_DTYPE.fields["rvec"][1] == 88
 TAP_MASKS, TAP_CANDIDATES, TAP_FILTERED, TAP_BITS, TAP_IDENT, TAP_PRESUBPIX, TAP_COUNTS, TAP_GRAY = range(8)
 
 # every symbol include/fid_abi.h declares
@@ -208,6 +220,7 @@ SYMBOLS = [
     "fid_set_charuco_board", "fid_charuco_last_cam", "fid_charuco_interpolate_cam", "fid_charuco_pose_last_cam", "fid_charuco_pose_cam",
     "fid_calibrate_charuco",
     "fid_default_diamond_opts", "fid_diamonds_last", "fid_diamonds_detect", "fid_diamond_pose_cam",
+    "fid_rig_camera_from_tf", "fid_set_rig", "fid_rig_steps_last", "fid_rig_pose_last", "fid_rig_pose",
     "fid_stag_pose_last_cov_cam", "fid_stag_bundle_pose_last_cov_cam", "fid_stag_bundle_pose_cov_cam",
     "fid_jpeg_probe", "fid_jpeg_create", "fid_jpeg_destroy", "fid_jpeg_decode", "fid_jpeg_device_ptr", "fid_jpeg_tap_bytes", "fid_jpeg_tap_read",
     "fid_jpeg_last_rounds", "fid_jpeg_last_error",
@@ -429,6 +442,12 @@ def load():
         L.fid_diamonds_last.argtypes = [vp, C.POINTER(FidDiamondOpts), vp, i32, vp]
         L.fid_diamonds_detect.argtypes = [vp, C.POINTER(FidDiamondOpts), vp, i32, vp, i32, i32, i32, vp, i32, C.POINTER(i32)]
         L.fid_diamond_pose_cam.argtypes = [vp, C.POINTER(FidCamera), vp, i32, C.c_double, vp]
+    if hasattr(L, "fid_set_rig"):  # (the camera rig; FID_LIB may name a build from before it)
+        L.fid_rig_camera_from_tf.argtypes = [vp, vp, C.POINTER(FidCamera), C.POINTER(FidRigCamera)]
+        L.fid_set_rig.argtypes = [vp, vp, i32]
+        L.fid_rig_steps_last.argtypes = [vp, C.POINTER(i32)]
+        L.fid_rig_pose_last.argtypes = [vp, vp, i32, C.c_double, vp]
+        L.fid_rig_pose.argtypes = [vp, vp, vp, vp, C.c_double, vp]
     L.fid_jpeg_probe.argtypes = [vp, i64, C.POINTER(FidJpegInfo)]
     L.fid_jpeg_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
     L.fid_jpeg_destroy.argtypes = [vp]

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import CAM_EQUIDISTANT, CAM_PLUMB_BOB, CAM_RATIONAL, FidCamera, FidError
+from ._lib import CAM_EQUIDISTANT, CAM_PLUMB_BOB, CAM_RATIONAL, FidCamera, FidError, FidRigCamera
 
 MODEL_NAMES = {CAM_PLUMB_BOB: "plumb_bob", CAM_RATIONAL: "rational_polynomial", CAM_EQUIDISTANT: "equidistant"}
 
@@ -80,6 +80,50 @@ def from_info(distortion_model: str, K, D) -> Camera:
     if rc != _lib.FID_OK:
         raise FidError(rc, L.fid_camera_last_error().decode())
     return Camera._from_struct(out)
+
+
+class RigCamera:
+    """A fid_rig_camera: a camera of a rig with the RIG frame in the CAMERA frame, X_cam = R X_rig + t (solvePnP's convention).
+    from_tf takes what a static transform says instead: the camera's pose in the rig frame."""
+
+    def __init__(self, camera: Camera, R, t):
+        if not isinstance(camera, Camera):
+            raise TypeError("RigCamera takes a fiducials_amd.camera.Camera")
+        self.c = FidRigCamera()
+        C.memmove(C.byref(self.c.cam), C.byref(camera.c), C.sizeof(FidCamera))
+        self.c.R[:] = [float(v) for v in np.asarray(R, dtype=np.float64).reshape(9)]
+        self.c.t[:] = [float(v) for v in np.asarray(t, dtype=np.float64).reshape(3)]
+
+    @classmethod
+    def from_tf(cls, xyz, quat, camera: Camera) -> "RigCamera":
+        """The camera at position xyz with orientation quat (x, y, z, w) in the rig frame -- a base_link -> camera_optical_frame
+        transform -- inverted (fid_rig_camera_from_tf).  Host code: no device is touched."""
+        L = _lib.load()
+        p = (C.c_double * 3)(*np.asarray(xyz, dtype=np.float64).reshape(3))
+        q = (C.c_double * 4)(*np.asarray(quat, dtype=np.float64).reshape(4))
+        self = cls.__new__(cls)
+        self.c = FidRigCamera()
+        rc = L.fid_rig_camera_from_tf(p, q, C.byref(camera.c), C.byref(self.c))
+        if rc != _lib.FID_OK:
+            raise FidError(rc, "fid_rig_camera_from_tf: xyz and quat must be finite and the quaternion not zero")
+        return self
+
+    @property
+    def camera(self) -> Camera:
+        c = FidCamera()
+        C.memmove(C.byref(c), C.byref(self.c.cam), C.sizeof(FidCamera))
+        return Camera._from_struct(c)
+
+    @property
+    def R(self) -> np.ndarray:
+        return np.array(self.c.R[:], dtype=np.float64).reshape(3, 3)
+
+    @property
+    def t(self) -> np.ndarray:
+        return np.array(self.c.t[:], dtype=np.float64)
+
+    def __repr__(self) -> str:
+        return f"RigCamera({self.camera!r}, R={self.R.tolist()}, t={self.t.tolist()})"
 
 
 def resolve(K, D, camera: Camera | None) -> Camera | None:

@@ -272,6 +272,8 @@ struct fid_ctx {
     struct CalibPtsBufs *calib_pts = nullptr;
     // ChArUco diamonds (fid_diamond.hip): proposals, result slots, staging; nothing until the first fid_diamonds_* call
     struct DiamondBufs *diamond = nullptr;
+    // the camera rig (fid_rig_pose.hip): its camera table and result slots; nothing until the first fid_set_rig
+    struct RigBufs *rig = nullptr;
     // last call
     int last_frames = 0, last_W = 0, last_H = 0, last_nsub = 1;
     const uint8_t *last_gray = nullptr;
@@ -302,6 +304,8 @@ static void charuco_free(fid_ctx *c);
 static void calib_pts_free(fid_ctx *c);
 // the diamonds' buffers (fid_diamond.hip, behind fid_calib_points.hip)
 static void diamond_free(fid_ctx *c);
+// the rig's buffers (fid_rig_pose.hip, behind fid_diamond.hip)
+static void rig_free(fid_ctx *c);
 
 namespace {
 
@@ -1722,6 +1726,7 @@ void fid_destroy(fid_ctx *c)
     charuco_free(c);
     calib_pts_free(c);
     diamond_free(c);
+    rig_free(c);
     if (c->h_res) (void)hipHostFree(c->h_res);
     for (hipEvent_t e : c->pose_ev)
         if (e) (void)hipEventDestroy(e);
@@ -2410,3 +2415,4 @@ int32_t fid_abi_version(void) { return FID_ABI_VERSION; }
 #include "fid_charuco.hip"
 #include "fid_calib_points.hip"
 #include "fid_diamond.hip"
+#include "fid_rig_pose.hip"

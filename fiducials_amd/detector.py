@@ -47,6 +47,7 @@ MAP_ROBUST_DTYPE = _lib.MAP_ROBUST_DTYPE  # fid_map_robust_out
 CHARUCO_CORNER_DTYPE = _lib.CHARUCO_CORNER_DTYPE  # fid_charuco_corner
 CHARUCO_POSE_DTYPE = _lib.CHARUCO_POSE_DTYPE  # fid_charuco_pose_out
 DIAMOND_DTYPE = _lib.DIAMOND_DTYPE  # fid_diamond
+RIG_POSE_DTYPE = _lib.RIG_POSE_DTYPE  # fid_rig_pose_out
 
 
 def map_robust_outlier_positions(rec) -> np.ndarray:
@@ -172,6 +173,7 @@ class ArucoDetector:
         self._out_np = np.frombuffer(self._out, dtype=_MARKER_DT)
         self._poses_np = np.frombuffer(self._poses, dtype=_POSE_DT)
         self._last_frames = 0
+        self._rig_cameras = 0  # cameras of the rig set_rig handed over (0: none)
 
     # -- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -486,6 +488,50 @@ class ArucoDetector:
         self._check(self._L.fid_map_pose_cov_cam(self._ctx, C.byref(cam.c), mk.ctypes.data if len(mk) else None, len(mk), out.ctypes.data,
                                                  float(sigma_px), cov.ctypes.data))
         return out[0], cov[0]
+
+    # -- the body that carries several cameras, among the fiducials of a map -------------------------
+    def set_rig(self, cameras) -> None:
+        """The rig (fid_set_rig): a sequence of camera.RigCamera, camera c of the rig taking frames c, c + C, c + 2 C, ... of a detect
+        call; None or an empty sequence clears it."""
+        cams = [] if cameras is None else list(cameras)
+        for rc in cams:
+            if not isinstance(rc, _camera.RigCamera):
+                raise TypeError("set_rig takes fiducials_amd.camera.RigCamera objects")
+        tab = (_lib.FidRigCamera * max(len(cams), 1))()
+        for i, rc in enumerate(cams):
+            C.memmove(C.byref(tab[i]), C.byref(rc.c), C.sizeof(_lib.FidRigCamera))
+        self._check(self._L.fid_set_rig(self._ctx, C.cast(tab, C.c_void_p) if cams else None, len(cams)))
+        self._rig_cameras = len(cams)
+
+    def rig_pose_last(self, sigma_px: float | None = None):
+        """One rig pose per time step of the last detect_* / collect call (fid_rig_pose_last): RIG_POSE_DTYPE records, frame f being
+        camera f % C of step f // C.  With sigma_px (0: the a-posteriori estimate) also MAP_POSE_COV_DTYPE records, cov_cam_pose being
+        the rig's covariance in the map frame: (records, covariances)."""
+        steps = max(self._last_frames // max(self._rig_cameras, 1), 1)
+        out = np.zeros(steps, RIG_POSE_DTYPE)
+        if sigma_px is None:
+            self._check(self._L.fid_rig_pose_last(self._ctx, out.ctypes.data, len(out), 0.0, None))
+            return out
+        cov = np.zeros(steps, MAP_POSE_COV_DTYPE)
+        self._check(self._L.fid_rig_pose_last(self._ctx, out.ctypes.data, len(out), float(sigma_px), cov.ctypes.data))
+        return out, cov
+
+    def rig_pose(self, corners_per_camera, ids_per_camera, sigma_px: float | None = None):
+        """The same kernel on one time step handed in from the host (fid_rig_pose): per camera of the rig, in its order, corners
+        (n_c, 4, 2) and ids (n_c,) in list order.  One RIG_POSE_DTYPE record; with sigma_px (record, MAP_POSE_COV_DTYPE record)."""
+        ids = [np.asarray(i, np.int32).reshape(-1) for i in ids_per_camera]
+        if len(ids) != len(corners_per_camera) or len(ids) != self._rig_cameras:
+            raise ValueError(f"rig_pose takes one marker list per camera of the rig ({self._rig_cameras})")
+        n = np.array([len(i) for i in ids], np.int32)
+        mk = np.zeros(int(n.sum()), _MARKER_DT)
+        if len(mk):
+            mk["id"] = np.concatenate(ids)
+            mk["corners"] = np.concatenate([np.asarray(c, np.float32).reshape(len(i), 8) for c, i in zip(corners_per_camera, ids)])
+        out = np.zeros(1, RIG_POSE_DTYPE)
+        cov = None if sigma_px is None else np.zeros(1, MAP_POSE_COV_DTYPE)
+        self._check(self._L.fid_rig_pose(self._ctx, mk.ctypes.data if len(mk) else None, n.ctypes.data, out.ctypes.data,
+                                         0.0 if sigma_px is None else float(sigma_px), None if cov is None else cov.ctypes.data))
+        return out[0] if cov is None else (out[0], cov[0])
 
     @staticmethod
     def _robust_opts(inlier_px, min_markers):

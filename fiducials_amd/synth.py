@@ -439,6 +439,22 @@ def make_aruco_board_frame(d: Dictionary, ids, placements, K, R, t, seed: int, w
     return ArucoBoardFrame(np.clip(np.rint(img), 0, 255).astype(np.uint8), ids, R, _rot_to_rvec(R), t, cm, ci)
 
 
+def make_rig_frames(d: Dictionary, ids, placements, K, extrinsics, R, t, seed: int, width: int = 640, height: int = 480,
+                    noise_sigma: float = 2.0, border_bits: int = 1) -> list[ArucoBoardFrame]:
+    """One board seen through every camera of a rig at ONE time step: make_aruco_board_frame once per camera.  extrinsics: per camera
+    (R_c, t_c), the rig frame in the camera frame (X_cam = R_c X_rig + t_c); R, t: the map frame in the RIG frame; K: every camera's
+    pinhole matrix.  Camera c is rendered with the pose (R_c R, R_c t + t_c) and the seed seed + c; the frames come in camera order, the
+    order of a time step's frames in a batch."""
+    R = np.asarray(R, float).reshape(3, 3)
+    t = np.asarray(t, float).reshape(3)
+    frames = []
+    for c, (Rc, tc) in enumerate(extrinsics):
+        Rc = np.asarray(Rc, float).reshape(3, 3)
+        frames.append(make_aruco_board_frame(d, ids, placements, K, Rc @ R, Rc @ t + np.asarray(tc, float).reshape(3), seed + c, width, height,
+                                             noise_sigma, border_bits))
+    return frames
+
+
 @dataclass
 class CharucoFrame:
     image: np.ndarray          # (H, W) uint8

@@ -1490,6 +1490,80 @@ fid_status fid_jpeg_enc_tap_read(fid_jpeg_enc_ctx *ctx, int32_t frame, void *dst
 fid_status fid_dict_load_file(const char *path, int32_t dicno, uint8_t *bytes, int64_t bytes_cap, fid_dict *out);
 const char *fid_dict_last_error(void); /* of the calling thread */
 
+/* ---- one rig pose per time step from all cameras of a multi-camera rig (additions to ABI 7: entry points and structs only).
+ * Several cameras rigidly attached to one body look at the same map; the pose wanted is the body's, solved over every corner every
+ * camera saw.  A context that never calls fid_set_rig allocates and launches what it always did.
+ *
+ * The rig.  fid_rig_camera is the RIG frame in the CAMERA frame, solvePnP's convention: X_cam = R X_rig + t.  fid_rig_camera_from_tf
+ * (host code) takes the camera's pose in the rig frame -- a static base_link -> camera_optical_frame transform: position xyz and the
+ * quaternion (x, y, z, w), normalised here -- and inverts it: R = R(q)^T, t = -R(q)^T xyz.  FID_E_INVALID_ARG: a NULL pointer, a value
+ * that is not finite, a zero quaternion.
+ * fid_set_rig copies the table to the device (D beyond n_dist zeroed); n = 0 clears it.  Refused, the rig unchanged, fid_last_error
+ * naming the bound: FID_E_UNSUPPORTED for n > FID_RIG_MAX_CAMERAS; FID_E_INVALID_ARG for a camera that is not usable (a model
+ * outside the enum, n_dist outside 0..12), an R with max |R^T R - I| > 1e-9 or det R < 0, a value of K, D, R or t that is not
+ * finite, a batch in flight.
+ *
+ * Frames.  With a rig of C cameras, frame f of a detect call belongs to camera f % C of time step f / C (the order in which a node
+ * that gathers one image per camera per tick fills a batch).  fid_rig_pose_last on a last call whose frame count is not a multiple
+ * of C: FID_E_INVALID_ARG.  A copy to the device that fails inside fid_set_rig (FID_E_HIP) leaves the context without a rig.
+ *
+ * Gather, per time step: the cameras in index order, within a camera the frame's marker list in list order.  Ids the map does not
+ * name are skipped.  An id that occurs more than once WITHIN ONE FRAME is left out of that frame (fid_map_pose's rule); the same id
+ * in two cameras counts as two observations.  Under FID_CAM_EQUIDISTANT a marker with a corner that cannot be undistorted (theta >=
+ * 89 degrees, or Newton has not converged) is left out and counted in n_unposable: it costs its marker, not the step.  The first
+ * FID_RIG_MAX_USED survivors are used, the rest are counted in n_over.
+ *
+ * Start.  The start camera is the camera whose used markers have the largest summed image area (shoelace over the four corners, the
+ * markers summed in order); of equals the lowest index.  fid_map_pose_cam's solve on that camera's points alone gives (R_s, t_s), the
+ * map in that camera; the rig start is R = R_c^T R_s, t = R_c^T (t_s - t_c), rvec = cv::Rodrigues(R).
+ *
+ * Joint solve.  CvLevMarq (20 accepted steps, FLT_EPSILON, the damping ladder) on the 2N pixel residuals of all used points: point p
+ * of camera c projects as proj_c(R_c (R(rvec) M_p + tvec) + t_c) under camera c's own model and coefficients; the Jacobian with
+ * respect to (rvec, tvec) is analytic.  Residual i sits on lane i % 64; sums are per-lane partial sums in residual order and one xor
+ * butterfly: the same bytes from run to run.  The joint solve always runs, also when one camera alone contributes.
+ *
+ * Covariance.  cov may be NULL (sigma_px is then not read).  Else fid_map_pose_cov's three matrices ("pose covariance" above) from
+ * the joint J^T J evaluated once more at the returned pose, N the points of all cameras; cov_cam_pose is the rig in the map; status
+ * as there (1: n_markers == 0). */
+#define FID_RIG_MAX_CAMERAS 16
+#define FID_RIG_MAX_USED 128 /* marker observations of one time step that enter the pose (512 points); the rest are counted in n_over */
+typedef struct fid_rig_camera {
+    fid_camera cam;
+    double R[9]; /* the rig frame in the camera frame, row-major ... */
+    double t[3]; /* ... X_cam = R X_rig + t */
+} fid_rig_camera;
+typedef struct fid_rig_pose_out {
+    int32_t n_markers;      /* marker observations used, over all cameras; 0 = no pose, everything else zero */
+    int32_t n_cameras;      /* cameras with at least one used marker */
+    int32_t n_over;
+    int32_t n_unposable;
+    int32_t start_camera;
+    int32_t n_per_camera[FID_RIG_MAX_CAMERAS];
+    int32_t reserved0;      /* 0 (the doubles start on a multiple of 8: every byte of a record is written, none is padding) */
+    double rvec[3];
+    double tvec[3];
+    double R[9];            /* the map in the rig frame */
+    double rig_R[9];        /* the rig in the map: R^T */
+    double rig_t[3];        /* -R^T t */
+    double image_error;     /* getReprojectionError's form over all used points: projections rounded to float, sum |d|^2 / N, px^2 */
+    double err_per_camera[FID_RIG_MAX_CAMERAS]; /* the same over that camera's points; 0 where n_per_camera is 0.
+                                                   A camera knocked out of its extrinsics shows here. */
+} fid_rig_pose_out;
+fid_status fid_rig_camera_from_tf(const double xyz[3], const double quat_xyzw[4], const fid_camera *cam, fid_rig_camera *out);
+fid_status fid_set_rig(fid_ctx *ctx, const fid_rig_camera *cams, int32_t n);
+/* the time steps of the last fid_detect* / fid_collect under the context's rig: its frame count / the rig's cameras, what
+ * fid_rig_pose_last fills.  FID_E_INVALID_ARG: no last call, no rig, a frame count that is no multiple of the rig's cameras. */
+fid_status fid_rig_steps_last(fid_ctx *ctx, int32_t *n_steps);
+/* every time step of the last fid_detect* / fid_collect from the markers where they lie on the device: one launch, one wave per time
+ * step; copies the records back and synchronises.  NOT a remembered request: the next detect call launches nothing for it.
+ * FID_E_INVALID_ARG: no map, no rig, no last call, a frame count that is no multiple of the rig's cameras, a batch in flight, cov with a
+ * sigma_px that is negative or not finite; FID_E_CAPACITY: cap_steps below the number of time steps.  cov: NULL or cap_steps records. */
+fid_status fid_rig_pose_last(fid_ctx *ctx, fid_rig_pose_out *out, int32_t cap_steps, double sigma_px, fid_map_pose_cov *cov);
+/* the same kernel on one time step handed in from host memory: the markers concatenated camera by camera, n_per_camera[c] of them for
+ * camera c of the rig (each >= 0).  The last detect call's results stay as they are. */
+fid_status fid_rig_pose(fid_ctx *ctx, const fid_marker *markers, const int32_t *n_per_camera, fid_rig_pose_out *out, double sigma_px,
+                        fid_map_pose_cov *cov);
+
 const char *fid_strerror(fid_status s);
 const char *fid_last_error(fid_ctx *ctx);
 int32_t fid_abi_version(void);
